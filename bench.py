@@ -1,10 +1,20 @@
 #!/usr/bin/env python3
 """Benchmark of the vertical-ionogram forward operator on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--workload config4|config3|config5]
+    python bench.py --gpus N --steps K --warmup W [--workload config4|config3|config5] [--full] [--dump-outputs DIR]
 
 A "step" is one pass of the hot path over one device-resident batch of synthetic profiles:
 one fused-kernel launch per GPU (plus, for N > 1, the gather of the result rows over RCCL).
+
+A plain run sets up, warms up, times the K steps and prints the line: its headline figure and what the
+timed steps themselves give (kernel time, roofline over it; roofline.traffic replayed from
+profiles/hbm_traffic.json).  `--full` adds everything else the benchmark measures (below): the live
+traffic measurement, the other BASELINE configurations, the single-profile, drop-in and host-buffer
+calls, the f-row legs, devices="all" and the CPU baselines; the --no-* options still drop parts of it.
+`--dump-outputs DIR` writes the virtual heights of the last timed step (what the caller of the path
+receives: rank 0's gathered rows for N > 1) as finite float64 arrays: DIR/reflects.npy (1 where the path
+returned a height, 0 where it returned NaN: no reflection) and DIR/vh.npy (the heights, 0 km where there
+is none); above 64 MB a fixed sample of rows.
 
 Workloads (DESIGN.md "Measurement"; always the rows rank r would own at N = 8, so N = 8 is the
 BASELINE configuration itself and smaller N are weak-scaling prefixes of it):
@@ -14,17 +24,17 @@ BASELINE configuration itself and smaller N are weak-scaling prefixes of it):
   config3            configs[2]: 10 000 profiles x 174 frequencies, O mode, n_points = 200 (per GPU);
   config5            per-GPU shard of configs[4]: 6 250 profiles x 512 frequencies, mixed O/X x
                      n_points in {200, 2000, 20000}, ONE work-list launch per GPU.
-The single-profile configs[1] (latency-bound: 174 pairs per launch) is timed too and reported under
-"single_profile".
+With --full, the single-profile configs[1] (latency-bound: 174 pairs per launch) is timed too and
+reported under "single_profile".
 
 Launch: `python bench.py --gpus N` starts its own N ranks (one process per GPU, torch.distributed.run
 on 127.0.0.1) when it is not already running under a launcher; under
 `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N` it uses the ranks it is given.
 Rank 0 prints ONE JSON line.  `value` counts every submitted (profile, frequency) pair; the
 reflecting fraction is reported beside it.  Inputs are resident in HBM before the timed region.
-`roofline.traffic` (HBM bytes per launch) of the default single-GPU workload is measured by two short child
-runs of this script under `rocprofv3 --pmc` before the timed run (measure_traffic_live; --no-traffic: replayed
-from profiles/hbm_traffic.json); `roofline.traffic_source` says which.
+With --full, `roofline.traffic` (HBM bytes per launch) of the default single-GPU workload is measured by two
+short child runs of this script under `rocprofv3 --pmc` before the timed run (measure_traffic_live; a plain run
+or --no-traffic: replayed from profiles/hbm_traffic.json); `roofline.traffic_source` says which.
 """
 
 from __future__ import annotations
@@ -71,6 +81,24 @@ def algorithmic_flops(vh, den, n_points_per_row, alt):
     reflecting = integrated_pairs(vh, alt).sum(axis=1).astype(np.float64)
     return float((FLOPS_PER_POINT * np.asarray(n_points_per_row, dtype=np.float64) * reflecting).sum()
                  + (FLOPS_PER_LEVEL * k * vh.shape[1]).sum())
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory, vh):
+    """--dump-outputs: `vh` (profiles x frequencies) as two finite float64 arrays of its shape: DIR/reflects.npy, 1 where
+    the path returned a height and 0 where it returned NaN (the frequency does not reflect), and DIR/vh.npy, the heights
+    with 0 km in place of NaN (no trace ends below the bottom of the grid, 80 km).  A result above 64 MB in all (config 4
+    gathered at N = 8: 410 MB) keeps a fixed sample of its rows - seed 0, in row order - so two runs write the same rows."""
+    os.makedirs(directory, exist_ok=True)
+    vh = np.asarray(vh, dtype=np.float64)
+    max_rows = (DUMP_LIMIT_BYTES - 8192) // (2 * 8 * max(1, vh.shape[1]))     # (8192: room for the two .npy headers)
+    if vh.shape[0] > max_rows:
+        vh = vh[np.sort(np.random.default_rng(0).choice(vh.shape[0], size=max_rows, replace=False))]
+    reflects = np.isfinite(vh)
+    np.save(os.path.join(directory, "reflects.npy"), reflects.astype(np.float64))
+    np.save(os.path.join(directory, "vh.npy"), np.where(reflects, vh, 0.0))
 
 
 # ------------------------------------------------------------------------------------------------
@@ -568,20 +596,30 @@ def main():
     ap.add_argument("--gather", default="root", choices=["root", "all"],
                     help="N > 1: result rows gathered on rank 0 alone (dist.gather: each peer's block over its own xGMI link, "
                          "SURVEY 8e) or on every rank (all_gather_into_tensor)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure, run everything else the benchmark measures: live HBM traffic, the "
+                         "extra legs, the single-profile / drop-in / host-buffer calls, devices='all' and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the virtual heights of the last timed step to DIR/vh.npy and where they exist to "
+                         "DIR/reflects.npy (finite float64; above 64 MB a fixed sample of rows)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-single-profile", action="store_true")
     ap.add_argument("--option", action="append", default=[], metavar="NAME=VALUE",
                     help="a context option of the library (prhf_ctx_set_option), e.g. shortx_kernel=0: A/B measurements")
     ap.add_argument("--no-legs", action="store_true",
-                    help="skip the extra driver-timed legs (config3, config5_shard, config4_full) of the default run")
+                    help="skip the extra driver-timed legs (config3, config5_shard, config4_full) of a --full run")
     ap.add_argument("--no-traffic", action="store_true",
-                    help="do not measure the HBM traffic of the default workload live (two short child runs under rocprofv3 "
-                         "--pmc before the timed run): roofline.traffic is then replayed from profiles/hbm_traffic.json")
+                    help="do not measure the HBM traffic of the default workload live in a --full run (two short child runs "
+                         "under rocprofv3 --pmc before the timed run): roofline.traffic is then replayed from "
+                         "profiles/hbm_traffic.json")
     ap.add_argument("--force-collective", action="store_true",
                     help="N = 1: initialise the process group anyway and push the result rows through the real "
                          "all_gather_into_tensor (RCCL with one rank) - the N > 1 code path on one GPU")
     ap.add_argument("--devices-all-child", type=int, default=0, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if not args.full:
+        # a plain run is run several times per change: it does what its headline figure needs and nothing else
+        args.no_cpu_baseline = args.no_single_profile = args.no_legs = args.no_traffic = True
 
     if args.devices_all_child:
         devices_all_child(args.devices_all_child)
@@ -716,9 +754,10 @@ def main():
 
     gather_events = []                       # (before, after) the gather of every step, on torch's current stream
     gather_dst = 0 if args.gather == "root" else None
+    gathered = None                          # N > 1: the rows rank 0 receives from the last step's gather
 
     def step():
-        nonlocal out
+        nonlocal out, gathered
         if local_segs is not None:
             out = library.vertical_forward_operator_mixed(t["freq"], t["den"], t["bmag"], t["bpsi"], t["alt"],
                                                           local_segs, math=math, sync=False)
@@ -729,9 +768,10 @@ def main():
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
             if local_segs is not None:
-                pdist.gather_mixed(out, global_segs, max(p1 for _, p1, _, _ in global_segs), force=True, dst=gather_dst)
+                gathered = pdist.gather_mixed(out, global_segs, max(p1 for _, p1, _, _ in global_segs), force=True,
+                                              dst=gather_dst)
             else:
-                pdist.gather_rows(out, p_total, force=True, dst=gather_dst)
+                gathered = pdist.gather_rows(out, p_total, force=True, dst=gather_dst)
             e1.record()
             gather_events.append((e0, e1))
 
@@ -769,6 +809,8 @@ def main():
 
     if rank == 0:
         vh = out.cpu().numpy()
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, gathered.cpu().numpy() if collective else vh)
         ms_step = 1e3 * elapsed / args.steps
         k_ms = float(np.mean(kernel_ms))
         abytes = algorithmic_bytes(p_gpu, alt.size, n_freq, grid_points)

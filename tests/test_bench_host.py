@@ -31,6 +31,30 @@ def test_algorithmic_flops():
     assert bench.algorithmic_flops(vh, den, [100, 100], alt) == 68 * 100 * 1 + 6 * (2 + 1) * 3
 
 
+def test_dump_outputs_writes_finite_float64_and_samples_rows_above_64_mb(tmp_path):
+    small = np.array([[101.0, np.nan, 202.5], [np.nan, 80.0 + 1e-14, 333.0]], dtype=np.float32)
+    bench.dump_outputs(str(tmp_path / "small"), small)
+    vh, refl = np.load(tmp_path / "small" / "vh.npy"), np.load(tmp_path / "small" / "reflects.npy")
+    assert vh.dtype == refl.dtype == np.float64 and vh.shape == refl.shape == small.shape
+    assert np.isfinite(vh).all() and np.isfinite(refl).all()
+    assert np.array_equal(refl, [[1.0, 0.0, 1.0], [0.0, 1.0, 1.0]])
+    assert np.array_equal(vh, np.where(np.isnan(small), 0.0, small.astype(np.float64)))
+    # config 4 gathered at N = 8 (100 000 x 256 float64): a fixed sample of whole rows, the same in every run
+    big = np.broadcast_to(np.arange(100000.0)[:, None], (100000, 256)).copy()
+    big[::7, ::3] = np.nan
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), big)
+    a, b = np.load(tmp_path / "a" / "vh.npy"), np.load(tmp_path / "b" / "vh.npy")
+    ra, rb = np.load(tmp_path / "a" / "reflects.npy"), np.load(tmp_path / "b" / "reflects.npy")
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in ("vh.npy", "reflects.npy")) <= 64 << 20
+    assert a.shape == ra.shape and a.shape[1] == 256 and a.shape[0] > 15000
+    assert np.array_equal(a, b) and np.array_equal(ra, rb) and np.isfinite(a).all()
+    rows = a[:, 1]                                                   # (column 1 is never NaN)
+    assert np.all(np.diff(rows) > 0) and np.array_equal(rows, np.round(rows))
+    want = big[rows.astype(np.int64)]
+    assert np.array_equal(ra, np.isfinite(want)) and np.array_equal(a, np.nan_to_num(want, nan=0.0))
+
+
 def test_config5_work_list_scales_with_world_size():
     from pyrayhf_amd import dist as pdist
     full = bench.config5_segments(8)

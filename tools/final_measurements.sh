@@ -6,9 +6,9 @@ TAG=${1:-r05}
 PART=${2:-all}
 OUT=gpurun_out/final_$TAG; mkdir -p $OUT
 if [ "$PART" = "bench" ] || [ "$PART" = "all" ]; then
-python bench.py > $OUT/bench_${TAG}_n1.json 2> $OUT/bench_n1.err; echo "bench rc=$?"
-python bench.py --workload config3 --steps 20 --no-single-profile > $OUT/bench_${TAG}_config3.json 2> $OUT/bench_c3.err; echo "config3 rc=$?"
-python bench.py --workload config5 --steps 10 --no-single-profile > $OUT/bench_${TAG}_config5.json 2> $OUT/bench_c5.err; echo "config5 rc=$?"
+python bench.py --full > $OUT/bench_${TAG}_n1.json 2> $OUT/bench_n1.err; echo "bench rc=$?"
+python bench.py --full --workload config3 --steps 20 --no-single-profile > $OUT/bench_${TAG}_config3.json 2> $OUT/bench_c3.err; echo "config3 rc=$?"
+python bench.py --full --workload config5 --steps 10 --no-single-profile > $OUT/bench_${TAG}_config5.json 2> $OUT/bench_c5.err; echo "config5 rc=$?"
 python bench.py --gpus 1 --force-collective --steps 5 --no-cpu-baseline --no-single-profile --no-legs > $OUT/bench_${TAG}_n1_rccl.json 2> $OUT/bench_rccl.err; echo "rccl rc=$?"
 PRHF_BENCH_BACKEND=gloo python bench.py --gpus 2 --steps 3 --no-cpu-baseline > $OUT/bench_${TAG}_n2_rehearsal.json 2> $OUT/bench_n2.err; echo "n2 rc=$?"
 # more ranks on the one GPU (the box admits six processes on the card and the launcher holds it open too - a six-rank

@@ -152,7 +152,7 @@ int prhf_ctx_set_option(prhf_ctx* ctx, const char* name, double value);
  *   first one wins (np.argmax, library.py:371: a density column padded with NaN is cut at the padding); a NaN in alt
  *   makes the profile's row NaN (:507), and so does a NaN in bmag below the peak in X mode (:389); in O mode, and for
  *   a NaN in bpsi, the grid points of the two segments next to that level drop out of the sum (:288).
- *   (prhf_regrid_f64 refuses a NaN in alt, or in bmag / bpsi below the peak: PRHF_EINVAL.)
+ *   (prhf_regrid_f64 refuses a NaN in alt, bmag or bpsi below the peak: PRHF_EINVAL.)
  * Limits: n_alt <= 65535, n_freq <= 2^20, n_points >= 1.  A profile's bottomside - the levels below its density
  * peak - is held in LDS when it has at most 1400 levels (for n_alt > 1400 a pre-pass finds the highest peak of the
  * launch: one synchronisation); taller bottomsides are staged in global memory (one slab per resident workgroup,
@@ -205,6 +205,11 @@ int prhf_find_vh_f64(prhf_ctx* ctx, const double* X, const double* Y, const doub
  * (n_freq, n_points) row-major: the reference's dict entries 'freq', 'den', 'bmag', 'bpsi', 'dist',
  * 'alt', 'crit_height' (float64) and 'ind' (int64).  IEEE arithmetic in the reference's order: the
  * outputs are bit-identical to NumPy's.  Synchronous; returns PRHF_ENEGDEN / PRHF_EPEAK0 on bad input.
+ * As in the reference only the levels below the density peak (np.argmax, the first NaN ranking highest) are used:
+ * at and above it only den is read, and a NaN in alt, bmag or bpsi there changes nothing; below it such a NaN is
+ * PRHF_EINVAL.  n_alt <= 65535.  Bottomside limit: the levels up to the peak are held in LDS, at most 1400 of them
+ * (the peak at level 1399 or lower); a column whose peak lies higher is PRHF_EINVAL.  For n_alt > 1400 the peak is
+ * found first (host scan; device buffers: one small kernel and one synchronisation).
  */
 int prhf_regrid_f64(prhf_ctx* ctx, const double* freq_hz, int64_t n_freq, const double* den, const double* bmag,
                     const double* bpsi, const double* alt, int64_t n_alt, const double* multiplier,

@@ -197,7 +197,7 @@ int status_to_code(unsigned bits) {
     if (bits & PRHF_STATUS_PEAK0)
         return fail(PRHF_EPEAK0, "density peak at index 0: no bottomside levels below the peak");
     if (bits & PRHF_STATUS_NANINPUT)
-        return fail(PRHF_EINVAL, "NaN in a profile (alt anywhere in the column, bmag or bpsi below the density peak)");
+        return fail(PRHF_EINVAL, "NaN in a profile (alt, bmag or bpsi below the density peak)");
     if (bits & PRHF_STATUS_NEGDEN) return fail(PRHF_ENEGDEN, "Density must be non-negative");
     if (bits & PRHF_STATUS_BADGROUP) return fail(PRHF_EINVAL, "ray_group outside [0, n_groups)");
     if (bits & PRHF_STATUS_BADINDEX) return fail(PRHF_EINVAL, "profile_index outside [0, n_prof)");
@@ -1253,15 +1253,41 @@ int prhf_regrid_f64(prhf_ctx* c, const double* freq_hz, int64_t n_freq, const do
     if (!freq_hz || !den || !bmag || !bpsi || !alt || !multiplier || !out_freq || !out_den || !out_bmag ||
         !out_bpsi || !out_dist || !out_alt || !out_crit || !out_ind)
         return fail(PRHF_EINVAL, "null array pointer");
-    if (n_freq < 1 || n_alt < 1 || n_alt > kMaxAlt || n_points < 1) return fail(PRHF_EINVAL, "bad shape");
+    if (n_freq < 1 || n_alt < 1 || n_alt > kMaxAltTall || n_points < 1) return fail(PRHF_EINVAL, "bad shape");
     if (mode != PRHF_MODE_O && mode != PRHF_MODE_X) return fail(PRHF_EINVAL, "mode must be 'O' or 'X'");
     if (flags & ~PRHF_FLAG_DEVICE_PTRS) return fail(PRHF_EINVAL, "unknown flag bits");
     ENTER_DEVICE(c->device);
     const bool dev = (flags & PRHF_FLAG_DEVICE_PTRS) != 0;
     const size_t fn = (size_t)n_freq * (size_t)n_points;
+    // The reference regrids the levels below the density peak only (library.py:371-375).  A column of more levels than
+    // LDS holds stages just those: its peak - np.argmax, the first NaN ranking highest, the kernel's own rule - comes
+    // from a host scan or, for device memory, from launch_peak_levels (one synchronisation).  Shorter columns take
+    // neither.
+    long long levels = n_alt;
+    if (n_alt > kMaxAlt) {
+        long long peak = 0;
+        if (dev) {
+            HIP_TRY(hipMemsetAsync(c->d_status + 7, 0, sizeof(unsigned), c->stream));
+            HIP_TRY(prhf::launch_peak_levels(den, 1, n_alt, n_alt, c->d_status + 7, c->stream));
+            unsigned p = 0;
+            HIP_TRY(hipMemcpyAsync(&p, c->d_status + 7, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            peak = p;
+        } else {
+            double bv = -HUGE_VAL;
+            for (int64_t i = 0; i < n_alt; ++i) {
+                const double key = (den[i] != den[i]) ? HUGE_VAL : den[i];
+                if (key > bv) { bv = key; peak = i; }
+            }
+        }
+        if (peak + 1 > kMaxAlt)
+            return fail(PRHF_EINVAL, "regrid stages at most %lld levels up to the density peak (the 1400-level "
+                        "bottomside limit); this column's peak is at level %lld", kMaxAlt, peak);
+        levels = peak + 1;
+    }
     prhf::RegridArgs a;
     std::memset(&a, 0, sizeof a);
-    a.n_freq = n_freq; a.n_alt = n_alt; a.n_points = n_points;
+    a.n_freq = n_freq; a.n_alt = n_alt; a.lds_levels = levels; a.n_points = n_points;
     a.mode = mode == PRHF_MODE_O ? PRHF_KMODE_O : PRHF_KMODE_X;
     a.status = c->h_status_dev;
     double* base = nullptr;
@@ -1294,7 +1320,7 @@ int prhf_regrid_f64(prhf_ctx* c, const double* freq_hz, int64_t n_freq, const do
         a.out_ind = reinterpret_cast<long long*>(d_out + 7 * fn);
     }
     HIP_TRY(hipEventRecord(c->begin_ev(), c->stream));
-    HIP_TRY(prhf::launch_regrid(a, prhf::lds_bytes_for(n_alt), c->stream));
+    HIP_TRY(prhf::launch_regrid(a, prhf::lds_bytes_for(levels), c->stream));
     HIP_TRY(hipEventRecord(c->pending_end_ev(), c->stream));
     c->mark_timed();
     c->status_pending = true;

@@ -63,15 +63,19 @@ PRHF_HD dd dd_add(dd a, dd b) {
     return quick_two_sum(s.hi, s.lo);
 }
 
-// x^4 and x^3, one rounding (NumPy evaluates YT**4 and YT**3 with pow; library.py:217, :244)
+// x^4 and x^3, one rounding (NumPy evaluates YT**4 and YT**3 with pow; library.py:217, :244).  A power that
+// overflows (|x| >= ~1.2e77 for x^4, x = +-inf included) leaves an error word of inf - inf = NaN: the result is then
+// the rounded product itself, +-inf as NumPy's pow gives it (NaN stays NaN).
 PRHF_HD double pow4(double x) {
     const dd s = two_prod(x, x);                 // x^2 = s.hi + s.lo exactly
     const dd p = two_prod(s.hi, s.hi);           // s.hi^2 exactly
+    if (!__builtin_isfinite(p.hi)) return p.hi;
     return p.hi + __builtin_fma(2.0 * s.hi, s.lo, p.lo);
 }
 PRHF_HD double pow3(double x) {
     const dd s = two_prod(x, x);
     const dd p = two_prod(s.hi, x);
+    if (!__builtin_isfinite(p.hi)) return p.hi;
     return p.hi + __builtin_fma(s.lo, x, p.lo);
 }
 

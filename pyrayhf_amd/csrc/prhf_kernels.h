@@ -238,6 +238,7 @@ struct RegridArgs {
     long long* out_ind;
     unsigned* status;
     long long n_freq, n_alt;
+    long long lds_levels;     // levels the staged arrays hold: n_alt, or - a taller column - its peak index + 1 (<= 1400)
     int n_points, mode;
 };
 hipError_t launch_regrid(const RegridArgs& a, size_t lds_bytes, hipStream_t stream);

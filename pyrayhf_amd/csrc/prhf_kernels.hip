@@ -470,7 +470,8 @@ __device__ __forceinline__ BlockInfo stage_profile(const double* __restrict__ de
                                                    const double* __restrict__ alt,
                                                    const double* __restrict__ freq, int n_freq,
                                                    int n_alt, Node* nodes, double* pf2, double* gb,
-                                                   unsigned short* hint, double* red, int capacity) {
+                                                   unsigned short* hint, double* red, int capacity,
+                                                   bool bottomside_alt = false) {
 #pragma clang fp contract(off)
     constexpr int W = THREADS / 64;
     static_assert(10 * W + 3 <= PRHF_RED_DOUBLES, "reduction scratch too small");
@@ -488,13 +489,15 @@ __device__ __forceinline__ BlockInfo stage_profile(const double* __restrict__ de
     // trace NaN (np.maximum.accumulate of X + Y, :389, :399); in O mode, like a NaN in psi in either mode, it blanks
     // the grid points of the two segments next to that level (np.interp), which the sum then skips (:288) - the
     // generic loop does exactly that (phase 2 keeps such a profile out of the main loop).
+    // bottomside_alt (the standalone regrid, which never reads np.min(alt)): only a NaN altitude BELOW the peak counts,
+    // and phase 2 finds it - the reference's regrid reads nothing at or above the peak but the density (:371-375).
     int nan_in = 0;
     for (int i = tid; i < n_alt; i += THREADS) {
         const double v = den[i], al = alt[i];
         const double key = (v != v) ? __builtin_inf() : v;
         if (key > bv) { bv = key; bi = i; }
         amin = fmin(amin, al);
-        nan_in |= (al != al) ? 1 : 0;
+        nan_in |= (al != al && !bottomside_alt) ? 1 : 0;
     }
     double fm = __builtin_inf();
     for (int i = tid; i < n_freq; i += THREADS) fm = fmin(fm, fabs(freq[i]));
@@ -656,10 +659,12 @@ __device__ __forceinline__ BlockInfo stage_profile(const double* __restrict__ de
         // some SAMPLED |B| is a number (np.nanmax over the regridded array, :201): grid point 0 sits on level 0, any
         // other grid point inside a segment - a number only when both its ends are
         neg |= ((k == 0 && b == b) || (k + 1 < K && b == b && bmag[k + 1] == bmag[k + 1])) ? 8 : 0;
+        neg |= (bottomside_alt && a != a) ? 16 : 0;   // NaN altitude below the peak (with bottomside_alt: phase 1 left it)
     }
     bmax = wave_max(bmax);
     pmax = wave_max(pmax);
-    neg = (__any(neg & 1) ? 1 : 0) | (__any(neg & 2) ? 2 : 0) | (__any(neg & 4) ? 4 : 0) | (__any(neg & 8) ? 8 : 0);
+    neg = (__any(neg & 1) ? 1 : 0) | (__any(neg & 2) ? 2 : 0) | (__any(neg & 4) ? 4 : 0) | (__any(neg & 8) ? 8 : 0) |
+          (bottomside_alt && __any(neg & 16) ? 16 : 0);
     ragged = __any(ragged) ? 1 : 0;
     // 5: some segment turns the field by more than kTrigAngle (sin() per point, generic loop), 1: some segment needs the
     // rotation form, 2: some segment keeps its cubic, 3: some keeps its quadratic, 0: all linear
@@ -698,6 +703,10 @@ __device__ __forceinline__ BlockInfo stage_profile(const double* __restrict__ de
     if (neg & 1) info.bad = PRHF_STATUS_NEGDEN;    // library.py:93-94
     info.nan_b = (neg & 2) ? 1 : 0;
     info.nan_p = (neg & 4) ? 1 : 0;
+    if (bottomside_alt && (neg & 16) && !info.bad) {
+        info.bad = kNanRow;
+        return info;
+    }
     // library.py:201: nanmax|Y| < y_tol over the call's whole (F, N) array.  |Y| is largest
     // at the lowest frequency and the strongest field; the node maximum bounds the sampled
     // maximum from above and equals it unless |B| < ~4e-18 T ("Deviations").
@@ -2409,17 +2418,20 @@ __global__ __launch_bounds__(THREADS) void regrid_kernel(const RegridArgs a) {
 #pragma clang fp contract(off)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int n_alt = (int)a.n_alt;
+    const int levels = (int)a.lds_levels;          // the staged arrays hold the levels up to the peak (prhf_regrid_f64)
     Node* nodes = reinterpret_cast<Node*>(smem);
-    double* pf2 = reinterpret_cast<double*>(smem + (size_t)(n_alt + 1) * sizeof(Node));
-    double* gb = pf2 + n_alt;
-    unsigned short* hint = reinterpret_cast<unsigned short*>(gb + n_alt);
+    double* pf2 = reinterpret_cast<double*>(smem + (size_t)(levels + 1) * sizeof(Node));
+    double* gb = pf2 + levels;
+    unsigned short* hint = reinterpret_cast<unsigned short*>(gb + levels);
     double* red = reinterpret_cast<double*>(hint + kHintBuckets + PRHF_MAX_CAND);
     const int f = blockIdx.x;
     const int lane = threadIdx.x & 63;
     const double one_mhz = 1.0;     // stage_profile only needs a frequency column for the isotropic test
+    // (the argmax reads the whole column; the nodes, f_N^2 and g_p |B| arrays only the levels below the peak)
     const BlockInfo info = stage_profile<0, THREADS>(a.den, a.bmag, a.bpsi, a.alt, &one_mhz, 0, n_alt, nodes,
-                                                     pf2, gb, hint, red, n_alt + 1);
-    // (the standalone regrid keeps refusing NaN profiles: the operator's NaN rules - stage_profile - are about its sums)
+                                                     pf2, gb, hint, red, levels + 1, true);
+    // (the standalone regrid keeps refusing NaN profiles below the peak: the operator's NaN rules - stage_profile - are
+    //  about its sums; what lies at or above the peak the reference's regrid never reads, :371-375)
     if (threadIdx.x == 0 && (info.bad || info.nan_b || info.nan_p))
         post_status(a.status, (unsigned)((info.bad & ~kNanRow) | ((info.bad & kNanRow) || info.nan_b || info.nan_p
                                                                    ? PRHF_STATUS_NANINPUT : 0)));

@@ -96,19 +96,26 @@ def _default_math(mode_code, math):
     return MATH_AUTO if math is None else int(math)
 
 
+# what NumPy says for np.nanmax of an empty array: the reference's find_mu_mup and find_vh raise it
+_EMPTY = "zero-size array to reduction operation fmax which has no identity"
+
+
 def find_mu_mup(X, Y, bpsi, mode, *, device=None, math=None):
     """Appleton-Hartree phase and group refractive indices on the GPU.
 
     Same arguments and results as the reference's ``find_mu_mup`` (library.py:161-256): ``X``,
     ``Y``, ``bpsi`` (degrees) broadcastable arrays, ``mode`` 'O' or 'X'; returns ``(mu, mup)``
     with the inputs' broadcast shape.  The isotropic formulas are used when ``nanmax|Y| <
-    1e-12`` over the whole array, as in the reference.  Default tier: faithful.
+    1e-12`` over the whole array, as in the reference.  Default tier: faithful.  A zero-size array raises
+    ``ValueError``, as ``np.nanmax`` does in the reference.
     """
     if mode not in _MODE_CODE:
         raise ValueError("Mode must be O or X")                   # reference library.py:225-226
     X, Y, bpsi = np.broadcast_arrays(np.asarray(X, dtype=np.float64), np.asarray(Y, dtype=np.float64),
                                      np.asarray(bpsi, dtype=np.float64))
     shape = X.shape
+    if X.size == 0:
+        raise ValueError(_EMPTY)                                  # np.nanmax of nothing, reference library.py:201
     x, y, p = (np.ascontiguousarray(a).reshape(-1) for a in (X, Y, bpsi))
     mu = np.empty(x.size, dtype=np.float64)
     mup = np.empty(x.size, dtype=np.float64)
@@ -123,13 +130,16 @@ def find_vh(X, Y, bpsi, dh, alt_min, mode, *, device=None, math=None):
     """Virtual height from already-regridded arrays; the reference's ``find_vh`` (library.py:259-293).
 
     ``X, Y, bpsi, dh``: ``(F, N)`` arrays; returns ``(F,)``: ``nansum(mu' * dh, axis=1)`` with an exact
-    zero mapped to NaN, plus ``alt_min``.  Default tier: faithful.
+    zero mapped to NaN, plus ``alt_min``.  Default tier: faithful.  A zero-size array (``(F, 0)`` or ``(0, N)``)
+    raises ``ValueError``, as the reference does.
     """
     if mode not in _MODE_CODE:
         raise ValueError("Mode must be O or X")                   # raised by find_mu_mup, library.py:225-226
     X, Y, bpsi, dh = np.broadcast_arrays(*(np.asarray(a, dtype=np.float64) for a in (X, Y, bpsi, dh)))
     if X.ndim != 2:
         raise ValueError("X, Y, bpsi and dh must be 2-D (frequencies x grid points)")
+    if X.size == 0:
+        raise ValueError(_EMPTY)                                  # find_mu_mup's np.nanmax, reference library.py:201
     x, y, p, d = (np.ascontiguousarray(a) for a in (X, Y, bpsi, dh))
     vh = np.empty(x.shape[0], dtype=np.float64)
     ctx = _native.host_context(device)
@@ -145,7 +155,11 @@ def regrid_to_nonuniform_grid(f, n_e, b, bpsi, aalt, mode='O', n_points=200, dh=
 
     ``f`` in **Hz**; returns the reference's dict of ``(F, N)`` arrays ``freq, den, bmag, bpsi, dist, alt,
     crit_height`` (float64) and ``ind`` (int64), bit-identical to NumPy's.  As in the reference the
-    ``dh`` argument is ignored (it is overwritten with 1e-6 km, library.py:378).
+    ``dh`` argument is ignored (it is overwritten with 1e-6 km, library.py:378), and only the levels below the
+    density peak are used (library.py:371-375): what lies at or above it - a NaN altitude, field strength or angle
+    included - changes nothing.  A NaN in ``aalt``, ``b`` or ``bpsi`` below the peak raises ``ValueError``.
+    Columns may have up to 65 535 levels; the bottomside limit is 1400 levels up to the density peak (the peak at
+    level 1399 or lower), beyond which ``ValueError`` is raised.
     """
     code = _mode_code(mode)
     fz = np.ascontiguousarray(np.atleast_1d(np.asarray(f)), dtype=np.float64)

@@ -138,3 +138,21 @@ def test_header_constants_match_the_binding():
               "PRHF_ABI_VERSION": _native.ABI_VERSION}
     for name, value in expect.items():
         assert defines.get(name) == value, (name, defines.get(name), value)
+
+
+@pytest.mark.parametrize("shape", [(0,), (3, 0), (0, 4)])
+def test_zero_size_stage_arrays_raise_before_any_native_call(monkeypatch, shape):
+    """The reference's find_mu_mup and find_vh raise ValueError on a zero-size array (np.nanmax of nothing has no
+    identity, library.py:201); the wrappers raise the same before they reach the library."""
+    def no_native_call(*args, **kwargs):
+        raise AssertionError("the library was called")
+    monkeypatch.setattr(_native, "host_context", no_native_call)
+    monkeypatch.setattr(_native, "context", no_native_call)
+    with pytest.raises(ValueError) as want:
+        np.nanmax(np.abs(np.zeros(shape)))
+    z = np.zeros(shape)
+    with pytest.raises(ValueError, match=str(want.value)):
+        library.find_mu_mup(z, z, z, "O")
+    if len(shape) == 2:
+        with pytest.raises(ValueError, match=str(want.value)):
+            library.find_vh(z, z, z, z, 100.0, "X")

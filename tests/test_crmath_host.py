@@ -121,3 +121,21 @@ def test_numpy_agrees_most_of_the_time(crlib):
     crlib.cr_pow34(x.ctypes.data, x.size, p3.ctypes.data, p4.ctypes.data)
     assert (p4 == x ** 4).mean() > 0.9 and (p3 == x ** 3).mean() > 0.9
     assert math.isclose(float(p4[0]), float(x[0]) ** 4, rel_tol=1e-15)
+
+
+def test_pow3_pow4_overflow_as_numpy_does(crlib):
+    """A power that overflows - x = +-inf included - is +-inf, as NumPy's pow gives it (reference library.py:217, :244:
+    YT**4 and YT**3 for an infinite Y); the double-double error word would be inf - inf = NaN."""
+    x = np.array([np.inf, -np.inf, 1e78, -1e78, 1e103, -1e103, 1e200, -1e300, 1.0e76, -1.0e76, np.nan])
+    p3 = np.empty_like(x)
+    p4 = np.empty_like(x)
+    crlib.cr_pow34(x.ctypes.data, x.size, p3.ctypes.data, p4.ctypes.data)
+    with np.errstate(over="ignore"):
+        w3, w4 = x ** 3, x ** 4
+    assert np.array_equal(np.isinf(p4), np.isinf(w4)) and np.array_equal(np.isinf(p3), np.isinf(w3))
+    inf = np.isinf(w4) | np.isinf(w3)
+    assert np.array_equal(p4[np.isinf(w4)], w4[np.isinf(w4)]) and np.array_equal(p3[np.isinf(w3)], w3[np.isinf(w3)])
+    fin = ~inf & ~np.isnan(x)
+    assert np.array_equal(p4[fin], np.array([float(Fraction(float(v)) ** 4) for v in x[fin]]))
+    assert np.array_equal(p3[fin], np.array([float(Fraction(float(v)) ** 3) for v in x[fin]]))
+    assert np.isnan(p3[-1]) and np.isnan(p4[-1])

@@ -278,3 +278,37 @@ def test_config5_rows_g15():
         for p in (range(8) if n <= 200 else (0, 7) if n <= 2000 else (3,)):
             vh = orc.virtual_heights(g["freq"], den[p], bmag[p], bpsi[p], alt, mode, int(n))
             assert same_bits(vh, g[f"{mode}_{n}_vh"][p]), (mode, n, p)
+
+
+def test_stage_ops_edges_g16():
+    """The reference's own regrid_to_nonuniform_grid, find_mu_mup and find_vh on edge inputs (fixture G16): K == 1,
+    reflection at level 0, f = 0 / NaN, X mode below f_H, valley and plateau, ragged and tall columns, NaN above the
+    peak, NaN padding; X and Y at and next to 1, Y = inf / NaN, isotropic arrays; find_vh rows that give NaN.  The GPU
+    tests compare the stage ops with the oracle wherever a shape is too large for a fixture."""
+    g = load_golden("g16_stage_edges.npz")
+    with np.errstate(all="ignore"):
+        for case in g["rg_cases"]:
+            a = [g[f"rg_{case}_{k}_in"] for k in ("freq", "den", "bmag", "bpsi", "alt")]
+            for mode in "OX":
+                cols = orc.stretched_columns(*a, mode, int(g[f"rg_{case}_n_points"]))
+                for key, v in cols.items():
+                    assert same_bits(v, g[f"rg_{case}_{key}_{mode}"]), (case, mode, key)
+                assert g[f"rg_{case}_ind_{mode}"].dtype == np.int64
+        for case in g["mu_cases"]:
+            a = [g[f"mu_{case}_{k}"] for k in ("X", "Y", "psi")]
+            for mode in "OX":
+                mu, mup = orc.phase_group_index(*a, mode)
+                assert same_bits(mu, g[f"mu_{case}_mu_{mode}"]) and same_bits(mup, g[f"mu_{case}_mup_{mode}"]), (case, mode)
+        for case in g["vh_cases"]:
+            a = [g[f"vh_{case}_{k}"] for k in ("X", "Y", "psi", "dh")]
+            for mode in "OX":
+                vh = orc.group_path(*a, float(g[f"vh_{case}_alt_min"]), mode)
+                assert same_bits(vh, g[f"vh_{case}_vh_{mode}"]), (case, mode)
+    # what the cases are there for
+    assert np.all(np.isnan(g["vh_rows_vh_O"][[1, 2]])) and np.isfinite(g["vh_rows_vh_O"][3])
+    k1 = g["rg_k1_den_O"]
+    assert np.all(k1[np.isfinite(k1)] == 1.0e11)                    # one level below the peak: a constant column
+    assert np.isnan(g["rg_day_crit_height_O"][1, 0]) and np.isnan(g["rg_day_crit_height_O"][-1, 0])  # f = NaN, escape
+    for case in ("day", "tall_day"):
+        for mode in "OX":
+            assert same_bits(g[f"rg_{case}_nan_above_alt_{mode}"], g[f"rg_{case}_alt_{mode}"]), (case, mode)

@@ -31,8 +31,9 @@
 extern "C" {
 #endif
 
-#define PRHF_ABI_VERSION 3   /* 2: + prhf_snell_fan_f64, prhf_recent_kernel_ms, PRHF_FLAG_SHARED_FIELD (round 2)
-                              * 3: + prhf_ctx_set_option (round 3) */
+#define PRHF_ABI_VERSION 4   /* 2: + prhf_snell_fan_f64, prhf_recent_kernel_ms, PRHF_FLAG_SHARED_FIELD (round 2)
+                              * 3: + prhf_ctx_set_option (round 3)
+                              * 4: + prhf_field_pack_f64, prhf_field_sample_f64, prhf_trace_gradient_f64 */
 
 /* return codes */
 #define PRHF_OK        0
@@ -300,6 +301,64 @@ int prhf_snell_fan_f64(prhf_ctx* ctx, int32_t geometry, const double* group_freq
                        int64_t alt_stride_elems, int32_t mode, double earth_radius_km, double dz_target_km,
                        double apex_boost, int32_t max_substeps, double* out, double* path_x, double* path_z,
                        int64_t path_stride, uint32_t flags);
+
+/*
+ * 2-D refractive-index fields mu(a0, a1) for the gradient tracer: node records.
+ * Replaces: the grid half of build_refractive_index_interpolator_cartesian / _spherical (reference library.py:1801-1835,
+ * :1879-1921) and of build_mup_function (:1978-2014).  mu and mup are n_fields planes of (n0, n1) values each,
+ * row-major (host memory, or device memory with PRHF_FLAG_DEVICE_PTRS); axis0 (n0) and axis1 (n1) are HOST memory in
+ * every flag combination and strictly increasing - altitude z and distance x of a Cartesian field, r = R_E + z and
+ * phi = x / R_E of a spherical one (:1887-1888).  records is DEVICE memory in every flag combination,
+ * (n_fields, n0, n1, 4) doubles: {mu, d mu / d a1, d mu / d a0, mu'} per node, the derivatives
+ * np.gradient(mu, axis0, axis1, edge_order = 1 or 2) (:1823, :1908) in NumPy's formulas and operation order - its
+ * scalar-spacing branch along an axis whose np.diff values are all equal, its three-point branch otherwise -
+ * bit-identical to NumPy, NaNs included.  An axis needs edge_order + 1 values; n0 + n1 <= 8000.  Synchronous.
+ */
+int prhf_field_pack_f64(prhf_ctx* ctx, const double* mu, const double* mup, int64_t n_fields, int64_t n0, int64_t n1,
+                        const double* axis0, const double* axis1, int32_t edge_order, double* records, uint32_t flags);
+
+/*
+ * The fields at n points (p0[i], p1[i]) along (axis0, axis1); field_index[i] (NULL: field 0) chooses the field.
+ * Replaces: the RegularGridInterpolator calls behind eval_refractive_index_and_grad, n_and_grad_rphi and mup_func
+ * (reference library.py:939-950, :1716-1752, :1987-2013) with method="linear", bounds_error=False: the cell i with
+ * g[i] <= v < g[i + 1] (the last cell for v = g[n - 1]); all four corner products are formed, so a NaN corner gives
+ * NaN even at weight 0; a point outside the hull gets fill_n (mu), fill_grad (both derivatives), fill_mup; a NaN
+ * coordinate gives NaN.  Any of the four outputs (n each) may be NULL.  records, axes and limits as for
+ * prhf_field_pack_f64; the point arrays and outputs are host memory, or device memory with PRHF_FLAG_DEVICE_PTRS.
+ * PRHF_EINVAL for a field_index outside [0, n_fields): checked on the host for host buffers, by the kernel for
+ * device-resident ones (that point's outputs are NaN, no memory outside the records is read).  Synchronous.
+ */
+int prhf_field_sample_f64(prhf_ctx* ctx, const double* records, int64_t n_fields, int64_t n0, int64_t n1,
+                          const double* axis0, const double* axis1, const double* p0, const double* p1,
+                          const int64_t* field_index, int64_t n, double fill_n, double fill_grad, double fill_mup,
+                          double* out_n, double* out_d1, double* out_d0, double* out_mup, uint32_t flags);
+
+/*
+ * Ray tracing through a horizontally varying mu(x, z) over a flat Earth, n_rays rays in one launch (one per lane).
+ * Replaces: trace_ray_cartesian_gradient (reference library.py:1270-1457) with ray_rhs_cartesian (:953-1006) and the
+ * event helpers (:1009-1031).  records: Cartesian records of prhf_field_pack_f64 on (z_axis (nz), x_axis (nx)).  Ray r
+ * starts at (x0_km[r], z0_km[r]) with elevation_deg[r] above the horizon in field ray_field[r] (NULL: field 0).  The
+ * controls are the reference's (:1278-1291; max_step_km = +inf for None; z_min_km is unused there and absent here);
+ * fill_n / fill_grad / fill_mup are the interpolators' fill values outside the grid (:1764-1766, :1938).  The system
+ * dr/ds = v, dv/ds = (grad mu - (grad mu . v) v) / mu is integrated by the Dormand-Prince 5(4) pair with the
+ * controller solve_ivp(method="RK45") documents; the four terminal events (+ -> -) are located on the step's dense
+ * output and the event point is the last node.
+ * out is (n_rays, 12): group_path_km, group_delay_sec, x_midpoint, z_midpoint, ground_range_km, x_apex_km, z_apex_km
+ * (the reference's dict entries, :1405-1441), status (0 ground, 1 domain, 2 length, 3 failure: the step fell below
+ * 10 ulp of s, :1391-1398), nodes, right-hand-side calls, rejected steps, 0.  path_t .. path_vz (all five or none,
+ * (n_rays, path_stride) each) receive the reference's 't', 'x', 'z', 'vx', 'vz' padded with NaN; PRHF_EINVAL when a
+ * ray has more nodes than path_stride (nothing is truncated: ask again with out[.., 8] nodes).  Ray arrays, out and
+ * paths are host memory, or device memory with PRHF_FLAG_DEVICE_PTRS.  PRHF_EINVAL for a ray_field outside
+ * [0, n_fields): on the host for host buffers, by the kernel for device-resident ones (NaN outputs, no memory outside
+ * the records is read).  Synchronous.
+ */
+int prhf_trace_gradient_f64(prhf_ctx* ctx, const double* records, int64_t n_fields, int64_t nz, int64_t nx,
+                            const double* z_axis, const double* x_axis, const double* x0_km, const double* z0_km,
+                            const double* elevation_deg, const int64_t* ray_field, int64_t n_rays, double s_max_km,
+                            double rtol, double atol, double max_step_km, double z_ground_km, double z_max_km,
+                            double x_min_km, double x_max_km, int32_t renormalize_every, double fill_n, double fill_grad,
+                            double fill_mup, double* out, double* path_t, double* path_x, double* path_z, double* path_vx,
+                            double* path_vz, int64_t path_stride, uint32_t flags);
 
 /* Diagnostics: workgroups of the fused kernel the runtime expects to keep resident per CU for
  * profiles of n_alt levels (LDS-limited) in arithmetic tier `math`. */

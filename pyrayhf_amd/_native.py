@@ -18,7 +18,7 @@ OK, EINVAL, ENEGDEN, EPEAK0, EHIP, ENOMEM = 0, -1, -2, -3, -4, -5
 MODE_O, MODE_X = 0, 1
 FLAG_DEVICE_PTRS, FLAG_ASYNC, FLAG_GRID_STABLE, FLAG_SHARED_FIELD = 0x1, 0x2, 0x4, 0x8
 MATH_FAITHFUL, MATH_FAST, MATH_AUTO = 0, 1, 2
-ABI_VERSION = 3
+ABI_VERSION = 4
 
 c_double_p = ctypes.POINTER(ctypes.c_double)
 
@@ -83,6 +83,16 @@ _PROTOTYPES = {
         ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_double, ctypes.c_double,
         ctypes.c_double, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
         ctypes.c_uint32]),
+    "prhf_field_pack_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                           ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                                           ctypes.c_int32, ctypes.c_void_p, ctypes.c_uint32]),
+    "prhf_field_sample_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                                             ctypes.c_int64] + [ctypes.c_void_p] * 5 + [ctypes.c_int64] +
+                              [ctypes.c_double] * 3 + [ctypes.c_void_p] * 4 + [ctypes.c_uint32]),
+    "prhf_trace_gradient_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                                               ctypes.c_int64] + [ctypes.c_void_p] * 6 + [ctypes.c_int64] +
+                                [ctypes.c_double] * 8 + [ctypes.c_int32] + [ctypes.c_double] * 3 +
+                                [ctypes.c_void_p] * 6 + [ctypes.c_int64, ctypes.c_uint32]),
     "prhf_occupancy": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
                                       ctypes.POINTER(ctypes.c_int32)]),
     "prhf_sync": (ctypes.c_int, [ctypes.c_void_p]),
@@ -265,6 +275,27 @@ class Context:
                                             elev, n_rays, den, bmag, bpsi, alt, n_prof, n_alt, alt_stride, mode,
                                             float(r_e), float(dz_target), float(apex_boost), int(max_substeps), out,
                                             path_x or None, path_z or None, path_stride, flags)
+
+    def field_pack(self, mu, mup, n_fields, n0, n1, axis0, axis1, edge_order, records, flags):
+        """``records``: a device address in every flag combination; the axes: host addresses."""
+        return self._lib.prhf_field_pack_f64(self._h, mu, mup, n_fields, n0, n1, axis0, axis1, int(edge_order),
+                                             records, flags)
+
+    def field_sample(self, records, n_fields, n0, n1, axis0, axis1, p0, p1, field_index, n, fills, outs, flags):
+        """fills: (fill_n, fill_grad, fill_mup); outs: four raw addresses (mu, d/da1, d/da0, mu'), None to skip."""
+        return self._lib.prhf_field_sample_f64(self._h, records, n_fields, n0, n1, axis0, axis1, p0, p1,
+                                               field_index or None, n, *(float(v) for v in fills),
+                                               *(o or None for o in outs), flags)
+
+    def trace_gradient(self, records, n_fields, nz, nx, z_axis, x_axis, x0, z0, elev, ray_field, n_rays, controls, fills,
+                       out, paths, path_stride, flags):
+        """controls: (s_max_km, rtol, atol, max_step_km, z_ground_km, z_max_km, x_min_km, x_max_km, renormalize_every);
+        paths: five raw addresses (t, x, z, vx, vz) or None."""
+        paths = paths or (None,) * 5
+        return self._lib.prhf_trace_gradient_f64(self._h, records, n_fields, nz, nx, z_axis, x_axis, x0, z0, elev,
+                                                 ray_field or None, n_rays, *(float(v) for v in controls[:8]),
+                                                 int(controls[8]), *(float(v) for v in fills), out, *paths,
+                                                 int(path_stride), flags)
 
     def occupancy(self, n_alt, math):
         n = ctypes.c_int32(0)

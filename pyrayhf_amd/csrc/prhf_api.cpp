@@ -201,6 +201,8 @@ int status_to_code(unsigned bits) {
     if (bits & PRHF_STATUS_NEGDEN) return fail(PRHF_ENEGDEN, "Density must be non-negative");
     if (bits & PRHF_STATUS_BADGROUP) return fail(PRHF_EINVAL, "ray_group outside [0, n_groups)");
     if (bits & PRHF_STATUS_BADINDEX) return fail(PRHF_EINVAL, "profile_index outside [0, n_prof)");
+    if (bits & PRHF_STATUS_BADFIELD) return fail(PRHF_EINVAL, "field index outside [0, n_fields)");
+    if (bits & PRHF_STATUS_PATHLEN) return fail(PRHF_EINVAL, "a ray has more path nodes than path_stride");
     return PRHF_OK;
 }
 
@@ -1600,6 +1602,194 @@ int prhf_snell_fan_f64(prhf_ctx* c, int32_t geometry, const double* group_freq_h
                                             : SnellGeometry{1, earth_radius_km, dz_target_km, apex_boost, max_substeps};
     return snell_run(c, geo, group_freq_hz, elevation_deg, group_profile_index, n_rays, den, bmag, bpsi, alt, n_prof, n_alt,
                      alt_stride_elems, mode, out, path_x, path_z, path_stride, flags, ray_group, n_groups);
+}
+
+namespace {
+// The two axes of a field: host memory, strictly increasing (a NaN fails the test), at least `least` values each and
+// together no more than the kernels stage in LDS.  *uniform: all np.diff(axis) are equal (np.gradient's scalar branch).
+int check_axis(const char* name, const double* g, int64_t n, int64_t least, int* uniform) {
+    if (n < least) return fail(PRHF_EINVAL, "%s needs at least %lld values", name, (long long)least);
+    *uniform = 1;
+    const double d0 = g[1] - g[0];
+    for (int64_t i = 0; i + 1 < n; ++i) {
+        const double d = g[i + 1] - g[i];
+        if (!(d > 0)) return fail(PRHF_EINVAL, "%s must be strictly increasing", name);
+        if (!(d == d0)) *uniform = 0;
+    }
+    return PRHF_OK;
+}
+int check_field_shape(const double* axis0, const double* axis1, int64_t n_fields, int64_t n0, int64_t n1, int64_t least,
+                      int* u0, int* u1) {
+    if (!axis0 || !axis1) return fail(PRHF_EINVAL, "null array pointer");
+    if (n_fields < 1 || n0 < 1 || n1 < 1 || n0 + n1 > PRHF_FIELD_MAX_AXES || n_fields > (int64_t)1 << 24)
+        return fail(PRHF_EINVAL, "bad shape (the two axes hold at most %d values together)", PRHF_FIELD_MAX_AXES);
+    int rc = check_axis("axis 0", axis0, n0, least, u0);
+    if (rc != PRHF_OK) return rc;
+    return check_axis("axis 1", axis1, n1, least, u1);
+}
+}  // namespace
+
+int prhf_field_pack_f64(prhf_ctx* c, const double* mu, const double* mup, int64_t n_fields, int64_t n0, int64_t n1,
+                        const double* axis0, const double* axis1, int32_t edge_order, double* records, uint32_t flags) {
+    if (!c) return fail(PRHF_EINVAL, "null context");
+    if (!mu || !mup || !records) return fail(PRHF_EINVAL, "null array pointer");
+    if (edge_order != 1 && edge_order != 2) return fail(PRHF_EINVAL, "edge_order is 1 or 2");
+    if (flags & ~PRHF_FLAG_DEVICE_PTRS) return fail(PRHF_EINVAL, "unknown flag bits");
+    int u0 = 0, u1 = 0;
+    int rc = check_field_shape(axis0, axis1, n_fields, n0, n1, edge_order + 1, &u0, &u1);
+    if (rc != PRHF_OK) return rc;
+    ENTER_DEVICE(c->device);
+    const bool dev = (flags & PRHF_FLAG_DEVICE_PTRS) != 0;
+    const size_t cells = (size_t)n_fields * (size_t)n0 * (size_t)n1;
+    rc = ensure(c, c->arena, ((size_t)(n0 + n1) + (dev ? 0 : 2 * cells)) * 8);
+    if (rc != PRHF_OK) return rc;
+    double* p = static_cast<double*>(c->arena.p);
+    prhf::FieldPackArgs a;
+    std::memset(&a, 0, sizeof a);
+    HIP_TRY(hipMemcpyAsync(p, axis0, (size_t)n0 * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(p + n0, axis1, (size_t)n1 * 8, hipMemcpyHostToDevice, c->stream));
+    a.a0 = p; a.a1 = p + n0; a.mu = mu; a.mup = mup;
+    if (!dev) {
+        double* d_mu = p + n0 + n1;
+        HIP_TRY(hipMemcpyAsync(d_mu, mu, cells * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_mu + cells, mup, cells * 8, hipMemcpyHostToDevice, c->stream));
+        a.mu = d_mu; a.mup = d_mu + cells;
+    }
+    a.rec = records; a.n_fields = n_fields; a.n0 = (int)n0; a.n1 = (int)n1; a.uniform0 = u0; a.uniform1 = u1;
+    a.edge_order = edge_order;
+    HIP_TRY(hipEventRecord(c->begin_ev(), c->stream));
+    HIP_TRY(prhf::launch_field_pack(a, c->stream));
+    HIP_TRY(hipEventRecord(c->pending_end_ev(), c->stream));
+    c->mark_timed();
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return PRHF_OK;
+}
+
+int prhf_field_sample_f64(prhf_ctx* c, const double* records, int64_t n_fields, int64_t n0, int64_t n1,
+                          const double* axis0, const double* axis1, const double* p0, const double* p1,
+                          const int64_t* field_index, int64_t n, double fill_n, double fill_grad, double fill_mup,
+                          double* out_n, double* out_d1, double* out_d0, double* out_mup, uint32_t flags) {
+    if (!c) return fail(PRHF_EINVAL, "null context");
+    if (!records || !p0 || !p1) return fail(PRHF_EINVAL, "null array pointer");
+    if (!out_n && !out_d1 && !out_d0 && !out_mup) return fail(PRHF_EINVAL, "no output asked for");
+    if (n < 0) return fail(PRHF_EINVAL, "bad shape");
+    if (flags & ~PRHF_FLAG_DEVICE_PTRS) return fail(PRHF_EINVAL, "unknown flag bits");
+    int u0 = 0, u1 = 0;
+    int rc = check_field_shape(axis0, axis1, n_fields, n0, n1, 2, &u0, &u1);
+    if (rc != PRHF_OK) return rc;
+    const bool dev = (flags & PRHF_FLAG_DEVICE_PTRS) != 0;
+    if (!dev && field_index)
+        for (int64_t i = 0; i < n; ++i)
+            if (field_index[i] < 0 || field_index[i] >= n_fields)
+                return fail(PRHF_EINVAL, "field_index[%lld] outside [0, n_fields)", (long long)i);
+    if (n == 0) return PRHF_OK;
+    ENTER_DEVICE(c->device);
+    double* outs[4] = {out_n, out_d1, out_d0, out_mup};
+    rc = ensure(c, c->arena, ((size_t)(n0 + n1) + (dev ? 0 : 7 * (size_t)n)) * 8);
+    if (rc != PRHF_OK) return rc;
+    double* p = static_cast<double*>(c->arena.p);
+    prhf::FieldSampleArgs a;
+    std::memset(&a, 0, sizeof a);
+    HIP_TRY(hipMemcpyAsync(p, axis0, (size_t)n0 * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(p + n0, axis1, (size_t)n1 * 8, hipMemcpyHostToDevice, c->stream));
+    a.rec = records; a.a0 = p; a.a1 = p + n0; a.n = n; a.n_fields = n_fields; a.n0 = (int)n0; a.n1 = (int)n1;
+    a.fill_n = fill_n; a.fill_grad = fill_grad; a.fill_mup = fill_mup; a.status = c->h_status_dev;
+    double* d_out[4] = {out_n, out_d1, out_d0, out_mup};
+    if (dev) {
+        a.p0 = p0; a.p1 = p1; a.field = reinterpret_cast<const long long*>(field_index);
+    } else {
+        double* q = p + n0 + n1;
+        HIP_TRY(hipMemcpyAsync(q, p0, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(q + n, p1, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+        if (field_index) HIP_TRY(hipMemcpyAsync(q + 2 * n, field_index, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+        a.p0 = q; a.p1 = q + n; a.field = field_index ? reinterpret_cast<const long long*>(q + 2 * n) : nullptr;
+        for (int k = 0; k < 4; ++k) d_out[k] = outs[k] ? q + (3 + k) * n : nullptr;
+    }
+    a.out_n = d_out[0]; a.out_d1 = d_out[1]; a.out_d0 = d_out[2]; a.out_mup = d_out[3];
+    HIP_TRY(hipEventRecord(c->begin_ev(), c->stream));
+    HIP_TRY(prhf::launch_field_sample(a, c->stream));
+    HIP_TRY(hipEventRecord(c->pending_end_ev(), c->stream));
+    c->mark_timed();
+    c->status_pending = true;
+    if (!dev)
+        for (int k = 0; k < 4; ++k)
+            if (outs[k]) HIP_TRY(hipMemcpyAsync(outs[k], d_out[k], (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+    return prhf_sync(c);
+}
+
+int prhf_trace_gradient_f64(prhf_ctx* c, const double* records, int64_t n_fields, int64_t nz, int64_t nx,
+                            const double* z_axis, const double* x_axis, const double* x0_km, const double* z0_km,
+                            const double* elevation_deg, const int64_t* ray_field, int64_t n_rays, double s_max_km,
+                            double rtol, double atol, double max_step_km, double z_ground_km, double z_max_km,
+                            double x_min_km, double x_max_km, int32_t renormalize_every, double fill_n, double fill_grad,
+                            double fill_mup, double* out, double* path_t, double* path_x, double* path_z, double* path_vx,
+                            double* path_vz, int64_t path_stride, uint32_t flags) {
+    if (!c) return fail(PRHF_EINVAL, "null context");
+    if (!records || !x0_km || !z0_km || !elevation_deg || !out) return fail(PRHF_EINVAL, "null array pointer");
+    if (n_rays < 0) return fail(PRHF_EINVAL, "bad shape");
+    if (flags & ~PRHF_FLAG_DEVICE_PTRS) return fail(PRHF_EINVAL, "unknown flag bits");
+    const int n_paths = (path_t != nullptr) + (path_x != nullptr) + (path_z != nullptr) + (path_vx != nullptr) + (path_vz != nullptr);
+    if (n_paths != 0 && n_paths != 5) return fail(PRHF_EINVAL, "the five path arrays go together");
+    if (n_paths && path_stride < 1) return fail(PRHF_EINVAL, "path_stride must hold at least the launch point");
+    if (!(s_max_km > 0) || !std::isfinite(s_max_km)) return fail(PRHF_EINVAL, "s_max_km must be positive and finite");
+    if (!(max_step_km > 0)) return fail(PRHF_EINVAL, "`max_step` must be positive.");
+    if (!(rtol >= 0) || !(atol >= 0)) return fail(PRHF_EINVAL, "`atol` must be positive.");
+    if (renormalize_every < 0) return fail(PRHF_EINVAL, "renormalize_every must not be negative");
+    int u0 = 0, u1 = 0;
+    int rc = check_field_shape(z_axis, x_axis, n_fields, nz, nx, 2, &u0, &u1);
+    if (rc != PRHF_OK) return rc;
+    const bool dev = (flags & PRHF_FLAG_DEVICE_PTRS) != 0;
+    if (!dev && ray_field)
+        for (int64_t r = 0; r < n_rays; ++r)
+            if (ray_field[r] < 0 || ray_field[r] >= n_fields)
+                return fail(PRHF_EINVAL, "ray_field[%lld] outside [0, n_fields)", (long long)r);
+    if (n_rays == 0) return PRHF_OK;
+    ENTER_DEVICE(c->device);
+    const size_t R = (size_t)n_rays, path_elems = n_paths ? R * (size_t)path_stride : 0;
+    rc = ensure(c, c->arena, ((size_t)(nz + nx) + (dev ? 0 : (4 + PRHF_GRAD_OUTPUTS) * R + 5 * path_elems)) * 8);
+    if (rc != PRHF_OK) return rc;
+    double* p = static_cast<double*>(c->arena.p);
+    prhf::GradTraceArgs a;
+    std::memset(&a, 0, sizeof a);
+    HIP_TRY(hipMemcpyAsync(p, z_axis, (size_t)nz * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(p + nz, x_axis, (size_t)nx * 8, hipMemcpyHostToDevice, c->stream));
+    a.rec = records; a.a0 = p; a.a1 = p + nz; a.n0 = (int)nz; a.n1 = (int)nx; a.n_fields = n_fields; a.n_rays = n_rays;
+    a.path_stride = n_paths ? path_stride : 0;
+    a.s_max = s_max_km;
+    a.rtol = rtol < 100 * 2.220446049250313e-16 ? 100 * 2.220446049250313e-16 : rtol;     // (solve_ivp raises a too small rtol so)
+    a.atol = atol; a.max_step = max_step_km; a.z_ground = z_ground_km; a.z_max = z_max_km;
+    a.x_min = x_min_km; a.x_max = x_max_km; a.renormalize_every = renormalize_every;
+    a.fill_n = fill_n; a.fill_grad = fill_grad; a.fill_mup = fill_mup; a.status = c->h_status_dev;
+    double* host_paths[5] = {path_t, path_x, path_z, path_vx, path_vz};
+    double* d_paths[5] = {path_t, path_x, path_z, path_vx, path_vz};
+    if (dev) {
+        a.x0 = x0_km; a.z0 = z0_km; a.elev = elevation_deg; a.ray_field = reinterpret_cast<const long long*>(ray_field);
+        a.out = out;
+    } else {
+        double* q = p + nz + nx;
+        HIP_TRY(hipMemcpyAsync(q, x0_km, R * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(q + R, z0_km, R * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(q + 2 * R, elevation_deg, R * 8, hipMemcpyHostToDevice, c->stream));
+        if (ray_field) HIP_TRY(hipMemcpyAsync(q + 3 * R, ray_field, R * 8, hipMemcpyHostToDevice, c->stream));
+        a.x0 = q; a.z0 = q + R; a.elev = q + 2 * R;
+        a.ray_field = ray_field ? reinterpret_cast<const long long*>(q + 3 * R) : nullptr;
+        a.out = q + 4 * R;
+        for (int k = 0; k < 5; ++k) d_paths[k] = n_paths ? a.out + PRHF_GRAD_OUTPUTS * R + k * path_elems : nullptr;
+    }
+    // nodes a ray does not reach stay NaN (all bits set)
+    for (int k = 0; k < 5 && n_paths; ++k) HIP_TRY(hipMemsetAsync(d_paths[k], 0xff, path_elems * 8, c->stream));
+    a.path_t = d_paths[0]; a.path_x = d_paths[1]; a.path_z = d_paths[2]; a.path_vx = d_paths[3]; a.path_vz = d_paths[4];
+    HIP_TRY(hipEventRecord(c->begin_ev(), c->stream));
+    HIP_TRY(prhf::launch_grad_trace(a, c->stream));
+    HIP_TRY(hipEventRecord(c->pending_end_ev(), c->stream));
+    c->mark_timed();
+    c->status_pending = true;
+    if (!dev) {
+        HIP_TRY(hipMemcpyAsync(out, a.out, PRHF_GRAD_OUTPUTS * R * 8, hipMemcpyDeviceToHost, c->stream));
+        for (int k = 0; k < 5 && n_paths; ++k)
+            HIP_TRY(hipMemcpyAsync(host_paths[k], d_paths[k], path_elems * 8, hipMemcpyDeviceToHost, c->stream));
+    }
+    return prhf_sync(c);
 }
 
 int prhf_occupancy(prhf_ctx* c, int64_t n_alt, int32_t math, int32_t* workgroups_per_cu) {

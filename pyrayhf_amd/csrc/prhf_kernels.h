@@ -12,6 +12,8 @@
 #define PRHF_STATUS_NEGDEN 0x1
 #define PRHF_STATUS_PEAK0  0x2
 #define PRHF_STATUS_BADINDEX 0x4    // a ray's profile_index outside [0, n_prof) (tracers)
+#define PRHF_STATUS_BADFIELD 0x20   // a point's / ray's field index outside [0, n_fields) (prhf_gradient.inc)
+#define PRHF_STATUS_PATHLEN 0x40    // a ray of the gradient tracer has more nodes than path_stride
 #define PRHF_STATUS_WORDS 8         // one word of host-visible memory per status bit (post_status)
 #define PRHF_STATUS_NANINPUT 0x10   // NaN in a profile's altitude column, or in |B| / psi below its peak
 #define PRHF_STATUS_BADGROUP 0x8    // a ray's ray_group outside [0, n_groups) (grouped tracer launch)
@@ -295,6 +297,62 @@ hipError_t launch_snell(const SnellArgs& a, hipStream_t stream);   // with a.ray
 // wavefronts of the per-ray kernel that one device keeps resident; cu_count: multiprocessors of the device
 hipError_t snell_resident_waves(long long n_alt, int cu_count, long long* waves, bool ptab = false, bool reduced = false,
                                 int geometry = 0);
+
+// 2-D refractive-index fields and the Cartesian gradient tracer (prhf_gradient.inc); device pointers throughout.
+struct FieldPackArgs {
+    const double* mu;            // (n_fields, n0, n1)
+    const double* mup;
+    const double* a0;            // (n0), (n1): the axes
+    const double* a1;
+    double* rec;                 // (n_fields, n0, n1, 4): mu, d/da1, d/da0, mu'
+    long long n_fields;
+    int n0, n1;
+    int uniform0, uniform1;      // all np.diff(axis) are equal: np.gradient's scalar-spacing branch
+    int edge_order;
+};
+struct FieldSampleArgs {
+    const double* rec;
+    const double* a0;
+    const double* a1;
+    const double* p0;            // (n) coordinates along a0 and a1
+    const double* p1;
+    const long long* field;      // (n) or null: field 0
+    double* out_n;               // (n) each, or null
+    double* out_d1;
+    double* out_d0;
+    double* out_mup;
+    unsigned* status;
+    long long n, n_fields;
+    int n0, n1;
+    double fill_n, fill_grad, fill_mup;
+};
+#define PRHF_GRAD_OUTPUTS 12     // path km, delay s, x_mid, z_mid, ground range, x_apex, z_apex, status, nodes, RHS calls, rejected steps, 0
+struct GradTraceArgs {
+    const double* rec;
+    const double* a0;            // z axis (n0), x axis (n1)
+    const double* a1;
+    const double* x0;            // (n_rays) each
+    const double* z0;
+    const double* elev;
+    const long long* ray_field;  // (n_rays) or null: field 0
+    double* out;                 // (n_rays, PRHF_GRAD_OUTPUTS)
+    double* path_t;              // (n_rays, path_stride) each, or all null
+    double* path_x;
+    double* path_z;
+    double* path_vx;
+    double* path_vz;
+    unsigned* status;
+    long long n_rays, n_fields, path_stride;
+    int n0, n1;
+    int renormalize_every;
+    double s_max, rtol, atol, max_step, z_ground, z_max, x_min, x_max;
+    double fill_n, fill_grad, fill_mup;
+};
+#define PRHF_FIELD_MAX_AXES 8000   // n0 + n1 at most: both axes are staged in 64 KiB of LDS
+inline size_t field_axes_lds_bytes(int n0, int n1) { return (size_t)(n0 + n1) * 8; }
+hipError_t launch_field_pack(const FieldPackArgs& a, hipStream_t stream);
+hipError_t launch_field_sample(const FieldSampleArgs& a, hipStream_t stream);
+hipError_t launch_grad_trace(const GradTraceArgs& a, hipStream_t stream);
 
 // residual / cost may be null
 hipError_t launch_residual(const double* vh_model, const double* vh_obs, long long n_prof, int n_freq,

@@ -1,0 +1,387 @@
+"""2-D refractive-index fields and the Cartesian gradient ray tracer on the GPU.
+
+``build_refractive_index_interpolator_cartesian``, ``build_refractive_index_interpolator_spherical`` and
+``build_mup_function`` keep the reference's signatures, defaults and error messages (reference
+``PyRayHF/library.py:1755-2017``) and return callable objects with the reference's call conventions that evaluate on
+the GPU: the grid values live on the device as node records {mu, d mu/d a1, d mu/d a0, mu'} (``prhf_field_pack_f64``:
+``np.gradient`` bit for bit) and a call samples them with ``RegularGridInterpolator``'s linear rule
+(``prhf_field_sample_f64``).  ``refractive_field`` builds the records of many frequencies in one go from the existing
+GPU ``find_mu_mup``.
+
+``trace_ray_cartesian_gradient`` is the reference's single-ray call (``:1270-1457``; the dict lacks ``'sol'``);
+``trace_rays_cartesian_gradient`` / ``trace_fan_cartesian_gradient`` trace a batch / a fan of elevations for every field
+in one launch, one ray per lane (``prhf_trace_gradient_f64``).
+
+Limitations: the tracer reads mu and mu' from ONE set of records, so the ``n_and_grad`` and ``mup_func`` objects given to
+``trace_ray_cartesian_gradient`` must have been built on the same ``z_grid`` and ``x_grid`` (``ValueError`` otherwise),
+and both must come from this module (``TypeError`` otherwise: there is no CPU path).  The spherical gradient tracer is
+not provided: see DESIGN.md section 8.
+"""
+
+from __future__ import annotations
+
+import numpy as np
+
+from . import _native
+from .library import constants, find_mu_mup, find_X, find_Y
+
+__all__ = ["build_refractive_index_interpolator_cartesian", "build_refractive_index_interpolator_spherical",
+           "build_mup_function", "refractive_field", "RefractiveField", "trace_ray_cartesian_gradient",
+           "trace_rays_cartesian_gradient", "trace_fan_cartesian_gradient", "STATUS_NAMES"]
+
+STATUS_NAMES = ("ground", "domain", "length", "failure")          # reference library.py:1391-1398
+_KEYS = ("group_path_km", "group_delay_sec", "x_midpoint", "z_midpoint", "ground_range_km", "x_apex_km", "z_apex_km",
+         "status", "n_nodes", "n_rhs", "n_rejected")
+_INT_KEYS = ("status", "n_nodes", "n_rhs", "n_rejected")
+_PATH_KEYS = ("t", "x", "z", "vx", "vz")
+_MAX_AXES = 8000
+
+
+class RefractiveField:
+    """``F`` fields mu, mu' on one grid: the device-resident node records the sampler and the tracer read.
+
+    ``mu, mup``: ``(F, n0, n1)`` (or ``(n0, n1)``) on ``axis0`` (altitude, or radius) and ``axis1`` (distance, or
+    angle).  The records are packed on first use, so that building a field needs no GPU."""
+
+    def __init__(self, axis0, axis1, mu, mup, *, edge_order=2, device=None, fill_n=np.nan, fill_grad=0.0,
+                 fill_mup=np.nan):
+        self.axis0 = np.ascontiguousarray(axis0, dtype=np.float64)
+        self.axis1 = np.ascontiguousarray(axis1, dtype=np.float64)
+        mu = np.asarray(mu, dtype=np.float64)
+        mup = np.asarray(mup, dtype=np.float64)
+        if mu.ndim == 2:
+            mu, mup = mu[None], mup[None]
+        if mu.ndim != 3 or mu.shape != mup.shape or mu.shape[1:] != (self.axis0.size, self.axis1.size):
+            raise ValueError("mu and mup must have shape (F, len(axis0), len(axis1))")
+        if edge_order not in (1, 2):
+            raise ValueError("'edge_order' greater than 2 not supported")          # np.gradient's message
+        if min(mu.shape[1:]) < edge_order + 1:
+            raise ValueError("Shape of array too small to calculate a numerical gradient, "
+                             "at least (edge_order + 1) elements are required.")
+        if self.axis0.size + self.axis1.size > _MAX_AXES:
+            raise ValueError(f"the two axes hold at most {_MAX_AXES} values together")
+        self.mu = np.ascontiguousarray(mu)
+        self.mup = np.ascontiguousarray(mup)
+        self.edge_order = int(edge_order)
+        self.device = device
+        self.fills = (float(fill_n), float(fill_grad), float(fill_mup))
+        self._rec = None
+
+    @property
+    def n_fields(self):
+        return self.mu.shape[0]
+
+    def _ctx(self):
+        return _native.host_context(self.device)
+
+    def records(self):
+        """The ``(F, n0, n1, 4)`` records as a device tensor (packed on first use)."""
+        if self._rec is None:
+            import torch
+            ctx = self._ctx()
+            rec = torch.empty(self.mu.shape + (4,), dtype=torch.float64, device=f"cuda:{ctx.device}")
+            _native.raise_for(ctx.field_pack(self.mu.ctypes.data, self.mup.ctypes.data, self.n_fields, self.axis0.size,
+                                             self.axis1.size, self.axis0.ctypes.data, self.axis1.ctypes.data,
+                                             self.edge_order, rec.data_ptr(), 0))
+            self._rec = rec
+        return self._rec
+
+    def sample(self, p0, p1, field_index=None, want=(True, True, True, True), fills=None):
+        """mu, d mu/d a1, d mu/d a0, mu' (those asked for, else None) at the points ``(p0, p1)`` (flat arrays)."""
+        p0 = np.ascontiguousarray(p0, dtype=np.float64).reshape(-1)
+        p1 = np.ascontiguousarray(p1, dtype=np.float64).reshape(-1)
+        idx = None
+        if field_index is not None:
+            idx = np.ascontiguousarray(np.broadcast_to(np.asarray(field_index, dtype=np.int64), p0.shape))
+        outs = [np.empty(p0.size, dtype=np.float64) if w else None for w in want]
+        if p0.size:
+            rec = self.records()
+            _native.raise_for(self._ctx().field_sample(
+                rec.data_ptr(), self.n_fields, self.axis0.size, self.axis1.size, self.axis0.ctypes.data,
+                self.axis1.ctypes.data, p0.ctypes.data, p1.ctypes.data, idx.ctypes.data if idx is not None else None,
+                p0.size, self.fills if fills is None else fills, [o.ctypes.data if o is not None else None for o in outs], 0))
+        return outs
+
+    def same_grid(self, other):
+        return np.array_equal(self.axis0, other.axis0) and np.array_equal(self.axis1, other.axis1)
+
+
+def _check_bounds(grids, pts):
+    """``bounds_error=True``: RegularGridInterpolator's test and message."""
+    for i, (g, p) in enumerate(zip(grids, pts)):
+        if not np.logical_and(np.all(g[0] <= p), np.all(p <= g[-1])):
+            raise ValueError("One of the requested xi is out of bounds in dimension %d" % i)
+
+
+class _NAndGrad:
+    """``(x, z) -> (n, dndx, dndz)`` (Cartesian) or ``(phi, r) -> (mu, dmu/dr, dmu/dphi)`` (spherical)."""
+
+    def __init__(self, field, geometry, bounds_error, z_grid, x_grid):
+        self.field = field
+        self.geometry = geometry
+        self.bounds_error = bool(bounds_error)
+        self.z_grid, self.x_grid = z_grid, x_grid
+        self._with_mup = {}
+
+    def __call__(self, first, second):
+        a1 = np.atleast_1d(np.asarray(first, dtype=float))
+        a0 = np.atleast_1d(np.asarray(second, dtype=float))
+        a1, a0 = np.broadcast_arrays(a1, a0)
+        if self.bounds_error:
+            _check_bounds((self.field.axis0, self.field.axis1), (a0.ravel(), a1.ravel()))
+        n, d1, d0, _ = self.field.sample(a0, a1, want=(True, True, True, False))
+        shape = a1.shape
+        if self.geometry == "cartesian":
+            return n.reshape(shape), d1.reshape(shape), d0.reshape(shape)
+        return n.reshape(shape), d0.reshape(shape), d1.reshape(shape)
+
+
+class _MupFunction:
+    """``(x, z) -> mu'``."""
+
+    def __init__(self, field, geometry, bounds_error, R_E, z_grid, x_grid):
+        self.field = field
+        self.geometry = geometry
+        self.bounds_error = bool(bounds_error)
+        self.R_E = R_E
+        self.z_grid, self.x_grid = z_grid, x_grid
+
+    def __call__(self, x, z):
+        if self.geometry == "cartesian":
+            a0, a1 = np.ravel(z), np.ravel(x)
+        else:
+            a0, a1 = (self.R_E + np.asarray(z)).ravel(), (np.asarray(x) / self.R_E).ravel()
+        a0 = np.asarray(a0, dtype=float)
+        a1 = np.asarray(a1, dtype=float)
+        if a0.shape != a1.shape:
+            raise ValueError("x and z must have the same number of elements")
+        if self.bounds_error:
+            _check_bounds((self.field.axis0, self.field.axis1), (a0, a1))
+        mup = self.field.sample(a0, a1, want=(False, False, False, True))[3]
+        return mup.reshape(np.shape(x))
+
+
+def build_refractive_index_interpolator_cartesian(z_grid, x_grid, n_field, *, fill_value_n=np.nan, fill_value_grad=0.0,
+                                                  bounds_error=False, edge_order=2, device=None):
+    """The reference's builder (library.py:1755-1835): a callable ``(x, z) -> (n, dndx, dndz)`` that samples mu and
+    ``np.gradient(n_field, z_grid, x_grid, edge_order=edge_order)`` linearly on the GPU."""
+    z_grid = np.asarray(z_grid, dtype=float)
+    x_grid = np.asarray(x_grid, dtype=float)
+    n_field = np.asarray(n_field, dtype=float)
+    if n_field.shape != (z_grid.size, x_grid.size):
+        raise ValueError(f"`n_field` must have shape (len(z_grid)={z_grid.size}, len(x_grid)={x_grid.size}), "
+                         f"got {n_field.shape}.")
+    if not (np.all(np.diff(z_grid) > 0) and np.all(np.diff(x_grid) > 0)):
+        raise ValueError("`z_grid` and `x_grid` must be strictly increasing.")
+    field = RefractiveField(z_grid, x_grid, n_field, np.full_like(n_field, np.nan), edge_order=edge_order, device=device,
+                            fill_n=fill_value_n, fill_grad=fill_value_grad)
+    return _NAndGrad(field, "cartesian", bounds_error, z_grid, x_grid)
+
+
+def build_refractive_index_interpolator_spherical(z_grid, x_grid, n_field, *, fill_value_n=np.nan, fill_value_grad=0.0,
+                                                  bounds_error=False, R_E=None, edge_order=2, device=None):
+    """The reference's builder (library.py:1838-1927): a callable ``(phi, r) -> (mu, dmu/dr, dmu/dphi)`` on the grid
+    ``r = R_E + z_grid``, ``phi = x_grid / R_E``."""
+    x_grid = np.asarray(x_grid, dtype=float)
+    z_grid = np.asarray(z_grid, dtype=float)
+    n_field = np.asarray(n_field, dtype=float)
+    if R_E is None:
+        R_E = constants()[2]
+    r_grid = R_E + z_grid
+    phi_grid = x_grid / R_E
+    if n_field.shape != (r_grid.size, phi_grid.size):
+        raise ValueError(f"`n_field` shape {n_field.shape} must be "
+                         f"(len(r_grid)={r_grid.size}, len(phi_grid)={phi_grid.size}).")
+    if not (np.all(np.diff(r_grid) > 0) and np.all(np.diff(phi_grid) > 0)):
+        raise ValueError("`r_grid` and `phi_grid` must be strictly increasing.")
+    field = RefractiveField(r_grid, phi_grid, n_field, np.full_like(n_field, np.nan), edge_order=edge_order,
+                            device=device, fill_n=fill_value_n, fill_grad=fill_value_grad)
+    return _NAndGrad(field, "spherical", bounds_error, z_grid, x_grid)
+
+
+def build_mup_function(mup_field, x_grid, z_grid, *, geometry="cartesian", R_E=None, bounds_error=False,
+                       fill_value=np.nan, device=None):
+    """The reference's builder (library.py:1930-2017): a callable ``(x, z) -> mu'`` (both geometries take x and z in km)."""
+    if R_E is None:
+        R_E = constants()[2]
+    if geometry not in ("cartesian", "spherical"):
+        raise ValueError("geometry must be 'cartesian' or 'spherical'")
+    x_grid = np.asarray(x_grid, dtype=float)
+    z_grid = np.asarray(z_grid, dtype=float)
+    mup_field = np.asarray(mup_field, dtype=float)
+    axis0, axis1 = (z_grid, x_grid) if geometry == "cartesian" else (R_E + z_grid, x_grid / R_E)
+    # RegularGridInterpolator's own checks (it is what the reference hands the grids to)
+    for i, g in enumerate((axis0, axis1)):
+        if g.ndim != 1 or not np.all(np.diff(g) > 0):
+            raise ValueError(f"The points in dimension {i} must be strictly ascending")
+    if mup_field.ndim != 2:
+        raise ValueError(f"There are 2 point arrays, but values has {mup_field.ndim} dimensions")
+    for i, g in enumerate((axis0, axis1)):
+        if mup_field.shape[i] != g.size:
+            raise ValueError(f"There are {g.size} points and {mup_field.shape[i]} values in dimension {i}")
+    field = RefractiveField(axis0, axis1, mup_field, mup_field, edge_order=1, device=device, fill_mup=fill_value)
+    return _MupFunction(field, geometry, bounds_error, R_E, z_grid, x_grid)
+
+
+def refractive_field(f0_Hz, Ne, Babs, bpsi, z_grid, x_grid, mode, geometry="cartesian", *, R_E=None, edge_order=2,
+                     fill_value_n=np.nan, fill_value_grad=0.0, fill_value_mup=np.nan, device=None):
+    """``F`` fields for the frequencies ``f0_Hz`` ``(F,)`` from one 2-D ionosphere ``Ne, Babs, bpsi`` ``(nz, nx)``:
+    mu and mu' by the GPU ``find_mu_mup`` (one call per frequency, so that the reference's isotropic rule
+    ``nanmax|Y| < 1e-12`` applies per frequency as it would to that frequency's arrays), then the records.
+    Returns a ``RefractiveField`` on ``(z_grid, x_grid)`` - or ``(R_E + z_grid, x_grid / R_E)`` for
+    ``geometry="spherical"`` - for ``trace_rays_cartesian_gradient`` / ``trace_fan_cartesian_gradient`` and the
+    ``sample`` method."""
+    if mode not in ("O", "X"):
+        raise ValueError("Mode must be O or X")
+    if geometry not in ("cartesian", "spherical"):
+        raise ValueError("geometry must be 'cartesian' or 'spherical'")
+    f = np.atleast_1d(np.asarray(f0_Hz, dtype=np.float64))
+    z_grid = np.asarray(z_grid, dtype=float)
+    x_grid = np.asarray(x_grid, dtype=float)
+    Ne, Babs, bpsi = (np.asarray(v, dtype=np.float64) for v in (Ne, Babs, bpsi))
+    if f.ndim != 1 or not (Ne.shape == Babs.shape == bpsi.shape == (z_grid.size, x_grid.size)):
+        raise ValueError("f0_Hz must be 1-D and Ne, Babs, bpsi of shape (len(z_grid), len(x_grid))")
+    if not (np.all(np.diff(z_grid) > 0) and np.all(np.diff(x_grid) > 0)):
+        raise ValueError("`z_grid` and `x_grid` must be strictly increasing.")
+    mu = np.empty((f.size,) + Ne.shape)
+    mup = np.empty_like(mu)
+    for k, fk in enumerate(f):
+        mu[k], mup[k] = find_mu_mup(find_X(Ne, fk), find_Y(fk, Babs), bpsi, mode, device=device)
+    if geometry == "spherical":
+        if R_E is None:
+            R_E = constants()[2]
+        axis0, axis1 = R_E + z_grid, x_grid / R_E
+    else:
+        axis0, axis1 = z_grid, x_grid
+    return RefractiveField(axis0, axis1, mu, mup, edge_order=edge_order, device=device, fill_n=fill_value_n,
+                           fill_grad=fill_value_grad, fill_mup=fill_value_mup)
+
+
+def _trace(field, x0, z0, elev, idx, controls, return_paths):
+    """Rays in the caller's order; the launch gets them sorted by (field, elevation) so that a wave shares a field and
+    neighbouring lanes take similar numbers of steps.  A lane's result does not depend on its neighbours."""
+    s_max_km, rtol, atol, max_step_km, z_ground_km, z_max_km, x_min_km, x_max_km, renormalize_every = controls
+    max_step = np.inf if max_step_km is None else float(max_step_km)
+    if max_step <= 0:
+        raise ValueError("`max_step` must be positive.")                   # solve_ivp's message
+    n = x0.size
+    if idx is None:
+        if field.n_fields != 1:
+            raise ValueError("field_index is needed when the field holds several frequencies")
+        idx = np.zeros(n, dtype=np.int64)
+    if n and (idx.min() < 0 or idx.max() >= field.n_fields):
+        raise ValueError("field_index outside [0, n_fields)")
+    order = np.lexsort((elev, idx))
+    xs, zs, es, fs = (np.ascontiguousarray(v[order]) for v in (x0, z0, elev, idx))
+    ctl = (s_max_km, rtol, atol, max_step, z_ground_km, z_max_km, x_min_km, x_max_km,
+           int(renormalize_every) if renormalize_every else 0)
+    out = np.empty((n, 12), dtype=np.float64)
+    res = {}
+    if n:
+        rec = field.records()
+        ctx = field._ctx()
+
+        def launch(paths, stride):
+            _native.raise_for(ctx.trace_gradient(
+                rec.data_ptr(), field.n_fields, field.axis0.size, field.axis1.size, field.axis0.ctypes.data,
+                field.axis1.ctypes.data, xs.ctypes.data, zs.ctypes.data, es.ctypes.data, fs.ctypes.data, n, ctl,
+                field.fills, out.ctypes.data, paths, stride, 0))
+        launch(None, 0)
+        if return_paths:
+            # the same rays again, now that the longest path is known: the steps are deterministic
+            stride = int(out[:, 8].max())
+            bufs = [np.empty((n, stride), dtype=np.float64) for _ in _PATH_KEYS]
+            launch([b.ctypes.data for b in bufs], stride)
+            for k, b in zip(_PATH_KEYS, bufs):
+                unsorted = np.empty_like(b)
+                unsorted[order] = b
+                res[k] = unsorted
+    elif return_paths:
+        for k in _PATH_KEYS:
+            res[k] = np.empty((0, 0))
+    back = np.empty_like(out)
+    back[order] = out
+    for i, k in enumerate(_KEYS):
+        res[k] = back[:, i].astype(np.int64) if k in _INT_KEYS else back[:, i].copy()
+    return res
+
+
+def _controls(s_max_km, rtol, atol, max_step_km, z_ground_km, z_max_km, x_min_km, x_max_km, renormalize_every):
+    return (float(s_max_km), float(rtol), float(atol), max_step_km, float(z_ground_km), float(z_max_km), float(x_min_km),
+            float(x_max_km), renormalize_every)
+
+
+def trace_rays_cartesian_gradient(field, x0_km, z0_km, elevation_deg, field_index=None, s_max_km=5000.0, *, rtol=1e-7,
+                                  atol=1e-9, max_step_km=None, z_ground_km=0.0, z_min_km=-1.0, z_max_km=1000.0,
+                                  x_min_km=-1e6, x_max_km=1e6, renormalize_every=50, return_paths=False):
+    """Trace ``R`` rays through ``field`` (a ``RefractiveField``, Cartesian) in one launch; ``x0_km, z0_km,
+    elevation_deg`` and ``field_index`` broadcast to ``(R,)``.  The controls are the reference's (library.py:1278-1291;
+    ``z_min_km`` is accepted and, as there, unused).  Returns a dict of ``(R,)`` arrays: the reference's
+    ``group_path_km, group_delay_sec, x_midpoint, z_midpoint, ground_range_km, x_apex_km, z_apex_km`` and ``status``
+    (index into ``STATUS_NAMES``), ``n_nodes``, ``n_rhs``, ``n_rejected``; with ``return_paths`` also ``t, x, z, vx,
+    vz``: ``(R, max n_nodes)`` padded with NaN."""
+    if not isinstance(field, RefractiveField):
+        raise TypeError("field must be a RefractiveField (refractive_field, or the .field of a builder's callable)")
+    arrs = [np.asarray(v, dtype=np.float64) for v in (x0_km, z0_km, elevation_deg)]
+    if field_index is not None:
+        arrs.append(np.asarray(field_index, dtype=np.int64))
+    arrs = np.broadcast_arrays(*arrs)
+    shape = arrs[0].shape
+    flat = [np.ascontiguousarray(v).reshape(-1) for v in arrs]
+    idx = flat[3] if field_index is not None else None
+    res = _trace(field, flat[0], flat[1], flat[2], idx,
+                 _controls(s_max_km, rtol, atol, max_step_km, z_ground_km, z_max_km, x_min_km, x_max_km, renormalize_every),
+                 return_paths)
+    return {k: v.reshape(shape + v.shape[1:]) for k, v in res.items()}
+
+
+def trace_fan_cartesian_gradient(field, elevation_deg, x0_km=0.0, z0_km=0.0, s_max_km=5000.0, *, rtol=1e-7, atol=1e-9,
+                                 max_step_km=None, z_ground_km=0.0, z_min_km=-1.0, z_max_km=1000.0, x_min_km=-1e6,
+                                 x_max_km=1e6, renormalize_every=50, return_paths=False):
+    """Every elevation of ``elevation_deg`` ``(E,)`` from ``(x0_km, z0_km)`` in every field of ``field``: the dict of
+    ``trace_rays_cartesian_gradient`` with arrays of shape ``(F, E)``, one launch."""
+    e = np.atleast_1d(np.asarray(elevation_deg, dtype=np.float64))
+    if e.ndim != 1:
+        raise ValueError("elevation_deg must be 1-D (the elevations of the fan)")
+    if not isinstance(field, RefractiveField):
+        raise TypeError("field must be a RefractiveField (refractive_field, or the .field of a builder's callable)")
+    idx = np.arange(field.n_fields, dtype=np.int64)[:, None]
+    return trace_rays_cartesian_gradient(field, x0_km, z0_km, e[None, :], idx, s_max_km, rtol=rtol, atol=atol,
+                                         max_step_km=max_step_km, z_ground_km=z_ground_km, z_min_km=z_min_km,
+                                         z_max_km=z_max_km, x_min_km=x_min_km, x_max_km=x_max_km,
+                                         renormalize_every=renormalize_every, return_paths=return_paths)
+
+
+def trace_ray_cartesian_gradient(n_and_grad, mup_func, x0_km, z0_km, elevation_deg, s_max_km=5000.0, *, rtol=1e-7,
+                                 atol=1e-9, max_step_km=None, z_ground_km=0.0, z_min_km=-1.0, z_max_km=1000.0,
+                                 x_min_km=-1e6, x_max_km=1e6, renormalize_every=50):
+    """One ray; the reference's signature and result dict (library.py:1270-1457) without ``'sol'``: ``t, x, z, vx, vz``
+    (path arrays), ``status`` (str), ``group_path_km, group_delay_sec, x_midpoint, z_midpoint, ground_range_km,
+    x_apex_km, z_apex_km``.  ``n_and_grad`` and ``mup_func`` must be the objects this module's builders return, in
+    Cartesian geometry and on the same grids."""
+    if mup_func is None:
+        raise ValueError("mup_func must be provided, build it with build_mup_function.")      # :1349-1351
+    if not isinstance(n_and_grad, _NAndGrad) or not isinstance(mup_func, _MupFunction):
+        raise TypeError("n_and_grad and mup_func must be built with this module's "
+                        "build_refractive_index_interpolator_cartesian and build_mup_function: there is no CPU path")
+    if n_and_grad.geometry != "cartesian" or mup_func.geometry != "cartesian":
+        raise ValueError("trace_ray_cartesian_gradient needs Cartesian n_and_grad and mup_func")
+    if not n_and_grad.field.same_grid(mup_func.field):
+        raise ValueError("n_and_grad and mup_func must be built on the same z_grid and x_grid")
+    field = n_and_grad._with_mup.get(id(mup_func))
+    if field is None or field[0] is not mup_func:
+        nf, mf = n_and_grad.field, mup_func.field
+        merged = RefractiveField(nf.axis0, nf.axis1, nf.mu, mf.mup, edge_order=nf.edge_order, device=nf.device,
+                                 fill_n=nf.fills[0], fill_grad=nf.fills[1], fill_mup=mf.fills[2])
+        n_and_grad._with_mup = {id(mup_func): (mup_func, merged)}
+        field = n_and_grad._with_mup[id(mup_func)]
+    r = trace_rays_cartesian_gradient(field[1], np.float64(x0_km), np.float64(z0_km), np.float64(elevation_deg), None,
+                                      s_max_km, rtol=rtol, atol=atol, max_step_km=max_step_km, z_ground_km=z_ground_km,
+                                      z_min_km=z_min_km, z_max_km=z_max_km, x_min_km=x_min_km, x_max_km=x_max_km,
+                                      renormalize_every=renormalize_every, return_paths=True)
+    n = int(r["n_nodes"])
+    out = {k: r[k][:n].copy() for k in _PATH_KEYS}
+    out["status"] = STATUS_NAMES[int(r["status"])]
+    for k in _KEYS[:7]:
+        out[k] = float(r[k])
+    return out

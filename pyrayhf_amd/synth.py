@@ -86,3 +86,49 @@ def sounder_frequencies(config):
     if config == 5:
         return np.linspace(0.5, 16.0, 512)
     raise ValueError(f"unknown config {config!r}")
+
+
+def _axis(n, lo, hi, uniform, power):
+    """``n`` strictly increasing values from ``lo`` to ``hi``: evenly spaced, or stretched by ``power``."""
+    k = np.arange(n, dtype=np.float64)
+    if uniform:
+        return lo + ((hi - lo) / (n - 1)) * k          # (a step such as 5 or 62.5 km gives exactly equal spacings)
+    return lo + (hi - lo) * (k / (n - 1)) ** power
+
+
+def tilted_ionosphere(nz, nx, tilt, seed, *, uniform=True, z_top_km=600.0, x_half_km=1000.0):
+    """A seeded two-layer (alpha-Chapman F2 + E) ionosphere that varies along x: the inputs of the gradient tracer's
+    fixtures (tests/golden g17, g18).
+
+    Returns ``(z_grid (nz,), x_grid (nx,), Ne, Babs, bpsi)`` with the last three ``(nz, nx)``.  NmF2 grows by
+    ``tilt / 2`` of itself and hmF2 rises by ``40 tilt`` km from the centre of the domain to its right edge (and falls
+    to the left); ``tilt = 0`` gives a horizontally uniform medium whose columns are all the same bits.  ``x_grid`` is
+    symmetric about 0 exactly (``-x_grid[::-1] == x_grid``); with ``uniform=False`` both axes are stretched, so that
+    no two neighbouring spacings are equal.  The draw order is part of the fixture contract.
+    """
+    rng = np.random.default_rng(seed)
+    nmf2 = 10.0 ** rng.uniform(11.95, 12.05)
+    hmf2 = rng.uniform(240.0, 260.0)
+    hf2 = rng.uniform(45.0, 55.0)
+    nme = 10.0 ** rng.uniform(10.9, 11.1)
+    he = rng.uniform(8.0, 10.0)
+    b0 = rng.uniform(3.5e-5, 4.5e-5)
+    psi0 = rng.uniform(40.0, 50.0)
+    z = _axis(nz, 0.0, z_top_km, uniform, 1.5)
+    half = _axis((nx + 1) // 2, 0.0, x_half_km, uniform, 1.3) if nx % 2 else None
+    if half is None:
+        raise ValueError("nx must be odd (the axis is mirrored about its centre node)")
+    x = np.concatenate([-half[:0:-1], half])
+    s = x[None, :] / x_half_km
+    nm = nmf2 * (1.0 + 0.5 * tilt * s)
+    hm = hmf2 + 40.0 * tilt * s
+    zz = z[:, None]
+
+    def chapman(n0, h0, scale):
+        u = (zz - h0) / scale
+        return n0 * np.exp(0.5 * (1.0 - u - np.exp(-u)))
+
+    den = chapman(nm, hm, hf2) + chapman(nme, 110.0, he) * np.ones_like(s)
+    bmag = b0 * (6371.0 / (6371.0 + zz)) ** 3 * np.ones_like(s)
+    bpsi = psi0 + 0.002 * zz + 2.0 * tilt * s
+    return z, x, np.ascontiguousarray(den), np.ascontiguousarray(bmag), np.ascontiguousarray(bpsi)

@@ -33,7 +33,9 @@ extern "C" {
 
 #define PRHF_ABI_VERSION 4   /* 2: + prhf_snell_fan_f64, prhf_recent_kernel_ms, PRHF_FLAG_SHARED_FIELD (round 2)
                               * 3: + prhf_ctx_set_option (round 3)
-                              * 4: + prhf_field_pack_f64, prhf_field_sample_f64, prhf_trace_gradient_f64 */
+                              * 4: + prhf_field_pack_f64, prhf_field_sample_f64, prhf_trace_gradient_f64;
+                              *    prhf_trace_gradient_spherical_f64 joined later without a new number: a new symbol
+                              *    changes nothing for a caller of the others */
 
 /* return codes */
 #define PRHF_OK        0
@@ -359,6 +361,35 @@ int prhf_trace_gradient_f64(prhf_ctx* ctx, const double* records, int64_t n_fiel
                             double x_min_km, double x_max_km, int32_t renormalize_every, double fill_n, double fill_grad,
                             double fill_mup, double* out, double* path_t, double* path_x, double* path_z, double* path_vx,
                             double* path_vz, int64_t path_stride, uint32_t flags);
+
+/*
+ * The same over a spherical Earth: mu(r, phi), n_rays rays in one launch (one per lane).
+ * Replaces: trace_ray_spherical_gradient (reference library.py:2128-2337) with rhs_spherical (:2094-2125), except its
+ * stop conditions: the reference hands the Cartesian event helpers the state [r, phi, v_r, v_phi] (:2239-2243 with
+ * :1009-1031), which tests phi against radii and r against angles, so that none can fire.  The four terminal events
+ * (+ -> -) here are ground r - (earth_radius_km + z_ground_km) - 1e-3, top r_max_km - r, left phi - phi_min, right
+ * phi_max - phi.  records: spherical records of prhf_field_pack_f64 on (r_axis (nr) =
+ * R_E + z, phi_axis (nphi) = x / R_E).  Ray r starts at r = earth_radius_km + z0_km[r], phi = x0_km[r] / earth_radius_km
+ * with (v_r, v_phi) = (sin, cos)(elevation_deg[r]) (:2230-2234).  The system is dr/ds = v_r, dphi/ds = v_phi / r,
+ * dv_r/ds = (mu_r - g v_r) / mu + v_phi^2 / r, dv_phi/ds = (mu_phi / r - g v_phi) / mu - v_r v_phi / r with
+ * g = mu_r v_r + (mu_phi / r) v_phi, zero for a non-finite or non-positive mu; renormalize_every is accepted and, as in
+ * the reference - whose renormalisation rebinds local names after the derivatives are formed -, changes nothing.
+ * Integrator, controller, event location, out (n_rays, 12), status codes, path_stride rule, flags and PRHF_EINVAL rules
+ * are those of prhf_trace_gradient_f64, with x = earth_radius_km * phi and z = r - earth_radius_km in x_midpoint,
+ * z_midpoint, ground_range_km, x_apex_km and z_apex_km; a chord is sqrt(dr^2 + (r_mid dphi)^2) (:2291-2294), mu' is
+ * sampled at (earth_radius_km + z_mid, x_mid / earth_radius_km) of the chord's x and z midpoints (:2299-2301), and the
+ * midpoint is the node searchsorted(cumsum(ds), group_path_km / 2) (:2309-2313; NaN for a path of length 0), the sums
+ * taken in node order.  path_t, path_r, path_phi, path_v_r, path_v_phi (all five or none) receive the reference's 't',
+ * 'r', 'phi', 'v_r', 'v_phi'.  PRHF_EINVAL also for an earth_radius_km that is not positive and finite.  Synchronous.
+ */
+int prhf_trace_gradient_spherical_f64(prhf_ctx* ctx, const double* records, int64_t n_fields, int64_t nr, int64_t nphi,
+                                      const double* r_axis, const double* phi_axis, const double* x0_km,
+                                      const double* z0_km, const double* elevation_deg, const int64_t* ray_field,
+                                      int64_t n_rays, double earth_radius_km, double s_max_km, double rtol, double atol,
+                                      double max_step_km, double z_ground_km, double r_max_km, double phi_min,
+                                      double phi_max, int32_t renormalize_every, double fill_n, double fill_grad,
+                                      double fill_mup, double* out, double* path_t, double* path_r, double* path_phi,
+                                      double* path_v_r, double* path_v_phi, int64_t path_stride, uint32_t flags);
 
 /* Diagnostics: workgroups of the fused kernel the runtime expects to keep resident per CU for
  * profiles of n_alt levels (LDS-limited) in arithmetic tier `math`. */

@@ -14,10 +14,12 @@ __version__ = "0.1.0"
 from .gradient import (STATUS_NAMES, RefractiveField, build_mup_function,                       # noqa: E402
                        build_refractive_index_interpolator_cartesian,
                        build_refractive_index_interpolator_spherical, refractive_field,
-                       trace_fan_cartesian_gradient, trace_ray_cartesian_gradient,
-                       trace_rays_cartesian_gradient)
+                       trace_fan_cartesian_gradient, trace_fan_spherical_gradient,
+                       trace_ray_cartesian_gradient, trace_ray_spherical_gradient,
+                       trace_rays_cartesian_gradient, trace_rays_spherical_gradient)
 
 __all__ = ["logger", "__version__", "STATUS_NAMES", "RefractiveField", "build_mup_function",
            "build_refractive_index_interpolator_cartesian", "build_refractive_index_interpolator_spherical",
-           "refractive_field", "trace_fan_cartesian_gradient", "trace_ray_cartesian_gradient",
-           "trace_rays_cartesian_gradient"]
+           "refractive_field", "trace_fan_cartesian_gradient", "trace_fan_spherical_gradient",
+           "trace_ray_cartesian_gradient", "trace_ray_spherical_gradient", "trace_rays_cartesian_gradient",
+           "trace_rays_spherical_gradient"]

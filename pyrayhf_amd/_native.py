@@ -93,6 +93,10 @@ _PROTOTYPES = {
                                                ctypes.c_int64] + [ctypes.c_void_p] * 6 + [ctypes.c_int64] +
                                 [ctypes.c_double] * 8 + [ctypes.c_int32] + [ctypes.c_double] * 3 +
                                 [ctypes.c_void_p] * 6 + [ctypes.c_int64, ctypes.c_uint32]),
+    "prhf_trace_gradient_spherical_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                                                         ctypes.c_int64] + [ctypes.c_void_p] * 6 + [ctypes.c_int64] +
+                                          [ctypes.c_double] * 9 + [ctypes.c_int32] + [ctypes.c_double] * 3 +
+                                          [ctypes.c_void_p] * 6 + [ctypes.c_int64, ctypes.c_uint32]),
     "prhf_occupancy": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
                                       ctypes.POINTER(ctypes.c_int32)]),
     "prhf_sync": (ctypes.c_int, [ctypes.c_void_p]),
@@ -296,6 +300,17 @@ class Context:
                                                  ray_field or None, n_rays, *(float(v) for v in controls[:8]),
                                                  int(controls[8]), *(float(v) for v in fills), out, *paths,
                                                  int(path_stride), flags)
+
+    def trace_gradient_spherical(self, records, n_fields, nr, nphi, r_axis, phi_axis, x0, z0, elev, ray_field, n_rays,
+                                 earth_radius, controls, fills, out, paths, path_stride, flags):
+        """controls: (s_max_km, rtol, atol, max_step_km, z_ground_km, r_max_km, phi_min, phi_max, renormalize_every);
+        paths: five raw addresses (t, r, phi, v_r, v_phi) or None."""
+        paths = paths or (None,) * 5
+        return self._lib.prhf_trace_gradient_spherical_f64(self._h, records, n_fields, nr, nphi, r_axis, phi_axis, x0, z0,
+                                                           elev, ray_field or None, n_rays, float(earth_radius),
+                                                           *(float(v) for v in controls[:8]), int(controls[8]),
+                                                           *(float(v) for v in fills), out, *paths, int(path_stride),
+                                                           flags)
 
     def occupancy(self, n_alt, math):
         n = ctypes.c_int32(0)

@@ -1717,13 +1717,15 @@ int prhf_field_sample_f64(prhf_ctx* c, const double* records, int64_t n_fields, 
     return prhf_sync(c);
 }
 
-int prhf_trace_gradient_f64(prhf_ctx* c, const double* records, int64_t n_fields, int64_t nz, int64_t nx,
-                            const double* z_axis, const double* x_axis, const double* x0_km, const double* z0_km,
-                            const double* elevation_deg, const int64_t* ray_field, int64_t n_rays, double s_max_km,
-                            double rtol, double atol, double max_step_km, double z_ground_km, double z_max_km,
-                            double x_min_km, double x_max_km, int32_t renormalize_every, double fill_n, double fill_grad,
-                            double fill_mup, double* out, double* path_t, double* path_x, double* path_z, double* path_vx,
-                            double* path_vz, int64_t path_stride, uint32_t flags) {
+namespace {
+// Both gradient tracers.  Spherical (geometry PRHF_GEO_SPHERICAL): the axes are r and phi, z_ground_km .. x_max_km carry
+// R_E + z_ground_km, r_max_km, phi_min, phi_max and the paths are t, r, phi, v_r, v_phi.
+int grad_trace_run(prhf_ctx* c, int geometry, double earth_radius_km, const double* records, int64_t n_fields, int64_t nz,
+                   int64_t nx, const double* z_axis, const double* x_axis, const double* x0_km, const double* z0_km,
+                   const double* elevation_deg, const int64_t* ray_field, int64_t n_rays, double s_max_km, double rtol,
+                   double atol, double max_step_km, double z_ground_km, double z_max_km, double x_min_km, double x_max_km,
+                   int32_t renormalize_every, double fill_n, double fill_grad, double fill_mup, double* out, double* path_t,
+                   double* path_x, double* path_z, double* path_vx, double* path_vz, int64_t path_stride, uint32_t flags) {
     if (!c) return fail(PRHF_EINVAL, "null context");
     if (!records || !x0_km || !z0_km || !elevation_deg || !out) return fail(PRHF_EINVAL, "null array pointer");
     if (n_rays < 0) return fail(PRHF_EINVAL, "bad shape");
@@ -1760,6 +1762,7 @@ int prhf_trace_gradient_f64(prhf_ctx* c, const double* records, int64_t n_fields
     a.atol = atol; a.max_step = max_step_km; a.z_ground = z_ground_km; a.z_max = z_max_km;
     a.x_min = x_min_km; a.x_max = x_max_km; a.renormalize_every = renormalize_every;
     a.fill_n = fill_n; a.fill_grad = fill_grad; a.fill_mup = fill_mup; a.status = c->h_status_dev;
+    a.geometry = geometry; a.earth_radius = earth_radius_km;
     double* host_paths[5] = {path_t, path_x, path_z, path_vx, path_vz};
     double* d_paths[5] = {path_t, path_x, path_z, path_vx, path_vz};
     if (dev) {
@@ -1790,6 +1793,38 @@ int prhf_trace_gradient_f64(prhf_ctx* c, const double* records, int64_t n_fields
             HIP_TRY(hipMemcpyAsync(host_paths[k], d_paths[k], path_elems * 8, hipMemcpyDeviceToHost, c->stream));
     }
     return prhf_sync(c);
+}
+}  // namespace
+
+int prhf_trace_gradient_f64(prhf_ctx* c, const double* records, int64_t n_fields, int64_t nz, int64_t nx,
+                            const double* z_axis, const double* x_axis, const double* x0_km, const double* z0_km,
+                            const double* elevation_deg, const int64_t* ray_field, int64_t n_rays, double s_max_km,
+                            double rtol, double atol, double max_step_km, double z_ground_km, double z_max_km,
+                            double x_min_km, double x_max_km, int32_t renormalize_every, double fill_n, double fill_grad,
+                            double fill_mup, double* out, double* path_t, double* path_x, double* path_z, double* path_vx,
+                            double* path_vz, int64_t path_stride, uint32_t flags) {
+    return grad_trace_run(c, PRHF_GEO_CARTESIAN, 0.0, records, n_fields, nz, nx, z_axis, x_axis, x0_km, z0_km, elevation_deg,
+                          ray_field, n_rays, s_max_km, rtol, atol, max_step_km, z_ground_km, z_max_km, x_min_km, x_max_km,
+                          renormalize_every, fill_n, fill_grad, fill_mup, out, path_t, path_x, path_z, path_vx, path_vz,
+                          path_stride, flags);
+}
+
+int prhf_trace_gradient_spherical_f64(prhf_ctx* c, const double* records, int64_t n_fields, int64_t nr, int64_t nphi,
+                                      const double* r_axis, const double* phi_axis, const double* x0_km,
+                                      const double* z0_km, const double* elevation_deg, const int64_t* ray_field,
+                                      int64_t n_rays, double earth_radius_km, double s_max_km, double rtol, double atol,
+                                      double max_step_km, double z_ground_km, double r_max_km, double phi_min,
+                                      double phi_max, int32_t renormalize_every, double fill_n, double fill_grad,
+                                      double fill_mup, double* out, double* path_t, double* path_r, double* path_phi,
+                                      double* path_v_r, double* path_v_phi, int64_t path_stride, uint32_t flags) {
+    if (!c) return fail(PRHF_EINVAL, "null context");
+    if (!(earth_radius_km > 0) || !std::isfinite(earth_radius_km))
+        return fail(PRHF_EINVAL, "earth_radius_km must be positive and finite");
+    // (the reference binds R_E + z_ground_km to the ground event before it subtracts, :2240)
+    return grad_trace_run(c, PRHF_GEO_SPHERICAL, earth_radius_km, records, n_fields, nr, nphi, r_axis, phi_axis, x0_km, z0_km,
+                          elevation_deg, ray_field, n_rays, s_max_km, rtol, atol, max_step_km, earth_radius_km + z_ground_km,
+                          r_max_km, phi_min, phi_max, renormalize_every, fill_n, fill_grad, fill_mup, out, path_t, path_r,
+                          path_phi, path_v_r, path_v_phi, path_stride, flags);
 }
 
 int prhf_occupancy(prhf_ctx* c, int64_t n_alt, int32_t math, int32_t* workgroups_per_cu) {

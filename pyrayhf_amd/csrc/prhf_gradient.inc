@@ -1,9 +1,10 @@
-// prhf_gradient.inc - 2-D refractive-index fields mu(a0, a1) and the Cartesian gradient ray tracer.
+// prhf_gradient.inc - 2-D refractive-index fields mu(a0, a1) and the gradient ray tracers of both geometries.
 // Included by prhf_kernels.hip inside namespace prhf.
 //
 // Replaces: build_refractive_index_interpolator_cartesian / _spherical (reference PyRayHF/library.py:1755-1927),
-// build_mup_function (:1930-2017), ray_rhs_cartesian (:953-1006), the event helpers (:1009-1031) and
-// trace_ray_cartesian_gradient (:1270-1457).  Line numbers below are that file.
+// build_mup_function (:1930-2017), ray_rhs_cartesian (:953-1006), the event helpers (:1009-1031),
+// trace_ray_cartesian_gradient (:1270-1457), rhs_spherical (:2094-2125) and trace_ray_spherical_gradient (:2128-2337,
+// with the stop conditions of DESIGN.md section 4.7).  Line numbers below are that file.
 //
 // FIELD RECORDS (field_pack_kernel): node (f, i0, i1) of a field is four doubles {mu, d mu/d a1, d mu/d a0, mu'}, the
 // derivatives np.gradient(mu, a0, a1, edge_order) in NumPy's formulas and operation order (IEEE + - x /, no
@@ -14,10 +15,13 @@
 // (v - g[i]) / (g[i + 1] - g[i]), the four products formed left to right and added left to right (a NaN corner
 // poisons the sum at weight 0), fill values outside the hull, NaN for a NaN coordinate.
 //
-// TRACER (grad_trace_kernel): one ray per lane.  Dormand-Prince 5(4) with the step controller that
-// scipy.integrate.solve_ivp(method="RK45") documents; the state y = (x, z, vx, vz), the seven stage vectors and the
-// controller live in registers, accept / reject is per lane and a wave loops until a ballot shows no active lane.
-// The two axes are staged in LDS; a lane remembers its last cell and hunts +-1 from it before it searches.
+// TRACER (grad_trace_kernel<GEO>): one ray per lane.  Dormand-Prince 5(4) with the step controller that
+// scipy.integrate.solve_ivp(method="RK45") documents; the state y = (x, z, vx, vz) - (r, phi, v_r, v_phi) for
+// GEO = PRHF_GEO_SPHERICAL -, the seven stage vectors and the controller live in registers, accept / reject is per lane
+// and a wave loops until a ballot shows no active lane.  The two axes are staged in LDS; a lane remembers its last cell
+// and hunts +-1 from it before it searches.  The geometry is a template parameter: the spherical instantiation differs
+// in the right-hand side, in the state component an event looks at, in a chord's length, in the point mu' is sampled
+// at and in the midpoint rule; stepper, controller, event location and path writer are shared text.
 
 namespace {
 
@@ -179,12 +183,17 @@ struct GradLane {
     unsigned n_rhs;     // all RHS calls
 };
 
-// ray_rhs_cartesian (:983-1006) on the sampled field: y = (x, z, vx, vz)
+// The right-hand side on the sampled field.  Cartesian: ray_rhs_cartesian (:983-1006), y = (x, z, vx, vz).
+// Spherical: rhs_spherical (:2094-2125), y = (r, phi, v_r, v_phi), records on (r, phi) axes, so that slot 1 is
+// d mu / d phi and slot 2 d mu / d r.
+template <int GEO>
 __device__ __forceinline__ void grad_rhs(const GradTraceArgs& a, const double* g0, const double* g1, GradLane& L, double x,
                                          double z, double vx, double vz, double& k0, double& k1, double& k2, double& k3) {
     ++L.n_rhs;
     double n, dndx, dndz, y0 = 0, y1 = 0;
-    const int where = field_locate(g0, a.n0, g1, a.n1, z, x, L.c0, L.c1, y0, y1);
+    // (a spherical state's first component runs along axis 0, a Cartesian state's second)
+    const int where = GEO == PRHF_GEO_SPHERICAL ? field_locate(g0, a.n0, g1, a.n1, x, z, L.c0, L.c1, y0, y1)
+                                                : field_locate(g0, a.n0, g1, a.n1, z, x, L.c0, L.c1, y0, y1);
     if (where == 0) {
         FieldCorners q;
         field_corners<true, true>(a.rec, L.f, a.n0, a.n1, L.c0, L.c1, q);
@@ -198,6 +207,17 @@ __device__ __forceinline__ void grad_rhs(const GradTraceArgs& a, const double* g
     }
     if (!(fabs(n) < __builtin_inf()) || n <= 0.0) {      // :986-987
         k0 = k1 = k2 = k3 = 0.0;
+        return;
+    }
+    if (GEO == PRHF_GEO_SPHERICAL) {
+        // :2106-2114 with r = x, v_r = vx, v_phi = vz, mu_phi = dndx, mu_r = dndz.  The reference's renormalisation
+        // (:2117-2122) rebinds its local v_r and v_phi after the four derivatives have been formed from the old ones:
+        // it changes nothing in the vector it returns, so there is nothing to do here on any call.
+        const double r = x, gv = dndz * vx + (dndx / r) * vz;
+        k0 = vx;
+        k1 = vz / r;
+        k2 = (dndz - gv * vx) / n + (vz * vz) / r;
+        k3 = ((dndx / r) - gv * vz) / n - (vx * vz) / r;
         return;
     }
     double dxds = vx, dzds = vz;
@@ -218,11 +238,11 @@ __device__ __forceinline__ void grad_rhs(const GradTraceArgs& a, const double* g
     k0 = dxds; k1 = dzds; k2 = dvx; k3 = dvz;
 }
 
-// mu' at a chord's midpoint (:1419-1424)
-__device__ __forceinline__ double grad_mup(const GradTraceArgs& a, const double* g0, const double* g1, GradLane& L, double x, double z) {
+// mu' at the point (p0, p1) along (axis 0, axis 1): a chord's midpoint (:1419-1424, :2299-2301)
+__device__ __forceinline__ double grad_mup(const GradTraceArgs& a, const double* g0, const double* g1, GradLane& L, double p0, double p1) {
     double y0 = 0, y1 = 0;
     int c0 = L.c0, c1 = L.c1;
-    const int where = field_locate(g0, a.n0, g1, a.n1, z, x, c0, c1, y0, y1);
+    const int where = field_locate(g0, a.n0, g1, a.n1, p0, p1, c0, c1, y0, y1);
     if (where == 1) return a.fill_mup;
     if (where == 2) return qnan();
     FieldCorners q;
@@ -282,7 +302,9 @@ __device__ __forceinline__ double dp_dense(const double (&q)[4], double y_old, d
 }
 
 // Event functions (:1009-1031 as trace_ray_cartesian_gradient wires them, :1370-1373): 0 ground (with its 1e-3 km
-// offset), 1 top, 2 left, 3 right; all terminal, direction + -> -.  EV & 2: the event looks at x, else at z.
+// offset), 1 top, 2 left, 3 right; all terminal, direction + -> -.  EV & 2: the event looks at x, else at z.  A
+// spherical launch carries R_E + z_ground_km, r_max_km, phi_min and phi_max in the same four places, and events 0 and 1
+// look at r, 2 and 3 at phi (DESIGN.md section 4.7; the reference's own wiring, :2239-2243, tests phi against radii).
 template <int EV>
 __device__ __forceinline__ double grad_event(const GradTraceArgs& a, double v) {
     if (EV == 0) return v - a.z_ground - 1e-3;
@@ -311,7 +333,9 @@ __device__ __forceinline__ double grad_event_root(const GradTraceArgs& a, const 
 
 #define PRHF_GRAD_MAX_ATTEMPTS (1 << 24)     // steps a lane may attempt before it gives up with status "failure"
 
+template <int GEO>
 __global__ __launch_bounds__(PRHF_GRAD_TRACE_THREADS) void grad_trace_kernel(const GradTraceArgs a) {
+    constexpr bool SPH = GEO == PRHF_GEO_SPHERICAL;
     extern __shared__ __attribute__((aligned(16))) double grad_axes[];
     const double* g0 = grad_axes;
     const double* g1 = grad_axes + a.n0;
@@ -327,27 +351,33 @@ __global__ __launch_bounds__(PRHF_GRAD_TRACE_THREADS) void grad_trace_kernel(con
         for (int k = 0; k < PRHF_GRAD_OUTPUTS; ++k) out[k] = qnan();
         return;
     }
-    // :1354-1357
+    // :1354-1357; :2230-2234: (r, phi, v_r, v_phi) = (R_E + z0, x0 / R_E, sin, cos), not normalised
     const double elev = a.elev[r] * (3.141592653589793 / 180.0);
     const double vx0 = cos(elev), vz0 = sin(elev), vnorm = hypot(vx0, vz0);
-    const double xs = a.x0[r], zs = a.z0[r], vxs = vx0 / vnorm, vzs = vz0 / vnorm;
+    const double xs = SPH ? a.earth_radius + a.z0[r] : a.x0[r], zs = SPH ? a.x0[r] / a.earth_radius : a.z0[r],
+                 vxs = SPH ? vz0 : vx0 / vnorm, vzs = SPH ? vx0 : vz0 / vnorm;
 
-    // results of pass 0
-    double path_km = 0.0, delay = 0.0, x_apex = xs, z_apex = zs, x_last = xs;
-    double x_mid = xs, z_mid = zs;
+    // results of pass 0 (x and z of a spherical node: R_E phi and r - R_E, :2277-2278)
+    double path_km = 0.0, delay = 0.0, x_apex = SPH ? a.earth_radius * zs : xs, z_apex = SPH ? xs - a.earth_radius : zs,
+           x_last = x_apex;
+    double x_mid = SPH ? qnan() : xs, z_mid = SPH ? qnan() : zs;
     int n_nodes = 1, status = 3, n_rej = 0;
     unsigned n_rhs = 0;
     bool too_long = false;
 
     // pass 0: the ray.  pass 1: the same steps again up to node n_nodes / 2 (:1428-1430), which no lane can know
-    // before its ray has ended and which is not kept anywhere unless the caller asked for the path.
+    // before its ray has ended and which is not kept anywhere unless the caller asked for the path.  Spherical
+    // (:2309-2313): up to node searchsorted(cumsum(ds), path / 2), the start of the first chord at whose end the lane's
+    // own running sum - the one that gave path_km - reaches half of it; no midpoint (NaN) for a path of length 0.
 #pragma nounroll
     for (int pass = 0; pass < 2; ++pass) {
-        const int target = pass == 0 ? 0x7fffffff : n_nodes / 2;
+        const int target = (pass == 0 || SPH) ? 0x7fffffff : n_nodes / 2;
+        const double half_km = 0.5 * path_km;
+        double cum_km = 0.0;
         L.c0 = L.c1 = 0; L.valid = 0; L.n_rhs = 0;
         double t = 0.0, y0 = xs, y1 = zs, y2 = vxs, y3 = vzs;
         double ka0, ka1, ka2, ka3;          // K1: f(t, y), first same as last
-        grad_rhs(a, g0, g1, L, y0, y1, y2, y3, ka0, ka1, ka2, ka3);
+        grad_rhs<GEO>(a, g0, g1, L, y0, y1, y2, y3, ka0, ka1, ka2, ka3);
         double h_abs;
         {   // the initial step (Hairer, Norsett & Wanner II.4, as solve_ivp applies it; error order 4)
             const double s0 = a.atol + fabs(y0) * a.rtol, s1 = a.atol + fabs(y1) * a.rtol, s2 = a.atol + fabs(y2) * a.rtol,
@@ -357,7 +387,7 @@ __global__ __launch_bounds__(PRHF_GRAD_TRACE_THREADS) void grad_trace_kernel(con
             double h0 = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1;
             h0 = py_min(h0, a.s_max);
             double f0, f1, f2, f3;
-            grad_rhs(a, g0, g1, L, y0 + h0 * ka0, y1 + h0 * ka1, y2 + h0 * ka2, y3 + h0 * ka3, f0, f1, f2, f3);
+            grad_rhs<GEO>(a, g0, g1, L, y0 + h0 * ka0, y1 + h0 * ka1, y2 + h0 * ka2, y3 + h0 * ka3, f0, f1, f2, f3);
             const double e0 = (f0 - ka0) / s0, e1 = (f1 - ka1) / s1, e2 = (f2 - ka2) / s2, e3 = (f3 - ka3) / s3;
             const double d2 = sqrt(e0 * e0 + e1 * e1 + e2 * e2 + e3 * e3) / 2.0 / h0;
             double h1;
@@ -366,9 +396,9 @@ __global__ __launch_bounds__(PRHF_GRAD_TRACE_THREADS) void grad_trace_kernel(con
             h_abs = py_min(py_min(py_min(100 * h0, h1), a.s_max), a.max_step);
         }
         int nodes = 1, attempts = 0;
-        bool active = nodes <= target, new_step = true, rejected = false;
+        bool active = nodes <= target && !(SPH && pass == 1 && !(path_km > 0.0)), new_step = true, rejected = false;
         double min_step = 0.0;
-        if (!active) { x_mid = y0; z_mid = y1; }          // (target 0: the launch point)
+        if (!SPH && !active) { x_mid = y0; z_mid = y1; }          // (target 0: the launch point)
         if (pass == 0 && a.path_t) {
             if (a.path_stride > 0) {
                 const long long o = r * a.path_stride;
@@ -394,19 +424,19 @@ __global__ __launch_bounds__(PRHF_GRAD_TRACE_THREADS) void grad_trace_kernel(con
                     h_abs = fabs(h);
                     double kb0, kb1, kb2, kb3, kc0, kc1, kc2, kc3, kd0, kd1, kd2, kd3, ke0, ke1, ke2, ke3, kf0, kf1, kf2, kf3,
                            kg0, kg1, kg2, kg3;
-                    grad_rhs(a, g0, g1, L, y0 + (DP_A21 * ka0) * h, y1 + (DP_A21 * ka1) * h, y2 + (DP_A21 * ka2) * h,
+                    grad_rhs<GEO>(a, g0, g1, L, y0 + (DP_A21 * ka0) * h, y1 + (DP_A21 * ka1) * h, y2 + (DP_A21 * ka2) * h,
                              y3 + (DP_A21 * ka3) * h, kb0, kb1, kb2, kb3);
-                    grad_rhs(a, g0, g1, L, y0 + (DP_A31 * ka0 + DP_A32 * kb0) * h, y1 + (DP_A31 * ka1 + DP_A32 * kb1) * h,
+                    grad_rhs<GEO>(a, g0, g1, L, y0 + (DP_A31 * ka0 + DP_A32 * kb0) * h, y1 + (DP_A31 * ka1 + DP_A32 * kb1) * h,
                              y2 + (DP_A31 * ka2 + DP_A32 * kb2) * h, y3 + (DP_A31 * ka3 + DP_A32 * kb3) * h, kc0, kc1, kc2, kc3);
-                    grad_rhs(a, g0, g1, L, y0 + (DP_A41 * ka0 + DP_A42 * kb0 + DP_A43 * kc0) * h,
+                    grad_rhs<GEO>(a, g0, g1, L, y0 + (DP_A41 * ka0 + DP_A42 * kb0 + DP_A43 * kc0) * h,
                              y1 + (DP_A41 * ka1 + DP_A42 * kb1 + DP_A43 * kc1) * h,
                              y2 + (DP_A41 * ka2 + DP_A42 * kb2 + DP_A43 * kc2) * h,
                              y3 + (DP_A41 * ka3 + DP_A42 * kb3 + DP_A43 * kc3) * h, kd0, kd1, kd2, kd3);
-                    grad_rhs(a, g0, g1, L, y0 + (DP_A51 * ka0 + DP_A52 * kb0 + DP_A53 * kc0 + DP_A54 * kd0) * h,
+                    grad_rhs<GEO>(a, g0, g1, L, y0 + (DP_A51 * ka0 + DP_A52 * kb0 + DP_A53 * kc0 + DP_A54 * kd0) * h,
                              y1 + (DP_A51 * ka1 + DP_A52 * kb1 + DP_A53 * kc1 + DP_A54 * kd1) * h,
                              y2 + (DP_A51 * ka2 + DP_A52 * kb2 + DP_A53 * kc2 + DP_A54 * kd2) * h,
                              y3 + (DP_A51 * ka3 + DP_A52 * kb3 + DP_A53 * kc3 + DP_A54 * kd3) * h, ke0, ke1, ke2, ke3);
-                    grad_rhs(a, g0, g1, L, y0 + (DP_A61 * ka0 + DP_A62 * kb0 + DP_A63 * kc0 + DP_A64 * kd0 + DP_A65 * ke0) * h,
+                    grad_rhs<GEO>(a, g0, g1, L, y0 + (DP_A61 * ka0 + DP_A62 * kb0 + DP_A63 * kc0 + DP_A64 * kd0 + DP_A65 * ke0) * h,
                              y1 + (DP_A61 * ka1 + DP_A62 * kb1 + DP_A63 * kc1 + DP_A64 * kd1 + DP_A65 * ke1) * h,
                              y2 + (DP_A61 * ka2 + DP_A62 * kb2 + DP_A63 * kc2 + DP_A64 * kd2 + DP_A65 * ke2) * h,
                              y3 + (DP_A61 * ka3 + DP_A62 * kb3 + DP_A63 * kc3 + DP_A64 * kd3 + DP_A65 * ke3) * h, kf0, kf1, kf2, kf3);
@@ -415,7 +445,7 @@ __global__ __launch_bounds__(PRHF_GRAD_TRACE_THREADS) void grad_trace_kernel(con
                     const double n1 = y1 + h * (DP_B1 * ka1 + 0.0 * kb1 + DP_B3 * kc1 + DP_B4 * kd1 + DP_B5 * ke1 + DP_B6 * kf1);
                     const double n2 = y2 + h * (DP_B1 * ka2 + 0.0 * kb2 + DP_B3 * kc2 + DP_B4 * kd2 + DP_B5 * ke2 + DP_B6 * kf2);
                     const double n3 = y3 + h * (DP_B1 * ka3 + 0.0 * kb3 + DP_B3 * kc3 + DP_B4 * kd3 + DP_B5 * ke3 + DP_B6 * kf3);
-                    grad_rhs(a, g0, g1, L, n0, n1, n2, n3, kg0, kg1, kg2, kg3);
+                    grad_rhs<GEO>(a, g0, g1, L, n0, n1, n2, n3, kg0, kg1, kg2, kg3);
                     const double r0 = (DP_E1 * ka0 + 0.0 * kb0 + DP_E3 * kc0 + DP_E4 * kd0 + DP_E5 * ke0 + DP_E6 * kf0 + DP_E7 * kg0) * h /
                                       (a.atol + np_maximum(fabs(y0), fabs(n0)) * a.rtol);
                     const double r1 = (DP_E1 * ka1 + 0.0 * kb1 + DP_E3 * kc1 + DP_E4 * kd1 + DP_E5 * ke1 + DP_E6 * kf1 + DP_E7 * kg1) * h /
@@ -425,41 +455,55 @@ __global__ __launch_bounds__(PRHF_GRAD_TRACE_THREADS) void grad_trace_kernel(con
                     const double r3 = (DP_E1 * ka3 + 0.0 * kb3 + DP_E3 * kc3 + DP_E4 * kd3 + DP_E5 * ke3 + DP_E6 * kf3 + DP_E7 * kg3) * h /
                                       (a.atol + np_maximum(fabs(y3), fabs(n3)) * a.rtol);
                     const double err = sqrt(r0 * r0 + r1 * r1 + r2 * r2 + r3 * r3) / 2.0;
-                    if (err < 1.0) {
+                    // Spherical only: r = R_E + z resolves 9e-13 km, more than the 10 ulp of s below which a step counts
+                    // as failed while s < 1024 km.  A ray that meets the underside of the NaN cap comes to rest one ulp
+                    // of r below it: a step that would move r is rejected on the NaN beyond, a shorter one is accepted and
+                    // moves nothing but s and phi, 1e-12 km at a time (the reference does just that, to no end).  A step
+                    // short of s_max that would be accepted and leaves r where it was although dr/ds is not zero is
+                    // below the resolution of the state as well: status "failure", no node (DESIGN.md section 4.7).
+                    const bool stalled = SPH && err < 1.0 && n0 == y0 && ka0 != 0.0 && t_new - a.s_max < 0;
+                    if (stalled) {
+                        active = false;
+                        if (pass == 0) status = 3;
+                    } else if (err < 1.0) {
                         double factor = err == 0.0 ? 10.0 : py_min(10.0, 0.9 * pow(err, -0.2));
                         if (rejected) factor = py_min(1.0, factor);
                         h_abs *= factor;
                         // the node this step ends on: (t_new, y_new), or the first terminal event on the way
                         double tn = t_new, e0 = n0, e1 = n1, e2 = n2, e3 = n3;
                         int ended = -1;                      // 0 ground, 1 domain, 2 length
-                        const double ga0 = grad_event<0>(a, y1), gb0 = grad_event<0>(a, n1);
-                        const double ga1 = grad_event<1>(a, y1), gb1 = grad_event<1>(a, n1);
-                        const double ga2 = grad_event<2>(a, y0), gb2 = grad_event<2>(a, n0);
-                        const double ga3 = grad_event<3>(a, y0), gb3 = grad_event<3>(a, n0);
+                        // the component the ground and top events look at, and the one left and right look at
+                        const double yv = SPH ? y0 : y1, nv = SPH ? n0 : n1, yh = SPH ? y1 : y0, nh = SPH ? n1 : n0;
+                        const double ga0 = grad_event<0>(a, yv), gb0 = grad_event<0>(a, nv);
+                        const double ga1 = grad_event<1>(a, yv), gb1 = grad_event<1>(a, nv);
+                        const double ga2 = grad_event<2>(a, yh), gb2 = grad_event<2>(a, nh);
+                        const double ga3 = grad_event<3>(a, yh), gb3 = grad_event<3>(a, nh);
                         const bool hit0 = ga0 >= 0 && gb0 <= 0, hit1 = ga1 >= 0 && gb1 <= 0, hit2 = ga2 >= 0 && gb2 <= 0,
                                    hit3 = ga3 >= 0 && gb3 <= 0;
                         if (hit0 || hit1 || hit2 || hit3) {
-                            double qx[4], qz[4];
-                            dp_dense_row(ka0, kc0, kd0, ke0, kf0, kg0, qx);
-                            dp_dense_row(ka1, kc1, kd1, ke1, kf1, kg1, qz);
+                            double q0[4], q1[4];
+                            dp_dense_row(ka0, kc0, kd0, ke0, kf0, kg0, q0);
+                            dp_dense_row(ka1, kc1, kd1, ke1, kf1, kg1, q1);
+                            const double(&qz)[4] = SPH ? q0 : q1;
+                            const double(&qx)[4] = SPH ? q1 : q0;
                             double root = __builtin_inf();
-                            if (hit0) { root = grad_event_root<0>(a, qz, y1, t, h, t_new, ga0, gb0); ended = 0; }
+                            if (hit0) { root = grad_event_root<0>(a, qz, yv, t, h, t_new, ga0, gb0); ended = 0; }
                             if (hit1) {
-                                const double s = grad_event_root<1>(a, qz, y1, t, h, t_new, ga1, gb1);
+                                const double s = grad_event_root<1>(a, qz, yv, t, h, t_new, ga1, gb1);
                                 if (s < root) { root = s; ended = 1; }
                             }
                             if (hit2) {
-                                const double s = grad_event_root<2>(a, qx, y0, t, h, t_new, ga2, gb2);
+                                const double s = grad_event_root<2>(a, qx, yh, t, h, t_new, ga2, gb2);
                                 if (s < root) { root = s; ended = 1; }
                             }
                             if (hit3) {
-                                const double s = grad_event_root<3>(a, qx, y0, t, h, t_new, ga3, gb3);
+                                const double s = grad_event_root<3>(a, qx, yh, t, h, t_new, ga3, gb3);
                                 if (s < root) { root = s; ended = 1; }
                             }
                             double qv[4];
                             tn = root;
-                            e0 = dp_dense(qx, y0, t, h, root);
-                            e1 = dp_dense(qz, y1, t, h, root);
+                            e0 = dp_dense(q0, y0, t, h, root);
+                            e1 = dp_dense(q1, y1, t, h, root);
                             dp_dense_row(ka2, kc2, kd2, ke2, kf2, kg2, qv);
                             e2 = dp_dense(qv, y2, t, h, root);
                             dp_dense_row(ka3, kc3, kd3, ke3, kf3, kg3, qv);
@@ -469,20 +513,42 @@ __global__ __launch_bounds__(PRHF_GRAD_TRACE_THREADS) void grad_trace_kernel(con
                         }
                         // solve_ivp does not append an event node that coincides with the node before it
                         if (!(ended >= 0 && ended < 2 && tn == t && nodes > 1)) {
+                            double ds = 0.0;                 // the chord to this node (the spherical replay needs it too)
+                            if (SPH) {                       // :2291-2294
+                                const double dr = e0 - y0, rdphi = (0.5 * (y0 + e0)) * (e1 - y1);
+                                ds = sqrt(dr * dr + rdphi * rdphi);
+                            } else if (pass == 0) {
+                                ds = hypot(e0 - y0, e1 - y1);                                 // :1413-1415
+                            }
                             if (pass == 0) {
-                                const double ds = hypot(e0 - y0, e1 - y1);                    // :1413-1415
+                                // this node's x and z
+                                const double ex = SPH ? a.earth_radius * e1 : e0, ez = SPH ? e0 - a.earth_radius : e1;
                                 if (ds == ds) {
                                     path_km += ds;
-                                    const double mup = grad_mup(a, g0, g1, L, 0.5 * (y0 + e0), 0.5 * (y1 + e1));
+                                    double mup;
+                                    if (SPH) {
+                                        // :2299-2301 and build_mup_function's way back to (r, phi) (:2009-2010): the
+                                        // midpoints of the x and z paths, not of r and phi
+                                        const double xm = 0.5 * (a.earth_radius * y1 + ex), zm = 0.5 * ((y0 - a.earth_radius) + ez);
+                                        mup = grad_mup(a, g0, g1, L, a.earth_radius + zm, xm / a.earth_radius);
+                                    } else {
+                                        mup = grad_mup(a, g0, g1, L, 0.5 * (y1 + e1), 0.5 * (y0 + e0));
+                                    }
                                     if (fabs(mup) < __builtin_inf()) delay += (mup / 299792.458) * ds;      // :1418-1425
                                 }
-                                if (e1 > z_apex) { z_apex = e1; x_apex = e0; }                 // np.nanargmax: the first maximum
-                                x_last = e0;
+                                if (ez > z_apex) { z_apex = ez; x_apex = ex; }                 // np.nanargmax: the first maximum
+                                x_last = ex;
                                 if (a.path_t) {
                                     if (nodes < a.path_stride) {
                                         const long long o = r * a.path_stride + nodes;
                                         a.path_t[o] = tn; a.path_x[o] = e0; a.path_z[o] = e1; a.path_vx[o] = e2; a.path_vz[o] = e3;
                                     } else too_long = true;
+                                }
+                            } else if (SPH) {
+                                if (ds == ds) cum_km += ds;
+                                if (cum_km >= half_km) {      // the chord's first node
+                                    x_mid = a.earth_radius * y1; z_mid = y0 - a.earth_radius;
+                                    active = false;
                                 }
                             } else if (nodes == target) {
                                 x_mid = e0; z_mid = e1;
@@ -545,7 +611,11 @@ hipError_t launch_field_sample(const FieldSampleArgs& a, hipStream_t stream) {
 hipError_t launch_grad_trace(const GradTraceArgs& a, hipStream_t stream) {
     if (a.n_rays <= 0) return hipSuccess;
     const long long blocks = (a.n_rays + PRHF_GRAD_TRACE_THREADS - 1) / PRHF_GRAD_TRACE_THREADS;
-    hipLaunchKernelGGL(grad_trace_kernel, dim3((unsigned)blocks), dim3(PRHF_GRAD_TRACE_THREADS), field_axes_lds_bytes(a.n0, a.n1),
-                       stream, a);
+    if (a.geometry == PRHF_GEO_SPHERICAL)
+        hipLaunchKernelGGL(grad_trace_kernel<PRHF_GEO_SPHERICAL>, dim3((unsigned)blocks), dim3(PRHF_GRAD_TRACE_THREADS),
+                           field_axes_lds_bytes(a.n0, a.n1), stream, a);
+    else
+        hipLaunchKernelGGL(grad_trace_kernel<PRHF_GEO_CARTESIAN>, dim3((unsigned)blocks), dim3(PRHF_GRAD_TRACE_THREADS),
+                           field_axes_lds_bytes(a.n0, a.n1), stream, a);
     return hipGetLastError();
 }

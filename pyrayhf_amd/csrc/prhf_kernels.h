@@ -298,7 +298,7 @@ hipError_t launch_snell(const SnellArgs& a, hipStream_t stream);   // with a.ray
 hipError_t snell_resident_waves(long long n_alt, int cu_count, long long* waves, bool ptab = false, bool reduced = false,
                                 int geometry = 0);
 
-// 2-D refractive-index fields and the Cartesian gradient tracer (prhf_gradient.inc); device pointers throughout.
+// 2-D refractive-index fields and the gradient tracers (prhf_gradient.inc); device pointers throughout.
 struct FieldPackArgs {
     const double* mu;            // (n_fields, n0, n1)
     const double* mup;
@@ -327,16 +327,18 @@ struct FieldSampleArgs {
     double fill_n, fill_grad, fill_mup;
 };
 #define PRHF_GRAD_OUTPUTS 12     // path km, delay s, x_mid, z_mid, ground range, x_apex, z_apex, status, nodes, RHS calls, rejected steps, 0
+#define PRHF_GEO_CARTESIAN 0     // state (x, z, vx, vz) on (z, x) axes
+#define PRHF_GEO_SPHERICAL 1     // state (r, phi, v_r, v_phi) on (r, phi) axes
 struct GradTraceArgs {
     const double* rec;
-    const double* a0;            // z axis (n0), x axis (n1)
+    const double* a0;            // z axis (n0), x axis (n1); spherical: r axis, phi axis
     const double* a1;
     const double* x0;            // (n_rays) each
     const double* z0;
     const double* elev;
     const long long* ray_field;  // (n_rays) or null: field 0
     double* out;                 // (n_rays, PRHF_GRAD_OUTPUTS)
-    double* path_t;              // (n_rays, path_stride) each, or all null
+    double* path_t;              // (n_rays, path_stride) each, or all null: t and the four state components
     double* path_x;
     double* path_z;
     double* path_vx;
@@ -344,9 +346,12 @@ struct GradTraceArgs {
     unsigned* status;
     long long n_rays, n_fields, path_stride;
     int n0, n1;
-    int renormalize_every;
+    int renormalize_every;       // (Cartesian only: the spherical right-hand side has nothing that depends on it)
+    int geometry;                // PRHF_GEO_*
+    // spherical: z_ground = R_E + z_ground_km, z_max = r_max_km, x_min / x_max = phi_min / phi_max
     double s_max, rtol, atol, max_step, z_ground, z_max, x_min, x_max;
     double fill_n, fill_grad, fill_mup;
+    double earth_radius;         // spherical only
 };
 #define PRHF_FIELD_MAX_AXES 8000   // n0 + n1 at most: both axes are staged in 64 KiB of LDS
 inline size_t field_axes_lds_bytes(int n0, int n1) { return (size_t)(n0 + n1) * 8; }

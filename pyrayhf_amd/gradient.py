@@ -1,4 +1,5 @@
-"""2-D refractive-index fields and the Cartesian gradient ray tracer on the GPU.
+"""2-D refractive-index fields and the gradient ray tracers of both geometries on the GPU (SURVEY.md section 2, rows 10
+and 11).
 
 ``build_refractive_index_interpolator_cartesian``, ``build_refractive_index_interpolator_spherical`` and
 ``build_mup_function`` keep the reference's signatures, defaults and error messages (reference
@@ -10,12 +11,15 @@ GPU ``find_mu_mup``.
 
 ``trace_ray_cartesian_gradient`` is the reference's single-ray call (``:1270-1457``; the dict lacks ``'sol'``);
 ``trace_rays_cartesian_gradient`` / ``trace_fan_cartesian_gradient`` trace a batch / a fan of elevations for every field
-in one launch, one ray per lane (``prhf_trace_gradient_f64``).
+in one launch, one ray per lane (``prhf_trace_gradient_f64``).  ``trace_ray_spherical_gradient``,
+``trace_rays_spherical_gradient`` and ``trace_fan_spherical_gradient`` are the same over a spherical Earth
+(``:2128-2337``, ``prhf_trace_gradient_spherical_f64``) with the stop conditions DESIGN.md section 4.7 defines: the
+reference's own wiring of its event helpers cannot fire.
 
-Limitations: the tracer reads mu and mu' from ONE set of records, so the ``n_and_grad`` and ``mup_func`` objects given to
-``trace_ray_cartesian_gradient`` must have been built on the same ``z_grid`` and ``x_grid`` (``ValueError`` otherwise),
-and both must come from this module (``TypeError`` otherwise: there is no CPU path).  The spherical gradient tracer is
-not provided: see DESIGN.md section 8.
+Limitations: a tracer reads mu and mu' from ONE set of records, so the ``n_and_grad`` and ``mup_func`` objects given to
+``trace_ray_cartesian_gradient`` / ``trace_ray_spherical_gradient`` must have been built on the same ``z_grid`` and
+``x_grid`` - and the same ``R_E`` - (``ValueError`` otherwise), and both must come from this module (``TypeError``
+otherwise: there is no CPU path).  A field knows its geometry; a tracer refuses a field of the other one.
 """
 
 from __future__ import annotations
@@ -27,13 +31,15 @@ from .library import constants, find_mu_mup, find_X, find_Y
 
 __all__ = ["build_refractive_index_interpolator_cartesian", "build_refractive_index_interpolator_spherical",
            "build_mup_function", "refractive_field", "RefractiveField", "trace_ray_cartesian_gradient",
-           "trace_rays_cartesian_gradient", "trace_fan_cartesian_gradient", "STATUS_NAMES"]
+           "trace_rays_cartesian_gradient", "trace_fan_cartesian_gradient", "trace_ray_spherical_gradient",
+           "trace_rays_spherical_gradient", "trace_fan_spherical_gradient", "STATUS_NAMES"]
 
 STATUS_NAMES = ("ground", "domain", "length", "failure")          # reference library.py:1391-1398
 _KEYS = ("group_path_km", "group_delay_sec", "x_midpoint", "z_midpoint", "ground_range_km", "x_apex_km", "z_apex_km",
          "status", "n_nodes", "n_rhs", "n_rejected")
 _INT_KEYS = ("status", "n_nodes", "n_rhs", "n_rejected")
 _PATH_KEYS = ("t", "x", "z", "vx", "vz")
+_PATH_KEYS_SPHERICAL = ("t", "r", "phi", "v_r", "v_phi")
 _MAX_AXES = 8000
 
 
@@ -41,10 +47,16 @@ class RefractiveField:
     """``F`` fields mu, mu' on one grid: the device-resident node records the sampler and the tracer read.
 
     ``mu, mup``: ``(F, n0, n1)`` (or ``(n0, n1)``) on ``axis0`` (altitude, or radius) and ``axis1`` (distance, or
-    angle).  The records are packed on first use, so that building a field needs no GPU."""
+    angle).  ``geometry`` says which: ``"cartesian"`` (the default), or ``"spherical"`` with the Earth radius ``R_E``
+    (default ``constants()[2]``) that made the axes ``R_E + z`` and ``x / R_E``; the tracers check it, the sampler does
+    not care.  The records are packed on first use, so that building a field needs no GPU."""
 
     def __init__(self, axis0, axis1, mu, mup, *, edge_order=2, device=None, fill_n=np.nan, fill_grad=0.0,
-                 fill_mup=np.nan):
+                 fill_mup=np.nan, geometry="cartesian", R_E=None):
+        if geometry not in ("cartesian", "spherical"):
+            raise ValueError("geometry must be 'cartesian' or 'spherical'")
+        self.geometry = geometry
+        self.R_E = None if geometry == "cartesian" else float(constants()[2] if R_E is None else R_E)
         self.axis0 = np.ascontiguousarray(axis0, dtype=np.float64)
         self.axis1 = np.ascontiguousarray(axis1, dtype=np.float64)
         mu = np.asarray(mu, dtype=np.float64)
@@ -174,7 +186,7 @@ def build_refractive_index_interpolator_cartesian(z_grid, x_grid, n_field, *, fi
     if not (np.all(np.diff(z_grid) > 0) and np.all(np.diff(x_grid) > 0)):
         raise ValueError("`z_grid` and `x_grid` must be strictly increasing.")
     field = RefractiveField(z_grid, x_grid, n_field, np.full_like(n_field, np.nan), edge_order=edge_order, device=device,
-                            fill_n=fill_value_n, fill_grad=fill_value_grad)
+                            fill_n=fill_value_n, fill_grad=fill_value_grad, geometry="cartesian")
     return _NAndGrad(field, "cartesian", bounds_error, z_grid, x_grid)
 
 
@@ -195,7 +207,7 @@ def build_refractive_index_interpolator_spherical(z_grid, x_grid, n_field, *, fi
     if not (np.all(np.diff(r_grid) > 0) and np.all(np.diff(phi_grid) > 0)):
         raise ValueError("`r_grid` and `phi_grid` must be strictly increasing.")
     field = RefractiveField(r_grid, phi_grid, n_field, np.full_like(n_field, np.nan), edge_order=edge_order,
-                            device=device, fill_n=fill_value_n, fill_grad=fill_value_grad)
+                            device=device, fill_n=fill_value_n, fill_grad=fill_value_grad, geometry="spherical", R_E=R_E)
     return _NAndGrad(field, "spherical", bounds_error, z_grid, x_grid)
 
 
@@ -219,7 +231,8 @@ def build_mup_function(mup_field, x_grid, z_grid, *, geometry="cartesian", R_E=N
     for i, g in enumerate((axis0, axis1)):
         if mup_field.shape[i] != g.size:
             raise ValueError(f"There are {g.size} points and {mup_field.shape[i]} values in dimension {i}")
-    field = RefractiveField(axis0, axis1, mup_field, mup_field, edge_order=1, device=device, fill_mup=fill_value)
+    field = RefractiveField(axis0, axis1, mup_field, mup_field, edge_order=1, device=device, fill_mup=fill_value,
+                            geometry=geometry, R_E=R_E)
     return _MupFunction(field, geometry, bounds_error, R_E, z_grid, x_grid)
 
 
@@ -229,8 +242,8 @@ def refractive_field(f0_Hz, Ne, Babs, bpsi, z_grid, x_grid, mode, geometry="cart
     mu and mu' by the GPU ``find_mu_mup`` (one call per frequency, so that the reference's isotropic rule
     ``nanmax|Y| < 1e-12`` applies per frequency as it would to that frequency's arrays), then the records.
     Returns a ``RefractiveField`` on ``(z_grid, x_grid)`` - or ``(R_E + z_grid, x_grid / R_E)`` for
-    ``geometry="spherical"`` - for ``trace_rays_cartesian_gradient`` / ``trace_fan_cartesian_gradient`` and the
-    ``sample`` method."""
+    ``geometry="spherical"`` - for ``trace_rays_cartesian_gradient`` / ``trace_fan_cartesian_gradient`` - or
+    ``trace_rays_spherical_gradient`` / ``trace_fan_spherical_gradient`` - and the ``sample`` method."""
     if mode not in ("O", "X"):
         raise ValueError("Mode must be O or X")
     if geometry not in ("cartesian", "spherical"):
@@ -254,12 +267,22 @@ def refractive_field(f0_Hz, Ne, Babs, bpsi, z_grid, x_grid, mode, geometry="cart
     else:
         axis0, axis1 = z_grid, x_grid
     return RefractiveField(axis0, axis1, mu, mup, edge_order=edge_order, device=device, fill_n=fill_value_n,
-                           fill_grad=fill_value_grad, fill_mup=fill_value_mup)
+                           fill_grad=fill_value_grad, fill_mup=fill_value_mup, geometry=geometry, R_E=R_E)
 
 
-def _trace(field, x0, z0, elev, idx, controls, return_paths):
+def _need_geometry(field, geometry, name):
+    if not isinstance(field, RefractiveField):
+        raise TypeError("field must be a RefractiveField (refractive_field, or the .field of a builder's callable)")
+    if field.geometry != geometry:
+        raise ValueError(f"{name} needs a {geometry} field, this one is {field.geometry}")
+
+
+def _trace(field, x0, z0, elev, idx, controls, return_paths, earth_radius=None):
     """Rays in the caller's order; the launch gets them sorted by (field, elevation) so that a wave shares a field and
-    neighbouring lanes take similar numbers of steps.  A lane's result does not depend on its neighbours."""
+    neighbouring lanes take similar numbers of steps.  A lane's result does not depend on its neighbours.
+    ``earth_radius``: the spherical tracer, whose ``controls`` hold ``r_max_km, phi_min, phi_max`` in the places of
+    ``z_max_km, x_min_km, x_max_km``."""
+    path_keys = _PATH_KEYS if earth_radius is None else _PATH_KEYS_SPHERICAL
     s_max_km, rtol, atol, max_step_km, z_ground_km, z_max_km, x_min_km, x_max_km, renormalize_every = controls
     max_step = np.inf if max_step_km is None else float(max_step_km)
     if max_step <= 0:
@@ -282,22 +305,25 @@ def _trace(field, x0, z0, elev, idx, controls, return_paths):
         ctx = field._ctx()
 
         def launch(paths, stride):
-            _native.raise_for(ctx.trace_gradient(
-                rec.data_ptr(), field.n_fields, field.axis0.size, field.axis1.size, field.axis0.ctypes.data,
-                field.axis1.ctypes.data, xs.ctypes.data, zs.ctypes.data, es.ctypes.data, fs.ctypes.data, n, ctl,
-                field.fills, out.ctypes.data, paths, stride, 0))
+            grid = (rec.data_ptr(), field.n_fields, field.axis0.size, field.axis1.size, field.axis0.ctypes.data,
+                    field.axis1.ctypes.data, xs.ctypes.data, zs.ctypes.data, es.ctypes.data, fs.ctypes.data, n)
+            tail = (ctl, field.fills, out.ctypes.data, paths, stride, 0)
+            if earth_radius is None:
+                _native.raise_for(ctx.trace_gradient(*grid, *tail))
+            else:
+                _native.raise_for(ctx.trace_gradient_spherical(*grid, earth_radius, *tail))
         launch(None, 0)
         if return_paths:
             # the same rays again, now that the longest path is known: the steps are deterministic
             stride = int(out[:, 8].max())
-            bufs = [np.empty((n, stride), dtype=np.float64) for _ in _PATH_KEYS]
+            bufs = [np.empty((n, stride), dtype=np.float64) for _ in path_keys]
             launch([b.ctypes.data for b in bufs], stride)
-            for k, b in zip(_PATH_KEYS, bufs):
+            for k, b in zip(path_keys, bufs):
                 unsorted = np.empty_like(b)
                 unsorted[order] = b
                 res[k] = unsorted
     elif return_paths:
-        for k in _PATH_KEYS:
+        for k in path_keys:
             res[k] = np.empty((0, 0))
     back = np.empty_like(out)
     back[order] = out
@@ -311,6 +337,15 @@ def _controls(s_max_km, rtol, atol, max_step_km, z_ground_km, z_max_km, x_min_km
             float(x_max_km), renormalize_every)
 
 
+def _broadcast_rays(x0_km, z0_km, elevation_deg, field_index):
+    arrs = [np.asarray(v, dtype=np.float64) for v in (x0_km, z0_km, elevation_deg)]
+    if field_index is not None:
+        arrs.append(np.asarray(field_index, dtype=np.int64))
+    arrs = np.broadcast_arrays(*arrs)
+    flat = [np.ascontiguousarray(v).reshape(-1) for v in arrs]
+    return arrs[0].shape, flat, flat[3] if field_index is not None else None
+
+
 def trace_rays_cartesian_gradient(field, x0_km, z0_km, elevation_deg, field_index=None, s_max_km=5000.0, *, rtol=1e-7,
                                   atol=1e-9, max_step_km=None, z_ground_km=0.0, z_min_km=-1.0, z_max_km=1000.0,
                                   x_min_km=-1e6, x_max_km=1e6, renormalize_every=50, return_paths=False):
@@ -320,15 +355,8 @@ def trace_rays_cartesian_gradient(field, x0_km, z0_km, elevation_deg, field_inde
     ``group_path_km, group_delay_sec, x_midpoint, z_midpoint, ground_range_km, x_apex_km, z_apex_km`` and ``status``
     (index into ``STATUS_NAMES``), ``n_nodes``, ``n_rhs``, ``n_rejected``; with ``return_paths`` also ``t, x, z, vx,
     vz``: ``(R, max n_nodes)`` padded with NaN."""
-    if not isinstance(field, RefractiveField):
-        raise TypeError("field must be a RefractiveField (refractive_field, or the .field of a builder's callable)")
-    arrs = [np.asarray(v, dtype=np.float64) for v in (x0_km, z0_km, elevation_deg)]
-    if field_index is not None:
-        arrs.append(np.asarray(field_index, dtype=np.int64))
-    arrs = np.broadcast_arrays(*arrs)
-    shape = arrs[0].shape
-    flat = [np.ascontiguousarray(v).reshape(-1) for v in arrs]
-    idx = flat[3] if field_index is not None else None
+    _need_geometry(field, "cartesian", "trace_rays_cartesian_gradient")
+    shape, flat, idx = _broadcast_rays(x0_km, z0_km, elevation_deg, field_index)
     res = _trace(field, flat[0], flat[1], flat[2], idx,
                  _controls(s_max_km, rtol, atol, max_step_km, z_ground_km, z_max_km, x_min_km, x_max_km, renormalize_every),
                  return_paths)
@@ -343,13 +371,20 @@ def trace_fan_cartesian_gradient(field, elevation_deg, x0_km=0.0, z0_km=0.0, s_m
     e = np.atleast_1d(np.asarray(elevation_deg, dtype=np.float64))
     if e.ndim != 1:
         raise ValueError("elevation_deg must be 1-D (the elevations of the fan)")
-    if not isinstance(field, RefractiveField):
-        raise TypeError("field must be a RefractiveField (refractive_field, or the .field of a builder's callable)")
+    _need_geometry(field, "cartesian", "trace_fan_cartesian_gradient")
     idx = np.arange(field.n_fields, dtype=np.int64)[:, None]
     return trace_rays_cartesian_gradient(field, x0_km, z0_km, e[None, :], idx, s_max_km, rtol=rtol, atol=atol,
                                          max_step_km=max_step_km, z_ground_km=z_ground_km, z_min_km=z_min_km,
                                          z_max_km=z_max_km, x_min_km=x_min_km, x_max_km=x_max_km,
                                          renormalize_every=renormalize_every, return_paths=return_paths)
+
+
+def _merged(n_and_grad, mup_func):
+    """One field with the mu of ``n_and_grad`` and the mu' of ``mup_func`` (same grids)."""
+    nf, mf = n_and_grad.field, mup_func.field
+    return RefractiveField(nf.axis0, nf.axis1, nf.mu, mf.mup, edge_order=nf.edge_order, device=nf.device,
+                           fill_n=nf.fills[0], fill_grad=nf.fills[1], fill_mup=mf.fills[2], geometry=nf.geometry,
+                           R_E=nf.R_E)
 
 
 def trace_ray_cartesian_gradient(n_and_grad, mup_func, x0_km, z0_km, elevation_deg, s_max_km=5000.0, *, rtol=1e-7,
@@ -371,9 +406,7 @@ def trace_ray_cartesian_gradient(n_and_grad, mup_func, x0_km, z0_km, elevation_d
     field = n_and_grad._with_mup.get(id(mup_func))
     if field is None or field[0] is not mup_func:
         nf, mf = n_and_grad.field, mup_func.field
-        merged = RefractiveField(nf.axis0, nf.axis1, nf.mu, mf.mup, edge_order=nf.edge_order, device=nf.device,
-                                 fill_n=nf.fills[0], fill_grad=nf.fills[1], fill_mup=mf.fills[2])
-        n_and_grad._with_mup = {id(mup_func): (mup_func, merged)}
+        n_and_grad._with_mup = {id(mup_func): (mup_func, _merged(n_and_grad, mup_func))}
         field = n_and_grad._with_mup[id(mup_func)]
     r = trace_rays_cartesian_gradient(field[1], np.float64(x0_km), np.float64(z0_km), np.float64(elevation_deg), None,
                                       s_max_km, rtol=rtol, atol=atol, max_step_km=max_step_km, z_ground_km=z_ground_km,
@@ -381,6 +414,85 @@ def trace_ray_cartesian_gradient(n_and_grad, mup_func, x0_km, z0_km, elevation_d
                                       renormalize_every=renormalize_every, return_paths=True)
     n = int(r["n_nodes"])
     out = {k: r[k][:n].copy() for k in _PATH_KEYS}
+    out["status"] = STATUS_NAMES[int(r["status"])]
+    for k in _KEYS[:7]:
+        out[k] = float(r[k])
+    return out
+
+
+def trace_rays_spherical_gradient(field, x0_km, z0_km, elevation_deg, field_index=None, s_max_km=6000.0, *, R_E=None,
+                                  z_ground_km=0.0, r_max_km=None, phi_min=-np.pi, phi_max=np.pi, rtol=1e-7, atol=1e-9,
+                                  max_step_km=2.0, renormalize_every=50, return_paths=False):
+    """Trace ``R`` rays through ``field`` (a ``RefractiveField``, spherical) in one launch; ``x0_km`` (surface arc),
+    ``z0_km`` (altitude), ``elevation_deg`` and ``field_index`` broadcast to ``(R,)``.  The controls are the reference's
+    (library.py:2135-2145; ``max_step_km=None``: no limit; ``r_max_km=None``: ``R_E + 1200``); ``R_E`` defaults to the
+    field's and must equal it.  The rays stop at ``r <= R_E + z_ground_km + 1e-3``, ``r >= r_max_km``, ``phi <= phi_min``
+    or ``phi >= phi_max``.  Returns the dict of ``trace_rays_cartesian_gradient`` with
+    ``x = R_E phi`` and ``z = r - R_E`` in every x and z entry; with ``return_paths`` also ``t, r, phi, v_r, v_phi, x,
+    z``: ``(R, max n_nodes)`` padded with NaN."""
+    _need_geometry(field, "spherical", "trace_rays_spherical_gradient")
+    if R_E is None:
+        R_E = field.R_E
+    if float(R_E) != field.R_E:
+        raise ValueError(f"R_E={R_E} is not the field's ({field.R_E})")
+    R_E = field.R_E
+    if r_max_km is None:
+        r_max_km = R_E + 1200.0                                             # :2226-2227
+    shape, flat, idx = _broadcast_rays(x0_km, z0_km, elevation_deg, field_index)
+    res = _trace(field, flat[0], flat[1], flat[2], idx,
+                 _controls(s_max_km, rtol, atol, max_step_km, z_ground_km, r_max_km, phi_min, phi_max, renormalize_every),
+                 return_paths, earth_radius=R_E)
+    if return_paths:
+        res["x"] = R_E * res["phi"]                                         # :2277-2278
+        res["z"] = res["r"] - R_E
+    return {k: v.reshape(shape + v.shape[1:]) for k, v in res.items()}
+
+
+def trace_fan_spherical_gradient(field, elevation_deg, x0_km=0.0, z0_km=0.0, s_max_km=6000.0, *, R_E=None,
+                                 z_ground_km=0.0, r_max_km=None, phi_min=-np.pi, phi_max=np.pi, rtol=1e-7, atol=1e-9,
+                                 max_step_km=2.0, renormalize_every=50, return_paths=False):
+    """Every elevation of ``elevation_deg`` ``(E,)`` from ``(x0_km, z0_km)`` in every field of ``field``: the dict of
+    ``trace_rays_spherical_gradient`` with arrays of shape ``(F, E)``, one launch."""
+    e = np.atleast_1d(np.asarray(elevation_deg, dtype=np.float64))
+    if e.ndim != 1:
+        raise ValueError("elevation_deg must be 1-D (the elevations of the fan)")
+    _need_geometry(field, "spherical", "trace_fan_spherical_gradient")
+    idx = np.arange(field.n_fields, dtype=np.int64)[:, None]
+    return trace_rays_spherical_gradient(field, x0_km, z0_km, e[None, :], idx, s_max_km, R_E=R_E, z_ground_km=z_ground_km,
+                                         r_max_km=r_max_km, phi_min=phi_min, phi_max=phi_max, rtol=rtol, atol=atol,
+                                         max_step_km=max_step_km, renormalize_every=renormalize_every,
+                                         return_paths=return_paths)
+
+
+def trace_ray_spherical_gradient(n_and_grad_rphi, mup_func, x0_km, z0_km, elevation_deg, s_max_km=6000.0, *, R_E=None,
+                                 z_ground_km=0.0, r_max_km=None, phi_min=-np.pi, phi_max=np.pi, rtol=1e-7, atol=1e-9,
+                                 max_step_km=2.0, renormalize_every=50):
+    """One ray; the reference's signature and result dict (library.py:2128-2337): ``t, r, phi, v_r, v_phi, x, z`` (path
+    arrays), ``status`` (str), ``group_path_km, group_delay_sec, x_midpoint, z_midpoint, ground_range_km, x_apex_km,
+    z_apex_km``.  ``n_and_grad_rphi`` and ``mup_func`` must be the objects this module's builders return, in spherical
+    geometry, on the same grids and with the same ``R_E``."""
+    if mup_func is None:
+        raise ValueError("mup_func must be provided \u2014 build it with "
+                         "build_mup_function(..., geometry='spherical').")                     # :2216-2219
+    if not isinstance(n_and_grad_rphi, _NAndGrad) or not isinstance(mup_func, _MupFunction):
+        raise TypeError("n_and_grad_rphi and mup_func must be built with this module's "
+                        "build_refractive_index_interpolator_spherical and build_mup_function: there is no CPU path")
+    if n_and_grad_rphi.geometry != "spherical" or mup_func.geometry != "spherical":
+        raise ValueError("trace_ray_spherical_gradient needs spherical n_and_grad_rphi and mup_func")
+    if n_and_grad_rphi.field.R_E != mup_func.field.R_E:
+        raise ValueError("n_and_grad_rphi and mup_func must be built with the same R_E")
+    if not n_and_grad_rphi.field.same_grid(mup_func.field):
+        raise ValueError("n_and_grad_rphi and mup_func must be built on the same z_grid and x_grid")
+    field = n_and_grad_rphi._with_mup.get(id(mup_func))
+    if field is None or field[0] is not mup_func:
+        n_and_grad_rphi._with_mup = {id(mup_func): (mup_func, _merged(n_and_grad_rphi, mup_func))}
+        field = n_and_grad_rphi._with_mup[id(mup_func)]
+    r = trace_rays_spherical_gradient(field[1], np.float64(x0_km), np.float64(z0_km), np.float64(elevation_deg), None,
+                                      s_max_km, R_E=R_E, z_ground_km=z_ground_km, r_max_km=r_max_km, phi_min=phi_min,
+                                      phi_max=phi_max, rtol=rtol, atol=atol, max_step_km=max_step_km,
+                                      renormalize_every=renormalize_every, return_paths=True)
+    n = int(r["n_nodes"])
+    out = {k: r[k][:n].copy() for k in _PATH_KEYS_SPHERICAL + ("x", "z")}
     out["status"] = STATUS_NAMES[int(r["status"])]
     for k in _KEYS[:7]:
         out[k] = float(r[k])

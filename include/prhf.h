@@ -123,6 +123,11 @@ int prhf_ctx_set_math(prhf_ctx* ctx, int level);
  *                        bottomside of the launch fits LDS, only the levels up to the highest peak are staged)
  *   "tall_lean"          0: a profile staged in global memory takes the generic loop (1: the main loop reads its nodes
  *                        from the slab)
+ *   "strided_top"        0: every grid point of a long X-mode grid is evaluated, the launch of ABI 4 before this option bit
+ *                        for bit (1: whole pairs of at least 8192 points in X mode, fast tier, on a grid that is the
+ *                        reference's stretch: the top three altitude segments are summed from every eighth point plus
+ *                        Euler-Maclaurin end corrections, within 1e-12 of the full sum; any other grid is detected on
+ *                        the device and keeps the full sum)
  *   "short_compact", "short_prio", "short_order", "short_lanes"
  *                        geometry of the short-grid kernels: four 4-wave workgroups per CU (1), wave priorities by age (1),
  *                        blocks in descending cost order (1), lanes per pair in the O kernel (8; 16: four pairs per work

@@ -140,6 +140,7 @@ struct prhf_ctx {
     DevBuf tall;         // profiles of more than kMaxAlt levels: one slab of staged levels per resident workgroup
     const double* pairs_src = nullptr;   // PRHF_FLAG_GRID_STABLE: multiplier array the table was built from
     int64_t pairs_len = 0;
+    prhf::StridedPieces pairs_pieces = {};   // ... and the strided table's pieces that were built behind it
     // PRHF_FLAG_GRID_STABLE with HOST buffers: the stretched grid at a host address that keeps its contents is
     // uploaded, and its pair table built, once (a 20 000-point grid is 160 KB: more than the rest of a
     // single-profile call's inputs together)
@@ -148,6 +149,7 @@ struct prhf_ctx {
         int64_t len = 0;
         DevBuf mult, pairs;
         bool pairs_ready = false;
+        prhf::StridedPieces pieces = {};     // the strided table's pieces behind the pair table
     };
     static constexpr int kHostGrids = 16;
     HostGrid host_grid[kHostGrids];
@@ -572,11 +574,39 @@ int run(prhf_ctx* c, const double* freq, int64_t n_freq, const double* den, cons
                            8 * (size_t)(compact ? compact_queue : short_queue);
         return (long long)c->cu_count * (compact ? PRHF_COMPACT_WGS_PER_CU : (lds <= lds_half ? 2 : 1));
     };
+    // The strided table (option strided_top): one piece behind the pair table for every distinct grid of
+    // the X-mode fast-tier slices that take whole pairs of at least PRHF_TOP3_MIN_POINTS points through the main loop.
+    // Built with the pair table and cached with it; a cached table serves a launch whose pieces are the same.
+    prhf::StridedPieces pieces;
+    std::memset(&pieces, 0, sizeof pieces);
+    long long table_entries = mult_len + PRHF_PAIR_PAD;
+    if (want_pairs && kn.strided_top != 0 && !tall) {
+        for (int i = 0; i < n_segs; ++i) {
+            prhf::SegDev& s = a.seg[i];
+            if (!(s.lean && s.tier == 1 && s.mode == PRHF_KMODE_X && s.chunks == 1 && s.n_points >= PRHF_TOP3_MIN_POINTS)) continue;
+            int p = 0;
+            while (p < pieces.n && !(pieces.mult_off[p] == s.mult_off && pieces.n_points[p] == s.n_points)) ++p;
+            if (p == pieces.n) {
+                const long long len = prhf::strided_piece_entries(s.n_points);
+                // (the main loop addresses the table through a 31-bit byte offset)
+                if ((table_entries + len) * 16 >= 0x7fffffffLL) continue;
+                pieces.mult_off[p] = s.mult_off;
+                pieces.n_points[p] = s.n_points;
+                pieces.sp_off[p] = table_entries;
+                table_entries += len;
+                ++pieces.n;
+            }
+            s.sp_off = pieces.sp_off[p];
+        }
+    }
+    auto same_pieces = [&](const prhf::StridedPieces& o) { return std::memcmp(&o, &pieces, sizeof pieces) == 0; };
     if (want_pairs && grid) {
-        if (!grid->pairs_ready) {
-            if ((rc = ensure(c, grid->pairs, ((size_t)mult_len + PRHF_PAIR_PAD) * 16)) != PRHF_OK) return rc;
+        if (!grid->pairs_ready || !same_pieces(grid->pieces)) {
+            if ((rc = ensure(c, grid->pairs, (size_t)table_entries * 16)) != PRHF_OK) return rc;
             HIP_TRY(prhf::launch_grid_pairs(a.mult, mult_len, static_cast<double*>(grid->pairs.p), c->stream));
+            HIP_TRY(prhf::launch_grid_strided(a.mult, static_cast<double*>(grid->pairs.p), pieces, c->stream));
             grid->pairs_ready = true;
+            grid->pieces = pieces;
         }
         a.pairs = static_cast<const double*>(grid->pairs.p);
     }
@@ -584,13 +614,15 @@ int run(prhf_ctx* c, const double* freq, int64_t n_freq, const double* den, cons
         const bool stable = dev && (flags & PRHF_FLAG_GRID_STABLE) != 0;
         if (grid) {
             // (table cached with the grid, above)
-        } else if (!(stable && c->pairs.p && c->pairs_src == a.mult && c->pairs_len == mult_len)) {
+        } else if (!(stable && c->pairs.p && c->pairs_src == a.mult && c->pairs_len == mult_len && same_pieces(c->pairs_pieces))) {
             c->pairs_src = nullptr;
-            if ((rc = ensure(c, c->pairs, ((size_t)mult_len + PRHF_PAIR_PAD) * 16)) != PRHF_OK) return rc;
+            if ((rc = ensure(c, c->pairs, (size_t)table_entries * 16)) != PRHF_OK) return rc;
             HIP_TRY(prhf::launch_grid_pairs(a.mult, mult_len, static_cast<double*>(c->pairs.p), c->stream));
+            HIP_TRY(prhf::launch_grid_strided(a.mult, static_cast<double*>(c->pairs.p), pieces, c->stream));
             if (stable) {
                 c->pairs_src = a.mult;
                 c->pairs_len = mult_len;
+                c->pairs_pieces = pieces;
             }
         }
         if (!grid) a.pairs = static_cast<const double*>(c->pairs.p);

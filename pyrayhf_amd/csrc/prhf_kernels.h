@@ -95,6 +95,8 @@ struct SegDev {
     int lean;                        // this slice uses the main loop (and KArgs::pairs); decided per slice so that a
                                      // slice gets the same arithmetic alone and inside a mixed launch
     int prio;                        // wave priority (0..3) of this slice's workgroups in a mixed launch: see vfo_kernel
+    long long sp_off;                // > 0: this slice's piece of the strided table, in entries from KArgs::pairs
+                                     // (launch_grid_strided; the main loop's strided sum); 0: none
     int thread_scan;                 // X mode: reflection heights settled one frequency per thread while the candidate
                                      // list is made (on by default; PRHF_THREAD_SCAN_MIN turns it off for A/B runs.
                                      // O mode always does, by binary search)
@@ -183,6 +185,16 @@ hipError_t configure_kernels(size_t max_lds_bytes);
 hipError_t query_occupancy(int tier, size_t lds_bytes, int* blocks_per_cu);
 // pairs[2 i], pairs[2 i + 1] = mult[i], mult[i + 1] - mult[i]; `pairs` holds n + PRHF_PAIR_PAD entries
 hipError_t launch_grid_pairs(const double* mult, long long n, double* pairs, hipStream_t stream);
+// The strided table's pieces (grid_strided_kernel): grid p is n_points[p] multipliers from mult + mult_off[p], its
+// piece starts sp_off[p] entries into `pairs` and holds strided_piece_entries(n_points[p]) entries
+struct StridedPieces {
+    int n;
+    int n_points[PRHF_MAX_SEGMENTS];
+    long long mult_off[PRHF_MAX_SEGMENTS];
+    long long sp_off[PRHF_MAX_SEGMENTS];
+};
+inline long long strided_piece_entries(long long n_points) { return 1 + ((n_points + 7) / 8 + 1) + PRHF_PAIR_PAD; }
+hipError_t launch_grid_strided(const double* mult, double* pairs, const StridedPieces& pc, hipStream_t stream);
 // tab[8 f ..] = f_hz, f2, cp^2/f2, (g_p/f)^2, 1/f2, 1/f_hz, 0, 0; row n_freq: min |freq_mhz| (tab holds n_freq + 1 rows)
 // Control words that the per-frequency table's kernel zeroes on the way (its workgroup 0): the block queues and list
 // heads of the launches that follow it on the stream.

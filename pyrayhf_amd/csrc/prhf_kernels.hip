@@ -1069,7 +1069,7 @@ template <int MODE, bool CHECK, int POLY, bool HINT, bool TOP, bool G>
 __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type nodes_arg, unsigned hint_lds,
                                                      const double2* __restrict__ pairs, int first, int end,
                                                      int last_special, double span, double a0, double kj,
-                                                     double cX, double cY2, double well_conditioned) {
+                                                     double cX, double cY2, double well_conditioned, int sp_off) {
 #pragma clang fp contract(fast)
     // arguments arrive in VGPRs: back to SGPRs.  The node table travels as its 32-bit LDS address (a
     // generic pointer would turn every node read into a flat load).
@@ -1104,8 +1104,9 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
     const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<double2*>(pairs), 0, 0x7fffffff, 0x00020000);
     typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+    int tab_off = 0;                                   // bytes; the strided phase points it at the strided table's piece
     auto grid_at = [&](int i) {
-        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, i * (int)sizeof(double2), 0);
+        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, i * (int)sizeof(double2) + tab_off, 0);
         double2 g;
         __builtin_memcpy(&g, &v, sizeof g);
         return g;
@@ -1123,6 +1124,7 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
     constexpr int kTopSegments = 3;
     static_assert(kTopSegments == 3, "the run loop below selects among three");
     int seg_begin[kTopSegments] = {0, 0, 0}, seg_end[kTopSegments] = {0, 0, 0}, seg_j[kTopSegments] = {0, 0, 0};   // [0]: the top segment
+    int seg_lo[kTopSegments] = {0, 0, 0};              // the segment's first grid point itself (strided sum)
     int n_seg = 0;
     TopSegment top;
     __builtin_memset(&top, 0, sizeof top);
@@ -1193,6 +1195,7 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
             seg_begin[sidx] = aligned;
             seg_end[sidx] = run_end;
             seg_j[sidx] = j;
+            seg_lo[sidx] = lo;
             n_seg = sidx + 1;
             search_hi = lo + 1;
             run_end = first + ((lo - first) & ~63);
@@ -1295,6 +1298,109 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
             }
         }
     };
+    // X mode, fast tier, whole pairs of at least PRHF_TOP3_MIN_POINTS points on a grid that grid_strided_kernel found to
+    // be the reference's stretch (its piece's header word is 0; the header also carries c1 = -expm1(-10 / (N - 1)))
+    constexpr bool STRIDED = TOP && MODE == PRHF_KMODE_X && !CHECK && !G;
+    const int i_last_s = last_special;                 // N - 1
+    bool strided_on = false;
+    double sc1 = 0.0;
+    sp_off = uniform(sp_off);
+    if (STRIDED && sp_off > 0 && n_seg > 0 && first == 0 && last_special >= 0 && end >= PRHF_TOP3_MIN_POINTS) {
+        const u32x4 vh = __builtin_amdgcn_raw_buffer_load_b128(rsrc, 0, sp_off * (int)sizeof(double2), 0);
+        double2 gh;
+        __builtin_memcpy(&gh, &vh, sizeof gh);
+        strided_on = uniform((int)vh.x) == 0;
+        sc1 = uniform(gh.y);
+    }
+    // The strided sum of a top segment ("every eighth point"): inside one segment the summand
+    // g(i) = mu'(m_i) w(m_i) is an analytic function of the index - linear interpolants, exponential stretch - so
+    // by Euler-Maclaurin  sum_{i=a..b} g(i) = s sum_j g(a + j s) - (s-1)/2 (g(a) + g(b)) - (s^2-1)/12 (g'(b) - g'(a))
+    // + (s^4-1)/720 (g'''(b) - g'''(a)),  s = 8, the derivatives from seven-point stencils around a and b.  Here the
+    // sum over [a, E), E = b + 8, is taken that way: a and E are multiples of 64, so the ordinary steps on either side
+    // keep their whole wave-iterations.  Strided points come from the strided table's piece (m_8j, 8 w(m_8j)) through
+    // run_top itself; the 7 + 11 points a-3 .. a+3 and b-3 .. b+7 (the stencils, the end corrections and the seven
+    // ordinary points b+1 .. E-1) and the strided points that do not fill a wave-iteration share one or two
+    // iterations whose lanes gather m from the pair table and carry their own weights.
+    // Guards: the segment's continuation reaches X + Y = 1 at m_sing; no strided or stencil point within 256 indices of
+    // it (there g is not smooth enough for the two correction terms), and none where 1 - X - Y < 1e-6: mu' carries a
+    // rounding error of about 1e-16 / (1 - X - Y) there, which the eightfold weights amplify instead of averaging out
+    // (a low frequency that reflects in a nearly flat layer has 1 - X - Y < 1e-7 over thousands of points: 4e-11 of
+    // its sum, measured; with this bound the per-point error of a strided term stays below 1e-10).
+    auto strided_run = [&](int lo_s, int q_s, int begin_s) {
+        constexpr int kGuard = 256;
+        constexpr double kTau = 1e-6;
+        int a_s = begin_s >= lo_s + 3 ? begin_s : begin_s + 64;    // a - 3 >= the segment's first point
+        int hi_lim = q_s - 3;                                      // b + 3 <= this
+        int skip = 0;
+        {
+            // 1 - X - Y = gap - sl m on the segment's continuation (X + Y = cX (d0 + d1 m) + sqrt(2) (b0 + b1 m)): zero at
+            // m_sing, below kTau within dm of it.  Indices by the closed form of the stretch (v_log_f32, good to 1e-3 of
+            // an index); a point past the stretch's own end (no logarithm) has no index: 1e9.
+            const double r2 = 1.4142135623730951;
+            const double sl = cX * top.d1 + r2 * top.b1, gap = 1.0 - cX * top.d0 - r2 * top.b0;
+            const double n1 = (double)i_last_s;
+            auto index_of = [&](double m) {
+                const double A = __builtin_fma(1.0 - m, 22025.465794806718, 1.0);
+                if (!(A > 0.0)) return 1e9;
+                const double ln_a = (double)__builtin_amdgcn_logf((float)A) * 0.6931471805599453;
+                return fmin(fmax(__builtin_fma(-ln_a, n1 * 0.1, n1), -1e9), 1e9);
+            };
+            if (__builtin_fabs(sl) > 1e-300) {
+                const double m_sing = gap / sl, dm = kTau / __builtin_fabs(sl);
+                const double i_sing = index_of(m_sing);
+                const int below = uniform((int)__builtin_floor(fmin(i_sing - (double)(kGuard + 1), index_of(m_sing - dm))));
+                const int above = uniform((int)__builtin_ceil(fmax(i_sing + (double)(kGuard + 1), index_of(m_sing + dm))));
+                if (2.0 * i_sing >= (double)(a_s + q_s)) hi_lim = min(hi_lim, below);          // points <= below are clear of it
+                else a_s = max(a_s, first + ((above + 3 - first + 63) & ~63));                 // points >= above too
+            } else if (!(__builtin_fabs(gap) >= kTau)) {
+                skip = 1;                                          // X + Y constant and next to 1: this segment runs as today
+            }
+        }
+        // (the guards come out of vector arithmetic: back to scalars, or the loops below lose their scalar control)
+        a_s = uniform(a_s);
+        hi_lim = uniform(hi_lim);
+        if (uniform(skip)) return;
+        const int e_s = min(q_s + 1, hi_lim + 5) & ~63;            // b = E - 8: b + 3 <= hi_lim, E - 1 <= q
+        const int count = (e_s - a_s) >> 3;                        // strided points a, a + 8, .. b
+        if (count < 64) return;                                    // (this segment runs as today)
+        run_top(a_s);                                              // one by one up to a
+        const int b_s = e_s - 8;
+        // whole wave-iterations of strided points
+        tab_off = (sp_off + 1) * (int)sizeof(double2);
+        first = a_s >> 3;
+        const int j_whole = first + (count & ~63);
+        g0 = grid_at(first);
+        run_top(j_whole);
+        tab_off = 0;
+        const int rest = count & 63;                               // strided points left over, from j_whole
+        const double c0 = 1.0 / 22025.465794806718;                // 1 / expm1(10)
+        for (int t0 = 0; t0 < 18 + rest; t0 += 64) {
+            const int t = t0 + lane;
+            int idx = a_s;
+            double coef = 0.0;
+            if (t < 18) {
+                const bool at_a = t < 7;
+                const int q = at_a ? t - 3 : t - 10;               // -3 .. 3 around a, -3 .. 7 around b
+                idx = (at_a ? a_s : b_s) + q;
+                const int qa = q < 0 ? -q : q;
+                // (s^2-1)/12 D1[q] - (s^4-1)/720 D3[q]: 5.25 (3/4, -3/20, 1/60) - 5.6875 (-13/8, 1, -1/8)
+                const double mag = qa == 1 ? 13.1796875 : (qa == 2 ? -6.475 : (qa == 3 ? 0.7984375 : 0.0));
+                const double sg = q < 0 ? -mag : mag;
+                coef = q == 0 ? -3.5 : (at_a ? sg : -sg);
+                if (!at_a && q >= 1) coef += 1.0;                  // the ordinary points b + 1 .. E - 1
+            } else if (t < 18 + rest) {
+                idx = (j_whole + (t - 18)) << 3;
+                coef = 8.0;
+            }
+            const u32x4 vm = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (unsigned)idx * (unsigned)sizeof(double2), 0, 0);
+            double2 gm;
+            __builtin_memcpy(&gm, &vm, sizeof gm);
+            gm.y = coef * (sc1 * ((1.0 - gm.x) + c0));             // w(m) = c1 (1 - m + c0): 1 - m is exact near the top
+            accm = lean_step_top<MODE, false, POLY>(gm, top, cX, hcY2, accm, wc, viol);
+        }
+        first = e_s;
+        g0 = grid_at(first);
+    };
     if (TOP) {
         // (one copy of the two loops: the run's bounds are picked with scalar selects, not by unrolling)
 #pragma unroll 1
@@ -1305,6 +1411,12 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
             run_indexed(begin_s);
             if (!(CHECK && viol)) {
                 top = top_segment(nodes_v, j_s, span, cYs);
+                if (STRIDED && strided_on) {
+                    const int lo_s = sidx == 0 ? seg_lo[0] : (sidx == 1 ? seg_lo[1] : seg_lo[2]);
+                    // the segment's last ordinary point: the one below the last of the grid, or below the next segment's first
+                    const int q_s = sidx == 0 ? i_last_s - 1 : (sidx == 1 ? seg_lo[0] - 1 : seg_lo[1] - 1);
+                    strided_run(lo_s, q_s, begin_s);
+                }
                 run_top(end_s);
             }
         }
@@ -1347,9 +1459,9 @@ template <int MODE, bool CHECK, int POLY, bool HINT, bool TOP, bool G>
 __device__ __attribute__((noinline)) LeanResult lean_loop(typename NodeArg<G>::type nodes_arg, unsigned hint_lds,
                                                           const double2* __restrict__ pairs, int first, int end,
                                                           int last_special, double span, double a0, double kj,
-                                                          double cX, double cY2, double well_conditioned) {
+                                                          double cX, double cY2, double well_conditioned, int sp_off) {
     return lean_loop_body<MODE, CHECK, POLY, HINT, TOP, G>(nodes_arg, hint_lds, pairs, first, end, last_special, span, a0,
-                                                            kj, cX, cY2, well_conditioned);
+                                                            kj, cX, cY2, well_conditioned, sp_off);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1362,7 +1474,7 @@ __device__ __forceinline__ double integrate_chunk(const Node* __restrict__ nodes
                                                   const BlockInfo& info, const double* __restrict__ mult,
                                                   const double2* __restrict__ pairs, int n_points, int i0,
                                                   int i1, double f_hz, double f2, double cX, double cY2,
-                                                  double h_refl, int lane, double well_conditioned) {
+                                                  double h_refl, int lane, double well_conditioned, int sp_off) {
     const int K = info.K;
     const double a0 = info.a0;
     const double span = uniform(h_refl - a0);      // :413 (critical_height - aalt[0])
@@ -1409,7 +1521,7 @@ __device__ __forceinline__ double integrate_chunk(const Node* __restrict__ nodes
             const int poly = info.poly_angle == 4 ? 4 : 4 - info.poly_angle;    // degree: 3 cubic, 2 quadratic, 1 linear; 4: rotation form
             LeanResult r;
 #define PRHF_LEAN(P, H, T) lean_loop<MODE, TIER == 0, P, H, T, G>(nodes_lds, hint_lds, pairs, first, lean_end, last_special, \
-                                                                 span, a0, kj, cX, cY2, well_conditioned)
+                                                                 span, a0, kj, cX, cY2, well_conditioned, (T) ? sp_off : 0)
 #define PRHF_LEAN_POLY(H, T) (poly == 1 ? PRHF_LEAN(1, H, T) : (poly == 2 ? PRHF_LEAN(2, H, T) : PRHF_LEAN(3, H, T)))
             if (poly == 4) r = by_hint ? PRHF_LEAN(4, true, false) : PRHF_LEAN(4, false, false);
             else if (by_hint) {
@@ -1784,6 +1896,8 @@ __device__ __forceinline__ void run_items(const KArgs& a, const SegDev& sg, cons
     const int T = info.n_cand >= 0 ? info.n_cand : F * C;      // < 2^31: n_freq <= 2^20, chunks <= n_points / 256
     const double* mult = a.mult + sg.mult_off;
     const double2* pairs = (a.pairs && sg.lean) ? reinterpret_cast<const double2*>(a.pairs) + sg.mult_off : nullptr;
+    // the strided table's piece of this slice's grid, in entries from `pairs`; 0: none
+    const int sp_off = (pairs && sg.sp_off > 0) ? uniform((int)(sg.sp_off - sg.mult_off)) : 0;
     const long long pair_base = prof_local * F;
     const int first_item = block_in_prof * W, round_items = blocks_per_prof * W;
     // Few pairs on a long grid (one profile, the reference's own call; SegDev::slots > 0): a pair is cut into C <= S
@@ -1839,10 +1953,10 @@ __device__ __forceinline__ void run_items(const KArgs& a, const SegDev& sg, cons
                 const int i1 = min(sg.n_points, i0 + sg.chunk_len);
                 if (info.unmag)
                     result = integrate_chunk<MODE, TIER, true, G>(nodes, hint, info, mult, pairs, sg.n_points, i0, i1,
-                                                               pf.f_hz, pf.f2, pf.cX, pf.cY2, h, lane, wc);
+                                                               pf.f_hz, pf.f2, pf.cX, pf.cY2, h, lane, wc, sp_off);
                 else
                     result = integrate_chunk<MODE, TIER, false, G>(nodes, hint, info, mult, pairs, sg.n_points, i0,
-                                                                i1, pf.f_hz, pf.f2, pf.cX, pf.cY2, h, lane, wc);
+                                                                i1, pf.f_hz, pf.f2, pf.cX, pf.cY2, h, lane, wc, sp_off);
             } else if (info.K == 1) {
                 result = (c == C - 1) ? one_level_term<MODE, TIER>(nodes, info, pf, sg.well_conditioned) : 0.0;
                 reflects = true;
@@ -2073,6 +2187,53 @@ hipError_t launch_grid_pairs(const double* mult, long long n, double* pairs, hip
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(grid_pairs_kernel, dim3((unsigned)((n + PRHF_PAIR_PAD + 255) / 256)), dim3(256), 0, stream, mult,
                        n, reinterpret_cast<double2*>(pairs));
+    return hipGetLastError();
+}
+
+// Strided table of the main loop's strided sum (lean_loop_body): for every grid of a launch that
+// qualifies, one piece behind the pair table - a header entry, then (m_8j, 8 w(m_8j)) for j = 0 .. ceil(N / 8), then
+// PRHF_PAIR_PAD entries of padding.  w(m) = c1 (1 - m + c0), c0 = 1 / expm1(10), c1 = -expm1(-10 / (N - 1)), is the
+// width m_i+1 - m_i of the reference's stretch (library.py:296-321) as a function of m_i.  One workgroup per piece:
+// it also compares every width of the grid with w(m_i) and leaves 1 in the header's first word when one deviates
+// by more than 1e-14 (any other stretch does by 1e-4; the reference's by 2e-15), 0 otherwise; the header's second
+// double is c1.
+__global__ __launch_bounds__(1024) void grid_strided_kernel(const double* __restrict__ mult, double2* __restrict__ pairs,
+                                                            const StridedPieces pc) {
+    const int p = blockIdx.x, tid = threadIdx.x;
+    const int N = pc.n_points[p];
+    const double* m = mult + pc.mult_off[p];
+    double2* out = pairs + pc.sp_off[p];
+    const double c0 = 1.0 / 22025.465794806718;
+    const double c1 = -expm1(-10.0 / (double)(N - 1));
+    int bad = 0;
+    for (int i = tid; i + 1 < N; i += 1024) {
+        const double mi = m[i];
+        const double dev = __builtin_fabs((m[i + 1] - mi) - c1 * ((1.0 - mi) + c0));
+        if (!(dev <= 1e-14)) bad = 1;              // (a NaN fails too)
+    }
+    const int any_bad = __syncthreads_or(bad);
+    const int cnt = (N + 7) / 8 + 1;
+    for (int j = tid; j < cnt + PRHF_PAIR_PAD; j += 1024) {
+        double2 e = make_double2(0.0, 0.0);
+        if (j < cnt && 8 * j < N) {
+            const double mm = fmin(fmax(m[8 * j], 0.0), 1.0);
+            e = make_double2(mm, 8.0 * (c1 * ((1.0 - mm) + c0)));
+        }
+        out[1 + j] = e;
+    }
+    if (tid == 0) {
+        double2 h;
+        const unsigned long long word = any_bad ? 1ull : 0ull;
+        __builtin_memcpy(&h.x, &word, sizeof word);
+        h.y = c1;
+        out[0] = h;
+    }
+}
+
+hipError_t launch_grid_strided(const double* mult, double* pairs, const StridedPieces& pc, hipStream_t stream) {
+    if (pc.n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(grid_strided_kernel, dim3((unsigned)pc.n), dim3(1024), 0, stream, mult,
+                       reinterpret_cast<double2*>(pairs), pc);
     return hipGetLastError();
 }
 

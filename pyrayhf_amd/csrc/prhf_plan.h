@@ -71,6 +71,9 @@ struct Knobs {
                                        // many times the profiles - a ray stops at its turning point, after a third to a
                                        // half of the column, the table covers all of it - and the table stays under
                                        // 1 GiB (0: never; values do not depend on it)
+    double strided_top = 1;            // X mode, fast tier, whole pairs of at least 8192 points on the reference's stretch:
+                                       // the top segments are summed from every eighth point plus end corrections
+                                       // (0: every point, the launch of before bit for bit)
 };
 struct KnobName {
     const char* name;
@@ -103,6 +106,7 @@ const KnobName kKnobNames[] = {
     {"short_lanes", &Knobs::short_lanes, 0, 16},
     {"snell_table", &Knobs::snell_table, 0, 1e9},
     {"tall_lean", &Knobs::tall_lean, 0, 1},
+    {"strided_top", &Knobs::strided_top, 0, 1},
 };
 constexpr int kWavesPerBlock = PRHF_BLOCK_THREADS / 64;
 

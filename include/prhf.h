@@ -128,6 +128,10 @@ int prhf_ctx_set_math(prhf_ctx* ctx, int level);
  *                        reference's stretch: the top three altitude segments are summed from every eighth point plus
  *                        Euler-Maclaurin end corrections, within 1e-12 of the full sum; any other grid is detected on
  *                        the device and keeps the full sum)
+ *   "strided_lower"      0: only those three segments take the strided sum, the launch of before this option bit for
+ *                        bit (1: on a uniform altitude grid the segments of at least 64 points below them do too - one
+ *                        strided pass plus one pass over the points around the segment boundaries; a pair with a
+ *                        segment too close to X + Y = 1 keeps the sum of before; "strided_top" = 0 switches both off)
  *   "short_compact", "short_prio", "short_order", "short_lanes"
  *                        geometry of the short-grid kernels: four 4-wave workgroups per CU (1), wave priorities by age (1),
  *                        blocks in descending cost order (1), lanes per pair in the O kernel (8; 16: four pairs per work

@@ -597,6 +597,7 @@ int run(prhf_ctx* c, const double* freq, int64_t n_freq, const double* den, cons
                 ++pieces.n;
             }
             s.sp_off = pieces.sp_off[p];
+            s.strided_lower = kn.strided_lower != 0;
         }
     }
     auto same_pieces = [&](const prhf::StridedPieces& o) { return std::memcmp(&o, &pieces, sizeof pieces) == 0; };

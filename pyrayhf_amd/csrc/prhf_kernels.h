@@ -57,6 +57,9 @@
 #ifndef PRHF_TOP3_MIN_POINTS
 #define PRHF_TOP3_MIN_POINTS 8192   // ... and from this many on, the two segments below it as well
 #endif
+#ifndef PRHF_STRIDED_MIN_SEGMENT
+#define PRHF_STRIDED_MIN_SEGMENT 64 // segments below the top three take the strided sum while they hold this many points
+#endif
 #ifndef PRHF_MIN_WAVES_PER_SIMD
 #define PRHF_MIN_WAVES_PER_SIMD 4   // two 8-wave workgroups per CU: caps VGPRs at 128
 #endif
@@ -97,6 +100,8 @@ struct SegDev {
     int prio;                        // wave priority (0..3) of this slice's workgroups in a mixed launch: see vfo_kernel
     long long sp_off;                // > 0: this slice's piece of the strided table, in entries from KArgs::pairs
                                      // (launch_grid_strided; the main loop's strided sum); 0: none
+    int strided_lower;               // with sp_off > 0: the segments below the top three take the strided sum too
+                                     // (option strided_lower)
     int thread_scan;                 // X mode: reflection heights settled one frequency per thread while the candidate
                                      // list is made (on by default; PRHF_THREAD_SCAN_MIN turns it off for A/B runs.
                                      // O mode always does, by binary search)

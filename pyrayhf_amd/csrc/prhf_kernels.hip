@@ -159,6 +159,8 @@ __device__ __forceinline__ double uniform(double v) {
     return __hiloint2double(hi, lo);
 }
 __device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
+// bit of the main loop's sp_off argument: the segments below the top three take the strided sum too (SegDev::strided_lower)
+constexpr int kStridedLowerBit = 1 << 30;
 
 // 1/sqrt(x) to ~0.6 ulp: v_rsq_f64 is good to 2^-24 on gfx950 (tools/probe_math.hip), one
 // third-order step cubes that.  NaN for x < 0, +inf for x == 0; no range fix-ups (arguments
@@ -1303,13 +1305,18 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
     constexpr bool STRIDED = TOP && MODE == PRHF_KMODE_X && !CHECK && !G;
     const int i_last_s = last_special;                 // N - 1
     bool strided_on = false;
+    bool lower_on = false;                             // ... and its origin too (bit 1 clear), option strided_lower set
     double sc1 = 0.0;
     sp_off = uniform(sp_off);
+    const bool lower_req = (sp_off & kStridedLowerBit) != 0;
+    sp_off &= ~kStridedLowerBit;
     if (STRIDED && sp_off > 0 && n_seg > 0 && first == 0 && last_special >= 0 && end >= PRHF_TOP3_MIN_POINTS) {
         const u32x4 vh = __builtin_amdgcn_raw_buffer_load_b128(rsrc, 0, sp_off * (int)sizeof(double2), 0);
         double2 gh;
         __builtin_memcpy(&gh, &vh, sizeof gh);
-        strided_on = uniform((int)vh.x) == 0;
+        const int hw = uniform((int)vh.x);
+        strided_on = (hw & 1) == 0;
+        lower_on = lower_req && hw == 0;
         sc1 = uniform(gh.y);
     }
     // The strided sum of a top segment ("every eighth point"): inside one segment the summand
@@ -1401,6 +1408,136 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
         first = e_s;
         g0 = grid_at(first);
     };
+    // The segments below the top three (option strided_lower): the run R of consecutive segments directly
+    // below them that hold at least PRHF_STRIDED_MIN_SEGMENT points each takes the same rule without any work per
+    // segment.  Segment j begins at the real-valued index x_j of the stretch's closed form; around the boundary x of two
+    // segments, b = 8 floor((x - 4.5) / 8) is the last strided point of the lower one and a = 8 ceil((x + 4.5) / 8) the
+    // first of the upper one (both stencils inside their segment, a - b = 16 or 24).  [S_R, E_R), multiples of 64, is
+    // summed in two passes of indexed steps: every multiple of 8 from the strided table (weight 8 w), then one 32-lane
+    // group per boundary over the points b-3 .. a+3, whose coefficients hold the end corrections of both segments, the
+    // ordinary points between them and -8 for the multiples of 8 the first pass took.  S_R is the a of the segment it
+    // falls in, E_R - 8 the b of the segment below the top three; those two ends share one group.  The guards of the
+    // top segments are evaluated one segment per lane; a single segment that is not clear of its band leaves the whole
+    // pair to the indexed steps.  Everything here is a function of the pair alone.
+    if constexpr (STRIDED && !HINT) {
+        bool lower = lower_on && strided_on && n_seg == kTopSegments;
+        int S_R = 0, E_R = 0, n_R = 0;
+        const double n1 = (double)i_last_s, rkj = uniform(1.0 / kj);
+        int j_b0 = seg_j[2];                           // boundary l (l = 0, 1, ..) is where segment j_b0 - l begins
+        auto index_of = [&](double m) {
+            const double A = __builtin_fma(1.0 - m, 22025.465794806718, 1.0);
+            if (!(A > 0.0)) return 1e9;
+            const double ln_a = (double)__builtin_amdgcn_logf((float)A) * 0.6931471805599453;
+            return fmin(fmax(__builtin_fma(-ln_a, n1 * 0.1, n1), -1e9), 1e9);
+        };
+        auto x_of = [&](int j) { return index_of((double)j * rkj); };
+        if (lower) {
+            constexpr int kGuard = 256;
+            constexpr double kTau = 1e-6;
+            // lane l: the segment s_l = j_b0 - 1 - l between boundaries l + 1 (below) and l (above)
+            const int js = j_b0 - 1 - lane;
+            const double x_hi = x_of(max(js + 1, 0)), x_lo = x_of(max(js, 0));
+            const unsigned long long qual = __ballot(js >= 0 && x_hi - x_lo >= (double)PRHF_STRIDED_MIN_SEGMENT);
+            const int n_0 = min(~qual == 0ull ? 64 : __ffsll((long long)~qual) - 1, 62);
+            const int b_gen = 8 * (int)__builtin_floor((x_hi - 4.5) * 0.125);
+            const int a_gen = 8 * (int)__builtin_ceil((x_lo + 4.5) * 0.125);
+            // were s_l the lowest / the highest of R: the multiple of 64 that is its a / its b + 8 (b + 3 stays below
+            // the segment's last point: the table's own one under the top three segments, x_hi - 1.5 elsewhere)
+            const int S_l = 64 * (int)__builtin_ceil((x_lo + 4.5) * 0.015625);
+            const int E_l = lane == 0 ? (seg_lo[2] + 4) & ~63 : 64 * (int)__builtin_floor((x_hi + 3.5) * 0.015625);
+            // R runs from the highest segment with room for such a b to the lowest one with room for such an a
+            const unsigned long long room_b = __ballot(lane < n_0 && a_gen + 16 <= E_l);
+            const int l_top = room_b ? __ffsll((long long)room_b) - 1 : 64;
+            const unsigned long long room_a = __ballot(lane < n_0 && lane >= l_top && S_l + 8 <= b_gen);
+            const int l_bot = room_a ? 63 - __builtin_clzll(room_a) : -1;
+            n_R = l_bot >= l_top ? l_bot - l_top + 1 : 0;
+            S_R = __builtin_amdgcn_readlane(S_l, max(l_bot, 0));
+            E_R = __builtin_amdgcn_readlane(E_l, min(l_top, 63));
+            const int a_l = lane == l_bot ? S_R : a_gen, b_l = lane == l_top ? E_R - 8 : b_gen;
+            // guards, from the segment's node: 1 - X - Y = gap - sl m on its continuation (strided_run)
+            const unsigned nd = __umul24((unsigned)max(js, 0), (unsigned)sizeof(Node));
+            const double o = nodes_v.f64(nd + 8), den = nodes_v.f64(nd + 16), sden = nodes_v.f64(nd + 24),
+                         bf = nodes_v.f64(nd + 32), sb = nodes_v.f64(nd + 40);
+            const double r2 = 1.4142135623730951;
+            const double sl = cX * (sden * span) + r2 * (cYs * (sb * span));
+            const double gap = 1.0 - cX * (den + sden * o) - r2 * (cYs * (bf + sb * o));
+            bool bad;
+            if (__builtin_fabs(sl) > 1e-300) {
+                const double m_sing = gap / sl, dm = kTau / __builtin_fabs(sl);
+                const double i_sing = index_of(m_sing);
+                const double below = __builtin_floor(fmin(i_sing - (double)(kGuard + 1), index_of(m_sing - dm)));
+                const double above = __builtin_ceil(fmax(i_sing + (double)(kGuard + 1), index_of(m_sing + dm)));
+                bad = !((double)(b_l + 3) <= below || (double)(a_l - 3) >= above);
+            } else {
+                bad = !(__builtin_fabs(gap) >= kTau);
+            }
+            const int any_bad = __ballot(bad && lane >= l_top && lane <= l_bot) != 0ull;
+            // (everything back to scalars before it steers a loop)
+            n_R = uniform(n_R);
+            S_R = uniform(S_R);
+            E_R = uniform(E_R);
+            // the closed form must name the table's own first point of the segment above R
+            const double x_0 = uniform(x_of(j_b0));
+            j_b0 = uniform(j_b0 - min(l_top, 63));     // from here on boundary 0 is the upper end of R's highest segment
+            lower = uniform(any_bad) == 0 && n_R > 0 && E_R - S_R >= 256 &&
+                    __builtin_fabs(x_0 - (double)seg_lo[2]) < 1.5;
+        }
+        if (lower) {
+            const int count = (E_R - S_R) >> 3;        // strided points S_R, S_R + 8, .. E_R - 8
+            const int j_whole = (S_R >> 3) + (count & ~63), rest = count & 63;
+#pragma unroll 1
+            for (int pass = 0; pass < 2; ++pass) {     // (one copy of the loop for both)
+                if (pass == 1) {
+                    tab_off = (sp_off + 1) * (int)sizeof(double2);
+                    first = S_R >> 3;
+                    g0 = grid_at(first);
+                }
+                run_indexed(pass == 0 ? S_R : j_whole); // one by one up to S_R, then the strided table's entries
+            }
+            tab_off = 0;
+            // coefficients of the points b-3+p around a boundary with a - b = 16 and 24, and of the two ends of R
+            // (a-3 .. a+3 around S_R, then b-3 .. b+7 around E_R - 8): per lane, once per pair
+            const int p = lane & 31;
+            auto mag = [](int q) { return q == 1 ? 13.1796875 : (q == 2 ? -6.475 : (q == 3 ? 0.7984375 : 0.0)); };
+            auto around = [&](int pp, int pa) {        // pa: where a sits
+                if (pp < 3) return mag(3 - pp);
+                if (pp == 3) return -3.5;
+                if (pp <= 6) return 1.0 - mag(pp - 3);
+                if (pp < pa - 3) return (pp & 7) == 3 ? -7.0 : 1.0;
+                if (pp < pa) return 1.0 - mag(pa - pp);
+                if (pp == pa) return -3.5;
+                return mag(pp - pa);                   // (0 beyond a + 3)
+            };
+            const double c16 = around(p, 19), c24 = around(p, 27);
+            const double c_ends = p < 3 ? -mag(3 - p) : (p == 3 ? -3.5 : (p < 7 ? mag(p - 3) : (p < 18 ? around(p - 7, 64) : 0.0)));
+            const double c0 = 1.0 / 22025.465794806718;
+            const int n_items = 32 * n_R + rest;
+            for (int t0 = 0; t0 < n_items; t0 += 64) {
+                const int grp = (t0 >> 5) + (lane >> 5);
+                int idx = S_R;
+                double coef = 0.0;
+                if (grp < n_R - 1) {
+                    const double x = x_of(j_b0 - 1 - grp);
+                    const int b = 8 * (int)__builtin_floor((x - 4.5) * 0.125), a = 8 * (int)__builtin_ceil((x + 4.5) * 0.125);
+                    idx = b - 3 + p;
+                    coef = a - b == 24 ? c24 : c16;
+                } else if (grp == n_R - 1) {
+                    idx = p < 7 ? S_R - 3 + p : (p < 18 ? E_R - 18 + p : S_R);
+                    coef = c_ends;
+                } else if (t0 + lane - 32 * n_R < rest) {
+                    idx = (j_whole + (t0 + lane - 32 * n_R)) << 3;
+                    coef = 8.0;
+                }
+                const u32x4 vm = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (unsigned)idx * (unsigned)sizeof(double2), 0, 0);
+                double2 gm;
+                __builtin_memcpy(&gm, &vm, sizeof gm);
+                gm.y = coef * (sc1 * ((1.0 - gm.x) + c0));
+                accm = lean_step<MODE, false, POLY, HINT, G>(gm, span, a0v, kj, cX, hcY2, accm, wc, viol, nodes_v, cur);
+            }
+            first = E_R;
+            g0 = grid_at(first);
+        }
+    }
     if (TOP) {
         // (one copy of the two loops: the run's bounds are picked with scalar selects, not by unrolling)
 #pragma unroll 1
@@ -1897,7 +2034,9 @@ __device__ __forceinline__ void run_items(const KArgs& a, const SegDev& sg, cons
     const double* mult = a.mult + sg.mult_off;
     const double2* pairs = (a.pairs && sg.lean) ? reinterpret_cast<const double2*>(a.pairs) + sg.mult_off : nullptr;
     // the strided table's piece of this slice's grid, in entries from `pairs`; 0: none
-    const int sp_off = (pairs && sg.sp_off > 0) ? uniform((int)(sg.sp_off - sg.mult_off)) : 0;
+    // (bit 30: the segments below the top three take the strided sum too - an offset stays below 2^27 entries)
+    const int sp_off = (pairs && sg.sp_off > 0)
+                           ? uniform((int)(sg.sp_off - sg.mult_off) | (sg.strided_lower ? kStridedLowerBit : 0)) : 0;
     const long long pair_base = prof_local * F;
     const int first_item = block_in_prof * W, round_items = blocks_per_prof * W;
     // Few pairs on a long grid (one profile, the reference's own call; SegDev::slots > 0): a pair is cut into C <= S
@@ -2196,7 +2335,8 @@ hipError_t launch_grid_pairs(const double* mult, long long n, double* pairs, hip
 // width m_i+1 - m_i of the reference's stretch (library.py:296-321) as a function of m_i.  One workgroup per piece:
 // it also compares every width of the grid with w(m_i) and leaves 1 in the header's first word when one deviates
 // by more than 1e-14 (any other stretch does by 1e-4; the reference's by 2e-15), 0 otherwise; the header's second
-// double is c1.
+// double is c1.  Bit 1 of that word: the stretch's origin - m_0 = 0, m_N-1 = 1 to 1e-14 - does not hold, so the closed
+// form of a point's index (lean_loop_body, the segments below the top three) is not this grid's.
 __global__ __launch_bounds__(1024) void grid_strided_kernel(const double* __restrict__ mult, double2* __restrict__ pairs,
                                                             const StridedPieces pc) {
     const int p = blockIdx.x, tid = threadIdx.x;
@@ -2223,7 +2363,8 @@ __global__ __launch_bounds__(1024) void grid_strided_kernel(const double* __rest
     }
     if (tid == 0) {
         double2 h;
-        const unsigned long long word = any_bad ? 1ull : 0ull;
+        const bool origin = __builtin_fabs(m[0]) <= 1e-14 && __builtin_fabs(m[N - 1] - 1.0) <= 1e-14;    // (a NaN fails)
+        const unsigned long long word = (any_bad ? 1ull : 0ull) | (origin ? 0ull : 2ull);
         __builtin_memcpy(&h.x, &word, sizeof word);
         h.y = c1;
         out[0] = h;

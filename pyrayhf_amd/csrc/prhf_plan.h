@@ -74,6 +74,10 @@ struct Knobs {
     double strided_top = 1;            // X mode, fast tier, whole pairs of at least 8192 points on the reference's stretch:
                                        // the top segments are summed from every eighth point plus end corrections
                                        // (0: every point, the launch of before bit for bit)
+    double strided_lower = 1;          // ... and on a uniform altitude grid the segments of at least
+                                       // PRHF_STRIDED_MIN_SEGMENT points below those three as well, in one strided pass
+                                       // and one pass over the segment boundaries (0: the launch of strided_top alone,
+                                       // bit for bit; strided_top = 0 switches both off)
 };
 struct KnobName {
     const char* name;
@@ -107,6 +111,7 @@ const KnobName kKnobNames[] = {
     {"snell_table", &Knobs::snell_table, 0, 1e9},
     {"tall_lean", &Knobs::tall_lean, 0, 1},
     {"strided_top", &Knobs::strided_top, 0, 1},
+    {"strided_lower", &Knobs::strided_lower, 0, 1},
 };
 constexpr int kWavesPerBlock = PRHF_BLOCK_THREADS / 64;
 

@@ -34,8 +34,8 @@ extern "C" {
 #define PRHF_ABI_VERSION 4   /* 2: + prhf_snell_fan_f64, prhf_recent_kernel_ms, PRHF_FLAG_SHARED_FIELD (round 2)
                               * 3: + prhf_ctx_set_option (round 3)
                               * 4: + prhf_field_pack_f64, prhf_field_sample_f64, prhf_trace_gradient_f64;
-                              *    prhf_trace_gradient_spherical_f64 joined later without a new number: a new symbol
-                              *    changes nothing for a caller of the others */
+                              *    prhf_trace_gradient_spherical_f64 and prhf_snell_home_f64 joined later without a new
+                              *    number: a new symbol changes nothing for a caller of the others */
 
 /* return codes */
 #define PRHF_OK        0
@@ -312,6 +312,37 @@ int prhf_snell_fan_f64(prhf_ctx* ctx, int32_t geometry, const double* group_freq
                        int64_t alt_stride_elems, int32_t mode, double earth_radius_km, double dz_target_km,
                        double apex_boost, int32_t max_substeps, double* out, double* path_x, double* path_z,
                        int64_t path_stride, uint32_t flags);
+
+/*
+ * Point-to-point homing (oblique ionograms): the rays of a (profile, frequency) group that land at a given ground
+ * range.  No counterpart in the reference; the definition is DESIGN.md section 4.8.  Groups as for
+ * prhf_snell_fan_f64 (group_freq_hz[g], group_profile_index[g] or NULL); link l is the pair (link_group[l] in
+ * [0, n_groups), link_range_km[l]); scan_elevation_deg holds n_scan >= 2 strictly increasing elevations.  Scan: D_i,
+ * the ground range of the group's fan ray at scan node i - the bits prhf_snell_fan_f64 gives for that ray.  Brackets
+ * of a link with target t, numbered in ascending elevation: the intervals i with D_i and D_i+1 finite and (D_i - t),
+ * (D_i+1 - t) of opposite signs or D_i == t; D_(n_scan-1) == t is a bracket of no width; a NaN target has none.
+ * Tangential contacts without a sign change on the scan grid are not found: what is found is a function of the grid.
+ * Each of the first max_roots (1 .. 64) brackets is narrowed by at most max_iter (1 .. 128) rays of the group that
+ * never leave it (Illinois steps, a bisection whenever a step did not halve the bracket) and gets row
+ * (l, rank) of out (n_links, max_roots, 11): elevation_deg, status, scan_index (the interval), then the eight outputs
+ * of prhf_snell_cartesian_f64 for the result ray.  status 0: a ray with |D - t| <= range_tol_km (>= 0, finite) was
+ * found - a scan node counts - and is the result; 1: the bracket cannot be split any further in float64, or max_iter
+ * is spent (a jump of D(e), not a crossing); 2: a ray inside the bracket does not turn; for 1 and 2 the result is the
+ * ray with the smallest miss among the bracket's two scan nodes and the rays tried.  Rows without a bracket are NaN
+ * with status -1; n_brackets[l] counts every bracket of the link, those beyond max_roots included.  The rows do not
+ * depend on scheduling.  geometry, the four spherical controls, mode, flags and errors as for prhf_snell_fan_f64;
+ * synchronous.  PRHF_EINVAL for a control outside the ranges above, for tables beyond 64 GiB, for a host scan grid
+ * that does not increase strictly and for a link_group or profile index out of range - checked on the host for host
+ * buffers, by the kernels for device-resident arrays (those links get NaN rows and no bracket; no memory outside the
+ * columns is read).
+ */
+int prhf_snell_home_f64(prhf_ctx* ctx, int32_t geometry, const double* group_freq_hz,
+                        const int64_t* group_profile_index, int64_t n_groups, const int64_t* link_group,
+                        const double* link_range_km, int64_t n_links, const double* scan_elevation_deg, int64_t n_scan,
+                        const double* den, const double* bmag, const double* bpsi, const double* alt, int64_t n_prof,
+                        int64_t n_alt, int64_t alt_stride_elems, int32_t mode, double earth_radius_km,
+                        double dz_target_km, double apex_boost, int32_t max_substeps, double range_tol_km,
+                        int32_t max_iter, int32_t max_roots, double* out, int64_t* n_brackets, uint32_t flags);
 
 /*
  * 2-D refractive-index fields mu(a0, a1) for the gradient tracer: node records.

@@ -17,9 +17,10 @@ from .gradient import (STATUS_NAMES, RefractiveField, build_mup_function,       
                        trace_fan_cartesian_gradient, trace_fan_spherical_gradient,
                        trace_ray_cartesian_gradient, trace_ray_spherical_gradient,
                        trace_rays_cartesian_gradient, trace_rays_spherical_gradient)
+from .tracers import home_rays_cartesian_snells, home_rays_spherical_snells                        # noqa: E402
 
 __all__ = ["logger", "__version__", "STATUS_NAMES", "RefractiveField", "build_mup_function",
            "build_refractive_index_interpolator_cartesian", "build_refractive_index_interpolator_spherical",
            "refractive_field", "trace_fan_cartesian_gradient", "trace_fan_spherical_gradient",
            "trace_ray_cartesian_gradient", "trace_ray_spherical_gradient", "trace_rays_cartesian_gradient",
-           "trace_rays_spherical_gradient"]
+           "trace_rays_spherical_gradient", "home_rays_cartesian_snells", "home_rays_spherical_snells"]

@@ -83,6 +83,12 @@ _PROTOTYPES = {
         ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_double, ctypes.c_double,
         ctypes.c_double, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
         ctypes.c_uint32]),
+    "prhf_snell_home_f64": (ctypes.c_int, [
+        ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
+        ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int32, ctypes.c_double, ctypes.c_int32,
+        ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32]),
     "prhf_field_pack_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
                                            ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
                                            ctypes.c_int32, ctypes.c_void_p, ctypes.c_uint32]),
@@ -279,6 +285,16 @@ class Context:
                                             elev, n_rays, den, bmag, bpsi, alt, n_prof, n_alt, alt_stride, mode,
                                             float(r_e), float(dz_target), float(apex_boost), int(max_substeps), out,
                                             path_x or None, path_z or None, path_stride, flags)
+
+    def snell_home(self, geometry, group_freq, group_prof, n_groups, link_group, link_range, n_links, scan_elev, n_scan,
+                   den, bmag, bpsi, alt, n_prof, n_alt, alt_stride, mode, r_e, dz_target, apex_boost, max_substeps,
+                   range_tol, max_iter, max_roots, out, n_brackets, flags):
+        """``out``: (n_links, max_roots, 11) doubles, ``n_brackets``: (n_links) int64 (include/prhf.h)."""
+        return self._lib.prhf_snell_home_f64(self._h, int(geometry), group_freq, group_prof or None, n_groups, link_group,
+                                             link_range, n_links, scan_elev, n_scan, den, bmag, bpsi, alt, n_prof, n_alt,
+                                             alt_stride, mode, float(r_e), float(dz_target), float(apex_boost),
+                                             int(max_substeps), float(range_tol), int(max_iter), int(max_roots), out,
+                                             n_brackets, flags)
 
     def field_pack(self, mu, mup, n_fields, n0, n1, axis0, axis1, edge_order, records, flags):
         """``records``: a device address in every flag combination; the axes: host addresses."""

@@ -1637,6 +1637,149 @@ int prhf_snell_fan_f64(prhf_ctx* c, int32_t geometry, const double* group_freq_h
                      alt_stride_elems, mode, out, path_x, path_z, path_stride, flags, ray_group, n_groups);
 }
 
+int prhf_snell_home_f64(prhf_ctx* c, int32_t geometry, const double* group_freq_hz, const int64_t* group_profile_index,
+                        int64_t n_groups, const int64_t* link_group, const double* link_range_km, int64_t n_links,
+                        const double* scan_elevation_deg, int64_t n_scan, const double* den, const double* bmag,
+                        const double* bpsi, const double* alt, int64_t n_prof, int64_t n_alt, int64_t alt_stride_elems,
+                        int32_t mode, double earth_radius_km, double dz_target_km, double apex_boost, int32_t max_substeps,
+                        double range_tol_km, int32_t max_iter, int32_t max_roots, double* out, int64_t* n_brackets,
+                        uint32_t flags) {
+    if (!c) return fail(PRHF_EINVAL, "null context");
+    if (!group_freq_hz || !link_group || !link_range_km || !scan_elevation_deg || !den || !bmag || !bpsi || !alt || !out ||
+        !n_brackets)
+        return fail(PRHF_EINVAL, "null array pointer");
+    if (geometry != 0 && geometry != 1) return fail(PRHF_EINVAL, "geometry is 0 (flat Earth) or 1 (spherical Earth)");
+    if (geometry == 1 && (!(earth_radius_km > 0.0) || !(earth_radius_km < 1e300) || !(dz_target_km > 0.0) || !(apex_boost >= 0.0) ||
+                          max_substeps < 1))
+        return fail(PRHF_EINVAL, "bad spherical tracer controls");
+    if (n_scan < 2) return fail(PRHF_EINVAL, "the scan grid needs at least 2 elevations");
+    if (max_iter < 1 || max_iter > 128) return fail(PRHF_EINVAL, "max_iter is 1 .. 128");
+    if (max_roots < 1 || max_roots > 64) return fail(PRHF_EINVAL, "max_roots is 1 .. 64");
+    if (!(range_tol_km >= 0.0) || !std::isfinite(range_tol_km))
+        return fail(PRHF_EINVAL, "range_tol_km must be finite and not negative");
+    if (n_groups < 1) return fail(PRHF_EINVAL, "homing needs at least one group");
+    // per group and level: mu' (8 B), the compacted entry (32 B), its grid level (4 B); per group: four scalars (snell_run)
+    const size_t level_cells = (size_t)n_groups * (size_t)(n_alt + 1);
+    const size_t mup_cells = (level_cells + 1) & ~(size_t)1;
+    const size_t level_bytes = mup_cells * 8 + level_cells * 36 + (size_t)n_groups * 16;
+    if (level_bytes > ((size_t)64 << 30) || n_groups > 0x7fffffffLL)
+        return fail(PRHF_EINVAL, "level tables of %lld groups exceed 64 GiB (or 2^31 - 1 groups): home in batches",
+                    (long long)n_groups);
+    if (n_links < 0 || n_prof < 1 || n_prof > 0x7fffffffLL || n_alt < 2 || n_alt > 3000) return fail(PRHF_EINVAL, "bad shape");
+    if (n_groups * n_scan > 0x7fffffffLL || n_links * (int64_t)max_roots > 0x7fffffffLL)
+        return fail(PRHF_EINVAL, "more than 2^31 - 1 scan rays or result rows: home in batches");
+    if (mode != PRHF_MODE_O && mode != PRHF_MODE_X) return fail(PRHF_EINVAL, "Mode must be O or X");
+    if (alt_stride_elems != 0 && alt_stride_elems != n_alt) return fail(PRHF_EINVAL, "alt stride is 0 or n_alt");
+    if (flags & ~PRHF_FLAG_DEVICE_PTRS) return fail(PRHF_EINVAL, "unknown flag bits");
+    const bool dev = (flags & PRHF_FLAG_DEVICE_PTRS) != 0;
+    if (!dev) {
+        for (int64_t i = 0; i + 1 < n_scan; ++i)
+            if (!(scan_elevation_deg[i + 1] > scan_elevation_deg[i]))
+                return fail(PRHF_EINVAL, "scan_elevation_deg must be strictly increasing");
+        if (group_profile_index)
+            for (int64_t g = 0; g < n_groups; ++g)
+                if (group_profile_index[g] < 0 || group_profile_index[g] >= n_prof)
+                    return fail(PRHF_EINVAL, "profile_index[%lld] outside [0, n_prof)", (long long)g);
+        for (int64_t l = 0; l < n_links; ++l)
+            if (link_group[l] < 0 || link_group[l] >= n_groups)
+                return fail(PRHF_EINVAL, "link_group[%lld] outside [0, n_groups)", (long long)l);
+    }
+    if (n_links == 0) return PRHF_OK;
+    ENTER_DEVICE(c->device);
+    prhf::HomeArgs h;
+    std::memset(&h, 0, sizeof h);
+    prhf::SnellArgs& a = h.s;
+    a.n_rays = 1; a.n_alt = n_alt; a.prof_stride = n_alt; a.alt_stride = alt_stride_elems;
+    a.mode = mode == PRHF_MODE_O ? PRHF_KMODE_O : PRHF_KMODE_X;
+    a.geometry = geometry;
+    a.earth_radius_km = geometry == 0 ? 6371.0 : earth_radius_km;
+    a.dz_target_km = geometry == 0 ? 1.0 : dz_target_km;
+    a.apex_boost = geometry == 0 ? 200.0 : apex_boost;
+    a.max_substeps = geometry == 0 ? 400 : max_substeps;
+    a.status = c->h_status_dev;
+    a.n_groups = n_groups; a.n_prof = n_prof; a.resident_cus = c->cu_count;
+    h.n_links = n_links; h.n_scan = (int)n_scan; h.range_tol = range_tol_km; h.max_iter = max_iter; h.max_roots = max_roots;
+    const size_t prof_elems = (size_t)n_prof * (size_t)n_alt;
+    const size_t alt_elems = alt_stride_elems ? prof_elems : (size_t)n_alt;
+    const size_t out_elems = (size_t)n_links * (size_t)max_roots * PRHF_HOME_OUTPUTS;
+    if (dev) {
+        a.den = den; a.bmag = bmag; a.bpsi = bpsi; a.alt = alt;
+        a.group_freq = group_freq_hz;
+        a.group_prof = reinterpret_cast<const long long*>(group_profile_index);
+        h.link_group = reinterpret_cast<const long long*>(link_group);
+        h.link_range = link_range_km; h.scan_elev = scan_elevation_deg;
+        h.out = out; h.n_brackets = reinterpret_cast<long long*>(n_brackets);
+    } else {
+        const size_t elems = 3 * prof_elems + alt_elems + 2 * (size_t)n_groups + 3 * (size_t)n_links + (size_t)n_scan + out_elems;
+        int rc = ensure(c, c->arena, elems * 8);
+        if (rc != PRHF_OK) return rc;
+        double* p = static_cast<double*>(c->arena.p);
+        double* d_den = p; p += prof_elems;
+        double* d_bmag = p; p += prof_elems;
+        double* d_bpsi = p; p += prof_elems;
+        double* d_alt = p; p += alt_elems;
+        double* d_f = p; p += n_groups;
+        long long* d_i = reinterpret_cast<long long*>(p); p += n_groups;
+        long long* d_lg = reinterpret_cast<long long*>(p); p += n_links;
+        double* d_lr = p; p += n_links;
+        double* d_e = p; p += n_scan;
+        long long* d_nb = reinterpret_cast<long long*>(p); p += n_links;
+        double* d_out = p;
+        HIP_TRY(hipMemcpyAsync(d_den, den, prof_elems * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_bmag, bmag, prof_elems * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_bpsi, bpsi, prof_elems * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_alt, alt, alt_elems * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_f, group_freq_hz, (size_t)n_groups * 8, hipMemcpyHostToDevice, c->stream));
+        if (group_profile_index)
+            HIP_TRY(hipMemcpyAsync(d_i, group_profile_index, (size_t)n_groups * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_lg, link_group, (size_t)n_links * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_lr, link_range_km, (size_t)n_links * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_e, scan_elevation_deg, (size_t)n_scan * 8, hipMemcpyHostToDevice, c->stream));
+        a.den = d_den; a.bmag = d_bmag; a.bpsi = d_bpsi; a.alt = d_alt;
+        a.group_freq = d_f; a.group_prof = group_profile_index ? d_i : nullptr;
+        h.link_group = d_lg; h.link_range = d_lr; h.scan_elev = d_e;
+        h.out = d_out; h.n_brackets = d_nb;
+    }
+    {
+        int rc = ensure(c, c->levels, level_bytes);
+        if (rc != PRHF_OK) return rc;
+        a.levels = static_cast<double*>(c->levels.p);
+        a.group_entries = a.levels + mup_cells;
+        a.group_info = reinterpret_cast<int*>(a.group_entries + 4 * level_cells);
+        a.group_kidx = a.group_info + 4 * (size_t)n_groups;
+    }
+    {
+        // per-profile scalars; behind them the refine launch's counters, the work list and the scan's ground ranges
+        const size_t info_bytes = (((size_t)n_prof * 32 + 127) / 128) * 128;
+        const size_t queue_bytes = ((prhf::home_queue_bytes() + 127) / 128) * 128;
+        const size_t work_bytes = (size_t)n_links * (size_t)max_roots * 16;
+        const size_t scan_bytes = (size_t)n_groups * (size_t)n_scan * 8;
+        int rc = ensure(c, c->partial, info_bytes + queue_bytes + work_bytes + scan_bytes);
+        if (rc != PRHF_OK) return rc;
+        char* q = static_cast<char*>(c->partial.p);
+        a.prof_info = reinterpret_cast<double*>(q);
+        h.queue = reinterpret_cast<unsigned*>(q + info_bytes);
+        h.work = reinterpret_cast<int*>(q + info_bytes + queue_bytes);
+        h.scan_d = reinterpret_cast<double*>(q + info_bytes + queue_bytes + work_bytes);
+    }
+    a.ptab = nullptr;
+    if (c->knobs.snell_table > 0 && (double)n_groups >= c->knobs.snell_table * (double)n_prof && prof_elems * 32 <= ((size_t)1 << 30)) {
+        int rc = ensure(c, c->ptab, prof_elems * 32);
+        if (rc != PRHF_OK) return rc;
+        a.ptab = static_cast<double*>(c->ptab.p);
+    }
+    HIP_TRY(hipEventRecord(c->begin_ev(), c->stream));
+    HIP_TRY(prhf::launch_snell_home(h, c->stream));
+    HIP_TRY(hipEventRecord(c->pending_end_ev(), c->stream));
+    c->mark_timed();
+    c->status_pending = true;
+    if (!dev) {
+        HIP_TRY(hipMemcpyAsync(out, h.out, out_elems * 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(n_brackets, h.n_brackets, (size_t)n_links * 8, hipMemcpyDeviceToHost, c->stream));
+    }
+    return prhf_sync(c);
+}
+
 namespace {
 // The two axes of a field: host memory, strictly increasing (a NaN fails the test), at least `least` values each and
 // together no more than the kernels stage in LDS.  *uniform: all np.diff(axis) are equal (np.gradient's scalar branch).

@@ -315,6 +315,26 @@ hipError_t launch_snell(const SnellArgs& a, hipStream_t stream);   // with a.ray
 hipError_t snell_resident_waves(long long n_alt, int cu_count, long long* waves, bool ptab = false, bool reduced = false,
                                 int geometry = 0);
 
+// Point-to-point homing for the grouped tracer (prhf_homing.inc): the rays of a group that land at a link's range.
+#define PRHF_HOME_OUTPUTS (3 + PRHF_SNELL_OUTPUTS)   // elevation_deg, status, scan_index, then the tracer's eight
+struct HomeArgs {
+    SnellArgs s;                 // a grouped launch's arguments (tables, columns, controls); elev_deg, ray_group, out unused
+    const double* scan_elev;     // (n_scan) scan grid [deg], strictly increasing
+    const long long* link_group; // (n_links) group of each link
+    const double* link_range;    // (n_links) target ground range [km]
+    long long n_links;
+    int n_scan;
+    double range_tol;            // [km]
+    int max_iter, max_roots;
+    double* scan_d;              // (n_groups, n_scan) scratch: ground range of every scan ray
+    int* work;                   // (n_links max_roots, 4) scratch: (link, rank, interval, 0) of the brackets to refine; 16-byte aligned
+    unsigned* queue;             // home_queue_bytes() of scratch: the refine launch's counters, the work list's length
+    double* out;                 // (n_links, max_roots, PRHF_HOME_OUTPUTS)
+    long long* n_brackets;       // (n_links)
+};
+size_t home_queue_bytes();
+hipError_t launch_snell_home(const HomeArgs& h, hipStream_t stream);   // tables, scan, brackets, refinement: five kernels
+
 // 2-D refractive-index fields and the gradient tracers (prhf_gradient.inc); device pointers throughout.
 struct FieldPackArgs {
     const double* mu;            // (n_fields, n0, n1)

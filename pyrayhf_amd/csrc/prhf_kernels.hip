@@ -2881,6 +2881,7 @@ hipError_t launch_vfo_shortx(const KArgs& a, long long grid_blocks, size_t lds_b
 }
 
 #include "prhf_snell.inc"
+#include "prhf_homing.inc"
 #include "prhf_gradient.inc"
 
 // Resident workgroups per CU the runtime predicts for the fused kernel (diagnostics).

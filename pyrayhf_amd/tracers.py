@@ -6,7 +6,9 @@ and result dictionaries (reference ``PyRayHF/library.py:1096-1268``, ``:1460-171
 (frequency, elevation[, profile]) rays in one launch, one wavefront per ray;
 ``trace_fan_cartesian_snells`` / ``trace_fan_spherical_snells`` trace every elevation of a fan for every
 frequency (and profile): the refractive-index levels, which depend on the profile and the frequency only, are
-computed once per (profile, frequency) and shared by the fan's rays.
+computed once per (profile, frequency) and shared by the fan's rays;
+``home_rays_cartesian_snells`` / ``home_rays_spherical_snells`` find, for every (profile, frequency) and every ground
+range, the rays that land there (point-to-point homing, the oblique ionogram of a link).
 """
 
 from __future__ import annotations
@@ -18,7 +20,7 @@ from .library import MATH_AUTO, _as_rows, constants
 
 __all__ = ["trace_ray_cartesian_snells", "trace_rays_cartesian_snells", "trace_ray_spherical_snells",
            "trace_rays_spherical_snells", "trace_fan_cartesian_snells", "trace_fan_spherical_snells",
-           "tan_from_mu_scalar", "find_turning_point"]
+           "home_rays_cartesian_snells", "home_rays_spherical_snells", "tan_from_mu_scalar", "find_turning_point"]
 
 _KEYS = ("group_path_km", "group_delay_sec", "x_midpoint", "z_midpoint", "ground_range_km", "x_turn_km",
          "z_turn_km", "n_path")
@@ -123,6 +125,106 @@ def trace_fan_spherical_snells(f0_Hz, elevation_deg, alt_km, Ne, Babs, bpsi, mod
     r_e = constants()[2] if R_E is None else float(R_E)
     return _trace_fan(True, f0_Hz, elevation_deg, alt_km, Ne, Babs, bpsi, mode, return_paths, device,
                       (r_e, dz_target_km, apex_boost, max_substeps), math)
+
+
+HOME_STATUS_NAMES = {0: "converged", 1: "discontinuity", 2: "escapes inside", -1: "unused"}
+
+
+def default_scan_elevations():
+    """The homing calls' default scan grid: 2 to 88 degrees in steps of 0.25."""
+    return np.linspace(2.0, 88.0, 345)
+
+
+def _home_rays(spherical, f0_Hz, ground_range_km, alt_km, Ne, Babs, bpsi, mode, scan_elevation_deg, max_roots,
+               range_tol_km, max_iter, device, controls):
+    if mode not in ("O", "X"):
+        raise ValueError("Mode must be O or X")
+    f = np.ascontiguousarray(np.atleast_1d(np.asarray(f0_Hz, dtype=np.float64)))
+    t = np.ascontiguousarray(np.atleast_1d(np.asarray(ground_range_km, dtype=np.float64)))
+    if f.ndim != 1 or t.ndim != 1 or f.size == 0 or t.size == 0:
+        raise ValueError("f0_Hz and ground_range_km must be 1-D and not empty (frequencies, target ranges)")
+    scan = default_scan_elevations() if scan_elevation_deg is None else \
+        np.ascontiguousarray(np.asarray(scan_elevation_deg, dtype=np.float64))
+    if scan.ndim != 1 or scan.size < 2:
+        raise ValueError("scan_elevation_deg needs at least 2 elevations")
+    if not np.all(np.diff(scan) > 0):
+        raise ValueError("scan_elevation_deg must be strictly increasing")
+    max_roots, max_iter, range_tol_km = int(max_roots), int(max_iter), float(range_tol_km)
+    if not 1 <= max_roots <= 64:
+        raise ValueError("max_roots is 1 .. 64")
+    if not 1 <= max_iter <= 128:
+        raise ValueError("max_iter is 1 .. 128")
+    if not (np.isfinite(range_tol_km) and range_tol_km >= 0.0):
+        raise ValueError("range_tol_km must be finite and not negative")
+    single = np.ndim(Ne) == 1
+    d2, b2, p2 = (np.atleast_2d(_as_rows(n, x)) for n, x in (("Ne", Ne), ("Babs", Babs), ("bpsi", bpsi)))
+    if not (d2.shape == b2.shape == p2.shape):
+        raise ValueError("Ne, Babs and bpsi must have the same shape")
+    n_prof, n_alt = d2.shape
+    a = _as_rows("alt_km", alt_km)
+    if a.shape[-1] != n_alt or (a.ndim == 2 and a.shape[0] != n_prof):
+        raise ValueError("alt_km must have one value per level")
+    if n_alt < 2:
+        raise ValueError("a profile needs at least 2 levels")
+    # groups: (profile, frequency) in C order; links: (profile, frequency, target) in C order
+    group_f = np.ascontiguousarray(np.tile(f, n_prof))
+    group_p = np.ascontiguousarray(np.repeat(np.arange(n_prof, dtype=np.int64), f.size))
+    n_groups = group_f.size
+    link_g = np.ascontiguousarray(np.repeat(np.arange(n_groups, dtype=np.int64), t.size))
+    link_t = np.ascontiguousarray(np.tile(t, n_groups))
+    n_links = link_g.size
+    out = np.empty((n_links, max_roots, 11), dtype=np.float64)
+    n_br = np.empty(n_links, dtype=np.int64)
+    r_e, dz_t, boost, nsub = controls if spherical else (6371.0, 1.0, 200.0, 400)
+    ctx = _native.host_context(device)
+    rc = ctx.snell_home(1 if spherical else 0, group_f.ctypes.data, group_p.ctypes.data, n_groups, link_g.ctypes.data,
+                        link_t.ctypes.data, n_links, scan.ctypes.data, scan.size, d2.ctypes.data, b2.ctypes.data,
+                        p2.ctypes.data, a.ctypes.data, n_prof, n_alt, n_alt if a.ndim == 2 else 0,
+                        _native.MODE_O if mode == "O" else _native.MODE_X, r_e, dz_t, boost, nsub, range_tol_km, max_iter,
+                        max_roots, out.ctypes.data, n_br.ctypes.data, 0)
+    _native.raise_for(rc)
+    lead = (f.size, t.size) if single else (n_prof, f.size, t.size)
+    out = out.reshape(lead + (max_roots, 11))
+    res = {"n_brackets": n_br.reshape(lead), "elevation_deg": out[..., 0].copy(),
+           "status": out[..., 1].astype(np.int64)}
+    idx = out[..., 2]
+    res["scan_index"] = np.where(np.isfinite(idx), idx, -1.0).astype(np.int64)
+    for i, k in enumerate(_KEYS):
+        res[k] = out[..., 3 + i].copy()
+    n_path = res["n_path"]
+    res["n_path"] = np.where(np.isfinite(n_path), n_path, 0.0).astype(np.int64)
+    return res
+
+
+def home_rays_cartesian_snells(f0_Hz, ground_range_km, alt_km, Ne, Babs, bpsi, mode, *, scan_elevation_deg=None,
+                               max_roots=4, range_tol_km=1e-6, max_iter=64, device=None):
+    """Point-to-point homing over a flat Earth: for every frequency of ``f0_Hz`` ``(F,)`` (and every profile when
+    ``Ne, Babs, bpsi`` are ``(P, N_alt)``) and every target of ``ground_range_km`` ``(T,)``, the rays that land at that
+    range - the oblique ionogram of the link (``prhf_snell_home_f64``).
+
+    The fan of ``scan_elevation_deg`` (strictly increasing, default ``np.linspace(2, 88, 345)``) is traced once per
+    (profile, frequency); an interval of the scan whose two rays land on either side of the target (or whose lower ray
+    lands on it) is a bracket, and each of the first ``max_roots`` brackets in ascending elevation is narrowed with at
+    most ``max_iter`` further rays.  What is found is a function of the scan grid: a tangential contact that causes no
+    sign change on it is not found.
+
+    Returns a dict: ``n_brackets`` ``([P,] F, T)`` - every bracket of the link, those beyond ``max_roots`` included -
+    and, with shape ``([P,] F, T, max_roots)``, ``elevation_deg``, ``status``, ``scan_index`` (the bracket's interval)
+    and the eight keys of ``trace_rays_cartesian_snells`` for the result ray.  ``status`` 0: the ray lands within
+    ``range_tol_km`` of the target; 1: the ground range jumps across the target inside the bracket (a ray stops
+    reflecting from a lower layer) - the ray given is the nearest one tried; 2: a ray inside the bracket does not
+    turn; -1: unused slot (NaN everywhere, ``scan_index`` -1, ``n_path`` 0)."""
+    return _home_rays(False, f0_Hz, ground_range_km, alt_km, Ne, Babs, bpsi, mode, scan_elevation_deg, max_roots,
+                      range_tol_km, max_iter, device, None)
+
+
+def home_rays_spherical_snells(f0_Hz, ground_range_km, alt_km, Ne, Babs, bpsi, mode="O", *, scan_elevation_deg=None,
+                               max_roots=4, range_tol_km=1e-6, max_iter=64, dz_target_km=1.0, apex_boost=200.0,
+                               max_substeps=400, R_E=None, device=None):
+    """The same over a spherical Earth, with the reference's apex-refinement controls (library.py:1470-1473)."""
+    r_e = constants()[2] if R_E is None else float(R_E)
+    return _home_rays(True, f0_Hz, ground_range_km, alt_km, Ne, Babs, bpsi, mode, scan_elevation_deg, max_roots,
+                      range_tol_km, max_iter, device, (r_e, dz_target_km, apex_boost, max_substeps))
 
 
 def _single(r, apex_keys):

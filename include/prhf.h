@@ -431,6 +431,66 @@ int prhf_trace_gradient_spherical_f64(prhf_ctx* ctx, const double* records, int6
                                       double fill_mup, double* out, double* path_t, double* path_r, double* path_phi,
                                       double* path_v_r, double* path_v_phi, int64_t path_stride, uint32_t flags);
 
+/*
+ * Point-to-point homing through a horizontally varying mu (oblique ionograms of a tilted ionosphere): the rays of a
+ * transmitter that land at a given coordinate, for the gradient tracers of both geometries.  No counterpart in the
+ * reference; the definition is DESIGN.md section 4.9, which carries section 4.8's semantics over.  geometry 0: the
+ * rays of prhf_trace_gradient_f64 (top, left, right = z_max_km, x_min_km, x_max_km; earth_radius_km ignored), 1: those
+ * of prhf_trace_gradient_spherical_f64 (top, left, right = r_max_km, phi_min, phi_max).  records, n_fields, n0, n1,
+ * axis0, axis1 (HOST memory), the controls s_max_km .. renormalize_every and the fills are that tracer's.
+ * Group g is a transmitter: field group_field[g] in [0, n_fields), launch point (group_x0_km[g], group_z0_km[g]).  Link l
+ * is the pair (link_group[l] in [0, n_groups), link_target_km[l]); the target is compared with the tracer's own
+ * ground_range_km (x of the landing node, earth_radius_km * phi in the spherical case; finite only for status ground).
+ * scan_elevation_deg holds n_scan >= 2 strictly increasing elevations (beyond 90 degrees is legal, as in the tracers).
+ *   Scan: D_i, ground_range_km of the group's ray at scan node i under the call's controls - the bits the tracer
+ * gives for that ray.  One scan serves all targets of a group.
+ *   Brackets of a link with target t, ranked in ascending elevation: the intervals i with D_i and D_i+1 finite and
+ * (D_i - t), (D_i+1 - t) of opposite signs, or D_i == t; D_(n_scan-1) == t is a bracket of no width; a NaN target has
+ * none.  What is found is a function of the scan grid.  n_brackets[l] counts every bracket of the link.
+ *   Refine: each of the first max_roots (1 .. 64) brackets, in float64 without contraction:
+ *     lo = e_i, hi = e_i+1, f_lo = D_i - t, f_hi = D_i+1 - t (no width: hi = lo, f_hi = f_lo); g_lo = f_lo, g_hi = f_hi;
+ *     best = the end with the smaller |f| (lo on a tie), best_miss = min(|f_lo|, |f_hi|); side = 0, bisect = false;
+ *     best_miss <= range_tol_km: status 0, no ray is traced.  Else at most max_iter (1 .. 128) times:
+ *       mid = lo + 0.5 * (hi - lo); unless lo < mid < hi: status 1, stop;
+ *       x = mid; if not bisect: xs = lo - g_lo * ((hi - lo) / (g_hi - g_lo)), and x = xs if lo < xs < hi;
+ *       D = ground_range_km of the group's ray at x; not finite: status 2, stop;
+ *       f = D - t; |f| < best_miss: best = x, best_miss = |f|; |f| <= range_tol_km: status 0, stop;
+ *       width = hi - lo; if (f < 0) == (f_lo < 0): lo = x, f_lo = g_lo = f, and g_hi = 0.5 * g_hi if side == -1; side = -1;
+ *       else: hi = x, g_hi = f, and g_lo = 0.5 * g_lo if side == +1; side = +1;
+ *       bisect = (hi - lo) > 0.5 * width;
+ *     max_iter rays traced without a stop: status 1.
+ * A bracket stops as soon as its status is decided.  status 0: a ray with |D - t| <= range_tol_km (>= 0, finite) was
+ * found, a scan node counts; 1: the bracket cannot be split further in float64 or max_iter is spent (a jump of D(e));
+ * 2: a ray inside the bracket does not land.  The result of a bracket is `best`: for 1 and 2 the ray with the smallest
+ * miss among the bracket's two scan nodes and the rays tried.
+ *   out is (n_links, max_roots, 15); row (l, rank): elevation_deg, status, scan_index (the interval i), then the twelve
+ * outputs of the tracer for the result ray, bit-identical to what the tracer returns for that elevation, launch point,
+ * field and controls (the full ray: midpoint, apex and delay included).  Rows without a bracket are NaN with status -1.
+ * No result depends on scheduling.  D(e) of these tracers is not continuous down to rounding (the step controller
+ * turns last-bit differences into other step sequences: about 3e-3 km at the default tolerances), so a range_tol_km
+ * below that yields status 1, not a better ray.
+ * Group, link and scan arrays, out and n_brackets are host memory, or device memory with PRHF_FLAG_DEVICE_PTRS.
+ * PRHF_EINVAL for a null context (before anything else), a control outside its range, a host scan grid that does not
+ * increase strictly, a range_tol_km that is negative or not finite, an earth_radius_km that is not positive and finite
+ * (geometry 1), and a link_group or group_field out of range - checked on the host for host buffers, by the kernels
+ * for device-resident arrays (those links get NaN rows and no bracket, no memory outside the records is read, and the
+ * error is reported at the synchronisation).  Synchronous.
+ */
+int prhf_gradient_home_f64(prhf_ctx* ctx, int32_t geometry, const double* records, int64_t n_fields, int64_t n0,
+                           int64_t n1, const double* axis0, const double* axis1, const int64_t* group_field,
+                           const double* group_x0_km, const double* group_z0_km, int64_t n_groups,
+                           const int64_t* link_group, const double* link_target_km, int64_t n_links,
+                           const double* scan_elevation_deg, int64_t n_scan, double earth_radius_km, double s_max_km,
+                           double rtol, double atol, double max_step_km, double z_ground_km, double top, double left,
+                           double right, int32_t renormalize_every, double fill_n, double fill_grad, double fill_mup,
+                           double range_tol_km, int32_t max_iter, int32_t max_roots, double* out, int64_t* n_brackets,
+                           uint32_t flags);
+
+/* Diagnostics of the context's last prhf_gradient_home_f64: counters[0] brackets refined (used rows), [1] rays the
+ * refine lanes traced, [2] ray slots (64 per trip of a refine wavefront's loop), [3] refine wavefronts with work.
+ * Lane utilisation of the refinement = [1] / [2].  No device call. */
+int prhf_gradient_home_counters(prhf_ctx* ctx, uint64_t* counters);
+
 /* Diagnostics: workgroups of the fused kernel the runtime expects to keep resident per CU for
  * profiles of n_alt levels (LDS-limited) in arithmetic tier `math`. */
 int prhf_occupancy(prhf_ctx* ctx, int64_t n_alt, int32_t math, int32_t* workgroups_per_cu);

@@ -13,7 +13,8 @@ __version__ = "0.1.0"
 
 from .gradient import (STATUS_NAMES, RefractiveField, build_mup_function,                       # noqa: E402
                        build_refractive_index_interpolator_cartesian,
-                       build_refractive_index_interpolator_spherical, refractive_field,
+                       build_refractive_index_interpolator_spherical, home_rays_cartesian_gradient,
+                       home_rays_spherical_gradient, refractive_field,
                        trace_fan_cartesian_gradient, trace_fan_spherical_gradient,
                        trace_ray_cartesian_gradient, trace_ray_spherical_gradient,
                        trace_rays_cartesian_gradient, trace_rays_spherical_gradient)
@@ -23,4 +24,5 @@ __all__ = ["logger", "__version__", "STATUS_NAMES", "RefractiveField", "build_mu
            "build_refractive_index_interpolator_cartesian", "build_refractive_index_interpolator_spherical",
            "refractive_field", "trace_fan_cartesian_gradient", "trace_fan_spherical_gradient",
            "trace_ray_cartesian_gradient", "trace_ray_spherical_gradient", "trace_rays_cartesian_gradient",
-           "trace_rays_spherical_gradient", "home_rays_cartesian_snells", "home_rays_spherical_snells"]
+           "trace_rays_spherical_gradient", "home_rays_cartesian_snells", "home_rays_spherical_snells",
+           "home_rays_cartesian_gradient", "home_rays_spherical_gradient"]

@@ -103,6 +103,12 @@ _PROTOTYPES = {
                                                          ctypes.c_int64] + [ctypes.c_void_p] * 6 + [ctypes.c_int64] +
                                           [ctypes.c_double] * 9 + [ctypes.c_int32] + [ctypes.c_double] * 3 +
                                           [ctypes.c_void_p] * 6 + [ctypes.c_int64, ctypes.c_uint32]),
+    "prhf_gradient_home_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64,
+                                              ctypes.c_int64, ctypes.c_int64] + [ctypes.c_void_p] * 5 + [ctypes.c_int64] +
+                               [ctypes.c_void_p] * 2 + [ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64] +
+                               [ctypes.c_double] * 9 + [ctypes.c_int32] + [ctypes.c_double] * 4 +
+                               [ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32]),
+    "prhf_gradient_home_counters": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
     "prhf_occupancy": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
                                       ctypes.POINTER(ctypes.c_int32)]),
     "prhf_sync": (ctypes.c_int, [ctypes.c_void_p]),
@@ -327,6 +333,24 @@ class Context:
                                                            *(float(v) for v in controls[:8]), int(controls[8]),
                                                            *(float(v) for v in fills), out, *paths, int(path_stride),
                                                            flags)
+
+    def gradient_home(self, geometry, records, n_fields, n0, n1, axis0, axis1, group_field, group_x0, group_z0, n_groups,
+                      link_group, link_target, n_links, scan_elev, n_scan, earth_radius, controls, fills, range_tol,
+                      max_iter, max_roots, out, n_brackets, flags):
+        """controls: (s_max_km, rtol, atol, max_step_km, z_ground_km, top, left, right, renormalize_every) - the tracer's;
+        ``out``: (n_links, max_roots, 15) doubles, ``n_brackets``: (n_links) int64 (include/prhf.h)."""
+        return self._lib.prhf_gradient_home_f64(self._h, int(geometry), records, n_fields, n0, n1, axis0, axis1,
+                                                group_field, group_x0, group_z0, n_groups, link_group, link_target,
+                                                n_links, scan_elev, n_scan, float(earth_radius),
+                                                *(float(v) for v in controls[:8]), int(controls[8]),
+                                                *(float(v) for v in fills), float(range_tol), int(max_iter),
+                                                int(max_roots), out, n_brackets, flags)
+
+    def gradient_home_counters(self):
+        """(brackets refined, rays traced by the refine lanes, ray slots, refine wavefronts) of the last gradient_home."""
+        buf = (ctypes.c_uint64 * 4)()
+        raise_for(self._lib.prhf_gradient_home_counters(self._h, buf))
+        return tuple(int(v) for v in buf)
 
     def occupancy(self, n_alt, math):
         n = ctypes.c_int32(0)

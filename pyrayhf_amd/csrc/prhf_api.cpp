@@ -166,6 +166,7 @@ struct prhf_ctx {
     unsigned long long* d_words = nullptr;   // 2 words: nanmax|Y| bits, any-not-NaN
     unsigned long long* h_words = nullptr;   // pinned
     bool status_pending = false;
+    uint64_t grad_home_counters[PRHF_GRAD_HOME_COUNTERS] = {};   // of the last prhf_gradient_home_f64 (prhf_gradient_home_counters)
 };
 
 namespace {
@@ -2001,6 +2002,129 @@ int prhf_trace_gradient_spherical_f64(prhf_ctx* c, const double* records, int64_
                           elevation_deg, ray_field, n_rays, s_max_km, rtol, atol, max_step_km, earth_radius_km + z_ground_km,
                           r_max_km, phi_min, phi_max, renormalize_every, fill_n, fill_grad, fill_mup, out, path_t, path_r,
                           path_phi, path_v_r, path_v_phi, path_stride, flags);
+}
+
+int prhf_gradient_home_f64(prhf_ctx* c, int32_t geometry, const double* records, int64_t n_fields, int64_t n0, int64_t n1,
+                           const double* axis0, const double* axis1, const int64_t* group_field, const double* group_x0_km,
+                           const double* group_z0_km, int64_t n_groups, const int64_t* link_group,
+                           const double* link_target_km, int64_t n_links, const double* scan_elevation_deg, int64_t n_scan,
+                           double earth_radius_km, double s_max_km, double rtol, double atol, double max_step_km,
+                           double z_ground_km, double top, double left, double right, int32_t renormalize_every,
+                           double fill_n, double fill_grad, double fill_mup, double range_tol_km, int32_t max_iter,
+                           int32_t max_roots, double* out, int64_t* n_brackets, uint32_t flags) {
+    if (!c) return fail(PRHF_EINVAL, "null context");
+    if (!records || !group_field || !group_x0_km || !group_z0_km || !link_group || !link_target_km || !scan_elevation_deg ||
+        !out || !n_brackets)
+        return fail(PRHF_EINVAL, "null array pointer");
+    if (geometry != PRHF_GEO_CARTESIAN && geometry != PRHF_GEO_SPHERICAL)
+        return fail(PRHF_EINVAL, "geometry is 0 (Cartesian) or 1 (spherical)");
+    if (geometry == PRHF_GEO_SPHERICAL && (!(earth_radius_km > 0) || !std::isfinite(earth_radius_km)))
+        return fail(PRHF_EINVAL, "earth_radius_km must be positive and finite");
+    if (flags & ~PRHF_FLAG_DEVICE_PTRS) return fail(PRHF_EINVAL, "unknown flag bits");
+    if (!(s_max_km > 0) || !std::isfinite(s_max_km)) return fail(PRHF_EINVAL, "s_max_km must be positive and finite");
+    if (!(max_step_km > 0)) return fail(PRHF_EINVAL, "`max_step` must be positive.");
+    if (!(rtol >= 0) || !(atol >= 0)) return fail(PRHF_EINVAL, "`atol` must be positive.");
+    if (renormalize_every < 0) return fail(PRHF_EINVAL, "renormalize_every must not be negative");
+    if (n_scan < 2) return fail(PRHF_EINVAL, "the scan grid needs at least 2 elevations");
+    if (max_iter < 1 || max_iter > 128) return fail(PRHF_EINVAL, "max_iter is 1 .. 128");
+    if (max_roots < 1 || max_roots > 64) return fail(PRHF_EINVAL, "max_roots is 1 .. 64");
+    if (!(range_tol_km >= 0.0) || !std::isfinite(range_tol_km))
+        return fail(PRHF_EINVAL, "range_tol_km must be finite and not negative");
+    if (n_groups < 1) return fail(PRHF_EINVAL, "homing needs at least one group");
+    if (n_links < 0) return fail(PRHF_EINVAL, "bad shape");
+    if (n_scan > 0x7fffffffLL || n_groups * ((n_scan + 63) / 64) > 0x7fffffffLL || n_links * (int64_t)max_roots > 0x7fffffffLL)
+        return fail(PRHF_EINVAL, "more than 2^31 - 1 scan rays or result rows: home in batches");
+    int u0 = 0, u1 = 0;
+    int rc = check_field_shape(axis0, axis1, n_fields, n0, n1, 2, &u0, &u1);
+    if (rc != PRHF_OK) return rc;
+    const bool dev = (flags & PRHF_FLAG_DEVICE_PTRS) != 0;
+    if (!dev) {
+        for (int64_t i = 0; i + 1 < n_scan; ++i)
+            if (!(scan_elevation_deg[i + 1] > scan_elevation_deg[i]))
+                return fail(PRHF_EINVAL, "scan_elevation_deg must be strictly increasing");
+        for (int64_t g = 0; g < n_groups; ++g)
+            if (group_field[g] < 0 || group_field[g] >= n_fields)
+                return fail(PRHF_EINVAL, "group_field[%lld] outside [0, n_fields)", (long long)g);
+        for (int64_t l = 0; l < n_links; ++l)
+            if (link_group[l] < 0 || link_group[l] >= n_groups)
+                return fail(PRHF_EINVAL, "link_group[%lld] outside [0, n_groups)", (long long)l);
+    }
+    for (uint64_t& w : c->grad_home_counters) w = 0;
+    if (n_links == 0) return PRHF_OK;
+    ENTER_DEVICE(c->device);
+    const size_t G = (size_t)n_groups, L = (size_t)n_links, E = (size_t)n_scan;
+    const size_t out_elems = L * (size_t)max_roots * PRHF_GRAD_HOME_OUTPUTS;
+    rc = ensure(c, c->arena, ((size_t)(n0 + n1) + (dev ? 0 : 3 * G + 3 * L + E + out_elems)) * 8);
+    if (rc != PRHF_OK) return rc;
+    double* p = static_cast<double*>(c->arena.p);
+    prhf::GradHomeArgs h;
+    std::memset(&h, 0, sizeof h);
+    prhf::GradTraceArgs& a = h.g;
+    HIP_TRY(hipMemcpyAsync(p, axis0, (size_t)n0 * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(p + n0, axis1, (size_t)n1 * 8, hipMemcpyHostToDevice, c->stream));
+    a.rec = records; a.a0 = p; a.a1 = p + n0; a.n0 = (int)n0; a.n1 = (int)n1; a.n_fields = n_fields;
+    a.s_max = s_max_km;
+    a.rtol = rtol < 100 * 2.220446049250313e-16 ? 100 * 2.220446049250313e-16 : rtol;     // (as the tracers: solve_ivp's floor)
+    a.atol = atol; a.max_step = max_step_km;
+    // (the spherical tracer binds R_E + z_ground_km to the ground event, prhf_trace_gradient_spherical_f64)
+    a.z_ground = geometry == PRHF_GEO_SPHERICAL ? earth_radius_km + z_ground_km : z_ground_km;
+    a.z_max = top; a.x_min = left; a.x_max = right; a.renormalize_every = renormalize_every;
+    a.fill_n = fill_n; a.fill_grad = fill_grad; a.fill_mup = fill_mup; a.status = c->h_status_dev;
+    a.geometry = geometry; a.earth_radius = geometry == PRHF_GEO_SPHERICAL ? earth_radius_km : 0.0;
+    h.n_groups = n_groups; h.n_links = n_links; h.n_scan = (int)n_scan; h.range_tol = range_tol_km; h.max_iter = max_iter;
+    h.max_roots = max_roots;
+    if (dev) {
+        h.group_field = reinterpret_cast<const long long*>(group_field); h.group_x0 = group_x0_km; h.group_z0 = group_z0_km;
+        h.link_group = reinterpret_cast<const long long*>(link_group); h.link_target = link_target_km;
+        h.scan_elev = scan_elevation_deg; h.out = out; h.n_brackets = reinterpret_cast<long long*>(n_brackets);
+    } else {
+        double* q = p + n0 + n1;
+        long long* d_gf = reinterpret_cast<long long*>(q); q += G;
+        double* d_x0 = q; q += G;
+        double* d_z0 = q; q += G;
+        long long* d_lg = reinterpret_cast<long long*>(q); q += L;
+        double* d_lt = q; q += L;
+        long long* d_nb = reinterpret_cast<long long*>(q); q += L;
+        double* d_e = q; q += E;
+        HIP_TRY(hipMemcpyAsync(d_gf, group_field, G * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_x0, group_x0_km, G * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_z0, group_z0_km, G * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_lg, link_group, L * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_lt, link_target_km, L * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_e, scan_elevation_deg, E * 8, hipMemcpyHostToDevice, c->stream));
+        h.group_field = d_gf; h.group_x0 = d_x0; h.group_z0 = d_z0; h.link_group = d_lg; h.link_target = d_lt;
+        h.scan_elev = d_e; h.n_brackets = d_nb; h.out = q;
+    }
+    {
+        // the counters, the work list and the scan's ground ranges
+        const size_t queue_bytes = 128, work_bytes = L * (size_t)max_roots * 16, scan_bytes = G * E * 8;
+        rc = ensure(c, c->partial, queue_bytes + work_bytes + scan_bytes);
+        if (rc != PRHF_OK) return rc;
+        char* q = static_cast<char*>(c->partial.p);
+        h.queue = reinterpret_cast<unsigned*>(q);
+        h.work = reinterpret_cast<int*>(q + queue_bytes);
+        h.scan_d = reinterpret_cast<double*>(q + queue_bytes + work_bytes);
+    }
+    HIP_TRY(hipEventRecord(c->begin_ev(), c->stream));
+    HIP_TRY(prhf::launch_grad_home(h, c->stream));
+    HIP_TRY(hipEventRecord(c->pending_end_ev(), c->stream));
+    c->mark_timed();
+    c->status_pending = true;
+    unsigned counters[PRHF_GRAD_HOME_COUNTERS] = {};
+    HIP_TRY(hipMemcpyAsync(counters, h.queue, sizeof counters, hipMemcpyDeviceToHost, c->stream));
+    if (!dev) {
+        HIP_TRY(hipMemcpyAsync(out, h.out, out_elems * 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(n_brackets, h.n_brackets, L * 8, hipMemcpyDeviceToHost, c->stream));
+    }
+    rc = prhf_sync(c);
+    for (int k = 0; k < PRHF_GRAD_HOME_COUNTERS; ++k) c->grad_home_counters[k] = counters[k];
+    return rc;
+}
+
+int prhf_gradient_home_counters(prhf_ctx* c, uint64_t* counters) {
+    if (!c || !counters) return fail(PRHF_EINVAL, "null pointer");
+    for (int k = 0; k < PRHF_GRAD_HOME_COUNTERS; ++k) counters[k] = c->grad_home_counters[k];
+    return PRHF_OK;
 }
 
 int prhf_occupancy(prhf_ctx* c, int64_t n_alt, int32_t math, int32_t* workgroups_per_cu) {

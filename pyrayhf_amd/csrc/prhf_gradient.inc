@@ -333,28 +333,23 @@ __device__ __forceinline__ double grad_event_root(const GradTraceArgs& a, const 
 
 #define PRHF_GRAD_MAX_ATTEMPTS (1 << 24)     // steps a lane may attempt before it gives up with status "failure"
 
-template <int GEO>
-__global__ __launch_bounds__(PRHF_GRAD_TRACE_THREADS) void grad_trace_kernel(const GradTraceArgs a) {
+// One ray of field `field` from (x0_km, z0_km) at `elev_deg` under the controls of `a`, on the axes g0, g1 staged in LDS:
+// the whole of a lane's work in grad_trace_kernel.  Returns the ray's ground_range_km (NaN unless it ends on the
+// ground).  FULL: the ray as the tracers return it - the twelve outputs to `out`, the path of ray `r` to a.path_* when
+// those are set.  !FULL: the range-only ray of the homing kernels (prhf_gradient_homing.inc) - the same stepper,
+// controller, events and dense-output bisection, hence the same steps and the same landing node to the bit, without mu'
+// sampling, chord lengths, the apex, path stores and the second pass that replays the steps up to the midpoint; `r` and
+// `out` are not used.  Both are this one text: what !FULL leaves out stands behind `if (FULL)`.
+template <int GEO, bool FULL>
+__device__ __forceinline__ double grad_ray(const GradTraceArgs& a, const double* g0, const double* g1, long long r,
+                                           long long field, double elev_deg, double x0_km, double z0_km, double* out) {
     constexpr bool SPH = GEO == PRHF_GEO_SPHERICAL;
-    extern __shared__ __attribute__((aligned(16))) double grad_axes[];
-    const double* g0 = grad_axes;
-    const double* g1 = grad_axes + a.n0;
-    for (int i = threadIdx.x; i < a.n0 + a.n1; i += blockDim.x) grad_axes[i] = i < a.n0 ? a.a0[i] : a.a1[i - a.n0];
-    __syncthreads();
-    const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= a.n_rays) return;
-    double* out = a.out + r * PRHF_GRAD_OUTPUTS;
     GradLane L;
-    L.f = a.ray_field ? a.ray_field[r] : 0;
-    if (L.f < 0 || L.f >= a.n_fields) {
-        post_status(a.status, (unsigned)PRHF_STATUS_BADFIELD);
-        for (int k = 0; k < PRHF_GRAD_OUTPUTS; ++k) out[k] = qnan();
-        return;
-    }
+    L.f = field;
     // :1354-1357; :2230-2234: (r, phi, v_r, v_phi) = (R_E + z0, x0 / R_E, sin, cos), not normalised
-    const double elev = a.elev[r] * (3.141592653589793 / 180.0);
+    const double elev = elev_deg * (3.141592653589793 / 180.0);
     const double vx0 = cos(elev), vz0 = sin(elev), vnorm = hypot(vx0, vz0);
-    const double xs = SPH ? a.earth_radius + a.z0[r] : a.x0[r], zs = SPH ? a.x0[r] / a.earth_radius : a.z0[r],
+    const double xs = SPH ? a.earth_radius + z0_km : x0_km, zs = SPH ? x0_km / a.earth_radius : z0_km,
                  vxs = SPH ? vz0 : vx0 / vnorm, vzs = SPH ? vx0 : vz0 / vnorm;
 
     // results of pass 0 (x and z of a spherical node: R_E phi and r - R_E, :2277-2278)
@@ -370,7 +365,7 @@ __global__ __launch_bounds__(PRHF_GRAD_TRACE_THREADS) void grad_trace_kernel(con
     // (:2309-2313): up to node searchsorted(cumsum(ds), path / 2), the start of the first chord at whose end the lane's
     // own running sum - the one that gave path_km - reaches half of it; no midpoint (NaN) for a path of length 0.
 #pragma nounroll
-    for (int pass = 0; pass < 2; ++pass) {
+    for (int pass = 0; pass < (FULL ? 2 : 1); ++pass) {
         const int target = (pass == 0 || SPH) ? 0x7fffffff : n_nodes / 2;
         const double half_km = 0.5 * path_km;
         double cum_km = 0.0;
@@ -399,7 +394,7 @@ __global__ __launch_bounds__(PRHF_GRAD_TRACE_THREADS) void grad_trace_kernel(con
         bool active = nodes <= target && !(SPH && pass == 1 && !(path_km > 0.0)), new_step = true, rejected = false;
         double min_step = 0.0;
         if (!SPH && !active) { x_mid = y0; z_mid = y1; }          // (target 0: the launch point)
-        if (pass == 0 && a.path_t) {
+        if (FULL && pass == 0 && a.path_t) {
             if (a.path_stride > 0) {
                 const long long o = r * a.path_stride;
                 a.path_t[o] = t; a.path_x[o] = y0; a.path_z[o] = y1; a.path_vx[o] = y2; a.path_vz[o] = y3;
@@ -514,16 +509,16 @@ __global__ __launch_bounds__(PRHF_GRAD_TRACE_THREADS) void grad_trace_kernel(con
                         // solve_ivp does not append an event node that coincides with the node before it
                         if (!(ended >= 0 && ended < 2 && tn == t && nodes > 1)) {
                             double ds = 0.0;                 // the chord to this node (the spherical replay needs it too)
-                            if (SPH) {                       // :2291-2294
+                            if (FULL && SPH) {               // :2291-2294
                                 const double dr = e0 - y0, rdphi = (0.5 * (y0 + e0)) * (e1 - y1);
                                 ds = sqrt(dr * dr + rdphi * rdphi);
-                            } else if (pass == 0) {
+                            } else if (FULL && pass == 0) {
                                 ds = hypot(e0 - y0, e1 - y1);                                 // :1413-1415
                             }
                             if (pass == 0) {
                                 // this node's x and z
                                 const double ex = SPH ? a.earth_radius * e1 : e0, ez = SPH ? e0 - a.earth_radius : e1;
-                                if (ds == ds) {
+                                if (FULL && ds == ds) {
                                     path_km += ds;
                                     double mup;
                                     if (SPH) {
@@ -536,9 +531,9 @@ __global__ __launch_bounds__(PRHF_GRAD_TRACE_THREADS) void grad_trace_kernel(con
                                     }
                                     if (fabs(mup) < __builtin_inf()) delay += (mup / 299792.458) * ds;      // :1418-1425
                                 }
-                                if (ez > z_apex) { z_apex = ez; x_apex = ex; }                 // np.nanargmax: the first maximum
+                                if (FULL && ez > z_apex) { z_apex = ez; x_apex = ex; }         // np.nanargmax: the first maximum
                                 x_last = ex;
-                                if (a.path_t) {
+                                if (FULL && a.path_t) {
                                     if (nodes < a.path_stride) {
                                         const long long o = r * a.path_stride + nodes;
                                         a.path_t[o] = tn; a.path_x[o] = e0; a.path_z[o] = e1; a.path_vx[o] = e2; a.path_vz[o] = e3;
@@ -573,6 +568,7 @@ __global__ __launch_bounds__(PRHF_GRAD_TRACE_THREADS) void grad_trace_kernel(con
         }
         if (pass == 0) { n_nodes = nodes; n_rhs = L.n_rhs; }
     }
+    if (!FULL) return status == 0 ? x_last : qnan();
     if (too_long) post_status(a.status, (unsigned)PRHF_STATUS_PATHLEN);
     out[0] = path_km;
     out[1] = delay;
@@ -586,6 +582,26 @@ __global__ __launch_bounds__(PRHF_GRAD_TRACE_THREADS) void grad_trace_kernel(con
     out[9] = (double)n_rhs;
     out[10] = (double)n_rej;
     out[11] = 0.0;
+    return status == 0 ? x_last : qnan();
+}
+
+template <int GEO>
+__global__ __launch_bounds__(PRHF_GRAD_TRACE_THREADS) void grad_trace_kernel(const GradTraceArgs a) {
+    extern __shared__ __attribute__((aligned(16))) double grad_axes[];
+    const double* g0 = grad_axes;
+    const double* g1 = grad_axes + a.n0;
+    for (int i = threadIdx.x; i < a.n0 + a.n1; i += blockDim.x) grad_axes[i] = i < a.n0 ? a.a0[i] : a.a1[i - a.n0];
+    __syncthreads();
+    const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= a.n_rays) return;
+    double* out = a.out + r * PRHF_GRAD_OUTPUTS;
+    const long long f = a.ray_field ? a.ray_field[r] : 0;
+    if (f < 0 || f >= a.n_fields) {
+        post_status(a.status, (unsigned)PRHF_STATUS_BADFIELD);
+        for (int k = 0; k < PRHF_GRAD_OUTPUTS; ++k) out[k] = qnan();
+        return;
+    }
+    (void)grad_ray<GEO, true>(a, g0, g1, r, f, a.elev[r], a.x0[r], a.z0[r], out);
 }
 
 }  // namespace

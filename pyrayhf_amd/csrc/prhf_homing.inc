@@ -58,6 +58,16 @@ __device__ __forceinline__ SnellArgs home_ray_args(const SnellArgs& s, double* s
     return b;
 }
 
+// The bracket rule of both homing calls (this file's, and prhf_gradient_homing.inc's): is interval i of the scan
+// d[0 .. n_scan) a bracket of the target t?  "Interval" n_scan - 1 stands for the bracket of no width at the last node.
+__device__ __forceinline__ bool home_is_bracket(const double* d, int n_scan, int i, double t) {
+    const double d0 = d[i];
+    if (i == n_scan - 1) return d0 == t;
+    const double d1 = d[i + 1];
+    const double f0 = d0 - t, f1 = d1 - t;
+    return finite64(d0) && finite64(d1) && ((f0 < 0.0 && f1 > 0.0) || (f0 > 0.0 && f1 < 0.0) || d0 == t);
+}
+
 }  // namespace
 
 #ifndef PRHF_HOME_WAVES
@@ -94,17 +104,7 @@ __global__ __launch_bounds__(64) void home_bracket_kernel(const HomeArgs h) {
     // "interval" E - 1 stands for the bracket of no width at the last node
     for (int base = 0; base < h.n_scan; base += 64) {
         const int i = base + lane;
-        bool is = false;
-        if (i < h.n_scan) {
-            const double d0 = d[i];
-            if (i == h.n_scan - 1) {
-                is = d0 == t;
-            } else {
-                const double d1 = d[i + 1];
-                const double f0 = d0 - t, f1 = d1 - t;
-                is = finite64(d0) && finite64(d1) && ((f0 < 0.0 && f1 > 0.0) || (f0 > 0.0 && f1 < 0.0) || d0 == t);
-            }
-        }
+        const bool is = i < h.n_scan && home_is_bracket(d, h.n_scan, i, t);
         const unsigned long long mask = __ballot(is);
         const int cnt = __popcll(mask);
         const int rank = found + __popcll(mask & ((1ull << lane) - 1ull));

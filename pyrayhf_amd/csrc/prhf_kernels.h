@@ -396,6 +396,31 @@ hipError_t launch_field_pack(const FieldPackArgs& a, hipStream_t stream);
 hipError_t launch_field_sample(const FieldSampleArgs& a, hipStream_t stream);
 hipError_t launch_grad_trace(const GradTraceArgs& a, hipStream_t stream);
 
+// Point-to-point homing for the gradient tracers (prhf_gradient_homing.inc): the rays of a transmitter that land at a
+// link's target coordinate.
+#define PRHF_GRAD_HOME_OUTPUTS (3 + PRHF_GRAD_OUTPUTS)   // elevation_deg, status, scan_index, then the tracer's twelve
+#define PRHF_GRAD_HOME_COUNTERS 4                        // records, rays refined, ray slots of the refine waves, refine waves
+struct GradHomeArgs {
+    GradTraceArgs g;             // records, axes, controls, fills, geometry, status; the per-ray arrays and the paths are null
+    const long long* group_field;   // (n_groups) field, launch point of each group
+    const double* group_x0;
+    const double* group_z0;
+    long long n_groups;
+    const long long* link_group; // (n_links) group of each link
+    const double* link_target;   // (n_links) target ground_range_km
+    long long n_links;
+    const double* scan_elev;     // (n_scan) scan grid [deg], strictly increasing
+    int n_scan;
+    double range_tol;            // [km]
+    int max_iter, max_roots;
+    double* scan_d;              // (n_groups, n_scan) scratch: ground range of every scan ray
+    int* work;                   // (n_links max_roots, 4) scratch: (link, rank, interval, 0) of the brackets to refine; 16-byte aligned
+    unsigned* queue;             // PRHF_GRAD_HOME_COUNTERS words of scratch, zeroed by the scan kernel
+    double* out;                 // (n_links, max_roots, PRHF_GRAD_HOME_OUTPUTS)
+    long long* n_brackets;       // (n_links)
+};
+hipError_t launch_grad_home(const GradHomeArgs& h, hipStream_t stream);   // scan, brackets, refinement, result rays: four kernels
+
 // residual / cost may be null
 hipError_t launch_residual(const double* vh_model, const double* vh_obs, long long n_prof, int n_freq,
                            double* residual, double* cost, hipStream_t stream);

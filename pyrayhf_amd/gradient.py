@@ -32,7 +32,8 @@ from .library import constants, find_mu_mup, find_X, find_Y
 __all__ = ["build_refractive_index_interpolator_cartesian", "build_refractive_index_interpolator_spherical",
            "build_mup_function", "refractive_field", "RefractiveField", "trace_ray_cartesian_gradient",
            "trace_rays_cartesian_gradient", "trace_fan_cartesian_gradient", "trace_ray_spherical_gradient",
-           "trace_rays_spherical_gradient", "trace_fan_spherical_gradient", "STATUS_NAMES"]
+           "trace_rays_spherical_gradient", "trace_fan_spherical_gradient", "home_rays_cartesian_gradient",
+           "home_rays_spherical_gradient", "STATUS_NAMES"]
 
 STATUS_NAMES = ("ground", "domain", "length", "failure")          # reference library.py:1391-1398
 _KEYS = ("group_path_km", "group_delay_sec", "x_midpoint", "z_midpoint", "ground_range_km", "x_apex_km", "z_apex_km",
@@ -462,6 +463,120 @@ def trace_fan_spherical_gradient(field, elevation_deg, x0_km=0.0, z0_km=0.0, s_m
                                          r_max_km=r_max_km, phi_min=phi_min, phi_max=phi_max, rtol=rtol, atol=atol,
                                          max_step_km=max_step_km, renormalize_every=renormalize_every,
                                          return_paths=return_paths)
+
+
+def _home(field, geometry, name, target_x_km, x0_km, z0_km, controls, scan_elevation_deg, max_roots, range_tol_km, max_iter,
+          earth_radius):
+    """Both homing calls: every field of ``field`` is a group launched from ``(x0_km, z0_km)``, the links are
+    (field, target) in C order.  ``controls``: the tracer's, as ``_trace`` takes them."""
+    from .tracers import default_scan_elevations
+    _need_geometry(field, geometry, name)
+    t = np.ascontiguousarray(np.atleast_1d(np.asarray(target_x_km, dtype=np.float64)))
+    if t.ndim != 1 or t.size == 0:
+        raise ValueError("target_x_km must be 1-D and not empty (the targets)")
+    scan = default_scan_elevations() if scan_elevation_deg is None else \
+        np.ascontiguousarray(np.asarray(scan_elevation_deg, dtype=np.float64))
+    if scan.ndim != 1 or scan.size < 2:
+        raise ValueError("scan_elevation_deg needs at least 2 elevations")
+    if not np.all(np.diff(scan) > 0):
+        raise ValueError("scan_elevation_deg must be strictly increasing")
+    max_roots, max_iter, range_tol_km = int(max_roots), int(max_iter), float(range_tol_km)
+    if not 1 <= max_roots <= 64:
+        raise ValueError("max_roots is 1 .. 64")
+    if not 1 <= max_iter <= 128:
+        raise ValueError("max_iter is 1 .. 128")
+    if not (np.isfinite(range_tol_km) and range_tol_km >= 0.0):
+        raise ValueError("range_tol_km must be finite and not negative")
+    s_max_km, rtol, atol, max_step_km, z_ground_km, top, left, right, renormalize_every = controls
+    max_step = np.inf if max_step_km is None else float(max_step_km)
+    if max_step <= 0:
+        raise ValueError("`max_step` must be positive.")                   # solve_ivp's message
+    ctl = (s_max_km, rtol, atol, max_step, z_ground_km, top, left, right, int(renormalize_every) if renormalize_every else 0)
+    n_groups = field.n_fields
+    group_f = np.arange(n_groups, dtype=np.int64)
+    group_x = np.full(n_groups, float(x0_km))
+    group_z = np.full(n_groups, float(z0_km))
+    link_g = np.ascontiguousarray(np.repeat(group_f, t.size))
+    link_t = np.ascontiguousarray(np.tile(t, n_groups))
+    out = np.empty((link_g.size, max_roots, 15), dtype=np.float64)
+    n_br = np.empty(link_g.size, dtype=np.int64)
+    rec = field.records()
+    ctx = field._ctx()
+    _native.raise_for(ctx.gradient_home(0 if earth_radius is None else 1, rec.data_ptr(), n_groups, field.axis0.size,
+                                        field.axis1.size, field.axis0.ctypes.data, field.axis1.ctypes.data,
+                                        group_f.ctypes.data, group_x.ctypes.data, group_z.ctypes.data, n_groups,
+                                        link_g.ctypes.data, link_t.ctypes.data, link_g.size, scan.ctypes.data, scan.size,
+                                        0.0 if earth_radius is None else earth_radius, ctl, field.fills, range_tol_km,
+                                        max_iter, max_roots, out.ctypes.data, n_br.ctypes.data, 0))
+    lead = (n_groups, t.size)
+    out = out.reshape(lead + (max_roots, 15))
+    res = {"n_brackets": n_br.reshape(lead), "elevation_deg": out[..., 0].copy(), "status": out[..., 1].astype(np.int64)}
+    idx = out[..., 2]
+    res["scan_index"] = np.where(np.isfinite(idx), idx, -1.0).astype(np.int64)
+    unused = res["status"] < 0
+    for i, k in enumerate(_KEYS):
+        v = out[..., 3 + i]
+        # (the tracer's integer keys: its status under its own name would collide with the bracket's)
+        if k == "status":
+            res["ray_status"] = np.where(unused, -1.0, v).astype(np.int64)
+        elif k in _INT_KEYS:
+            res[k] = np.where(unused, 0.0, v).astype(np.int64)
+        else:
+            res[k] = v.copy()
+    return res
+
+
+def home_rays_cartesian_gradient(field, target_x_km, x0_km=0.0, z0_km=0.0, s_max_km=5000.0, *, scan_elevation_deg=None,
+                                 max_roots=4, range_tol_km=0.05, max_iter=64, rtol=1e-7, atol=1e-9, max_step_km=None,
+                                 z_ground_km=0.0, z_min_km=-1.0, z_max_km=1000.0, x_min_km=-1e6, x_max_km=1e6,
+                                 renormalize_every=50):
+    """Point-to-point homing through a horizontally varying ionosphere over a flat Earth: for every field of ``field``
+    (a ``RefractiveField``, Cartesian; ``F`` of them), launched from ``(x0_km, z0_km)``, and every target of
+    ``target_x_km`` ``(T,)``, the rays that land at that x - the oblique ionogram of the link
+    (``prhf_gradient_home_f64``).  The controls are ``trace_rays_cartesian_gradient``'s.
+
+    The fan of ``scan_elevation_deg`` (strictly increasing, default ``tracers.default_scan_elevations()``; elevations
+    beyond 90 degrees look behind the transmitter) is traced once per field; an interval of the scan whose two rays land
+    on either side of the target (or whose lower ray lands on it) is a bracket, and each of the first ``max_roots``
+    brackets in ascending elevation is narrowed with at most ``max_iter`` further rays.  What is found is a function of
+    the scan grid.
+
+    ``range_tol_km`` defaults to 0.05 km: twice the reference tracer's own recorded range error at the default
+    tolerances (2.3e-2 km).  The landing coordinate of these tracers is not continuous in the
+    elevation down to rounding - the step-size controller turns last-bit differences into other step sequences, a
+    sawtooth of about 3e-3 km at the default controls - so a tolerance below the sawtooth of D(e) under the chosen
+    controls yields status 1, not a better ray.
+
+    Returns a dict: ``n_brackets`` ``(F, T)`` - every bracket of the link, those beyond ``max_roots`` included - and,
+    with shape ``(F, T, max_roots)``, ``elevation_deg``, ``status``, ``scan_index`` (the bracket's interval) and the
+    keys of ``trace_rays_cartesian_gradient`` for the result ray, bit for bit what that call returns at
+    ``elevation_deg`` (the tracer's own ``status`` is ``ray_status`` here).  ``status`` 0: the ray lands within
+    ``range_tol_km`` of the target; 1: the landing coordinate jumps across the target inside the bracket, or
+    ``max_iter`` is spent - the ray given is the nearest one tried; 2: a ray inside the bracket does not land; -1: unused
+    slot (NaN everywhere, ``scan_index`` and ``ray_status`` -1, the counts 0)."""
+    return _home(field, "cartesian", "home_rays_cartesian_gradient", target_x_km, x0_km, z0_km,
+                 _controls(s_max_km, rtol, atol, max_step_km, z_ground_km, z_max_km, x_min_km, x_max_km, renormalize_every),
+                 scan_elevation_deg, max_roots, range_tol_km, max_iter, None)
+
+
+def home_rays_spherical_gradient(field, target_x_km, x0_km=0.0, z0_km=0.0, s_max_km=6000.0, *, R_E=None,
+                                 scan_elevation_deg=None, max_roots=4, range_tol_km=0.05, max_iter=64, z_ground_km=0.0,
+                                 r_max_km=None, phi_min=-np.pi, phi_max=np.pi, rtol=1e-7, atol=1e-9, max_step_km=2.0,
+                                 renormalize_every=50):
+    """The same over a spherical Earth: ``field`` is spherical, the controls and their defaults are
+    ``trace_rays_spherical_gradient``'s, and a target is compared with that tracer's ``ground_range_km``, the surface arc
+    ``R_E phi`` of the landing node (``x0_km`` is a surface arc as well)."""
+    _need_geometry(field, "spherical", "home_rays_spherical_gradient")
+    if R_E is None:
+        R_E = field.R_E
+    if float(R_E) != field.R_E:
+        raise ValueError(f"R_E={R_E} is not the field's ({field.R_E})")
+    R_E = field.R_E
+    if r_max_km is None:
+        r_max_km = R_E + 1200.0                                             # :2226-2227
+    return _home(field, "spherical", "home_rays_spherical_gradient", target_x_km, x0_km, z0_km,
+                 _controls(s_max_km, rtol, atol, max_step_km, z_ground_km, r_max_km, phi_min, phi_max, renormalize_every),
+                 scan_elevation_deg, max_roots, range_tol_km, max_iter, R_E)
 
 
 def trace_ray_spherical_gradient(n_and_grad_rphi, mup_func, x0_km, z0_km, elevation_deg, s_max_km=6000.0, *, R_E=None,

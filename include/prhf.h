@@ -35,7 +35,8 @@ extern "C" {
                               * 3: + prhf_ctx_set_option (round 3)
                               * 4: + prhf_field_pack_f64, prhf_field_sample_f64, prhf_trace_gradient_f64;
                               *    prhf_trace_gradient_spherical_f64 and prhf_snell_home_f64 joined later without a new
-                              *    number: a new symbol changes nothing for a caller of the others */
+                              *    number: a new symbol changes nothing for a caller of the others (so did
+                              *    prhf_gradient_home_f64, prhf_snell_skip_f64 and prhf_snell_muf_f64) */
 
 /* return codes */
 #define PRHF_OK        0
@@ -343,6 +344,60 @@ int prhf_snell_home_f64(prhf_ctx* ctx, int32_t geometry, const double* group_fre
                         int64_t n_alt, int64_t alt_stride_elems, int32_t mode, double earth_radius_km,
                         double dz_target_km, double apex_boost, int32_t max_substeps, double range_tol_km,
                         int32_t max_iter, int32_t max_roots, double* out, int64_t* n_brackets, uint32_t flags);
+
+/*
+ * Skip distance: the smallest ground range any ray of a (profile, frequency) group reaches on a scan grid.  No
+ * counterpart in the reference; the definition is DESIGN.md section 4.10.  Groups, columns, geometry, the four spherical
+ * controls, mode, flags and errors as for prhf_snell_home_f64; scan_elevation_deg holds n_scan >= 1 strictly increasing
+ * elevations.  Per group, in float64 without contraction:
+ *   Scan: D_i, ground_range_km of the group's fan ray at scan node i (the bits prhf_snell_fan_f64 gives), NaN for a ray
+ *   that does not turn.
+ *   Node: i* = the FIRST index that attains the minimum over the finite D_i.  None finite: status -1, every output NaN
+ *   (scan_index -1, n_evals and the node count 0).
+ *   Edge: i* == 0, i* == n_scan - 1, or a neighbour of i* that is not finite: status 1, the result is the scan node's
+ *   own ray, bracket_deg NaN ("no skip zone inside the scan", or "the minimum sits beside penetration").
+ *   Refine otherwise: a = e_(i*-1), b = e_(i*), c = e_(i*+1), Db = D_(i*), g = 0.3819660112501051; per trip, in this order:
+ *     c - a <= elev_tol_deg: status 0, stop;
+ *     right = (c - b) >= (b - a); x = right ? b + g * (c - b) : b - g * (b - a) (difference, product, sum: one rounding each);
+ *     unless a < x < c and x != b: status 0, stop (the doubles are exhausted);
+ *     max_iter (1 .. 128) rays traced already: status 3, stop;
+ *     Dx = ground_range_km of the group's ray at x; not finite: status 2, stop (a ray inside the bracket escapes);
+ *     Dx < Db: the old b becomes a (right) or c (left), b = x, Db = Dx; otherwise x becomes c (right) or a (left): a tie keeps b.
+ *   The result is the ray at b for every status; a b that is still the scan node is traced once more for its outputs
+ *   and that ray is not counted.
+ * out is (n_groups, 13): elevation_deg (b), status, scan_index (i*), bracket_deg (c - a at the end), n_evals (rays
+ * traced by the search, an escaping one included), then the eight outputs of prhf_snell_cartesian_f64 for the result ray -
+ * the skip distance is its ground_range_km, out[.., 9].  No result depends on how many groups share the call or on
+ * scheduling.  elev_tol_deg is finite and >= 0.  Synchronous; one call, no host round trip between its kernels.
+ */
+int prhf_snell_skip_f64(prhf_ctx* ctx, int32_t geometry, const double* group_freq_hz,
+                        const int64_t* group_profile_index, int64_t n_groups, const double* scan_elevation_deg,
+                        int64_t n_scan, const double* den, const double* bmag, const double* bpsi, const double* alt,
+                        int64_t n_prof, int64_t n_alt, int64_t alt_stride_elems, int32_t mode, double earth_radius_km,
+                        double dz_target_km, double apex_boost, int32_t max_substeps, double elev_tol_deg,
+                        int32_t max_iter, double* out, uint32_t flags);
+
+/*
+ * MUF of a link (junction frequency, the nose of the oblique ionogram): the frequency at which the skip distance
+ * reaches the link's ground range.  DESIGN.md section 4.10.  Link l is the pair (link_profile_index[l] in [0, n_prof), or
+ * profile 0 for a NULL array; link_range_km[l] = t).  S(f) is the skip distance of prhf_snell_skip_f64 for that column,
+ * frequency f, mode, scan grid and controls, +inf when its status is -1.  0 < f_lo_hz < f_hi_hz, both finite.
+ *   status -1: t is NaN.  2: S(f_lo) > t, unreachable even at f_lo.  Both: every other output NaN.
+ *   status 1: S(f_hi) <= t, the link is open at f_hi: muf_hz = f_hi with its skip row, f_above_hz NaN.
+ *   status 0: S(f_lo) <= t < S(f_hi); lo = f_lo, hi = f_hi, then n_bisect (1 .. 64) trips: m = lo + 0.5 * (hi - lo);
+ *   a trip whose m is not strictly inside (lo, hi) changes nothing; S(m) <= t: lo = m, otherwise hi = m.
+ *   muf_hz = lo, f_above_hz = hi: S(muf_hz) <= t < S(f_above_hz) whether or not S is monotone - the rule says which
+ *   crossing is found.
+ * out is (n_links, 16): muf_hz, f_above_hz, status, then the 13 values of the skip row at muf_hz.  The per-trip
+ * kernels (the links' next frequencies into the device-side group table, tables, scan, refine, decide) are enqueued on
+ * one stream and the call waits once, at its end.  Arrays are host memory, or device memory with PRHF_FLAG_DEVICE_PTRS.
+ */
+int prhf_snell_muf_f64(prhf_ctx* ctx, int32_t geometry, const int64_t* link_profile_index, const double* link_range_km,
+                       int64_t n_links, double f_lo_hz, double f_hi_hz, int32_t n_bisect,
+                       const double* scan_elevation_deg, int64_t n_scan, const double* den, const double* bmag,
+                       const double* bpsi, const double* alt, int64_t n_prof, int64_t n_alt, int64_t alt_stride_elems,
+                       int32_t mode, double earth_radius_km, double dz_target_km, double apex_boost, int32_t max_substeps,
+                       double elev_tol_deg, int32_t max_iter, double* out, uint32_t flags);
 
 /*
  * 2-D refractive-index fields mu(a0, a1) for the gradient tracer: node records.

@@ -18,11 +18,13 @@ from .gradient import (STATUS_NAMES, RefractiveField, build_mup_function,       
                        trace_fan_cartesian_gradient, trace_fan_spherical_gradient,
                        trace_ray_cartesian_gradient, trace_ray_spherical_gradient,
                        trace_rays_cartesian_gradient, trace_rays_spherical_gradient)
-from .tracers import home_rays_cartesian_snells, home_rays_spherical_snells                        # noqa: E402
+from .tracers import (home_rays_cartesian_snells, home_rays_spherical_snells, muf_cartesian_snells,  # noqa: E402
+                      muf_spherical_snells, skip_distance_cartesian_snells, skip_distance_spherical_snells)
 
 __all__ = ["logger", "__version__", "STATUS_NAMES", "RefractiveField", "build_mup_function",
            "build_refractive_index_interpolator_cartesian", "build_refractive_index_interpolator_spherical",
            "refractive_field", "trace_fan_cartesian_gradient", "trace_fan_spherical_gradient",
            "trace_ray_cartesian_gradient", "trace_ray_spherical_gradient", "trace_rays_cartesian_gradient",
            "trace_rays_spherical_gradient", "home_rays_cartesian_snells", "home_rays_spherical_snells",
-           "home_rays_cartesian_gradient", "home_rays_spherical_gradient"]
+           "home_rays_cartesian_gradient", "home_rays_spherical_gradient", "skip_distance_cartesian_snells",
+           "skip_distance_spherical_snells", "muf_cartesian_snells", "muf_spherical_snells"]

@@ -89,6 +89,17 @@ _PROTOTYPES = {
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
         ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int32, ctypes.c_double, ctypes.c_int32,
         ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32]),
+    "prhf_snell_skip_f64": (ctypes.c_int, [
+        ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+        ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+        ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+        ctypes.c_int32, ctypes.c_double, ctypes.c_int32, ctypes.c_void_p, ctypes.c_uint32]),
+    "prhf_snell_muf_f64": (ctypes.c_int, [
+        ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_double,
+        ctypes.c_double, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
+        ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int32, ctypes.c_double, ctypes.c_int32,
+        ctypes.c_void_p, ctypes.c_uint32]),
     "prhf_field_pack_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
                                            ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
                                            ctypes.c_int32, ctypes.c_void_p, ctypes.c_uint32]),
@@ -301,6 +312,23 @@ class Context:
                                              alt_stride, mode, float(r_e), float(dz_target), float(apex_boost),
                                              int(max_substeps), float(range_tol), int(max_iter), int(max_roots), out,
                                              n_brackets, flags)
+
+    def snell_skip(self, geometry, group_freq, group_prof, n_groups, scan_elev, n_scan, den, bmag, bpsi, alt, n_prof,
+                   n_alt, alt_stride, mode, r_e, dz_target, apex_boost, max_substeps, elev_tol, max_iter, out, flags):
+        """``out``: (n_groups, 13) doubles (include/prhf.h)."""
+        return self._lib.prhf_snell_skip_f64(self._h, int(geometry), group_freq, group_prof or None, n_groups, scan_elev,
+                                             n_scan, den, bmag, bpsi, alt, n_prof, n_alt, alt_stride, mode, float(r_e),
+                                             float(dz_target), float(apex_boost), int(max_substeps), float(elev_tol),
+                                             int(max_iter), out, flags)
+
+    def snell_muf(self, geometry, link_prof, link_range, n_links, f_lo, f_hi, n_bisect, scan_elev, n_scan, den, bmag,
+                  bpsi, alt, n_prof, n_alt, alt_stride, mode, r_e, dz_target, apex_boost, max_substeps, elev_tol, max_iter,
+                  out, flags):
+        """``out``: (n_links, 16) doubles (include/prhf.h)."""
+        return self._lib.prhf_snell_muf_f64(self._h, int(geometry), link_prof or None, link_range, n_links, float(f_lo),
+                                            float(f_hi), int(n_bisect), scan_elev, n_scan, den, bmag, bpsi, alt, n_prof,
+                                            n_alt, alt_stride, mode, float(r_e), float(dz_target), float(apex_boost),
+                                            int(max_substeps), float(elev_tol), int(max_iter), out, flags)
 
     def field_pack(self, mu, mup, n_fields, n0, n1, axis0, axis1, edge_order, records, flags):
         """``records``: a device address in every flag combination; the axes: host addresses."""

@@ -1782,6 +1782,185 @@ int prhf_snell_home_f64(prhf_ctx* c, int32_t geometry, const double* group_freq_
 }
 
 namespace {
+// prhf_snell_skip_f64 (link_range_km null: group_freq_hz and group_profile_index describe n_groups groups) and
+// prhf_snell_muf_f64 (a link is a group: group_profile_index is the links' profile index, n_groups their number, and the
+// group frequencies are the device's own).
+int skip_run(prhf_ctx* c, int32_t geometry, const double* group_freq_hz, const int64_t* group_profile_index, int64_t n_groups,
+             const double* link_range_km, double f_lo_hz, double f_hi_hz, int32_t n_bisect, const double* scan_elevation_deg,
+             int64_t n_scan, const double* den, const double* bmag, const double* bpsi, const double* alt, int64_t n_prof,
+             int64_t n_alt, int64_t alt_stride_elems, int32_t mode, double earth_radius_km, double dz_target_km,
+             double apex_boost, int32_t max_substeps, double elev_tol_deg, int32_t max_iter, double* out, uint32_t flags) {
+    const bool muf = link_range_km != nullptr;
+    if (!c) return fail(PRHF_EINVAL, "null context");
+    if ((!muf && !group_freq_hz) || !scan_elevation_deg || !den || !bmag || !bpsi || !alt || !out)
+        return fail(PRHF_EINVAL, "null array pointer");
+    if (geometry != 0 && geometry != 1) return fail(PRHF_EINVAL, "geometry is 0 (flat Earth) or 1 (spherical Earth)");
+    if (geometry == 1 && (!(earth_radius_km > 0.0) || !(earth_radius_km < 1e300) || !(dz_target_km > 0.0) || !(apex_boost >= 0.0) ||
+                          max_substeps < 1))
+        return fail(PRHF_EINVAL, "bad spherical tracer controls");
+    if (n_scan < 1) return fail(PRHF_EINVAL, "the scan grid needs at least 1 elevation");
+    if (max_iter < 1 || max_iter > 128) return fail(PRHF_EINVAL, "max_iter is 1 .. 128");
+    if (!(elev_tol_deg >= 0.0) || !std::isfinite(elev_tol_deg))
+        return fail(PRHF_EINVAL, "elev_tol_deg must be finite and not negative");
+    if (muf) {
+        if (n_bisect < 1 || n_bisect > 64) return fail(PRHF_EINVAL, "n_bisect is 1 .. 64");
+        if (!(f_lo_hz > 0.0) || !(f_hi_hz > f_lo_hz) || !std::isfinite(f_hi_hz))
+            return fail(PRHF_EINVAL, "the frequency bracket needs 0 < f_lo_hz < f_hi_hz, both finite");
+    }
+    if (n_groups < 0 || n_prof < 1 || n_prof > 0x7fffffffLL || n_alt < 2 || n_alt > 3000) return fail(PRHF_EINVAL, "bad shape");
+    // per group and level: mu' (8 B), the compacted entry (32 B), its grid level (4 B); per group: four scalars (snell_run)
+    const size_t level_cells = (size_t)n_groups * (size_t)(n_alt + 1);
+    const size_t mup_cells = (level_cells + 1) & ~(size_t)1;
+    const size_t level_bytes = mup_cells * 8 + level_cells * 36 + (size_t)n_groups * 16;
+    if (level_bytes > ((size_t)64 << 30) || n_groups > 0x7fffffffLL)
+        return fail(PRHF_EINVAL, "level tables of %lld groups exceed 64 GiB (or 2^31 - 1 groups): search in batches",
+                    (long long)n_groups);
+    if (n_groups * n_scan > 0x7fffffffLL) return fail(PRHF_EINVAL, "more than 2^31 - 1 scan rays: search in batches");
+    if (mode != PRHF_MODE_O && mode != PRHF_MODE_X) return fail(PRHF_EINVAL, "Mode must be O or X");
+    if (alt_stride_elems != 0 && alt_stride_elems != n_alt) return fail(PRHF_EINVAL, "alt stride is 0 or n_alt");
+    if (flags & ~PRHF_FLAG_DEVICE_PTRS) return fail(PRHF_EINVAL, "unknown flag bits");
+    const bool dev = (flags & PRHF_FLAG_DEVICE_PTRS) != 0;
+    if (!dev) {
+        for (int64_t i = 0; i + 1 < n_scan; ++i)
+            if (!(scan_elevation_deg[i + 1] > scan_elevation_deg[i]))
+                return fail(PRHF_EINVAL, "scan_elevation_deg must be strictly increasing");
+        if (n_scan == 1 && !std::isfinite(scan_elevation_deg[0])) return fail(PRHF_EINVAL, "scan_elevation_deg must be finite");
+        if (group_profile_index)
+            for (int64_t g = 0; g < n_groups; ++g)
+                if (group_profile_index[g] < 0 || group_profile_index[g] >= n_prof)
+                    return fail(PRHF_EINVAL, "profile_index[%lld] outside [0, n_prof)", (long long)g);
+    }
+    if (n_groups == 0) return PRHF_OK;
+    ENTER_DEVICE(c->device);
+    prhf::MufArgs m;
+    std::memset(&m, 0, sizeof m);
+    prhf::SkipArgs& h = m.k;
+    prhf::SnellArgs& a = h.s;
+    a.n_rays = 1; a.n_alt = n_alt; a.prof_stride = n_alt; a.alt_stride = alt_stride_elems;
+    a.mode = mode == PRHF_MODE_O ? PRHF_KMODE_O : PRHF_KMODE_X;
+    a.geometry = geometry;
+    a.earth_radius_km = geometry == 0 ? 6371.0 : earth_radius_km;
+    a.dz_target_km = geometry == 0 ? 1.0 : dz_target_km;
+    a.apex_boost = geometry == 0 ? 200.0 : apex_boost;
+    a.max_substeps = geometry == 0 ? 400 : max_substeps;
+    a.status = c->h_status_dev;
+    a.n_groups = n_groups; a.n_prof = n_prof; a.resident_cus = c->cu_count;
+    h.n_scan = (int)n_scan; h.elev_tol = elev_tol_deg; h.max_iter = max_iter;
+    m.n_links = n_groups; m.f_lo = f_lo_hz; m.f_hi = f_hi_hz; m.n_bisect = n_bisect;
+    const size_t prof_elems = (size_t)n_prof * (size_t)n_alt;
+    const size_t alt_elems = alt_stride_elems ? prof_elems : (size_t)n_alt;
+    const size_t width = muf ? PRHF_MUF_OUTPUTS : PRHF_SKIP_OUTPUTS;
+    const size_t out_elems = (size_t)n_groups * width;
+    double* d_result = out;
+    if (dev) {
+        a.den = den; a.bmag = bmag; a.bpsi = bpsi; a.alt = alt;
+        a.group_freq = group_freq_hz;
+        a.group_prof = reinterpret_cast<const long long*>(group_profile_index);
+        m.link_range = link_range_km; h.scan_elev = scan_elevation_deg;
+    } else {
+        const size_t elems = 3 * prof_elems + alt_elems + 3 * (size_t)n_groups + (size_t)n_scan + out_elems;
+        int rc = ensure(c, c->arena, elems * 8);
+        if (rc != PRHF_OK) return rc;
+        double* p = static_cast<double*>(c->arena.p);
+        double* d_den = p; p += prof_elems;
+        double* d_bmag = p; p += prof_elems;
+        double* d_bpsi = p; p += prof_elems;
+        double* d_alt = p; p += alt_elems;
+        double* d_f = p; p += n_groups;
+        long long* d_i = reinterpret_cast<long long*>(p); p += n_groups;
+        double* d_lr = p; p += n_groups;
+        double* d_e = p; p += n_scan;
+        d_result = p;
+        HIP_TRY(hipMemcpyAsync(d_den, den, prof_elems * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_bmag, bmag, prof_elems * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_bpsi, bpsi, prof_elems * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_alt, alt, alt_elems * 8, hipMemcpyHostToDevice, c->stream));
+        if (!muf) HIP_TRY(hipMemcpyAsync(d_f, group_freq_hz, (size_t)n_groups * 8, hipMemcpyHostToDevice, c->stream));
+        if (group_profile_index)
+            HIP_TRY(hipMemcpyAsync(d_i, group_profile_index, (size_t)n_groups * 8, hipMemcpyHostToDevice, c->stream));
+        if (muf) HIP_TRY(hipMemcpyAsync(d_lr, link_range_km, (size_t)n_groups * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_e, scan_elevation_deg, (size_t)n_scan * 8, hipMemcpyHostToDevice, c->stream));
+        a.den = d_den; a.bmag = d_bmag; a.bpsi = d_bpsi; a.alt = d_alt;
+        a.group_freq = d_f; a.group_prof = group_profile_index ? d_i : nullptr;
+        m.link_range = d_lr; h.scan_elev = d_e;
+    }
+    {
+        int rc = ensure(c, c->levels, level_bytes);
+        if (rc != PRHF_OK) return rc;
+        a.levels = static_cast<double*>(c->levels.p);
+        a.group_entries = a.levels + mup_cells;
+        a.group_info = reinterpret_cast<int*>(a.group_entries + 4 * level_cells);
+        a.group_kidx = a.group_info + 4 * (size_t)n_groups;
+    }
+    {
+        // per-profile scalars; behind them the scan's ground ranges and - MUF - the links' frequencies, brackets, skip rows
+        // of the trip and of the bracket's lower end, and "still searching" words
+        const size_t info_bytes = (((size_t)n_prof * 32 + 127) / 128) * 128;
+        const size_t scan_bytes = (size_t)n_groups * (size_t)n_scan * 8;
+        const size_t link_doubles = muf ? (size_t)n_groups * (1 + 4 + 2 * PRHF_SKIP_OUTPUTS) : 0;
+        const size_t flag_bytes = muf ? (size_t)n_groups * 4 : 0;
+        int rc = ensure(c, c->partial, info_bytes + scan_bytes + link_doubles * 8 + flag_bytes);
+        if (rc != PRHF_OK) return rc;
+        char* q = static_cast<char*>(c->partial.p);
+        a.prof_info = reinterpret_cast<double*>(q);
+        h.scan_d = reinterpret_cast<double*>(q + info_bytes);
+        if (muf) {
+            double* p = h.scan_d + (size_t)n_groups * (size_t)n_scan;
+            m.group_freq = p; p += n_groups;
+            m.state = p; p += 4 * (size_t)n_groups;
+            m.best = p; p += (size_t)n_groups * PRHF_SKIP_OUTPUTS;
+            h.out = p; p += (size_t)n_groups * PRHF_SKIP_OUTPUTS;
+            m.active = reinterpret_cast<int*>(p);
+            a.group_freq = m.group_freq;
+            h.active = m.active;
+            m.out = d_result;
+        } else {
+            h.out = d_result;
+        }
+    }
+    a.ptab = nullptr;
+    if (c->knobs.snell_table > 0 && (double)n_groups >= c->knobs.snell_table * (double)n_prof && prof_elems * 32 <= ((size_t)1 << 30)) {
+        int rc = ensure(c, c->ptab, prof_elems * 32);
+        if (rc != PRHF_OK) return rc;
+        a.ptab = static_cast<double*>(c->ptab.p);
+    }
+    HIP_TRY(hipEventRecord(c->begin_ev(), c->stream));
+    if (muf) HIP_TRY(prhf::launch_snell_muf(m, c->stream));
+    else HIP_TRY(prhf::launch_snell_skip(h, c->stream));
+    HIP_TRY(hipEventRecord(c->pending_end_ev(), c->stream));
+    c->mark_timed();
+    c->status_pending = true;
+    if (!dev) HIP_TRY(hipMemcpyAsync(out, d_result, out_elems * 8, hipMemcpyDeviceToHost, c->stream));
+    return prhf_sync(c);
+}
+}  // namespace
+
+int prhf_snell_skip_f64(prhf_ctx* c, int32_t geometry, const double* group_freq_hz, const int64_t* group_profile_index,
+                        int64_t n_groups, const double* scan_elevation_deg, int64_t n_scan, const double* den,
+                        const double* bmag, const double* bpsi, const double* alt, int64_t n_prof, int64_t n_alt,
+                        int64_t alt_stride_elems, int32_t mode, double earth_radius_km, double dz_target_km,
+                        double apex_boost, int32_t max_substeps, double elev_tol_deg, int32_t max_iter, double* out,
+                        uint32_t flags) {
+    if (c && n_groups < 1) return fail(PRHF_EINVAL, "the search needs at least one group");
+    return skip_run(c, geometry, group_freq_hz, group_profile_index, n_groups, nullptr, 0.0, 0.0, 0, scan_elevation_deg, n_scan,
+                    den, bmag, bpsi, alt, n_prof, n_alt, alt_stride_elems, mode, earth_radius_km, dz_target_km, apex_boost,
+                    max_substeps, elev_tol_deg, max_iter, out, flags);
+}
+
+int prhf_snell_muf_f64(prhf_ctx* c, int32_t geometry, const int64_t* link_profile_index, const double* link_range_km,
+                       int64_t n_links, double f_lo_hz, double f_hi_hz, int32_t n_bisect, const double* scan_elevation_deg,
+                       int64_t n_scan, const double* den, const double* bmag, const double* bpsi, const double* alt,
+                       int64_t n_prof, int64_t n_alt, int64_t alt_stride_elems, int32_t mode, double earth_radius_km,
+                       double dz_target_km, double apex_boost, int32_t max_substeps, double elev_tol_deg, int32_t max_iter,
+                       double* out, uint32_t flags) {
+    if (c && !link_range_km) return fail(PRHF_EINVAL, "null array pointer");
+    if (c && n_links < 1) return fail(PRHF_EINVAL, "the search needs at least one link");
+    return skip_run(c, geometry, nullptr, link_profile_index, n_links, link_range_km, f_lo_hz, f_hi_hz, n_bisect,
+                    scan_elevation_deg, n_scan, den, bmag, bpsi, alt, n_prof, n_alt, alt_stride_elems, mode, earth_radius_km,
+                    dz_target_km, apex_boost, max_substeps, elev_tol_deg, max_iter, out, flags);
+}
+
+namespace {
 // The two axes of a field: host memory, strictly increasing (a NaN fails the test), at least `least` values each and
 // together no more than the kernels stage in LDS.  *uniform: all np.diff(axis) are equal (np.gradient's scalar branch).
 int check_axis(const char* name, const double* g, int64_t n, int64_t least, int* uniform) {

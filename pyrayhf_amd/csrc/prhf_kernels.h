@@ -335,6 +335,35 @@ struct HomeArgs {
 size_t home_queue_bytes();
 hipError_t launch_snell_home(const HomeArgs& h, hipStream_t stream);   // tables, scan, brackets, refinement: five kernels
 
+// Skip distance of a group and MUF of a link for the grouped tracer (prhf_skip.inc).
+#define PRHF_SKIP_OUTPUTS (5 + PRHF_SNELL_OUTPUTS)   // elevation_deg, status, scan_index, bracket_deg, n_evals, then the tracer's eight
+#define PRHF_MUF_OUTPUTS (3 + PRHF_SKIP_OUTPUTS)     // muf_hz, f_above_hz, status, then the skip row at muf_hz
+struct SkipArgs {
+    SnellArgs s;                 // a grouped launch's arguments (tables, columns, controls); elev_deg, ray_group, out unused
+    const double* scan_elev;     // (n_scan) scan grid [deg], strictly increasing
+    int n_scan;
+    double elev_tol;             // [deg]
+    int max_iter;
+    const int* active;           // (n_groups) or null: groups with a 0 here are left alone (the MUF search's settled links)
+    double* scan_d;              // (n_groups, n_scan) scratch: ground range of every scan ray
+    double* out;                 // (n_groups, PRHF_SKIP_OUTPUTS)
+};
+hipError_t launch_snell_skip(const SkipArgs& h, hipStream_t stream);   // tables, scan, refinement: four kernels
+struct MufArgs {
+    SkipArgs k;                  // a link is a group: k.s.n_groups == n_links, k.s.group_freq == group_freq, k.active == active,
+                                 // k.out (n_links, PRHF_SKIP_OUTPUTS) scratch: the skip rows of the trip
+    const double* link_range;    // (n_links) target ground range [km]
+    long long n_links;
+    double f_lo, f_hi;           // [Hz]
+    int n_bisect;
+    double* group_freq;          // (n_links) scratch: the device-side group table's frequencies, written once per trip
+    int* active;                 // (n_links) scratch
+    double* state;               // (n_links, 4) scratch: lo, hi, status, 0
+    double* best;                // (n_links, PRHF_SKIP_OUTPUTS) scratch: the skip row at lo
+    double* out;                 // (n_links, PRHF_MUF_OUTPUTS)
+};
+hipError_t launch_snell_muf(const MufArgs& m, hipStream_t stream);     // (2 + n_bisect) x (set, tables, scan, refine, decide)
+
 // 2-D refractive-index fields and the gradient tracers (prhf_gradient.inc); device pointers throughout.
 struct FieldPackArgs {
     const double* mu;            // (n_fields, n0, n1)

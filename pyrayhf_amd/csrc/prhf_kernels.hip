@@ -2882,6 +2882,7 @@ hipError_t launch_vfo_shortx(const KArgs& a, long long grid_blocks, size_t lds_b
 
 #include "prhf_snell.inc"
 #include "prhf_homing.inc"
+#include "prhf_skip.inc"
 #include "prhf_gradient.inc"
 #include "prhf_gradient_homing.inc"
 

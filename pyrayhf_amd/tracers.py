@@ -8,7 +8,10 @@ and result dictionaries (reference ``PyRayHF/library.py:1096-1268``, ``:1460-171
 frequency (and profile): the refractive-index levels, which depend on the profile and the frequency only, are
 computed once per (profile, frequency) and shared by the fan's rays;
 ``home_rays_cartesian_snells`` / ``home_rays_spherical_snells`` find, for every (profile, frequency) and every ground
-range, the rays that land there (point-to-point homing, the oblique ionogram of a link).
+range, the rays that land there (point-to-point homing, the oblique ionogram of a link; DESIGN.md section 4.8);
+``skip_distance_cartesian_snells`` / ``skip_distance_spherical_snells`` find the smallest ground range a
+(profile, frequency) reaches, and ``muf_cartesian_snells`` / ``muf_spherical_snells`` the frequency at which that skip
+distance equals a link's range.
 """
 
 from __future__ import annotations
@@ -20,7 +23,9 @@ from .library import MATH_AUTO, _as_rows, constants
 
 __all__ = ["trace_ray_cartesian_snells", "trace_rays_cartesian_snells", "trace_ray_spherical_snells",
            "trace_rays_spherical_snells", "trace_fan_cartesian_snells", "trace_fan_spherical_snells",
-           "home_rays_cartesian_snells", "home_rays_spherical_snells", "tan_from_mu_scalar", "find_turning_point"]
+           "home_rays_cartesian_snells", "home_rays_spherical_snells", "skip_distance_cartesian_snells",
+           "skip_distance_spherical_snells", "muf_cartesian_snells", "muf_spherical_snells", "tan_from_mu_scalar",
+           "find_turning_point"]
 
 _KEYS = ("group_path_km", "group_delay_sec", "x_midpoint", "z_midpoint", "ground_range_km", "x_turn_km",
          "z_turn_km", "n_path")
@@ -225,6 +230,173 @@ def home_rays_spherical_snells(f0_Hz, ground_range_km, alt_km, Ne, Babs, bpsi, m
     r_e = constants()[2] if R_E is None else float(R_E)
     return _home_rays(True, f0_Hz, ground_range_km, alt_km, Ne, Babs, bpsi, mode, scan_elevation_deg, max_roots,
                       range_tol_km, max_iter, device, (r_e, dz_target_km, apex_boost, max_substeps))
+
+
+SKIP_STATUS_NAMES = {0: "converged", 1: "edge of the scan", 2: "escapes inside", 3: "max_iter spent", -1: "no ray lands"}
+MUF_STATUS_NAMES = {0: "bracketed", 1: "open at f_hi", 2: "unreachable at f_lo", -1: "no target"}
+
+
+def _skip_arguments(alt_km, Ne, Babs, bpsi, mode, scan_elevation_deg, elev_tol_deg, max_iter):
+    """The checks and conversions the skip-distance and MUF calls share; all before any native call."""
+    if mode not in ("O", "X"):
+        raise ValueError("Mode must be O or X")
+    scan = default_scan_elevations() if scan_elevation_deg is None else \
+        np.ascontiguousarray(np.asarray(scan_elevation_deg, dtype=np.float64))
+    if scan.ndim != 1 or scan.size < 1:
+        raise ValueError("scan_elevation_deg needs at least 1 elevation")
+    if not (np.all(np.isfinite(scan)) and np.all(np.diff(scan) > 0)):
+        raise ValueError("scan_elevation_deg must be finite and strictly increasing")
+    max_iter, elev_tol_deg = int(max_iter), float(elev_tol_deg)
+    if not 1 <= max_iter <= 128:
+        raise ValueError("max_iter is 1 .. 128")
+    if not (np.isfinite(elev_tol_deg) and elev_tol_deg >= 0.0):
+        raise ValueError("elev_tol_deg must be finite and not negative")
+    d2, b2, p2 = (np.atleast_2d(_as_rows(n, x)) for n, x in (("Ne", Ne), ("Babs", Babs), ("bpsi", bpsi)))
+    if not (d2.shape == b2.shape == p2.shape):
+        raise ValueError("Ne, Babs and bpsi must have the same shape")
+    n_prof, n_alt = d2.shape
+    a = _as_rows("alt_km", alt_km)
+    if a.shape[-1] != n_alt or (a.ndim == 2 and a.shape[0] != n_prof):
+        raise ValueError("alt_km must have one value per level")
+    if n_alt < 2:
+        raise ValueError("a profile needs at least 2 levels")
+    return scan, elev_tol_deg, max_iter, a, d2, b2, p2
+
+
+def _skip_row(out, res, first):
+    """The 13 values of a skip row, out[..., first:first + 13], into the dict under the public names."""
+    res["elevation_deg"] = out[..., first].copy()
+    idx, n_evals = out[..., first + 2], out[..., first + 4]
+    res["scan_index"] = np.where(np.isfinite(idx), idx, -1.0).astype(np.int64)
+    res["bracket_deg"] = out[..., first + 3].copy()
+    res["n_evals"] = np.where(np.isfinite(n_evals), n_evals, 0.0).astype(np.int64)
+    for i, k in enumerate(_KEYS):
+        res[k] = out[..., first + 5 + i].copy()
+    res["skip_km"] = res["ground_range_km"].copy()
+    n_path = res["n_path"]
+    res["n_path"] = np.where(np.isfinite(n_path), n_path, 0.0).astype(np.int64)
+    status = out[..., first + 1]
+    return np.where(np.isfinite(status), status, -1.0).astype(np.int64)
+
+
+def _skip_distance(spherical, f0_Hz, alt_km, Ne, Babs, bpsi, mode, scan_elevation_deg, elev_tol_deg, max_iter, device,
+                   controls):
+    scan, elev_tol_deg, max_iter, a, d2, b2, p2 = _skip_arguments(alt_km, Ne, Babs, bpsi, mode, scan_elevation_deg,
+                                                                   elev_tol_deg, max_iter)
+    f = np.ascontiguousarray(np.atleast_1d(np.asarray(f0_Hz, dtype=np.float64)))
+    if f.ndim != 1 or f.size == 0:
+        raise ValueError("f0_Hz must be 1-D and not empty (frequencies)")
+    single = np.ndim(Ne) == 1
+    n_prof, n_alt = d2.shape
+    # groups: (profile, frequency) in C order
+    group_f = np.ascontiguousarray(np.tile(f, n_prof))
+    group_p = np.ascontiguousarray(np.repeat(np.arange(n_prof, dtype=np.int64), f.size))
+    out = np.empty((group_f.size, 13), dtype=np.float64)
+    r_e, dz_t, boost, nsub = controls if spherical else (6371.0, 1.0, 200.0, 400)
+    ctx = _native.host_context(device)
+    rc = ctx.snell_skip(1 if spherical else 0, group_f.ctypes.data, group_p.ctypes.data, group_f.size, scan.ctypes.data,
+                        scan.size, d2.ctypes.data, b2.ctypes.data, p2.ctypes.data, a.ctypes.data, n_prof, n_alt,
+                        n_alt if a.ndim == 2 else 0, _native.MODE_O if mode == "O" else _native.MODE_X, r_e, dz_t, boost,
+                        nsub, elev_tol_deg, max_iter, out.ctypes.data, 0)
+    _native.raise_for(rc)
+    out = out.reshape(((f.size,) if single else (n_prof, f.size)) + (13,))
+    res = {}
+    res["status"] = _skip_row(out, res, 0)
+    return res
+
+
+def skip_distance_cartesian_snells(f0_Hz, alt_km, Ne, Babs, bpsi, mode, *, scan_elevation_deg=None, elev_tol_deg=1e-6,
+                                   max_iter=64, device=None):
+    """Skip distance over a flat Earth: for every frequency of ``f0_Hz`` ``(F,)`` (and every profile when
+    ``Ne, Babs, bpsi`` are ``(P, N_alt)``) the smallest ground range any ray of the scan reaches, refined
+    (``prhf_snell_skip_f64``).
+
+    The fan of ``scan_elevation_deg`` (strictly increasing, at least one elevation, default ``np.linspace(2, 88, 345)``)
+    is traced once per (profile, frequency); ``scan_index`` is the first node that attains the smallest finite ground
+    range.  A node at either end of the scan, or beside a ray that does not turn, is returned as it stands (``status``
+    1: no skip zone inside the scan, or the minimum sits beside penetration).  Otherwise a golden-section search between
+    the node's two neighbours traces at most ``max_iter`` further rays until the bracket is ``elev_tol_deg`` wide or
+    cannot be split in float64 (``status`` 0), ``max_iter`` is spent (3) or a ray inside the bracket escapes (2); the
+    result is the ray with the smallest ground range seen.  ``status`` -1: no ray of the scan lands (NaN everywhere,
+    ``scan_index`` -1, ``n_path`` 0).  What is found is a function of the scan grid.
+
+    Returns a dict of ``([P,] F)`` arrays: ``skip_km``, ``elevation_deg``, ``status`` (``SKIP_STATUS_NAMES``),
+    ``scan_index``, ``bracket_deg`` (width of the final bracket, NaN for status 1), ``n_evals`` (rays the search traced)
+    and the eight keys of ``trace_rays_cartesian_snells`` for the result ray - bit for bit what the fan call gives at
+    ``elevation_deg``; ``skip_km`` is its ``ground_range_km``."""
+    return _skip_distance(False, f0_Hz, alt_km, Ne, Babs, bpsi, mode, scan_elevation_deg, elev_tol_deg, max_iter, device,
+                          None)
+
+
+def skip_distance_spherical_snells(f0_Hz, alt_km, Ne, Babs, bpsi, mode="O", *, scan_elevation_deg=None, elev_tol_deg=1e-6,
+                                   max_iter=64, dz_target_km=1.0, apex_boost=200.0, max_substeps=400, R_E=None,
+                                   device=None):
+    """The same over a spherical Earth, with the reference's apex-refinement controls (library.py:1470-1473)."""
+    r_e = constants()[2] if R_E is None else float(R_E)
+    return _skip_distance(True, f0_Hz, alt_km, Ne, Babs, bpsi, mode, scan_elevation_deg, elev_tol_deg, max_iter, device,
+                          (r_e, dz_target_km, apex_boost, max_substeps))
+
+
+def _muf(spherical, ground_range_km, f_lo_Hz, f_hi_Hz, alt_km, Ne, Babs, bpsi, mode, n_bisect, scan_elevation_deg,
+         elev_tol_deg, max_iter, device, controls):
+    scan, elev_tol_deg, max_iter, a, d2, b2, p2 = _skip_arguments(alt_km, Ne, Babs, bpsi, mode, scan_elevation_deg,
+                                                                   elev_tol_deg, max_iter)
+    t = np.ascontiguousarray(np.atleast_1d(np.asarray(ground_range_km, dtype=np.float64)))
+    if t.ndim != 1 or t.size == 0:
+        raise ValueError("ground_range_km must be 1-D and not empty (target ranges)")
+    f_lo, f_hi, n_bisect = float(f_lo_Hz), float(f_hi_Hz), int(n_bisect)
+    if not (np.isfinite(f_lo) and np.isfinite(f_hi) and 0.0 < f_lo < f_hi):
+        raise ValueError("the frequency bracket needs 0 < f_lo_Hz < f_hi_Hz, both finite")
+    if not 1 <= n_bisect <= 64:
+        raise ValueError("n_bisect is 1 .. 64")
+    single = np.ndim(Ne) == 1
+    n_prof, n_alt = d2.shape
+    # links: (profile, target) in C order
+    link_p = np.ascontiguousarray(np.repeat(np.arange(n_prof, dtype=np.int64), t.size))
+    link_t = np.ascontiguousarray(np.tile(t, n_prof))
+    out = np.empty((link_t.size, 16), dtype=np.float64)
+    r_e, dz_t, boost, nsub = controls if spherical else (6371.0, 1.0, 200.0, 400)
+    ctx = _native.host_context(device)
+    rc = ctx.snell_muf(1 if spherical else 0, link_p.ctypes.data, link_t.ctypes.data, link_t.size, f_lo, f_hi, n_bisect,
+                       scan.ctypes.data, scan.size, d2.ctypes.data, b2.ctypes.data, p2.ctypes.data, a.ctypes.data, n_prof,
+                       n_alt, n_alt if a.ndim == 2 else 0, _native.MODE_O if mode == "O" else _native.MODE_X, r_e, dz_t,
+                       boost, nsub, elev_tol_deg, max_iter, out.ctypes.data, 0)
+    _native.raise_for(rc)
+    out = out.reshape(((t.size,) if single else (n_prof, t.size)) + (16,))
+    res = {"muf_hz": out[..., 0].copy(), "f_above_hz": out[..., 1].copy(), "status": out[..., 2].astype(np.int64)}
+    res["skip_status"] = _skip_row(out, res, 3)
+    return res
+
+
+def muf_cartesian_snells(ground_range_km, f_lo_Hz, f_hi_Hz, alt_km, Ne, Babs, bpsi, mode, *, n_bisect=40,
+                         scan_elevation_deg=None, elev_tol_deg=1e-6, max_iter=64, device=None):
+    """MUF (junction frequency) of links over a flat Earth: for every target of ``ground_range_km`` ``(T,)`` (and
+    every profile when ``Ne, Babs, bpsi`` are ``(P, N_alt)``) the frequency in ``[f_lo_Hz, f_hi_Hz]`` at which the skip
+    distance ``S(f)`` of ``skip_distance_cartesian_snells`` (same column, mode, scan and controls; +inf when no ray
+    lands) reaches the target (``prhf_snell_muf_f64``).
+
+    ``status`` (``MUF_STATUS_NAMES``) -1: the target is NaN; 2: ``S(f_lo) > t``, the link is unreachable even at
+    ``f_lo_Hz`` (both: NaN everywhere else); 1: ``S(f_hi) <= t``, the link is open at ``f_hi_Hz``, which is returned with
+    its skip row (``f_above_hz`` NaN); 0: ``S(f_lo) <= t < S(f_hi)`` and ``n_bisect`` (1 .. 64) halvings of the frequency
+    bracket, ``m = lo + 0.5 (hi - lo)``, ``lo = m`` when ``S(m) <= t`` and ``hi = m`` otherwise, give ``muf_hz = lo`` and
+    ``f_above_hz = hi`` with ``S(muf_hz) <= t < S(f_above_hz)`` - also where ``S`` is not monotone: the rule says which
+    crossing is found.
+
+    Returns a dict of ``([P,] T)`` arrays: ``muf_hz``, ``f_above_hz``, ``status`` and the skip call's results at
+    ``muf_hz`` (``skip_km``, ``elevation_deg``, ``skip_status``, ``scan_index``, ``bracket_deg``, ``n_evals`` and the
+    eight ray keys).  All trips run inside one native call; with few links few wavefronts are resident and the call is
+    bound by the latency of its chain of kernels."""
+    return _muf(False, ground_range_km, f_lo_Hz, f_hi_Hz, alt_km, Ne, Babs, bpsi, mode, n_bisect, scan_elevation_deg,
+                elev_tol_deg, max_iter, device, None)
+
+
+def muf_spherical_snells(ground_range_km, f_lo_Hz, f_hi_Hz, alt_km, Ne, Babs, bpsi, mode="O", *, n_bisect=40,
+                         scan_elevation_deg=None, elev_tol_deg=1e-6, max_iter=64, dz_target_km=1.0, apex_boost=200.0,
+                         max_substeps=400, R_E=None, device=None):
+    """The same over a spherical Earth, with the reference's apex-refinement controls (library.py:1470-1473)."""
+    r_e = constants()[2] if R_E is None else float(R_E)
+    return _muf(True, ground_range_km, f_lo_Hz, f_hi_Hz, alt_km, Ne, Babs, bpsi, mode, n_bisect, scan_elevation_deg,
+                elev_tol_deg, max_iter, device, (r_e, dz_target_km, apex_boost, max_substeps))
 
 
 def _single(r, apex_keys):

@@ -36,7 +36,8 @@ extern "C" {
                               * 4: + prhf_field_pack_f64, prhf_field_sample_f64, prhf_trace_gradient_f64;
                               *    prhf_trace_gradient_spherical_f64 and prhf_snell_home_f64 joined later without a new
                               *    number: a new symbol changes nothing for a caller of the others (so did
-                              *    prhf_gradient_home_f64, prhf_snell_skip_f64 and prhf_snell_muf_f64) */
+                              *    prhf_gradient_home_f64, prhf_snell_skip_f64, prhf_snell_muf_f64 and
+                              *    prhf_pair_plan_counters) */
 
 /* return codes */
 #define PRHF_OK        0
@@ -133,6 +134,13 @@ int prhf_ctx_set_math(prhf_ctx* ctx, int level);
  *                        bit (1: on a uniform altitude grid the segments of at least 64 points below them do too - one
  *                        strided pass plus one pass over the points around the segment boundaries; a pair with a
  *                        segment too close to X + Y = 1 keeps the sum of before; "strided_top" = 0 switches both off)
+ *   "pair_plan"          0: every wavefront computes the integers that steer its pair's strided sum itself, the launch of
+ *                        before this option bit for bit (1: where "strided_lower" applies and a workgroup settles its
+ *                        reflection heights one frequency per thread - at most 512 frequencies, grids of fewer than 65536
+ *                        points - one thread per pair computes them beforehand; a pair whose plan finds no room, or whose
+ *                        closed-form guess of a segment's first point does not bracket it, still computes its own.  The
+ *                        integers are the same either way: no value depends on this option)
+ *   "pair_plan_cap"      > 0: a workgroup keeps at most this many plans (0: as many as fit; tests)
  *   "short_compact", "short_prio", "short_order", "short_lanes"
  *                        geometry of the short-grid kernels: four 4-wave workgroups per CU (1), wave priorities by age (1),
  *                        blocks in descending cost order (1), lanes per pair in the O kernel (8; 16: four pairs per work
@@ -545,6 +553,12 @@ int prhf_gradient_home_f64(prhf_ctx* ctx, int32_t geometry, const double* record
  * refine lanes traced, [2] ray slots (64 per trip of a refine wavefront's loop), [3] refine wavefronts with work.
  * Lane utilisation of the refinement = [1] / [2].  No device call. */
 int prhf_gradient_home_counters(prhf_ctx* ctx, uint64_t* counters);
+
+/* Diagnostics of option "pair_plan", summed over every launch since the context was made: counters[0] reflecting pairs
+ * whose sum ran from a plan made by one thread, [1] pairs of the same slices that computed their plan themselves (no
+ * room for the plan, or a guess that did not bracket).  Pairs of slices that are not eligible count in neither.
+ * Waits for the context's stream. */
+int prhf_pair_plan_counters(prhf_ctx* ctx, uint64_t* counters);
 
 /* Diagnostics: workgroups of the fused kernel the runtime expects to keep resident per CU for
  * profiles of n_alt levels (LDS-limited) in arithmetic tier `math`. */

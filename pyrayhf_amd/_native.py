@@ -120,6 +120,7 @@ _PROTOTYPES = {
                                [ctypes.c_double] * 9 + [ctypes.c_int32] + [ctypes.c_double] * 4 +
                                [ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32]),
     "prhf_gradient_home_counters": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
+    "prhf_pair_plan_counters": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
     "prhf_occupancy": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
                                       ctypes.POINTER(ctypes.c_int32)]),
     "prhf_sync": (ctypes.c_int, [ctypes.c_void_p]),
@@ -378,6 +379,13 @@ class Context:
         """(brackets refined, rays traced by the refine lanes, ray slots, refine wavefronts) of the last gradient_home."""
         buf = (ctypes.c_uint64 * 4)()
         raise_for(self._lib.prhf_gradient_home_counters(self._h, buf))
+        return tuple(int(v) for v in buf)
+
+    def pair_plan_counters(self):
+        """(pairs whose sum ran from a plan, eligible pairs that planned themselves) since this context was made
+        (option ``pair_plan``, include/prhf.h)."""
+        buf = (ctypes.c_uint64 * 2)()
+        raise_for(self._lib.prhf_pair_plan_counters(self._h, buf))
         return tuple(int(v) for v in buf)
 
     def occupancy(self, n_alt, math):

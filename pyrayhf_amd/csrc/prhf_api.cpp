@@ -165,6 +165,7 @@ struct prhf_ctx {
     double* h_pack_dev = nullptr;   // half, mapped into the device (h_pack_dev), takes a small result straight from the kernel
     unsigned long long* d_words = nullptr;   // 2 words: nanmax|Y| bits, any-not-NaN
     unsigned long long* h_words = nullptr;   // pinned
+    unsigned long long* d_plan_counters = nullptr;   // 2 words, since the context was made (prhf_pair_plan_counters)
     bool status_pending = false;
     uint64_t grad_home_counters[PRHF_GRAD_HOME_COUNTERS] = {};   // of the last prhf_gradient_home_f64 (prhf_gradient_home_counters)
 };
@@ -581,6 +582,7 @@ int run(prhf_ctx* c, const double* freq, int64_t n_freq, const double* den, cons
     prhf::StridedPieces pieces;
     std::memset(&pieces, 0, sizeof pieces);
     long long table_entries = mult_len + PRHF_PAIR_PAD;
+    bool any_plan = false;                     // a slice takes the planning pass: it needs the candidate list
     if (want_pairs && kn.strided_top != 0 && !tall) {
         for (int i = 0; i < n_segs; ++i) {
             prhf::SegDev& s = a.seg[i];
@@ -599,8 +601,12 @@ int run(prhf_ctx* c, const double* freq, int64_t n_freq, const double* den, cons
             }
             s.sp_off = pieces.sp_off[p];
             s.strided_lower = kn.strided_lower != 0;
+            s.pair_plan = slice_plans_pairs(s, tall, n_freq, lds_levels, kn) ? 1 : 0;
+            any_plan = any_plan || s.pair_plan != 0;
         }
     }
+    a.plan_counters = c->d_plan_counters;
+    a.plan_cap = (int)kn.pair_plan_cap;
     auto same_pieces = [&](const prhf::StridedPieces& o) { return std::memcmp(&o, &pieces, sizeof pieces) == 0; };
     if (want_pairs && grid) {
         if (!grid->pairs_ready || !same_pieces(grid->pieces)) {
@@ -630,7 +636,9 @@ int run(prhf_ctx* c, const double* freq, int64_t n_freq, const double* den, cons
         if (!grid) a.pairs = static_cast<const double*>(c->pairs.p);
         // per-frequency scalars: long launches read them from a table instead of dividing once per pair (a short
         // launch - one profile - is latency bound: it does without the extra kernel)
-        if (n_prof * n_freq >= 4096) {
+        // (... and so does a launch with a slice that plans its pairs: the heights that pass starts from are settled with
+        //  the candidate list, which reads the table.  By default such a slice has 4096 pairs anyway - fewer are chunked)
+        if (n_prof * n_freq >= 4096 || any_plan) {
             if ((rc = ensure(c, c->ftab, ((size_t)n_freq + 1) * 64)) != PRHF_OK) return rc;
             // The table's kernel zeroes, on the way, every control word the launches behind it count in: the block
             // queues and - their buffers sized here, as launch_short_kind sizes them again - the heads of the short-grid
@@ -1057,6 +1065,8 @@ int prhf_ctx_create(int device, prhf_ctx** out) {
         (e = hipMalloc(reinterpret_cast<void**>(&c->d_words), 2 * sizeof(unsigned long long))) != hipSuccess ||
         (e = hipHostMalloc(reinterpret_cast<void**>(&c->h_words), 2 * sizeof(unsigned long long),
                            hipHostMallocDefault)) != hipSuccess ||
+        (e = hipMalloc(reinterpret_cast<void**>(&c->d_plan_counters), 2 * sizeof(unsigned long long))) != hipSuccess ||
+        (e = hipMemset(c->d_plan_counters, 0, 2 * sizeof(unsigned long long))) != hipSuccess ||
         (e = prhf::configure_kernels(prhf::lds_bytes_for(kMaxAlt))) != hipSuccess) {
         prhf_ctx_destroy(c);
         return fail(PRHF_EHIP, "context setup failed: %s", hipGetErrorString(e));
@@ -1104,6 +1114,7 @@ int prhf_ctx_destroy(prhf_ctx* c) {
     if (c->h_pack) (void)hipHostFree(c->h_pack);
     if (c->d_words) (void)hipFree(c->d_words);
     if (c->h_words) (void)hipHostFree(c->h_words);
+    if (c->d_plan_counters) (void)hipFree(c->d_plan_counters);
     for (int i = 0; i < prhf_ctx::kTimingRing; ++i) {
         if (c->ring0[i]) (void)hipEventDestroy(c->ring0[i]);
         if (c->ring1[i]) (void)hipEventDestroy(c->ring1[i]);
@@ -2303,6 +2314,17 @@ int prhf_gradient_home_f64(prhf_ctx* c, int32_t geometry, const double* records,
 int prhf_gradient_home_counters(prhf_ctx* c, uint64_t* counters) {
     if (!c || !counters) return fail(PRHF_EINVAL, "null pointer");
     for (int k = 0; k < PRHF_GRAD_HOME_COUNTERS; ++k) counters[k] = c->grad_home_counters[k];
+    return PRHF_OK;
+}
+
+int prhf_pair_plan_counters(prhf_ctx* c, uint64_t* counters) {
+    if (!c || !counters) return fail(PRHF_EINVAL, "null pointer");
+    DeviceScope device_scope_(c->device);
+    unsigned long long w[2] = {0, 0};
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpy(w, c->d_plan_counters, sizeof w, hipMemcpyDeviceToHost));
+    counters[0] = w[0];
+    counters[1] = w[1];
     return PRHF_OK;
 }
 

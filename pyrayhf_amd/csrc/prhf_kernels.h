@@ -102,6 +102,8 @@ struct SegDev {
                                      // (launch_grid_strided; the main loop's strided sum); 0: none
     int strided_lower;               // with sp_off > 0: the segments below the top three take the strided sum too
                                      // (option strided_lower)
+    int pair_plan;                   // with sp_off > 0: the workgroup plans its pairs' sums one pair per thread (option
+                                     // pair_plan; plan_pairs in prhf_kernels.hip)
     int thread_scan;                 // X mode: reflection heights settled one frequency per thread while the candidate
                                      // list is made (on by default; PRHF_THREAD_SCAN_MIN turns it off for A/B runs.
                                      // O mode always does, by binary search)
@@ -142,6 +144,10 @@ struct KArgs {
     // Levels the staged arrays (nodes, f_N^2, g_p |B|) have room for: n_alt, or - a column of more than 1400 levels
     // whose bottomsides all fit LDS (launch_peak_levels) - the highest peak index of the launch + 1
     long long lds_levels;
+    // The planning pass (SegDev::pair_plan): [0] pairs that ran from a plan, [1] eligible pairs that planned themselves,
+    // added to once per workgroup and block; plan_cap > 0 caps the records per workgroup (tests)
+    unsigned long long* plan_counters;
+    int plan_cap;
     SegDev seg[PRHF_MAX_SEGMENTS];
 };
 

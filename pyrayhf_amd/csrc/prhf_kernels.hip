@@ -1016,6 +1016,77 @@ struct TopSegment {
     double b0, b1;          // Y / sqrt(2) = g_p |B| / (sqrt(2) f) = b0 + b1 m
     double q0, q1, q2, q3;  // 2 cos^2 psi = q0 + m (q1 + m (q2 + m q3))
 };
+// The plan of a pair's sum ("the planning pass"): which grid points the top three segments begin at and
+// which stretch [a, E) of each takes the strided rule.  These integers steer the main loop's scalar control; they are
+// computed either by the wave itself - every lane the same values - or, once per pair, by one thread while the
+// workgroup makes its candidate list (plan_pairs).  Both callers go through the functions below, which spell every
+// fused multiply-add out: they are compiled once with contraction on (the main loop) and once with it off (the
+// workgroup's prologue), and a differently rounded singular index moves a strided stretch by 64 points.
+struct SegLinear {
+    double d0, d1;          // den  = d0 + d1 m
+    double b0, b1;          // Y / sqrt(2) = b0 + b1 m
+};
+__device__ __forceinline__ SegLinear seg_linear(double o, double den, double sden, double b, double sb, double s, double cY) {
+    SegLinear t;
+    t.d0 = __builtin_fma(sden, o, den);  t.d1 = sden * s;
+    t.b0 = cY * __builtin_fma(sb, o, b);  t.b1 = cY * (sb * s);
+    return t;
+}
+// floor(i*) - 1 for the first index i* with m_i >= m_star by the closed form of the reference's stretch (one v_log_f32)
+__device__ __forceinline__ int stretch_guess(double m_star, double n1) {
+    const double A = __builtin_fma(1.0 - m_star, 22025.465794806718, 1.0);
+    const double ln_a = (double)__builtin_amdgcn_logf((float)A) * 0.6931471805599453;      // (v_log_f32: log2)
+    return (int)__builtin_fma(-ln_a, n1 * 0.1, n1) - 1;
+}
+// the real-valued index of multiplier m on that stretch; a point past the stretch's own end (no logarithm) has none: 1e9
+__device__ __forceinline__ double stretch_index(double m, double n1) {
+    const double A = __builtin_fma(1.0 - m, 22025.465794806718, 1.0);
+    if (!(A > 0.0)) return 1e9;
+    const double ln_a = (double)__builtin_amdgcn_logf((float)A) * 0.6931471805599453;
+    return fmin(fmax(__builtin_fma(-ln_a, n1 * 0.1, n1), -1e9), 1e9);
+}
+// The strided stretch [a_s, e_s) of a top segment whose first point is lo_s, whose last ordinary point is q_s and whose
+// whole wave-iterations begin at begin_s (a multiple of 64): both guards of strided_run and its "at least 64 strided
+// points" test.  a_s == e_s: the segment runs point by point.
+struct StridedSpan {
+    int a_s, e_s;
+};
+__device__ __forceinline__ StridedSpan strided_span(int lo_s, int q_s, int begin_s, const SegLinear& t, double cX, double n1) {
+    constexpr int kGuard = 256;
+    constexpr double kTau = 1e-6;
+    int a_s = begin_s >= lo_s + 3 ? begin_s : begin_s + 64;    // a - 3 >= the segment's first point
+    int hi_lim = q_s - 3;                                      // b + 3 <= this
+    bool skip = false;
+    // 1 - X - Y = gap - sl m on the segment's continuation (X + Y = cX (d0 + d1 m) + sqrt(2) (b0 + b1 m)): zero at
+    // m_sing, below kTau within dm of it
+    const double r2 = 1.4142135623730951;
+    const double sl = __builtin_fma(cX, t.d1, r2 * t.b1);
+    const double gap = __builtin_fma(-r2, t.b0, __builtin_fma(-cX, t.d0, 1.0));
+    if (__builtin_fabs(sl) > 1e-300) {
+        const double m_sing = gap / sl, dm = kTau / __builtin_fabs(sl);
+        const double i_sing = stretch_index(m_sing, n1);
+        const int below = (int)__builtin_floor(fmin(i_sing - (double)(kGuard + 1), stretch_index(m_sing - dm, n1)));
+        const int above = (int)__builtin_ceil(fmax(i_sing + (double)(kGuard + 1), stretch_index(m_sing + dm, n1)));
+        if (2.0 * i_sing >= (double)(a_s + q_s)) hi_lim = min(hi_lim, below);              // points <= below are clear of it
+        else a_s = max(a_s, begin_s + ((above + 3 - begin_s + 63) & ~63));                 // points >= above too
+    } else if (!(__builtin_fabs(gap) >= kTau)) {
+        skip = true;                                           // X + Y constant and next to 1
+    }
+    const int e_s = min(q_s + 1, hi_lim + 5) & ~63;            // b = E - 8: b + 3 <= hi_lim, E - 1 <= q
+    StridedSpan r;
+    r.a_s = r.e_s = 0;
+    if (!skip && ((e_s - a_s) >> 3) >= 64) {                   // strided points a, a + 8, .. b: at least 64
+        r.a_s = a_s;
+        r.e_s = e_s;
+    }
+    return r;
+}
+// A pair's plan as it lies in LDS, four words: the first points of the top three segments and the top segment's level
+// (16 bits each: grids of fewer than 65536 points), then a_s / 64 and e_s / 64 of the three segments (10 bits each),
+// the number of segments with a loop of their own and the "planned" bit.
+constexpr int kPlanBytes = 16;
+constexpr unsigned kPlanValid = 1u << 30;
+
 template <bool G>
 __device__ __forceinline__ TopSegment top_segment(const NodeSpace<G>& nodes_v, int j, double span, double cY) {
 #pragma clang fp contract(fast)
@@ -1025,8 +1096,9 @@ __device__ __forceinline__ TopSegment top_segment(const NodeSpace<G>& nodes_v, i
     const double den = nodes_v.f64(nd + 16), sden = nodes_v.f64(nd + 24), b = nodes_v.f64(nd + 32), sb = nodes_v.f64(nd + 40),
                  u0 = nodes_v.f64(nd + 48), u1 = nodes_v.f64(nd + 56), u2 = nodes_v.f64(nd + 64), u3 = nodes_v.f64(nd + 72);
     TopSegment t;
-    t.d0 = den + sden * o;  t.d1 = sden * s;
-    t.b0 = cY * (b + sb * o);  t.b1 = cY * (sb * s);
+    const SegLinear lin = seg_linear(o, den, sden, b, sb, s, cY);
+    t.d0 = lin.d0;  t.d1 = lin.d1;
+    t.b0 = lin.b0;  t.b1 = lin.b1;
     t.q0 = u0 + o * (u1 + o * (u2 + o * u3));
     t.q1 = s * (u1 + o * (2.0 * u2 + 3.0 * o * u3));
     t.q2 = (s * s) * (u2 + 3.0 * o * u3);
@@ -1130,7 +1202,39 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
     int n_seg = 0;
     TopSegment top;
     __builtin_memset(&top, 0, sizeof top);
-    if (TOP && end - first >= PRHF_TOP_MIN_POINTS) {
+    // The pair's plan, where the workgroup made one (plan_pairs; whole pairs only, first == 0): four words of LDS.  Their
+    // address arrives in the place of the hint table's, which a uniform altitude grid does not use (the loop function
+    // passes its arguments in registers: one more would travel through scratch memory); 0: no plan.  A planned pair
+    // skips the searches below and the guard arithmetic of strided_run; a pair without a plan computes the same
+    // integers itself.
+    constexpr bool PLANNABLE = TOP && MODE == PRHF_KMODE_X && !CHECK && !G && !HINT;
+    // (nothing of it stays in a scalar register across the loops, which need every one they can get: the address waits
+    //  in a vector register, like a0 and the node table's, and strided_run reads its two words when its turn comes)
+    typedef __attribute__((address_space(3))) const unsigned* LdsU32;
+    unsigned plan_lds = 0u, plan_v = 0u;
+    if constexpr (PLANNABLE) {
+        plan_lds = (unsigned)uniform((int)hint_lds);
+        if (plan_lds != 0u && ((unsigned)uniform((int)((LdsU32)(uintptr_t)plan_lds)[3]) & kPlanValid) == 0u) plan_lds = 0u;
+        plan_v = plan_lds;
+        asm volatile("" : "+v"(plan_v));
+    }
+    if (TOP && PLANNABLE && plan_lds != 0u) {
+        const LdsU32 rec = (LdsU32)(uintptr_t)plan_lds;
+        const unsigned pw0 = (unsigned)uniform((int)rec[0]), pw1 = (unsigned)uniform((int)rec[1]);
+        n_seg = uniform((int)(rec[2] >> 30));
+        const int j_top = (int)(pw1 >> 16);
+        int run_end = whole_end;
+#pragma unroll
+        for (int sidx = 0; sidx < kTopSegments; ++sidx) {
+            if (sidx >= n_seg) break;
+            const int lo = (int)(sidx == 0 ? pw0 & 0xffffu : (sidx == 1 ? pw0 >> 16 : pw1 & 0xffffu));
+            seg_begin[sidx] = first + ((lo - first + 63) & ~63);
+            seg_end[sidx] = run_end;
+            seg_j[sidx] = j_top - sidx;
+            seg_lo[sidx] = lo;
+            run_end = first + ((lo - first) & ~63);
+        }
+    } else if (TOP && end - first >= PRHF_TOP_MIN_POINTS) {
         const int i_last = (last_special >= 0 ? last_special : end - 1);
         const u32x4 vl = __builtin_amdgcn_raw_buffer_load_b128(rsrc, 0, i_last * (int)sizeof(double2), 0);
         double2 gl;
@@ -1162,10 +1266,8 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
             // every non-decreasing multiplier - or a guess at the range's edge falls through to the search below, which
             // costs three dependent loads per segment.  The index is the search's own either way.
             {
-                const double A = __builtin_fma(1.0 - m_star, 22025.465794806718, 1.0);
-                const double ln_a = (double)__builtin_amdgcn_logf((float)A) * 0.6931471805599453;      // (v_log_f32: log2)
                 const double n1 = (double)(CHECK ? i_last + 1 : i_last);                                // N - 1
-                const int base = uniform((int)__builtin_fma(-ln_a, n1 * 0.1, n1)) - 1;                  // floor(i*) - 1
+                const int base = uniform(stretch_guess(m_star, n1));                                    // floor(i*) - 1
                 if (base >= lo && base + 3 < hi) {
                     const u32x4 vg = __builtin_amdgcn_raw_buffer_load_b128(
                         rsrc, (unsigned)(base + (lane & 3)) * (unsigned)sizeof(double2), 0, 0);
@@ -1333,41 +1435,25 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
     // rounding error of about 1e-16 / (1 - X - Y) there, which the eightfold weights amplify instead of averaging out
     // (a low frequency that reflects in a nearly flat layer has 1 - X - Y < 1e-7 over thousands of points: 4e-11 of
     // its sum, measured; with this bound the per-point error of a strided term stays below 1e-10).
-    auto strided_run = [&](int lo_s, int q_s, int begin_s) {
-        constexpr int kGuard = 256;
-        constexpr double kTau = 1e-6;
-        int a_s = begin_s >= lo_s + 3 ? begin_s : begin_s + 64;    // a - 3 >= the segment's first point
-        int hi_lim = q_s - 3;                                      // b + 3 <= this
-        int skip = 0;
-        {
-            // 1 - X - Y = gap - sl m on the segment's continuation (X + Y = cX (d0 + d1 m) + sqrt(2) (b0 + b1 m)): zero at
-            // m_sing, below kTau within dm of it.  Indices by the closed form of the stretch (v_log_f32, good to 1e-3 of
-            // an index); a point past the stretch's own end (no logarithm) has no index: 1e9.
-            const double r2 = 1.4142135623730951;
-            const double sl = cX * top.d1 + r2 * top.b1, gap = 1.0 - cX * top.d0 - r2 * top.b0;
-            const double n1 = (double)i_last_s;
-            auto index_of = [&](double m) {
-                const double A = __builtin_fma(1.0 - m, 22025.465794806718, 1.0);
-                if (!(A > 0.0)) return 1e9;
-                const double ln_a = (double)__builtin_amdgcn_logf((float)A) * 0.6931471805599453;
-                return fmin(fmax(__builtin_fma(-ln_a, n1 * 0.1, n1), -1e9), 1e9);
-            };
-            if (__builtin_fabs(sl) > 1e-300) {
-                const double m_sing = gap / sl, dm = kTau / __builtin_fabs(sl);
-                const double i_sing = index_of(m_sing);
-                const int below = uniform((int)__builtin_floor(fmin(i_sing - (double)(kGuard + 1), index_of(m_sing - dm))));
-                const int above = uniform((int)__builtin_ceil(fmax(i_sing + (double)(kGuard + 1), index_of(m_sing + dm))));
-                if (2.0 * i_sing >= (double)(a_s + q_s)) hi_lim = min(hi_lim, below);          // points <= below are clear of it
-                else a_s = max(a_s, first + ((above + 3 - first + 63) & ~63));                 // points >= above too
-            } else if (!(__builtin_fabs(gap) >= kTau)) {
-                skip = 1;                                          // X + Y constant and next to 1: this segment runs as today
-            }
+    auto strided_run = [&](int lo_s, int q_s, int begin_s, int sidx) {
+        int a_s, e_s;
+        const unsigned plan_s = PLANNABLE ? (unsigned)uniform((int)plan_v) : 0u;
+        if (PLANNABLE && plan_s != 0u) {
+            // (a_s / 64, e_s / 64: ten bits each, in segment order from bit 0 of the third word)
+            const LdsU32 rec = (LdsU32)(uintptr_t)plan_s;
+            const unsigned pw2 = (unsigned)uniform((int)rec[2]), pw3 = (unsigned)uniform((int)rec[3]);
+            const unsigned pa = sidx == 0 ? pw2 : (sidx == 1 ? pw2 >> 20 : pw3 >> 10);
+            const unsigned pe = sidx == 0 ? pw2 >> 10 : (sidx == 1 ? pw3 : pw3 >> 20);
+            a_s = (int)((pa & 1023u) << 6);
+            e_s = (int)((pe & 1023u) << 6);
+        } else {
+            // (the guards come out of vector arithmetic: back to scalars, or the loops below lose their scalar control)
+            SegLinear lin;
+            lin.d0 = top.d0; lin.d1 = top.d1; lin.b0 = top.b0; lin.b1 = top.b1;
+            const StridedSpan sp = strided_span(lo_s, q_s, begin_s, lin, cX, (double)i_last_s);
+            a_s = uniform(sp.a_s);
+            e_s = uniform(sp.e_s);
         }
-        // (the guards come out of vector arithmetic: back to scalars, or the loops below lose their scalar control)
-        a_s = uniform(a_s);
-        hi_lim = uniform(hi_lim);
-        if (uniform(skip)) return;
-        const int e_s = min(q_s + 1, hi_lim + 5) & ~63;            // b = E - 8: b + 3 <= hi_lim, E - 1 <= q
         const int count = (e_s - a_s) >> 3;                        // strided points a, a + 8, .. b
         if (count < 64) return;                                    // (this segment runs as today)
         run_top(a_s);                                              // one by one up to a
@@ -1552,7 +1638,7 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
                     const int lo_s = sidx == 0 ? seg_lo[0] : (sidx == 1 ? seg_lo[1] : seg_lo[2]);
                     // the segment's last ordinary point: the one below the last of the grid, or below the next segment's first
                     const int q_s = sidx == 0 ? i_last_s - 1 : (sidx == 1 ? seg_lo[0] - 1 : seg_lo[1] - 1);
-                    strided_run(lo_s, q_s, begin_s);
+                    strided_run(lo_s, q_s, begin_s, sidx);
                 }
                 run_top(end_s);
             }
@@ -1611,7 +1697,8 @@ __device__ __forceinline__ double integrate_chunk(const Node* __restrict__ nodes
                                                   const BlockInfo& info, const double* __restrict__ mult,
                                                   const double2* __restrict__ pairs, int n_points, int i0,
                                                   int i1, double f_hz, double f2, double cX, double cY2,
-                                                  double h_refl, int lane, double well_conditioned, int sp_off) {
+                                                  double h_refl, int lane, double well_conditioned, int sp_off,
+                                                  unsigned plan_lds) {
     const int K = info.K;
     const double a0 = info.a0;
     const double span = uniform(h_refl - a0);      // :413 (critical_height - aalt[0])
@@ -1657,8 +1744,10 @@ __device__ __forceinline__ double integrate_chunk(const Node* __restrict__ nodes
             const unsigned hint_lds = (unsigned)(uintptr_t)(LdsU16)hint;
             const int poly = info.poly_angle == 4 ? 4 : 4 - info.poly_angle;    // degree: 3 cubic, 2 quadratic, 1 linear; 4: rotation form
             LeanResult r;
-#define PRHF_LEAN(P, H, T) lean_loop<MODE, TIER == 0, P, H, T, G>(nodes_lds, hint_lds, pairs, first, lean_end, last_special, \
-                                                                 span, a0, kj, cX, cY2, well_conditioned, (T) ? sp_off : 0)
+            // (a uniform altitude grid has no use for the hint table: its argument carries the pair's plan, see lean_loop_body)
+#define PRHF_LEAN(P, H, T) lean_loop<MODE, TIER == 0, P, H, T, G>(nodes_lds, ((T) && !(H)) ? plan_lds : hint_lds, pairs, first, \
+                                                                 lean_end, last_special, span, a0, kj, cX, cY2,                \
+                                                                 well_conditioned, (T) ? sp_off : 0)
 #define PRHF_LEAN_POLY(H, T) (poly == 1 ? PRHF_LEAN(1, H, T) : (poly == 2 ? PRHF_LEAN(2, H, T) : PRHF_LEAN(3, H, T)))
             if (poly == 4) r = by_hint ? PRHF_LEAN(4, true, false) : PRHF_LEAN(4, false, false);
             else if (by_hint) {
@@ -2018,11 +2107,158 @@ __device__ __forceinline__ bool collapsed_grid_sum(const Node* nodes, const Bloc
     return true;
 }
 
+// Where a workgroup keeps the plans of its pairs (plan_pairs): LDS that is dead once an X-mode candidate list with
+// settled heights exists - the g_p |B| array, the hint table of a uniform altitude grid, the tail of the f_N^2 array
+// behind the heights.  Record r lies in the first of the three with room; the items beyond `total` plan themselves.
+struct PlanRoom {
+    unsigned base0, base1, base2;      // LDS byte addresses
+    int cap0, cap01;                   // records in the first area, in the first two
+    int total;                         // records in all (0: this workgroup plans nothing)
+};
+__device__ __forceinline__ unsigned plan_slot(const PlanRoom& r, int i) {
+    return i < r.cap0 ? r.base0 + (unsigned)i * (unsigned)kPlanBytes
+                      : (i < r.cap01 ? r.base1 + (unsigned)(i - r.cap0) * (unsigned)kPlanBytes
+                                     : r.base2 + (unsigned)(i - r.cap01) * (unsigned)kPlanBytes);
+}
+
+// The plan of one pair by one thread: the integers lean_loop_body would compute wave-uniformly - first points of the
+// top three segments by the closed form of the stretch and its four-entry bracket check, then the strided stretch of
+// each - written to `rec` (four words).  Returns false where the guess does not bracket (another grid, a range's
+// edge): that pair's wave runs its own search.  `h` is the settled reflection height (span > 0 and kj inside the node
+// table: checked by the caller, as integrate_chunk does).
+__device__ __attribute__((noinline)) bool plan_pair(const Node* nodes, int K, const double2* __restrict__ pairs, int n_points,
+                                                    double span, double kj, double cX, double cY2, unsigned* rec) {
+    const int i_last = n_points - 1;
+    const double n1 = (double)i_last;
+    const int j_top = (int)(pairs[i_last].x * kj);
+    if (j_top < 0 || j_top > K - 1) return false;
+    int search_hi = i_last + 1, run_end = i_last & ~63;
+    // one segment: 0 the guess does not bracket, 1 a loop of its own from *lo, 2 too short for one (nor are those below)
+    auto find = [&](int j, int* lo_out) {
+        if (j < 0) return 2;
+        const double m_star = (double)j / kj;
+        const int base = stretch_guess(m_star, n1);
+        if (!(base >= 0 && base + 3 < search_hi)) return 0;
+        const unsigned hit4 = (pairs[base].x >= m_star ? 1u : 0u) | (pairs[base + 1].x >= m_star ? 2u : 0u) |
+                              (pairs[base + 2].x >= m_star ? 4u : 0u) | (pairs[base + 3].x >= m_star ? 8u : 0u);
+        if (!(hit4 != 0u && (hit4 & 1u) == 0u)) return 0;
+        const int lo = base + __ffs((int)hit4) - 1;
+        if (((lo + 63) & ~63) + 128 > run_end) return 2;
+        *lo_out = lo;
+        search_hi = lo + 1;
+        run_end = lo & ~63;
+        return 1;
+    };
+    int lo0 = 0, lo1 = 0, lo2 = 0, n_seg = 0;
+    const int f0 = find(j_top, &lo0);
+    if (f0 == 0) return false;
+    if (f0 == 1) {
+        n_seg = 1;
+        const int f1 = find(j_top - 1, &lo1);
+        if (f1 == 0) return false;
+        if (f1 == 1) {
+            n_seg = 2;
+            const int f2 = find(j_top - 2, &lo2);
+            if (f2 == 0) return false;
+            if (f2 == 1) n_seg = 3;
+        }
+    }
+    const double hcY2 = 0.5 * cY2;
+    const double cYs = hcY2 * rsqrt_cubic(hcY2);
+    // a_s / 64 | e_s / 64 << 10 of one segment
+    auto span_of = [&](int j, int lo, int q_s) {
+        const Node& nd = nodes[j];
+        const SegLinear lin = seg_linear(nd.off, nd.den, nd.sden, nd.b, nd.sb, span, cYs);
+        const StridedSpan sp = strided_span(lo, q_s, (lo + 63) & ~63, lin, cX, n1);
+        return (unsigned)(sp.a_s >> 6) | ((unsigned)(sp.e_s >> 6) << 10);
+    };
+    const unsigned ae0 = n_seg > 0 ? span_of(j_top, lo0, i_last - 1) : 0u;
+    const unsigned ae1 = n_seg > 1 ? span_of(j_top - 1, lo1, lo0 - 1) : 0u;
+    const unsigned ae2 = n_seg > 2 ? span_of(j_top - 2, lo2, lo1 - 1) : 0u;
+    rec[0] = (unsigned)lo0 | ((unsigned)lo1 << 16);
+    rec[1] = (unsigned)lo2 | ((unsigned)j_top << 16);
+    rec[2] = ae0 | ((ae1 & 1023u) << 20) | ((unsigned)n_seg << 30);
+    rec[3] = (ae1 >> 10) | (ae2 << 10) | kPlanValid;
+    return true;
+}
+
+// The planning pass: after the candidate list, before the items.  Thread i plans the i-th item this
+// workgroup will pull (a profile cut into several workgroups: each plans its own share).  Eligible: what the strided
+// sum requires - X mode, fast tier, whole pairs of PRHF_TOP3_MIN_POINTS .. 65535 points on the reference's stretch
+// (header word 0) - with heights settled per thread and a uniform altitude grid.  Counts, once per workgroup, the
+// main-loop pairs that got a plan and those that will plan themselves (no room, guess not bracketing).
+template <int TIER, int THREADS, bool G>
+__device__ __forceinline__ PlanRoom plan_pairs(const KArgs& a, const SegDev& sg, const Node* nodes, double* pf2, double* gb,
+                                               unsigned short* hint, const unsigned short* cand, const BlockInfo& info,
+                                               int block_in_prof, int blocks_per_prof, unsigned* plan_cnt) {
+    constexpr int W = THREADS / 64;
+    PlanRoom room;
+    room.base0 = room.base1 = room.base2 = 0u;
+    room.cap0 = room.cap01 = room.total = 0;
+    if (TIER != 1 || G) return room;
+    const bool shape_ok = sg.pair_plan && sg.mode == PRHF_KMODE_X && sg.lean && a.pairs && sg.sp_off > 0 && sg.chunks == 1 &&
+                          sg.n_points >= PRHF_TOP3_MIN_POINTS && sg.n_points < 65536 && info.heights && info.n_cand > 0 &&
+                          info.uniform && !info.unmag && info.poly_angle >= 1 && info.poly_angle <= 3;
+    if (!shape_ok) return room;
+    const double2* pairs = reinterpret_cast<const double2*>(a.pairs) + sg.mult_off;
+    // (the strided table's header word: 0 on the reference's stretch from its own origin, see grid_strided_kernel)
+    if (reinterpret_cast<const unsigned*>(pairs + (sg.sp_off - sg.mult_off))[0] != 0u) return room;
+    typedef __attribute__((address_space(3))) const double* LdsDouble;
+    typedef __attribute__((address_space(3))) const unsigned short* LdsU16;
+    const int levels = (int)a.lds_levels;
+    const int used = (info.n_cand + 1) & ~1;           // heights live in pf2[0 .. n_cand)
+    room.base0 = (unsigned)(uintptr_t)(LdsDouble)gb;
+    room.base1 = (unsigned)(uintptr_t)(LdsU16)hint;
+    room.base2 = (unsigned)(uintptr_t)(LdsDouble)(pf2 + used);
+    room.cap0 = levels * 8 / kPlanBytes;
+    room.cap01 = room.cap0 + kHintBuckets * 2 / kPlanBytes;
+    room.total = room.cap01 + max(levels - used, 0) * 8 / kPlanBytes;
+    if (a.plan_cap > 0) room.total = min(room.total, a.plan_cap);
+    const int first_item = block_in_prof * W, round_items = blocks_per_prof * W;
+    int n_planned = 0, n_self = 0;
+    for (int u = threadIdx.x;; u += THREADS) {
+        const int t = (u / W) * round_items + first_item + (u % W);
+        if (t >= info.n_cand) break;
+        const double span = info.heights[t] - info.a0;
+        const double kj = span * info.inv_step;
+        const bool main_loop = span > 0.0 && kj <= (double)(info.K - 1);       // (integrate_chunk's own test)
+        bool done = false;
+        if (u < room.total) {
+            unsigned* rec = u < room.cap0 ? reinterpret_cast<unsigned*>(gb) + 4 * u
+                                          : (u < room.cap01 ? reinterpret_cast<unsigned*>(hint) + 4 * (u - room.cap0)
+                                                            : reinterpret_cast<unsigned*>(pf2 + used) + 4 * (u - room.cap01));
+            if (main_loop) {
+                const double* row = a.ftab + 8 * (long long)cand[t];
+                done = plan_pair(nodes, info.K, pairs, sg.n_points, span, kj, row[2], row[3], rec);
+            }
+            if (!done) rec[3] = 0u;
+        }
+        if (main_loop) {
+            if (done) ++n_planned; else ++n_self;
+        }
+    }
+    if (n_planned) atomicAdd(&plan_cnt[0], (unsigned)n_planned);
+    if (n_self) atomicAdd(&plan_cnt[1], (unsigned)n_self);
+    __syncthreads();
+    if (threadIdx.x == 0 && a.plan_counters) {
+        if (plan_cnt[0]) atomicAdd(&a.plan_counters[0], (unsigned long long)plan_cnt[0]);
+        if (plan_cnt[1]) atomicAdd(&a.plan_counters[1], (unsigned long long)plan_cnt[1]);
+    }
+    room.base0 = (unsigned)uniform((int)room.base0);
+    room.base1 = (unsigned)uniform((int)room.base1);
+    room.base2 = (unsigned)uniform((int)room.base2);
+    room.cap0 = uniform(room.cap0);
+    room.cap01 = uniform(room.cap01);
+    room.total = uniform(room.total);
+    return room;
+}
+
 template <int MODE, int TIER, int THREADS, bool G>
 __device__ __forceinline__ void run_items(const KArgs& a, const SegDev& sg, const Node* nodes,
                                           const double* pf2, const double* gb, const unsigned short* hint,
                                           const unsigned short* cand, const BlockInfo& info, long long prof_local,
-                                          int block_in_prof, int blocks_per_prof, int* item_next, double* red) {
+                                          int block_in_prof, int blocks_per_prof, int* item_next, double* red,
+                                          const PlanRoom& room) {
     constexpr int W = THREADS / 64;
     const int lane = threadIdx.x & 63;
     const double* keep = kept_scalars<THREADS>(red);
@@ -2057,8 +2293,10 @@ __device__ __forceinline__ void run_items(const KArgs& a, const SegDev& sg, cons
     const bool local = S > 0;
     double* part = red + 10 * W + 8;                   // (behind the kept scalars; rows 0 .. 9 may still be read by a
     if (local && lane == 0) part[wave] = 0.0;          //  wave that left stage_profile early)
+    int pulled = 0;                                    // how many items this workgroup had pulled before the current one
     auto next_item = [&]() {
         const int u = uniform(atomicAdd(item_next, 1)) >> 6;
+        pulled = u;
         // this block's items: rounds of W, interleaved with the profile's other blocks
         return uniform((u / W) * round_items + first_item + (u % W));
     };
@@ -2078,6 +2316,8 @@ __device__ __forceinline__ void run_items(const KArgs& a, const SegDev& sg, cons
         }
         double result = qnan();
         bool reflects = false;
+        // the pair's plan, if the workgroup made one (plan_pairs): records are numbered in the order the items are pulled
+        const unsigned plan_lds = pulled < room.total ? plan_slot(room, pulled) : 0u;
         if (!info.bad) {
             const PairFreq pf = pair_freq(a, f);
             double h = 0.0;
@@ -2092,10 +2332,10 @@ __device__ __forceinline__ void run_items(const KArgs& a, const SegDev& sg, cons
                 const int i1 = min(sg.n_points, i0 + sg.chunk_len);
                 if (info.unmag)
                     result = integrate_chunk<MODE, TIER, true, G>(nodes, hint, info, mult, pairs, sg.n_points, i0, i1,
-                                                               pf.f_hz, pf.f2, pf.cX, pf.cY2, h, lane, wc, sp_off);
+                                                               pf.f_hz, pf.f2, pf.cX, pf.cY2, h, lane, wc, sp_off, plan_lds);
                 else
                     result = integrate_chunk<MODE, TIER, false, G>(nodes, hint, info, mult, pairs, sg.n_points, i0,
-                                                                i1, pf.f_hz, pf.f2, pf.cX, pf.cY2, h, lane, wc, sp_off);
+                                                                i1, pf.f_hz, pf.f2, pf.cX, pf.cY2, h, lane, wc, sp_off, plan_lds);
             } else if (info.K == 1) {
                 result = (c == C - 1) ? one_level_term<MODE, TIER>(nodes, info, pf, sg.well_conditioned) : 0.0;
                 reflects = true;
@@ -2133,7 +2373,7 @@ template <int TIER, int THREADS, bool G>
 __device__ __forceinline__ unsigned long long run_block(const KArgs& a, const SegDev& sg, Node* nodes, double* pf2, double* gb,
                                           unsigned short* hint, unsigned short* cand, int* cand_count, double* red,
                                           long long prof_local, int block_in_prof, int blocks_per_prof,
-                                          int* item_next) {
+                                          int* item_next, unsigned* plan_cnt) {
     const long long p = sg.prof_begin + prof_local;
     BlockInfo info = stage_profile<TIER, THREADS>(
         a.den + p * a.prof_stride, a.bmag + p * a.field_stride, a.bpsi + p * a.field_stride,
@@ -2166,12 +2406,15 @@ __device__ __forceinline__ unsigned long long run_block(const KArgs& a, const Se
         if (info.bad) post_status(a.status, (unsigned)info.bad);
         if (sg.chunks > 1 && sg.slots == 0) a.altmin[sg.altmin_off + prof_local] = kept_scalars<THREADS>(red)[kKeepAltMin];
     }
+    // (every thread of the workgroup takes the same branches up to here: the pass has a barrier of its own)
+    const PlanRoom room = plan_pairs<TIER, THREADS, G>(a, sg, nodes, pf2, gb, hint, cand, info, block_in_prof, blocks_per_prof,
+                                                       plan_cnt);
     if (sg.mode == PRHF_KMODE_O)
         run_items<PRHF_KMODE_O, TIER, THREADS, G>(a, sg, nodes, pf2, gb, hint, cand, info, prof_local, block_in_prof,
-                                               blocks_per_prof, item_next, red);
+                                               blocks_per_prof, item_next, red, room);
     else
         run_items<PRHF_KMODE_X, TIER, THREADS, G>(a, sg, nodes, pf2, gb, hint, cand, info, prof_local, block_in_prof,
-                                               blocks_per_prof, item_next, red);
+                                               blocks_per_prof, item_next, red, room);
     return t_staged;
 }
 
@@ -2214,6 +2457,7 @@ __device__ __forceinline__ void vfo_kernel_body(const KArgs& a) {
     __shared__ long long next_bid;
     __shared__ int item_next;
     __shared__ int cand_count[PRHF_BLOCK_THREADS / 64 + 1];
+    __shared__ unsigned plan_cnt[2];           // pairs of this block that got a plan / that plan themselves (plan_pairs)
     // Follow-up of a short-grid launch: the blocks to evaluate are listed (block_list[1 .. block_list[0]])
     const unsigned* list = a.block_list;
     const long long n_blocks = list ? (long long)list[0] : a.n_blocks;
@@ -2224,7 +2468,10 @@ __device__ __forceinline__ void vfo_kernel_body(const KArgs& a) {
     if (ticket >= n_blocks) return;
     long long bid = list ? (long long)list[1 + ticket] : ticket;
     for (;;) {
-        if (threadIdx.x == 0) item_next = 0;   // ordered before its first use by the barriers of stage_profile
+        if (threadIdx.x == 0) {                // ordered before their first use by the barriers of stage_profile
+            item_next = 0;
+            plan_cnt[0] = plan_cnt[1] = 0u;
+        }
 #ifdef PRHF_TRACE
         const unsigned long long t_start = wall_clock64();
 #endif
@@ -2269,9 +2516,9 @@ __device__ __forceinline__ void vfo_kernel_body(const KArgs& a) {
 
         const unsigned long long t_staged = (TIER_SEL == 0 || (TIER_SEL == 2 && sg.tier == 0))
             ? run_block<0, THREADS, TALL>(a, sg, nodes, pf2, gb, hint, cand, cand_count, red, prof_local, block_in_prof, bpp,
-                                    &item_next)
+                                    &item_next, plan_cnt)
             : run_block<1, THREADS, TALL>(a, sg, nodes, pf2, gb, hint, cand, cand_count, red, prof_local, block_in_prof, bpp,
-                                    &item_next);
+                                    &item_next, plan_cnt);
         (void)t_staged;
 #ifdef PRHF_TRACE
         if (a.trace && (threadIdx.x & 63) == 0) {

@@ -78,6 +78,12 @@ struct Knobs {
                                        // PRHF_STRIDED_MIN_SEGMENT points below those three as well, in one strided pass
                                        // and one pass over the segment boundaries (0: the launch of strided_top alone,
                                        // bit for bit; strided_top = 0 switches both off)
+    double pair_plan = 1;              // ... and the integers that steer such a pair's sum - first points of the top three
+                                       // segments, the strided stretch of each - are computed once per pair, by one thread
+                                       // while the workgroup makes its candidate list, instead of by all 64 lanes of the
+                                       // pair's wave (0: the launch of before, bit for bit; values never
+                                       // depend on it)
+    double pair_plan_cap = 0;          // > 0: a workgroup keeps at most this many plans, the other pairs plan themselves (tests)
 };
 struct KnobName {
     const char* name;
@@ -112,6 +118,8 @@ const KnobName kKnobNames[] = {
     {"tall_lean", &Knobs::tall_lean, 0, 1},
     {"strided_top", &Knobs::strided_top, 0, 1},
     {"strided_lower", &Knobs::strided_lower, 0, 1},
+    {"pair_plan", &Knobs::pair_plan, 0, 1},
+    {"pair_plan_cap", &Knobs::pair_plan_cap, 0, 1024},
 };
 constexpr int kWavesPerBlock = PRHF_BLOCK_THREADS / 64;
 
@@ -177,6 +185,16 @@ inline void plan_slice(prhf::SegDev& s, long long n_freq, long long wg_slots, co
         s.tail_prof = P - tail;
         s.tail_bpp = kTailBpp;
     }
+}
+
+// Does a slice take the planning pass (SegDev::pair_plan)?  Only where the strided sum is on (a piece of the strided
+// table: X mode, fast tier, whole pairs of at least PRHF_TOP3_MIN_POINTS points, profiles staged in LDS) and a workgroup
+// settles its reflection heights one frequency per thread (one round of frequencies that fits the staged arrays); the
+// plan's fields are 16 bits wide.  Tall and chunked slices never do.
+inline bool slice_plans_pairs(const prhf::SegDev& s, bool tall, long long n_freq, long long lds_levels, const Knobs& kn) {
+    return kn.pair_plan != 0 && !tall && s.sp_off > 0 && s.chunks == 1 && s.slots == 0 && s.lean != 0 && s.tier == 1 &&
+           s.mode == PRHF_KMODE_X && s.thread_scan != 0 && kn.no_candidates == 0 && n_freq <= PRHF_BLOCK_THREADS &&
+           n_freq <= lds_levels && s.n_points >= PRHF_TOP3_MIN_POINTS && s.n_points < 65536;
 }
 
 // The stretched grid must not decrease (smooth_nonuniform_grid never does): the top-segment search of the main loop

@@ -37,7 +37,7 @@ extern "C" {
                               *    prhf_trace_gradient_spherical_f64 and prhf_snell_home_f64 joined later without a new
                               *    number: a new symbol changes nothing for a caller of the others (so did
                               *    prhf_gradient_home_f64, prhf_snell_skip_f64, prhf_snell_muf_f64 and
-                              *    prhf_pair_plan_counters) */
+                              *    prhf_pair_plan_counters, prhf_panel_counters) */
 
 /* return codes */
 #define PRHF_OK        0
@@ -134,6 +134,12 @@ int prhf_ctx_set_math(prhf_ctx* ctx, int level);
  *                        bit (1: on a uniform altitude grid the segments of at least 64 points below them do too - one
  *                        strided pass plus one pass over the points around the segment boundaries; a pair with a
  *                        segment too close to X + Y = 1 keeps the sum of before; "strided_top" = 0 switches both off)
+ *   "panel_lower"        0: the segments below the top three are summed as "strided_lower" says, the launch of before this
+ *                        option bit for bit (1: where "strided_lower" applies, the region below the top three segments is
+ *                        cut at every multiple of 128 points and at every segment's first point; a piece of more than 8
+ *                        points is summed from eight nodes at real-valued indices - Gauss-Legendre abscissae, weights
+ *                        that make the rule exact for the discrete sum of polynomials of degree 7 - within 1e-12 of
+ *                        the full sum; a pair with such a piece too close to X + Y = 1 keeps the sum of before)
  *   "pair_plan"          0: every wavefront computes the integers that steer its pair's strided sum itself, the launch of
  *                        before this option bit for bit (1: where "strided_lower" applies and a workgroup settles its
  *                        reflection heights one frequency per thread - at most 512 frequencies, grids of fewer than 65536
@@ -559,6 +565,12 @@ int prhf_gradient_home_counters(prhf_ctx* ctx, uint64_t* counters);
  * room for the plan, or a guess that did not bracket).  Pairs of slices that are not eligible count in neither.
  * Waits for the context's stream. */
 int prhf_pair_plan_counters(prhf_ctx* ctx, uint64_t* counters);
+
+/* Diagnostics of option "panel_lower", summed over every launch since the context was made: counters[0] reflecting pairs
+ * whose segments below the top three took the panel sum, [1] pairs that were eligible for it and kept the sum of before
+ * (a piece too close to X + Y = 1, a region of fewer than 256 points, a guess that did not bracket).  Waits for the
+ * context's stream. */
+int prhf_panel_counters(prhf_ctx* ctx, uint64_t* counters);
 
 /* Diagnostics: workgroups of the fused kernel the runtime expects to keep resident per CU for
  * profiles of n_alt levels (LDS-limited) in arithmetic tier `math`. */

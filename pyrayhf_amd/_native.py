@@ -121,6 +121,7 @@ _PROTOTYPES = {
                                [ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32]),
     "prhf_gradient_home_counters": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
     "prhf_pair_plan_counters": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
+    "prhf_panel_counters": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
     "prhf_occupancy": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
                                       ctypes.POINTER(ctypes.c_int32)]),
     "prhf_sync": (ctypes.c_int, [ctypes.c_void_p]),
@@ -386,6 +387,13 @@ class Context:
         (option ``pair_plan``, include/prhf.h)."""
         buf = (ctypes.c_uint64 * 2)()
         raise_for(self._lib.prhf_pair_plan_counters(self._h, buf))
+        return tuple(int(v) for v in buf)
+
+    def panel_counters(self):
+        """(pairs whose lower segments took the panel sum, eligible pairs that kept the sum of before) since this
+        context was made (option ``panel_lower``, include/prhf.h)."""
+        buf = (ctypes.c_uint64 * 2)()
+        raise_for(self._lib.prhf_panel_counters(self._h, buf))
         return tuple(int(v) for v in buf)
 
     def occupancy(self, n_alt, math):

@@ -165,7 +165,7 @@ struct prhf_ctx {
     double* h_pack_dev = nullptr;   // half, mapped into the device (h_pack_dev), takes a small result straight from the kernel
     unsigned long long* d_words = nullptr;   // 2 words: nanmax|Y| bits, any-not-NaN
     unsigned long long* h_words = nullptr;   // pinned
-    unsigned long long* d_plan_counters = nullptr;   // 2 words, since the context was made (prhf_pair_plan_counters)
+    unsigned long long* d_plan_counters = nullptr;   // 4 words, since the context was made (prhf_pair_plan_counters, prhf_panel_counters)
     bool status_pending = false;
     uint64_t grad_home_counters[PRHF_GRAD_HOME_COUNTERS] = {};   // of the last prhf_gradient_home_f64 (prhf_gradient_home_counters)
 };
@@ -601,6 +601,7 @@ int run(prhf_ctx* c, const double* freq, int64_t n_freq, const double* den, cons
             }
             s.sp_off = pieces.sp_off[p];
             s.strided_lower = kn.strided_lower != 0;
+            s.panel_lower = s.strided_lower && kn.panel_lower != 0;
             s.pair_plan = slice_plans_pairs(s, tall, n_freq, lds_levels, kn) ? 1 : 0;
             any_plan = any_plan || s.pair_plan != 0;
         }
@@ -1065,8 +1066,8 @@ int prhf_ctx_create(int device, prhf_ctx** out) {
         (e = hipMalloc(reinterpret_cast<void**>(&c->d_words), 2 * sizeof(unsigned long long))) != hipSuccess ||
         (e = hipHostMalloc(reinterpret_cast<void**>(&c->h_words), 2 * sizeof(unsigned long long),
                            hipHostMallocDefault)) != hipSuccess ||
-        (e = hipMalloc(reinterpret_cast<void**>(&c->d_plan_counters), 2 * sizeof(unsigned long long))) != hipSuccess ||
-        (e = hipMemset(c->d_plan_counters, 0, 2 * sizeof(unsigned long long))) != hipSuccess ||
+        (e = hipMalloc(reinterpret_cast<void**>(&c->d_plan_counters), 4 * sizeof(unsigned long long))) != hipSuccess ||
+        (e = hipMemset(c->d_plan_counters, 0, 4 * sizeof(unsigned long long))) != hipSuccess ||
         (e = prhf::configure_kernels(prhf::lds_bytes_for(kMaxAlt))) != hipSuccess) {
         prhf_ctx_destroy(c);
         return fail(PRHF_EHIP, "context setup failed: %s", hipGetErrorString(e));
@@ -2323,6 +2324,17 @@ int prhf_pair_plan_counters(prhf_ctx* c, uint64_t* counters) {
     unsigned long long w[2] = {0, 0};
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipMemcpy(w, c->d_plan_counters, sizeof w, hipMemcpyDeviceToHost));
+    counters[0] = w[0];
+    counters[1] = w[1];
+    return PRHF_OK;
+}
+
+int prhf_panel_counters(prhf_ctx* c, uint64_t* counters) {
+    if (!c || !counters) return fail(PRHF_EINVAL, "null pointer");
+    DeviceScope device_scope_(c->device);
+    unsigned long long w[2] = {0, 0};
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpy(w, c->d_plan_counters + 2, sizeof w, hipMemcpyDeviceToHost));
     counters[0] = w[0];
     counters[1] = w[1];
     return PRHF_OK;

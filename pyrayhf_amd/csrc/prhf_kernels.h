@@ -60,6 +60,12 @@
 #ifndef PRHF_STRIDED_MIN_SEGMENT
 #define PRHF_STRIDED_MIN_SEGMENT 64 // segments below the top three take the strided sum while they hold this many points
 #endif
+#ifndef PRHF_PANEL_BLOCK
+#define PRHF_PANEL_BLOCK 128        // the panel sum below the top three segments cuts its region at every multiple of this (64 or 128)
+#endif
+#ifndef PRHF_PANEL_MIN_SEGMENT
+#define PRHF_PANEL_MIN_SEGMENT 8    // ... and begins at the lowest segment that holds this many points
+#endif
 #ifndef PRHF_MIN_WAVES_PER_SIMD
 #define PRHF_MIN_WAVES_PER_SIMD 4   // two 8-wave workgroups per CU: caps VGPRs at 128
 #endif
@@ -102,6 +108,8 @@ struct SegDev {
                                      // (launch_grid_strided; the main loop's strided sum); 0: none
     int strided_lower;               // with sp_off > 0: the segments below the top three take the strided sum too
                                      // (option strided_lower)
+    int panel_lower;                 // with strided_lower: those segments are summed from eight nodes per piece where the
+                                     // pair's guard allows it (option panel_lower)
     int pair_plan;                   // with sp_off > 0: the workgroup plans its pairs' sums one pair per thread (option
                                      // pair_plan; plan_pairs in prhf_kernels.hip)
     int thread_scan;                 // X mode: reflection heights settled one frequency per thread while the candidate
@@ -145,7 +153,8 @@ struct KArgs {
     // whose bottomsides all fit LDS (launch_peak_levels) - the highest peak index of the launch + 1
     long long lds_levels;
     // The planning pass (SegDev::pair_plan): [0] pairs that ran from a plan, [1] eligible pairs that planned themselves,
-    // added to once per workgroup and block; plan_cap > 0 caps the records per workgroup (tests)
+    // added to once per workgroup and block; plan_cap > 0 caps the records per workgroup (tests).  [2] pairs whose lower
+    // segments took the panel sum, [3] eligible pairs that fell back (SegDev::panel_lower), added to once per wave and block
     unsigned long long* plan_counters;
     int plan_cap;
     SegDev seg[PRHF_MAX_SEGMENTS];

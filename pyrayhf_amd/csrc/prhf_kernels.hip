@@ -161,6 +161,18 @@ __device__ __forceinline__ double uniform(double v) {
 __device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
 // bit of the main loop's sp_off argument: the segments below the top three take the strided sum too (SegDev::strided_lower)
 constexpr int kStridedLowerBit = 1 << 30;
+// ... and bit 29: where they do, the panel sum comes first (SegDev::panel_lower)
+constexpr int kPanelLowerBit = 1 << 29;
+// what the main loop reports about the panel sum in the bits above kPanelStateShift of LeanResult::first (a grid point's
+// index stays below 2^27): 1 the pair's lower segments took it, 2 the pair was eligible and kept the sum of before
+constexpr int kPanelStateShift = 28;
+#define PRHF_PANEL_NODES_DECL [[maybe_unused]] static __device__ const double kPanelNodes[8]   // (the table's own abscissae: the pairs below hold them as offsets)
+#define PRHF_PANEL_PAIRS_DECL static __device__ __attribute__((aligned(16))) const double kPanelPairs[(PRHF_PANEL_N_MAX + 1) * 16]
+#include "prhf_panel_table.inc"
+static_assert(PRHF_PANEL_BLOCK == 64 || PRHF_PANEL_BLOCK == 128, "the weight table ends at 128 points");
+static_assert(PRHF_PANEL_BLOCK <= PRHF_PANEL_N_MAX, "a piece holds at most one block");
+static_assert(PRHF_PANEL_MIN_SEGMENT >= 1 && (PRHF_PANEL_MIN_SEGMENT & (PRHF_PANEL_MIN_SEGMENT - 1)) == 0,
+              "a power of two: the closed form squares its way up");
 
 // 1/sqrt(x) to ~0.6 ulp: v_rsq_f64 is good to 2^-24 on gfx950 (tools/probe_math.hip), one
 // third-order step cubes that.  NaN for x < 0, +inf for x == 0; no range fix-ups (arguments
@@ -1132,7 +1144,7 @@ __device__ __forceinline__ double lean_step_top(double2 g, const TopSegment& t, 
 // loop keeps its dozen scalars in SGPRs whatever the caller looks like; the call costs ~100 cycles per pair.
 struct LeanResult {
     double acc;     // span * sum of mu' * weight, per lane
-    int first;      // first grid point not consumed
+    int first;      // first grid point not consumed; above bit kPanelStateShift: what became of the panel sum
 };
 
 // CHECK (default O-mode arithmetic): stop in front of the first point with 1 - X <= well_conditioned; the
@@ -1197,7 +1209,7 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
     // and everything below them takes the indexed steps.
     constexpr int kTopSegments = 3;
     static_assert(kTopSegments == 3, "the run loop below selects among three");
-    int seg_begin[kTopSegments] = {0, 0, 0}, seg_end[kTopSegments] = {0, 0, 0}, seg_j[kTopSegments] = {0, 0, 0};   // [0]: the top segment
+    int seg_j[kTopSegments] = {0, 0, 0};               // [0]: the top segment
     int seg_lo[kTopSegments] = {0, 0, 0};              // the segment's first grid point itself (strided sum)
     int n_seg = 0;
     TopSegment top;
@@ -1223,16 +1235,12 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
         const unsigned pw0 = (unsigned)uniform((int)rec[0]), pw1 = (unsigned)uniform((int)rec[1]);
         n_seg = uniform((int)(rec[2] >> 30));
         const int j_top = (int)(pw1 >> 16);
-        int run_end = whole_end;
 #pragma unroll
         for (int sidx = 0; sidx < kTopSegments; ++sidx) {
             if (sidx >= n_seg) break;
             const int lo = (int)(sidx == 0 ? pw0 & 0xffffu : (sidx == 1 ? pw0 >> 16 : pw1 & 0xffffu));
-            seg_begin[sidx] = first + ((lo - first + 63) & ~63);
-            seg_end[sidx] = run_end;
             seg_j[sidx] = j_top - sidx;
             seg_lo[sidx] = lo;
-            run_end = first + ((lo - first) & ~63);
         }
     } else if (TOP && end - first >= PRHF_TOP_MIN_POINTS) {
         const int i_last = (last_special >= 0 ? last_special : end - 1);
@@ -1296,8 +1304,6 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
             if (!found) break;
             const int aligned = first + ((lo - first + 63) & ~63);
             if (aligned + 128 > run_end) break;        // not worth a loop of its own (nor are the sparser ones below)
-            seg_begin[sidx] = aligned;
-            seg_end[sidx] = run_end;
             seg_j[sidx] = j;
             seg_lo[sidx] = lo;
             n_seg = sidx + 1;
@@ -1411,7 +1417,10 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
     double sc1 = 0.0;
     sp_off = uniform(sp_off);
     const bool lower_req = (sp_off & kStridedLowerBit) != 0;
-    sp_off &= ~kStridedLowerBit;
+    const bool panel_req = (sp_off & kPanelLowerBit) != 0;
+    sp_off &= ~(kStridedLowerBit | kPanelLowerBit);
+    int panel_state = 0;                               // (waits in a vector register, where the result travels anyway)
+    asm volatile("" : "+v"(panel_state));
     if (STRIDED && sp_off > 0 && n_seg > 0 && first == 0 && last_special >= 0 && end >= PRHF_TOP3_MIN_POINTS) {
         const u32x4 vh = __builtin_amdgcn_raw_buffer_load_b128(rsrc, 0, sp_off * (int)sizeof(double2), 0);
         double2 gh;
@@ -1517,7 +1526,147 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
             return fmin(fmax(__builtin_fma(-ln_a, n1 * 0.1, n1), -1e9), 1e9);
         };
         auto x_of = [&](int j) { return index_of((double)j * rkj); };
-        if (lower) {
+        // The panel sum (option panel_lower): the region [S_P, E_P), multiples of PRHF_PANEL_BLOCK, from the
+        // lowest segment that holds PRHF_PANEL_MIN_SEGMENT points up to where the top three segments' own loops begin, is
+        // cut at every multiple of the block and at every segment's first point.  A piece [p, p + n) lies in one segment,
+        // where the summand is an analytic function of the real-valued index x: m(x) = 1 + c0 - e(x), w = c1 e(x),
+        // e(x) = (1 - m_i + c0) exp(-10 (x - i) / (N - 1)) from the table entry i next to x.  Eight lanes sum a piece: its
+        // own points if it holds at most eight, else the Gauss-Legendre abscissae of order 8 over [p, p + n - 1] with the
+        // weights of kPanelPairs, which make the rule the discrete sum of every polynomial of degree 7.  The nodes go
+        // through the indexed step like any point.  One lane per piece makes the list, 63 pieces at a time: the first
+        // n_blk pieces begin at a multiple of the block and end at the next one or at the next segment's first point, the
+        // others begin at a segment's first point inside the region - found like the top segments' by the closed form and
+        // four table entries around it, with a grid point's segment the indexed step's own (int)(m kj) - and end at the
+        // next segment's (the next lane's) or at the next multiple.  Guard, per piece of more than eight points: the
+        // index where the segment's continuation reaches X + Y = 1 lies at least max(32, 4 n) from the piece's centre,
+        // and 1 - X - Y >= 1e-6 at both levels of the segment; one piece that fails, or one guess that does not bracket,
+        // leaves the whole pair to the sums below.  Everything here is a function of the pair alone.
+        if (lower && panel_req && end < 65536) {
+            bool panel_ok = false;
+            int S_P = 0;
+            constexpr int B = PRHF_PANEL_BLOCK, kLogB = B == 128 ? 7 : 6;
+            const double c0 = 1.0 / 22025.465794806718;
+            panel_state = 2;
+            asm volatile("" : "+v"(panel_state));
+            // segment j holds at least M points where ln(a_j / (a_j - 1 / kj)) >= 10 M / (N - 1), a_j = 1 - j / kj + c0:
+            // j >= kj (1 + c0) - 1 / (1 - q^M), q = exp(-10 / (N - 1)) = 1 - c1
+            double qm = 1.0 - sc1;
+            for (int s = 1; s < PRHF_PANEL_MIN_SEGMENT; s *= 2) qm = qm * qm;
+            const int j_min = uniform((int)fmin(fmax(__builtin_ceil(__builtin_fma(kj, 1.0 + c0, -1.0 / (1.0 - qm))), 0.0), 1e6));
+            // the first grid point of segment j (per lane); ok: the four entries around the guess bracket it
+            auto first_point = [&](int j, bool& ok) {
+                const int guess = stretch_guess((double)j * rkj, n1);
+                const int base = min(max(guess, 0) + 3, i_last_s) - 3;
+                typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+                bool hit[4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rsrc, (unsigned)(base + q) * (unsigned)sizeof(double2), 0, 0);
+                    double mq;
+                    __builtin_memcpy(&mq, &v, sizeof mq);
+                    hit[q] = (int)(mq * kj) >= j;
+                }
+                ok = j <= 0 || (guess == base && !hit[0] && hit[3]);
+                return j <= 0 ? 0 : base + (hit[1] ? 1 : (hit[2] ? 2 : 3));
+            };
+            bool ok_min;
+            const int lo_min = uniform(first_point(j_min, ok_min));
+            S_P = (lo_min + B - 1) & ~(B - 1);
+            auto region_end = [&]() { return ((seg_lo[2] + 4) & ~63) & ~(B - 1); };
+            if (__ballot(!ok_min) == 0ull && j_min < seg_j[2] && region_end() - S_P >= 256) {
+                const int E_P = region_end();
+                // the segments of the region's first and last point
+                const u32x4 vs = __builtin_amdgcn_raw_buffer_load_b128(rsrc, 0, S_P * (int)sizeof(double2), 0);
+                const u32x4 ve = __builtin_amdgcn_raw_buffer_load_b128(rsrc, 0, (E_P - 1) * (int)sizeof(double2), 0);
+                double2 gs, ge;
+                __builtin_memcpy(&gs, &vs, sizeof gs);
+                __builtin_memcpy(&ge, &ve, sizeof ge);
+                const int j_s = uniform((int)(gs.x * kj)), j_e = uniform((int)(ge.x * kj));
+                const int n_blk = (E_P - S_P) >> kLogB, total = n_blk + (j_e - j_s);
+                const int l7 = lane & 7;
+                const double s10 = uniform(-10.0 / n1);
+                const double r2 = 1.4142135623730951;
+                bool fail = false;
+#pragma unroll 1
+                for (int s0 = 0; s0 < total && !fail; s0 += 63) {
+                    // lane l: piece s0 + l (lane 63 only finds the first point that ends lane 62's piece)
+                    const int s = s0 + lane;
+                    const bool live = s < total, is_blk = s < n_blk;
+                    const int bs = S_P + (min(s, n_blk - 1) << kLogB);
+                    typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+                    const u32x2 vb = __builtin_amdgcn_raw_buffer_load_b64(rsrc, (unsigned)bs * (unsigned)sizeof(double2), 0, 0);
+                    double mb;
+                    __builtin_memcpy(&mb, &vb, sizeof mb);
+                    const int j_a = (int)(mb * kj);
+                    const int jq = is_blk ? j_a + 1 : (live ? j_s + 1 + (s - n_blk) : j_s + 1);
+                    bool ok;
+                    const int fq = first_point(jq, ok);
+                    const int F = live ? fq : (1 << 20);
+                    const int F_next = __shfl_down(F, 1);
+                    const int p = is_blk ? bs : F;
+                    const int e = is_blk ? min(bs + B, F) : min(F_next, (F & ~(B - 1)) + B);
+                    int n = live && lane < 63 && (is_blk || (F & (B - 1)) != 0) ? max(e - p, 0) : 0;
+                    const int j_g = is_blk ? j_a : jq;
+                    // guard, from the segment's node: 1 - X - Y = gap - sl m on its continuation (strided_run)
+                    const unsigned nd = __umul24((unsigned)j_g, (unsigned)sizeof(Node));
+                    const double o = nodes_v.f64(nd + 8), den = nodes_v.f64(nd + 16), sden = nodes_v.f64(nd + 24),
+                                 bf = nodes_v.f64(nd + 32), sb = nodes_v.f64(nd + 40);
+                    const double sl = cX * (sden * span) + r2 * (cYs * (sb * span));
+                    const double gap = 1.0 - cX * (den + sden * o) - r2 * (cYs * (bf + sb * o));
+                    const double m_hi = (double)(j_g + 1) * rkj;
+                    const double g_lo = gap - sl * ((double)j_g * rkj), g_hi = gap - sl * m_hi;
+                    const bool big = n > 8;
+                    bool clear = g_lo >= 1e-6 && g_hi >= 1e-6;
+                    // (nearly always the continuation reaches X + Y = 1 far above the segment: the index grows by at least
+                    //  (N - 1) / (10 a_j+1) per unit of m up there, so g_hi / sl of m is more than 4 B + 2 indices - no
+                    //  logarithm, no division)
+                    const bool far = sl > 0.0 && (n1 * 0.1) * g_hi >= (double)(4 * B + 2) * (sl * ((1.0 - m_hi) + c0));
+                    if (__any(big && clear && !far)) {
+                        if (__builtin_fabs(sl) > 1e-300) {
+                            const double i_sing = index_of(gap / sl);
+                            const double c = (double)p + 0.5 * (double)(n - 1);
+                            clear = clear && __builtin_fabs(i_sing - c) >= fmax(32.0, 4.0 * (double)n);
+                        }
+                    }
+                    fail = __ballot((live && !ok) || (big && !clear)) != 0ull;
+                    if (fail) break;
+                    const unsigned word = n > 0 ? (unsigned)p | ((unsigned)n << 16) : 0u;
+                    const int n_live = min(63, total - s0);
+                    for (int it = 0; it * 8 < n_live; ++it) {
+                        // eight pieces of eight lanes
+                        const unsigned w = (unsigned)__builtin_amdgcn_ds_bpermute(((lane >> 3) + it * 8) << 2, (int)word);
+                        const int pp = (int)(w & 0xffffu), nn = (int)(w >> 16);
+                        // the node's offset from the piece's first point, its weight
+                        const double2 ow = reinterpret_cast<const double2*>(kPanelPairs)[nn * 8 + l7];
+                        const double xk = (double)pp + ow.x;
+                        const double xr = __builtin_rint(xk);
+                        const u32x2 vm = __builtin_amdgcn_raw_buffer_load_b64(rsrc, (unsigned)(int)xr * (unsigned)sizeof(double2), 0, 0);
+                        double m0;
+                        __builtin_memcpy(&m0, &vm, sizeof m0);
+                        const double t = (xk - xr) * s10;             // |t| <= 5 / (N - 1): five terms of the exponential
+                        const double ex = 1.0 + t * (1.0 + t * (0.5 + t * (1.0 / 6.0 + t * (1.0 / 24.0))));
+                        const double ek = ((1.0 - m0) + c0) * ex;
+                        double2 gm;
+                        gm.x = (1.0 + c0) - ek;
+                        gm.y = ow.y * (sc1 * ek);
+                        accm = lean_step<MODE, false, POLY, HINT, G>(gm, span, a0v, kj, cX, hcY2, accm, wc, viol, nodes_v, cur);
+                    }
+                }
+                panel_ok = !fail;
+                if (!panel_ok) accm = 0.0;                 // (nothing else has been summed yet: first == 0)
+                g0 = grid_at(first);                       // (loaded again: four vector registers fewer across this block)
+            }
+            // (the loop function is at the end of its scalar registers: the region travels on in the lower block's own
+            //  variables, n_R < 0 says that the panel sum has taken it)
+            if (panel_ok) {
+                panel_state = 1;
+                asm volatile("" : "+v"(panel_state));
+                S_R = S_P;
+                E_R = region_end();
+                n_R = -1;
+            }
+        }
+        if (lower && n_R >= 0) {
             constexpr int kGuard = 256;
             constexpr double kTau = 1e-6;
             // lane l: the segment s_l = j_b0 - 1 - l between boundaries l + 1 (below) and l (above)
@@ -1571,8 +1720,9 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
         if (lower) {
             const int count = (E_R - S_R) >> 3;        // strided points S_R, S_R + 8, .. E_R - 8
             const int j_whole = (S_R >> 3) + (count & ~63), rest = count & 63;
+            const int n_pass = n_R < 0 ? 1 : 2;        // (the panel sum has taken [S_R, E_R): one by one up to S_R, no more)
 #pragma unroll 1
-            for (int pass = 0; pass < 2; ++pass) {     // (one copy of the loop for both)
+            for (int pass = 0; pass < n_pass; ++pass) { // (one copy of the loop for all)
                 if (pass == 1) {
                     tab_off = (sp_off + 1) * (int)sizeof(double2);
                     first = S_R >> 3;
@@ -1597,7 +1747,7 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
             const double c16 = around(p, 19), c24 = around(p, 27);
             const double c_ends = p < 3 ? -mag(3 - p) : (p == 3 ? -3.5 : (p < 7 ? mag(p - 3) : (p < 18 ? around(p - 7, 64) : 0.0)));
             const double c0 = 1.0 / 22025.465794806718;
-            const int n_items = 32 * n_R + rest;
+            const int n_items = n_R < 0 ? 0 : 32 * n_R + rest;
             for (int t0 = 0; t0 < n_items; t0 += 64) {
                 const int grp = (t0 >> 5) + (lane >> 5);
                 int idx = S_R;
@@ -1628,9 +1778,12 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
         // (one copy of the two loops: the run's bounds are picked with scalar selects, not by unrolling)
 #pragma unroll 1
         for (int sidx = n_seg - 1; sidx >= 0 && !(CHECK && viol); --sidx) {
-            const int begin_s = sidx == 0 ? seg_begin[0] : (sidx == 1 ? seg_begin[1] : seg_begin[2]);
-            const int end_s = sidx == 0 ? seg_end[0] : (sidx == 1 ? seg_end[1] : seg_end[2]);
-            const int j_s = sidx == 0 ? seg_j[0] : (sidx == 1 ? seg_j[1] : seg_j[2]);
+            // (the runs' bounds from the segments' first points, as the search set them - a whole pair begins at grid point
+            //  0: six scalar registers fewer across the blocks above)
+            const int lo_b = sidx == 0 ? seg_lo[0] : (sidx == 1 ? seg_lo[1] : seg_lo[2]);
+            const int begin_s = (lo_b + 63) & ~63;
+            const int end_s = sidx == 0 ? whole_end : ((sidx == 1 ? seg_lo[0] : seg_lo[1]) & ~63);
+            const int j_s = seg_j[0] - sidx;
             run_indexed(begin_s);
             if (!(CHECK && viol)) {
                 top = top_segment(nodes_v, j_s, span, cYs);
@@ -1674,7 +1827,7 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
     }
     LeanResult r;
     r.acc = accm * span;                               // :415: dh = (m_i+1 - m_i) * span
-    r.first = first;
+    r.first = first | (panel_state << kPanelStateShift);
     return r;
 }
 
@@ -1698,7 +1851,7 @@ __device__ __forceinline__ double integrate_chunk(const Node* __restrict__ nodes
                                                   const double2* __restrict__ pairs, int n_points, int i0,
                                                   int i1, double f_hz, double f2, double cX, double cY2,
                                                   double h_refl, int lane, double well_conditioned, int sp_off,
-                                                  unsigned plan_lds) {
+                                                  unsigned plan_lds, int& panel_state) {
     const int K = info.K;
     const double a0 = info.a0;
     const double span = uniform(h_refl - a0);      // :413 (critical_height - aalt[0])
@@ -1770,8 +1923,9 @@ __device__ __forceinline__ double integrate_chunk(const Node* __restrict__ nodes
 #endif
             } else {
                 acc = r.acc;
-                first = uniform(r.first);
+                first = uniform(r.first) & ((1 << kPanelStateShift) - 1);
             }
+            panel_state = uniform(r.first) >> kPanelStateShift;
         }
     }
     // Generic loop over [first, i1).  Its wave-iterations are aligned to the END of the range - a short first
@@ -2272,7 +2426,8 @@ __device__ __forceinline__ void run_items(const KArgs& a, const SegDev& sg, cons
     // the strided table's piece of this slice's grid, in entries from `pairs`; 0: none
     // (bit 30: the segments below the top three take the strided sum too - an offset stays below 2^27 entries)
     const int sp_off = (pairs && sg.sp_off > 0)
-                           ? uniform((int)(sg.sp_off - sg.mult_off) | (sg.strided_lower ? kStridedLowerBit : 0)) : 0;
+                           ? uniform((int)(sg.sp_off - sg.mult_off) | (sg.strided_lower ? kStridedLowerBit : 0) |
+                                     (sg.strided_lower && sg.panel_lower ? kPanelLowerBit : 0)) : 0;
     const long long pair_base = prof_local * F;
     const int first_item = block_in_prof * W, round_items = blocks_per_prof * W;
     // Few pairs on a long grid (one profile, the reference's own call; SegDev::slots > 0): a pair is cut into C <= S
@@ -2294,6 +2449,8 @@ __device__ __forceinline__ void run_items(const KArgs& a, const SegDev& sg, cons
     double* part = red + 10 * W + 8;                   // (behind the kept scalars; rows 0 .. 9 may still be read by a
     if (local && lane == 0) part[wave] = 0.0;          //  wave that left stage_profile early)
     int pulled = 0;                                    // how many items this workgroup had pulled before the current one
+    int panel_cnt = 0;                                 // pairs of this wave whose lower segments took the panel sum (low half:
+                                                       // a wave pulls far fewer than 65536 items of a block) / fell back (high)
     auto next_item = [&]() {
         const int u = uniform(atomicAdd(item_next, 1)) >> 6;
         pulled = u;
@@ -2316,6 +2473,7 @@ __device__ __forceinline__ void run_items(const KArgs& a, const SegDev& sg, cons
         }
         double result = qnan();
         bool reflects = false;
+        int panel = 0;                             // what the main loop reports about the panel sum (kPanelStateShift)
         // the pair's plan, if the workgroup made one (plan_pairs): records are numbered in the order the items are pulled
         const unsigned plan_lds = pulled < room.total ? plan_slot(room, pulled) : 0u;
         if (!info.bad) {
@@ -2332,14 +2490,17 @@ __device__ __forceinline__ void run_items(const KArgs& a, const SegDev& sg, cons
                 const int i1 = min(sg.n_points, i0 + sg.chunk_len);
                 if (info.unmag)
                     result = integrate_chunk<MODE, TIER, true, G>(nodes, hint, info, mult, pairs, sg.n_points, i0, i1,
-                                                               pf.f_hz, pf.f2, pf.cX, pf.cY2, h, lane, wc, sp_off, plan_lds);
+                                                               pf.f_hz, pf.f2, pf.cX, pf.cY2, h, lane, wc, sp_off, plan_lds, panel);
                 else
                     result = integrate_chunk<MODE, TIER, false, G>(nodes, hint, info, mult, pairs, sg.n_points, i0,
-                                                                i1, pf.f_hz, pf.f2, pf.cX, pf.cY2, h, lane, wc, sp_off, plan_lds);
+                                                                i1, pf.f_hz, pf.f2, pf.cX, pf.cY2, h, lane, wc, sp_off, plan_lds, panel);
             } else if (info.K == 1) {
                 result = (c == C - 1) ? one_level_term<MODE, TIER>(nodes, info, pf, sg.well_conditioned) : 0.0;
                 reflects = true;
             }
+        }
+        if constexpr (MODE == PRHF_KMODE_X && TIER == 1 && !G) {
+            panel_cnt += panel == 1 ? 1 : (panel == 2 ? 0x10000 : 0);
         }
         if (lane == 0) {
             if (local) {
@@ -2351,6 +2512,12 @@ __device__ __forceinline__ void run_items(const KArgs& a, const SegDev& sg, cons
             } else {
                 a.partial[sg.partial_off + (pair_base + f) * C + c] = reflects ? result : qnan();
             }
+        }
+    }
+    if constexpr (MODE == PRHF_KMODE_X && TIER == 1 && !G) {
+        if (lane == 0 && a.plan_counters) {
+            if (panel_cnt & 0xffff) atomicAdd(&a.plan_counters[2], (unsigned long long)(panel_cnt & 0xffff));
+            if (panel_cnt >> 16) atomicAdd(&a.plan_counters[3], (unsigned long long)(panel_cnt >> 16));
         }
     }
     if (local) {

@@ -78,6 +78,10 @@ struct Knobs {
                                        // PRHF_STRIDED_MIN_SEGMENT points below those three as well, in one strided pass
                                        // and one pass over the segment boundaries (0: the launch of strided_top alone,
                                        // bit for bit; strided_top = 0 switches both off)
+    double panel_lower = 1;            // ... and where strided_lower applies, the region below the top three segments is cut
+                                       // into pieces of at most PRHF_PANEL_BLOCK points inside one segment, each summed from
+                                       // eight nodes at real-valued indices (a pair with a piece too close to
+                                       // X + Y = 1 keeps strided_lower's sum; 0: the launch of before, bit for bit)
     double pair_plan = 1;              // ... and the integers that steer such a pair's sum - first points of the top three
                                        // segments, the strided stretch of each - are computed once per pair, by one thread
                                        // while the workgroup makes its candidate list, instead of by all 64 lanes of the
@@ -118,6 +122,7 @@ const KnobName kKnobNames[] = {
     {"tall_lean", &Knobs::tall_lean, 0, 1},
     {"strided_top", &Knobs::strided_top, 0, 1},
     {"strided_lower", &Knobs::strided_lower, 0, 1},
+    {"panel_lower", &Knobs::panel_lower, 0, 1},
     {"pair_plan", &Knobs::pair_plan, 0, 1},
     {"pair_plan_cap", &Knobs::pair_plan_cap, 0, 1024},
 };

@@ -37,7 +37,8 @@ extern "C" {
                               *    prhf_trace_gradient_spherical_f64 and prhf_snell_home_f64 joined later without a new
                               *    number: a new symbol changes nothing for a caller of the others (so did
                               *    prhf_gradient_home_f64, prhf_snell_skip_f64, prhf_snell_muf_f64 and
-                              *    prhf_pair_plan_counters, prhf_panel_counters) */
+                              *    prhf_pair_plan_counters, prhf_panel_counters, and prhf_field_build_f64,
+                              *    prhf_gradient_skip_f64, prhf_gradient_muf_f64, prhf_gradient_skip_counters) */
 
 /* return codes */
 #define PRHF_OK        0
@@ -559,6 +560,95 @@ int prhf_gradient_home_f64(prhf_ctx* ctx, int32_t geometry, const double* record
  * refine lanes traced, [2] ray slots (64 per trip of a refine wavefront's loop), [3] refine wavefronts with work.
  * Lane utilisation of the refinement = [1] / [2].  No device call. */
 int prhf_gradient_home_counters(prhf_ctx* ctx, uint64_t* counters);
+
+/*
+ * Fields of many frequencies built on the device: the records (n_freq, n0, n1, 4) of
+ * prhf_field_pack_f64 for the frequencies freq_hz (n_freq) of ONE 2-D ionosphere den, bmag, bpsi (n0, n1) - electron
+ * density [m^-3], |B| [T], angle [deg] - with no host round trip inside the call.  Per node and frequency, in float64
+ * without contraction, each operation rounded once: f_N = sqrt(den) c_p, X = (f_N f_N) / (f f), Y = (g_p |B|) / f, then mu
+ * and mu' in the faithful tier's arithmetic, or the isotropic formulas when that frequency's field is isotropic:
+ * nanmax|Y| < 1e-12 (an all-NaN Y counts as magnetised), prhf_mu_mup_f64's decision on that frequency's Y array, taken
+ * here from nanmax|B|, found once per call.  f squared is the PRODUCT f f - what the reference's find_X gives for an
+ * array of frequencies; its scalar f ** 2 (libm pow) differs in the last bit for about one frequency in a thousand.
+ * Then np.gradient as prhf_field_pack_f64 computes it (edge_order 1 or 2).  A negative density gives NaN as sqrt does.
+ * den, bmag, bpsi, freq_hz and, when given, mu_out and mup_out (n_freq, n0, n1; both or neither) are host memory, or
+ * device memory with PRHF_FLAG_DEVICE_PTRS; axis0 and axis1 are host memory; records is device memory.
+ * PRHF_EINVAL for a null context (before anything else), a null array, a bad mode, edge_order, shape or axis;
+ * PRHF_ENEGDEN for a negative density in a host array.  Synchronous.
+ */
+int prhf_field_build_f64(prhf_ctx* ctx, const double* den, const double* bmag, const double* bpsi, int64_t n0, int64_t n1,
+                         const double* axis0, const double* axis1, const double* freq_hz, int64_t n_freq, int32_t mode,
+                         int32_t edge_order, double* records, double* mu_out, double* mup_out, uint32_t flags);
+
+/*
+ * Skip distance through a horizontally varying mu: the least ground_range_km over the elevations of a transmitter's
+ * rays, for the gradient tracers of both geometries.  No counterpart in the reference; DESIGN.md section 4.11 carries the
+ * rule of section 4.10 (prhf_snell_skip_f64) over unchanged.  geometry, records .. axis1, the groups (field, launch
+ * point), the controls s_max_km .. renormalize_every and the fills are prhf_gradient_home_f64's.  scan_elevation_deg
+ * holds n_scan >= 1 strictly increasing elevations.
+ *   Scan: D_i = ground_range_km of the group's ray at scan node i (the landing coordinate: x, or earth_radius_km * phi;
+ * finite only for status ground) - the bits the tracer gives.  i* = the first index that attains the minimum over the
+ * finite D_i.  No finite D_i: status -1, a NaN row, scan_index -1, n_evals 0.  i* at either end of the scan or beside a
+ * node whose D is not finite: status 1, the node as it stands, no further ray.  Otherwise, in float64 without contraction,
+ * with a = e_(i*-1), b = e_i*, c = e_(i*+1), D_b = D_i*, n = 0, g = 0.3819660112501051, at most max_iter + 1 times:
+ *     c - a <= elev_tol_deg: status 0, stop;
+ *     right = (c - b) >= (b - a); x = right ? b + g * (c - b) : b - g * (b - a);
+ *     unless a < x < c and x != b: status 0, stop (the doubles are exhausted);
+ *     n >= max_iter (1 .. 128): status 3, stop;
+ *     D = ground_range_km of the group's ray at x; n = n + 1; D not finite: status 2, stop;
+ *     D < D_b: (right ? a : c) = b, b = x, D_b = D; else (right ? c : a) = x.
+ * There is no early stop: n_evals = n is part of the result.
+ *   out is (n_groups, 18): skip_km (D_b), elevation_deg (b), status, scan_index (i*), bracket_deg (c - a; NaN for status
+ * 1), n_evals, then the tracer's twelve outputs for the ray at elevation_deg, bit-identical to what the tracer returns
+ * for that elevation, field, launch point and controls.  For a scan that looks forward the skip distance is skip_km -
+ * x0_km.  D(e) of these tracers carries the step controller's sawtooth (section 4.9): skip_km is robust against it, the
+ * elevation of a flat minimum is not.  No result depends on scheduling.
+ * Group and scan arrays and out are host memory, or device memory with PRHF_FLAG_DEVICE_PTRS.  PRHF_EINVAL for a null
+ * context (before anything else), a control outside its range, a host scan grid that does not increase strictly, an
+ * elev_tol_deg that is negative or not finite, an earth_radius_km that is not positive and finite (geometry 1), and a
+ * group_field out of range - checked on the host for host buffers, by the kernels for device-resident arrays (those
+ * groups get NaN rows, no memory outside the records is read, and the error is reported at the synchronisation).
+ * Synchronous.
+ */
+int prhf_gradient_skip_f64(prhf_ctx* ctx, int32_t geometry, const double* records, int64_t n_fields, int64_t n0,
+                           int64_t n1, const double* axis0, const double* axis1, const int64_t* group_field,
+                           const double* group_x0_km, const double* group_z0_km, int64_t n_groups,
+                           const double* scan_elevation_deg, int64_t n_scan, double earth_radius_km, double s_max_km,
+                           double rtol, double atol, double max_step_km, double z_ground_km, double top, double left,
+                           double right, int32_t renormalize_every, double fill_n, double fill_grad, double fill_mup,
+                           double elev_tol_deg, int32_t max_iter, double* out, uint32_t flags);
+
+/*
+ * MUF of a link through a tilted ionosphere: link l is (link_x0_km[l], link_z0_km[l], link_target_km[l]) over the one
+ * ionosphere den, bmag, bpsi (n0, n1) on axis0, axis1 (prhf_field_build_f64's inputs; mode, edge_order likewise).
+ * S(f) = skip_km of prhf_gradient_skip_f64 on prhf_field_build_f64's field at f (+inf at status -1).  Semantics,
+ * statuses and the bisection are prhf_snell_muf_f64's: a NaN target: status -1; S(f_lo_hz) > t:
+ * 2; S(f_hi_hz) <= t: 1 with muf_hz = f_hi_hz; else lo = f_lo_hz, hi = f_hi_hz and n_bisect (1 .. 64) times m = lo + 0.5 *
+ * (hi - lo), a trip whose m is not strictly inside (lo, hi) changes nothing, S(m) <= t ? lo = m : hi = m: status 0 with
+ * S(muf_hz = lo) <= t < S(f_above_hz = hi).
+ *   out is (n_links, 21): muf_hz, f_above_hz, status, then the 18 values prhf_gradient_skip_f64 gives on
+ * prhf_field_build_f64's field at muf_hz, bit for bit (NaN for status -1 and 2; f_above_hz is NaN for status 1).
+ * One synchronisation at the end; the call is latency-bound: 3 + n_bisect dependent rounds of seven short kernels.
+ * Scratch is 48 * n0 * n1 bytes per link (mu, mu' and the records of the link's field): PRHF_ENOMEM when it cannot be
+ * allocated - search in batches of links; no result depends on the batching.
+ * The ionosphere, the link and scan arrays and out are host memory, or device memory with PRHF_FLAG_DEVICE_PTRS; the axes
+ * are host memory.  PRHF_EINVAL for a null context (before anything else) and as in the two calls above, for n_bisect
+ * outside 1 .. 64 and unless 0 < f_lo_hz < f_hi_hz, both finite; PRHF_ENEGDEN for a negative density in a host array.
+ * Synchronous.
+ */
+int prhf_gradient_muf_f64(prhf_ctx* ctx, int32_t geometry, const double* den, const double* bmag, const double* bpsi,
+                          int64_t n0, int64_t n1, const double* axis0, const double* axis1, int32_t mode, int32_t edge_order,
+                          const double* link_x0_km, const double* link_z0_km, const double* link_target_km, int64_t n_links,
+                          double f_lo_hz, double f_hi_hz, int32_t n_bisect, const double* scan_elevation_deg, int64_t n_scan,
+                          double earth_radius_km, double s_max_km, double rtol, double atol, double max_step_km,
+                          double z_ground_km, double top, double left, double right, int32_t renormalize_every,
+                          double fill_n, double fill_grad, double fill_mup, double elev_tol_deg, int32_t max_iter,
+                          double* out, uint32_t flags);
+
+/* Diagnostics of the context's last prhf_gradient_skip_f64 or prhf_gradient_muf_f64 (all its trips): counters[0] groups
+ * refined, [1] rays the refine lanes traced, [2] ray slots (64 per trip of a refine wavefront's loop), [3] refine
+ * wavefronts with work.  Lane utilisation of the refinement = [1] / [2].  No device call. */
+int prhf_gradient_skip_counters(prhf_ctx* ctx, uint64_t* counters);
 
 /* Diagnostics of option "pair_plan", summed over every launch since the context was made: counters[0] reflecting pairs
  * whose sum ran from a plan made by one thread, [1] pairs of the same slices that computed their plan themselves (no

@@ -120,6 +120,20 @@ _PROTOTYPES = {
                                [ctypes.c_double] * 9 + [ctypes.c_int32] + [ctypes.c_double] * 4 +
                                [ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32]),
     "prhf_gradient_home_counters": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
+    "prhf_field_build_f64": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int64, ctypes.c_int64] +
+                             [ctypes.c_void_p] * 3 + [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32] +
+                             [ctypes.c_void_p] * 3 + [ctypes.c_uint32]),
+    "prhf_gradient_skip_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64,
+                                              ctypes.c_int64, ctypes.c_int64] + [ctypes.c_void_p] * 5 + [ctypes.c_int64] +
+                               [ctypes.c_void_p, ctypes.c_int64] + [ctypes.c_double] * 9 + [ctypes.c_int32] +
+                               [ctypes.c_double] * 4 + [ctypes.c_int32, ctypes.c_void_p, ctypes.c_uint32]),
+    "prhf_gradient_muf_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32] + [ctypes.c_void_p] * 3 +
+                              [ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
+                               ctypes.c_int32] + [ctypes.c_void_p] * 3 +
+                              [ctypes.c_int64, ctypes.c_double, ctypes.c_double, ctypes.c_int32, ctypes.c_void_p,
+                               ctypes.c_int64] + [ctypes.c_double] * 9 + [ctypes.c_int32] + [ctypes.c_double] * 4 +
+                              [ctypes.c_int32, ctypes.c_void_p, ctypes.c_uint32]),
+    "prhf_gradient_skip_counters": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
     "prhf_pair_plan_counters": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
     "prhf_panel_counters": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
     "prhf_occupancy": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
@@ -380,6 +394,38 @@ class Context:
         """(brackets refined, rays traced by the refine lanes, ray slots, refine wavefronts) of the last gradient_home."""
         buf = (ctypes.c_uint64 * 4)()
         raise_for(self._lib.prhf_gradient_home_counters(self._h, buf))
+        return tuple(int(v) for v in buf)
+
+    def field_build(self, den, bmag, bpsi, n0, n1, axis0, axis1, freq_hz, n_freq, mode, edge_order, records, mu, mup,
+                    flags):
+        """``records``: a device address in every flag combination; the axes: host addresses; ``mu``, ``mup``: both or
+        neither (include/prhf.h)."""
+        return self._lib.prhf_field_build_f64(self._h, den, bmag, bpsi, n0, n1, axis0, axis1, freq_hz, n_freq, int(mode),
+                                              int(edge_order), records, mu or None, mup or None, flags)
+
+    def gradient_skip(self, geometry, records, n_fields, n0, n1, axis0, axis1, group_field, group_x0, group_z0, n_groups,
+                      scan_elev, n_scan, earth_radius, controls, fills, elev_tol, max_iter, out, flags):
+        """controls: gradient_home's; ``out``: (n_groups, 18) doubles (include/prhf.h)."""
+        return self._lib.prhf_gradient_skip_f64(self._h, int(geometry), records, n_fields, n0, n1, axis0, axis1,
+                                                group_field, group_x0, group_z0, n_groups, scan_elev, n_scan,
+                                                float(earth_radius), *(float(v) for v in controls[:8]), int(controls[8]),
+                                                *(float(v) for v in fills), float(elev_tol), int(max_iter), out, flags)
+
+    def gradient_muf(self, geometry, den, bmag, bpsi, n0, n1, axis0, axis1, mode, edge_order, link_x0, link_z0, link_target,
+                     n_links, f_lo, f_hi, n_bisect, scan_elev, n_scan, earth_radius, controls, fills, elev_tol, max_iter,
+                     out, flags):
+        """controls: gradient_home's; ``out``: (n_links, 21) doubles (include/prhf.h)."""
+        return self._lib.prhf_gradient_muf_f64(self._h, int(geometry), den, bmag, bpsi, n0, n1, axis0, axis1, int(mode),
+                                               int(edge_order), link_x0, link_z0, link_target, n_links, float(f_lo),
+                                               float(f_hi), int(n_bisect), scan_elev, n_scan, float(earth_radius),
+                                               *(float(v) for v in controls[:8]), int(controls[8]),
+                                               *(float(v) for v in fills), float(elev_tol), int(max_iter), out, flags)
+
+    def gradient_skip_counters(self):
+        """(groups refined, rays traced by the refine lanes, ray slots, refine wavefronts) of the last gradient_skip or
+        gradient_muf."""
+        buf = (ctypes.c_uint64 * 4)()
+        raise_for(self._lib.prhf_gradient_skip_counters(self._h, buf))
         return tuple(int(v) for v in buf)
 
     def pair_plan_counters(self):

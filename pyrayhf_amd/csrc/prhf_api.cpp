@@ -168,6 +168,8 @@ struct prhf_ctx {
     unsigned long long* d_plan_counters = nullptr;   // 4 words, since the context was made (prhf_pair_plan_counters, prhf_panel_counters)
     bool status_pending = false;
     uint64_t grad_home_counters[PRHF_GRAD_HOME_COUNTERS] = {};   // of the last prhf_gradient_home_f64 (prhf_gradient_home_counters)
+    DevBuf fields;    // prhf_gradient_muf_f64: mu, mu' and the records of every link's field (48 bytes per node and link)
+    uint64_t grad_skip_counters[PRHF_GRAD_SKIP_COUNTERS] = {};   // of the last prhf_gradient_skip_f64 / prhf_gradient_muf_f64
 };
 
 namespace {
@@ -1106,6 +1108,7 @@ int prhf_ctx_destroy(prhf_ctx* c) {
     if (c->leftover_tall_x.p) (void)hipFree(c->leftover_tall_x.p);
     if (c->order.p) (void)hipFree(c->order.p);
     if (c->tall.p) (void)hipFree(c->tall.p);
+    if (c->fields.p) (void)hipFree(c->fields.p);
     for (int g = 0; g < c->n_host_grids; ++g) {
         if (c->host_grid[g].mult.p) (void)hipFree(c->host_grid[g].mult.p);
         if (c->host_grid[g].pairs.p) (void)hipFree(c->host_grid[g].pairs.p);
@@ -2315,6 +2318,299 @@ int prhf_gradient_home_f64(prhf_ctx* c, int32_t geometry, const double* records,
 int prhf_gradient_home_counters(prhf_ctx* c, uint64_t* counters) {
     if (!c || !counters) return fail(PRHF_EINVAL, "null pointer");
     for (int k = 0; k < PRHF_GRAD_HOME_COUNTERS; ++k) counters[k] = c->grad_home_counters[k];
+    return PRHF_OK;
+}
+
+namespace {
+// What prhf_gradient_skip_f64 and prhf_gradient_muf_f64 share: the checks of the tracer's controls and of the search's,
+// and the tracer's arguments (prhf_gradient_home_f64's rules).
+int grad_search_check(int32_t geometry, double earth_radius_km, double s_max_km, double rtol, double atol, double max_step_km,
+                      int32_t renormalize_every, int64_t n_scan, double elev_tol_deg, int32_t max_iter, uint32_t flags) {
+    if (geometry != PRHF_GEO_CARTESIAN && geometry != PRHF_GEO_SPHERICAL)
+        return fail(PRHF_EINVAL, "geometry is 0 (Cartesian) or 1 (spherical)");
+    if (geometry == PRHF_GEO_SPHERICAL && (!(earth_radius_km > 0) || !std::isfinite(earth_radius_km)))
+        return fail(PRHF_EINVAL, "earth_radius_km must be positive and finite");
+    if (flags & ~PRHF_FLAG_DEVICE_PTRS) return fail(PRHF_EINVAL, "unknown flag bits");
+    if (!(s_max_km > 0) || !std::isfinite(s_max_km)) return fail(PRHF_EINVAL, "s_max_km must be positive and finite");
+    if (!(max_step_km > 0)) return fail(PRHF_EINVAL, "`max_step` must be positive.");
+    if (!(rtol >= 0) || !(atol >= 0)) return fail(PRHF_EINVAL, "`atol` must be positive.");
+    if (renormalize_every < 0) return fail(PRHF_EINVAL, "renormalize_every must not be negative");
+    if (n_scan < 1 || n_scan > 0x7fffffffLL) return fail(PRHF_EINVAL, "the scan grid needs at least 1 elevation");
+    if (max_iter < 1 || max_iter > 128) return fail(PRHF_EINVAL, "max_iter is 1 .. 128");
+    if (!(elev_tol_deg >= 0.0) || !std::isfinite(elev_tol_deg))
+        return fail(PRHF_EINVAL, "elev_tol_deg must be finite and not negative");
+    return PRHF_OK;
+}
+int grad_scan_check(const double* scan_elevation_deg, int64_t n_scan) {
+    for (int64_t i = 0; i + 1 < n_scan; ++i)
+        if (!(scan_elevation_deg[i + 1] > scan_elevation_deg[i]))
+            return fail(PRHF_EINVAL, "scan_elevation_deg must be strictly increasing");
+    if (n_scan == 1 && !std::isfinite(scan_elevation_deg[0])) return fail(PRHF_EINVAL, "scan_elevation_deg must be finite");
+    return PRHF_OK;
+}
+void grad_search_args(prhf_ctx* c, prhf::GradTraceArgs& a, int32_t geometry, const double* records, int64_t n_fields, int64_t n0,
+                      int64_t n1, const double* d_axes, double earth_radius_km, double s_max_km, double rtol, double atol,
+                      double max_step_km, double z_ground_km, double top, double left, double right, int32_t renormalize_every,
+                      double fill_n, double fill_grad, double fill_mup) {
+    a.rec = records; a.a0 = d_axes; a.a1 = d_axes + n0; a.n0 = (int)n0; a.n1 = (int)n1; a.n_fields = n_fields;
+    a.s_max = s_max_km;
+    a.rtol = rtol < 100 * 2.220446049250313e-16 ? 100 * 2.220446049250313e-16 : rtol;     // (as the tracers: solve_ivp's floor)
+    a.atol = atol; a.max_step = max_step_km;
+    // (the spherical tracer binds R_E + z_ground_km to the ground event, prhf_trace_gradient_spherical_f64)
+    a.z_ground = geometry == PRHF_GEO_SPHERICAL ? earth_radius_km + z_ground_km : z_ground_km;
+    a.z_max = top; a.x_min = left; a.x_max = right; a.renormalize_every = renormalize_every;
+    a.fill_n = fill_n; a.fill_grad = fill_grad; a.fill_mup = fill_mup; a.status = c->h_status_dev;
+    a.geometry = geometry; a.earth_radius = geometry == PRHF_GEO_SPHERICAL ? earth_radius_km : 0.0;
+}
+int grad_skip_finish(prhf_ctx* c, const unsigned* queue) {
+    unsigned w[PRHF_GRAD_SKIP_QUEUE_WORDS] = {};
+    HIP_TRY(hipMemcpyAsync(w, queue, sizeof w, hipMemcpyDeviceToHost, c->stream));
+    const int rc = prhf_sync(c);
+    c->grad_skip_counters[0] = w[4];
+    for (int k = 1; k < PRHF_GRAD_SKIP_COUNTERS; ++k) c->grad_skip_counters[k] = w[k];
+    return rc;
+}
+}  // namespace
+
+int prhf_field_build_f64(prhf_ctx* c, const double* den, const double* bmag, const double* bpsi, int64_t n0, int64_t n1,
+                         const double* axis0, const double* axis1, const double* freq_hz, int64_t n_freq, int32_t mode,
+                         int32_t edge_order, double* records, double* mu_out, double* mup_out, uint32_t flags) {
+    if (!c) return fail(PRHF_EINVAL, "null context");
+    if (!den || !bmag || !bpsi || !freq_hz || !records) return fail(PRHF_EINVAL, "null array pointer");
+    if ((mu_out == nullptr) != (mup_out == nullptr)) return fail(PRHF_EINVAL, "mu_out and mup_out go together");
+    if (mode != PRHF_MODE_O && mode != PRHF_MODE_X) return fail(PRHF_EINVAL, "Mode must be O or X");
+    if (edge_order != 1 && edge_order != 2) return fail(PRHF_EINVAL, "edge_order is 1 or 2");
+    if (flags & ~PRHF_FLAG_DEVICE_PTRS) return fail(PRHF_EINVAL, "unknown flag bits");
+    int u0 = 0, u1 = 0;
+    int rc = check_field_shape(axis0, axis1, n_freq, n0, n1, edge_order + 1, &u0, &u1);
+    if (rc != PRHF_OK) return rc;
+    const bool dev = (flags & PRHF_FLAG_DEVICE_PTRS) != 0;
+    const size_t plane = (size_t)n0 * (size_t)n1, F = (size_t)n_freq, cells = F * plane;
+    if (!dev)
+        for (size_t i = 0; i < plane; ++i)
+            if (den[i] < 0) return fail(PRHF_ENEGDEN, "Density must be non-negative");
+    ENTER_DEVICE(c->device);
+    const bool own_mu = !dev || !mu_out;
+    rc = ensure(c, c->arena, ((size_t)(n0 + n1) + (dev ? 0 : 3 * plane + F) + (own_mu ? 2 * cells : 0)) * 8);
+    if (rc != PRHF_OK) return rc;
+    double* p = static_cast<double*>(c->arena.p);
+    HIP_TRY(hipMemcpyAsync(p, axis0, (size_t)n0 * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(p + n0, axis1, (size_t)n1 * 8, hipMemcpyHostToDevice, c->stream));
+    prhf::FieldBuildArgs b;
+    std::memset(&b, 0, sizeof b);
+    prhf::FieldPackArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.a0 = p; a.a1 = p + n0;
+    double* q = p + n0 + n1;
+    b.den = den; b.bmag = bmag; b.bpsi = bpsi; b.freq = freq_hz;
+    if (!dev) {
+        HIP_TRY(hipMemcpyAsync(q, den, plane * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(q + plane, bmag, plane * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(q + 2 * plane, bpsi, plane * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(q + 3 * plane, freq_hz, F * 8, hipMemcpyHostToDevice, c->stream));
+        b.den = q; b.bmag = q + plane; b.bpsi = q + 2 * plane; b.freq = q + 3 * plane;
+        q += 3 * plane + F;
+    }
+    b.mu = own_mu ? q : mu_out; b.mup = own_mu ? q + cells : mup_out;
+    b.bmax = c->d_words; b.n_freq = n_freq; b.plane = (long long)plane;
+    b.mode = mode == PRHF_MODE_O ? PRHF_KMODE_O : PRHF_KMODE_X;
+    a.mu = b.mu; a.mup = b.mup; a.rec = records; a.n_fields = n_freq; a.n0 = (int)n0; a.n1 = (int)n1;
+    a.uniform0 = u0; a.uniform1 = u1; a.edge_order = edge_order;
+    HIP_TRY(hipEventRecord(c->begin_ev(), c->stream));
+    HIP_TRY(prhf::launch_field_bmax(b.bmag, b.plane, c->d_words, c->stream));
+    HIP_TRY(prhf::launch_field_build(b, c->stream));
+    HIP_TRY(prhf::launch_field_pack(a, c->stream));
+    HIP_TRY(hipEventRecord(c->pending_end_ev(), c->stream));
+    c->mark_timed();
+    if (!dev && mu_out) {
+        HIP_TRY(hipMemcpyAsync(mu_out, b.mu, cells * 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(mup_out, b.mup, cells * 8, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return PRHF_OK;
+}
+
+int prhf_gradient_skip_f64(prhf_ctx* c, int32_t geometry, const double* records, int64_t n_fields, int64_t n0, int64_t n1,
+                           const double* axis0, const double* axis1, const int64_t* group_field, const double* group_x0_km,
+                           const double* group_z0_km, int64_t n_groups, const double* scan_elevation_deg, int64_t n_scan,
+                           double earth_radius_km, double s_max_km, double rtol, double atol, double max_step_km,
+                           double z_ground_km, double top, double left, double right, int32_t renormalize_every,
+                           double fill_n, double fill_grad, double fill_mup, double elev_tol_deg, int32_t max_iter,
+                           double* out, uint32_t flags) {
+    if (!c) return fail(PRHF_EINVAL, "null context");
+    if (!records || !group_field || !group_x0_km || !group_z0_km || !scan_elevation_deg || !out)
+        return fail(PRHF_EINVAL, "null array pointer");
+    int rc = grad_search_check(geometry, earth_radius_km, s_max_km, rtol, atol, max_step_km, renormalize_every, n_scan,
+                               elev_tol_deg, max_iter, flags);
+    if (rc != PRHF_OK) return rc;
+    if (n_groups < 1) return fail(PRHF_EINVAL, "the search needs at least one group");
+    if (n_groups > 0x7fffffffLL || n_groups * ((n_scan + 63) / 64) > 0x7fffffffLL)
+        return fail(PRHF_EINVAL, "more than 2^31 - 1 groups or scan wavefronts: search in batches");
+    int u0 = 0, u1 = 0;
+    rc = check_field_shape(axis0, axis1, n_fields, n0, n1, 2, &u0, &u1);
+    if (rc != PRHF_OK) return rc;
+    const bool dev = (flags & PRHF_FLAG_DEVICE_PTRS) != 0;
+    if (!dev) {
+        rc = grad_scan_check(scan_elevation_deg, n_scan);
+        if (rc != PRHF_OK) return rc;
+        for (int64_t g = 0; g < n_groups; ++g)
+            if (group_field[g] < 0 || group_field[g] >= n_fields)
+                return fail(PRHF_EINVAL, "group_field[%lld] outside [0, n_fields)", (long long)g);
+    }
+    for (uint64_t& w : c->grad_skip_counters) w = 0;
+    ENTER_DEVICE(c->device);
+    const size_t G = (size_t)n_groups, E = (size_t)n_scan, out_elems = G * PRHF_GRAD_SKIP_OUTPUTS;
+    rc = ensure(c, c->arena, ((size_t)(n0 + n1) + (dev ? 0 : 3 * G + E + out_elems)) * 8);
+    if (rc != PRHF_OK) return rc;
+    double* p = static_cast<double*>(c->arena.p);
+    prhf::GradSkipArgs h;
+    std::memset(&h, 0, sizeof h);
+    HIP_TRY(hipMemcpyAsync(p, axis0, (size_t)n0 * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(p + n0, axis1, (size_t)n1 * 8, hipMemcpyHostToDevice, c->stream));
+    grad_search_args(c, h.g, geometry, records, n_fields, n0, n1, p, earth_radius_km, s_max_km, rtol, atol, max_step_km,
+                     z_ground_km, top, left, right, renormalize_every, fill_n, fill_grad, fill_mup);
+    h.n_groups = n_groups; h.n_scan = (int)n_scan; h.elev_tol = elev_tol_deg; h.max_iter = max_iter;
+    if (dev) {
+        h.group_field = reinterpret_cast<const long long*>(group_field); h.group_x0 = group_x0_km; h.group_z0 = group_z0_km;
+        h.scan_elev = scan_elevation_deg; h.out = out;
+    } else {
+        double* q = p + n0 + n1;
+        long long* d_gf = reinterpret_cast<long long*>(q); q += G;
+        double* d_x0 = q; q += G;
+        double* d_z0 = q; q += G;
+        double* d_e = q; q += E;
+        HIP_TRY(hipMemcpyAsync(d_gf, group_field, G * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_x0, group_x0_km, G * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_z0, group_z0_km, G * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_e, scan_elevation_deg, E * 8, hipMemcpyHostToDevice, c->stream));
+        h.group_field = d_gf; h.group_x0 = d_x0; h.group_z0 = d_z0; h.scan_elev = d_e; h.out = q;
+    }
+    {
+        // the counters, the work list and the scan's ground ranges
+        const size_t queue_bytes = 128, work_bytes = G * 8, scan_bytes = G * E * 8;
+        rc = ensure(c, c->partial, queue_bytes + work_bytes + scan_bytes);
+        if (rc != PRHF_OK) return rc;
+        char* q = static_cast<char*>(c->partial.p);
+        h.queue = reinterpret_cast<unsigned*>(q);
+        h.work = reinterpret_cast<int*>(q + queue_bytes);
+        h.scan_d = reinterpret_cast<double*>(q + queue_bytes + work_bytes);
+    }
+    HIP_TRY(hipEventRecord(c->begin_ev(), c->stream));
+    HIP_TRY(prhf::launch_grad_skip(h, c->stream));
+    HIP_TRY(hipEventRecord(c->pending_end_ev(), c->stream));
+    c->mark_timed();
+    c->status_pending = true;
+    if (!dev) HIP_TRY(hipMemcpyAsync(out, h.out, out_elems * 8, hipMemcpyDeviceToHost, c->stream));
+    return grad_skip_finish(c, h.queue);
+}
+
+int prhf_gradient_muf_f64(prhf_ctx* c, int32_t geometry, const double* den, const double* bmag, const double* bpsi, int64_t n0,
+                          int64_t n1, const double* axis0, const double* axis1, int32_t mode, int32_t edge_order,
+                          const double* link_x0_km, const double* link_z0_km, const double* link_target_km, int64_t n_links,
+                          double f_lo_hz, double f_hi_hz, int32_t n_bisect, const double* scan_elevation_deg, int64_t n_scan,
+                          double earth_radius_km, double s_max_km, double rtol, double atol, double max_step_km,
+                          double z_ground_km, double top, double left, double right, int32_t renormalize_every, double fill_n,
+                          double fill_grad, double fill_mup, double elev_tol_deg, int32_t max_iter, double* out, uint32_t flags) {
+    if (!c) return fail(PRHF_EINVAL, "null context");
+    if (!den || !bmag || !bpsi || !link_x0_km || !link_z0_km || !link_target_km || !scan_elevation_deg || !out)
+        return fail(PRHF_EINVAL, "null array pointer");
+    int rc = grad_search_check(geometry, earth_radius_km, s_max_km, rtol, atol, max_step_km, renormalize_every, n_scan,
+                               elev_tol_deg, max_iter, flags);
+    if (rc != PRHF_OK) return rc;
+    if (mode != PRHF_MODE_O && mode != PRHF_MODE_X) return fail(PRHF_EINVAL, "Mode must be O or X");
+    if (edge_order != 1 && edge_order != 2) return fail(PRHF_EINVAL, "edge_order is 1 or 2");
+    if (n_bisect < 1 || n_bisect > 64) return fail(PRHF_EINVAL, "n_bisect is 1 .. 64");
+    if (!(f_lo_hz > 0.0) || !(f_hi_hz > f_lo_hz) || !std::isfinite(f_hi_hz))
+        return fail(PRHF_EINVAL, "the frequency bracket needs 0 < f_lo_hz < f_hi_hz, both finite");
+    if (n_links < 1) return fail(PRHF_EINVAL, "the search needs at least one link");
+    if (n_links * ((n_scan + 63) / 64) > 0x7fffffffLL)
+        return fail(PRHF_EINVAL, "more than 2^31 - 1 scan wavefronts: search in batches");
+    int u0 = 0, u1 = 0;
+    rc = check_field_shape(axis0, axis1, n_links, n0, n1, edge_order + 1 > 2 ? edge_order + 1 : 2, &u0, &u1);
+    if (rc != PRHF_OK) return rc;
+    const bool dev = (flags & PRHF_FLAG_DEVICE_PTRS) != 0;
+    const size_t plane = (size_t)n0 * (size_t)n1, L = (size_t)n_links, E = (size_t)n_scan;
+    if (!dev) {
+        rc = grad_scan_check(scan_elevation_deg, n_scan);
+        if (rc != PRHF_OK) return rc;
+        for (size_t i = 0; i < plane; ++i)
+            if (den[i] < 0) return fail(PRHF_ENEGDEN, "Density must be non-negative");
+    }
+    for (uint64_t& w : c->grad_skip_counters) w = 0;
+    ENTER_DEVICE(c->device);
+    const size_t out_elems = L * PRHF_GRAD_MUF_OUTPUTS;
+    rc = ensure(c, c->arena, ((size_t)(n0 + n1) + (dev ? 0 : 3 * plane + 3 * L + E + out_elems)) * 8);
+    if (rc != PRHF_OK) return rc;
+    // one field per link: mu, mu' and the records, 48 bytes per node
+    rc = ensure(c, c->fields, L * plane * 48);
+    if (rc != PRHF_OK) return rc;
+    double* p = static_cast<double*>(c->arena.p);
+    prhf::GradMufArgs m;
+    std::memset(&m, 0, sizeof m);
+    prhf::GradSkipArgs& h = m.k;
+    HIP_TRY(hipMemcpyAsync(p, axis0, (size_t)n0 * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(p + n0, axis1, (size_t)n1 * 8, hipMemcpyHostToDevice, c->stream));
+    double* fields = static_cast<double*>(c->fields.p);
+    m.b.mu = fields; m.b.mup = fields + L * plane;
+    double* rec = fields + 2 * L * plane;
+    grad_search_args(c, h.g, geometry, rec, n_links, n0, n1, p, earth_radius_km, s_max_km, rtol, atol, max_step_km,
+                     z_ground_km, top, left, right, renormalize_every, fill_n, fill_grad, fill_mup);
+    h.n_groups = n_links; h.n_scan = (int)n_scan; h.elev_tol = elev_tol_deg; h.max_iter = max_iter;
+    m.n_links = n_links; m.f_lo = f_lo_hz; m.f_hi = f_hi_hz; m.n_bisect = n_bisect;
+    double* d_result = out;
+    if (dev) {
+        m.b.den = den; m.b.bmag = bmag; m.b.bpsi = bpsi;
+        h.group_x0 = link_x0_km; h.group_z0 = link_z0_km; m.link_target = link_target_km; h.scan_elev = scan_elevation_deg;
+    } else {
+        double* q = p + n0 + n1;
+        const double* src[3] = {den, bmag, bpsi};
+        for (int k = 0; k < 3; ++k) HIP_TRY(hipMemcpyAsync(q + k * plane, src[k], plane * 8, hipMemcpyHostToDevice, c->stream));
+        m.b.den = q; m.b.bmag = q + plane; m.b.bpsi = q + 2 * plane;
+        q += 3 * plane;
+        HIP_TRY(hipMemcpyAsync(q, link_x0_km, L * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(q + L, link_z0_km, L * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(q + 2 * L, link_target_km, L * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(q + 3 * L, scan_elevation_deg, E * 8, hipMemcpyHostToDevice, c->stream));
+        h.group_x0 = q; h.group_z0 = q + L; m.link_target = q + 2 * L; h.scan_elev = q + 3 * L;
+        d_result = q + 3 * L + E;
+    }
+    {
+        // the counters, the work list, the scan's ground ranges; per link its frequency, field index, bracket, the skip
+        // row of the trip, the head of the row at the bracket's lower end and the "is searching" word
+        const size_t queue_bytes = 128, work_bytes = L * 8, scan_bytes = L * E * 8;
+        const size_t link_doubles = L * (1 + 1 + 4 + (PRHF_GRAD_SKIP_OUTPUTS - PRHF_GRAD_OUTPUTS) + PRHF_GRAD_SKIP_OUTPUTS);
+        rc = ensure(c, c->partial, queue_bytes + work_bytes + scan_bytes + link_doubles * 8 + L * 4);
+        if (rc != PRHF_OK) return rc;
+        char* q = static_cast<char*>(c->partial.p);
+        h.queue = reinterpret_cast<unsigned*>(q);
+        h.work = reinterpret_cast<int*>(q + queue_bytes);
+        h.scan_d = reinterpret_cast<double*>(q + queue_bytes + work_bytes);
+        double* r = h.scan_d + L * E;
+        m.group_freq = r; r += L;
+        m.group_field = reinterpret_cast<long long*>(r); r += L;
+        m.state = r; r += 4 * L;
+        m.best = r; r += L * (PRHF_GRAD_SKIP_OUTPUTS - PRHF_GRAD_OUTPUTS);
+        h.out = r; r += L * PRHF_GRAD_SKIP_OUTPUTS;
+        m.active = reinterpret_cast<int*>(r);
+    }
+    h.group_field = m.group_field; h.active = m.active;
+    m.out = d_result;
+    m.b.freq = m.group_freq; m.b.active = m.active; m.b.bmax = c->d_words; m.b.n_freq = n_links; m.b.plane = (long long)plane;
+    m.b.mode = mode == PRHF_MODE_O ? PRHF_KMODE_O : PRHF_KMODE_X;
+    m.p.mu = m.b.mu; m.p.mup = m.b.mup; m.p.a0 = p; m.p.a1 = p + n0; m.p.rec = rec; m.p.n_fields = n_links;
+    m.p.n0 = (int)n0; m.p.n1 = (int)n1; m.p.uniform0 = u0; m.p.uniform1 = u1; m.p.edge_order = edge_order;
+    HIP_TRY(hipEventRecord(c->begin_ev(), c->stream));
+    HIP_TRY(prhf::launch_grad_muf(m, c->stream));
+    HIP_TRY(hipEventRecord(c->pending_end_ev(), c->stream));
+    c->mark_timed();
+    c->status_pending = true;
+    if (!dev) HIP_TRY(hipMemcpyAsync(out, d_result, out_elems * 8, hipMemcpyDeviceToHost, c->stream));
+    return grad_skip_finish(c, h.queue);
+}
+
+int prhf_gradient_skip_counters(prhf_ctx* c, uint64_t* counters) {
+    if (!c || !counters) return fail(PRHF_EINVAL, "null pointer");
+    for (int k = 0; k < PRHF_GRAD_SKIP_COUNTERS; ++k) counters[k] = c->grad_skip_counters[k];
     return PRHF_OK;
 }
 

@@ -465,6 +465,63 @@ struct GradHomeArgs {
 };
 hipError_t launch_grad_home(const GradHomeArgs& h, hipStream_t stream);   // scan, brackets, refinement, result rays: four kernels
 
+// Fields of many frequencies built on the device, skip distance of a transmitter and MUF of a link for the gradient
+// tracers (prhf_gradient_skip.inc).
+struct FieldBuildArgs {
+    const double* den;           // (plane) each: one 2-D ionosphere
+    const double* bmag;
+    const double* bpsi;
+    const double* freq;          // (n_freq) [Hz]
+    const int* active;           // (n_freq) or null: frequencies with a 0 here are left alone (the MUF search's settled links)
+    const unsigned long long* bmax;   // 2 words (launch_field_bmax): nanmax|B| as a bit pattern, != 0 when any B is not NaN
+    double* mu;                  // (n_freq, plane) each
+    double* mup;
+    long long n_freq, plane;
+    int mode;                    // PRHF_KMODE_*
+};
+hipError_t launch_field_bmax(const double* bmag, long long plane, unsigned long long* words, hipStream_t stream);
+hipError_t launch_field_build(const FieldBuildArgs& a, hipStream_t stream);
+
+#define PRHF_GRAD_SKIP_OUTPUTS (6 + PRHF_GRAD_OUTPUTS)       // skip_km, elevation_deg, status, scan_index, bracket_deg, n_evals, then the tracer's twelve
+#define PRHF_GRAD_MUF_OUTPUTS (3 + PRHF_GRAD_SKIP_OUTPUTS)   // muf_hz, f_above_hz, status, then the skip row at muf_hz
+#define PRHF_GRAD_SKIP_COUNTERS 4                            // groups refined, rays refined, ray slots of the refine waves, refine waves
+#define PRHF_GRAD_SKIP_QUEUE_WORDS 8                         // [0] the work list's length, [1..3] counters 1..3, [4] counter 0
+struct GradSkipArgs {
+    GradTraceArgs g;             // records, axes, controls, fills, geometry, status; the per-ray arrays and the paths are null
+    const long long* group_field;   // (n_groups) field, launch point of each group
+    const double* group_x0;
+    const double* group_z0;
+    long long n_groups;
+    const double* scan_elev;     // (n_scan) scan grid [deg], strictly increasing
+    int n_scan;
+    double elev_tol;             // [deg]
+    int max_iter;
+    const int* active;           // (n_groups) or null: groups with a 0 here are left alone (the MUF search's settled links)
+    double* scan_d;              // (n_groups, n_scan) scratch: ground range of every scan ray
+    int* work;                   // (n_groups, 2) scratch: (group, scan node) of the groups to refine; 8-byte aligned
+    unsigned* queue;             // PRHF_GRAD_SKIP_QUEUE_WORDS words of scratch, zero when the call's first kernel starts
+    double* out;                 // (n_groups, PRHF_GRAD_SKIP_OUTPUTS)
+};
+hipError_t launch_grad_skip(const GradSkipArgs& h, hipStream_t stream);   // scan, node, refinement, result rays: four kernels
+struct GradMufArgs {
+    GradSkipArgs k;              // a link is a group: k.n_groups == n_links, k.group_field == group_field, k.active == active,
+                                 // k.g.rec == p.rec, k.out (n_links, PRHF_GRAD_SKIP_OUTPUTS) scratch: the skip rows of the trip
+    FieldBuildArgs b;            // b.freq == group_freq, b.active == active, b.n_freq == n_links
+    FieldPackArgs p;             // p.mu == b.mu, p.mup == b.mup, p.n_fields == n_links
+    const double* link_target;   // (n_links) target ground_range_km
+    long long n_links;
+    double f_lo, f_hi;           // [Hz]
+    int n_bisect;
+    double* group_freq;          // (n_links) scratch: every link's frequency of the trip
+    long long* group_field;      // (n_links) scratch: 0 .. n_links - 1
+    int* active;                 // (n_links) scratch
+    double* state;               // (n_links, 4) scratch: lo, hi, status, 0
+    double* best;                // (n_links, 6) scratch: the head of the skip row at lo
+    double* out;                 // (n_links, PRHF_GRAD_MUF_OUTPUTS)
+};
+// Bmax, then (2 + n_bisect) x (set, build, pack, scan, node, refine, decide), then set, build, pack, result, decide
+hipError_t launch_grad_muf(const GradMufArgs& m, hipStream_t stream);
+
 // residual / cost may be null
 hipError_t launch_residual(const double* vh_model, const double* vh_obs, long long n_prof, int n_freq,
                            double* residual, double* cost, hipStream_t stream);

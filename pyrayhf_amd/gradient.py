@@ -29,11 +29,14 @@ import numpy as np
 from . import _native
 from .library import constants, find_mu_mup, find_X, find_Y
 
+_MODE_CODE = {"O": _native.MODE_O, "X": _native.MODE_X}
+
 __all__ = ["build_refractive_index_interpolator_cartesian", "build_refractive_index_interpolator_spherical",
            "build_mup_function", "refractive_field", "RefractiveField", "trace_ray_cartesian_gradient",
            "trace_rays_cartesian_gradient", "trace_fan_cartesian_gradient", "trace_ray_spherical_gradient",
            "trace_rays_spherical_gradient", "trace_fan_spherical_gradient", "home_rays_cartesian_gradient",
-           "home_rays_spherical_gradient", "STATUS_NAMES"]
+           "home_rays_spherical_gradient", "refractive_field_device", "skip_distance_cartesian_gradient",
+           "skip_distance_spherical_gradient", "muf_cartesian_gradient", "muf_spherical_gradient", "STATUS_NAMES"]
 
 STATUS_NAMES = ("ground", "domain", "length", "failure")          # reference library.py:1391-1398
 _KEYS = ("group_path_km", "group_delay_sec", "x_midpoint", "z_midpoint", "ground_range_km", "x_apex_km", "z_apex_km",
@@ -269,6 +272,67 @@ def refractive_field(f0_Hz, Ne, Babs, bpsi, z_grid, x_grid, mode, geometry="cart
         axis0, axis1 = z_grid, x_grid
     return RefractiveField(axis0, axis1, mu, mup, edge_order=edge_order, device=device, fill_n=fill_value_n,
                            fill_grad=fill_value_grad, fill_mup=fill_value_mup, geometry=geometry, R_E=R_E)
+
+
+def _ionosphere(Ne, Babs, bpsi, z_grid, x_grid, mode, geometry, R_E, edge_order):
+    """The checks and the axes that ``refractive_field_device`` and the MUF calls share; nothing here needs a GPU."""
+    if mode not in ("O", "X"):
+        raise ValueError("Mode must be O or X")
+    if geometry not in ("cartesian", "spherical"):
+        raise ValueError("geometry must be 'cartesian' or 'spherical'")
+    if edge_order not in (1, 2):
+        raise ValueError("'edge_order' greater than 2 not supported")          # np.gradient's message
+    z_grid = np.asarray(z_grid, dtype=float)
+    x_grid = np.asarray(x_grid, dtype=float)
+    Ne, Babs, bpsi = (np.ascontiguousarray(v, dtype=np.float64) for v in (Ne, Babs, bpsi))
+    if z_grid.ndim != 1 or x_grid.ndim != 1 or not (Ne.shape == Babs.shape == bpsi.shape == (z_grid.size, x_grid.size)):
+        raise ValueError("Ne, Babs, bpsi must have shape (len(z_grid), len(x_grid))")
+    if not (np.all(np.diff(z_grid) > 0) and np.all(np.diff(x_grid) > 0)):
+        raise ValueError("`z_grid` and `x_grid` must be strictly increasing.")
+    if min(Ne.shape) < edge_order + 1:
+        raise ValueError("Shape of array too small to calculate a numerical gradient, "
+                         "at least (edge_order + 1) elements are required.")
+    if z_grid.size + x_grid.size > _MAX_AXES:
+        raise ValueError(f"the two axes hold at most {_MAX_AXES} values together")
+    if np.any(Ne < 0):
+        raise ValueError("Density must be non-negative")                       # den2freq's
+    if geometry == "spherical":
+        R_E = float(constants()[2] if R_E is None else R_E)
+        axis0, axis1 = R_E + z_grid, x_grid / R_E
+    else:
+        R_E, axis0, axis1 = None, z_grid, x_grid
+    return Ne, Babs, bpsi, np.ascontiguousarray(axis0), np.ascontiguousarray(axis1), R_E
+
+
+def refractive_field_device(f0_Hz, Ne, Babs, bpsi, z_grid, x_grid, mode, geometry="cartesian", *, R_E=None, edge_order=2,
+                            fill_value_n=np.nan, fill_value_grad=0.0, fill_value_mup=np.nan, device=None):
+    """``refractive_field`` built on the device in one call with no host round trip inside it
+    (``prhf_field_build_f64``): X, Y, mu and mu' of every frequency of ``f0_Hz`` ``(F,)`` and the
+    records, from one upload of ``Ne, Babs, bpsi`` ``(nz, nx)``.  Returns a ``RefractiveField`` that already holds its
+    records; its ``.mu`` and ``.mup`` are copied back once.
+
+    Per frequency the fields are bit for bit those of ``find_mu_mup(find_X(Ne, np.array([f])), find_Y(np.array([f]),
+    Babs), bpsi, mode)``, the isotropic rule ``nanmax|Y| < 1e-12`` applied per frequency.  f squared is the PRODUCT
+    ``f * f``, which is what ``find_X`` gives for an ARRAY of frequencies.  ``refractive_field`` hands ``find_X`` a NumPy
+    scalar, whose ``f ** 2`` is libm's ``pow`` and differs from the product in the last bit for about one frequency in a
+    thousand: for those frequencies the two functions differ by a rounding of X.  ``ValueError`` for a negative
+    density."""
+    Ne, Babs, bpsi, axis0, axis1, R_E = _ionosphere(Ne, Babs, bpsi, z_grid, x_grid, mode, geometry, R_E, edge_order)
+    f = np.ascontiguousarray(np.atleast_1d(np.asarray(f0_Hz, dtype=np.float64)))
+    if f.ndim != 1 or f.size == 0:
+        raise ValueError("f0_Hz must be 1-D and not empty")
+    import torch
+    ctx = _native.host_context(device)
+    rec = torch.empty((f.size,) + Ne.shape + (4,), dtype=torch.float64, device=f"cuda:{ctx.device}")
+    mu = np.empty((f.size,) + Ne.shape)
+    mup = np.empty_like(mu)
+    _native.raise_for(ctx.field_build(Ne.ctypes.data, Babs.ctypes.data, bpsi.ctypes.data, axis0.size, axis1.size,
+                                      axis0.ctypes.data, axis1.ctypes.data, f.ctypes.data, f.size, _MODE_CODE[mode],
+                                      edge_order, rec.data_ptr(), mu.ctypes.data, mup.ctypes.data, 0))
+    field = RefractiveField(axis0, axis1, mu, mup, edge_order=edge_order, device=device, fill_n=fill_value_n,
+                            fill_grad=fill_value_grad, fill_mup=fill_value_mup, geometry=geometry, R_E=R_E)
+    field._rec = rec
+    return field
 
 
 def _need_geometry(field, geometry, name):
@@ -577,6 +641,214 @@ def home_rays_spherical_gradient(field, target_x_km, x0_km=0.0, z0_km=0.0, s_max
     return _home(field, "spherical", "home_rays_spherical_gradient", target_x_km, x0_km, z0_km,
                  _controls(s_max_km, rtol, atol, max_step_km, z_ground_km, r_max_km, phi_min, phi_max, renormalize_every),
                  scan_elevation_deg, max_roots, range_tol_km, max_iter, R_E)
+
+
+def _search_controls(scan_elevation_deg, elev_tol_deg, max_iter, controls):
+    """The scan grid, the rule's controls and the tracer's, checked (no GPU needed)."""
+    from .tracers import default_scan_elevations
+    scan = default_scan_elevations() if scan_elevation_deg is None else \
+        np.ascontiguousarray(np.atleast_1d(np.asarray(scan_elevation_deg, dtype=np.float64)))
+    if scan.ndim != 1 or scan.size < 1:
+        raise ValueError("scan_elevation_deg needs at least 1 elevation")
+    if not np.all(np.diff(scan) > 0) or not np.all(np.isfinite(scan)):
+        raise ValueError("scan_elevation_deg must be strictly increasing")
+    max_iter, elev_tol_deg = int(max_iter), float(elev_tol_deg)
+    if not 1 <= max_iter <= 128:
+        raise ValueError("max_iter is 1 .. 128")
+    if not (np.isfinite(elev_tol_deg) and elev_tol_deg >= 0.0):
+        raise ValueError("elev_tol_deg must be finite and not negative")
+    s_max_km, rtol, atol, max_step_km, z_ground_km, top, left, right, renormalize_every = controls
+    max_step = np.inf if max_step_km is None else float(max_step_km)
+    if max_step <= 0:
+        raise ValueError("`max_step` must be positive.")                   # solve_ivp's message
+    ctl = (s_max_km, rtol, atol, max_step, z_ground_km, top, left, right, int(renormalize_every) if renormalize_every else 0)
+    return scan, elev_tol_deg, max_iter, ctl
+
+
+def _skip_rows(out, lead):
+    """The dict of the skip calls from rows of 18 (include/prhf.h), reshaped to ``lead``."""
+    out = out.reshape(lead + (18,))
+    res = {"skip_km": out[..., 0].copy(), "elevation_deg": out[..., 1].copy()}
+    status = np.where(np.isfinite(out[..., 2]), out[..., 2], -1.0).astype(np.int64)
+    res["status"] = status
+    res["scan_index"] = np.where(np.isfinite(out[..., 3]), out[..., 3], -1.0).astype(np.int64)
+    res["bracket_deg"] = out[..., 4].copy()
+    res["n_evals"] = np.where(np.isfinite(out[..., 5]), out[..., 5], 0.0).astype(np.int64)
+    none = status < 0
+    for i, k in enumerate(_KEYS):
+        v = out[..., 6 + i]
+        # (the tracer's integer keys: its status under its own name would collide with the rule's)
+        if k == "status":
+            res["ray_status"] = np.where(none | ~np.isfinite(v), -1.0, v).astype(np.int64)
+        elif k in _INT_KEYS:
+            res[k] = np.where(none | ~np.isfinite(v), 0.0, v).astype(np.int64)
+        else:
+            res[k] = v.copy()
+    return res
+
+
+def _skip(field, geometry, name, x0_km, z0_km, controls, scan_elevation_deg, elev_tol_deg, max_iter, earth_radius):
+    """Both skip calls: the groups are (field, transmitter) in C order."""
+    _need_geometry(field, geometry, name)
+    scan, elev_tol_deg, max_iter, ctl = _search_controls(scan_elevation_deg, elev_tol_deg, max_iter, controls)
+    x0 = np.atleast_1d(np.asarray(x0_km, dtype=np.float64))
+    z0 = np.atleast_1d(np.asarray(z0_km, dtype=np.float64))
+    if x0.ndim != 1 or z0.ndim != 1:
+        raise ValueError("x0_km and z0_km are scalars or 1-D (the transmitters)")
+    x0, z0 = np.broadcast_arrays(x0, z0)
+    n_tx = x0.size
+    if n_tx == 0:
+        raise ValueError("x0_km and z0_km must not be empty")
+    n_fields = field.n_fields
+    group_f = np.ascontiguousarray(np.repeat(np.arange(n_fields, dtype=np.int64), n_tx))
+    group_x = np.ascontiguousarray(np.tile(x0, n_fields))
+    group_z = np.ascontiguousarray(np.tile(z0, n_fields))
+    out = np.empty((group_f.size, 18), dtype=np.float64)
+    rec = field.records()
+    ctx = field._ctx()
+    _native.raise_for(ctx.gradient_skip(0 if earth_radius is None else 1, rec.data_ptr(), n_fields, field.axis0.size,
+                                        field.axis1.size, field.axis0.ctypes.data, field.axis1.ctypes.data,
+                                        group_f.ctypes.data, group_x.ctypes.data, group_z.ctypes.data, group_f.size,
+                                        scan.ctypes.data, scan.size, 0.0 if earth_radius is None else earth_radius, ctl,
+                                        field.fills, elev_tol_deg, max_iter, out.ctypes.data, 0))
+    return _skip_rows(out, (n_fields, n_tx))
+
+
+def skip_distance_cartesian_gradient(field, x0_km=0.0, z0_km=0.0, s_max_km=5000.0, *, scan_elevation_deg=None,
+                                     elev_tol_deg=1e-3, max_iter=64, rtol=1e-7, atol=1e-9, max_step_km=None,
+                                     z_ground_km=0.0, z_min_km=-1.0, z_max_km=1000.0, x_min_km=-1e6, x_max_km=1e6,
+                                     renormalize_every=50):
+    """Skip distance through a horizontally varying ionosphere over a flat Earth: for every field of ``field`` (a
+    ``RefractiveField``, Cartesian; ``F`` of them) and every transmitter ``(x0_km, z0_km)`` (scalars or ``(T,)``), the
+    least ``ground_range_km`` over the elevations of that transmitter's rays (``prhf_gradient_skip_f64``, DESIGN.md
+    section 4.11; the rule is section 4.10's, ``skip_distance_cartesian``'s).  The controls are
+    ``trace_rays_cartesian_gradient``'s.
+
+    ``skip_km`` is the tracer's ``ground_range_km`` of the ray found: the LANDING COORDINATE x.  For a scan that looks
+    forward the skip distance is ``skip_km - x0_km``.
+
+    The fan of ``scan_elevation_deg`` (strictly increasing, default ``tracers.default_scan_elevations()``) is traced
+    once per group; the first scan node that attains the least finite landing coordinate is refined by a golden-section
+    search between its neighbours, with at most ``max_iter`` (1 .. 128) further rays, until the bracket is no wider than
+    ``elev_tol_deg``.  The default, 1e-3 degrees, costs 18 - 19 rays from a 2.5 degree scan; the step controller's
+    sawtooth in D(e) already moves the elevation of so flat a minimum by about 1e-2 degrees, so ``elevation_deg`` is not a
+    robust output - ``skip_km`` is.
+
+    Returns a dict of ``(F, T)`` arrays: ``skip_km``, ``elevation_deg``, ``status``, ``scan_index``, ``bracket_deg``,
+    ``n_evals`` and the keys of ``trace_rays_cartesian_gradient`` for the ray at ``elevation_deg``, bit for bit what that
+    call returns there (the tracer's own ``status`` is ``ray_status`` here).  ``status`` 0: the bracket is within
+    ``elev_tol_deg`` (or no float64 is left inside it); 1: the minimum of the scan lies at either end of it or beside a
+    ray that does not land - the node as it stands, no further ray; 2: a ray inside the bracket does not land; 3:
+    ``max_iter`` is spent; -1: no ray of the scan lands (NaN everywhere, ``scan_index`` and ``ray_status`` -1, the counts
+    0)."""
+    return _skip(field, "cartesian", "skip_distance_cartesian_gradient", x0_km, z0_km,
+                 _controls(s_max_km, rtol, atol, max_step_km, z_ground_km, z_max_km, x_min_km, x_max_km, renormalize_every),
+                 scan_elevation_deg, elev_tol_deg, max_iter, None)
+
+
+def _spherical_defaults(R_E, field_R_E, r_max_km):
+    if R_E is None:
+        R_E = field_R_E
+    if float(R_E) != field_R_E:
+        raise ValueError(f"R_E={R_E} is not the field's ({field_R_E})")
+    return field_R_E, (field_R_E + 1200.0 if r_max_km is None else r_max_km)      # :2226-2227
+
+
+def skip_distance_spherical_gradient(field, x0_km=0.0, z0_km=0.0, s_max_km=6000.0, *, R_E=None, scan_elevation_deg=None,
+                                     elev_tol_deg=1e-3, max_iter=64, z_ground_km=0.0, r_max_km=None, phi_min=-np.pi,
+                                     phi_max=np.pi, rtol=1e-7, atol=1e-9, max_step_km=2.0, renormalize_every=50):
+    """The same over a spherical Earth: ``field`` is spherical, the controls and their defaults are
+    ``trace_rays_spherical_gradient``'s, and ``skip_km`` is that tracer's ``ground_range_km``, the surface arc ``R_E phi``
+    of the landing node (``x0_km`` is a surface arc as well)."""
+    _need_geometry(field, "spherical", "skip_distance_spherical_gradient")
+    R_E, r_max_km = _spherical_defaults(R_E, field.R_E, r_max_km)
+    return _skip(field, "spherical", "skip_distance_spherical_gradient", x0_km, z0_km,
+                 _controls(s_max_km, rtol, atol, max_step_km, z_ground_km, r_max_km, phi_min, phi_max, renormalize_every),
+                 scan_elevation_deg, elev_tol_deg, max_iter, R_E)
+
+
+_MUF_SCRATCH_BYTES = 1 << 30      # the MUF calls cut their links into slabs whose fields stay under this
+
+
+def _muf(geometry, target_x_km, x0_km, z0_km, Ne, Babs, bpsi, z_grid, x_grid, mode, f_lo_hz, f_hi_hz, n_bisect, controls,
+         scan_elevation_deg, elev_tol_deg, max_iter, R_E, edge_order, fills, device, slab_links):
+    Ne, Babs, bpsi, axis0, axis1, R_E = _ionosphere(Ne, Babs, bpsi, z_grid, x_grid, mode, geometry, R_E, edge_order)
+    scan, elev_tol_deg, max_iter, ctl = _search_controls(scan_elevation_deg, elev_tol_deg, max_iter, controls)
+    n_bisect, f_lo_hz, f_hi_hz = int(n_bisect), float(f_lo_hz), float(f_hi_hz)
+    if not 1 <= n_bisect <= 64:
+        raise ValueError("n_bisect is 1 .. 64")
+    if not (0.0 < f_lo_hz < f_hi_hz < np.inf):
+        raise ValueError("the frequency bracket needs 0 < f_lo_hz < f_hi_hz, both finite")
+    arrs = np.broadcast_arrays(*(np.asarray(v, dtype=np.float64) for v in (target_x_km, x0_km, z0_km)))
+    shape = arrs[0].shape
+    t, x0, z0 = (np.ascontiguousarray(v).reshape(-1) for v in arrs)
+    if t.size == 0:
+        raise ValueError("target_x_km must not be empty")
+    if slab_links is None:
+        slab_links = max(1, _MUF_SCRATCH_BYTES // (48 * Ne.size))
+    slab_links = int(slab_links)
+    if slab_links < 1:
+        raise ValueError("a slab holds at least one link")
+    out = np.empty((t.size, 21), dtype=np.float64)
+    ctx = _native.host_context(device)
+    for lo in range(0, t.size, slab_links):
+        n = min(slab_links, t.size - lo)
+        # (contiguous 1-D arrays: a slice's address is its first element's)
+        _native.raise_for(ctx.gradient_muf(0 if geometry == "cartesian" else 1, Ne.ctypes.data, Babs.ctypes.data,
+                                           bpsi.ctypes.data, axis0.size, axis1.size, axis0.ctypes.data, axis1.ctypes.data,
+                                           _MODE_CODE[mode], edge_order, x0[lo:].ctypes.data, z0[lo:].ctypes.data,
+                                           t[lo:].ctypes.data, n, f_lo_hz, f_hi_hz, n_bisect, scan.ctypes.data, scan.size,
+                                           0.0 if R_E is None else R_E, ctl, fills, elev_tol_deg, max_iter,
+                                           out[lo:].ctypes.data, 0))
+    res = {"muf_hz": out[:, 0].reshape(shape).copy(), "f_above_hz": out[:, 1].reshape(shape).copy(),
+           "status": out[:, 2].astype(np.int64).reshape(shape)}
+    for k, v in _skip_rows(np.ascontiguousarray(out[:, 3:]), shape).items():
+        res["skip_status" if k == "status" else k] = v
+    return res
+
+
+def muf_cartesian_gradient(target_x_km, Ne, Babs, bpsi, z_grid, x_grid, mode, f_lo_hz, f_hi_hz, x0_km=0.0, z0_km=0.0,
+                           s_max_km=5000.0, *, n_bisect=40, scan_elevation_deg=None, elev_tol_deg=1e-3, max_iter=64,
+                           edge_order=2, fill_value_n=np.nan, fill_value_grad=0.0, fill_value_mup=np.nan, rtol=1e-7,
+                           atol=1e-9, max_step_km=None, z_ground_km=0.0, z_min_km=-1.0, z_max_km=1000.0, x_min_km=-1e6,
+                           x_max_km=1e6, renormalize_every=50, device=None, _slab_links=None):
+    """MUF of links through a tilted ionosphere over a flat Earth: for every link - ``target_x_km``, ``x0_km`` and
+    ``z0_km`` broadcast against each other - the highest frequency in ``[f_lo_hz, f_hi_hz]`` whose skip distance through
+    the ionosphere ``Ne, Babs, bpsi`` ``(nz, nx)`` on ``z_grid, x_grid`` still reaches the target
+    (``prhf_gradient_muf_f64``).  S(f) is ``skip_distance_cartesian_gradient``'s ``skip_km`` (the
+    landing coordinate) on ``refractive_field_device``'s field at f, +inf where no ray of the scan lands; the semantics,
+    statuses and the bisection are ``muf_cartesian``'s (section 4.10): ``n_bisect`` (1 .. 64) halvings of the bracket, m =
+    lo + 0.5 (hi - lo).  The fields of the frequencies tried are built on the device (f squared is the product f f), the
+    whole search is one call with one synchronisation, and it is latency-bound: 3 + ``n_bisect`` dependent rounds.
+
+    The fields of a call's links take 48 bytes per node and link; the links go in slabs that keep that under 1 GiB, and
+    no result depends on the slabs.
+
+    Returns a dict of arrays of the links' broadcast shape: ``muf_hz``, ``f_above_hz``, ``status`` and the keys of
+    ``skip_distance_cartesian_gradient`` for the field at ``muf_hz``, bit for bit what that call returns on
+    ``refractive_field_device([muf_hz], ...)`` (its ``status`` is ``skip_status`` here).  ``status`` 0: S(muf_hz) <=
+    target < S(f_above_hz); 1: S(f_hi_hz) <= target, ``muf_hz`` is ``f_hi_hz`` and ``f_above_hz`` NaN; 2: S(f_lo_hz) >
+    target, nothing found; -1: a NaN target."""
+    return _muf("cartesian", target_x_km, x0_km, z0_km, Ne, Babs, bpsi, z_grid, x_grid, mode, f_lo_hz, f_hi_hz, n_bisect,
+                _controls(s_max_km, rtol, atol, max_step_km, z_ground_km, z_max_km, x_min_km, x_max_km, renormalize_every),
+                scan_elevation_deg, elev_tol_deg, max_iter, None, edge_order,
+                (float(fill_value_n), float(fill_value_grad), float(fill_value_mup)), device, _slab_links)
+
+
+def muf_spherical_gradient(target_x_km, Ne, Babs, bpsi, z_grid, x_grid, mode, f_lo_hz, f_hi_hz, x0_km=0.0, z0_km=0.0,
+                           s_max_km=6000.0, *, R_E=None, n_bisect=40, scan_elevation_deg=None, elev_tol_deg=1e-3,
+                           max_iter=64, edge_order=2, fill_value_n=np.nan, fill_value_grad=0.0, fill_value_mup=np.nan,
+                           z_ground_km=0.0, r_max_km=None, phi_min=-np.pi, phi_max=np.pi, rtol=1e-7, atol=1e-9,
+                           max_step_km=2.0, renormalize_every=50, device=None, _slab_links=None):
+    """The same over a spherical Earth of radius ``R_E`` (default ``constants()[2]``): the controls and their defaults are
+    ``trace_rays_spherical_gradient``'s, targets and ``x0_km`` are surface arcs."""
+    R_E = float(constants()[2] if R_E is None else R_E)
+    if r_max_km is None:
+        r_max_km = R_E + 1200.0                                             # :2226-2227
+    return _muf("spherical", target_x_km, x0_km, z0_km, Ne, Babs, bpsi, z_grid, x_grid, mode, f_lo_hz, f_hi_hz, n_bisect,
+                _controls(s_max_km, rtol, atol, max_step_km, z_ground_km, r_max_km, phi_min, phi_max, renormalize_every),
+                scan_elevation_deg, elev_tol_deg, max_iter, R_E, edge_order,
+                (float(fill_value_n), float(fill_value_grad), float(fill_value_mup)), device, _slab_links)
 
 
 def trace_ray_spherical_gradient(n_and_grad_rphi, mup_func, x0_km, z0_km, elevation_deg, s_max_km=6000.0, *, R_E=None,

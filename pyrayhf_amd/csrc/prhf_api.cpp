@@ -1,6 +1,8 @@
-// prhf_api.cpp - the C ABI of libprhf.so (include/prhf.h): contexts, launch planning,
-// host<->device staging, timing and error reporting.  No compute happens on the host;
-// there is no CPU fallback: without a GPU every compute entry point fails with PRHF_EHIP.
+// prhf_api.cpp - the C ABI of libprhf.so (include/prhf.h): contexts, host<->device staging, the
+// execution of a launch plan, timing and error reporting.  What an operator call launches is decided
+// in prhf_plan.h (plan_launch), without HIP; run() here carries the plan out in named steps.  No
+// compute happens on the host; there is no CPU fallback: without a GPU every compute entry point
+// fails with PRHF_EHIP.
 
 #include <hip/hip_runtime_api.h>
 
@@ -18,7 +20,7 @@
 
 #include "prhf.h"
 #include "prhf_kernels.h"
-#include "prhf_plan.h"        // Knobs, plan_slice, validate_work_list: the HIP-free part of the launch planning
+#include "prhf_plan.h"        // Knobs, plan_launch, StatusWord: the launch planning, HIP-free
 
 namespace {
 
@@ -45,7 +47,6 @@ constexpr size_t kPackBytes = 1u << 20;
 constexpr size_t kSlabMinBytes = 16u << 20;    // host-buffer batches from this many input bytes on go in slabs (run_host_slabs)
 constexpr size_t kDirectBytes = 128u << 10;   // inputs up to this size are written by the CPU through the BAR (direct_upload)
 
-constexpr int kStatusWords = 12;           // prhf_ctx::d_status: block queues and scratch words of the launches
 constexpr long long kMaxAlt = 1400;        // nodes + hints must fit 160 KiB of LDS
 constexpr long long kMaxAltTall = 65535;   // taller profiles are staged in global memory (vfo_tall_kernel); level
                                            // indices travel as uint16 in the hint table
@@ -156,9 +157,8 @@ struct prhf_ctx {
     int n_host_grids = 0;
     bool order_clean = false;       // the class counters at the head of `order` are zero (short_order_kernel needs them so; the
                                     // follow-up kernel of the launch that used them leaves them so)
-    unsigned* d_status = nullptr;   // device words [1..5]: block queues of persistent launches (general, short-grid O and its
-                                    // follow-up, short-grid X and its follow-up); [6]: ray queue of the per-ray tracer launch;
-                                    // [0] unused
+    unsigned* d_status = nullptr;   // kStatusWords device words, named by StatusWord (prhf_plan.h): the block queues of the
+                                    // operator's persistent launches and the word of the peak pre-pass
     unsigned* h_status = nullptr;   // PRHF_STATUS_WORDS words of pinned host memory mapped into the device: word b = status
     unsigned* h_status_dev = nullptr;   // bit b (post_status) - nothing to copy back or reset on the device; its device address
     double* h_pack = nullptr;       // pinned, kPackBytes: inputs of a small host-buffer call, sent in one piece; its upper
@@ -212,257 +212,144 @@ int status_to_code(unsigned bits) {
     return PRHF_OK;
 }
 
-int run(prhf_ctx* c, const double* freq, int64_t n_freq, const double* den, const double* bmag,
-        const double* bpsi, const double* alt, int64_t n_prof, int64_t n_alt, int64_t prof_stride,
-        int64_t alt_stride, const double* mult, int64_t mult_len, const prhf_segment* segs, int32_t n_segs,
-        double* out, uint32_t flags, const Residual* post = nullptr) {
-    if (!c) return fail(PRHF_EINVAL, "null context");
-    if (!freq || !den || !bmag || !bpsi || !alt || !mult || !segs || (!out && !post))
+// One operator call on its way through run(): the caller's arguments, and what one step leaves for the next
+struct Call {
+    prhf_ctx* c;
+    const double *freq, *den, *bmag, *bpsi, *alt, *mult;
+    int64_t n_freq, n_prof, n_alt, prof_stride, alt_stride, mult_len;
+    const prhf_segment* segs;
+    int32_t n_segs;
+    double* out;
+    uint32_t flags;
+    const Residual* post;
+    bool dev, shared_field;
+    // stage_inputs:
+    prhf_ctx::HostGrid* grid;   // host buffers with PRHF_FLAG_GRID_STABLE: the cached device copy of the grid
+    double* d_out;              // host buffers: the result rows in the arena
+    size_t in_elems, out_elems; // ... the doubles in front of them, and theirs
+    bool out_direct;            // the kernels write the result into pinned host memory themselves
+    double* vh_dev;             // the modeled trace and the residual stage's other arrays on the device
+    const double* d_obs;
+    double *d_res, *d_cost;
+    // update_tables:
+    unsigned* order_made;       // the short-grid O launch's blocks by cost (short_order_kernel), or null: index order
+};
+
+// PRHF_FLAG_GRID_STABLE with host buffers: the cached copy of this grid, or null
+prhf_ctx::HostGrid* find_host_grid(prhf_ctx* c, const double* mult, int64_t mult_len) {
+    for (int g = 0; g < c->n_host_grids; ++g)
+        if (c->host_grid[g].host == mult && c->host_grid[g].len == mult_len) return &c->host_grid[g];
+    return nullptr;
+}
+
+int check_arguments(const Call& k) {
+    if (!k.c) return fail(PRHF_EINVAL, "null context");
+    if (!k.freq || !k.den || !k.bmag || !k.bpsi || !k.alt || !k.mult || !k.segs || (!k.out && !k.post))
         return fail(PRHF_EINVAL, "null array pointer");
-    if (post && (!post->vh_obs || (!post->residual && !post->cost)))
+    if (k.post && (!k.post->vh_obs || (!k.post->residual && !k.post->cost)))
         return fail(PRHF_EINVAL, "null array pointer");
-    if (n_freq < 1 || n_prof < 0 || n_alt < 1) return fail(PRHF_EINVAL, "bad shape");
-    if (n_alt > kMaxAltTall) return fail(PRHF_EINVAL, "n_alt %lld exceeds the limit of %lld levels",
-                                         (long long)n_alt, kMaxAltTall);
-    // Profiles of more levels than LDS holds are staged in global memory and take the generic loop (vfo_tall_kernel):
-    // no main loop, no candidate list, no short-grid kernels - the same values as any profile that leaves those paths.
-    // Decided below, once the highest density peak of the launch is known: only the bottomside is staged, and a
-    // column of 2 500 levels at 0.25 km has its peak near level 900.
-    bool tall = n_alt > kMaxAlt;
-    if (n_freq > (1 << 20)) return fail(PRHF_EINVAL, "n_freq too large");
-    if (prof_stride < n_alt || (alt_stride != 0 && alt_stride < n_alt))
+    if (k.n_freq < 1 || k.n_prof < 0 || k.n_alt < 1) return fail(PRHF_EINVAL, "bad shape");
+    if (k.n_alt > kMaxAltTall) return fail(PRHF_EINVAL, "n_alt %lld exceeds the limit of %lld levels",
+                                           (long long)k.n_alt, kMaxAltTall);
+    if (k.n_freq > (1 << 20)) return fail(PRHF_EINVAL, "n_freq too large");
+    if (k.prof_stride < k.n_alt || (k.alt_stride != 0 && k.alt_stride < k.n_alt))
         return fail(PRHF_EINVAL, "row stride shorter than a row");
-    if (n_segs < 1 || n_segs > PRHF_MAX_SEGMENTS)
+    if (k.n_segs < 1 || k.n_segs > PRHF_MAX_SEGMENTS)
         return fail(PRHF_EINVAL, "1..%d segments per launch", PRHF_MAX_SEGMENTS);
-    if (flags & ~(PRHF_FLAG_DEVICE_PTRS | PRHF_FLAG_ASYNC | PRHF_FLAG_GRID_STABLE | PRHF_FLAG_SHARED_FIELD))
+    if (k.flags & ~(PRHF_FLAG_DEVICE_PTRS | PRHF_FLAG_ASYNC | PRHF_FLAG_GRID_STABLE | PRHF_FLAG_SHARED_FIELD))
         return fail(PRHF_EINVAL, "unknown flag bits");
-    const bool dev = (flags & PRHF_FLAG_DEVICE_PTRS) != 0;
-    const bool shared_field = (flags & PRHF_FLAG_SHARED_FIELD) != 0;
-    if ((flags & PRHF_FLAG_ASYNC) && !dev) return fail(PRHF_EINVAL, "PRHF_FLAG_ASYNC needs device pointers");
+    if ((k.flags & PRHF_FLAG_ASYNC) && !k.dev) return fail(PRHF_EINVAL, "PRHF_FLAG_ASYNC needs device pointers");
     // (A sounder frequency that is not a positive finite number gives a NaN column, host and device buffers alike:
     //  freq_table_kernel / pair_freq.  The reference returns NaN for 0 and NaN, and something meaningless for f < 0.)
     // The stretched grid must not decrease (smooth_nonuniform_grid never does): the top-segment search of the main
     // loop relies on it.  Checked here for host buffers; device-resident grids are the caller's.
-    bool grid_known = false;                   // (a stable host grid that is cached already was checked when it was uploaded)
-    if (!dev && (flags & PRHF_FLAG_GRID_STABLE))
-        for (int g = 0; g < c->n_host_grids; ++g)
-            grid_known = grid_known || (c->host_grid[g].host == mult && c->host_grid[g].len == mult_len);
-    if (!dev && !grid_known) {
-        const long long bad = first_decreasing_grid_entry(mult, mult_len, segs, n_segs);
+    // (a stable host grid that is cached already was checked when it was uploaded)
+    const bool grid_known = !k.dev && (k.flags & PRHF_FLAG_GRID_STABLE) && find_host_grid(k.c, k.mult, k.mult_len);
+    if (!k.dev && !grid_known) {
+        const long long bad = first_decreasing_grid_entry(k.mult, k.mult_len, k.segs, k.n_segs);
         if (bad >= 0) return fail(PRHF_EINVAL, "multiplier[%lld] decreases: the stretched grid must be non-decreasing", bad);
     }
+    return PRHF_OK;
+}
 
-    ENTER_DEVICE(c->device);
-
-    // More levels than LDS holds: find the highest peak index of the launch (np.argmax, the first NaN ranking highest -
-    // stage_profile's rule).  When every bottomside fits, the LDS kernels run with their staged arrays sized for that
-    // peak (KArgs::lds_levels).
-    long long lds_levels = n_alt;
-    if (tall && n_prof > 0 && c->knobs.trim_lds != 0) {
-        long long max_peak = 0;
-        if (dev) {
-            HIP_TRY(hipMemsetAsync(c->d_status + 7, 0, sizeof(unsigned), c->stream));
-            HIP_TRY(prhf::launch_peak_levels(den, n_prof, n_alt, prof_stride, c->d_status + 7, c->stream));
-            unsigned peak = 0;
-            HIP_TRY(hipMemcpyAsync(&peak, c->d_status + 7, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            max_peak = peak;
-        } else {
-            for (int64_t p = 0; p < n_prof; ++p) {
-                const double* d = den + (size_t)p * prof_stride;
-                double bv = -HUGE_VAL;
-                long long bi = 0;
-                for (int64_t i = 0; i < n_alt; ++i) {
-                    const double key = (d[i] != d[i]) ? HUGE_VAL : d[i];
-                    if (key > bv) { bv = key; bi = i; }
-                }
-                max_peak = std::max(max_peak, bi);
+// Profiles of more levels than LDS holds are staged in global memory and take the generic loop (vfo_tall_kernel):
+// no main loop, no candidate list, no short-grid kernels - the same values as any profile that leaves those paths.
+// Decided once the highest density peak of the launch is known: only the bottomside is staged, and a column of 2 500
+// levels at 0.25 km has its peak near level 900.  The peak index is np.argmax's, the first NaN ranking highest -
+// stage_profile's rule.  When every bottomside fits, the LDS kernels run with their staged arrays sized for that
+// peak (KArgs::lds_levels).
+int decide_tall(const Call& k, bool& tall, long long& lds_levels) {
+    prhf_ctx* c = k.c;
+    tall = k.n_alt > kMaxAlt;
+    lds_levels = k.n_alt;
+    if (!(tall && k.n_prof > 0 && c->knobs.trim_lds != 0)) return PRHF_OK;
+    long long max_peak = 0;
+    if (k.dev) {
+        HIP_TRY(hipMemsetAsync(c->d_status + kWordPeak, 0, sizeof(unsigned), c->stream));
+        HIP_TRY(prhf::launch_peak_levels(k.den, k.n_prof, k.n_alt, k.prof_stride, c->d_status + kWordPeak, c->stream));
+        unsigned peak = 0;
+        HIP_TRY(hipMemcpyAsync(&peak, c->d_status + kWordPeak, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        max_peak = peak;
+    } else {
+        for (int64_t p = 0; p < k.n_prof; ++p) {
+            const double* d = k.den + (size_t)p * k.prof_stride;
+            double bv = -HUGE_VAL;
+            long long bi = 0;
+            for (int64_t i = 0; i < k.n_alt; ++i) {
+                const double key = (d[i] != d[i]) ? HUGE_VAL : d[i];
+                if (key > bv) { bv = key; bi = i; }
             }
-        }
-        if (max_peak + 1 <= kMaxAlt) {
-            tall = false;
-            lds_levels = max_peak + 1;
+            max_peak = std::max(max_peak, bi);
         }
     }
+    if (max_peak + 1 <= kMaxAlt) {
+        tall = false;
+        lds_levels = max_peak + 1;
+    }
+    return PRHF_OK;
+}
 
-    const Knobs& kn = c->knobs;
-    const double kWellConditioned = kn.well_conditioned, kThreadScanMinWork = kn.thread_scan_min;
-    const int kLeanMinPoints = (int)kn.lean_min_points, kNoCandidates = kn.no_candidates != 0;
-    const bool kPersistent = kn.persistent != 0, kShortKernel = kn.short_kernel != 0, kShortXKernel = kn.shortx_kernel != 0;
-    const bool kShortConcurrent = kn.short_concurrent != 0;
-    const int kShortQueueFixed = (int)kn.short_queue;
-    const int n_user_segs = n_segs;
-    prhf::KArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.n_freq = n_freq;
-    a.n_alt = n_alt;
-    a.lds_levels = lds_levels;
-    a.n_segs = n_segs;
-    // Slices of short O-mode grids leave for a launch of their own (vfo_short_kernel): `a` keeps the others
-    prhf::SegDev short_seg[PRHF_MAX_SEGMENTS], shortx_seg[PRHF_MAX_SEGMENTS];
-    int n_short = 0, n_shortx = 0;
-    // LDS budget of a short-grid workgroup: two per CU where its nodes allow that, else one (a few hundred bytes of
-    // static LDS - tickets, counters - come on top)
-    const size_t lds_half = 80 * 1024 - 512, lds_full = 160 * 1024 - 512;
-    const size_t short_budget = prhf::short_queue_entries(lds_levels, n_freq, lds_half, PRHF_SHORT_THREADS) ? lds_half : lds_full;
-    const int short_queue = prhf::short_queue_entries(lds_levels, n_freq, short_budget, PRHF_SHORT_THREADS);
-    // The compact geometry of the short-grid O kernel: four 4-wave workgroups per CU instead of two
-    // 8-wave ones - four independent profiles in flight per CU, so that one workgroup's staging and barrier waits are
-    // covered by three others' items (config 3: -10 %).  A quarter of the LDS holds the lists and fewer levels than
-    // the column has; a profile whose peak lies above them goes to a second launch with full-size arrays.  Taken when
-    // those arrays hold at least half of the column (PyIRI columns peak at 25 - 50 % of their height).
-#ifndef PRHF_COMPACT_RESERVE
-#define PRHF_COMPACT_RESERVE 512    // bytes kept back per workgroup for its static LDS (tickets, counters)
-#endif
-    const size_t lds_quarter = (160 * 1024) / PRHF_COMPACT_WGS_PER_CU - PRHF_COMPACT_RESERVE;
-    long long compact_levels = 0;
-    int compact_queue = 0;
-    if (kn.short_compact != 0 && short_queue > 0) {
-        long long L = lds_levels;
-        while (L > 1 && prhf::short_lds_fixed(L, n_freq, PRHF_COMPACT_THREADS) + 8 * PRHF_COMPACT_MIN_QUEUE > lds_quarter) --L;
-        if (2 * L >= lds_levels && L >= 8 &&
-            prhf::short_lds_fixed(L, n_freq, PRHF_COMPACT_THREADS) + 8 * PRHF_COMPACT_MIN_QUEUE <= lds_quarter) {
-            compact_levels = L;
-            compact_queue = prhf::short_queue_entries(L, n_freq, lds_quarter, PRHF_COMPACT_THREADS);
-        }
-    }
-    long long blocks = 0, partial_elems = 0, altmin_elems = 0, out_rows = 0;
-    int launch_tier = 0;
-    bool want_pairs = false;
-    // resident workgroups: LDS admits two per CU up to 80 KiB each, else one
-    const long long wg_slots = (long long)c->cu_count * ((tall || prhf::lds_bytes_for(lds_levels) <= 80 * 1024) ? 2 : 1);
-    {
-        char why[160];
-        if (validate_work_list(segs, n_segs, n_prof, n_freq, mult_len, why, sizeof why) != PRHF_OK) return fail(PRHF_EINVAL, "%s", why);
-    }
-    for (int i = 0; i < n_segs; ++i) {
-        const prhf_segment& u = segs[i];
-        prhf::SegDev& s = a.seg[i];
-        s.prof_begin = u.prof_begin;
-        s.prof_end = u.prof_end;
-        s.mult_off = u.mult_offset;
-        s.out_off = u.out_offset;
-        s.mode = u.mode == PRHF_MODE_O ? PRHF_KMODE_O : PRHF_KMODE_X;
-        s.n_points = u.n_points;
-        s.tier = c->math == PRHF_MATH_AUTO ? (u.mode == PRHF_MODE_O ? 0 : 1) : (c->math == PRHF_MATH_FAST ? 1 : 0);
-        // AUTO, O mode: the reference's operation order where it decides the answer (1 - X <= well_conditioned = 1e-5), the
-        // reduced algebra elsewhere; PRHF_MATH_FAITHFUL keeps the reference's order everywhere
-        s.well_conditioned = (c->math == PRHF_MATH_AUTO && s.tier == 0) ? kWellConditioned : HUGE_VAL;
-        launch_tier = (i == 0 || launch_tier == s.tier) ? s.tier : 2;
-        // the main loop needs the pair table: one more (small) kernel unless the caller's grid is cached - not
-        // worth it for a handful of pairs on a short grid, where the launch itself is the cost
-        const long long seg_pairs = (u.prof_end - u.prof_begin) * n_freq;
-        // (decided from the slice's shape alone: host and device callers must get the same arithmetic)
-        const bool table_is_cheap = seg_pairs >= 4096 || u.n_points >= 2048;
-        // (a profile staged in global memory - `tall` - takes the main loop too: it reads the nodes from the workgroup's
-        //  slab through a buffer resource, NodeSpace<true>; option tall_lean = 0: the generic loop, as up to round 4)
-        s.lean = ((!tall || kn.tall_lean != 0) && (s.tier == 1 || s.well_conditioned < 1.0) && u.n_points >= kLeanMinPoints &&
-                  seg_pairs > 0 && table_is_cheap) ? 1 : 0;
-        want_pairs = want_pairs || s.lean != 0;
-        s.thread_scan = (!tall && (double)n_freq * (double)u.n_points >= kThreadScanMinWork) ? 1 : 0;
-        plan_slice(s, n_freq, wg_slots, kn);
-        out_rows = std::max<long long>(out_rows, u.out_offset / n_freq + (u.prof_end - u.prof_begin));
-    }
-    // (a.seg[i] was filled for every slice; now the short-grid slices move out and the others close ranks)
-    {
-        int kept = 0;
-        for (int i = 0; i < n_segs; ++i) {
-            const prhf::SegDev& s = a.seg[i];
-            // the short-grid kernel reads the per-frequency table (launches of >= 4096 pairs) and lists at most
-            // PRHF_MAX_CAND frequencies per profile
-            // (grids shorter than the general kernel's main loop takes - lean_min_points - are theirs too: the pair
-            //  table is built for them)
-            const long long slice_pairs = (s.prof_end - s.prof_begin) * n_freq;
-            const bool table = !tall && (s.lean || (slice_pairs >= 4096 && s.n_points < kLeanMinPoints));
-            const bool is_short = kShortKernel && s.tier == 0 && s.well_conditioned < 1.0 && table && s.chunks == 1 &&
-                                  s.n_points >= PRHF_SHORT_MIN_POINTS && s.n_points <= PRHF_SHORT_MAX_POINTS &&
-                                  n_freq <= PRHF_MAX_CAND && n_prof * n_freq >= 4096 && !kNoCandidates && short_queue > 0;
-            // ... and its X-mode variant (fast tier, reflection heights per thread, no top-segment phase)
-            const bool is_shortx = kShortXKernel && s.tier == 1 && s.mode == PRHF_KMODE_X && table && s.chunks == 1 &&
-                                   s.n_points >= PRHF_SHORT_MIN_POINTS && s.n_points <= PRHF_SHORTX_MAX_POINTS &&
-                                   n_freq <= PRHF_MAX_CAND && n_prof * n_freq >= 4096 && !kNoCandidates && s.thread_scan &&
-                                   prhf::shortx_lds_bytes(lds_levels, n_freq) <= lds_full;
-            if (is_short || is_shortx) {
-                prhf::SegDev& t = is_short ? short_seg[n_short++] : shortx_seg[n_shortx++];
-                t = s;
-                t.lean = 1;
-                want_pairs = true;
-                t.blocks_per_prof = 1;
-                t.tail_prof = t.prof_end - t.prof_begin;
-                t.tail_bpp = 1;
-                t.prio = 0;
-            } else {
-                if (kept != i) a.seg[kept] = a.seg[i];
-                ++kept;
-            }
-        }
-        n_segs = kept;
-        a.n_segs = kept;
-        launch_tier = 0;
-        for (int i = 0; i < kept; ++i) launch_tier = (i == 0 || launch_tier == a.seg[i].tier) ? a.seg[i].tier : 2;
-    }
-    // Workgroups are dispatched roughly in index order: give the slices with the most work per workgroup
-    // the lowest indices so that a mixed launch does not end on its longest workgroups.
-    std::stable_sort(a.seg, a.seg + n_segs, [](const prhf::SegDev& x, const prhf::SegDev& y) {
-        auto cost = [](const prhf::SegDev& s) {
-            const double per_point = s.tier == 1 ? 1.0 : (s.well_conditioned < 1.0 ? 1.8 : 3.5);
-            return (double)s.n_points / s.chunks / s.blocks_per_prof * per_point;   // head workgroups
-        };
-        return cost(x) > cost(y);
-    });
-    for (int i = 0; i < n_segs; ++i) {
-        prhf::SegDev& s = a.seg[i];
-        const long long P = s.prof_end - s.prof_begin;
-        s.prio = std::max(0, 3 - i);               // (sorted: the slice with the longest workgroups first)
-        s.block_begin = blocks;
-        blocks += s.tail_prof * s.blocks_per_prof + (P - s.tail_prof) * s.tail_bpp;
-        if (s.chunks > 1 && s.slots == 0) {
-            s.partial_off = partial_elems;
-            s.altmin_off = altmin_elems;
-            partial_elems += P * n_freq * s.chunks;
-            altmin_elems += P;
-        }
-    }
-    if (blocks > 0x7fffffffLL) return fail(PRHF_EINVAL, "launch too large");
-
+// The scratch of the chunked slices, the inputs of a host-buffer call on the device (three routes: the CPU's own
+// stores through the BAR, one copy from the pinned pack buffer, or a copy per array), the residual stage's arrays;
+// then the launch arguments' pointers and strides.
+int stage_inputs(Call& k, const LaunchPlan& pl, prhf::KArgs& a) {
+    prhf_ctx* c = k.c;
+    const int64_t n_freq = k.n_freq, n_prof = k.n_prof, n_alt = k.n_alt, mult_len = k.mult_len;
     int rc;
-    if ((rc = ensure(c, c->partial, (size_t)partial_elems * 8)) != PRHF_OK) return rc;
-    if ((rc = ensure(c, c->altmin, (size_t)altmin_elems * 8)) != PRHF_OK) return rc;
+    if ((rc = ensure(c, c->partial, (size_t)pl.partial_elems * 8)) != PRHF_OK) return rc;
+    if ((rc = ensure(c, c->altmin, (size_t)pl.altmin_elems * 8)) != PRHF_OK) return rc;
     a.partial = static_cast<double*>(c->partial.p);
     a.altmin = static_cast<double*>(c->altmin.p);
     a.status = c->h_status_dev;
 
     const size_t row_bytes = (size_t)n_alt * 8;
-    double* d_out = nullptr;
-    bool out_direct = false;
-    prhf_ctx::HostGrid* grid = nullptr;        // host buffers with PRHF_FLAG_GRID_STABLE: the cached device copy of the grid
-    const size_t out_elems = (size_t)out_rows * (size_t)n_freq;
-    if (dev) {
-        a.freq = freq; a.den = den; a.bmag = bmag; a.bpsi = bpsi; a.alt = alt; a.mult = mult;
-        a.out = out;
-        a.prof_stride = prof_stride;
-        a.field_stride = shared_field ? 0 : prof_stride;
-        a.alt_stride = alt_stride;
+    const size_t out_elems = k.out_elems = (size_t)pl.out_rows * (size_t)n_freq;
+    if (k.dev) {
+        a.freq = k.freq; a.den = k.den; a.bmag = k.bmag; a.bpsi = k.bpsi; a.alt = k.alt; a.mult = k.mult;
+        a.out = k.out;
+        a.prof_stride = k.prof_stride;
+        a.field_stride = k.shared_field ? 0 : k.prof_stride;
+        a.alt_stride = k.alt_stride;
     } else {
-        const size_t n_alt_rows = alt_stride ? (size_t)n_prof : 1;
-        const size_t n_field_rows = shared_field ? 1 : (size_t)n_prof;
-        const size_t post_elems = post ? (size_t)n_freq + out_elems + (size_t)n_prof : 0;
+        const size_t n_alt_rows = k.alt_stride ? (size_t)n_prof : 1;
+        const size_t n_field_rows = k.shared_field ? 1 : (size_t)n_prof;
+        const size_t post_elems = k.post ? (size_t)n_freq + out_elems + (size_t)n_prof : 0;
         // a stable host grid lives in a device buffer of its own, uploaded on first sight
-        if (flags & PRHF_FLAG_GRID_STABLE) {
-            for (int g = 0; g < c->n_host_grids; ++g)
-                if (c->host_grid[g].host == mult && c->host_grid[g].len == mult_len) grid = &c->host_grid[g];
-            if (!grid && c->n_host_grids < prhf_ctx::kHostGrids) {
+        if (k.flags & PRHF_FLAG_GRID_STABLE) {
+            k.grid = find_host_grid(c, k.mult, mult_len);
+            if (!k.grid && c->n_host_grids < prhf_ctx::kHostGrids) {
                 prhf_ctx::HostGrid& g = c->host_grid[c->n_host_grids];
                 if ((rc = ensure(c, g.mult, (size_t)mult_len * 8)) != PRHF_OK) return rc;
-                HIP_TRY(hipMemcpyAsync(g.mult.p, mult, (size_t)mult_len * 8, hipMemcpyHostToDevice, c->stream));
-                g.host = mult;
+                HIP_TRY(hipMemcpyAsync(g.mult.p, k.mult, (size_t)mult_len * 8, hipMemcpyHostToDevice, c->stream));
+                g.host = k.mult;
                 g.len = mult_len;
                 g.pairs_ready = false;
-                grid = &g;
+                k.grid = &g;
                 ++c->n_host_grids;
             }
         }
-        const size_t mult_arena = grid ? 0 : (size_t)mult_len;
+        const size_t mult_arena = k.grid ? 0 : (size_t)mult_len;
         const size_t elems = (size_t)n_freq + ((size_t)n_prof + 2 * n_field_rows) * n_alt + n_alt_rows * n_alt +
                              mult_arena + out_elems + post_elems;
         if ((rc = ensure(c, c->arena, elems * 8)) != PRHF_OK) return rc;
@@ -473,8 +360,8 @@ int run(prhf_ctx* c, const double* freq, int64_t n_freq, const double* den, cons
         double* d_bpsi = d_bmag + n_field_rows * n_alt;
         double* d_alt = d_bpsi + n_field_rows * n_alt;
         double* d_mult = d_alt + n_alt_rows * n_alt;
-        d_out = d_mult + mult_arena;
-        const size_t in_elems = (size_t)(d_out - base);
+        double* d_out = k.d_out = d_mult + mult_arena;
+        const size_t in_elems = k.in_elems = (size_t)(d_out - base);
         if (in_elems * 8 <= kPackBytes && c->h_pack) {
             // A small call (the reference's usual one: a single profile): six separate uploads from pageable
             // memory cost more than the kernel.  Pack the inputs in the arena's own order into a pinned
@@ -490,410 +377,383 @@ int run(prhf_ctx* c, const double* freq, int64_t n_freq, const double* den, cons
             // must be idle: host-buffer calls synchronise before they return, but an asynchronous device-pointer call -
             // or a launch on a stream the context borrowed before - may still be using it; then the staged copy, which is
             // ordered by the stream, is taken.
-            bool direct = c->large_bar && kn.direct_upload != 0 && in_elems * 8 <= kDirectBytes &&
+            bool direct = c->large_bar && c->knobs.direct_upload != 0 && in_elems * 8 <= kDirectBytes &&
                           hipStreamQuery(c->stream) == hipSuccess && (!c->timed || hipEventQuery(c->end_ev()) == hipSuccess);
             (void)hipGetLastError();               // (hipErrorNotReady from the two queries is not an error)
             double* h = direct ? base : c->h_pack;
-            std::memcpy(h + (d_freq - base), freq, (size_t)n_freq * 8);
+            std::memcpy(h + (d_freq - base), k.freq, (size_t)n_freq * 8);
             for (int64_t p = 0; p < n_prof; ++p) {
-                std::memcpy(h + (d_den - base) + (size_t)p * n_alt, den + (size_t)p * prof_stride, row_bytes);
-                if (!shared_field || p == 0) {
-                    std::memcpy(h + (d_bmag - base) + (size_t)p * n_alt, bmag + (size_t)p * prof_stride, row_bytes);
-                    std::memcpy(h + (d_bpsi - base) + (size_t)p * n_alt, bpsi + (size_t)p * prof_stride, row_bytes);
+                std::memcpy(h + (d_den - base) + (size_t)p * n_alt, k.den + (size_t)p * k.prof_stride, row_bytes);
+                if (!k.shared_field || p == 0) {
+                    std::memcpy(h + (d_bmag - base) + (size_t)p * n_alt, k.bmag + (size_t)p * k.prof_stride, row_bytes);
+                    std::memcpy(h + (d_bpsi - base) + (size_t)p * n_alt, k.bpsi + (size_t)p * k.prof_stride, row_bytes);
                 }
-                if (alt_stride) std::memcpy(h + (d_alt - base) + (size_t)p * n_alt, alt + (size_t)p * alt_stride, row_bytes);
+                if (k.alt_stride) std::memcpy(h + (d_alt - base) + (size_t)p * n_alt, k.alt + (size_t)p * k.alt_stride, row_bytes);
             }
-            if (!alt_stride) std::memcpy(h + (d_alt - base), alt, row_bytes);
-            if (!grid) std::memcpy(h + (d_mult - base), mult, (size_t)mult_len * 8);
+            if (!k.alt_stride) std::memcpy(h + (d_alt - base), k.alt, row_bytes);
+            if (!k.grid) std::memcpy(h + (d_mult - base), k.mult, (size_t)mult_len * 8);
             if (direct) _mm_sfence();
             else HIP_TRY(hipMemcpyAsync(base, h, in_elems * 8, hipMemcpyHostToDevice, c->stream));
         } else {
-            HIP_TRY(hipMemcpyAsync(d_freq, freq, (size_t)n_freq * 8, hipMemcpyHostToDevice, c->stream));
-            if (!grid) HIP_TRY(hipMemcpyAsync(d_mult, mult, (size_t)mult_len * 8, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(hipMemcpyAsync(d_freq, k.freq, (size_t)n_freq * 8, hipMemcpyHostToDevice, c->stream));
+            if (!k.grid) HIP_TRY(hipMemcpyAsync(d_mult, k.mult, (size_t)mult_len * 8, hipMemcpyHostToDevice, c->stream));
             if (n_prof > 0) {
-                HIP_TRY(hipMemcpy2DAsync(d_den, row_bytes, den, (size_t)prof_stride * 8, row_bytes, (size_t)n_prof,
+                HIP_TRY(hipMemcpy2DAsync(d_den, row_bytes, k.den, (size_t)k.prof_stride * 8, row_bytes, (size_t)n_prof,
                                          hipMemcpyHostToDevice, c->stream));
-                HIP_TRY(hipMemcpy2DAsync(d_bmag, row_bytes, bmag, (size_t)prof_stride * 8, row_bytes, n_field_rows,
+                HIP_TRY(hipMemcpy2DAsync(d_bmag, row_bytes, k.bmag, (size_t)k.prof_stride * 8, row_bytes, n_field_rows,
                                          hipMemcpyHostToDevice, c->stream));
-                HIP_TRY(hipMemcpy2DAsync(d_bpsi, row_bytes, bpsi, (size_t)prof_stride * 8, row_bytes, n_field_rows,
+                HIP_TRY(hipMemcpy2DAsync(d_bpsi, row_bytes, k.bpsi, (size_t)k.prof_stride * 8, row_bytes, n_field_rows,
                                          hipMemcpyHostToDevice, c->stream));
             }
-            if (alt_stride) {
+            if (k.alt_stride) {
                 if (n_prof > 0)
-                    HIP_TRY(hipMemcpy2DAsync(d_alt, row_bytes, alt, (size_t)alt_stride * 8, row_bytes, (size_t)n_prof,
+                    HIP_TRY(hipMemcpy2DAsync(d_alt, row_bytes, k.alt, (size_t)k.alt_stride * 8, row_bytes, (size_t)n_prof,
                                              hipMemcpyHostToDevice, c->stream));
             } else {
-                HIP_TRY(hipMemcpyAsync(d_alt, alt, row_bytes, hipMemcpyHostToDevice, c->stream));
+                HIP_TRY(hipMemcpyAsync(d_alt, k.alt, row_bytes, hipMemcpyHostToDevice, c->stream));
             }
         }
         a.freq = d_freq; a.den = d_den; a.bmag = d_bmag; a.bpsi = d_bpsi; a.alt = d_alt;
-        a.mult = grid ? static_cast<const double*>(grid->mult.p) : d_mult;
+        a.mult = k.grid ? static_cast<const double*>(k.grid->mult.p) : d_mult;
         a.out = d_out;
         // rows that no segment covers must come back as NaN, not as whatever the arena held (all-ones bytes = NaN)
         long long covered = 0;
-        for (int i = 0; i < n_user_segs; ++i) covered += segs[i].prof_end - segs[i].prof_begin;
+        for (int i = 0; i < k.n_segs; ++i) covered += k.segs[i].prof_end - k.segs[i].prof_begin;
         // A small result (the reference's usual call: one profile) goes straight from the kernel into pinned host
         // memory - the upper half of the pack buffer, which the device sees - instead of into the arena and through
         // a copy of its own: one runtime call and one DMA round trip less per call.
-        out_direct = out && out_elems && !post && c->h_pack && out_elems * 8 <= kPackBytes / 4 &&
-                     in_elems * 8 <= kPackBytes / 2;
-        if (out_direct) {
+        k.out_direct = k.out && out_elems && !k.post && c->h_pack && out_elems * 8 <= kPackBytes / 4 &&
+                       in_elems * 8 <= kPackBytes / 2;
+        if (k.out_direct) {
             a.out = c->h_pack_dev + kPackBytes / 16;           // doubles: byte offset kPackBytes / 2
-            if (covered < out_rows) std::memset(c->h_pack + kPackBytes / 16, 0xFF, out_elems * 8);
-            covered = out_rows;                                // (no device-side fill)
+            if (covered < pl.out_rows) std::memset(c->h_pack + kPackBytes / 16, 0xFF, out_elems * 8);
+            covered = pl.out_rows;                             // (no device-side fill)
         }
-        if (covered < out_rows && out_elems) HIP_TRY(hipMemsetAsync(d_out, 0xFF, out_elems * 8, c->stream));
+        if (covered < pl.out_rows && out_elems) HIP_TRY(hipMemsetAsync(d_out, 0xFF, out_elems * 8, c->stream));
         a.prof_stride = n_alt;
-        a.field_stride = shared_field ? 0 : n_alt;
-        a.alt_stride = alt_stride ? n_alt : 0;
+        a.field_stride = k.shared_field ? 0 : n_alt;
+        a.alt_stride = k.alt_stride ? n_alt : 0;
     }
 
-    double* vh_dev = a.out;
-    if (dev && post && !out) {                 // caller does not want the modeled trace: keep it in scratch
+    k.vh_dev = a.out;
+    if (k.dev && k.post && !k.out) {           // caller does not want the modeled trace: keep it in scratch
         if ((rc = ensure(c, c->arena, out_elems * 8)) != PRHF_OK) return rc;
-        vh_dev = a.out = static_cast<double*>(c->arena.p);
+        k.vh_dev = a.out = static_cast<double*>(c->arena.p);
     }
-    const double* d_obs = post ? post->vh_obs : nullptr;
-    double* d_res = post ? post->residual : nullptr;
-    double* d_cost = post ? post->cost : nullptr;
-    if (post && !dev) {
-        double* p0 = d_out + out_elems;
-        HIP_TRY(hipMemcpyAsync(p0, post->vh_obs, (size_t)n_freq * 8, hipMemcpyHostToDevice, c->stream));
-        d_obs = p0;
-        d_res = post->residual ? p0 + n_freq : nullptr;
-        d_cost = post->cost ? p0 + n_freq + out_elems : nullptr;
+    k.d_obs = k.post ? k.post->vh_obs : nullptr;
+    k.d_res = k.post ? k.post->residual : nullptr;
+    k.d_cost = k.post ? k.post->cost : nullptr;
+    if (k.post && !k.dev) {
+        double* p0 = k.d_out + out_elems;
+        HIP_TRY(hipMemcpyAsync(p0, k.post->vh_obs, (size_t)n_freq * 8, hipMemcpyHostToDevice, c->stream));
+        k.d_obs = p0;
+        k.d_res = k.post->residual ? p0 + n_freq : nullptr;
+        k.d_cost = k.post->cost ? p0 + n_freq + out_elems : nullptr;
     }
+    return PRHF_OK;
+}
+
+// The pair table of the main loop with the strided table's pieces behind it (option strided_top), into
+// `table`: the context's own, or the one cached with a stable host grid
+int build_pair_table(prhf_ctx* c, DevBuf& table, const double* d_mult, int64_t mult_len, const LaunchPlan& pl) {
+    int rc;
+    if ((rc = ensure(c, table, (size_t)pl.table_entries * 16)) != PRHF_OK) return rc;
+    HIP_TRY(prhf::launch_grid_pairs(d_mult, mult_len, static_cast<double*>(table.p), c->stream));
+    HIP_TRY(prhf::launch_grid_strided(d_mult, static_cast<double*>(table.p), pl.pieces, c->stream));
+    return PRHF_OK;
+}
+
+// The tables the plan asks for: the pair table - built with the strided pieces and cached with them; a cached table
+// serves a launch whose pieces are the same - and the per-frequency table.
+int update_tables(Call& k, const LaunchPlan& pl, prhf::KArgs& a) {
+    prhf_ctx* c = k.c;
+    if (!pl.want_pairs) return PRHF_OK;
+    int rc;
+    auto same_pieces = [&](const prhf::StridedPieces& o) { return std::memcmp(&o, &pl.pieces, sizeof pl.pieces) == 0; };
+    if (k.grid) {
+        if (!k.grid->pairs_ready || !same_pieces(k.grid->pieces)) {
+            if ((rc = build_pair_table(c, k.grid->pairs, a.mult, k.mult_len, pl)) != PRHF_OK) return rc;
+            k.grid->pairs_ready = true;
+            k.grid->pieces = pl.pieces;
+        }
+        a.pairs = static_cast<const double*>(k.grid->pairs.p);
+    } else {
+        const bool stable = k.dev && (k.flags & PRHF_FLAG_GRID_STABLE) != 0;
+        if (!(stable && c->pairs.p && c->pairs_src == a.mult && c->pairs_len == k.mult_len && same_pieces(c->pairs_pieces))) {
+            c->pairs_src = nullptr;
+            if ((rc = build_pair_table(c, c->pairs, a.mult, k.mult_len, pl)) != PRHF_OK) return rc;
+            if (stable) {
+                c->pairs_src = a.mult;
+                c->pairs_len = k.mult_len;
+                c->pairs_pieces = pl.pieces;
+            }
+        }
+        a.pairs = static_cast<const double*>(c->pairs.p);
+    }
+    if (!pl.freq_table) return PRHF_OK;
+    if ((rc = ensure(c, c->ftab, ((size_t)k.n_freq + 1) * 64)) != PRHF_OK) return rc;
+    // The table's kernel zeroes, on the way, every control word the launches behind it count in: the block
+    // queues and the heads of the short-grid kernels' lists and the classes of the block order.  One memset each,
+    // they were six operations on the stream in front of a short-grid launch (config 3: ~25 us of 530).
+    prhf::ZeroWords zero;
+    std::memset(&zero, 0, sizeof zero);
+    auto zero_head = [&](DevBuf& b, size_t bytes) -> int {
+        int rcz = ensure(c, b, bytes);
+        if (rcz != PRHF_OK) return rcz;
+        zero.p[zero.n] = static_cast<unsigned*>(b.p);
+        zero.words[zero.n++] = 1;
+        return PRHF_OK;
+    };
+    zero.p[zero.n] = c->d_status;
+    zero.words[zero.n++] = kStatusWords;
+    if (pl.o.blocks > 0) {
+        if ((rc = zero_head(c->leftover, pl.o.list_bytes)) != PRHF_OK) return rc;
+        if ((rc = zero_head(c->leftover_tall, pl.o.list_bytes)) != PRHF_OK) return rc;
+    }
+    if (pl.x.blocks > 0) {
+        if ((rc = zero_head(c->leftover_x, pl.x.list_bytes)) != PRHF_OK) return rc;
+        if ((rc = zero_head(c->leftover_tall_x, pl.x.list_bytes)) != PRHF_OK) return rc;
+    }
+    if (pl.short_order) {
+        const size_t words = PRHF_ORDER_CLASSES * (size_t)(pl.o.blocks + 1);
+        const void* before = c->order.p;
+        if ((rc = ensure(c, c->order, words * sizeof(unsigned))) != PRHF_OK) return rc;
+        unsigned* order = static_cast<unsigned*>(c->order.p);
+        if (!c->order_clean || c->order.p != before)
+            HIP_TRY(hipMemsetAsync(order, 0, PRHF_ORDER_CLASSES * sizeof(unsigned), c->stream));
+        prhf::KArgs ap = a;
+        ap.n_segs = pl.o.n_segs;
+        ap.n_blocks = pl.o.blocks;
+        std::copy(pl.o.seg, pl.o.seg + pl.o.n_segs, ap.seg);
+        c->order_clean = false;                // (until the follow-up kernel of this launch has run)
+        HIP_TRY(prhf::launch_short_order(ap, order, a.freq, static_cast<double*>(c->ftab.p), zero, c->stream));
+        k.order_made = order;
+    } else {
+        HIP_TRY(prhf::launch_freq_table(a.freq, k.n_freq, static_cast<double*>(c->ftab.p), zero, c->stream));
+    }
+    a.ftab = static_cast<const double*>(c->ftab.p);
+    return PRHF_OK;
+}
+
+// The launches' block queues (StatusWord), where the per-frequency table's kernel has not zeroed them already.  A launch
+// without a queue - the single profile - enqueues nothing.
+int zero_control_words(prhf_ctx* c, const LaunchPlan& pl) {
+    if (!pl.zero_queues) return PRHF_OK;
+    HIP_TRY(hipMemsetAsync(c->d_status, 0, kLaunchQueueWords * sizeof(unsigned), c->stream));
+    if (pl.x.n_segs > 0) HIP_TRY(hipMemsetAsync(c->d_status + kWordShortXFull, 0, sizeof(unsigned), c->stream));
+    return PRHF_OK;
+}
+
+int launch_general(prhf_ctx* c, const LaunchPlan& pl, prhf::KArgs& a) {
+    if (pl.queue) a.queue = c->d_status + kWordGeneral;
+    if (pl.tall) HIP_TRY(prhf::launch_vfo_tall(a, pl.grid, c->stream));
+    else HIP_TRY(prhf::launch_vfo(a, pl.grid, pl.launch_tier, pl.lds_bytes, c->stream));
+    return PRHF_OK;
+}
+
+// What tells the two short-grid kinds apart when they are launched: their control words, their lists, the tier of the
+// follow-up launch
+struct ShortRoute {
+    StatusWord first, full, follow;
+    DevBuf *left, *left_tall;
+    int follow_tier;
+    unsigned* order;            // O mode: the blocks by cost class (or null)
+    bool traced;                // -DPRHF_TRACE builds: this kind's waves are stamped
+};
+
+// One kind of short-grid slices (ShortKind): the short-grid kernel, where the plan says so a second launch of it with
+// full-size arrays over the profiles the compact one left, and the general kernel over the profiles both left on their
+// list.  launch(args, geometry) starts the kind's kernel.
+template <class Launch>
+int launch_short_kind(prhf_ctx* c, const LaunchPlan& pl, const ShortKind& sk, const ShortRoute& r, const prhf::KArgs& a,
+                      hipStream_t stream, Launch launch) {
+    if (sk.blocks == 0) return PRHF_OK;
+    prhf::KArgs as = a;
+    as.n_segs = sk.n_segs;
+    std::copy(sk.seg, sk.seg + sk.n_segs, as.seg);
+    as.n_blocks = sk.blocks;
+    as.short_prio = (int)c->knobs.short_prio;
+    as.partial = nullptr;
+    as.altmin = nullptr;
+    as.trace = nullptr;
+    int rc;
+#ifdef PRHF_TRACE
+    static DevBuf trace_short;
+    const size_t short_trace_words = (size_t)sk.blocks * kWavesPerBlock * 8;
+    unsigned long long* trace = nullptr;
+    if (std::getenv("PRHF_TRACE_FILE") && r.traced) {
+        if ((rc = ensure(c, trace_short, short_trace_words * 8)) != PRHF_OK) return rc;
+        HIP_TRY(hipMemsetAsync(trace_short.p, 0, short_trace_words * 8, stream));
+        as.trace = trace = static_cast<unsigned long long*>(trace_short.p);
+    }
+#endif
+    // the list heads: zeroed by the per-frequency table's kernel where there is one
+    if ((rc = ensure(c, *r.left, sk.list_bytes)) != PRHF_OK) return rc;
+    as.leftover = static_cast<unsigned*>(r.left->p);
+    if (!pl.freq_table) HIP_TRY(hipMemsetAsync(as.leftover, 0, sizeof(unsigned), stream));
+    if (sk.second) {
+        // a profile that peaks above the compact arrays goes on a block list of its own
+        if ((rc = ensure(c, *r.left_tall, sk.list_bytes)) != PRHF_OK) return rc;
+        as.leftover_tall = static_cast<unsigned*>(r.left_tall->p);
+        if (!pl.freq_table) HIP_TRY(hipMemsetAsync(as.leftover_tall, 0, sizeof(unsigned), stream));
+    }
+    as.lds_levels = sk.first.lds_levels;
+    as.short_queue = sk.first.short_queue;
+    as.queue = sk.first.queue ? c->d_status + r.first : nullptr;
+    // from four resident rounds on, the blocks are drawn in descending order of a cost estimate
+    as.order = r.order;                        // (sorted beside the per-frequency table, or null: index order)
+    if ((rc = launch(as, sk.first)) != PRHF_OK) return rc;
+    if (sk.second) {
+        // the profiles the compact launch left for full-size arrays: persistent workgroups read their number from
+        // the device (3 us when there is none); what these leave - another input shape - joins the general list
+        as.trace = nullptr;
+        as.lds_levels = sk.full.lds_levels;
+        as.short_queue = sk.full.short_queue;
+        as.block_list = as.leftover_tall;
+        as.order = nullptr;
+        as.leftover_tall = nullptr;
+        as.queue = c->d_status + r.full;
+        if ((rc = launch(as, sk.full)) != PRHF_OK) return rc;
+    }
+#ifdef PRHF_TRACE
+    if (trace) {                                   // eight wall-clock marks per wave and block (tools/wave_trace_short.py)
+        std::vector<unsigned long long> host(short_trace_words);
+        HIP_TRY(hipMemcpyAsync(host.data(), trace, short_trace_words * 8, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        if (FILE* fp = std::fopen(std::getenv("PRHF_TRACE_FILE"), "wb")) {
+            std::fwrite(host.data(), 8, short_trace_words, fp);
+            std::fclose(fp);
+        }
+    }
+#endif
+    // the follow-up: the general kernel over the blocks on the list
+    as.trace = nullptr;
+    as.lds_levels = a.lds_levels;
+    as.short_queue = sk.first.short_queue;
+    as.leftover_tall = nullptr;
+    as.order = nullptr;
+    as.block_list = as.leftover;
+    as.leftover = nullptr;
+    as.queue = c->d_status + r.follow;
+    as.zero_after = r.order;
+    HIP_TRY(prhf::launch_vfo(as, sk.follow_grid, r.follow_tier, pl.lds_bytes, stream));
+    if (as.zero_after) c->order_clean = true;
+    return PRHF_OK;
+}
+
+// Every kernel of the operator, in the order and on the streams the plan sets
+int launch_all(Call& k, const LaunchPlan& pl, prhf::KArgs& a) {
+    prhf_ctx* c = k.c;
+    int rc;
+    hipStream_t short_stream = pl.forked ? c->aux_stream : c->stream;
+    // Fork and join by events: the general launch goes first, on the caller's stream (LaunchPlan::forked)
+    if (pl.forked) {
+        HIP_TRY(hipEventRecord(c->fork_ev, c->stream));        // tables, queues and inputs are in place
+        HIP_TRY(hipStreamWaitEvent(c->aux_stream, c->fork_ev, 0));
+        if ((rc = launch_general(c, pl, a)) != PRHF_OK) return rc;
+    }
+    const ShortRoute route_x = {kWordShortX, kWordShortXFull, kWordShortXFollow, &c->leftover_x, &c->leftover_tall_x, 1, nullptr, false};
+    const ShortRoute route_o = {kWordShortO, kWordShortOFull, kWordShortOFollow, &c->leftover, &c->leftover_tall, 0, k.order_made, true};
+    rc = launch_short_kind(c, pl, pl.x, route_x, a, short_stream, [&](const prhf::KArgs& as, const ShortLaunch& l) -> int {   // (the longer blocks first)
+        HIP_TRY(prhf::launch_vfo_shortx(as, l.grid, l.lds_bytes, l.threads, short_stream));
+        return PRHF_OK;
+    });
+    if (rc != PRHF_OK) return rc;
+    rc = launch_short_kind(c, pl, pl.o, route_o, a, short_stream, [&](const prhf::KArgs& as, const ShortLaunch& l) -> int {
+        HIP_TRY(prhf::launch_vfo_short(as, l.grid, l.lds_bytes, l.threads, pl.o.lanes, short_stream));
+        return PRHF_OK;
+    });
+    if (rc != PRHF_OK) return rc;
+    if (pl.forked) {
+        HIP_TRY(hipEventRecord(c->join_ev, c->aux_stream));
+        HIP_TRY(hipStreamWaitEvent(c->stream, c->join_ev, 0));
+        return PRHF_OK;
+    }
+    return launch_general(c, pl, a);
+}
+
+// The results of a host-buffer call on their way back, and the synchronisation of every call that is not asynchronous
+int download_and_sync(Call& k) {
+    prhf_ctx* c = k.c;
+    const size_t out_elems = k.out_elems;
+    // small results come back through the pinned buffer too (its upper half; the inputs of a call this small
+    // fit the lower one) and are handed over after the synchronisation below
+    const bool out_via_pack = !k.out_direct && !k.dev && k.out && out_elems && c->h_pack && out_elems * 8 <= kPackBytes / 4 &&
+                              k.in_elems * 8 <= kPackBytes / 2;
+    double* h_out = c->h_pack ? c->h_pack + kPackBytes / 16 : nullptr;       // doubles: byte offset kPackBytes / 2
+    if (k.out_direct) {
+        // (written by the kernel itself)
+    } else if (out_via_pack)
+        HIP_TRY(hipMemcpyAsync(h_out, k.d_out, out_elems * 8, hipMemcpyDeviceToHost, c->stream));
+    else if (!k.dev && out_elems && k.out)
+        HIP_TRY(hipMemcpyAsync(k.out, k.d_out, out_elems * 8, hipMemcpyDeviceToHost, c->stream));
+    if (!k.dev && k.post) {
+        if (k.post->residual)
+            HIP_TRY(hipMemcpyAsync(k.post->residual, k.d_res, out_elems * 8, hipMemcpyDeviceToHost, c->stream));
+        if (k.post->cost)
+            HIP_TRY(hipMemcpyAsync(k.post->cost, k.d_cost, (size_t)k.n_prof * 8, hipMemcpyDeviceToHost, c->stream));
+    }
+    if (k.flags & PRHF_FLAG_ASYNC) return PRHF_OK;
+    const int rc = prhf_sync(c);
+    if (out_via_pack || k.out_direct) std::memcpy(k.out, h_out, out_elems * 8);
+    return rc;
+}
+
+// Every prhf_vfo_* call: check, decide where the profiles are staged, plan (plan_launch, prhf_plan.h), then carry the
+// plan out step by step.  The steps above enqueue on the context's stream in the order they are called here.
+int run(prhf_ctx* c, const double* freq, int64_t n_freq, const double* den, const double* bmag,
+        const double* bpsi, const double* alt, int64_t n_prof, int64_t n_alt, int64_t prof_stride,
+        int64_t alt_stride, const double* mult, int64_t mult_len, const prhf_segment* segs, int32_t n_segs,
+        double* out, uint32_t flags, const Residual* post = nullptr) {
+    Call k = {c, freq, den, bmag, bpsi, alt, mult, n_freq, n_prof, n_alt, prof_stride, alt_stride, mult_len, segs, n_segs,
+              out, flags, post, (flags & PRHF_FLAG_DEVICE_PTRS) != 0, (flags & PRHF_FLAG_SHARED_FIELD) != 0};
+    int rc;
+    if ((rc = check_arguments(k)) != PRHF_OK) return rc;
+    ENTER_DEVICE(c->device);
+    bool tall;
+    long long lds_levels;
+    if ((rc = decide_tall(k, tall, lds_levels)) != PRHF_OK) return rc;
+
+    const LaunchShape shape = {n_prof, n_freq, n_alt, lds_levels, tall, mult_len, c->cu_count, c->math};
+    LaunchPlan pl;
+    char why[160];
+    if (plan_launch(shape, segs, n_segs, c->knobs, pl, why, sizeof why) != PRHF_OK) return fail(PRHF_EINVAL, "%s", why);
+
+    prhf::KArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.n_freq = n_freq;
+    a.n_alt = n_alt;
+    a.lds_levels = lds_levels;
+    a.n_segs = pl.n_segs;
+    std::copy(pl.seg, pl.seg + pl.n_segs, a.seg);
+    a.n_blocks = pl.blocks;
+    a.no_candidates = pl.no_candidates;
+    a.plan_counters = c->d_plan_counters;
+    a.plan_cap = (int)c->knobs.pair_plan_cap;
+    if ((rc = stage_inputs(k, pl, a)) != PRHF_OK) return rc;
 
     // (a synchronous host-buffer call may go untimed - option `timing`: nothing is left on the stream when it returns,
     //  so no later launch or stream switch needs its end event either)
-    const bool timed_launch = dev || kn.timing != 0;
+    const bool timed_launch = k.dev || c->knobs.timing != 0;
     if (timed_launch) HIP_TRY(hipEventRecord(c->begin_ev(), c->stream));
-    bool zeroed_by_table = false;              // the control words below were zeroed by the per-frequency table's kernel
-    unsigned* order_made = nullptr;            // ... which also sorted the short-grid O launch's blocks by cost (short_order_kernel)
-    // resident workgroups of the short-grid O launch (launch_short_kind sizes it the same way)
-    auto short_o_slots = [&]() -> long long {
-        const bool compact = compact_levels > 0;
-        const int threads = compact ? PRHF_COMPACT_THREADS : PRHF_SHORT_THREADS;
-        const size_t lds = prhf::short_lds_fixed(compact ? compact_levels : lds_levels, n_freq, threads) +
-                           8 * (size_t)(compact ? compact_queue : short_queue);
-        return (long long)c->cu_count * (compact ? PRHF_COMPACT_WGS_PER_CU : (lds <= lds_half ? 2 : 1));
-    };
-    // The strided table (option strided_top): one piece behind the pair table for every distinct grid of
-    // the X-mode fast-tier slices that take whole pairs of at least PRHF_TOP3_MIN_POINTS points through the main loop.
-    // Built with the pair table and cached with it; a cached table serves a launch whose pieces are the same.
-    prhf::StridedPieces pieces;
-    std::memset(&pieces, 0, sizeof pieces);
-    long long table_entries = mult_len + PRHF_PAIR_PAD;
-    bool any_plan = false;                     // a slice takes the planning pass: it needs the candidate list
-    if (want_pairs && kn.strided_top != 0 && !tall) {
-        for (int i = 0; i < n_segs; ++i) {
-            prhf::SegDev& s = a.seg[i];
-            if (!(s.lean && s.tier == 1 && s.mode == PRHF_KMODE_X && s.chunks == 1 && s.n_points >= PRHF_TOP3_MIN_POINTS)) continue;
-            int p = 0;
-            while (p < pieces.n && !(pieces.mult_off[p] == s.mult_off && pieces.n_points[p] == s.n_points)) ++p;
-            if (p == pieces.n) {
-                const long long len = prhf::strided_piece_entries(s.n_points);
-                // (the main loop addresses the table through a 31-bit byte offset)
-                if ((table_entries + len) * 16 >= 0x7fffffffLL) continue;
-                pieces.mult_off[p] = s.mult_off;
-                pieces.n_points[p] = s.n_points;
-                pieces.sp_off[p] = table_entries;
-                table_entries += len;
-                ++pieces.n;
-            }
-            s.sp_off = pieces.sp_off[p];
-            s.strided_lower = kn.strided_lower != 0;
-            s.panel_lower = s.strided_lower && kn.panel_lower != 0;
-            s.pair_plan = slice_plans_pairs(s, tall, n_freq, lds_levels, kn) ? 1 : 0;
-            any_plan = any_plan || s.pair_plan != 0;
-        }
-    }
-    a.plan_counters = c->d_plan_counters;
-    a.plan_cap = (int)kn.pair_plan_cap;
-    auto same_pieces = [&](const prhf::StridedPieces& o) { return std::memcmp(&o, &pieces, sizeof pieces) == 0; };
-    if (want_pairs && grid) {
-        if (!grid->pairs_ready || !same_pieces(grid->pieces)) {
-            if ((rc = ensure(c, grid->pairs, (size_t)table_entries * 16)) != PRHF_OK) return rc;
-            HIP_TRY(prhf::launch_grid_pairs(a.mult, mult_len, static_cast<double*>(grid->pairs.p), c->stream));
-            HIP_TRY(prhf::launch_grid_strided(a.mult, static_cast<double*>(grid->pairs.p), pieces, c->stream));
-            grid->pairs_ready = true;
-            grid->pieces = pieces;
-        }
-        a.pairs = static_cast<const double*>(grid->pairs.p);
-    }
-    if (want_pairs) {
-        const bool stable = dev && (flags & PRHF_FLAG_GRID_STABLE) != 0;
-        if (grid) {
-            // (table cached with the grid, above)
-        } else if (!(stable && c->pairs.p && c->pairs_src == a.mult && c->pairs_len == mult_len && same_pieces(c->pairs_pieces))) {
-            c->pairs_src = nullptr;
-            if ((rc = ensure(c, c->pairs, (size_t)table_entries * 16)) != PRHF_OK) return rc;
-            HIP_TRY(prhf::launch_grid_pairs(a.mult, mult_len, static_cast<double*>(c->pairs.p), c->stream));
-            HIP_TRY(prhf::launch_grid_strided(a.mult, static_cast<double*>(c->pairs.p), pieces, c->stream));
-            if (stable) {
-                c->pairs_src = a.mult;
-                c->pairs_len = mult_len;
-                c->pairs_pieces = pieces;
-            }
-        }
-        if (!grid) a.pairs = static_cast<const double*>(c->pairs.p);
-        // per-frequency scalars: long launches read them from a table instead of dividing once per pair (a short
-        // launch - one profile - is latency bound: it does without the extra kernel)
-        // (... and so does a launch with a slice that plans its pairs: the heights that pass starts from are settled with
-        //  the candidate list, which reads the table.  By default such a slice has 4096 pairs anyway - fewer are chunked)
-        if (n_prof * n_freq >= 4096 || any_plan) {
-            if ((rc = ensure(c, c->ftab, ((size_t)n_freq + 1) * 64)) != PRHF_OK) return rc;
-            // The table's kernel zeroes, on the way, every control word the launches behind it count in: the block
-            // queues and - their buffers sized here, as launch_short_kind sizes them again - the heads of the short-grid
-            // kernels' lists and the classes of the block order.  One memset each, they were six operations on the stream
-            // in front of a short-grid launch (config 3: ~25 us of 530).
-            prhf::ZeroWords zero;
-            std::memset(&zero, 0, sizeof zero);
-            auto zero_head = [&](DevBuf& b, size_t bytes, int words) -> int {
-                int rcz = ensure(c, b, bytes);
-                if (rcz != PRHF_OK) return rcz;
-                zero.p[zero.n] = static_cast<unsigned*>(b.p);
-                zero.words[zero.n++] = words;
-                return PRHF_OK;
-            };
-            zero.p[zero.n] = c->d_status;
-            zero.words[zero.n++] = kStatusWords;
-            long long o_blocks = 0;
-            for (int xmode = 0; xmode < 2; ++xmode) {
-                long long kind_blocks = 0;
-                for (int i = 0; i < (xmode ? n_shortx : n_short); ++i)
-                    kind_blocks += (xmode ? shortx_seg : short_seg)[i].prof_end - (xmode ? shortx_seg : short_seg)[i].prof_begin;
-                if (kind_blocks == 0 || kind_blocks > 0x7fffffffLL) continue;
-                if (!xmode) o_blocks = kind_blocks;
-                const size_t list_bytes = (size_t)(kind_blocks + 1) * sizeof(unsigned);
-                if ((rc = zero_head(xmode ? c->leftover_x : c->leftover, list_bytes, 1)) != PRHF_OK) return rc;
-                if ((rc = zero_head(xmode ? c->leftover_tall_x : c->leftover_tall, list_bytes, 1)) != PRHF_OK) return rc;
-            }
-            // A short-grid O launch of four resident rounds and more draws its blocks in descending order of a cost
-            // estimate: the kernel that sorts them makes the table as well (short_order_kernel)
-            if (o_blocks > 0 && kn.short_order != 0 && o_blocks >= 4 * short_o_slots()) {
-                const size_t words = PRHF_ORDER_CLASSES * (size_t)(o_blocks + 1);
-                const void* before = c->order.p;
-                if ((rc = ensure(c, c->order, words * sizeof(unsigned))) != PRHF_OK) return rc;
-                unsigned* order = static_cast<unsigned*>(c->order.p);
-                if (!c->order_clean || c->order.p != before)
-                    HIP_TRY(hipMemsetAsync(order, 0, PRHF_ORDER_CLASSES * sizeof(unsigned), c->stream));
-                prhf::KArgs ap = a;
-                ap.n_segs = n_short;
-                ap.n_blocks = 0;
-                for (int i = 0; i < n_short; ++i) {
-                    ap.seg[i] = short_seg[i];
-                    ap.seg[i].block_begin = ap.n_blocks;
-                    ap.n_blocks += short_seg[i].prof_end - short_seg[i].prof_begin;
-                }
-                c->order_clean = false;                // (until the follow-up kernel of this launch has run)
-                HIP_TRY(prhf::launch_short_order(ap, order, a.freq, static_cast<double*>(c->ftab.p), zero, c->stream));
-                order_made = order;
-            } else {
-                HIP_TRY(prhf::launch_freq_table(a.freq, n_freq, static_cast<double*>(c->ftab.p), zero, c->stream));
-            }
-            a.ftab = static_cast<const double*>(c->ftab.p);
-            zeroed_by_table = true;
-        }
-    }
+    if ((rc = update_tables(k, pl, a)) != PRHF_OK) return rc;
 #ifdef PRHF_TRACE
     // diagnostics build (tools/wave_trace.py): per-wave wall-clock stamps of this launch, dumped to $PRHF_TRACE_FILE
     static DevBuf trace_buf;
-    const size_t trace_words = (size_t)blocks * kWavesPerBlock * 6;   // start, end, staged, and three staging marks
-    if (std::getenv("PRHF_TRACE_FILE") && blocks > 0) {
+    const size_t trace_words = (size_t)pl.blocks * kWavesPerBlock * 6;   // start, end, staged, and three staging marks
+    if (std::getenv("PRHF_TRACE_FILE") && pl.blocks > 0) {
         if ((rc = ensure(c, trace_buf, trace_words * 8)) != PRHF_OK) return rc;
         HIP_TRY(hipMemsetAsync(trace_buf.p, 0, trace_words * 8, c->stream));
         a.trace = static_cast<unsigned long long*>(trace_buf.p);
     }
 #endif
-    a.n_blocks = blocks;
-    a.no_candidates = kNoCandidates || tall;
-    if (tall && blocks > 0) {
-        a.tall_stride = prhf::tall_slab_bytes(n_alt);
-        if ((rc = ensure(c, c->tall, (size_t)std::min(blocks, wg_slots) * a.tall_stride)) != PRHF_OK) return rc;
+    if (pl.tall_stride) {                      // a tall launch: one slab of staged levels per resident workgroup
+        a.tall_stride = pl.tall_stride;
+        if ((rc = ensure(c, c->tall, (size_t)pl.tall_slabs * a.tall_stride)) != PRHF_OK) return rc;
         a.tall = static_cast<unsigned char*>(c->tall.p);
     }
-    // the launches' block queues: words 0 - 5, and word 8 for the second launch of the X-mode short grids (words 6 and 7
-    // belong to the tracers and the peak pre-pass).  A launch without a queue - the single profile - enqueues neither.
-    if (!zeroed_by_table && (n_short > 0 || n_shortx > 0 || ((kPersistent || tall) && blocks > wg_slots))) {
-        HIP_TRY(hipMemsetAsync(c->d_status, 0, 6 * sizeof(unsigned), c->stream));
-        if (n_shortx > 0) HIP_TRY(hipMemsetAsync(c->d_status + 8, 0, sizeof(unsigned), c->stream));
-    }
-    // A list with both kinds of slices: the general launch goes first, on the caller's stream, and takes every
-    // workgroup slot; the short-grid launch runs on a second stream and its workgroups move in as the general
-    // launch's persistent workgroups leave - its 30 - 100 us blocks fill the end of the launch, which otherwise drains
-    // on a few long blocks.  (One after the other on one stream the config-5 shard took 8.04 ms, general kernel alone
-    // 7.94 ms.)  Fork and join by events; a launch of one kind stays on the caller's stream.
-    auto launch_general = [&]() -> int {
-        long long grid_blocks = blocks;
-        if ((kPersistent || tall) && blocks > wg_slots) {    // persistent workgroups pulling blocks from a queue (vfo_kernel)
-            a.queue = c->d_status + 1;
-            grid_blocks = wg_slots;
-        }
-        if (tall) HIP_TRY(prhf::launch_vfo_tall(a, grid_blocks, c->stream));
-        else HIP_TRY(prhf::launch_vfo(a, grid_blocks, launch_tier, prhf::lds_bytes_for(lds_levels), c->stream));
-        return PRHF_OK;
-    };
-    const bool any_short = n_short > 0 || n_shortx > 0;
-    const bool forked = any_short && blocks > 0 && kShortConcurrent;
-    hipStream_t short_stream = forked ? c->aux_stream : c->stream;
-    if (forked) {
-        HIP_TRY(hipEventRecord(c->fork_ev, c->stream));        // tables, queues and inputs are in place
-        HIP_TRY(hipStreamWaitEvent(c->aux_stream, c->fork_ev, 0));
-        if ((rc = launch_general()) != PRHF_OK) return rc;
-    }
-    // Short grids: vfo_short_kernel (O mode) / vfo_shortx_kernel (X mode), each followed by the general kernel over the
-    // profiles it left on its list (non-uniform altitude grid, fast-turning or vanishing field, negative density,
-    // peak at level 0 or 1, a sum that is not finite)
-    auto launch_short_kind = [&](bool xmode) -> int {
-        const int n_kind = xmode ? n_shortx : n_short;
-        if (n_kind == 0) return PRHF_OK;
-        prhf::SegDev* kind_seg = xmode ? shortx_seg : short_seg;
-        prhf::KArgs as = a;
-        as.n_segs = n_kind;
-        long long short_blocks = 0;
-        for (int i = 0; i < n_kind; ++i) {
-            kind_seg[i].block_begin = short_blocks;
-            short_blocks += kind_seg[i].prof_end - kind_seg[i].prof_begin;
-            as.seg[i] = kind_seg[i];
-        }
-        if (short_blocks > 0x7fffffffLL) return fail(PRHF_EINVAL, "launch too large");
-        if (short_blocks == 0) return PRHF_OK;
-        as.n_blocks = short_blocks;
-        as.short_queue = 0;                        // (set with the geometry below)
-        as.short_prio = (int)kn.short_prio;
-        as.partial = nullptr;
-        as.altmin = nullptr;
-        as.trace = nullptr;
-        as.queue = nullptr;
-#ifdef PRHF_TRACE
-        static DevBuf trace_short;
-        const size_t short_trace_words = (size_t)short_blocks * kWavesPerBlock * 8;
-        if (std::getenv("PRHF_TRACE_FILE") && !xmode) {
-            int rct;
-            if ((rct = ensure(c, trace_short, short_trace_words * 8)) != PRHF_OK) return rct;
-            HIP_TRY(hipMemsetAsync(trace_short.p, 0, short_trace_words * 8, short_stream));
-            as.trace = static_cast<unsigned long long*>(trace_short.p);
-        }
-#endif
-        DevBuf& left = xmode ? c->leftover_x : c->leftover;
-        int rcl;
-        if ((rcl = ensure(c, left, (size_t)(short_blocks + 1) * sizeof(unsigned))) != PRHF_OK) return rcl;
-        as.leftover = static_cast<unsigned*>(left.p);
-        if (!zeroed_by_table) HIP_TRY(hipMemsetAsync(as.leftover, 0, sizeof(unsigned), short_stream));
-        if (xmode) {
-            // the compact geometry of the O kernel (four 4-wave workgroups per CU, staged arrays for as many levels as a
-            // quarter of the LDS holds), taken on the same condition; a profile that peaks above them goes on a block
-            // list of its own, which a second launch of this kernel with full-size arrays takes (a2 below, queue word 8)
-            long long Lx = 0;
-            if (kn.short_compact != 0) {
-                long long L = lds_levels;
-                while (L > 1 && prhf::shortx_lds_bytes(L, n_freq) > lds_quarter) --L;
-                if (2 * L >= lds_levels && L >= 8 && prhf::shortx_lds_bytes(L, n_freq) <= lds_quarter) Lx = L;
-            }
-            const int threads = Lx > 0 ? PRHF_COMPACT_THREADS : PRHF_SHORT_THREADS;
-            const bool second_x = Lx > 0 && Lx < lds_levels;      // some bottomsides may not fit the compact arrays
-            if (Lx > 0) as.lds_levels = Lx;
-            if (second_x) {
-                if ((rcl = ensure(c, c->leftover_tall_x, (size_t)(short_blocks + 1) * sizeof(unsigned))) != PRHF_OK) return rcl;
-                as.leftover_tall = static_cast<unsigned*>(c->leftover_tall_x.p);
-                if (!zeroed_by_table) HIP_TRY(hipMemsetAsync(as.leftover_tall, 0, sizeof(unsigned), short_stream));
-            }
-            const size_t lds = prhf::shortx_lds_bytes(as.lds_levels, n_freq);
-            const long long short_slots = (long long)c->cu_count * (Lx > 0 ? PRHF_COMPACT_WGS_PER_CU : (lds <= lds_half ? 2 : 1));
-            long long grid_short = short_blocks;
-            if (short_blocks > short_slots) {
-                as.queue = c->d_status + 4;
-                grid_short = short_slots;
-            }
-            HIP_TRY(prhf::launch_vfo_shortx(as, grid_short, lds, threads, short_stream));
-            if (second_x) {
-                // the profiles the compact launch left for full-size arrays: persistent workgroups read their number from
-                // the device; what these leave - another input shape - joins the general list
-                prhf::KArgs a2 = as;
-                a2.lds_levels = lds_levels;
-                a2.block_list = as.leftover_tall;
-                a2.leftover_tall = nullptr;
-                a2.queue = c->d_status + 8;
-                const size_t lds2 = prhf::shortx_lds_bytes(lds_levels, n_freq);
-                const long long slots2 = (long long)c->cu_count * (lds2 <= lds_half ? 2 : 1);
-                HIP_TRY(prhf::launch_vfo_shortx(a2, std::min(short_blocks, slots2), lds2, PRHF_SHORT_THREADS, short_stream));
-            }
-        } else {
-            const bool compact = compact_levels > 0;
-            const bool second = compact && compact_levels < lds_levels;    // some bottomsides may not fit the compact arrays
-            const int fixed_q = kShortQueueFixed > 0 ? -std::min(kShortQueueFixed, compact ? compact_queue : short_queue) : 0;
-            if (second) {
-                if ((rcl = ensure(c, c->leftover_tall, (size_t)(short_blocks + 1) * sizeof(unsigned))) != PRHF_OK) return rcl;
-                as.leftover_tall = static_cast<unsigned*>(c->leftover_tall.p);
-                if (!zeroed_by_table) HIP_TRY(hipMemsetAsync(as.leftover_tall, 0, sizeof(unsigned), short_stream));
-            }
-            const int threads = compact ? PRHF_COMPACT_THREADS : PRHF_SHORT_THREADS;
-            // lanes per pair: eight on grids of up to 256 points (the launch's longest), sixteen beyond (Knobs::short_lanes)
-            int longest = 0;
-            for (int i = 0; i < n_kind; ++i) longest = std::max(longest, kind_seg[i].n_points);
-            const int short_lanes = kn.short_lanes == 0 ? (longest <= 256 ? 8 : 16) : (kn.short_lanes < 12 ? 8 : 16);
-            const int queue_entries = compact ? compact_queue : short_queue;
-            as.lds_levels = compact ? compact_levels : lds_levels;
-            as.short_queue = fixed_q ? fixed_q : queue_entries;
-            const size_t lds = prhf::short_lds_fixed(as.lds_levels, n_freq, threads) + 8 * (size_t)queue_entries;
-            const long long short_slots = (long long)c->cu_count * (compact ? PRHF_COMPACT_WGS_PER_CU : (lds <= lds_half ? 2 : 1));
-            long long grid_short = short_blocks;
-            if (short_blocks > short_slots) {
-                as.queue = c->d_status + 2;
-                grid_short = short_slots;
-            }
-            // from four resident rounds on, the blocks are drawn in descending order of a cost estimate
-            as.order = order_made;             // (sorted beside the per-frequency table, or null: index order)
-            HIP_TRY(prhf::launch_vfo_short(as, grid_short, lds, threads, short_lanes, short_stream));
-            if (second) {
-                // the profiles the compact launch left for full-size arrays: persistent workgroups read their number from
-                // the device (3 us when there is none); what these leave - another input shape - joins the general list
-                prhf::KArgs a2 = as;
-                a2.trace = nullptr;
-                a2.lds_levels = lds_levels;
-                a2.short_queue = fixed_q ? -std::min(kShortQueueFixed, short_queue) : short_queue;
-                a2.block_list = as.leftover_tall;
-                a2.order = nullptr;
-                a2.leftover_tall = nullptr;
-                a2.queue = c->d_status + 0;
-                const size_t lds2 = prhf::short_lds_fixed(lds_levels, n_freq, PRHF_SHORT_THREADS) + 8 * (size_t)short_queue;
-                const long long slots2 = (long long)c->cu_count * (lds2 <= lds_half ? 2 : 1);
-                HIP_TRY(prhf::launch_vfo_short(a2, std::min(short_blocks, slots2), lds2, PRHF_SHORT_THREADS, short_lanes, short_stream));
-            }
-        }
-#ifdef PRHF_TRACE
-        if (as.trace) {                            // eight wall-clock marks per wave and block (tools/wave_trace_short.py)
-            std::vector<unsigned long long> host(short_trace_words);
-            HIP_TRY(hipMemcpyAsync(host.data(), as.trace, short_trace_words * 8, hipMemcpyDeviceToHost, short_stream));
-            HIP_TRY(hipStreamSynchronize(short_stream));
-            if (FILE* fp = std::fopen(std::getenv("PRHF_TRACE_FILE"), "wb")) {
-                std::fwrite(host.data(), 8, short_trace_words, fp);
-                std::fclose(fp);
-            }
-        }
-#endif
-        prhf::KArgs af = as;
-        af.trace = nullptr;
-        af.lds_levels = lds_levels;
-        af.leftover_tall = nullptr;
-        af.order = nullptr;
-        af.block_list = as.leftover;
-        af.leftover = nullptr;
-        af.queue = c->d_status + (xmode ? 5 : 3);
-        af.zero_after = (!xmode && order_made) ? order_made : nullptr;
-        HIP_TRY(prhf::launch_vfo(af, std::min(short_blocks, wg_slots), xmode ? 1 : 0, prhf::lds_bytes_for(lds_levels), short_stream));
-        if (af.zero_after) c->order_clean = true;
-        return PRHF_OK;
-    };
-    if ((rc = launch_short_kind(true)) != PRHF_OK) return rc;          // (the longer blocks first)
-    if ((rc = launch_short_kind(false)) != PRHF_OK) return rc;
-    if (forked) {
-        HIP_TRY(hipEventRecord(c->join_ev, c->aux_stream));
-        HIP_TRY(hipStreamWaitEvent(c->stream, c->join_ev, 0));
-    } else {
-        if ((rc = launch_general()) != PRHF_OK) return rc;
-    }
+    if ((rc = zero_control_words(c, pl)) != PRHF_OK) return rc;
+    if ((rc = launch_all(k, pl, a)) != PRHF_OK) return rc;
 #ifdef PRHF_TRACE
     if (a.trace) {
         std::vector<unsigned long long> host(trace_words);
@@ -905,34 +765,13 @@ int run(prhf_ctx* c, const double* freq, int64_t n_freq, const double* den, cons
         }
     }
 #endif
-    if (post) HIP_TRY(prhf::launch_residual(vh_dev, d_obs, n_prof, (int)n_freq, d_res, d_cost, c->stream));
+    if (post) HIP_TRY(prhf::launch_residual(k.vh_dev, k.d_obs, n_prof, (int)n_freq, k.d_res, k.d_cost, c->stream));
     if (timed_launch) {
         HIP_TRY(hipEventRecord(c->pending_end_ev(), c->stream));
         c->mark_timed();
     }
     c->status_pending = true;
-
-    // small results come back through the pinned buffer too (its upper half; the inputs of a call this small
-    // fit the lower one) and are handed over after the synchronisation below
-    const bool out_via_pack = !out_direct && !dev && out && out_elems && c->h_pack && out_elems * 8 <= kPackBytes / 4 &&
-                              (size_t)(d_out - static_cast<double*>(c->arena.p)) * 8 <= kPackBytes / 2;
-    double* h_out = c->h_pack ? c->h_pack + kPackBytes / 16 : nullptr;       // doubles: byte offset kPackBytes / 2
-    if (out_direct) {
-        // (written by the kernel itself)
-    } else if (out_via_pack)
-        HIP_TRY(hipMemcpyAsync(h_out, d_out, out_elems * 8, hipMemcpyDeviceToHost, c->stream));
-    else if (!dev && out_elems && out)
-        HIP_TRY(hipMemcpyAsync(out, d_out, out_elems * 8, hipMemcpyDeviceToHost, c->stream));
-    if (!dev && post) {
-        if (post->residual)
-            HIP_TRY(hipMemcpyAsync(post->residual, d_res, out_elems * 8, hipMemcpyDeviceToHost, c->stream));
-        if (post->cost)
-            HIP_TRY(hipMemcpyAsync(post->cost, d_cost, (size_t)n_prof * 8, hipMemcpyDeviceToHost, c->stream));
-    }
-    if (flags & PRHF_FLAG_ASYNC) return PRHF_OK;
-    rc = prhf_sync(c);
-    if (out_via_pack || out_direct) std::memcpy(out, h_out, out_elems * 8);
-    return rc;
+    return download_and_sync(k);
 }
 
 // A large batch from HOST buffers (a NumPy caller with an ensemble): uploaded whole in front of one launch, the
@@ -1070,7 +909,7 @@ int prhf_ctx_create(int device, prhf_ctx** out) {
                            hipHostMallocDefault)) != hipSuccess ||
         (e = hipMalloc(reinterpret_cast<void**>(&c->d_plan_counters), 4 * sizeof(unsigned long long))) != hipSuccess ||
         (e = hipMemset(c->d_plan_counters, 0, 4 * sizeof(unsigned long long))) != hipSuccess ||
-        (e = prhf::configure_kernels(prhf::lds_bytes_for(kMaxAlt))) != hipSuccess) {
+        (e = prhf::configure_kernels(staged_lds_bytes(kMaxAlt))) != hipSuccess) {
         prhf_ctx_destroy(c);
         return fail(PRHF_EHIP, "context setup failed: %s", hipGetErrorString(e));
     }
@@ -1318,10 +1157,10 @@ int prhf_regrid_f64(prhf_ctx* c, const double* freq_hz, int64_t n_freq, const do
     if (n_alt > kMaxAlt) {
         long long peak = 0;
         if (dev) {
-            HIP_TRY(hipMemsetAsync(c->d_status + 7, 0, sizeof(unsigned), c->stream));
-            HIP_TRY(prhf::launch_peak_levels(den, 1, n_alt, n_alt, c->d_status + 7, c->stream));
+            HIP_TRY(hipMemsetAsync(c->d_status + kWordPeak, 0, sizeof(unsigned), c->stream));
+            HIP_TRY(prhf::launch_peak_levels(den, 1, n_alt, n_alt, c->d_status + kWordPeak, c->stream));
             unsigned p = 0;
-            HIP_TRY(hipMemcpyAsync(&p, c->d_status + 7, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipMemcpyAsync(&p, c->d_status + kWordPeak, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
             HIP_TRY(hipStreamSynchronize(c->stream));
             peak = p;
         } else {
@@ -1371,7 +1210,7 @@ int prhf_regrid_f64(prhf_ctx* c, const double* freq_hz, int64_t n_freq, const do
         a.out_ind = reinterpret_cast<long long*>(d_out + 7 * fn);
     }
     HIP_TRY(hipEventRecord(c->begin_ev(), c->stream));
-    HIP_TRY(prhf::launch_regrid(a, prhf::lds_bytes_for(levels), c->stream));
+    HIP_TRY(prhf::launch_regrid(a, staged_lds_bytes(levels), c->stream));
     HIP_TRY(hipEventRecord(c->pending_end_ev(), c->stream));
     c->mark_timed();
     c->status_pending = true;
@@ -2641,7 +2480,7 @@ int prhf_occupancy(prhf_ctx* c, int64_t n_alt, int32_t math, int32_t* workgroups
     if (n_alt < 1 || n_alt > kMaxAlt) return fail(PRHF_EINVAL, "n_alt out of range");
     ENTER_DEVICE(c->device);
     int n = 0;
-    HIP_TRY(prhf::query_occupancy(math, prhf::lds_bytes_for(n_alt), &n));
+    HIP_TRY(prhf::query_occupancy(math, staged_lds_bytes(n_alt), &n));
     *workgroups_per_cu = n;
     return PRHF_OK;
 }

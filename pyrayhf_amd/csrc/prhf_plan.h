@@ -1,15 +1,21 @@
-// prhf_plan.h - the host-side launch planner of libprhf.so: the context options (Knobs), the decomposition of a slice
-// into wave-sized items and blocks (plan_slice) and the validation of a work list (validate_work_list).  No HIP call
-// and no device state in here - plain arithmetic on the caller's descriptors - so that the same code is compiled
-// into prhf_api.cpp and, under -fsanitize=address,undefined, into the host test tests/devtools/sanitize_host.cpp
-// (tests/test_sanitizers_host.py).  Everything lives in an anonymous namespace: internal to the including file.
+// prhf_plan.h - the host-side launch planner of libprhf.so: the context options (Knobs), the validation of a work list
+// (validate_work_list), the decomposition of a slice into wave-sized items and blocks (plan_slice) and, on top of them,
+// plan_launch: every decision of one operator call - which slices go to the general kernel and which to the short-grid
+// kernels, the geometry, LDS size and block queue of each launch, the strided table's pieces, the tables to build, the
+// second stream - as one LaunchPlan of plain data, which run() in prhf_api.cpp executes.  The names of the context's
+// control words (StatusWord) live here too.  No HIP call and no device state in here - plain arithmetic on the
+// caller's descriptors - so that the same code is compiled into prhf_api.cpp and into the host tests
+// (tests/test_launch_plan_host.py; under -fsanitize=address,undefined tests/devtools/sanitize_host.cpp,
+// tests/test_sanitizers_host.py).  Everything lives in an anonymous namespace: internal to the including file.
 
 #ifndef PRHF_PLAN_H
 #define PRHF_PLAN_H
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
 
 #include "prhf.h"
 #include "prhf_kernels.h"
@@ -249,6 +255,336 @@ inline int validate_work_list(const prhf_segment* segs, int32_t n_segs, int64_t 
             }
         }
     }
+    return PRHF_OK;
+}
+
+// The control words of a context (prhf_ctx::d_status, kStatusWords device words).  A persistent launch counts the blocks
+// it has handed out in its queue word, which must be zero when the launch starts; every launch of one operator call
+// has a word of its own, because they may run side by side.
+enum StatusWord : int {
+    kWordShortOFull = 0,      // short-grid O: the second launch, with full-size arrays
+    kWordGeneral = 1,         // the general launch (vfo_kernel, vfo_tall_kernel)
+    kWordShortO = 2,          // short-grid O: the first launch
+    kWordShortOFollow = 3,    // ... and the general kernel over the profiles it left
+    kWordShortX = 4,          // short-grid X: the first launch
+    kWordShortXFollow = 5,    // ... and the general kernel over the profiles it left
+    kLaunchQueueWords = 6,    // words [0, this) are zeroed in one piece in front of a launch with a queue
+    kWordRayQueue = 6,        // kept for the tracers (their per-ray launch now keeps its queue behind the per-profile scalars)
+    kWordPeak = 7,            // the peak pre-pass of a tall column: the highest peak index (launch_peak_levels)
+    kWordShortXFull = 8,      // short-grid X: the second launch, with full-size arrays
+    kStatusWords = 12,
+};
+
+// LDS of one CU and the budgets of a short-grid workgroup: two per CU where its nodes allow that, else one, or - the
+// compact geometry - PRHF_COMPACT_WGS_PER_CU; a few hundred bytes of static LDS (tickets, counters) come on top.
+#ifndef PRHF_COMPACT_RESERVE
+#define PRHF_COMPACT_RESERVE 512    // bytes kept back per workgroup for its static LDS (tickets, counters)
+#endif
+constexpr size_t kLdsPerCu = 160 * 1024;
+constexpr size_t kShortReserve = 512;
+constexpr size_t kLdsHalf = kLdsPerCu / 2 - kShortReserve, kLdsFull = kLdsPerCu - kShortReserve;
+constexpr size_t kLdsQuarter = kLdsPerCu / PRHF_COMPACT_WGS_PER_CU - PRHF_COMPACT_RESERVE;
+
+// LDS of a workgroup that stages `levels` levels of a profile: the general kernel's launches, the regrid kernel's, and
+// - at the most levels LDS holds - what the kernels are configured for.  The one name the API uses for it.
+inline size_t staged_lds_bytes(long long levels) { return prhf::lds_bytes_for(levels); }
+
+// Resident workgroups of a launch: LDS admits two per CU up to half of it each (less `reserve` bytes of static LDS), else one
+inline long long resident_slots(int cu_count, size_t lds_bytes, size_t reserve) {
+    return (long long)cu_count * (lds_bytes + reserve <= kLdsPerCu / 2 ? 2 : 1);
+}
+
+// The compact geometry of the short-grid kernels: four 4-wave workgroups per CU instead of two 8-wave
+// ones - four independent profiles in flight per CU, so that one workgroup's staging and barrier waits are covered by
+// three others' items (config 3: -10 %).  A quarter of the LDS holds the lists and fewer levels than the column has; a
+// profile whose peak lies above them goes to a second launch with full-size arrays.  Taken when those arrays hold at
+// least half of the column (PyIRI columns peak at 25 - 50 % of their height).  Returns the levels the compact arrays
+// hold - the most for which lds_of(levels) fits a quarter of the LDS - or 0: no compact launch.
+template <class LdsOf>
+inline long long compact_levels_for(long long lds_levels, LdsOf lds_of) {
+    long long L = lds_levels;
+    while (L > 1 && lds_of(L) > kLdsQuarter) --L;
+    return (2 * L >= lds_levels && L >= 8 && lds_of(L) <= kLdsQuarter) ? L : 0;
+}
+
+// The shape of one operator call, as far as the plan depends on it
+struct LaunchShape {
+    long long n_prof, n_freq, n_alt;
+    long long lds_levels;     // levels the staged arrays have room for: n_alt, or the highest peak index of a tall column + 1
+    bool tall;                // profiles staged in global memory (vfo_tall_kernel); decided by run()'s peak pre-pass
+    long long mult_len;
+    int cu_count;
+    int math;                 // PRHF_MATH_*
+};
+
+// One launch of a short-grid kernel
+struct ShortLaunch {
+    long long lds_levels;     // levels its staged arrays hold (KArgs::lds_levels)
+    int threads;              // PRHF_COMPACT_THREADS or PRHF_SHORT_THREADS
+    int queue_entries;        // O mode: entries of the LDS queue of ill-conditioned points (X mode has none: 0)
+    int short_queue;          // KArgs::short_queue: those entries, or - option short_queue - minus the fixed number
+    size_t lds_bytes;
+    long long slots;          // resident workgroups
+    long long grid;           // workgroups launched: one per block, or `slots` persistent ones
+    bool queue;               // ... which pull their blocks from a queue word
+};
+
+// The short-grid slices of one mode: vfo_short_kernel (O) / vfo_shortx_kernel (X) over one-profile blocks, a second
+// launch with full-size arrays over the profiles the compact one left, and the general kernel over what both left
+// (non-uniform altitude grid, fast-turning or vanishing field, negative density, peak at level 0 or 1, a sum that is
+// not finite)
+struct ShortKind {
+    int n_segs;
+    long long blocks;         // 0: nothing is launched
+    ShortLaunch first;
+    bool second;              // compact launch whose arrays hold fewer levels than the column: `full` follows
+    ShortLaunch full;
+    int lanes;                // O mode: lanes per pair (Knobs::short_lanes)
+    long long follow_grid;    // the follow-up general launch: persistent workgroups that read their list from the device
+    size_t list_bytes;        // each leftover list: a count and `blocks` block indices
+    prhf::SegDev seg[PRHF_MAX_SEGMENTS];
+};
+
+// Everything one operator call decides before it touches the device
+struct LaunchPlan {
+    // the general launch (vfo_kernel<launch_tier> or vfo_tall_kernel): its slices, longest workgroups first
+    int n_segs;
+    bool tall;                // vfo_tall_kernel: profiles staged in global memory (LaunchShape::tall)
+    int launch_tier;          // else vfo_kernel's: 0 faithful, 1 fast, 2 per slice
+    long long blocks;
+    long long wg_slots;       // resident workgroups
+    long long grid;           // workgroups launched: `blocks`, or `wg_slots` persistent ones
+    bool queue;               // ... which pull their blocks from kWordGeneral
+    size_t lds_bytes;
+    int no_candidates;        // KArgs::no_candidates
+    long long partial_elems, altmin_elems;   // scratch of the chunked slices, in doubles
+    long long out_rows;
+    unsigned long long tall_stride;          // tall launch: bytes of one workgroup's slab, and the slabs
+    long long tall_slabs;
+    // tables
+    bool want_pairs;          // a slice takes the main loop: the pair table
+    long long table_entries;  // ... with the strided table's pieces behind it
+    bool any_plan;            // a slice takes the planning pass (SegDev::pair_plan)
+    bool freq_table;          // the per-frequency table is built; its kernel zeroes the control words on the way
+    bool short_order;         // ... by short_order_kernel, which sorts the short-grid O launch's blocks by cost as well
+    bool zero_queues;         // without that table: the queue words are zeroed by a memset
+    bool forked;              // short-grid launches on the second stream, beside the general launch
+    prhf::StridedPieces pieces;
+    prhf::SegDev seg[PRHF_MAX_SEGMENTS];
+    ShortKind o, x;
+};
+
+// The one place that sizes a short-grid launch: `levels` staged levels in the compact or the full-size geometry,
+// `queue_entries` of LDS queue (O mode), over `blocks` blocks - or over a device-side list of at most as many
+inline ShortLaunch size_short_launch(bool xmode, bool compact, long long levels, int queue_entries, bool from_list,
+                                     long long blocks, const LaunchShape& sh, const Knobs& kn) {
+    ShortLaunch l;
+    l.lds_levels = levels;
+    l.threads = compact ? PRHF_COMPACT_THREADS : PRHF_SHORT_THREADS;
+    l.queue_entries = xmode ? 0 : queue_entries;
+    const int fixed = (int)kn.short_queue;
+    l.short_queue = fixed > 0 && !xmode ? -std::min(fixed, queue_entries) : l.queue_entries;
+    l.lds_bytes = xmode ? prhf::shortx_lds_bytes(levels, sh.n_freq)
+                        : prhf::short_lds_fixed(levels, sh.n_freq, l.threads) + 8 * (size_t)queue_entries;
+    l.slots = compact ? (long long)sh.cu_count * PRHF_COMPACT_WGS_PER_CU : resident_slots(sh.cu_count, l.lds_bytes, kShortReserve);
+    l.queue = from_list || blocks > l.slots;
+    l.grid = std::min(blocks, l.slots);
+    return l;
+}
+
+// Number the blocks of one kind's slices and size its launches.  full_queue: queue entries of the full-size O geometry.
+inline void plan_short_kind(ShortKind& k, bool xmode, int full_queue, long long wg_slots, const LaunchShape& sh, const Knobs& kn) {
+    k.blocks = 0;
+    for (int i = 0; i < k.n_segs; ++i) {
+        k.seg[i].block_begin = k.blocks;
+        k.blocks += k.seg[i].prof_end - k.seg[i].prof_begin;
+    }
+    k.second = false;
+    k.lanes = 0;
+    k.follow_grid = std::min(k.blocks, wg_slots);
+    k.list_bytes = (size_t)(k.blocks + 1) * sizeof(unsigned);
+    k.first = k.full = ShortLaunch();
+    if (k.blocks == 0) return;
+    long long compact = 0;
+    int compact_queue = 0;
+    if (kn.short_compact != 0) {
+        if (xmode) {
+            compact = compact_levels_for(sh.lds_levels, [&](long long L) { return prhf::shortx_lds_bytes(L, sh.n_freq); });
+        } else {
+            compact = compact_levels_for(sh.lds_levels, [&](long long L) {
+                return prhf::short_lds_fixed(L, sh.n_freq, PRHF_COMPACT_THREADS) + 8 * PRHF_COMPACT_MIN_QUEUE;
+            });
+            if (compact) compact_queue = prhf::short_queue_entries(compact, sh.n_freq, kLdsQuarter, PRHF_COMPACT_THREADS);
+        }
+    }
+    k.first = size_short_launch(xmode, compact > 0, compact ? compact : sh.lds_levels, compact ? compact_queue : full_queue,
+                                false, k.blocks, sh, kn);
+    k.second = compact > 0 && compact < sh.lds_levels;        // some bottomsides may not fit the compact arrays
+    if (k.second) k.full = size_short_launch(xmode, false, sh.lds_levels, full_queue, true, k.blocks, sh, kn);
+    if (!xmode) {
+        // lanes per pair: eight on grids of up to 256 points (the launch's longest), sixteen beyond (Knobs::short_lanes)
+        int longest = 0;
+        for (int i = 0; i < k.n_segs; ++i) longest = std::max(longest, k.seg[i].n_points);
+        k.lanes = kn.short_lanes == 0 ? (longest <= 256 ? 8 : 16) : (kn.short_lanes < 12 ? 8 : 16);
+    }
+}
+
+// Plan one operator call ("Launch geometry"): PRHF_OK and the plan in `pl`, or PRHF_EINVAL with the
+// reason in `msg`.  Nothing is allocated; of the plan's slice arrays only the entries in use are written.
+inline int plan_launch(const LaunchShape& sh, const prhf_segment* segs, int32_t n_user_segs, const Knobs& kn, LaunchPlan& pl,
+                       char* msg, size_t msg_len) {
+    const long long n_freq = sh.n_freq, n_prof = sh.n_prof, lds_levels = sh.lds_levels;
+    const bool tall = sh.tall;
+    const int kLeanMinPoints = (int)kn.lean_min_points;
+    const bool kNoCandidates = kn.no_candidates != 0, kPersistent = kn.persistent != 0;
+    if (validate_work_list(segs, n_user_segs, n_prof, n_freq, sh.mult_len, msg, msg_len) != PRHF_OK) return PRHF_EINVAL;
+    // (a tall launch keeps its profile in a slab of global memory: its LDS always admits two workgroups per CU)
+    pl.tall = tall;
+    pl.lds_bytes = tall ? prhf::lds_bytes_tall() : staged_lds_bytes(lds_levels);
+    pl.wg_slots = resident_slots(sh.cu_count, pl.lds_bytes, 0);
+    // queue entries of a full-size short-grid O workgroup (0: the kernel cannot run)
+    const size_t short_budget = prhf::short_queue_entries(lds_levels, n_freq, kLdsHalf, PRHF_SHORT_THREADS) ? kLdsHalf : kLdsFull;
+    const int full_queue = prhf::short_queue_entries(lds_levels, n_freq, short_budget, PRHF_SHORT_THREADS);
+
+    pl.n_segs = pl.o.n_segs = pl.x.n_segs = 0;
+    pl.want_pairs = false;
+    pl.out_rows = 0;
+    for (int i = 0; i < n_user_segs; ++i) {
+        const prhf_segment& u = segs[i];
+        prhf::SegDev s;
+        std::memset(&s, 0, sizeof s);
+        s.prof_begin = u.prof_begin;
+        s.prof_end = u.prof_end;
+        s.mult_off = u.mult_offset;
+        s.out_off = u.out_offset;
+        s.mode = u.mode == PRHF_MODE_O ? PRHF_KMODE_O : PRHF_KMODE_X;
+        s.n_points = u.n_points;
+        s.tier = sh.math == PRHF_MATH_AUTO ? (u.mode == PRHF_MODE_O ? 0 : 1) : (sh.math == PRHF_MATH_FAST ? 1 : 0);
+        // AUTO, O mode: the reference's operation order where it decides the answer (1 - X <= well_conditioned = 1e-5), the
+        // reduced algebra elsewhere; PRHF_MATH_FAITHFUL keeps the reference's order everywhere
+        s.well_conditioned = (sh.math == PRHF_MATH_AUTO && s.tier == 0) ? kn.well_conditioned : HUGE_VAL;
+        // the main loop needs the pair table: one more (small) kernel unless the caller's grid is cached - not
+        // worth it for a handful of pairs on a short grid, where the launch itself is the cost
+        const long long seg_pairs = (u.prof_end - u.prof_begin) * n_freq;
+        // (decided from the slice's shape alone: host and device callers must get the same arithmetic)
+        const bool table_is_cheap = seg_pairs >= 4096 || u.n_points >= 2048;
+        // (a profile staged in global memory - `tall` - takes the main loop too: it reads the nodes from the workgroup's
+        //  slab through a buffer resource, NodeSpace<true>; option tall_lean = 0: the generic loop, as up to round 4)
+        s.lean = ((!tall || kn.tall_lean != 0) && (s.tier == 1 || s.well_conditioned < 1.0) && u.n_points >= kLeanMinPoints &&
+                  seg_pairs > 0 && table_is_cheap) ? 1 : 0;
+        s.thread_scan = (!tall && (double)n_freq * (double)u.n_points >= kn.thread_scan_min) ? 1 : 0;
+        plan_slice(s, n_freq, pl.wg_slots, kn);
+        pl.out_rows = std::max<long long>(pl.out_rows, u.out_offset / n_freq + (u.prof_end - u.prof_begin));
+        // Slices of short grids leave for a launch of their own.  The short-grid kernels read the per-frequency table
+        // (launches of >= 4096 pairs) and list at most PRHF_MAX_CAND frequencies per profile
+        // (grids shorter than the general kernel's main loop takes - lean_min_points - are theirs too: the pair
+        //  table is built for them)
+        const bool table = !tall && (s.lean || (seg_pairs >= 4096 && s.n_points < kLeanMinPoints));
+        const bool fits_short = table && s.chunks == 1 && s.n_points >= PRHF_SHORT_MIN_POINTS && n_freq <= PRHF_MAX_CAND &&
+                                n_prof * n_freq >= 4096 && !kNoCandidates;
+        const bool is_short = kn.short_kernel != 0 && fits_short && s.tier == 0 && s.well_conditioned < 1.0 &&
+                              s.n_points <= PRHF_SHORT_MAX_POINTS && full_queue > 0;
+        // ... and its X-mode variant (fast tier, reflection heights per thread, no top-segment phase)
+        const bool is_shortx = kn.shortx_kernel != 0 && fits_short && s.tier == 1 && s.mode == PRHF_KMODE_X &&
+                               s.n_points <= PRHF_SHORTX_MAX_POINTS && s.thread_scan &&
+                               prhf::shortx_lds_bytes(lds_levels, n_freq) <= kLdsFull;
+        if (is_short || is_shortx) {
+            ShortKind& k = is_short ? pl.o : pl.x;
+            prhf::SegDev& t = k.seg[k.n_segs++];
+            t = s;
+            t.lean = 1;
+            t.blocks_per_prof = 1;
+            t.tail_prof = t.prof_end - t.prof_begin;
+            t.tail_bpp = 1;
+            pl.want_pairs = true;
+        } else {
+            pl.want_pairs = pl.want_pairs || s.lean != 0;
+            pl.seg[pl.n_segs++] = s;
+        }
+    }
+    pl.launch_tier = 0;
+    for (int i = 0; i < pl.n_segs; ++i) pl.launch_tier = (i == 0 || pl.launch_tier == pl.seg[i].tier) ? pl.seg[i].tier : 2;
+    // Workgroups are dispatched roughly in index order: give the slices with the most work per workgroup
+    // the lowest indices so that a mixed launch does not end on its longest workgroups.  (A stable insertion sort: at
+    // most PRHF_MAX_SEGMENTS entries, and nothing is allocated.)
+    auto cost = [](const prhf::SegDev& s) {
+        const double per_point = s.tier == 1 ? 1.0 : (s.well_conditioned < 1.0 ? 1.8 : 3.5);
+        return (double)s.n_points / s.chunks / s.blocks_per_prof * per_point;   // head workgroups
+    };
+    for (int i = 1; i < pl.n_segs; ++i)
+        for (int k = i; k > 0 && cost(pl.seg[k]) > cost(pl.seg[k - 1]); --k) std::swap(pl.seg[k], pl.seg[k - 1]);
+    pl.blocks = pl.partial_elems = pl.altmin_elems = 0;
+    for (int i = 0; i < pl.n_segs; ++i) {
+        prhf::SegDev& s = pl.seg[i];
+        const long long P = s.prof_end - s.prof_begin;
+        s.prio = std::max(0, 3 - i);               // (sorted: the slice with the longest workgroups first)
+        s.block_begin = pl.blocks;
+        pl.blocks += s.tail_prof * s.blocks_per_prof + (P - s.tail_prof) * s.tail_bpp;
+        if (s.chunks > 1 && s.slots == 0) {
+            s.partial_off = pl.partial_elems;
+            s.altmin_off = pl.altmin_elems;
+            pl.partial_elems += P * n_freq * s.chunks;
+            pl.altmin_elems += P;
+        }
+    }
+    // persistent workgroups pulling blocks from a queue (vfo_kernel) once the launch has more blocks than slots
+    pl.queue = (kPersistent || tall) && pl.blocks > pl.wg_slots;
+    pl.grid = pl.queue ? pl.wg_slots : pl.blocks;
+    pl.no_candidates = kNoCandidates || tall;
+    pl.tall_stride = tall && pl.blocks > 0 ? prhf::tall_slab_bytes(sh.n_alt) : 0;
+    pl.tall_slabs = tall ? std::min(pl.blocks, pl.wg_slots) : 0;
+    plan_short_kind(pl.x, true, full_queue, pl.wg_slots, sh, kn);
+    plan_short_kind(pl.o, false, full_queue, pl.wg_slots, sh, kn);
+    if (pl.blocks > 0x7fffffffLL || pl.o.blocks > 0x7fffffffLL || pl.x.blocks > 0x7fffffffLL) {
+        std::snprintf(msg, msg_len, "launch too large");
+        return PRHF_EINVAL;
+    }
+
+    // The strided table (option strided_top): one piece behind the pair table for every distinct grid of
+    // the X-mode fast-tier slices that take whole pairs of at least PRHF_TOP3_MIN_POINTS points through the main loop.
+    std::memset(&pl.pieces, 0, sizeof pl.pieces);
+    pl.table_entries = sh.mult_len + PRHF_PAIR_PAD;
+    pl.any_plan = false;                       // a slice takes the planning pass: it needs the candidate list
+    if (pl.want_pairs && kn.strided_top != 0 && !tall) {
+        prhf::StridedPieces& pieces = pl.pieces;
+        for (int i = 0; i < pl.n_segs; ++i) {
+            prhf::SegDev& s = pl.seg[i];
+            if (!(s.lean && s.tier == 1 && s.mode == PRHF_KMODE_X && s.chunks == 1 && s.n_points >= PRHF_TOP3_MIN_POINTS)) continue;
+            int p = 0;
+            while (p < pieces.n && !(pieces.mult_off[p] == s.mult_off && pieces.n_points[p] == s.n_points)) ++p;
+            if (p == pieces.n) {
+                const long long len = prhf::strided_piece_entries(s.n_points);
+                // (the main loop addresses the table through a 31-bit byte offset)
+                if ((pl.table_entries + len) * 16 >= 0x7fffffffLL) continue;
+                pieces.mult_off[p] = s.mult_off;
+                pieces.n_points[p] = s.n_points;
+                pieces.sp_off[p] = pl.table_entries;
+                pl.table_entries += len;
+                ++pieces.n;
+            }
+            s.sp_off = pieces.sp_off[p];
+            s.strided_lower = kn.strided_lower != 0;
+            s.panel_lower = s.strided_lower && kn.panel_lower != 0;
+            s.pair_plan = slice_plans_pairs(s, tall, n_freq, lds_levels, kn) ? 1 : 0;
+            pl.any_plan = pl.any_plan || s.pair_plan != 0;
+        }
+    }
+    // per-frequency scalars: long launches read them from a table instead of dividing once per pair (a short
+    // launch - one profile - is latency bound: it does without the extra kernel)
+    // (... and so does a launch with a slice that plans its pairs: the heights that pass starts from are settled with
+    //  the candidate list, which reads the table.  By default such a slice has 4096 pairs anyway - fewer are chunked)
+    pl.freq_table = pl.want_pairs && (n_prof * n_freq >= 4096 || pl.any_plan);
+    // A short-grid O launch of four resident rounds and more draws its blocks in descending order of a cost
+    // estimate: the kernel that sorts them makes the table as well (short_order_kernel)
+    pl.short_order = pl.freq_table && pl.o.blocks > 0 && kn.short_order != 0 && pl.o.blocks >= 4 * pl.o.first.slots;
+    const bool any_short = pl.o.n_segs > 0 || pl.x.n_segs > 0;
+    pl.zero_queues = !pl.freq_table && (any_short || pl.queue);
+    // A list with both kinds of slices: the general launch goes first, on the caller's stream, and takes every
+    // workgroup slot; the short-grid launch runs on a second stream and its workgroups move in as the general
+    // launch's persistent workgroups leave - its 30 - 100 us blocks fill the end of the launch, which otherwise drains
+    // on a few long blocks.  (One after the other on one stream the config-5 shard took 8.04 ms, general kernel alone
+    // 7.94 ms.)  A launch of one kind stays on the caller's stream.
+    pl.forked = any_short && pl.blocks > 0 && kn.short_concurrent != 0;
     return PRHF_OK;
 }
 

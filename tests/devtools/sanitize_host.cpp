@@ -1,8 +1,8 @@
 // Host-side code of the build under AddressSanitizer + UndefinedBehaviorSanitizer (tests/test_sanitizers_host.py; CPU
 // only - GPU sanitizers are not available on the pool).  One executable, three parts:
-//   1. the launch planner of libprhf.so (pyrayhf_amd/csrc/prhf_plan.h: plan_slice, validate_work_list,
+//   1. the launch planner of libprhf.so (pyrayhf_amd/csrc/prhf_plan.h: plan_slice, plan_launch, validate_work_list,
 //      first_decreasing_grid_entry) over a sweep of launch shapes and option settings, with the invariants the kernels
-//      rely on checked on every plan;
+//      rely on checked on every plan (those of a whole launch: launch_plan_checks.h);
 //   2. the double-double sin / cos / pow of the reference-order tier (prhf_crmath.h via crmath_host.cpp);
 //   3. the plain-C oracle (oracle/vfo_oracle.c, TEST INFRASTRUCTURE) on a small seeded batch with its edge cases.
 // Prints "sanitize_host: ok" and exits 0; a sanitizer report or a broken invariant ends it with a non-zero code.
@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "prhf_plan.h"
+#include "launch_plan_checks.h"
 
 extern "C" {
 void cr_sincos(const double* r, long n, double* s, double* c);
@@ -71,6 +72,34 @@ static void planner() {
             CHECK(s.blocks_per_prof == 1 || (long long)(s.blocks_per_prof - 1) * kWavesPerBlock < items,
                   "%d workgroups per profile for %lld items", s.blocks_per_prof, items);
             CHECK(s.tail_bpp <= 64 || s.tail_bpp == s.blocks_per_prof, "tail_bpp %d", s.tail_bpp);
+        }
+    }
+    // whole launches: one-, three- and eight-segment lists, O and X mixed, columns that fit LDS, trimmed ones and tall ones
+    struct Shape { long long n_alt, lds_levels; bool tall; };
+    const Shape shapes_of[] = {{620, 620, false}, {1400, 1400, false}, {2000, 900, false}, {2000, 2000, true}, {65535, 65535, true}};
+    const int list_of[] = {1, 3, 8};
+    for (int variant = 0; variant < 4; ++variant) {
+        Knobs kn;
+        if (variant == 1) { kn.short_compact = 0; kn.persistent = 0; kn.short_queue = 16; }
+        if (variant == 2) { kn.short_kernel = 0; kn.strided_top = 0; kn.short_concurrent = 0; }
+        if (variant == 3) { kn.shortx_kernel = 0; kn.pair_plan = 0; kn.no_candidates = 1; kn.tall_lean = 0; }
+        for (const Shape& shape : shapes_of) for (int n_segs : list_of) for (long long per : {0LL, 1LL, 100LL, 3000LL}) for (long long F : freqs_of) {
+            const int points[PRHF_MAX_SEGMENTS] = {200, 2000, 500, 20000, 1, 8192, 1024, 8192};
+            prhf_segment segs[PRHF_MAX_SEGMENTS];
+            long long off = 0;
+            for (int i = 0; i < n_segs; ++i) {                    // (slice 4 is empty; slices 5 and 7 share a grid size, not a grid)
+                const long long P = i == 4 ? 0 : per;
+                segs[i] = prhf_segment{i * per, i * per + P, (i + (int)(F & 1)) % 2 ? PRHF_MODE_X : PRHF_MODE_O, points[i], off, i * per * F};
+                off += points[i];
+            }
+            const LaunchShape sh = {n_segs * per, F, shape.n_alt, shape.lds_levels, shape.tall, off, 256, PRHF_MATH_AUTO};
+            LaunchPlan pl;
+            char msg[160] = "";
+            const int rc = plan_launch(sh, segs, n_segs, kn, pl, msg, sizeof msg);
+            CHECK(rc == PRHF_OK, "plan_launch: %s", msg);
+            char what[96];
+            std::snprintf(what, sizeof what, "variant %d, %lld levels, %d slices x %lld x %lld", variant, shape.n_alt, n_segs, per, F);
+            if (rc == PRHF_OK) failures += check_plan(what, sh, segs, n_segs, kn, pl);
         }
     }
     // work lists: every rule of validate_work_list, and the grid check

@@ -38,7 +38,8 @@ extern "C" {
                               *    number: a new symbol changes nothing for a caller of the others (so did
                               *    prhf_gradient_home_f64, prhf_snell_skip_f64, prhf_snell_muf_f64 and
                               *    prhf_pair_plan_counters, prhf_panel_counters, and prhf_field_build_f64,
-                              *    prhf_gradient_skip_f64, prhf_gradient_muf_f64, prhf_gradient_skip_counters) */
+                              *    prhf_gradient_skip_f64, prhf_gradient_muf_f64, prhf_gradient_skip_counters,
+                              *    prhf_trace_gradient_hops_f64, prhf_gradient_hop_home_f64) */
 
 /* return codes */
 #define PRHF_OK        0
@@ -560,6 +561,61 @@ int prhf_gradient_home_f64(prhf_ctx* ctx, int32_t geometry, const double* record
  * refine lanes traced, [2] ray slots (64 per trip of a refine wavefront's loop), [3] refine wavefronts with work.
  * Lane utilisation of the refinement = [1] / [2].  No device call. */
 int prhf_gradient_home_counters(prhf_ctx* ctx, uint64_t* counters);
+
+/*
+ * Multi-hop rays through a horizontally varying mu: a ray that lands is reflected off the ground and traced on, n_rays
+ * chains of n_hops (1 .. 16) hops in one launch, a chain per lane.  No counterpart in the reference (over a stratified
+ * ionosphere n hops are n copies of one hop; through a tilt they are not); the definition is DESIGN.md section 4.12.
+ * geometry, records .. axis1, the ray arrays, earth_radius_km, the controls s_max_km .. renormalize_every (top, left,
+ * right as in prhf_gradient_home_f64) and the fills are the tracer's of that geometry.  The chain of ray r, every hop
+ * under the call's controls:
+ *   hop 0 launches at (x0_km[r], z0_km[r]) with elevation_deg[r];
+ *   hop h + 1 exists only if h + 1 < n_hops and hop h ended with status 0 (ground);
+ *   it launches at x = ground_range_km of hop h (the x of its landing node, those bits), z = z_ground_km, with the
+ *   elevation atan2(-v_vert, v_horiz) * (180.0 / 3.141592653589793) - one multiplication by that constant -, where
+ *   (v_horiz, v_vert) = (vx, vz) of hop h's last path node in a Cartesian call and (v_phi, v_r) in a spherical one: the
+ *   bits the tracer stores in path_vx / path_vz (path_v_r / path_v_phi).  This is specular reflection off the ground;
+ *   the launch normalises the direction again.  An elevation beyond 90 degrees (a ray travelling backwards) is legal.
+ *   Every hop has the whole s_max_km and starts the step controller and the right-hand-side counter afresh, as a tracer
+ *   call does.  The ground event sits at z_ground_km + 1e-3: a hop launched at z_ground_km starts below it, rising.
+ * out is (n_rays, n_hops, 15): launch x, launch z, launch elevation, then the tracer's twelve.  Every used hop row is
+ * bit for bit what prhf_trace_gradient_f64 / prhf_trace_gradient_spherical_f64 returns for that row's launch point,
+ * elevation, field and controls.  Rows behind the first hop that does not land are unused: NaN, status -1, nodes,
+ * right-hand-side calls, rejected steps and the last column 0.  path_t .. path_vb (all five or none) are
+ * (n_rays * n_hops, path_stride): row r * n_hops + h holds the tracer's path of hop h, NaN where unused; PRHF_EINVAL when
+ * a hop has more nodes than path_stride, as in the tracers.  Host memory, or device memory with PRHF_FLAG_DEVICE_PTRS.
+ * PRHF_EINVAL for a null context (before anything else), n_hops outside 1 .. 16, a geometry other than 0 or 1, and
+ * whatever the tracer of that geometry refuses - a ray_field out of range on the host for host buffers, by the kernel
+ * for device-resident ones (NaN rows, no memory outside the records is read).  Synchronous.
+ */
+int prhf_trace_gradient_hops_f64(prhf_ctx* ctx, int32_t geometry, const double* records, int64_t n_fields, int64_t n0,
+                                 int64_t n1, const double* axis0, const double* axis1, const double* x0_km,
+                                 const double* z0_km, const double* elevation_deg, const int64_t* ray_field, int64_t n_rays,
+                                 double earth_radius_km, double s_max_km, double rtol, double atol, double max_step_km,
+                                 double z_ground_km, double top, double left, double right, int32_t renormalize_every,
+                                 double fill_n, double fill_grad, double fill_mup, int32_t n_hops, double* out,
+                                 double* path_t, double* path_a, double* path_b, double* path_va, double* path_vb,
+                                 int64_t path_stride, uint32_t flags);
+
+/*
+ * Homing on the landing of hop n_hops - 1 (2F, 3F .. modes of a long link): prhf_gradient_home_f64 with D(e) the
+ * ground_range_km of the last hop of prhf_trace_gradient_hops_f64's chain at elevation e, NaN unless all n_hops
+ * (1 .. 16) hops land.  Scan, brackets, the refine rule, statuses, n_brackets, flags and every PRHF_EINVAL rule are
+ * that call's, unchanged; so are all arguments before n_hops.  out is (n_links, max_roots, 3 + 15 * n_hops):
+ * elevation_deg, status, scan_index, then the n_hops hop rows of prhf_trace_gradient_hops_f64 for the result chain, bit
+ * for bit what that call returns at elevation_deg.  Rows without a bracket: elevation and scan_index NaN, status -1, hop
+ * rows unused as that call writes them.  With n_hops = 1 the call finds what prhf_gradient_home_f64 finds.
+ * prhf_gradient_home_counters reports this call as well.  PRHF_EINVAL also for n_hops outside 1 .. 16.  Synchronous.
+ */
+int prhf_gradient_hop_home_f64(prhf_ctx* ctx, int32_t geometry, const double* records, int64_t n_fields, int64_t n0,
+                               int64_t n1, const double* axis0, const double* axis1, const int64_t* group_field,
+                               const double* group_x0_km, const double* group_z0_km, int64_t n_groups,
+                               const int64_t* link_group, const double* link_target_km, int64_t n_links,
+                               const double* scan_elevation_deg, int64_t n_scan, double earth_radius_km, double s_max_km,
+                               double rtol, double atol, double max_step_km, double z_ground_km, double top, double left,
+                               double right, int32_t renormalize_every, double fill_n, double fill_grad, double fill_mup,
+                               double range_tol_km, int32_t max_iter, int32_t max_roots, int32_t n_hops, double* out,
+                               int64_t* n_brackets, uint32_t flags);
 
 /*
  * Fields of many frequencies built on the device: the records (n_freq, n0, n1, 4) of

@@ -13,11 +13,14 @@ __version__ = "0.1.0"
 
 from .gradient import (STATUS_NAMES, RefractiveField, build_mup_function,                       # noqa: E402
                        build_refractive_index_interpolator_cartesian,
-                       build_refractive_index_interpolator_spherical, home_rays_cartesian_gradient,
+                       build_refractive_index_interpolator_spherical, home_hops_cartesian_gradient,
+                       home_hops_spherical_gradient, home_rays_cartesian_gradient,
                        home_rays_spherical_gradient, muf_cartesian_gradient, muf_spherical_gradient,
                        refractive_field, refractive_field_device, skip_distance_cartesian_gradient,
                        skip_distance_spherical_gradient,
                        trace_fan_cartesian_gradient, trace_fan_spherical_gradient,
+                       trace_hop_fan_cartesian_gradient, trace_hop_fan_spherical_gradient,
+                       trace_hops_cartesian_gradient, trace_hops_spherical_gradient,
                        trace_ray_cartesian_gradient, trace_ray_spherical_gradient,
                        trace_rays_cartesian_gradient, trace_rays_spherical_gradient)
 from .tracers import (home_rays_cartesian_snells, home_rays_spherical_snells, muf_cartesian_snells,  # noqa: E402
@@ -31,4 +34,6 @@ __all__ = ["logger", "__version__", "STATUS_NAMES", "RefractiveField", "build_mu
            "home_rays_cartesian_gradient", "home_rays_spherical_gradient", "skip_distance_cartesian_snells",
            "skip_distance_spherical_snells", "muf_cartesian_snells", "muf_spherical_snells",
            "refractive_field_device", "skip_distance_cartesian_gradient", "skip_distance_spherical_gradient",
-           "muf_cartesian_gradient", "muf_spherical_gradient"]
+           "muf_cartesian_gradient", "muf_spherical_gradient", "trace_hops_cartesian_gradient",
+           "trace_hops_spherical_gradient", "trace_hop_fan_cartesian_gradient", "trace_hop_fan_spherical_gradient",
+           "home_hops_cartesian_gradient", "home_hops_spherical_gradient"]

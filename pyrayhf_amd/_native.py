@@ -120,6 +120,17 @@ _PROTOTYPES = {
                                [ctypes.c_double] * 9 + [ctypes.c_int32] + [ctypes.c_double] * 4 +
                                [ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32]),
     "prhf_gradient_home_counters": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
+    "prhf_trace_gradient_hops_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64,
+                                                    ctypes.c_int64, ctypes.c_int64] + [ctypes.c_void_p] * 6 +
+                                     [ctypes.c_int64] + [ctypes.c_double] * 9 + [ctypes.c_int32] + [ctypes.c_double] * 3 +
+                                     [ctypes.c_int32] + [ctypes.c_void_p] * 6 + [ctypes.c_int64, ctypes.c_uint32]),
+    "prhf_gradient_hop_home_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64,
+                                                  ctypes.c_int64, ctypes.c_int64] + [ctypes.c_void_p] * 5 +
+                                   [ctypes.c_int64] + [ctypes.c_void_p] * 2 +
+                                   [ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64] + [ctypes.c_double] * 9 +
+                                   [ctypes.c_int32] + [ctypes.c_double] * 4 +
+                                   [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                    ctypes.c_uint32]),
     "prhf_field_build_f64": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int64, ctypes.c_int64] +
                              [ctypes.c_void_p] * 3 + [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32] +
                              [ctypes.c_void_p] * 3 + [ctypes.c_uint32]),
@@ -389,6 +400,28 @@ class Context:
                                                 *(float(v) for v in controls[:8]), int(controls[8]),
                                                 *(float(v) for v in fills), float(range_tol), int(max_iter),
                                                 int(max_roots), out, n_brackets, flags)
+
+    def trace_gradient_hops(self, geometry, records, n_fields, n0, n1, axis0, axis1, x0, z0, elev, ray_field, n_rays,
+                            earth_radius, controls, fills, n_hops, out, paths, path_stride, flags):
+        """controls: gradient_home's; ``out``: (n_rays, n_hops, 15) doubles; paths: five raw addresses of
+        (n_rays n_hops, path_stride) doubles each, or None (include/prhf.h)."""
+        paths = paths or (None,) * 5
+        return self._lib.prhf_trace_gradient_hops_f64(self._h, int(geometry), records, n_fields, n0, n1, axis0, axis1, x0, z0,
+                                                      elev, ray_field or None, n_rays, float(earth_radius),
+                                                      *(float(v) for v in controls[:8]), int(controls[8]),
+                                                      *(float(v) for v in fills), int(n_hops), out, *paths,
+                                                      int(path_stride), flags)
+
+    def gradient_hop_home(self, geometry, records, n_fields, n0, n1, axis0, axis1, group_field, group_x0, group_z0, n_groups,
+                          link_group, link_target, n_links, scan_elev, n_scan, earth_radius, controls, fills, range_tol,
+                          max_iter, max_roots, n_hops, out, n_brackets, flags):
+        """gradient_home on the landing of hop ``n_hops`` - 1; ``out``: (n_links, max_roots, 3 + 15 n_hops) doubles."""
+        return self._lib.prhf_gradient_hop_home_f64(self._h, int(geometry), records, n_fields, n0, n1, axis0, axis1,
+                                                    group_field, group_x0, group_z0, n_groups, link_group, link_target,
+                                                    n_links, scan_elev, n_scan, float(earth_radius),
+                                                    *(float(v) for v in controls[:8]), int(controls[8]),
+                                                    *(float(v) for v in fills), float(range_tol), int(max_iter),
+                                                    int(max_roots), int(n_hops), out, n_brackets, flags)
 
     def gradient_home_counters(self):
         """(brackets refined, rays traced by the refine lanes, ray slots, refine wavefronts) of the last gradient_home."""

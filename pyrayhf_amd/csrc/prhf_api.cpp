@@ -1929,8 +1929,10 @@ int prhf_field_sample_f64(prhf_ctx* c, const double* records, int64_t n_fields, 
 
 namespace {
 // Both gradient tracers.  Spherical (geometry PRHF_GEO_SPHERICAL): the axes are r and phi, z_ground_km .. x_max_km carry
-// R_E + z_ground_km, r_max_km, phi_min, phi_max and the paths are t, r, phi, v_r, v_phi.
-int grad_trace_run(prhf_ctx* c, int geometry, double earth_radius_km, const double* records, int64_t n_fields, int64_t nz,
+// R_E + z_ground_km, r_max_km, phi_min, phi_max and the paths are t, r, phi, v_r, v_phi.  n_hops > 0: the multi-hop call
+// (prhf_trace_gradient_hops_f64) - out is (n_rays, n_hops, 15), the paths hold n_rays n_hops rows and hop_z0_km is
+// z_ground_km as the caller gave it.
+int grad_trace_run(prhf_ctx* c, int n_hops, double hop_z0_km, int geometry, double earth_radius_km, const double* records, int64_t n_fields, int64_t nz,
                    int64_t nx, const double* z_axis, const double* x_axis, const double* x0_km, const double* z0_km,
                    const double* elevation_deg, const int64_t* ray_field, int64_t n_rays, double s_max_km, double rtol,
                    double atol, double max_step_km, double z_ground_km, double z_max_km, double x_min_km, double x_max_km,
@@ -1957,8 +1959,9 @@ int grad_trace_run(prhf_ctx* c, int geometry, double earth_radius_km, const doub
                 return fail(PRHF_EINVAL, "ray_field[%lld] outside [0, n_fields)", (long long)r);
     if (n_rays == 0) return PRHF_OK;
     ENTER_DEVICE(c->device);
-    const size_t R = (size_t)n_rays, path_elems = n_paths ? R * (size_t)path_stride : 0;
-    rc = ensure(c, c->arena, ((size_t)(nz + nx) + (dev ? 0 : (4 + PRHF_GRAD_OUTPUTS) * R + 5 * path_elems)) * 8);
+    const size_t R = (size_t)n_rays, path_elems = n_paths ? R * (size_t)(n_hops ? n_hops : 1) * (size_t)path_stride : 0;
+    const size_t out_elems = R * (n_hops ? (size_t)n_hops * PRHF_GRAD_HOP_OUTPUTS : (size_t)PRHF_GRAD_OUTPUTS);
+    rc = ensure(c, c->arena, ((size_t)(nz + nx) + (dev ? 0 : 4 * R + out_elems + 5 * path_elems)) * 8);
     if (rc != PRHF_OK) return rc;
     double* p = static_cast<double*>(c->arena.p);
     prhf::GradTraceArgs a;
@@ -1972,7 +1975,7 @@ int grad_trace_run(prhf_ctx* c, int geometry, double earth_radius_km, const doub
     a.atol = atol; a.max_step = max_step_km; a.z_ground = z_ground_km; a.z_max = z_max_km;
     a.x_min = x_min_km; a.x_max = x_max_km; a.renormalize_every = renormalize_every;
     a.fill_n = fill_n; a.fill_grad = fill_grad; a.fill_mup = fill_mup; a.status = c->h_status_dev;
-    a.geometry = geometry; a.earth_radius = earth_radius_km;
+    a.geometry = geometry; a.earth_radius = earth_radius_km; a.n_hops = n_hops; a.hop_z0 = hop_z0_km;
     double* host_paths[5] = {path_t, path_x, path_z, path_vx, path_vz};
     double* d_paths[5] = {path_t, path_x, path_z, path_vx, path_vz};
     if (dev) {
@@ -1987,18 +1990,18 @@ int grad_trace_run(prhf_ctx* c, int geometry, double earth_radius_km, const doub
         a.x0 = q; a.z0 = q + R; a.elev = q + 2 * R;
         a.ray_field = ray_field ? reinterpret_cast<const long long*>(q + 3 * R) : nullptr;
         a.out = q + 4 * R;
-        for (int k = 0; k < 5; ++k) d_paths[k] = n_paths ? a.out + PRHF_GRAD_OUTPUTS * R + k * path_elems : nullptr;
+        for (int k = 0; k < 5; ++k) d_paths[k] = n_paths ? a.out + out_elems + k * path_elems : nullptr;
     }
     // nodes a ray does not reach stay NaN (all bits set)
     for (int k = 0; k < 5 && n_paths; ++k) HIP_TRY(hipMemsetAsync(d_paths[k], 0xff, path_elems * 8, c->stream));
     a.path_t = d_paths[0]; a.path_x = d_paths[1]; a.path_z = d_paths[2]; a.path_vx = d_paths[3]; a.path_vz = d_paths[4];
     HIP_TRY(hipEventRecord(c->begin_ev(), c->stream));
-    HIP_TRY(prhf::launch_grad_trace(a, c->stream));
+    HIP_TRY(n_hops ? prhf::launch_grad_hop_trace(a, c->stream) : prhf::launch_grad_trace(a, c->stream));
     HIP_TRY(hipEventRecord(c->pending_end_ev(), c->stream));
     c->mark_timed();
     c->status_pending = true;
     if (!dev) {
-        HIP_TRY(hipMemcpyAsync(out, a.out, PRHF_GRAD_OUTPUTS * R * 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(out, a.out, out_elems * 8, hipMemcpyDeviceToHost, c->stream));
         for (int k = 0; k < 5 && n_paths; ++k)
             HIP_TRY(hipMemcpyAsync(host_paths[k], d_paths[k], path_elems * 8, hipMemcpyDeviceToHost, c->stream));
     }
@@ -2013,7 +2016,7 @@ int prhf_trace_gradient_f64(prhf_ctx* c, const double* records, int64_t n_fields
                             double x_min_km, double x_max_km, int32_t renormalize_every, double fill_n, double fill_grad,
                             double fill_mup, double* out, double* path_t, double* path_x, double* path_z, double* path_vx,
                             double* path_vz, int64_t path_stride, uint32_t flags) {
-    return grad_trace_run(c, PRHF_GEO_CARTESIAN, 0.0, records, n_fields, nz, nx, z_axis, x_axis, x0_km, z0_km, elevation_deg,
+    return grad_trace_run(c, 0, 0.0, PRHF_GEO_CARTESIAN, 0.0, records, n_fields, nz, nx, z_axis, x_axis, x0_km, z0_km, elevation_deg,
                           ray_field, n_rays, s_max_km, rtol, atol, max_step_km, z_ground_km, z_max_km, x_min_km, x_max_km,
                           renormalize_every, fill_n, fill_grad, fill_mup, out, path_t, path_x, path_z, path_vx, path_vz,
                           path_stride, flags);
@@ -2031,21 +2034,46 @@ int prhf_trace_gradient_spherical_f64(prhf_ctx* c, const double* records, int64_
     if (!(earth_radius_km > 0) || !std::isfinite(earth_radius_km))
         return fail(PRHF_EINVAL, "earth_radius_km must be positive and finite");
     // (the reference binds R_E + z_ground_km to the ground event before it subtracts, :2240)
-    return grad_trace_run(c, PRHF_GEO_SPHERICAL, earth_radius_km, records, n_fields, nr, nphi, r_axis, phi_axis, x0_km, z0_km,
+    return grad_trace_run(c, 0, 0.0, PRHF_GEO_SPHERICAL, earth_radius_km, records, n_fields, nr, nphi, r_axis, phi_axis, x0_km, z0_km,
                           elevation_deg, ray_field, n_rays, s_max_km, rtol, atol, max_step_km, earth_radius_km + z_ground_km,
                           r_max_km, phi_min, phi_max, renormalize_every, fill_n, fill_grad, fill_mup, out, path_t, path_r,
                           path_phi, path_v_r, path_v_phi, path_stride, flags);
 }
 
-int prhf_gradient_home_f64(prhf_ctx* c, int32_t geometry, const double* records, int64_t n_fields, int64_t n0, int64_t n1,
-                           const double* axis0, const double* axis1, const int64_t* group_field, const double* group_x0_km,
-                           const double* group_z0_km, int64_t n_groups, const int64_t* link_group,
-                           const double* link_target_km, int64_t n_links, const double* scan_elevation_deg, int64_t n_scan,
-                           double earth_radius_km, double s_max_km, double rtol, double atol, double max_step_km,
-                           double z_ground_km, double top, double left, double right, int32_t renormalize_every,
-                           double fill_n, double fill_grad, double fill_mup, double range_tol_km, int32_t max_iter,
-                           int32_t max_roots, double* out, int64_t* n_brackets, uint32_t flags) {
+int prhf_trace_gradient_hops_f64(prhf_ctx* c, int32_t geometry, const double* records, int64_t n_fields, int64_t n0,
+                                 int64_t n1, const double* axis0, const double* axis1, const double* x0_km,
+                                 const double* z0_km, const double* elevation_deg, const int64_t* ray_field, int64_t n_rays,
+                                 double earth_radius_km, double s_max_km, double rtol, double atol, double max_step_km,
+                                 double z_ground_km, double top, double left, double right, int32_t renormalize_every,
+                                 double fill_n, double fill_grad, double fill_mup, int32_t n_hops, double* out,
+                                 double* path_t, double* path_a, double* path_b, double* path_va, double* path_vb,
+                                 int64_t path_stride, uint32_t flags) {
     if (!c) return fail(PRHF_EINVAL, "null context");
+    if (n_hops < 1 || n_hops > PRHF_GRAD_MAX_HOPS) return fail(PRHF_EINVAL, "n_hops is 1 .. 16");
+    if (geometry != PRHF_GEO_CARTESIAN && geometry != PRHF_GEO_SPHERICAL)
+        return fail(PRHF_EINVAL, "geometry is 0 (Cartesian) or 1 (spherical)");
+    const bool sph = geometry == PRHF_GEO_SPHERICAL;
+    if (sph && (!(earth_radius_km > 0) || !std::isfinite(earth_radius_km)))
+        return fail(PRHF_EINVAL, "earth_radius_km must be positive and finite");
+    if (n_rays > 0x7fffffffLL / PRHF_GRAD_MAX_HOPS) return fail(PRHF_EINVAL, "more than 2^27 - 1 rays: trace in batches");
+    // (the spherical tracer binds R_E + z_ground_km to the ground event, prhf_trace_gradient_spherical_f64)
+    return grad_trace_run(c, n_hops, z_ground_km, geometry, sph ? earth_radius_km : 0.0, records, n_fields, n0, n1, axis0, axis1,
+                          x0_km, z0_km, elevation_deg, ray_field, n_rays, s_max_km, rtol, atol, max_step_km,
+                          sph ? earth_radius_km + z_ground_km : z_ground_km, top, left, right, renormalize_every, fill_n,
+                          fill_grad, fill_mup, out, path_t, path_a, path_b, path_va, path_vb, path_stride, flags);
+}
+
+namespace {
+// Both homing calls.  n_hops 0: prhf_gradient_home_f64 (rows of 15); else prhf_gradient_hop_home_f64.
+int grad_home_run(prhf_ctx* c, int32_t n_hops, int32_t geometry, const double* records, int64_t n_fields, int64_t n0, int64_t n1,
+                  const double* axis0, const double* axis1, const int64_t* group_field, const double* group_x0_km,
+                  const double* group_z0_km, int64_t n_groups, const int64_t* link_group,
+                  const double* link_target_km, int64_t n_links, const double* scan_elevation_deg, int64_t n_scan,
+                  double earth_radius_km, double s_max_km, double rtol, double atol, double max_step_km,
+                  double z_ground_km, double top, double left, double right, int32_t renormalize_every,
+                  double fill_n, double fill_grad, double fill_mup, double range_tol_km, int32_t max_iter,
+                  int32_t max_roots, double* out, int64_t* n_brackets, uint32_t flags) {
+    const int row_width = n_hops ? 3 + PRHF_GRAD_HOP_OUTPUTS * n_hops : PRHF_GRAD_HOME_OUTPUTS;
     if (!records || !group_field || !group_x0_km || !group_z0_km || !link_group || !link_target_km || !scan_elevation_deg ||
         !out || !n_brackets)
         return fail(PRHF_EINVAL, "null array pointer");
@@ -2086,7 +2114,7 @@ int prhf_gradient_home_f64(prhf_ctx* c, int32_t geometry, const double* records,
     if (n_links == 0) return PRHF_OK;
     ENTER_DEVICE(c->device);
     const size_t G = (size_t)n_groups, L = (size_t)n_links, E = (size_t)n_scan;
-    const size_t out_elems = L * (size_t)max_roots * PRHF_GRAD_HOME_OUTPUTS;
+    const size_t out_elems = L * (size_t)max_roots * (size_t)row_width;
     rc = ensure(c, c->arena, ((size_t)(n0 + n1) + (dev ? 0 : 3 * G + 3 * L + E + out_elems)) * 8);
     if (rc != PRHF_OK) return rc;
     double* p = static_cast<double*>(c->arena.p);
@@ -2105,7 +2133,7 @@ int prhf_gradient_home_f64(prhf_ctx* c, int32_t geometry, const double* records,
     a.fill_n = fill_n; a.fill_grad = fill_grad; a.fill_mup = fill_mup; a.status = c->h_status_dev;
     a.geometry = geometry; a.earth_radius = geometry == PRHF_GEO_SPHERICAL ? earth_radius_km : 0.0;
     h.n_groups = n_groups; h.n_links = n_links; h.n_scan = (int)n_scan; h.range_tol = range_tol_km; h.max_iter = max_iter;
-    h.max_roots = max_roots;
+    h.max_roots = max_roots; h.row_width = row_width; a.n_hops = n_hops ? n_hops : 1; a.hop_z0 = z_ground_km;
     if (dev) {
         h.group_field = reinterpret_cast<const long long*>(group_field); h.group_x0 = group_x0_km; h.group_z0 = group_z0_km;
         h.link_group = reinterpret_cast<const long long*>(link_group); h.link_target = link_target_km;
@@ -2152,6 +2180,39 @@ int prhf_gradient_home_f64(prhf_ctx* c, int32_t geometry, const double* records,
     rc = prhf_sync(c);
     for (int k = 0; k < PRHF_GRAD_HOME_COUNTERS; ++k) c->grad_home_counters[k] = counters[k];
     return rc;
+}
+}  // namespace
+
+int prhf_gradient_home_f64(prhf_ctx* c, int32_t geometry, const double* records, int64_t n_fields, int64_t n0, int64_t n1,
+                           const double* axis0, const double* axis1, const int64_t* group_field, const double* group_x0_km,
+                           const double* group_z0_km, int64_t n_groups, const int64_t* link_group,
+                           const double* link_target_km, int64_t n_links, const double* scan_elevation_deg, int64_t n_scan,
+                           double earth_radius_km, double s_max_km, double rtol, double atol, double max_step_km,
+                           double z_ground_km, double top, double left, double right, int32_t renormalize_every,
+                           double fill_n, double fill_grad, double fill_mup, double range_tol_km, int32_t max_iter,
+                           int32_t max_roots, double* out, int64_t* n_brackets, uint32_t flags) {
+    if (!c) return fail(PRHF_EINVAL, "null context");
+    return grad_home_run(c, 0, geometry, records, n_fields, n0, n1, axis0, axis1, group_field, group_x0_km, group_z0_km, n_groups,
+                         link_group, link_target_km, n_links, scan_elevation_deg, n_scan, earth_radius_km, s_max_km, rtol, atol,
+                         max_step_km, z_ground_km, top, left, right, renormalize_every, fill_n, fill_grad, fill_mup, range_tol_km,
+                         max_iter, max_roots, out, n_brackets, flags);
+}
+
+int prhf_gradient_hop_home_f64(prhf_ctx* c, int32_t geometry, const double* records, int64_t n_fields, int64_t n0, int64_t n1,
+                               const double* axis0, const double* axis1, const int64_t* group_field,
+                               const double* group_x0_km, const double* group_z0_km, int64_t n_groups,
+                               const int64_t* link_group, const double* link_target_km, int64_t n_links,
+                               const double* scan_elevation_deg, int64_t n_scan, double earth_radius_km, double s_max_km,
+                               double rtol, double atol, double max_step_km, double z_ground_km, double top, double left,
+                               double right, int32_t renormalize_every, double fill_n, double fill_grad, double fill_mup,
+                               double range_tol_km, int32_t max_iter, int32_t max_roots, int32_t n_hops, double* out,
+                               int64_t* n_brackets, uint32_t flags) {
+    if (!c) return fail(PRHF_EINVAL, "null context");
+    if (n_hops < 1 || n_hops > PRHF_GRAD_MAX_HOPS) return fail(PRHF_EINVAL, "n_hops is 1 .. 16");
+    return grad_home_run(c, n_hops, geometry, records, n_fields, n0, n1, axis0, axis1, group_field, group_x0_km, group_z0_km,
+                         n_groups, link_group, link_target_km, n_links, scan_elevation_deg, n_scan, earth_radius_km, s_max_km, rtol,
+                         atol, max_step_km, z_ground_km, top, left, right, renormalize_every, fill_n, fill_grad, fill_mup,
+                         range_tol_km, max_iter, max_roots, out, n_brackets, flags);
 }
 
 int prhf_gradient_home_counters(prhf_ctx* c, uint64_t* counters) {

@@ -339,10 +339,12 @@ __device__ __forceinline__ double grad_event_root(const GradTraceArgs& a, const 
 // those are set.  !FULL: the range-only ray of the homing kernels (prhf_gradient_homing.inc) - the same stepper,
 // controller, events and dense-output bisection, hence the same steps and the same landing node to the bit, without mu'
 // sampling, chord lengths, the apex, path stores and the second pass that replays the steps up to the midpoint; `r` and
-// `out` are not used.  Both are this one text: what !FULL leaves out stands behind `if (FULL)`.
+// `out` are not used.  Both are this one text: what !FULL leaves out stands behind `if (FULL)`.  `v_land` (optional):
+// the last path node's two velocity components of pass 0, the bits path_vx / path_vz get (prhf_gradient_hops.inc).
 template <int GEO, bool FULL>
 __device__ __forceinline__ double grad_ray(const GradTraceArgs& a, const double* g0, const double* g1, long long r,
-                                           long long field, double elev_deg, double x0_km, double z0_km, double* out) {
+                                           long long field, double elev_deg, double x0_km, double z0_km, double* out,
+                                           double* v_land = nullptr) {
     constexpr bool SPH = GEO == PRHF_GEO_SPHERICAL;
     GradLane L;
     L.f = field;
@@ -356,6 +358,7 @@ __device__ __forceinline__ double grad_ray(const GradTraceArgs& a, const double*
     double path_km = 0.0, delay = 0.0, x_apex = SPH ? a.earth_radius * zs : xs, z_apex = SPH ? xs - a.earth_radius : zs,
            x_last = x_apex;
     double x_mid = SPH ? qnan() : xs, z_mid = SPH ? qnan() : zs;
+    if (v_land) { v_land[0] = vxs; v_land[1] = vzs; }
     int n_nodes = 1, status = 3, n_rej = 0;
     unsigned n_rhs = 0;
     bool too_long = false;
@@ -533,6 +536,7 @@ __device__ __forceinline__ double grad_ray(const GradTraceArgs& a, const double*
                                 }
                                 if (FULL && ez > z_apex) { z_apex = ez; x_apex = ex; }         // np.nanargmax: the first maximum
                                 x_last = ex;
+                                if (v_land) { v_land[0] = e2; v_land[1] = e3; }
                                 if (FULL && a.path_t) {
                                     if (nodes < a.path_stride) {
                                         const long long o = r * a.path_stride + nodes;

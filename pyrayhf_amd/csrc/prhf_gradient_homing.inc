@@ -25,12 +25,25 @@
 //   result   grad_home_result_kernel<GEO>: one record per lane again: the full two-pass ray at the row's elevation,
 //            its twelve outputs behind the row's first three.  Only the records of the work list become rays.
 // The refine and result launches are sized for n_links max_roots records; wavefronts beyond the list's length leave.
+// MULTI-HOP HOMING (prhf_gradient_hop_home_f64, DESIGN.md section 4.12) is these four kernels with g.n_hops > 1 or a
+// row_width other than PRHF_GRAD_HOME_OUTPUTS: D(e) is grad_hops<GEO, false> of prhf_gradient_hops.inc - the landing x
+// of hop n_hops - 1, for one hop grad_ray itself - and a result row holds the row of every hop behind its first three.
 // Counters (queue[]): 0 records, 1 rays traced by the refine lanes, 2 ray slots (64 per trip of a refine wavefront's
 // loop), 3 refine wavefronts with work: lane utilisation = [1] / [2].
 
 namespace {
 
 constexpr int kGradHomeOutputs = PRHF_GRAD_HOME_OUTPUTS;
+
+// (prhf_gradient_hops.inc)
+template <int GEO, bool FULL>
+__device__ __forceinline__ double grad_hops(const GradTraceArgs& a, const double* g0, const double* g1, long long r,
+                                            long long field, double elev_deg, double x0_km, double z0_km, double* out);
+// Column j of an unused hop row (launch x, z, elevation, then the tracer's twelve): NaN, status -1, the counters and the pad 0
+__device__ __forceinline__ double grad_hop_unused(int j) { return j < 10 ? qnan() : j == 10 ? -1.0 : 0.0; }
+__device__ __forceinline__ void grad_hop_unused_row(double* row) {
+    for (int j = 0; j < PRHF_GRAD_HOP_OUTPUTS; ++j) row[j] = grad_hop_unused(j);
+}
 
 __device__ __forceinline__ void grad_home_stage_axes(const GradTraceArgs& a, double* axes) {
     for (int i = threadIdx.x; i < a.n0 + a.n1; i += blockDim.x) axes[i] = i < a.n0 ? a.a0[i] : a.a1[i - a.n0];
@@ -51,8 +64,8 @@ __global__ __launch_bounds__(PRHF_GRAD_TRACE_THREADS) void grad_home_scan_kernel
     if (f < 0 || f >= h.g.n_fields)       // (device-resident group_field: not checked by the host) no ray, no bracket
         post_status(h.g.status, (unsigned)PRHF_STATUS_BADFIELD);
     else
-        d = grad_ray<GEO, false>(h.g, grad_axes, grad_axes + h.g.n0, 0, f, h.scan_elev[i], h.group_x0[grp], h.group_z0[grp],
-                                 nullptr);
+        d = grad_hops<GEO, false>(h.g, grad_axes, grad_axes + h.g.n0, 0, f, h.scan_elev[i], h.group_x0[grp], h.group_z0[grp],
+                                  nullptr);
     h.scan_d[grp * h.n_scan + i] = d;
 }
 
@@ -64,9 +77,13 @@ __global__ __launch_bounds__(64) void grad_home_bracket_kernel(const GradHomeArg
     const long long g = bad ? 0 : g_given;
     const double t = bad ? qnan() : h.link_target[link];            // (a NaN target brackets nothing)
     const double* d = h.scan_d + g * h.n_scan;
-    double* rows = h.out + link * ((long long)h.max_roots * kGradHomeOutputs);
+    double* rows = h.out + link * ((long long)h.max_roots * h.row_width);
     if (bad && lane == 0) post_status(h.g.status, (unsigned)PRHF_STATUS_BADGROUP);
-    for (int k = lane; k < h.max_roots * kGradHomeOutputs; k += 64) rows[k] = (k % kGradHomeOutputs == 1) ? -1.0 : qnan();
+    const bool hop_rows = h.row_width != kGradHomeOutputs;          // (the one-hop call's unused rows are NaN throughout)
+    for (int k = lane; k < h.max_roots * h.row_width; k += 64) {
+        const int col = k % h.row_width;
+        rows[k] = col == 1 ? -1.0 : (hop_rows && col >= 3) ? grad_hop_unused((col - 3) % PRHF_GRAD_HOP_OUTPUTS) : qnan();
+    }
     int found = 0;
     for (int base = 0; base < h.n_scan; base += 64) {
         const int i = base + lane;
@@ -131,7 +148,7 @@ __global__ __launch_bounds__(PRHF_GRAD_TRACE_THREADS) void grad_home_refine_kern
                     const double xs = lo - g_lo * ((hi - lo) / (g_hi - g_lo));
                     if (xs > lo && xs < hi) x = xs;
                 }
-                const double dx = grad_ray<GEO, false>(h.g, grad_axes, grad_axes + h.g.n0, 0, f, x, x0, z0, nullptr);
+                const double dx = grad_hops<GEO, false>(h.g, grad_axes, grad_axes + h.g.n0, 0, f, x, x0, z0, nullptr);
                 ++rays;
                 if (!finite64(dx)) {
                     status = 2;                                      // the ray does not land inside the bracket
@@ -161,7 +178,7 @@ __global__ __launch_bounds__(PRHF_GRAD_TRACE_THREADS) void grad_home_refine_kern
         }
     }
     if (mine) {
-        double* row = h.out + (link * h.max_roots + rank) * kGradHomeOutputs;
+        double* row = h.out + (link * h.max_roots + rank) * h.row_width;
         row[0] = best_e;
         row[1] = (double)status;
         row[2] = (double)i;
@@ -184,8 +201,11 @@ __global__ __launch_bounds__(PRHF_GRAD_TRACE_THREADS) void grad_home_result_kern
     const int4 rec = reinterpret_cast<const int4*>(h.work)[w];
     const long long link = rec.x;
     const long long g = h.link_group[link];
-    double* row = h.out + (link * h.max_roots + rec.y) * kGradHomeOutputs;
-    (void)grad_ray<GEO, true>(h.g, grad_axes, grad_axes + h.g.n0, 0, h.group_field[g], row[0], h.group_x0[g], h.group_z0[g], row + 3);
+    double* row = h.out + (link * h.max_roots + rec.y) * h.row_width;
+    if (h.row_width == kGradHomeOutputs)
+        (void)grad_ray<GEO, true>(h.g, grad_axes, grad_axes + h.g.n0, 0, h.group_field[g], row[0], h.group_x0[g], h.group_z0[g], row + 3);
+    else
+        (void)grad_hops<GEO, true>(h.g, grad_axes, grad_axes + h.g.n0, 0, h.group_field[g], row[0], h.group_x0[g], h.group_z0[g], row + 3);
 }
 
 }  // namespace

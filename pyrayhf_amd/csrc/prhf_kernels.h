@@ -341,6 +341,9 @@ struct HomeArgs {
     int n_scan;
     double range_tol;            // [km]
     int max_iter, max_roots;
+    // D(e) is the landing x of hop g.n_hops - 1 (1: the tracer's ray).  row_width: PRHF_GRAD_HOME_OUTPUTS for the one-hop
+    // call; 3 + PRHF_GRAD_HOP_OUTPUTS g.n_hops for the multi-hop call, whose rows hold every hop's row with its launch.
+    int row_width;
     double* scan_d;              // (n_groups, n_scan) scratch: ground range of every scan ray
     int* work;                   // (n_links max_roots, 4) scratch: (link, rank, interval, 0) of the brackets to refine; 16-byte aligned
     unsigned* queue;             // home_queue_bytes() of scratch: the refine launch's counters, the work list's length
@@ -433,12 +436,21 @@ struct GradTraceArgs {
     double s_max, rtol, atol, max_step, z_ground, z_max, x_min, x_max;
     double fill_n, fill_grad, fill_mup;
     double earth_radius;         // spherical only
+    // multi-hop calls only (prhf_gradient_hops.inc): hops per ray, and z_ground_km as the caller gave it (the launch
+    // altitude of every hop after the first; z_ground above carries R_E + z_ground_km in a spherical call)
+    int n_hops;
+    double hop_z0;
 };
 #define PRHF_FIELD_MAX_AXES 8000   // n0 + n1 at most: both axes are staged in 64 KiB of LDS
 inline size_t field_axes_lds_bytes(int n0, int n1) { return (size_t)(n0 + n1) * 8; }
 hipError_t launch_field_pack(const FieldPackArgs& a, hipStream_t stream);
 hipError_t launch_field_sample(const FieldSampleArgs& a, hipStream_t stream);
 hipError_t launch_grad_trace(const GradTraceArgs& a, hipStream_t stream);
+#define PRHF_GRAD_MAX_HOPS 16
+#define PRHF_GRAD_HOP_OUTPUTS (3 + PRHF_GRAD_OUTPUTS)    // launch x, launch z, launch elevation, then the tracer's twelve
+// Chains of a.n_hops rays: a.out is (n_rays, n_hops, PRHF_GRAD_HOP_OUTPUTS), the paths
+// (n_rays n_hops, path_stride).
+hipError_t launch_grad_hop_trace(const GradTraceArgs& a, hipStream_t stream);
 
 // Point-to-point homing for the gradient tracers (prhf_gradient_homing.inc): the rays of a transmitter that land at a
 // link's target coordinate.
@@ -457,10 +469,13 @@ struct GradHomeArgs {
     int n_scan;
     double range_tol;            // [km]
     int max_iter, max_roots;
+    // D(e) is the landing x of hop g.n_hops - 1 (1: the tracer's ray).  row_width: PRHF_GRAD_HOME_OUTPUTS for the one-hop
+    // call; 3 + PRHF_GRAD_HOP_OUTPUTS g.n_hops for the multi-hop call, whose rows hold every hop's row with its launch.
+    int row_width;
     double* scan_d;              // (n_groups, n_scan) scratch: ground range of every scan ray
     int* work;                   // (n_links max_roots, 4) scratch: (link, rank, interval, 0) of the brackets to refine; 16-byte aligned
     unsigned* queue;             // PRHF_GRAD_HOME_COUNTERS words of scratch, zeroed by the scan kernel
-    double* out;                 // (n_links, max_roots, PRHF_GRAD_HOME_OUTPUTS)
+    double* out;                 // (n_links, max_roots, row_width)
     long long* n_brackets;       // (n_links)
 };
 hipError_t launch_grad_home(const GradHomeArgs& h, hipStream_t stream);   // scan, brackets, refinement, result rays: four kernels

@@ -3299,6 +3299,7 @@ hipError_t launch_vfo_shortx(const KArgs& a, long long grid_blocks, size_t lds_b
 #include "prhf_skip.inc"
 #include "prhf_gradient.inc"
 #include "prhf_gradient_homing.inc"
+#include "prhf_gradient_hops.inc"
 #include "prhf_gradient_skip.inc"
 
 // Resident workgroups per CU the runtime predicts for the fused kernel (diagnostics).

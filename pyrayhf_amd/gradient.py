@@ -36,7 +36,9 @@ __all__ = ["build_refractive_index_interpolator_cartesian", "build_refractive_in
            "trace_rays_cartesian_gradient", "trace_fan_cartesian_gradient", "trace_ray_spherical_gradient",
            "trace_rays_spherical_gradient", "trace_fan_spherical_gradient", "home_rays_cartesian_gradient",
            "home_rays_spherical_gradient", "refractive_field_device", "skip_distance_cartesian_gradient",
-           "skip_distance_spherical_gradient", "muf_cartesian_gradient", "muf_spherical_gradient", "STATUS_NAMES"]
+           "skip_distance_spherical_gradient", "muf_cartesian_gradient", "muf_spherical_gradient", "STATUS_NAMES",
+           "trace_hops_cartesian_gradient", "trace_hops_spherical_gradient", "trace_hop_fan_cartesian_gradient",
+           "trace_hop_fan_spherical_gradient", "home_hops_cartesian_gradient", "home_hops_spherical_gradient"]
 
 STATUS_NAMES = ("ground", "domain", "length", "failure")          # reference library.py:1391-1398
 _KEYS = ("group_path_km", "group_delay_sec", "x_midpoint", "z_midpoint", "ground_range_km", "x_apex_km", "z_apex_km",
@@ -45,6 +47,8 @@ _INT_KEYS = ("status", "n_nodes", "n_rhs", "n_rejected")
 _PATH_KEYS = ("t", "x", "z", "vx", "vz")
 _PATH_KEYS_SPHERICAL = ("t", "r", "phi", "v_r", "v_phi")
 _MAX_AXES = 8000
+_MAX_HOPS = 16
+_HOP_LAUNCH_KEYS = ("launch_x_km", "launch_z_km", "launch_elevation_deg")
 
 
 class RefractiveField:
@@ -530,11 +534,14 @@ def trace_fan_spherical_gradient(field, elevation_deg, x0_km=0.0, z0_km=0.0, s_m
 
 
 def _home(field, geometry, name, target_x_km, x0_km, z0_km, controls, scan_elevation_deg, max_roots, range_tol_km, max_iter,
-          earth_radius):
+          earth_radius, n_hops=None):
     """Both homing calls: every field of ``field`` is a group launched from ``(x0_km, z0_km)``, the links are
-    (field, target) in C order.  ``controls``: the tracer's, as ``_trace`` takes them."""
+    (field, target) in C order.  ``controls``: the tracer's, as ``_trace`` takes them.  ``n_hops``: homing on the landing
+    of hop ``n_hops - 1`` (``prhf_gradient_hop_home_f64``), whose rows hold every hop."""
     from .tracers import default_scan_elevations
     _need_geometry(field, geometry, name)
+    if n_hops is not None:
+        n_hops = _check_hops(n_hops)
     t = np.ascontiguousarray(np.atleast_1d(np.asarray(target_x_km, dtype=np.float64)))
     if t.ndim != 1 or t.size == 0:
         raise ValueError("target_x_km must be 1-D and not empty (the targets)")
@@ -562,21 +569,27 @@ def _home(field, geometry, name, target_x_km, x0_km, z0_km, controls, scan_eleva
     group_z = np.full(n_groups, float(z0_km))
     link_g = np.ascontiguousarray(np.repeat(group_f, t.size))
     link_t = np.ascontiguousarray(np.tile(t, n_groups))
-    out = np.empty((link_g.size, max_roots, 15), dtype=np.float64)
+    width = 15 if n_hops is None else 3 + 15 * n_hops
+    out = np.empty((link_g.size, max_roots, width), dtype=np.float64)
     n_br = np.empty(link_g.size, dtype=np.int64)
     rec = field.records()
     ctx = field._ctx()
-    _native.raise_for(ctx.gradient_home(0 if earth_radius is None else 1, rec.data_ptr(), n_groups, field.axis0.size,
-                                        field.axis1.size, field.axis0.ctypes.data, field.axis1.ctypes.data,
-                                        group_f.ctypes.data, group_x.ctypes.data, group_z.ctypes.data, n_groups,
-                                        link_g.ctypes.data, link_t.ctypes.data, link_g.size, scan.ctypes.data, scan.size,
-                                        0.0 if earth_radius is None else earth_radius, ctl, field.fills, range_tol_km,
-                                        max_iter, max_roots, out.ctypes.data, n_br.ctypes.data, 0))
+    head = (0 if earth_radius is None else 1, rec.data_ptr(), n_groups, field.axis0.size, field.axis1.size,
+            field.axis0.ctypes.data, field.axis1.ctypes.data, group_f.ctypes.data, group_x.ctypes.data, group_z.ctypes.data,
+            n_groups, link_g.ctypes.data, link_t.ctypes.data, link_g.size, scan.ctypes.data, scan.size,
+            0.0 if earth_radius is None else earth_radius, ctl, field.fills, range_tol_km, max_iter, max_roots)
+    if n_hops is None:
+        _native.raise_for(ctx.gradient_home(*head, out.ctypes.data, n_br.ctypes.data, 0))
+    else:
+        _native.raise_for(ctx.gradient_hop_home(*head, n_hops, out.ctypes.data, n_br.ctypes.data, 0))
     lead = (n_groups, t.size)
-    out = out.reshape(lead + (max_roots, 15))
+    out = out.reshape(lead + (max_roots, width))
     res = {"n_brackets": n_br.reshape(lead), "elevation_deg": out[..., 0].copy(), "status": out[..., 1].astype(np.int64)}
     idx = out[..., 2]
     res["scan_index"] = np.where(np.isfinite(idx), idx, -1.0).astype(np.int64)
+    if n_hops is not None:
+        res.update(_hop_dict(out[..., 3:].reshape(lead + (max_roots, n_hops, 15)), "ray_status"))
+        return res
     unused = res["status"] < 0
     for i, k in enumerate(_KEYS):
         v = out[..., 3 + i]
@@ -641,6 +654,187 @@ def home_rays_spherical_gradient(field, target_x_km, x0_km=0.0, z0_km=0.0, s_max
     return _home(field, "spherical", "home_rays_spherical_gradient", target_x_km, x0_km, z0_km,
                  _controls(s_max_km, rtol, atol, max_step_km, z_ground_km, r_max_km, phi_min, phi_max, renormalize_every),
                  scan_elevation_deg, max_roots, range_tol_km, max_iter, R_E)
+
+
+def _check_hops(n_hops):
+    if isinstance(n_hops, bool) or int(n_hops) != n_hops or not 1 <= int(n_hops) <= _MAX_HOPS:
+        raise ValueError(f"n_hops is an integer in 1 .. {_MAX_HOPS}")
+    return int(n_hops)
+
+
+def _hop_dict(rows, status_key="status"):
+    """The per-hop arrays and the totals from hop rows ``(..., H, 15)`` (include/prhf.h: launch x, z, elevation, then
+    the tracer's twelve; an unused row is NaN with status -1 and counters 0)."""
+    n_hops = rows.shape[-2]
+    res = {k: rows[..., i].copy() for i, k in enumerate(_HOP_LAUNCH_KEYS)}
+    for i, k in enumerate(_KEYS):
+        v = rows[..., 3 + i]
+        res[status_key if k == "status" else k] = v.astype(np.int64) if k in _INT_KEYS else v.copy()
+    st = res[status_key]
+    res["n_landed"] = (st == 0).sum(axis=-1)
+    for k in ("group_path_km", "group_delay_sec"):
+        total = np.zeros(rows.shape[:-2])
+        for h in range(n_hops):                                             # in hop order, over the used hops
+            total = np.where(st[..., h] >= 0, total + res[k][..., h], total)
+        res["total_" + k] = np.where(st[..., 0] >= 0, total, np.nan)         # (an unused slot of a homing call: NaN)
+    res["total_ground_range_km"] = np.where(res["n_landed"] == n_hops, res["ground_range_km"][..., n_hops - 1], np.nan)
+    return res
+
+
+def _trace_hops(field, x0, z0, elev, idx, controls, n_hops, return_paths, earth_radius=None):
+    """``_trace`` for chains of ``n_hops`` hops (``prhf_trace_gradient_hops_f64``): arrays ``(R, H)``, paths
+    ``(R, H, max n_nodes)``."""
+    path_keys = _PATH_KEYS if earth_radius is None else _PATH_KEYS_SPHERICAL
+    s_max_km, rtol, atol, max_step_km, z_ground_km, top, left, right, renormalize_every = controls
+    max_step = np.inf if max_step_km is None else float(max_step_km)
+    if max_step <= 0:
+        raise ValueError("`max_step` must be positive.")                   # solve_ivp's message
+    n = x0.size
+    if idx is None:
+        if field.n_fields != 1:
+            raise ValueError("field_index is needed when the field holds several frequencies")
+        idx = np.zeros(n, dtype=np.int64)
+    if n and (idx.min() < 0 or idx.max() >= field.n_fields):
+        raise ValueError("field_index outside [0, n_fields)")
+    order = np.lexsort((elev, idx))
+    xs, zs, es, fs = (np.ascontiguousarray(v[order]) for v in (x0, z0, elev, idx))
+    ctl = (s_max_km, rtol, atol, max_step, z_ground_km, top, left, right, int(renormalize_every) if renormalize_every else 0)
+    out = np.empty((n, n_hops, 15), dtype=np.float64)
+    paths = {}
+    if n:
+        rec = field.records()
+        ctx = field._ctx()
+
+        def launch(bufs, stride):
+            _native.raise_for(ctx.trace_gradient_hops(
+                0 if earth_radius is None else 1, rec.data_ptr(), field.n_fields, field.axis0.size, field.axis1.size,
+                field.axis0.ctypes.data, field.axis1.ctypes.data, xs.ctypes.data, zs.ctypes.data, es.ctypes.data,
+                fs.ctypes.data, n, 0.0 if earth_radius is None else earth_radius, ctl, field.fills, n_hops, out.ctypes.data,
+                bufs, stride, 0))
+        launch(None, 0)
+        if return_paths:
+            # the same chains again, now that the longest path is known: the steps are deterministic
+            stride = max(int(out[:, :, 11].max()), 1)
+            bufs = [np.empty((n, n_hops, stride), dtype=np.float64) for _ in path_keys]
+            launch([b.ctypes.data for b in bufs], stride)
+            for k, b in zip(path_keys, bufs):
+                unsorted = np.empty_like(b)
+                unsorted[order] = b
+                paths[k] = unsorted
+    elif return_paths:
+        for k in path_keys:
+            paths[k] = np.empty((0, n_hops, 0))
+    back = np.empty_like(out)
+    back[order] = out
+    res = _hop_dict(back)
+    res.update(paths)
+    return res
+
+
+def trace_hops_cartesian_gradient(field, x0_km, z0_km, elevation_deg, n_hops, field_index=None, s_max_km=5000.0, *,
+                                  rtol=1e-7, atol=1e-9, max_step_km=None, z_ground_km=0.0, z_min_km=-1.0, z_max_km=1000.0,
+                                  x_min_km=-1e6, x_max_km=1e6, renormalize_every=50, return_paths=False):
+    """Multi-hop rays through ``field`` (a ``RefractiveField``, Cartesian): ``R`` chains of ``n_hops`` (1 .. 16) hops in
+    one launch, a chain per lane (``prhf_trace_gradient_hops_f64``).  The arguments are
+    ``trace_rays_cartesian_gradient``'s and every hop runs under them.  A hop that lands (status 0) is reflected off the
+    ground: the next hop launches at ``(ground_range_km, z_ground_km)`` with the elevation
+    ``degrees(arctan2(-vz, vx))`` of the landing node; a chain ends with its first hop that does not land.
+
+    Returns that call's keys with a trailing hop axis, ``(R, H)`` - every used hop bit for bit what
+    ``trace_rays_cartesian_gradient`` returns for the hop's ``launch_x_km``, ``launch_z_km``, ``launch_elevation_deg``,
+    which are returned as well; unused hops are NaN with ``status`` -1 and the counts 0 -, and per chain ``n_landed``,
+    ``total_group_path_km`` and ``total_group_delay_sec`` (summed in hop order over the used hops) and
+    ``total_ground_range_km`` (the landing x of the last hop, NaN unless all ``n_hops`` hops landed).  With
+    ``return_paths`` also ``t, x, z, vx, vz``: ``(R, H, max n_nodes)`` padded with NaN."""
+    _need_geometry(field, "cartesian", "trace_hops_cartesian_gradient")
+    n_hops = _check_hops(n_hops)
+    shape, flat, idx = _broadcast_rays(x0_km, z0_km, elevation_deg, field_index)
+    res = _trace_hops(field, flat[0], flat[1], flat[2], idx,
+                      _controls(s_max_km, rtol, atol, max_step_km, z_ground_km, z_max_km, x_min_km, x_max_km,
+                                renormalize_every), n_hops, return_paths)
+    return {k: v.reshape(shape + v.shape[1:]) for k, v in res.items()}
+
+
+def trace_hop_fan_cartesian_gradient(field, elevation_deg, n_hops, x0_km=0.0, z0_km=0.0, s_max_km=5000.0, **controls):
+    """Every elevation of ``elevation_deg`` ``(E,)`` from ``(x0_km, z0_km)`` in every field of ``field``: the dict of
+    ``trace_hops_cartesian_gradient`` (whose keyword controls these are) with arrays of shape ``(F, E, H)``, one launch."""
+    e = np.atleast_1d(np.asarray(elevation_deg, dtype=np.float64))
+    if e.ndim != 1:
+        raise ValueError("elevation_deg must be 1-D (the elevations of the fan)")
+    _need_geometry(field, "cartesian", "trace_hop_fan_cartesian_gradient")
+    idx = np.arange(field.n_fields, dtype=np.int64)[:, None]
+    return trace_hops_cartesian_gradient(field, x0_km, z0_km, e[None, :], n_hops, idx, s_max_km, **controls)
+
+
+def _spherical_controls(field, R_E, r_max_km):
+    if R_E is None:
+        R_E = field.R_E
+    if float(R_E) != field.R_E:
+        raise ValueError(f"R_E={R_E} is not the field's ({field.R_E})")
+    return field.R_E, field.R_E + 1200.0 if r_max_km is None else r_max_km                      # :2226-2227
+
+
+def trace_hops_spherical_gradient(field, x0_km, z0_km, elevation_deg, n_hops, field_index=None, s_max_km=6000.0, *,
+                                  R_E=None, z_ground_km=0.0, r_max_km=None, phi_min=-np.pi, phi_max=np.pi, rtol=1e-7,
+                                  atol=1e-9, max_step_km=2.0, renormalize_every=50, return_paths=False):
+    """The same over a spherical Earth: the arguments are ``trace_rays_spherical_gradient``'s, the reflected elevation is
+    ``degrees(arctan2(-v_r, v_phi))`` of the landing node, and the next hop launches at the surface arc
+    ``ground_range_km = R_E phi`` of the landing, altitude ``z_ground_km``.  With ``return_paths`` also ``t, r, phi, v_r,
+    v_phi, x, z``: ``(R, H, max n_nodes)``."""
+    _need_geometry(field, "spherical", "trace_hops_spherical_gradient")
+    n_hops = _check_hops(n_hops)
+    R_E, r_max_km = _spherical_controls(field, R_E, r_max_km)
+    shape, flat, idx = _broadcast_rays(x0_km, z0_km, elevation_deg, field_index)
+    res = _trace_hops(field, flat[0], flat[1], flat[2], idx,
+                      _controls(s_max_km, rtol, atol, max_step_km, z_ground_km, r_max_km, phi_min, phi_max, renormalize_every),
+                      n_hops, return_paths, earth_radius=R_E)
+    if return_paths:
+        res["x"] = R_E * res["phi"]                                         # :2277-2278
+        res["z"] = res["r"] - R_E
+    return {k: v.reshape(shape + v.shape[1:]) for k, v in res.items()}
+
+
+def trace_hop_fan_spherical_gradient(field, elevation_deg, n_hops, x0_km=0.0, z0_km=0.0, s_max_km=6000.0, **controls):
+    """Every elevation of ``elevation_deg`` ``(E,)`` from ``(x0_km, z0_km)`` in every field of ``field``: the dict of
+    ``trace_hops_spherical_gradient`` (whose keyword controls these are) with arrays of shape ``(F, E, H)``, one launch."""
+    e = np.atleast_1d(np.asarray(elevation_deg, dtype=np.float64))
+    if e.ndim != 1:
+        raise ValueError("elevation_deg must be 1-D (the elevations of the fan)")
+    _need_geometry(field, "spherical", "trace_hop_fan_spherical_gradient")
+    idx = np.arange(field.n_fields, dtype=np.int64)[:, None]
+    return trace_hops_spherical_gradient(field, x0_km, z0_km, e[None, :], n_hops, idx, s_max_km, **controls)
+
+
+def home_hops_cartesian_gradient(field, target_x_km, n_hops, x0_km=0.0, z0_km=0.0, s_max_km=5000.0, *,
+                                 scan_elevation_deg=None, max_roots=4, range_tol_km=0.05, max_iter=64, rtol=1e-7, atol=1e-9,
+                                 max_step_km=None, z_ground_km=0.0, z_min_km=-1.0, z_max_km=1000.0, x_min_km=-1e6,
+                                 x_max_km=1e6, renormalize_every=50):
+    """Homing on the landing of hop ``n_hops - 1`` (the 2F, 3F .. modes of a long link through a tilted ionosphere):
+    ``home_rays_cartesian_gradient`` with the landing coordinate of a ray replaced by ``total_ground_range_km`` of
+    ``trace_hops_cartesian_gradient``'s chain (``prhf_gradient_hop_home_f64``); scan, brackets,
+    refinement, statuses and arguments are that call's.
+
+    Returns ``n_brackets`` ``(F, T)``, with shape ``(F, T, max_roots)`` ``elevation_deg``, ``status``, ``scan_index``,
+    ``n_landed`` and the three totals, and with shape ``(F, T, max_roots, H)`` the per-hop keys of
+    ``trace_hops_cartesian_gradient`` for the result chain, bit for bit what that call returns at ``elevation_deg`` (the
+    tracer's own ``status`` is ``ray_status`` here).  Unused slots are NaN with ``status``, ``scan_index`` and
+    ``ray_status`` -1 and the counts 0."""
+    return _home(field, "cartesian", "home_hops_cartesian_gradient", target_x_km, x0_km, z0_km,
+                 _controls(s_max_km, rtol, atol, max_step_km, z_ground_km, z_max_km, x_min_km, x_max_km, renormalize_every),
+                 scan_elevation_deg, max_roots, range_tol_km, max_iter, None, n_hops=n_hops)
+
+
+def home_hops_spherical_gradient(field, target_x_km, n_hops, x0_km=0.0, z0_km=0.0, s_max_km=6000.0, *, R_E=None,
+                                 scan_elevation_deg=None, max_roots=4, range_tol_km=0.05, max_iter=64, z_ground_km=0.0,
+                                 r_max_km=None, phi_min=-np.pi, phi_max=np.pi, rtol=1e-7, atol=1e-9, max_step_km=2.0,
+                                 renormalize_every=50):
+    """The same over a spherical Earth: ``home_rays_spherical_gradient``'s arguments, ``trace_hops_spherical_gradient``'s
+    chains."""
+    _need_geometry(field, "spherical", "home_hops_spherical_gradient")
+    R_E, r_max_km = _spherical_controls(field, R_E, r_max_km)
+    return _home(field, "spherical", "home_hops_spherical_gradient", target_x_km, x0_km, z0_km,
+                 _controls(s_max_km, rtol, atol, max_step_km, z_ground_km, r_max_km, phi_min, phi_max, renormalize_every),
+                 scan_elevation_deg, max_roots, range_tol_km, max_iter, R_E, n_hops=n_hops)
 
 
 def _search_controls(scan_elevation_deg, elev_tol_deg, max_iter, controls):

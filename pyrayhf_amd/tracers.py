@@ -12,6 +12,11 @@ range, the rays that land there (point-to-point homing, the oblique ionogram of 
 ``skip_distance_cartesian_snells`` / ``skip_distance_spherical_snells`` find the smallest ground range a
 (profile, frequency) reaches, and ``muf_cartesian_snells`` / ``muf_spherical_snells`` the frequency at which that skip
 distance equals a link's range.
+
+There is no multi-hop call here: over a stratified ionosphere n hops are n copies of one hop (n times its ground range,
+path and delay at the same elevation), so these tracers need nothing new.  Through a horizontally varying ionosphere a
+hop is not a copy of the one before it; ``pyrayhf_amd.gradient.trace_hops_cartesian_gradient`` and its kin chain them
+(DESIGN.md section 4.12).
 """
 
 from __future__ import annotations

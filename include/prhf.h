@@ -142,6 +142,12 @@ int prhf_ctx_set_math(prhf_ctx* ctx, int level);
  *                        points is summed from eight nodes at real-valued indices - Gauss-Legendre abscissae, weights
  *                        that make the rule exact for the discrete sum of polynomials of degree 7 - within 1e-12 of
  *                        the full sum; a pair with such a piece too close to X + Y = 1 keeps the sum of before)
+ *   "panel_nodes"        8: every piece of the panel sum takes eight lanes, the launch of before this option bit for bit
+ *                        (4: a piece of at most four points, or one whose segment's continuation reaches X + Y = 1 at
+ *                        least 16 piece lengths from its centre, takes four lanes - its own points, or the four nodes of
+ *                        the Gauss rule of the counting measure on its points, exact for the same polynomials; every
+ *                        other piece takes eight lanes as before.  The same pairs take the rule and the same pairs fall
+ *                        back; values stay within 1e-12.  Values between 4 and 8 count as 8)
  *   "pair_plan"          0: every wavefront computes the integers that steer its pair's strided sum itself, the launch of
  *                        before this option bit for bit (1: where "strided_lower" applies and a workgroup settles its
  *                        reflection heights one frequency per thread - at most 512 frequencies, grids of fewer than 65536

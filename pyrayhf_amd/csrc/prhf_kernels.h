@@ -110,6 +110,8 @@ struct SegDev {
                                      // (option strided_lower)
     int panel_lower;                 // with strided_lower: those segments are summed from eight nodes per piece where the
                                      // pair's guard allows it (option panel_lower)
+    int panel_nodes;                 // with panel_lower: 4 - pieces far from X + Y = 1 take four nodes on four lanes; 8 - every
+                                     // piece takes eight lanes (option panel_nodes)
     int pair_plan;                   // with sp_off > 0: the workgroup plans its pairs' sums one pair per thread (option
                                      // pair_plan; plan_pairs in prhf_kernels.hip)
     int thread_scan;                 // X mode: reflection heights settled one frequency per thread while the candidate

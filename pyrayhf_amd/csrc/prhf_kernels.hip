@@ -163,12 +163,19 @@ __device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirs
 constexpr int kStridedLowerBit = 1 << 30;
 // ... and bit 29: where they do, the panel sum comes first (SegDev::panel_lower)
 constexpr int kPanelLowerBit = 1 << 29;
+// ... and bit 28: pieces far from X + Y = 1 are summed from four nodes on four lanes (SegDev::panel_nodes == 4)
+constexpr int kPanelNodes4Bit = 1 << 28;
+// a piece takes four nodes where X + Y = 1 lies at least kPanelFar n + 2 indices from its centre
+constexpr int kPanelFar = 16;
 // what the main loop reports about the panel sum in the bits above kPanelStateShift of LeanResult::first (a grid point's
 // index stays below 2^27): 1 the pair's lower segments took it, 2 the pair was eligible and kept the sum of before
 constexpr int kPanelStateShift = 28;
 #define PRHF_PANEL_NODES_DECL [[maybe_unused]] static __device__ const double kPanelNodes[8]   // (the table's own abscissae: the pairs below hold them as offsets)
 #define PRHF_PANEL_PAIRS_DECL static __device__ __attribute__((aligned(16))) const double kPanelPairs[(PRHF_PANEL_N_MAX + 1) * 16]
 #include "prhf_panel_table.inc"
+#define PRHF_PANEL4_PAIRS_DECL static __device__ __attribute__((aligned(16))) const double kPanel4Pairs[(PRHF_PANEL4_N_MAX + 1) * 8]
+#include "prhf_panel4_table.inc"
+static_assert(PRHF_PANEL4_N_MAX == PRHF_PANEL_N_MAX, "both tables end at the same piece length");
 static_assert(PRHF_PANEL_BLOCK == 64 || PRHF_PANEL_BLOCK == 128, "the weight table ends at 128 points");
 static_assert(PRHF_PANEL_BLOCK <= PRHF_PANEL_N_MAX, "a piece holds at most one block");
 static_assert(PRHF_PANEL_MIN_SEGMENT >= 1 && (PRHF_PANEL_MIN_SEGMENT & (PRHF_PANEL_MIN_SEGMENT - 1)) == 0,
@@ -1418,7 +1425,8 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
     sp_off = uniform(sp_off);
     const bool lower_req = (sp_off & kStridedLowerBit) != 0;
     const bool panel_req = (sp_off & kPanelLowerBit) != 0;
-    sp_off &= ~(kStridedLowerBit | kPanelLowerBit);
+    const bool nodes4_req = (sp_off & kPanelNodes4Bit) != 0;
+    sp_off &= ~(kStridedLowerBit | kPanelLowerBit | kPanelNodes4Bit);
     int panel_state = 0;                               // (waits in a vector register, where the result travels anyway)
     asm volatile("" : "+v"(panel_state));
     if (STRIDED && sp_off > 0 && n_seg > 0 && first == 0 && last_special >= 0 && end >= PRHF_TOP3_MIN_POINTS) {
@@ -1540,7 +1548,10 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
         // next segment's (the next lane's) or at the next multiple.  Guard, per piece of more than eight points: the
         // index where the segment's continuation reaches X + Y = 1 lies at least max(32, 4 n) from the piece's centre,
         // and 1 - X - Y >= 1e-6 at both levels of the segment; one piece that fails, or one guess that does not bracket,
-        // leaves the whole pair to the sums below.  Everything here is a function of the pair alone.
+        // leaves the whole pair to the sums below.  With option panel_nodes = 4 a piece far from that index, or of at most
+        // four points, takes four lanes instead - its own points, or the four nodes of the Gauss rule of the counting
+        // measure on its n points (kPanel4Pairs), exact for the same polynomials - sixteen pieces per wave-iteration; the
+        // guard and with it the pairs that fall back stay the same.  Everything here is a function of the pair alone.
         if (lower && panel_req && end < 65536) {
             bool panel_ok = false;
             int S_P = 0;
@@ -1583,7 +1594,6 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
                 __builtin_memcpy(&ge, &ve, sizeof ge);
                 const int j_s = uniform((int)(gs.x * kj)), j_e = uniform((int)(ge.x * kj));
                 const int n_blk = (E_P - S_P) >> kLogB, total = n_blk + (j_e - j_s);
-                const int l7 = lane & 7;
                 const double s10 = uniform(-10.0 / n1);
                 const double r2 = 1.4142135623730951;
                 bool fail = false;
@@ -1630,14 +1640,52 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
                     }
                     fail = __ballot((live && !ok) || (big && !clear)) != 0ull;
                     if (fail) break;
-                    const unsigned word = n > 0 ? (unsigned)p | ((unsigned)n << 16) : 0u;
-                    const int n_live = min(63, total - s0);
-                    for (int it = 0; it * 8 < n_live; ++it) {
-                        // eight pieces of eight lanes
-                        const unsigned w = (unsigned)__builtin_amdgcn_ds_bpermute(((lane >> 3) + it * 8) << 2, (int)word);
-                        const int pp = (int)(w & 0xffffu), nn = (int)(w >> 16);
+                    unsigned word = n > 0 ? (unsigned)p | ((unsigned)n << 16) : 0u;
+                    // the list the evaluation reads: n4 four-lane pieces from lane 0 up, n8 eight-lane pieces from lane
+                    // flip down (option panel_nodes = 8: every piece takes eight lanes, the list is the lanes' own)
+                    int n4 = 0, n8 = min(63, total - s0);
+                    unsigned flip = 0u;
+                    if (nodes4_req) {
+                        // Four lanes: a piece of at most four points (its own), or one whose segment's continuation
+                        // reaches X + Y = 1 at least kPanelFar n + 2 indices from its centre - above it where sl > 0,
+                        // below it where sl < 0.  The stretch has 1 - m_i + c0 = (1 + c0) exp(-10 i / (N - 1)), so
+                        // 1 - m_sing + c0 is set against that at the index so far from the centre; multiplied by sl
+                        // both sides read the same (no logarithm, no division; the two spare indices cover the
+                        // single-precision exponential).  Everything else takes eight lanes as before.
+                        const double kk = (double)(kPanelFar * n + 2);
+                        const double i_far = ((double)p + 0.5 * (double)(n - 1)) + (sl < 0.0 ? -kk : kk);
+                        const double e_far = (double)__builtin_amdgcn_exp2f((float)(i_far * (s10 * 1.4426950408889634)));
+                        const bool c4 = n > 0 && (n <= 4 || (g_lo >= 1e-6 && g_hi >= 1e-6 &&
+                                                            (1.0 + c0) * sl - gap <= sl * ((1.0 + c0) * e_far)));
+                        const unsigned long long b4 = __ballot(c4), b8 = __ballot(n > 0 && !c4);
+                        const int r4 = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(b4 >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b4, 0u));
+                        const int r8 = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(b8 >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b8, 0u));
+                        n4 = __builtin_popcountll(b4);
+                        n8 = __builtin_popcountll(b8);
+                        // (a permutation of the 64 lanes: the lanes without a piece fill the middle with their zeros)
+                        const int dest = c4 ? r4 : (n > 0 ? 63 - r8 : n4 + (lane - r4 - r8));
+                        word = (unsigned)__builtin_amdgcn_ds_permute(dest << 2, (int)word);
+                        flip = 63u;
+                    }
+                    // (one copy of the evaluation loop for both classes: lanes per piece and table by scalar selects)
+#pragma unroll 1
+                    for (int cls = nodes4_req ? 0 : 1; cls < 2; ++cls) {
+                    const int sh = cls == 0 ? 2 : 3, cnt = cls == 0 ? n4 : n8;
+                    const unsigned fl = cls == 0 ? 0u : flip;
+                    const char* tab = reinterpret_cast<const char*>(cls == 0 ? kPanel4Pairs : kPanelPairs);
+                    // (the class' own words, zeros elsewhere: the last wave-iteration may reach past them)
+                    const unsigned lst = ((unsigned)lane ^ fl) < (unsigned)cnt ? word : 0u;
+                    const unsigned lk16 = (unsigned)(lane & ((1 << sh) - 1)) << 4;
+                    int src = (int)((((unsigned)lane >> sh) ^ fl) << 2);
+                    const int step = fl != 0u ? -(256 >> sh) : 256 >> sh;
+#pragma unroll 1
+                    for (int k0 = 0; k0 < cnt; k0 += 64 >> sh) {
+                        // sixteen pieces of four lanes, or eight pieces of eight lanes
+                        const unsigned w = (unsigned)__builtin_amdgcn_ds_bpermute(src, (int)lst);
+                        src += step;
+                        const int pp = (int)(w & 0xffffu);
                         // the node's offset from the piece's first point, its weight
-                        const double2 ow = reinterpret_cast<const double2*>(kPanelPairs)[nn * 8 + l7];
+                        const double2 ow = *reinterpret_cast<const double2*>(tab + (((w >> 16) << (sh + 4)) | lk16));
                         const double xk = (double)pp + ow.x;
                         const double xr = __builtin_rint(xk);
                         const u32x2 vm = __builtin_amdgcn_raw_buffer_load_b64(rsrc, (unsigned)(int)xr * (unsigned)sizeof(double2), 0, 0);
@@ -1650,6 +1698,7 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
                         gm.x = (1.0 + c0) - ek;
                         gm.y = ow.y * (sc1 * ek);
                         accm = lean_step<MODE, false, POLY, HINT, G>(gm, span, a0v, kj, cX, hcY2, accm, wc, viol, nodes_v, cur);
+                    }
                     }
                 }
                 panel_ok = !fail;
@@ -2427,7 +2476,8 @@ __device__ __forceinline__ void run_items(const KArgs& a, const SegDev& sg, cons
     // (bit 30: the segments below the top three take the strided sum too - an offset stays below 2^27 entries)
     const int sp_off = (pairs && sg.sp_off > 0)
                            ? uniform((int)(sg.sp_off - sg.mult_off) | (sg.strided_lower ? kStridedLowerBit : 0) |
-                                     (sg.strided_lower && sg.panel_lower ? kPanelLowerBit : 0)) : 0;
+                                     (sg.strided_lower && sg.panel_lower ? kPanelLowerBit : 0) |
+                                     (sg.strided_lower && sg.panel_lower && sg.panel_nodes == 4 ? kPanelNodes4Bit : 0)) : 0;
     const long long pair_base = prof_local * F;
     const int first_item = block_in_prof * W, round_items = blocks_per_prof * W;
     // Few pairs on a long grid (one profile, the reference's own call; SegDev::slots > 0): a pair is cut into C <= S

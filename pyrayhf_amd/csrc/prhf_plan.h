@@ -88,6 +88,11 @@ struct Knobs {
                                        // into pieces of at most PRHF_PANEL_BLOCK points inside one segment, each summed from
                                        // eight nodes at real-valued indices (a pair with a piece too close to
                                        // X + Y = 1 keeps strided_lower's sum; 0: the launch of before, bit for bit)
+    double panel_nodes = 4;            // ... and a piece whose segment's continuation reaches X + Y = 1 at least 16 piece
+                                       // lengths from its centre, or that holds at most four points, is summed from the four
+                                       // nodes of the Gauss rule of the counting measure on four lanes, sixteen pieces per
+                                       // wave-iteration (8, or anything but 4: eight lanes for every piece,
+                                       // the launch of before, bit for bit)
     double pair_plan = 1;              // ... and the integers that steer such a pair's sum - first points of the top three
                                        // segments, the strided stretch of each - are computed once per pair, by one thread
                                        // while the workgroup makes its candidate list, instead of by all 64 lanes of the
@@ -129,6 +134,7 @@ const KnobName kKnobNames[] = {
     {"strided_top", &Knobs::strided_top, 0, 1},
     {"strided_lower", &Knobs::strided_lower, 0, 1},
     {"panel_lower", &Knobs::panel_lower, 0, 1},
+    {"panel_nodes", &Knobs::panel_nodes, 4, 8},
     {"pair_plan", &Knobs::pair_plan, 0, 1},
     {"pair_plan_cap", &Knobs::pair_plan_cap, 0, 1024},
 };
@@ -565,6 +571,7 @@ inline int plan_launch(const LaunchShape& sh, const prhf_segment* segs, int32_t 
             s.sp_off = pieces.sp_off[p];
             s.strided_lower = kn.strided_lower != 0;
             s.panel_lower = s.strided_lower && kn.panel_lower != 0;
+            s.panel_nodes = s.panel_lower && kn.panel_nodes == 4 ? 4 : 8;
             s.pair_plan = slice_plans_pairs(s, tall, n_freq, lds_levels, kn) ? 1 : 0;
             pl.any_plan = pl.any_plan || s.pair_plan != 0;
         }

@@ -39,7 +39,8 @@ extern "C" {
                               *    prhf_gradient_home_f64, prhf_snell_skip_f64, prhf_snell_muf_f64 and
                               *    prhf_pair_plan_counters, prhf_panel_counters, and prhf_field_build_f64,
                               *    prhf_gradient_skip_f64, prhf_gradient_muf_f64, prhf_gradient_skip_counters,
-                              *    prhf_trace_gradient_hops_f64, prhf_gradient_hop_home_f64) */
+                              *    prhf_trace_gradient_hops_f64, prhf_gradient_hop_home_f64, and
+                              *    prhf_residual_many_f64, prhf_vfo_residual_many_f64) */
 
 /* return codes */
 #define PRHF_OK        0
@@ -274,6 +275,50 @@ int prhf_vfo_residual_f64(prhf_ctx* ctx, const double* freq_mhz, int64_t n_freq,
                           int64_t n_alt, int64_t prof_stride_elems, int64_t alt_stride_elems,
                           const double* multiplier, int32_t n_points, int32_t mode, const double* vh_obs,
                           double* vh_out, double* residual_out, double* cost_out, uint32_t flags);
+
+/*
+ * The residual stage for MANY ionograms on one common frequency grid, and the winning candidate of each, in one launch.
+ * vh_obs is (n_iono, n_freq); NaN (any non-finite value) means "ionogram i has no observation at grid frequency f".
+ * Per ionogram i and candidate row p of that ionogram, with K_i = { f : vh_obs[i, f] finite } and m = vh_model[p, :]:
+ * the rule of prhf_residual_f64 (residual_VH, reference library.py:660-669) on the compacted pair
+ * (vh_model[p, K_i], vh_obs[i, K_i]), i.e. after minimize_parameters' filter (:741-745) -
+ *     fill    = max(mean of |m[f]| over f in K_i with m[f] not NaN, 100), NaN when there is no such f;
+ *     r[p, f] = vh_obs[i, f] - (m[f], or fill where m[f] is NaN)   for f in K_i;   NaN for f outside K_i;
+ *     cost    = sum of r^2 over K_i;   NaN when K_i is empty
+ * - bit for bit what prhf_residual_f64 returns for that compacted pair.
+ * best[i] is the first row with the smallest finite cost among the rows of ionogram i and best_cost[i] that cost;
+ * -1 and NaN when no cost of the ionogram is finite (or it has no row).
+ * Two layouts:
+ *   own candidates     ionogram_of_row (n_rows) int32, non-decreasing, values in [0, n_iono): row p belongs to that
+ *                      ionogram (groups may be ragged or empty).  residual_out (n_rows, n_freq) or NULL, cost_out
+ *                      (n_rows), best_out (n_iono) GLOBAL row indices, best_cost_out (n_iono).
+ *   shared candidates  ionogram_of_row == NULL: every row is a candidate of every ionogram.  residual_out must be
+ *                      NULL, cost_out is (n_iono, n_rows), best_out (n_iono) candidate indices.
+ * cost_out, best_out and best_cost_out are required.  n_freq <= 4096; n_rows, n_iono < 2^31; at most 2^36 pairs.
+ * Host buffers: an ionogram_of_row entry outside [0, n_iono) or below its predecessor is PRHF_EINVAL.  Device buffers
+ * (PRHF_FLAG_DEVICE_PTRS) are not inspected by the host: a row whose entry is out of range gets a NaN cost (and NaN
+ * residuals) and nothing outside vh_obs is read; no error is raised for it.  Flags: PRHF_FLAG_DEVICE_PTRS,
+ * PRHF_FLAG_ASYNC (device pointers only).
+ */
+int prhf_residual_many_f64(prhf_ctx* ctx, const double* vh_model, int64_t n_rows, const double* vh_obs, int64_t n_iono,
+                           int64_t n_freq, const int32_t* ionogram_of_row, double* residual_out, double* cost_out,
+                           int64_t* best_out, double* best_cost_out, uint32_t flags);
+
+/*
+ * prhf_vfo_batch_f64 followed by prhf_residual_many_f64 in one call, the twin of prhf_vfo_residual_f64: the operator
+ * runs once on the n_prof profiles and the n_freq grid frequencies (with shared candidates: once for all ionograms),
+ * the modeled traces never leave HBM.  freq_mhz is the common grid: finite (PRHF_EINVAL otherwise, host buffers),
+ * and positive and ascending if the traces are to mean anything.  vh_out (n_prof, n_freq) may be NULL.  The other
+ * arguments and flags (PRHF_FLAG_DEVICE_PTRS, PRHF_FLAG_ASYNC, PRHF_FLAG_GRID_STABLE, PRHF_FLAG_SHARED_FIELD) are
+ * those of prhf_vfo_residual_f64 and prhf_residual_many_f64 (n_rows = n_prof).  The operator's values are those of
+ * prhf_vfo_batch_f64 on the same arguments.
+ */
+int prhf_vfo_residual_many_f64(prhf_ctx* ctx, const double* freq_mhz, int64_t n_freq, const double* den,
+                               const double* bmag, const double* bpsi, const double* alt, int64_t n_prof,
+                               int64_t n_alt, int64_t prof_stride_elems, int64_t alt_stride_elems,
+                               const double* multiplier, int32_t n_points, int32_t mode, const double* vh_obs,
+                               int64_t n_iono, const int32_t* ionogram_of_row, double* vh_out, double* residual_out,
+                               double* cost_out, int64_t* best_out, double* best_cost_out, uint32_t flags);
 
 /*
  * Stratified Snell's-law ray tracing over a flat Earth for n_rays rays (one wavefront each).

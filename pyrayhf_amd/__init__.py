@@ -25,6 +25,7 @@ from .gradient import (STATUS_NAMES, RefractiveField, build_mup_function,       
                        trace_rays_cartesian_gradient, trace_rays_spherical_gradient)
 from .tracers import (home_rays_cartesian_snells, home_rays_spherical_snells, muf_cartesian_snells,  # noqa: E402
                       muf_spherical_snells, skip_distance_cartesian_snells, skip_distance_spherical_snells)
+from .fitting import brute_force_fit_many, minimize_parameters_many, residual_VH_many               # noqa: E402
 
 __all__ = ["logger", "__version__", "STATUS_NAMES", "RefractiveField", "build_mup_function",
            "build_refractive_index_interpolator_cartesian", "build_refractive_index_interpolator_spherical",
@@ -36,4 +37,5 @@ __all__ = ["logger", "__version__", "STATUS_NAMES", "RefractiveField", "build_mu
            "refractive_field_device", "skip_distance_cartesian_gradient", "skip_distance_spherical_gradient",
            "muf_cartesian_gradient", "muf_spherical_gradient", "trace_hops_cartesian_gradient",
            "trace_hops_spherical_gradient", "trace_hop_fan_cartesian_gradient", "trace_hop_fan_spherical_gradient",
-           "home_hops_cartesian_gradient", "home_hops_spherical_gradient"]
+           "home_hops_cartesian_gradient", "home_hops_spherical_gradient", "residual_VH_many", "brute_force_fit_many",
+           "minimize_parameters_many"]

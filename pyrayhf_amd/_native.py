@@ -68,6 +68,12 @@ _PROTOTYPES = {
         ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
         ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
         ctypes.c_uint32]),
+    "prhf_residual_many_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                              ctypes.c_int64, ctypes.c_int64] + [ctypes.c_void_p] * 5 + [ctypes.c_uint32]),
+    "prhf_vfo_residual_many_f64": (ctypes.c_int, [
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
+        ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64] + [ctypes.c_void_p] * 6 + [ctypes.c_uint32]),
     "prhf_snell_cartesian_f64": (ctypes.c_int, [
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
@@ -308,6 +314,19 @@ class Context:
         return self._lib.prhf_vfo_residual_f64(self._h, freq, n_freq, den, bmag, bpsi, alt, n_prof, n_alt,
                                                prof_stride, alt_stride, mult, n_points, mode, vh_obs,
                                                vh or None, residual or None, cost or None, flags)
+
+    def residual_many(self, vh_model, n_rows, vh_obs, n_iono, n_freq, ionogram_of_row, residual, cost, best, best_cost,
+                      flags):
+        """``ionogram_of_row``: (n_rows) int32, or None for shared candidates (``cost`` is then (n_iono, n_rows))."""
+        return self._lib.prhf_residual_many_f64(self._h, vh_model, n_rows, vh_obs, n_iono, n_freq,
+                                                ionogram_of_row or None, residual or None, cost, best, best_cost, flags)
+
+    def vfo_residual_many(self, freq, n_freq, den, bmag, bpsi, alt, n_prof, n_alt, prof_stride, alt_stride, mult,
+                          n_points, mode, vh_obs, n_iono, ionogram_of_row, vh, residual, cost, best, best_cost, flags):
+        return self._lib.prhf_vfo_residual_many_f64(self._h, freq, n_freq, den, bmag, bpsi, alt, n_prof, n_alt,
+                                                    prof_stride, alt_stride, mult, n_points, mode, vh_obs, n_iono,
+                                                    ionogram_of_row or None, vh or None, residual or None, cost, best,
+                                                    best_cost, flags)
 
     def snell_cartesian(self, freq_hz, elev, prof_idx, n_rays, den, bmag, bpsi, alt, n_prof, n_alt, alt_stride,
                         mode, out, path_x, path_z, path_stride, flags):

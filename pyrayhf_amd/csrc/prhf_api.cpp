@@ -192,11 +192,18 @@ int ensure(prhf_ctx* c, DevBuf& b, size_t bytes) {
     return PRHF_OK;
 }
 
-// Optional second stage of a launch: residual rows against one observed trace (prhf_vfo_residual_f64).
+// Optional second stage of a launch: residual rows against one observed trace (prhf_vfo_residual_f64), or - n_iono > 0 -
+// against the traces of many ionograms on the launch's frequency grid (prhf_vfo_residual_many_f64).
 struct Residual {
-    const double* vh_obs;   // (n_freq)
+    const double* vh_obs;   // (n_freq); many ionograms: (n_iono, n_freq), NaN where there is no observation
     double* residual;       // (n_prof, n_freq) or null
-    double* cost;           // (n_prof) or null
+    double* cost;           // (n_prof) or null; many ionograms: (n_prof), shared candidates (n_iono, n_prof), never null
+    // many ionograms only:
+    int64_t n_iono = 0;
+    const int32_t* ionogram_of_row = nullptr;   // (n_prof), or null: shared candidates
+    int64_t* best = nullptr;                    // (n_iono)
+    double* best_cost = nullptr;                // (n_iono)
+    size_t cost_elems(int64_t n_prof) const { return (size_t)n_prof * (size_t)(n_iono && !ionogram_of_row ? n_iono : 1); }
 };
 
 int status_to_code(unsigned bits) {
@@ -231,6 +238,9 @@ struct Call {
     double* vh_dev;             // the modeled trace and the residual stage's other arrays on the device
     const double* d_obs;
     double *d_res, *d_cost;
+    const int32_t* d_ion;       // many ionograms: ionogram_of_row, best and best_cost on the device
+    int64_t* d_best;
+    double* d_best_cost;
     // update_tables:
     unsigned* order_made;       // the short-grid O launch's blocks by cost (short_order_kernel), or null: index order
 };
@@ -334,7 +344,10 @@ int stage_inputs(Call& k, const LaunchPlan& pl, prhf::KArgs& a) {
     } else {
         const size_t n_alt_rows = k.alt_stride ? (size_t)n_prof : 1;
         const size_t n_field_rows = k.shared_field ? 1 : (size_t)n_prof;
-        const size_t post_elems = k.post ? (size_t)n_freq + out_elems + (size_t)n_prof : 0;
+        size_t post_elems = k.post ? (size_t)n_freq + out_elems + (size_t)n_prof : 0;
+        if (k.post && k.post->n_iono)      // observations, residual rows, costs, best and best_cost, ionogram_of_row (int32)
+            post_elems = (size_t)k.post->n_iono * ((size_t)n_freq + 2) + (k.post->residual ? out_elems : 0) +
+                         k.post->cost_elems(n_prof) + ((size_t)n_prof + 1) / 2;
         // a stable host grid lives in a device buffer of its own, uploaded on first sight
         if (k.flags & PRHF_FLAG_GRID_STABLE) {
             k.grid = find_host_grid(c, k.mult, mult_len);
@@ -443,12 +456,34 @@ int stage_inputs(Call& k, const LaunchPlan& pl, prhf::KArgs& a) {
     k.d_obs = k.post ? k.post->vh_obs : nullptr;
     k.d_res = k.post ? k.post->residual : nullptr;
     k.d_cost = k.post ? k.post->cost : nullptr;
-    if (k.post && !k.dev) {
+    k.d_ion = k.post ? k.post->ionogram_of_row : nullptr;
+    k.d_best = k.post ? k.post->best : nullptr;
+    k.d_best_cost = k.post ? k.post->best_cost : nullptr;
+    if (k.post && !k.dev && !k.post->n_iono) {
         double* p0 = k.d_out + out_elems;
         HIP_TRY(hipMemcpyAsync(p0, k.post->vh_obs, (size_t)n_freq * 8, hipMemcpyHostToDevice, c->stream));
         k.d_obs = p0;
         k.d_res = k.post->residual ? p0 + n_freq : nullptr;
         k.d_cost = k.post->cost ? p0 + n_freq + out_elems : nullptr;
+    } else if (k.post && !k.dev) {
+        const Residual& r = *k.post;
+        const size_t obs_elems = (size_t)r.n_iono * (size_t)n_freq;
+        double* p0 = k.d_out + out_elems;
+        HIP_TRY(hipMemcpyAsync(p0, r.vh_obs, obs_elems * 8, hipMemcpyHostToDevice, c->stream));
+        k.d_obs = p0;
+        p0 += obs_elems;
+        k.d_res = r.residual ? p0 : nullptr;
+        if (r.residual) p0 += out_elems;
+        k.d_cost = p0;
+        p0 += r.cost_elems(n_prof);
+        k.d_best_cost = p0;
+        p0 += r.n_iono;
+        k.d_best = reinterpret_cast<int64_t*>(p0);
+        p0 += r.n_iono;
+        if (r.ionogram_of_row && n_prof > 0) {
+            HIP_TRY(hipMemcpyAsync(p0, r.ionogram_of_row, (size_t)n_prof * 4, hipMemcpyHostToDevice, c->stream));
+            k.d_ion = reinterpret_cast<const int32_t*>(p0);
+        }
     }
     return PRHF_OK;
 }
@@ -641,6 +676,55 @@ int launch_short_kind(prhf_ctx* c, const LaunchPlan& pl, const ShortKind& sk, co
     return PRHF_OK;
 }
 
+// The many-ionogram residual stage on device arrays: masked residuals and costs, then every ionogram's winner
+int launch_many(prhf_ctx* c, const double* vh_model, int64_t n_rows, const double* vh_obs, int64_t n_iono, int64_t n_freq,
+                const int32_t* ionogram_of_row, double* residual, double* cost, int64_t* best, double* best_cost) {
+    prhf::ResidualManyArgs m;
+    m.vh_model = vh_model;
+    m.vh_obs = vh_obs;
+    m.ionogram_of_row = ionogram_of_row;
+    m.n_rows = n_rows;
+    m.n_items = ionogram_of_row ? n_rows : n_iono * n_rows;
+    m.n_iono = (int)n_iono;
+    m.n_freq = (int)n_freq;
+    m.items_per_wave = PRHF_MANY_ITEMS_PER_WAVE;
+    m.residual = residual;
+    m.cost = cost;
+    HIP_TRY(prhf::launch_residual_many(m, c->stream));
+    HIP_TRY(prhf::launch_residual_best(cost, ionogram_of_row, n_rows, (int)n_iono, reinterpret_cast<long long*>(best), best_cost,
+                                       c->stream));
+    return PRHF_OK;
+}
+
+// What the two many-ionogram entries ask of their arguments, before any device is touched.  freq_mhz: the fused entry's
+// grid, or null.
+int check_many(const double* freq_mhz, int64_t n_freq, int64_t n_rows, const double* vh_obs, int64_t n_iono,
+               const int32_t* ionogram_of_row, const double* residual_out, const double* cost_out, const int64_t* best_out,
+               const double* best_cost_out, uint32_t flags) {
+    if (!vh_obs || !cost_out || !best_out || !best_cost_out) return fail(PRHF_EINVAL, "null array pointer");
+    if (n_rows < 0 || n_iono < 1 || n_freq < 1) return fail(PRHF_EINVAL, "bad shape");
+    if (n_freq > PRHF_MANY_MAX_FREQ)
+        return fail(PRHF_EINVAL, "n_freq %lld exceeds the many-ionogram limit of %d grid frequencies", (long long)n_freq,
+                    PRHF_MANY_MAX_FREQ);
+    if (n_rows > 0x7fffffffLL || n_iono > 0x7fffffffLL) return fail(PRHF_EINVAL, "bad shape: more than 2^31 - 1 rows or ionograms");
+    if (!ionogram_of_row && residual_out)
+        return fail(PRHF_EINVAL, "shared candidates have no dense residual output");
+    if (!ionogram_of_row && n_rows > 0 && n_iono > (int64_t)((1LL << 36) / n_rows))
+        return fail(PRHF_EINVAL, "bad shape: more than 2^36 (ionogram, candidate) pairs");
+    if (flags & PRHF_FLAG_DEVICE_PTRS) return PRHF_OK;
+    if (freq_mhz)
+        for (int64_t f = 0; f < n_freq; ++f)
+            if (!std::isfinite(freq_mhz[f])) return fail(PRHF_EINVAL, "freq_mhz[%lld] is not finite: the common grid must be", (long long)f);
+    if (ionogram_of_row)
+        for (int64_t p = 0; p < n_rows; ++p) {
+            if (ionogram_of_row[p] < 0 || ionogram_of_row[p] >= n_iono)
+                return fail(PRHF_EINVAL, "ionogram_of_row[%lld] outside [0, n_iono)", (long long)p);
+            if (p > 0 && ionogram_of_row[p] < ionogram_of_row[p - 1])
+                return fail(PRHF_EINVAL, "ionogram_of_row[%lld] decreases: the rows of an ionogram must be contiguous", (long long)p);
+        }
+    return PRHF_OK;
+}
+
 // Every kernel of the operator, in the order and on the streams the plan sets
 int launch_all(Call& k, const LaunchPlan& pl, prhf::KArgs& a) {
     prhf_ctx* c = k.c;
@@ -690,8 +774,15 @@ int download_and_sync(Call& k) {
     if (!k.dev && k.post) {
         if (k.post->residual)
             HIP_TRY(hipMemcpyAsync(k.post->residual, k.d_res, out_elems * 8, hipMemcpyDeviceToHost, c->stream));
-        if (k.post->cost)
+        if (k.post->cost && !k.post->n_iono)
             HIP_TRY(hipMemcpyAsync(k.post->cost, k.d_cost, (size_t)k.n_prof * 8, hipMemcpyDeviceToHost, c->stream));
+        if (k.post->n_iono) {
+            if (k.post->cost_elems(k.n_prof))
+                HIP_TRY(hipMemcpyAsync(k.post->cost, k.d_cost, k.post->cost_elems(k.n_prof) * 8, hipMemcpyDeviceToHost,
+                                       c->stream));
+            HIP_TRY(hipMemcpyAsync(k.post->best, k.d_best, (size_t)k.post->n_iono * 8, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipMemcpyAsync(k.post->best_cost, k.d_best_cost, (size_t)k.post->n_iono * 8, hipMemcpyDeviceToHost, c->stream));
+        }
     }
     if (k.flags & PRHF_FLAG_ASYNC) return PRHF_OK;
     const int rc = prhf_sync(c);
@@ -765,7 +856,10 @@ int run(prhf_ctx* c, const double* freq, int64_t n_freq, const double* den, cons
         }
     }
 #endif
-    if (post) HIP_TRY(prhf::launch_residual(k.vh_dev, k.d_obs, n_prof, (int)n_freq, k.d_res, k.d_cost, c->stream));
+    if (post && post->n_iono) {
+        if ((rc = launch_many(c, k.vh_dev, n_prof, k.d_obs, post->n_iono, n_freq, k.d_ion, k.d_res, k.d_cost, k.d_best,
+                              k.d_best_cost)) != PRHF_OK) return rc;
+    } else if (post) HIP_TRY(prhf::launch_residual(k.vh_dev, k.d_obs, n_prof, (int)n_freq, k.d_res, k.d_cost, c->stream));
     if (timed_launch) {
         HIP_TRY(hipEventRecord(c->pending_end_ev(), c->stream));
         c->mark_timed();
@@ -1065,6 +1159,32 @@ int prhf_vfo_residual_f64(prhf_ctx* ctx, const double* freq_mhz, int64_t n_freq,
                multiplier, n_points, &seg, 1, vh_out, flags, &post);
 }
 
+int prhf_vfo_residual_many_f64(prhf_ctx* ctx, const double* freq_mhz, int64_t n_freq, const double* den,
+                               const double* bmag, const double* bpsi, const double* alt, int64_t n_prof,
+                               int64_t n_alt, int64_t prof_stride_elems, int64_t alt_stride_elems,
+                               const double* multiplier, int32_t n_points, int32_t mode, const double* vh_obs,
+                               int64_t n_iono, const int32_t* ionogram_of_row, double* vh_out, double* residual_out,
+                               double* cost_out, int64_t* best_out, double* best_cost_out, uint32_t flags) {
+    if (!freq_mhz) return fail(PRHF_EINVAL, "null array pointer");
+    int rc = check_many(freq_mhz, n_freq, n_prof, vh_obs, n_iono, ionogram_of_row, residual_out, cost_out, best_out,
+                        best_cost_out, flags);
+    if (rc != PRHF_OK) return rc;
+    prhf_segment seg;
+    seg.prof_begin = 0;
+    seg.prof_end = n_prof;
+    seg.mode = mode;
+    seg.n_points = n_points;
+    seg.mult_offset = 0;
+    seg.out_offset = 0;
+    Residual post{vh_obs, residual_out, cost_out};
+    post.n_iono = n_iono;
+    post.ionogram_of_row = ionogram_of_row;
+    post.best = best_out;
+    post.best_cost = best_cost_out;
+    return run(ctx, freq_mhz, n_freq, den, bmag, bpsi, alt, n_prof, n_alt, prof_stride_elems, alt_stride_elems,
+               multiplier, n_points, &seg, 1, vh_out, flags, &post);
+}
+
 int prhf_mu_mup_f64(prhf_ctx* c, const double* X, const double* Y, const double* psi_deg, int64_t n,
                     int32_t mode, double* mu_out, double* mup_out, uint32_t flags) {
     if (!c) return fail(PRHF_EINVAL, "null context");
@@ -1256,6 +1376,62 @@ int prhf_residual_f64(prhf_ctx* c, const double* vh_model, const double* vh_obs,
     if (!dev) {
         if (residual_out) HIP_TRY(hipMemcpyAsync(residual_out, dR, pf * 8, hipMemcpyDeviceToHost, c->stream));
         if (cost_out) HIP_TRY(hipMemcpyAsync(cost_out, dC, (size_t)n_prof * 8, hipMemcpyDeviceToHost, c->stream));
+    }
+    if (flags & PRHF_FLAG_ASYNC) return PRHF_OK;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return PRHF_OK;
+}
+
+int prhf_residual_many_f64(prhf_ctx* c, const double* vh_model, int64_t n_rows, const double* vh_obs, int64_t n_iono,
+                           int64_t n_freq, const int32_t* ionogram_of_row, double* residual_out, double* cost_out,
+                           int64_t* best_out, double* best_cost_out, uint32_t flags) {
+    if (!vh_model) return fail(PRHF_EINVAL, "null array pointer");
+    int rc = check_many(nullptr, n_freq, n_rows, vh_obs, n_iono, ionogram_of_row, residual_out, cost_out, best_out,
+                        best_cost_out, flags);
+    if (rc != PRHF_OK) return rc;
+    if (!c) return fail(PRHF_EINVAL, "null context");
+    if (flags & ~(PRHF_FLAG_DEVICE_PTRS | PRHF_FLAG_ASYNC)) return fail(PRHF_EINVAL, "unknown flag bits");
+    const bool dev = (flags & PRHF_FLAG_DEVICE_PTRS) != 0;
+    if ((flags & PRHF_FLAG_ASYNC) && !dev) return fail(PRHF_EINVAL, "PRHF_FLAG_ASYNC needs device pointers");
+    ENTER_DEVICE(c->device);
+    const size_t pf = (size_t)n_rows * (size_t)n_freq, obs_elems = (size_t)n_iono * (size_t)n_freq;
+    const size_t cost_elems = (size_t)n_rows * (size_t)(ionogram_of_row ? 1 : n_iono);
+    const double *dM = vh_model, *dO = vh_obs;
+    const int32_t* dI = ionogram_of_row;
+    double *dR = residual_out, *dC = cost_out, *dBC = best_cost_out;
+    int64_t* dB = best_out;
+    if (!dev) {
+        const size_t elems = pf + obs_elems + (residual_out ? pf : 0) + cost_elems + 2 * (size_t)n_iono + ((size_t)n_rows + 1) / 2;
+        if ((rc = ensure(c, c->arena, elems * 8)) != PRHF_OK) return rc;
+        double* p0 = static_cast<double*>(c->arena.p);
+        if (pf) HIP_TRY(hipMemcpyAsync(p0, vh_model, pf * 8, hipMemcpyHostToDevice, c->stream));
+        dM = p0;
+        p0 += pf;
+        HIP_TRY(hipMemcpyAsync(p0, vh_obs, obs_elems * 8, hipMemcpyHostToDevice, c->stream));
+        dO = p0;
+        p0 += obs_elems;
+        dR = residual_out ? p0 : nullptr;
+        if (residual_out) p0 += pf;
+        dC = p0;
+        p0 += cost_elems;
+        dBC = p0;
+        p0 += n_iono;
+        dB = reinterpret_cast<int64_t*>(p0);
+        p0 += n_iono;
+        if (ionogram_of_row && n_rows > 0) {
+            HIP_TRY(hipMemcpyAsync(p0, ionogram_of_row, (size_t)n_rows * 4, hipMemcpyHostToDevice, c->stream));
+            dI = reinterpret_cast<const int32_t*>(p0);
+        }
+    }
+    HIP_TRY(hipEventRecord(c->begin_ev(), c->stream));
+    if ((rc = launch_many(c, dM, n_rows, dO, n_iono, n_freq, dI, dR, dC, dB, dBC)) != PRHF_OK) return rc;
+    HIP_TRY(hipEventRecord(c->pending_end_ev(), c->stream));
+    c->mark_timed();
+    if (!dev) {
+        if (residual_out && pf) HIP_TRY(hipMemcpyAsync(residual_out, dR, pf * 8, hipMemcpyDeviceToHost, c->stream));
+        if (cost_elems) HIP_TRY(hipMemcpyAsync(cost_out, dC, cost_elems * 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(best_out, dB, (size_t)n_iono * 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(best_cost_out, dBC, (size_t)n_iono * 8, hipMemcpyDeviceToHost, c->stream));
     }
     if (flags & PRHF_FLAG_ASYNC) return PRHF_OK;
     HIP_TRY(hipStreamSynchronize(c->stream));

@@ -543,6 +543,24 @@ hipError_t launch_grad_muf(const GradMufArgs& m, hipStream_t stream);
 hipError_t launch_residual(const double* vh_model, const double* vh_obs, long long n_prof, int n_freq,
                            double* residual, double* cost, hipStream_t stream);
 
+// Many ionograms on one frequency grid (prhf_residual_many.inc): an item is a (candidate row, ionogram) pair
+#define PRHF_MANY_MAX_FREQ 4096          // grid frequencies: a wave keeps 12 bytes of LDS for each
+#define PRHF_MANY_ITEMS_PER_WAVE 16
+struct ResidualManyArgs {
+    const double* vh_model;              // (n_rows, n_freq)
+    const double* vh_obs;                // (n_iono, n_freq), NaN: no observation
+    const int* ionogram_of_row;          // (n_rows), or null: shared candidates - every row against every ionogram
+    long long n_rows;
+    long long n_items;                   // n_rows, or n_iono n_rows with shared candidates (item q = i n_rows + row)
+    int n_iono, n_freq, items_per_wave;
+    double* residual;                    // (n_rows, n_freq) or null; own candidates only
+    double* cost;                        // (n_items)
+};
+hipError_t launch_residual_many(const ResidualManyArgs& a, hipStream_t stream);
+// best (n_iono): the first row of the smallest finite cost (a global row; shared candidates: the candidate), -1: none
+hipError_t launch_residual_best(const double* cost, const int* ionogram_of_row, long long n_rows, int n_iono, long long* best,
+                                double* best_cost, hipStream_t stream);
+
 }  // namespace prhf
 
 #endif

@@ -3302,6 +3302,7 @@ hipError_t launch_residual(const double* vh_model, const double* vh_obs, long lo
     return hipGetLastError();
 }
 
+#include "prhf_residual_many.inc"
 #include "prhf_short.inc"
 
 static const void* short_kernel_for(int threads, int lanes) {

@@ -23,7 +23,8 @@ from . import _native
 from .library import _mode_code, _multiplier, _as_rows, _is_torch, _device_grid, _grid_flag, MATH_AUTO
 
 __all__ = ["residual_VH_batch", "brute_force_fit", "peak_density_from_trace", "brute_grid", "minimize_parameters",
-           "resolve_method", "BoundedPair", "pyiri_edp_builder", "model_VH", "residual_VH"]
+           "resolve_method", "BoundedPair", "pyiri_edp_builder", "model_VH", "residual_VH", "residual_VH_many",
+           "brute_force_fit_many", "minimize_parameters_many"]
 
 
 def pyiri_edp_builder(F2, F1, E, alt, bottom_type='B_bot'):
@@ -466,3 +467,317 @@ def minimize_parameters(F2, F1, E, f_in0, vh_obs0, alt, b_mag, b_psi, method='br
     from .library import vertical_forward_operator
     vh_result = vertical_forward_operator(f_in0, EDP_result, b_mag, b_psi, alt, mode, n_points, device=device, math=math)
     return vh_result, EDP_result, F2_fit
+
+
+# ---- many ionograms in one launch (DESIGN.md 4.5 "many ionograms") ----------------------------------------------------
+# The ionograms of a sounder programme share one frequency grid; what differs is which grid frequencies carry an echo.
+# ``vh_obs`` is (I, F) with NaN for "no observation"; per ionogram the rule is residual_VH's on the kept frequencies
+# (the filter of minimize_parameters, reference library.py:741-745), and the winner of every ionogram is chosen on the
+# device.  The operator runs once, on the whole grid.
+
+def _common_grid(freq, vh_obs):
+    """The common grid sorted ascending, the (I, F) observations with their columns permuted alike, and the order:
+    ``freq_sorted = freq[order]``, ``obs_sorted = vh_obs[:, order]``.  The grid must be finite and positive (an
+    ionogram's missing echoes are NaNs of ``vh_obs``, never of the grid).  ``vh_obs`` may be a tensor: it stays where
+    it is."""
+    f = np.asarray(freq.detach().cpu().numpy() if _is_torch(freq) else freq, dtype=np.float64)
+    if f.ndim != 1 or f.size < 1:
+        raise ValueError("freq must be 1-D: the common frequency grid of the ionograms")
+    if not np.all(np.isfinite(f)) or not np.all(f > 0.0):
+        raise ValueError("the common frequency grid must be finite and positive (mark missing echoes in vh_obs)")
+    order = np.argsort(f, kind="stable")
+    f = np.ascontiguousarray(f[order])
+    if _is_torch(vh_obs):
+        import torch
+        obs = vh_obs.reshape(1, -1) if vh_obs.dim() == 1 else vh_obs
+        if obs.dim() != 2 or obs.shape[1] != f.size:
+            raise ValueError("vh_obs must be (I, F): one row per ionogram on the common grid")
+        if not np.array_equal(order, np.arange(f.size)):
+            obs = obs[:, torch.as_tensor(order, device=obs.device)]
+        return f, obs, order
+    obs = np.atleast_2d(np.asarray(vh_obs, dtype=np.float64))
+    if obs.ndim != 2 or obs.shape[1] != f.size:
+        raise ValueError("vh_obs must be (I, F): one row per ionogram on the common grid")
+    return f, np.ascontiguousarray(obs[:, order]), order
+
+
+def _check_rows(ionogram_of_row, n_rows, n_iono):
+    """``ionogram_of_row`` as a contiguous int32 array, checked: one entry per row, non-decreasing, in [0, I)."""
+    raw = np.asarray(ionogram_of_row)
+    if raw.ndim != 1 or raw.size != n_rows:
+        raise ValueError("ionogram_of_row must be 1-D with one entry per candidate row")
+    if raw.size and not np.issubdtype(raw.dtype, np.integer):
+        raise ValueError("ionogram_of_row must hold integers")
+    if raw.size and (raw.min() < 0 or raw.max() >= n_iono):
+        raise ValueError("ionogram_of_row has an entry outside [0, I)")
+    if np.any(np.diff(raw) < 0):
+        raise ValueError("ionogram_of_row must be non-decreasing: the rows of an ionogram are contiguous")
+    return np.ascontiguousarray(raw, dtype=np.int32)
+
+
+def residual_VH_many(freq, vh_obs, den, bmag, bpsi, alt, mode='O', n_points=200, *, ionogram_of_row=None, shared=False,
+                     return_residual=False, return_vh=False, device=None, math=None):
+    """Costs of candidate profiles against MANY ionograms on one common frequency grid, and every ionogram's best
+    candidate, in one launch.
+
+    ``freq`` (F,) is the common grid [MHz] (finite, positive; sorted here, and the columns of ``vh_obs`` with it);
+    ``vh_obs`` (I, F) [km] holds NaN where an ionogram has no echo.  Per ionogram the rule is ``residual_VH_batch``'s on
+    its kept frequencies ``K_i``: what ``residual_VH_batch(freq[K_i], vh_obs[i, K_i], rows of i, ...)`` returns.
+
+    Own candidates (default): ``den`` (P, N_alt) and ``ionogram_of_row`` (P,) integers, non-decreasing, in [0, I) - row
+    ``p`` is a candidate of that ionogram only (ragged and empty groups are fine; with one ionogram it may be omitted).
+    ``shared=True``: each of the C rows of ``den`` is a candidate of every ionogram, the operator runs once on C x F.
+    ``bmag``, ``bpsi``: (N_alt,), one row per candidate, or - own candidates - (I, N_alt), one row per ionogram.
+    A 2-D field with as many rows as ``den`` is ALWAYS read as one row per candidate: when P == I the per-ionogram reading
+    is not available (expand it with ``field[ionogram_of_row]``).
+
+    Returns ``(cost, best, best_cost)``: ``cost`` (P,) or, shared, (I, C); ``best`` (I,) int64, the first row (a global
+    row index; shared: the candidate) with the smallest finite cost of the ionogram, -1 if it has none; ``best_cost``
+    (I,), NaN then.  ``return_residual`` (own candidates only) appends the dense residual rows (P, F), NaN outside
+    ``K_i``; ``return_vh`` appends the modeled traces (P, F) or (C, F).  Columns follow the ASCENDING grid.
+    NumPy inputs, or a GPU-resident torch ``den`` (results are tensors on its device), as ``residual_VH_batch``.
+    """
+    code = _mode_code(mode)
+    if shared and ionogram_of_row is not None:
+        raise ValueError("shared=True makes every row a candidate of every ionogram: ionogram_of_row must be None")
+    if shared and return_residual:
+        raise ValueError("the shared layout has no dense residual output")
+    on_gpu = _is_torch(den) and den.is_cuda
+    if _is_torch(vh_obs) and not on_gpu:
+        vh_obs = vh_obs.detach().cpu().numpy()
+    elif _is_torch(vh_obs) and vh_obs.device != den.device:
+        vh_obs = vh_obs.to(den.device)                     # (as a NumPy vh_obs is uploaded)
+    f, obs, _ = _common_grid(freq, vh_obs)
+    n_iono = int(obs.shape[0])
+    if on_gpu:
+        return _torch_residual_many(f, obs, den, bmag, bpsi, alt, code, n_points, ionogram_of_row, shared,
+                                    return_residual, return_vh, math)
+    d2 = np.atleast_2d(_as_rows("den", den))
+    n_prof, n_alt = d2.shape
+    ion = None
+    if not shared:
+        if ionogram_of_row is None:
+            if n_iono != 1:
+                raise ValueError("ionogram_of_row is required for more than one ionogram (or pass shared=True)")
+            ionogram_of_row = np.zeros(n_prof, dtype=np.int32)
+        ion = _check_rows(ionogram_of_row, n_prof, n_iono)
+    b2, p2 = (_as_rows(n, x) for n, x in (("bmag", bmag), ("bpsi", bpsi)))
+    one_field = b2.ndim == 1 and p2.ndim == 1
+    if one_field:
+        if b2.shape != (n_alt,) or p2.shape != (n_alt,):
+            raise ValueError("bmag and bpsi must have one value per density level")
+    else:
+        b2, p2 = (_field_rows(x, d2.shape, ion, n_iono, lambda a, k: np.ascontiguousarray(a[k])) for x in (b2, p2))
+    a = _as_rows("alt", alt)
+    if a.shape != (n_alt,):
+        raise ValueError("alt must be 1-D with one value per density level")
+    mult = _multiplier(n_points)
+    cost = np.empty((n_iono, n_prof) if shared else n_prof, dtype=np.float64)
+    best = np.empty(n_iono, dtype=np.int64)
+    best_cost = np.empty(n_iono, dtype=np.float64)
+    residual = np.empty((n_prof, f.size), dtype=np.float64) if return_residual else None
+    vh = np.empty((n_prof, f.size), dtype=np.float64) if return_vh else None
+    ctx = _native.host_context(device)
+    ctx.set_math(MATH_AUTO if math is None else int(math))
+    _native.raise_for(ctx.vfo_residual_many(
+        f.ctypes.data, f.size, d2.ctypes.data, b2.ctypes.data, p2.ctypes.data, a.ctypes.data, n_prof, n_alt, n_alt, 0,
+        mult.ctypes.data, int(n_points), code, obs.ctypes.data, n_iono, None if shared else ion.ctypes.data,
+        vh.ctypes.data if return_vh else None, residual.ctypes.data if return_residual else None, cost.ctypes.data,
+        best.ctypes.data, best_cost.ctypes.data,
+        (_native.FLAG_SHARED_FIELD if one_field else 0) | _grid_flag(mult, n_points)))
+    out = (cost, best, best_cost)
+    if return_residual:
+        out = out + (residual,)
+    if return_vh:
+        out = out + (vh,)
+    return out
+
+
+def _field_rows(x, den_shape, ion, n_iono, take):
+    """A 2-D ``bmag`` / ``bpsi``: one row per candidate as it is, one row per ionogram expanded to rows
+    (``take(x, ion)``); a single row serves every candidate."""
+    if len(x.shape) == 1:
+        x = x.reshape(1, -1)
+    if tuple(x.shape) == tuple(den_shape):
+        return x
+    if x.shape[0] == 1 and x.shape[1] == den_shape[1]:
+        return take(x, np.zeros(den_shape[0], dtype=np.int64) if ion is None else 0 * ion)
+    if ion is not None and tuple(x.shape) == (n_iono, den_shape[1]):
+        return take(x, ion)
+    raise ValueError("bmag and bpsi must be (N_alt,), one row per candidate, or (own candidates) one row per ionogram")
+
+
+def _torch_residual_many(f, obs, den, bmag, bpsi, alt, code, n_points, ionogram_of_row, shared, return_residual,
+                         return_vh, math):
+    import torch
+
+    dev = den.device
+
+    def prep(x, name):
+        if not _is_torch(x):
+            x = torch.as_tensor(np.asarray(x, dtype=np.float64), device=dev)
+        if x.device != dev:
+            raise ValueError(f"{name} is on {x.device}, expected {dev}")
+        return x.to(torch.float64).contiguous()
+
+    freq, obs = prep(f, "freq"), prep(obs, "vh_obs")
+    n_iono, n_freq = obs.shape
+    d2 = prep(den, "den")
+    d2 = d2.reshape(1, -1) if d2.dim() == 1 else d2
+    n_prof, n_alt = d2.shape
+    ion = None
+    if not shared:
+        if ionogram_of_row is None:
+            if n_iono != 1:
+                raise ValueError("ionogram_of_row is required for more than one ionogram (or pass shared=True)")
+            ionogram_of_row = np.zeros(n_prof, dtype=np.int32)
+        if _is_torch(ionogram_of_row):
+            # a device-resident index is used as it is (the kernel reads nothing outside vh_obs for a bad entry and
+            # gives that row a NaN cost); checking it would cost a copy to the host
+            if ionogram_of_row.device != dev or ionogram_of_row.dim() != 1 or ionogram_of_row.numel() != n_prof:
+                raise ValueError("ionogram_of_row must be 1-D with one entry per candidate row, on den's device")
+            ion = ionogram_of_row.to(torch.int32).contiguous()
+        else:
+            ion = torch.as_tensor(_check_rows(ionogram_of_row, n_prof, n_iono), device=dev)
+    b2, p2, a = prep(bmag, "bmag"), prep(bpsi, "bpsi"), prep(alt, "alt")
+    one_field = b2.dim() == 1 and p2.dim() == 1
+    if one_field:
+        if b2.shape != (n_alt,) or p2.shape != (n_alt,):
+            raise ValueError("bmag and bpsi must have one value per density level")
+    else:
+        rows = None if ion is None else ion.to(torch.int64)
+        take = lambda x, k: x[torch.as_tensor(k, device=dev)].contiguous()      # noqa: E731
+        b2, p2 = (_field_rows(x, d2.shape, rows, n_iono, take) for x in (b2, p2))
+    if a.shape != (n_alt,):
+        raise ValueError("alt must be 1-D with one value per density level")
+    mult, grid_flag = _device_grid((int(n_points),), dev)
+    cost = torch.empty((n_iono, n_prof) if shared else (n_prof,), dtype=torch.float64, device=dev)
+    best = torch.empty(n_iono, dtype=torch.int64, device=dev)
+    best_cost = torch.empty(n_iono, dtype=torch.float64, device=dev)
+    residual = torch.empty((n_prof, n_freq), dtype=torch.float64, device=dev) if return_residual else None
+    vh = torch.empty((n_prof, n_freq), dtype=torch.float64, device=dev) if return_vh else None
+    ctx = _native.context(dev.index if dev.index is not None else torch.cuda.current_device())
+    ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+    ctx.set_math(MATH_AUTO if math is None else int(math))
+    _native.raise_for(ctx.vfo_residual_many(
+        freq.data_ptr(), n_freq, d2.data_ptr(), b2.data_ptr(), p2.data_ptr(), a.data_ptr(), n_prof, n_alt, n_alt, 0,
+        mult.data_ptr(), int(n_points), code, obs.data_ptr(), n_iono, None if shared else ion.data_ptr(),
+        vh.data_ptr() if return_vh else None, residual.data_ptr() if return_residual else None, cost.data_ptr(),
+        best.data_ptr(), best_cost.data_ptr(),
+        _native.FLAG_DEVICE_PTRS | grid_flag | (_native.FLAG_SHARED_FIELD if one_field else 0)))
+    out = (cost, best, best_cost)
+    if return_residual:
+        out = out + (residual,)
+    if return_vh:
+        out = out + (vh,)
+    return out
+
+
+def brute_force_fit_many(freq, vh_obs, den_candidates, bmag, bpsi, alt, mode='O', n_points=200, *, ionogram_of_row=None,
+                         shared=False, device=None, math=None):
+    """``brute_force_fit`` for many ionograms on one common grid in one launch (``residual_VH_many``).
+
+    Returns ``(best (I,), best_cost (I,), vh_best (I, F), freq_sorted)``: ``best[i]`` is the first candidate row with
+    the smallest finite cost of ionogram ``i`` (-1, and a NaN ``best_cost`` and trace, when it has none - nothing is
+    raised for one ionogram among many); ``vh_best[i]`` is the operator's trace of that row on the whole ascending
+    grid, NaN where a frequency escapes."""
+    _, best, best_cost, vh = residual_VH_many(freq, vh_obs, den_candidates, bmag, bpsi, alt, mode, n_points,
+                                              ionogram_of_row=ionogram_of_row, shared=shared, return_vh=True,
+                                              device=device, math=math)
+    f = np.sort(np.asarray(freq.detach().cpu().numpy() if _is_torch(freq) else freq, dtype=np.float64))
+    if _is_torch(vh):
+        import torch
+        vh_best = torch.full((best.numel(), vh.shape[1]), float("nan"), dtype=vh.dtype, device=vh.device)
+        if vh.shape[0]:
+            vh_best = torch.where((best >= 0)[:, None], vh[best.clamp(min=0)], vh_best)
+        return best, best_cost, vh_best, f
+    vh_best = np.full((best.size, vh.shape[1]), np.nan)
+    found = best >= 0
+    vh_best[found] = vh[best[found]]
+    return best, best_cost, vh_best, f
+
+
+def minimize_parameters_many(F2s, F1s, Es, freq, vh_obs, alt, b_mag, b_psi, percent_sigma=20., step=1., mode='O',
+                             n_points=200, bottom_type='B_bot', *, edp_builder=None, method='brute', device=None,
+                             math=None):
+    """``minimize_parameters`` (brute-force search) for many ionograms on one common frequency grid: every ionogram's
+    whole (hmF2 x B_bot) grid in ONE launch, the winners chosen on the device.
+
+    ``F2s``, ``F1s``, ``Es``: sequences of I layer dictionaries (what ``minimize_parameters`` takes, one per ionogram);
+    ``freq`` (F,) the common grid, ``vh_obs`` (I, F) with NaN for "no echo"; ``b_mag``, ``b_psi`` (N_alt,) or
+    (I, N_alt).  Per ionogram, as in ``minimize_parameters``: NmF2 from its highest kept frequency
+    (``peak_density_from_trace``), candidates on ``brute_grid`` around its own initial values (so the groups are ragged),
+    the first node of the smallest cost wins, and the result trace is evaluated at the grid frequencies as given
+    (one batched operator call for all ionograms).  Returns a list of ``(vh_result, EDP_result, F2_fit)``.
+    Only the brute-force search is batched: for any other ``method`` call ``minimize_parameters`` per ionogram."""
+    from copy import deepcopy
+
+    if resolve_method(method)[0] != 'brute':
+        raise NotImplementedError(f"method={method!r}: minimize_parameters_many batches the brute-force search only; "
+                                  "call minimize_parameters per ionogram for the other methods")
+    if bottom_type not in ('B_bot', 'B0_B1'):
+        raise ValueError("bottom_type must be 'B_bot' or 'B0_B1'")
+    n_iono = len(F2s)
+    if len(F1s) != n_iono or len(Es) != n_iono:
+        raise ValueError("F2s, F1s and Es must have one entry per ionogram")
+    for F2 in F2s:
+        if (bottom_type == 'B_bot') and (F2.get('B_bot') is None):
+            raise ValueError('B_bot is not provided in F, but bottom_type is B_bot')
+        if (bottom_type == 'B0_B1') and ((F2.get('B0') is None) or (F2.get('B1') is None)):
+            raise ValueError('B0 and B1 are not provided in F, but bottom_type is B0_B1')
+    if edp_builder is None:
+        edp_builder = pyiri_edp_builder
+    freq0 = np.asarray(freq, dtype=np.float64)
+    alt = np.asarray(alt, dtype=np.float64)
+    f_sorted, obs_sorted, _ = _common_grid(freq0, vh_obs)
+    if obs_sorted.shape[0] != n_iono:
+        raise ValueError("vh_obs must have one row per ionogram")
+    b_mag, b_psi = np.asarray(b_mag, dtype=np.float64), np.asarray(b_psi, dtype=np.float64)
+    if b_mag.ndim == 2 and b_mag.shape[0] != n_iono or b_psi.ndim == 2 and b_psi.shape[0] != n_iono:
+        raise ValueError("b_mag and b_psi must be (N_alt,) or (I, N_alt)")
+    second = 'B_bot' if bottom_type == 'B_bot' else 'B0'
+
+    def layers(i, nm, hm, bb):
+        f2 = deepcopy(F2s[i])
+        f2['Nm'] = np.full_like(F2s[i]['Nm'], nm)
+        f2['hm'] = np.full_like(F2s[i]['Nm'], hm)
+        f2[second] = np.full_like(F2s[i]['Nm'], bb)
+        return f2
+
+    nodes, rows, nm_of = [], [], []
+    for i in range(n_iono):
+        kept = np.nonzero(np.isfinite(obs_sorted[i]))[0]
+        if kept.size == 0:
+            raise ValueError(f"ionogram {i}: no finite observation")
+        field = b_mag[i] if b_mag.ndim == 2 else b_mag
+        nm = peak_density_from_trace(f_sorted[kept[-1]], mode, alt=alt, bmag=field,
+                                     hmf2=float(np.asarray(F2s[i]['hm']).squeeze()))
+        hm_nodes = brute_grid(F2s[i]['hm'], percent_sigma, step)
+        bb_nodes = brute_grid(F2s[i][second], percent_sigma, step)
+        if hm_nodes.size == 0 or bb_nodes.size == 0:
+            raise ValueError(f"ionogram {i}: empty search grid: percent_sigma too small for this step")
+        nm_of.append(nm)
+        nodes.append([(hm, bb) for hm in hm_nodes for bb in bb_nodes])
+        rows.append(np.full(len(nodes[-1]), i, dtype=np.int32))
+    den = np.empty((sum(len(n) for n in nodes), alt.size), dtype=np.float64)
+    k = 0
+    for i in range(n_iono):
+        for hm, bb in nodes[i]:
+            den[k] = np.asarray(edp_builder(layers(i, nm_of[i], hm, bb), deepcopy(F1s[i]), deepcopy(Es[i]), alt, bottom_type),
+                                dtype=np.float64).ravel()
+            k += 1
+    ion = np.concatenate(rows)
+    _, best, _ = residual_VH_many(f_sorted, obs_sorted, den, b_mag, b_psi, alt, mode, n_points, ionogram_of_row=ion,
+                                  device=device, math=math)
+    starts = np.concatenate([[0], np.cumsum([len(n) for n in nodes])])
+    fits, edps = [], np.empty((n_iono, alt.size), dtype=np.float64)
+    for i in range(n_iono):
+        if best[i] < 0:
+            raise ValueError(f"ionogram {i}: no node of the search grid produced a finite cost")
+        F2_fit = layers(i, nm_of[i], *nodes[i][int(best[i] - starts[i])])
+        edps[i] = np.asarray(edp_builder(deepcopy(F2_fit), deepcopy(F1s[i]), deepcopy(Es[i]), alt, bottom_type),
+                             dtype=np.float64).ravel()
+        fits.append(F2_fit)
+    from .library import vertical_forward_operator
+    vh = vertical_forward_operator(freq0.ravel(), edps, b_mag, b_psi, alt, mode, n_points, device=device, math=math)
+    return [(vh[i], edps[i], fits[i]) for i in range(n_iono)]

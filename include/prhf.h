@@ -149,6 +149,14 @@ int prhf_ctx_set_math(prhf_ctx* ctx, int level);
  *                        the Gauss rule of the counting measure on its points, exact for the same polynomials; every
  *                        other piece takes eight lanes as before.  The same pairs take the rule and the same pairs fall
  *                        back; values stay within 1e-12.  Values between 4 and 8 count as 8)
+ *   "strided_grade"      0: the strided stretch of each of the top three segments takes every eighth point throughout, the
+ *                        launch of before this option bit for bit (1: the stretch is cut into zones by the distance to
+ *                        the index where the segment's continuation reaches X + Y = 1 - every 32nd point at least 1024
+ *                        indices below it and only where 1 - X - Y >= 1.6e-4, every 16th at least 512 below it and only
+ *                        where 1 - X - Y >= 1e-5, every eighth next to it as before - with Euler-Maclaurin corrections
+ *                        of both zones at each junction.  A coarse zone holds whole wavefront iterations: a multiple of
+ *                        2048 indices at stride 32, of 1024 at stride 16; the last 64 indices stay at stride 8.  Values
+ *                        stay within 1e-12 of the full sum.  A segment that has that index below it is not cut)
  *   "pair_plan"          0: every wavefront computes the integers that steer its pair's strided sum itself, the launch of
  *                        before this option bit for bit (1: where "strided_lower" applies and a workgroup settles its
  *                        reflection heights one frequency per thread - at most 512 frequencies, grids of fewer than 65536

@@ -50,7 +50,8 @@
 #ifndef PRHF_COMPACT_MIN_QUEUE
 #define PRHF_COMPACT_MIN_QUEUE 256  // queue entries such a workgroup has at least (a profile's unused nodes come on top)
 #endif
-#define PRHF_PAIR_PAD 256           // entries behind the pair table that the main loop's prefetch may touch
+#define PRHF_PAIR_PAD 256           // entries behind the pair table that the main loop's prefetch may touch (127; 63 x 4 = 252
+                                    // behind a stride-32 zone of the strided table: static_assert in strided_run)
 #ifndef PRHF_TOP_MIN_POINTS
 #define PRHF_TOP_MIN_POINTS 1024    // grids from this many points on give their top segment a loop of its own
 #endif
@@ -112,6 +113,8 @@ struct SegDev {
                                      // pair's guard allows it (option panel_lower)
     int panel_nodes;                 // with panel_lower: 4 - pieces far from X + Y = 1 take four nodes on four lanes; 8 - every
                                      // piece takes eight lanes (option panel_nodes)
+    int strided_grade;               // with sp_off > 0: a strided stretch of the top three segments is cut into zones of
+                                     // stride 32, 16 and 8 by the distance to X + Y = 1 (option strided_grade)
     int pair_plan;                   // with sp_off > 0: the workgroup plans its pairs' sums one pair per thread (option
                                      // pair_plan; plan_pairs in prhf_kernels.hip)
     int thread_scan;                 // X mode: reflection heights settled one frequency per thread while the candidate

@@ -165,6 +165,8 @@ constexpr int kStridedLowerBit = 1 << 30;
 constexpr int kPanelLowerBit = 1 << 29;
 // ... and bit 28: pieces far from X + Y = 1 are summed from four nodes on four lanes (SegDev::panel_nodes == 4)
 constexpr int kPanelNodes4Bit = 1 << 28;
+// ... and bit 27: a strided stretch of the top three segments is cut into zones of stride 32, 16 and 8 (SegDev::strided_grade)
+constexpr int kStridedGradeBit = 1 << 27;
 // a piece takes four nodes where X + Y = 1 lies at least kPanelFar n + 2 indices from its centre
 constexpr int kPanelFar = 16;
 // what the main loop reports about the panel sum in the bits above kPanelStateShift of LeanResult::first (a grid point's
@@ -1100,10 +1102,70 @@ __device__ __forceinline__ StridedSpan strided_span(int lo_s, int q_s, int begin
     }
     return r;
 }
-// A pair's plan as it lies in LDS, four words: the first points of the top three segments and the top segment's level
+// The zones of a strided stretch (option strided_grade): [a_s, z2_s] is summed at stride 32, [z2_s, z1_s]
+// at stride 16 and [z1_s, e_s) at stride 8 as before, all four multiples of 64; an empty zone has equal ends.  A point
+// of stride s lies at least 32 s indices below the index i_sing where the segment's continuation reaches X + Y = 1, and
+// a point of stride 16 has 1 - X - Y >= 1e-5, one of stride 32 1 - X - Y >= 1.6e-4: strided_span's second guard, wider by
+// what the end corrections' largest coefficient grows by - 13.2 at stride 8, 164 at 16, 2431 at 32, like s^4 - so that
+// a stencil point's rounding error, coefficient x 1e-16 / (1 - X - Y), stays at 1.5e-9 of a summand for every stride
+// (with 1e-5 for both, the flat-layer pairs of the benchmark's draw come out at 1.7e-12 on the CPU model instead of
+// 2e-13).  The stride-8 zone keeps at least the last 64 indices,
+// so the far end's stencil and the ordinary points behind it stay what they were.  A coarse zone holds whole
+// wave-iterations only - a multiple of 2048 indices at stride 32, of 1024 at stride 16, counted from a_s - since a
+// point in a gather iteration costs three times what it costs in the loop.  A segment whose i_sing lies below it (strided_span moved a_s up, not e_s down) is not
+// graded, nor is one with grade == false: z2_s == z1_s == a_s.
+// The gather lanes of a strided stretch with coarse zones (strided_run): lanes 0 .. 6 the stencil at a, 7 .. 17 the
+// stencil at b and the ordinary points behind it, 18 .. 24 the junction at z1, 25 .. 31 the junction at z2.  Row 0:
+// strides 32, 16, 8; row 1: 32, 8; row 2: 16, 8.  With D(s)[q] = (s^2-1)/12 D1[q] - (s^4-1)/720 D3[q]: +D(s) around a and
+// -(s-1)/2 at a itself; -D(8) around b, -3.5 at b, +1 for b+1 .. b+7; D(right) - D(left) around a junction and
+// (left - right)/2 at it.  tests/test_strided_grade_host.py holds every entry to these formulas.
+static __device__ const double kGradeCoef[3 * 32] = {
+    -183.46510416666666, 1469.1416666666667, -2430.5130208333335, -15.5, 2430.5130208333335, -1469.1416666666667, 183.46510416666666, 0.7984375, -6.475, 13.1796875, -3.5, -12.1796875, 7.475, 0.2015625, 1.0, 1.0, 1.0, 1.0, 10.933333333333334, -87.73333333333333, 150.66666666666666, 4.0, -150.66666666666666, 87.73333333333333, -10.933333333333334, 171.73333333333332, -1374.9333333333334, 2266.6666666666665, 8.0, -2266.6666666666665, 1374.9333333333334, -171.73333333333332,
+    -183.46510416666666, 1469.1416666666667, -2430.5130208333335, -15.5, 2430.5130208333335, -1469.1416666666667, 183.46510416666666, 0.7984375, -6.475, 13.1796875, -3.5, -12.1796875, 7.475, 0.2015625, 1.0, 1.0, 1.0, 1.0, 182.66666666666666, -1462.6666666666667, 2417.3333333333335, 12.0, -2417.3333333333335, 1462.6666666666667, -182.66666666666666, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0,
+    -11.731770833333334, 94.20833333333333, -163.84635416666666, -7.5, 163.84635416666666, -94.20833333333333, 11.731770833333334, 0.7984375, -6.475, 13.1796875, -3.5, -12.1796875, 7.475, 0.2015625, 1.0, 1.0, 1.0, 1.0, 10.933333333333334, -87.73333333333333, 150.66666666666666, 4.0, -150.66666666666666, 87.73333333333333, -10.933333333333334, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0,
+};
+struct StridedZones {
+    int a_s, z2_s, z1_s, e_s;
+};
+__device__ __forceinline__ StridedZones strided_zones(int lo_s, int q_s, int begin_s, const SegLinear& t, double cX, double n1,
+                                                      bool grade) {
+    const StridedSpan sp = strided_span(lo_s, q_s, begin_s, t, cX, n1);
+    StridedZones r;
+    r.a_s = r.z2_s = r.z1_s = sp.a_s;
+    r.e_s = sp.e_s;
+    if (!grade || sp.e_s == sp.a_s || sp.e_s >= (1 << 22)) return r;       // (strided_run packs z / 64 into 16 bits)
+    constexpr double kTau16 = 1e-5, kTau32 = 1.6e-4;
+    const int cap = sp.e_s - 64;
+    int z1 = cap, z2 = cap;
+    const double r2 = 1.4142135623730951;
+    const double sl = __builtin_fma(cX, t.d1, r2 * t.b1);
+    const double gap = __builtin_fma(-r2, t.b0, __builtin_fma(-cX, t.d0, 1.0));
+    if (__builtin_fabs(sl) > 1e-300) {
+        const double m_sing = gap / sl, dm16 = kTau16 / __builtin_fabs(sl), dm32 = kTau32 / __builtin_fabs(sl);
+        const double i_sing = stretch_index(m_sing, n1);
+        const int a0 = begin_s >= lo_s + 3 ? begin_s : begin_s + 64;
+        if (!(2.0 * i_sing >= (double)(a0 + q_s))) return r;                       // (strided_span's own test)
+        const double lim1 = fmin(i_sing - 512.0, stretch_index(m_sing - dm16, n1));
+        const double lim2 = fmin(i_sing - 1024.0, stretch_index(m_sing - dm32, n1));
+        z1 = min(cap, (int)__builtin_floor(lim1) & ~63);
+        z2 = min(z1, (int)__builtin_floor(lim2) & ~63);
+    } else if (!(__builtin_fabs(gap) >= kTau16)) {
+        return r;
+    } else if (!(__builtin_fabs(gap) >= kTau32)) {
+        z2 = sp.a_s;                                           // X + Y constant: stride 16 throughout
+    }
+    // (whole wave-iterations only: 64 points of stride 32 and of stride 16)
+    z2 = sp.a_s + (max(z2 - sp.a_s, 0) & ~2047);
+    z1 = z2 + (max(z1 - z2, 0) & ~1023);
+    r.z2_s = z2;
+    r.z1_s = z1;
+    return r;
+}
+// A pair's plan as it lies in LDS, six words: the first points of the top three segments and the top segment's level
 // (16 bits each: grids of fewer than 65536 points), then a_s / 64 and e_s / 64 of the three segments (10 bits each),
-// the number of segments with a loop of their own and the "planned" bit.
-constexpr int kPlanBytes = 16;
+// the number of segments with a loop of their own and the "planned" bit, then z2_s / 64 and z1_s / 64 of the three
+// segments (10 bits each, in segment order from bit 0 of the fifth word).
+constexpr int kPlanBytes = 24;
 constexpr unsigned kPlanValid = 1u << 30;
 
 template <bool G>
@@ -1158,7 +1220,8 @@ struct LeanResult {
 // caller continues from there in the reference's operation order.
 // TOP: with the top-segment phase (long grids on a uniform altitude grid); the short-grid callers use the
 // variant without it, which needs 24 fewer vector registers around the call.
-template <int MODE, bool CHECK, int POLY, bool HINT, bool TOP, bool G>
+// GRADE: with the zones of the strided sum (option strided_grade); without, the function is the one of before.
+template <int MODE, bool CHECK, int POLY, bool HINT, bool TOP, bool G, bool GRADE>
 __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type nodes_arg, unsigned hint_lds,
                                                      const double2* __restrict__ pairs, int first, int end,
                                                      int last_special, double span, double a0, double kj,
@@ -1191,15 +1254,16 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
     }
     // Pair-table loads go through a buffer descriptor: lane offset in a VGPR, grid position in an
     // SGPR, so the loop spends no vector instruction on addresses.  A prefetch may reach up to 127 entries
-    // past `end`: the table is padded by PRHF_PAIR_PAD entries (launch_grid_pairs), and what is read there
-    // is never used.
+    // (252 in a stride-32 zone of the strided table, strided_run) past `end`: the table is padded by PRHF_PAIR_PAD
+    // entries (launch_grid_pairs), and what is read there is never used.
     const unsigned voff = (unsigned)lane * (unsigned)sizeof(double2);
     const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<double2*>(pairs), 0, 0x7fffffff, 0x00020000);
     typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
     int tab_off = 0;                                   // bytes; the strided phase points it at the strided table's piece
-    auto grid_at = [&](int i) {
-        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, i * (int)sizeof(double2) + tab_off, 0);
+    // (sh: a coarse zone of the strided sum reads every second or fourth entry of its table - the lane offset twice, four times)
+    auto grid_at = [&](int i, int sh = 0) {
+        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff << sh, i * (int)sizeof(double2) + tab_off, 0);
         double2 g;
         __builtin_memcpy(&g, &v, sizeof g);
         return g;
@@ -1221,10 +1285,10 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
     int n_seg = 0;
     TopSegment top;
     __builtin_memset(&top, 0, sizeof top);
-    // The pair's plan, where the workgroup made one (plan_pairs; whole pairs only, first == 0): four words of LDS.  Their
+    // The pair's plan, where the workgroup made one (plan_pairs; whole pairs only, first == 0): six words of LDS.  Their
     // address arrives in the place of the hint table's, which a uniform altitude grid does not use (the loop function
     // passes its arguments in registers: one more would travel through scratch memory); 0: no plan.  A planned pair
-    // skips the searches below and the guard arithmetic of strided_run; a pair without a plan computes the same
+    // skips the searches below and the guard and zone arithmetic of strided_run; a pair without a plan computes the same
     // integers itself.
     constexpr bool PLANNABLE = TOP && MODE == PRHF_KMODE_X && !CHECK && !G && !HINT;
     // (nothing of it stays in a scalar register across the loops, which need every one they can get: the address waits
@@ -1372,18 +1436,19 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
             }
         }
     };
-    // ... and with the node of one segment held in registers
-    auto run_top = [&](int stop) {
-        for (; first + 128 <= stop; first += 128) {
-            const double2 g1 = grid_at(first + 64);
+    // ... and with the node of one segment held in registers (step: table entries per wave-iteration - 64, or 128 and
+    // 256 where a coarse zone of the strided sum reads every second and fourth entry)
+    auto run_top = [&](int stop, int step = 64, int sh = 0) {
+        for (; first + 2 * step <= stop; first += 2 * step) {
+            const double2 g1 = grid_at(first + step, sh);
             if (!CHECK) {
                 accm = lean_step_top<MODE, false, POLY>(g0, top, cX, hcY2, accm, wc, viol);
-                g0 = grid_at(first + 128);
+                g0 = grid_at(first + 2 * step, sh);
                 accm = lean_step_top<MODE, false, POLY>(g1, top, cX, hcY2, accm, wc, viol);
             } else {
                 unsigned long long viol2 = 0;
                 const double a1 = lean_step_top<MODE, true, POLY>(g0, top, cX, hcY2, accm, wc, viol);
-                const double2 g2 = grid_at(first + 128);
+                const double2 g2 = grid_at(first + 2 * step, sh);
                 const double a2 = lean_step_top<MODE, true, POLY>(g1, top, cX, hcY2, a1, wc, viol2);
                 if (viol) {
                     const int L = __ffsll((long long)viol) - 1;
@@ -1394,7 +1459,7 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
                 if (viol2) {
                     const int L = __ffsll((long long)viol2) - 1;
                     accm = lane < L ? a2 : a1;
-                    first += 64 + L;
+                    first += step + L;
                     viol = viol2;
                     return;
                 }
@@ -1402,12 +1467,12 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
                 g0 = g2;
             }
         }
-        if (first + 64 <= stop) {
+        if (first + step <= stop) {
             const double a1 = lean_step_top<MODE, CHECK, POLY>(g0, top, cX, hcY2, accm, wc, viol);
             if (!(CHECK && viol)) {
                 accm = a1;
-                first += 64;
-                g0 = grid_at(first);
+                first += step;
+                g0 = grid_at(first, sh);
             } else {
                 const int L = __ffsll((long long)viol) - 1;
                 if (lane < L) accm = a1;
@@ -1426,7 +1491,8 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
     const bool lower_req = (sp_off & kStridedLowerBit) != 0;
     const bool panel_req = (sp_off & kPanelLowerBit) != 0;
     const bool nodes4_req = (sp_off & kPanelNodes4Bit) != 0;
-    sp_off &= ~(kStridedLowerBit | kPanelLowerBit | kPanelNodes4Bit);
+    constexpr bool grade_req = GRADE;                  // (lean_loop picks the instance by the option's bit)
+    sp_off &= ~(kStridedLowerBit | kPanelLowerBit | kPanelNodes4Bit | kStridedGradeBit);
     int panel_state = 0;                               // (waits in a vector register, where the result travels anyway)
     asm volatile("" : "+v"(panel_state));
     if (STRIDED && sp_off > 0 && n_seg > 0 && first == 0 && last_special >= 0 && end >= PRHF_TOP3_MIN_POINTS) {
@@ -1452,8 +1518,14 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
     // rounding error of about 1e-16 / (1 - X - Y) there, which the eightfold weights amplify instead of averaging out
     // (a low frequency that reflects in a nearly flat layer has 1 - X - Y < 1e-7 over thousands of points: 4e-11 of
     // its sum, measured; with this bound the per-point error of a strided term stays below 1e-10).
+    // Zones (option strided_grade, strided_zones above): away from i_sing the summand varies on the scale of the distance
+    // to it, so [a, z2] takes every 32nd point and [z2, z1] every 16th, from the same strided table read at every fourth
+    // and second entry; [z1, E) is the stretch of before.  The sum is that of the zones' own rules less g at the
+    // junctions, which both neighbours count: a junction's seven points carry the end corrections of both zones.  A
+    // coarse zone holds whole wave-iterations only, which take the table's weight 8 w with the sum scaled by 1/4 or 1/2
+    // around them; the junctions join the gather iterations.  Without coarse zones every lane does what it did.
     auto strided_run = [&](int lo_s, int q_s, int begin_s, int sidx) {
-        int a_s, e_s;
+        int a_s, e_s, z2_s, z1_s;
         const unsigned plan_s = PLANNABLE ? (unsigned)uniform((int)plan_v) : 0u;
         if (PLANNABLE && plan_s != 0u) {
             // (a_s / 64, e_s / 64: ten bits each, in segment order from bit 0 of the third word)
@@ -1463,50 +1535,109 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
             const unsigned pe = sidx == 0 ? pw2 >> 10 : (sidx == 1 ? pw3 : pw3 >> 20);
             a_s = (int)((pa & 1023u) << 6);
             e_s = (int)((pe & 1023u) << 6);
+            z2_s = z1_s = a_s;
+            if (grade_req) {
+                const unsigned pw4 = (unsigned)uniform((int)rec[4]), pw5 = (unsigned)uniform((int)rec[5]);
+                const unsigned p2 = sidx == 0 ? pw4 : (sidx == 1 ? pw4 >> 20 : pw5 >> 10);
+                const unsigned p1 = sidx == 0 ? pw4 >> 10 : (sidx == 1 ? pw5 : pw5 >> 20);
+                z2_s = (int)((p2 & 1023u) << 6);
+                z1_s = (int)((p1 & 1023u) << 6);
+            }
         } else {
             // (the guards come out of vector arithmetic: back to scalars, or the loops below lose their scalar control)
             SegLinear lin;
             lin.d0 = top.d0; lin.d1 = top.d1; lin.b0 = top.b0; lin.b1 = top.b1;
-            const StridedSpan sp = strided_span(lo_s, q_s, begin_s, lin, cX, (double)i_last_s);
+            const StridedZones sp = strided_zones(lo_s, q_s, begin_s, lin, cX, (double)i_last_s, grade_req);
             a_s = uniform(sp.a_s);
             e_s = uniform(sp.e_s);
+            z2_s = uniform(sp.z2_s);
+            z1_s = uniform(sp.z1_s);
         }
-        const int count = (e_s - a_s) >> 3;                        // strided points a, a + 8, .. b
+        if constexpr (!GRADE) z2_s = z1_s = a_s;
+        const int count = (e_s - a_s) >> 3;                        // strided points a, a + 8, .. b without zones
         if (count < 64) return;                                    // (this segment runs as today)
         run_top(a_s);                                              // one by one up to a
-        const int b_s = e_s - 8;
-        // whole wave-iterations of strided points
+        // whole wave-iterations of strided points: the coarse zones first, behind one scalar branch that a stretch without
+        // them never enters (a loop over the zones with scalar selects cost every pair 100 scalar instructions per
+        // segment: +3 % on the headline launch, measured), each with its literal step; then the stride-8 zone as before
         tab_off = (sp_off + 1) * (int)sizeof(double2);
-        first = a_s >> 3;
-        const int j_whole = first + (count & ~63);
-        g0 = grid_at(first);
-        run_top(j_whole);
-        tab_off = 0;
-        const int rest = count & 63;                               // strided points left over, from j_whole
-        const double c0 = 1.0 / 22025.465794806718;                // 1 / expm1(10)
-        for (int t0 = 0; t0 < 18 + rest; t0 += 64) {
-            const int t = t0 + lane;
-            int idx = a_s;
-            double coef = 0.0;
-            if (t < 18) {
-                const bool at_a = t < 7;
-                const int q = at_a ? t - 3 : t - 10;               // -3 .. 3 around a, -3 .. 7 around b
-                idx = (at_a ? a_s : b_s) + q;
-                const int qa = q < 0 ? -q : q;
-                // (s^2-1)/12 D1[q] - (s^4-1)/720 D3[q]: 5.25 (3/4, -3/20, 1/60) - 5.6875 (-13/8, 1, -1/8)
-                const double mag = qa == 1 ? 13.1796875 : (qa == 2 ? -6.475 : (qa == 3 ? 0.7984375 : 0.0));
-                const double sg = q < 0 ? -mag : mag;
-                coef = q == 0 ? -3.5 : (at_a ? sg : -sg);
-                if (!at_a && q >= 1) coef += 1.0;                  // the ordinary points b + 1 .. E - 1
-            } else if (t < 18 + rest) {
-                idx = (j_whole + (t - 18)) << 3;
-                coef = 8.0;
+        // (a coarse zone's prefetch reaches 63 x 4 entries past the zone's last wave-iteration, which ends below E / 8)
+        static_assert(PRHF_PAIR_PAD >= 63 * 4 + 4, "the strided table's padding must cover the stride-32 zone's prefetch");
+        if (GRADE && z1_s > a_s) {
+            // (the table's weight is 8 w: the sum so far divided by 4 or 2, the product afterwards - both exact - is the
+            //  sum with weights 32 w and 16 w, without a second accumulator and without an instruction per point)
+            if (z2_s > a_s) {
+                first = a_s >> 3;
+                g0 = grid_at(first, 2);
+                accm *= 0.25;
+                run_top(z2_s >> 3, 256, 2);
+                accm *= 4.0;
             }
+            if (z1_s > z2_s) {
+                first = z2_s >> 3;
+                g0 = grid_at(first, 1);
+                accm *= 0.5;
+                run_top(z1_s >> 3, 128, 1);
+                accm *= 2.0;
+            }
+        }
+        first = z1_s >> 3;
+        g0 = grid_at(first);
+        run_top(first + (((e_s - z1_s) >> 3) & ~63));
+        tab_off = 0;
+        // The gather iterations: the two end stencils and the stride-8 zone's points left over, as before.  A stretch with
+        // coarse zones (a scalar branch) has 32 lanes in front of those points instead of 18 - the junctions at z1 and z2
+        // behind the stencils - and every such lane reads its coefficient from kGradeCoef: per-lane constants that
+        // depend on the lane and on which zones exist alone.
+        const double c0 = 1.0 / 22025.465794806718;                // 1 / expm1(10)
+        const int b_s = e_s - 8;
+        const int n2 = (e_s - z1_s) >> 3;
+        const int j_whole = (z1_s >> 3) + (n2 & ~63);
+        const int rest = n2 & 63;                                  // strided points left over, from j_whole
+        auto gather = [&](int idx, double coef) {
             const u32x4 vm = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (unsigned)idx * (unsigned)sizeof(double2), 0, 0);
             double2 gm;
             __builtin_memcpy(&gm, &vm, sizeof gm);
             gm.y = coef * (sc1 * ((1.0 - gm.x) + c0));             // w(m) = c1 (1 - m + c0): 1 - m is exact near the top
             accm = lean_step_top<MODE, false, POLY>(gm, top, cX, hcY2, accm, wc, viol);
+        };
+        if (GRADE && z1_s > a_s) {
+            const int row = z2_s > a_s ? (z1_s > z2_s ? 0 : 32) : 64;
+            for (int t0 = 0; t0 < 32 + rest; t0 += 64) {
+                const int t = t0 + lane;
+                int idx = a_s;
+                double coef = 0.0;
+                if (t < 32) {
+                    coef = kGradeCoef[row + t];
+                    const int base = t < 7 ? a_s : (t < 18 ? b_s : (t < 25 ? z1_s : z2_s));
+                    idx = base + t - (t < 7 ? 3 : (t < 18 ? 10 : (t < 25 ? 21 : 28)));
+                } else if (t < 32 + rest) {
+                    idx = (j_whole + (t - 32)) << 3;
+                    coef = 8.0;
+                }
+                gather(idx, coef);
+            }
+        } else {
+            for (int t0 = 0; t0 < 18 + rest; t0 += 64) {
+                const int t = t0 + lane;
+                int idx = a_s;
+                double coef = 0.0;
+                if (t < 18) {
+                    const bool at_a = t < 7;
+                    const int q = at_a ? t - 3 : t - 10;           // -3 .. 3 around a, -3 .. 7 around b
+                    idx = (at_a ? a_s : b_s) + q;
+                    const int qa = q < 0 ? -q : q;
+                    // (s^2-1)/12 D1[q] - (s^4-1)/720 D3[q]: 5.25 (3/4, -3/20, 1/60) - 5.6875 (-13/8, 1, -1/8)
+                    const double mag = qa == 1 ? 13.1796875 : (qa == 2 ? -6.475 : (qa == 3 ? 0.7984375 : 0.0));
+                    const double sg = q < 0 ? -mag : mag;
+                    coef = q == 0 ? -3.5 : (at_a ? sg : -sg);
+                    if (!at_a && q >= 1) coef += 1.0;              // the ordinary points b + 1 .. E - 1
+                } else if (t < 18 + rest) {
+                    idx = (j_whole + (t - 18)) << 3;
+                    coef = 8.0;
+                }
+                gather(idx, coef);
+            }
         }
         first = e_s;
         g0 = grid_at(first);
@@ -1880,13 +2011,29 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
     return r;
 }
 
+template <int MODE, bool CHECK, int POLY, bool HINT, bool TOP, bool G, bool GRADE>
+__device__ __attribute__((noinline)) LeanResult lean_loop_instance(typename NodeArg<G>::type nodes_arg, unsigned hint_lds,
+                                                                   const double2* __restrict__ pairs, int first, int end,
+                                                                   int last_special, double span, double a0, double kj,
+                                                                   double cX, double cY2, double well_conditioned, int sp_off) {
+    return lean_loop_body<MODE, CHECK, POLY, HINT, TOP, G, GRADE>(nodes_arg, hint_lds, pairs, first, end, last_special, span,
+                                                                   a0, kj, cX, cY2, well_conditioned, sp_off);
+}
+// (the option strided_grade picks one of two instances of the loop function here, by one scalar branch and a tail call:
+//  a launch without it runs the instruction stream of before in a function of its own, and the kernel keeps its single
+//  call site)
 template <int MODE, bool CHECK, int POLY, bool HINT, bool TOP, bool G>
 __device__ __attribute__((noinline)) LeanResult lean_loop(typename NodeArg<G>::type nodes_arg, unsigned hint_lds,
                                                           const double2* __restrict__ pairs, int first, int end,
                                                           int last_special, double span, double a0, double kj,
                                                           double cX, double cY2, double well_conditioned, int sp_off) {
-    return lean_loop_body<MODE, CHECK, POLY, HINT, TOP, G>(nodes_arg, hint_lds, pairs, first, end, last_special, span, a0,
-                                                            kj, cX, cY2, well_conditioned, sp_off);
+    if constexpr (TOP && MODE == PRHF_KMODE_X && !CHECK && !G) {
+        if ((uniform(sp_off) & kStridedGradeBit) != 0)
+            return lean_loop_instance<MODE, CHECK, POLY, HINT, TOP, G, true>(nodes_arg, hint_lds, pairs, first, end, last_special,
+                                                                             span, a0, kj, cX, cY2, well_conditioned, sp_off);
+    }
+    return lean_loop_instance<MODE, CHECK, POLY, HINT, TOP, G, false>(nodes_arg, hint_lds, pairs, first, end, last_special, span,
+                                                                       a0, kj, cX, cY2, well_conditioned, sp_off);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -2326,11 +2473,12 @@ __device__ __forceinline__ unsigned plan_slot(const PlanRoom& r, int i) {
 
 // The plan of one pair by one thread: the integers lean_loop_body would compute wave-uniformly - first points of the
 // top three segments by the closed form of the stretch and its four-entry bracket check, then the strided stretch of
-// each - written to `rec` (four words).  Returns false where the guess does not bracket (another grid, a range's
+// each - written to `rec` (six words).  Returns false where the guess does not bracket (another grid, a range's
 // edge): that pair's wave runs its own search.  `h` is the settled reflection height (span > 0 and kj inside the node
 // table: checked by the caller, as integrate_chunk does).
 __device__ __attribute__((noinline)) bool plan_pair(const Node* nodes, int K, const double2* __restrict__ pairs, int n_points,
-                                                    double span, double kj, double cX, double cY2, unsigned* rec) {
+                                                    double span, double kj, double cX, double cY2, bool grade,
+                                                    unsigned* rec) {
     const int i_last = n_points - 1;
     const double n1 = (double)i_last;
     const int j_top = (int)(pairs[i_last].x * kj);
@@ -2368,20 +2516,25 @@ __device__ __attribute__((noinline)) bool plan_pair(const Node* nodes, int K, co
     }
     const double hcY2 = 0.5 * cY2;
     const double cYs = hcY2 * rsqrt_cubic(hcY2);
-    // a_s / 64 | e_s / 64 << 10 of one segment
+    // a_s / 64 | e_s / 64 << 10 of one segment, and z2_s / 64 | z1_s / 64 << 10 in the high word
     auto span_of = [&](int j, int lo, int q_s) {
         const Node& nd = nodes[j];
         const SegLinear lin = seg_linear(nd.off, nd.den, nd.sden, nd.b, nd.sb, span, cYs);
-        const StridedSpan sp = strided_span(lo, q_s, (lo + 63) & ~63, lin, cX, n1);
-        return (unsigned)(sp.a_s >> 6) | ((unsigned)(sp.e_s >> 6) << 10);
+        const StridedZones sp = strided_zones(lo, q_s, (lo + 63) & ~63, lin, cX, n1, grade);
+        const unsigned zz = (unsigned)(sp.z2_s >> 6) | ((unsigned)(sp.z1_s >> 6) << 10);
+        return ((unsigned long long)zz << 32) | ((unsigned)(sp.a_s >> 6) | ((unsigned)(sp.e_s >> 6) << 10));
     };
-    const unsigned ae0 = n_seg > 0 ? span_of(j_top, lo0, i_last - 1) : 0u;
-    const unsigned ae1 = n_seg > 1 ? span_of(j_top - 1, lo1, lo0 - 1) : 0u;
-    const unsigned ae2 = n_seg > 2 ? span_of(j_top - 2, lo2, lo1 - 1) : 0u;
+    const unsigned long long s0 = n_seg > 0 ? span_of(j_top, lo0, i_last - 1) : 0ull;
+    const unsigned long long s1 = n_seg > 1 ? span_of(j_top - 1, lo1, lo0 - 1) : 0ull;
+    const unsigned long long s2 = n_seg > 2 ? span_of(j_top - 2, lo2, lo1 - 1) : 0ull;
+    const unsigned ae0 = (unsigned)s0, ae1 = (unsigned)s1, ae2 = (unsigned)s2;
+    const unsigned zz0 = (unsigned)(s0 >> 32), zz1 = (unsigned)(s1 >> 32), zz2 = (unsigned)(s2 >> 32);
     rec[0] = (unsigned)lo0 | ((unsigned)lo1 << 16);
     rec[1] = (unsigned)lo2 | ((unsigned)j_top << 16);
     rec[2] = ae0 | ((ae1 & 1023u) << 20) | ((unsigned)n_seg << 30);
     rec[3] = (ae1 >> 10) | (ae2 << 10) | kPlanValid;
+    rec[4] = zz0 | ((zz1 & 1023u) << 20);
+    rec[5] = (zz1 >> 10) | (zz2 << 10);
     return true;
 }
 
@@ -2427,12 +2580,13 @@ __device__ __forceinline__ PlanRoom plan_pairs(const KArgs& a, const SegDev& sg,
         const bool main_loop = span > 0.0 && kj <= (double)(info.K - 1);       // (integrate_chunk's own test)
         bool done = false;
         if (u < room.total) {
-            unsigned* rec = u < room.cap0 ? reinterpret_cast<unsigned*>(gb) + 4 * u
-                                          : (u < room.cap01 ? reinterpret_cast<unsigned*>(hint) + 4 * (u - room.cap0)
-                                                            : reinterpret_cast<unsigned*>(pf2 + used) + 4 * (u - room.cap01));
+            constexpr int kWords = kPlanBytes / 4;
+            unsigned* rec = u < room.cap0 ? reinterpret_cast<unsigned*>(gb) + kWords * u
+                                          : (u < room.cap01 ? reinterpret_cast<unsigned*>(hint) + kWords * (u - room.cap0)
+                                                            : reinterpret_cast<unsigned*>(pf2 + used) + kWords * (u - room.cap01));
             if (main_loop) {
                 const double* row = a.ftab + 8 * (long long)cand[t];
-                done = plan_pair(nodes, info.K, pairs, sg.n_points, span, kj, row[2], row[3], rec);
+                done = plan_pair(nodes, info.K, pairs, sg.n_points, span, kj, row[2], row[3], sg.strided_grade != 0, rec);
             }
             if (!done) rec[3] = 0u;
         }
@@ -2477,7 +2631,8 @@ __device__ __forceinline__ void run_items(const KArgs& a, const SegDev& sg, cons
     const int sp_off = (pairs && sg.sp_off > 0)
                            ? uniform((int)(sg.sp_off - sg.mult_off) | (sg.strided_lower ? kStridedLowerBit : 0) |
                                      (sg.strided_lower && sg.panel_lower ? kPanelLowerBit : 0) |
-                                     (sg.strided_lower && sg.panel_lower && sg.panel_nodes == 4 ? kPanelNodes4Bit : 0)) : 0;
+                                     (sg.strided_lower && sg.panel_lower && sg.panel_nodes == 4 ? kPanelNodes4Bit : 0) |
+                                     (sg.strided_grade ? kStridedGradeBit : 0)) : 0;
     const long long pair_base = prof_local * F;
     const int first_item = block_in_prof * W, round_items = blocks_per_prof * W;
     // Few pairs on a long grid (one profile, the reference's own call; SegDev::slots > 0): a pair is cut into C <= S

@@ -93,6 +93,12 @@ struct Knobs {
                                        // nodes of the Gauss rule of the counting measure on four lanes, sixteen pieces per
                                        // wave-iteration (8, or anything but 4: eight lanes for every piece,
                                        // the launch of before, bit for bit)
+    double strided_grade = 1;          // ... and the strided stretch of each of the top three segments is cut into zones:
+                                       // every 32nd point at least 1024 indices below the index where the segment's
+                                       // continuation reaches X + Y = 1 and where 1 - X - Y >= 1.6e-4, every 16th at
+                                       // least 512 below it and where 1 - X - Y >= 1e-5, in multiples of 2048 and 1024
+                                       // indices (whole wave-iterations), every eighth next to it as before (DESIGN.md
+                                       // 4.1; 0: every eighth point throughout, the launch of before, bit for bit)
     double pair_plan = 1;              // ... and the integers that steer such a pair's sum - first points of the top three
                                        // segments, the strided stretch of each - are computed once per pair, by one thread
                                        // while the workgroup makes its candidate list, instead of by all 64 lanes of the
@@ -135,6 +141,7 @@ const KnobName kKnobNames[] = {
     {"strided_lower", &Knobs::strided_lower, 0, 1},
     {"panel_lower", &Knobs::panel_lower, 0, 1},
     {"panel_nodes", &Knobs::panel_nodes, 4, 8},
+    {"strided_grade", &Knobs::strided_grade, 0, 1},
     {"pair_plan", &Knobs::pair_plan, 0, 1},
     {"pair_plan_cap", &Knobs::pair_plan_cap, 0, 1024},
 };
@@ -572,6 +579,7 @@ inline int plan_launch(const LaunchShape& sh, const prhf_segment* segs, int32_t 
             s.strided_lower = kn.strided_lower != 0;
             s.panel_lower = s.strided_lower && kn.panel_lower != 0;
             s.panel_nodes = s.panel_lower && kn.panel_nodes == 4 ? 4 : 8;
+            s.strided_grade = kn.strided_grade != 0;
             s.pair_plan = slice_plans_pairs(s, tall, n_freq, lds_levels, kn) ? 1 : 0;
             pl.any_plan = pl.any_plan || s.pair_plan != 0;
         }

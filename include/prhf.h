@@ -40,7 +40,9 @@ extern "C" {
                               *    prhf_pair_plan_counters, prhf_panel_counters, and prhf_field_build_f64,
                               *    prhf_gradient_skip_f64, prhf_gradient_muf_f64, prhf_gradient_skip_counters,
                               *    prhf_trace_gradient_hops_f64, prhf_gradient_hop_home_f64, and
-                              *    prhf_residual_many_f64, prhf_vfo_residual_many_f64) */
+                              *    prhf_residual_many_f64, prhf_vfo_residual_many_f64, and
+                              *    prhf_gradient_hop_skip_f64, prhf_gradient_hop_muf_f64,
+                              *    prhf_gradient_hop_skip_counters) */
 
 /* return codes */
 #define PRHF_OK        0
@@ -764,6 +766,65 @@ int prhf_gradient_muf_f64(prhf_ctx* ctx, int32_t geometry, const double* den, co
  * refined, [1] rays the refine lanes traced, [2] ray slots (64 per trip of a refine wavefront's loop), [3] refine
  * wavefronts with work.  Lane utilisation of the refinement = [1] / [2].  No device call. */
 int prhf_gradient_skip_counters(prhf_ctx* ctx, uint64_t* counters);
+
+/*
+ * Skip distance of the n_hops-hop mode (2F, 3F ..) through a horizontally varying mu: prhf_gradient_skip_f64 with D(e)
+ * the ground_range_km of hop n_hops - 1 of prhf_trace_gradient_hops_f64's chain launched at elevation e, NaN unless all
+ * n_hops (1 .. 16) hops land.  All arguments before n_hops are that call's.  Written out:
+ *   Scan: D_i = D(e_i) for every scan node, a node whose chain fails on any hop has a D that is not finite.  i* = the
+ * first index that attains the minimum over the finite D_i (D(e) of a chain is not unimodal: the first index is part of
+ * the definition).  No finite D_i: status -1.  i* at either end of the scan or beside a node whose D is not finite:
+ * status 1, the node as it stands, no further chain.  Otherwise, in float64 without contraction, with a = e_(i*-1),
+ * b = e_i*, c = e_(i*+1), D_b = D_i*, n = 0, g = 0.3819660112501051, at most max_iter + 1 times:
+ *     c - a <= elev_tol_deg: status 0, stop;
+ *     right = (c - b) >= (b - a); x = right ? b + g * (c - b) : b - g * (b - a);
+ *     unless a < x < c and x != b: status 0, stop (the doubles are exhausted);
+ *     n >= max_iter (1 .. 128): status 3, stop;
+ *     D = D(x); n = n + 1; D not finite: status 2, stop;
+ *     D < D_b: (right ? a : c) = b, b = x, D_b = D; else (right ? c : a) = x.
+ *   out is (n_groups, 6 + 15 * n_hops): skip_km (D_b), elevation_deg (b), status, scan_index (i*), bracket_deg (c - a;
+ * NaN for status 1), n_evals (n: chains, not hops), then the n_hops hop rows of prhf_trace_gradient_hops_f64 for the
+ * chain at elevation_deg, bit for bit what that call returns there; skip_km has the bits of the last hop's
+ * ground_range_km.  Status -1: skip_km, elevation_deg and bracket_deg NaN, scan_index -1, n_evals 0, and the hop rows
+ * unused as prhf_trace_gradient_hops_f64 writes them.  With n_hops = 1 the call finds what prhf_gradient_skip_f64 finds.
+ * Memory, flags, the handling of a device-resident group_field out of range and every PRHF_EINVAL rule are
+ * prhf_gradient_skip_f64's; PRHF_EINVAL also for n_hops outside 1 .. 16 (after the null context, before the rest).
+ * Synchronous.
+ */
+int prhf_gradient_hop_skip_f64(prhf_ctx* ctx, int32_t geometry, const double* records, int64_t n_fields, int64_t n0,
+                               int64_t n1, const double* axis0, const double* axis1, const int64_t* group_field,
+                               const double* group_x0_km, const double* group_z0_km, int64_t n_groups,
+                               const double* scan_elevation_deg, int64_t n_scan, double earth_radius_km, double s_max_km,
+                               double rtol, double atol, double max_step_km, double z_ground_km, double top, double left,
+                               double right, int32_t renormalize_every, double fill_n, double fill_grad, double fill_mup,
+                               double elev_tol_deg, int32_t max_iter, int32_t n_hops, double* out, uint32_t flags);
+
+/*
+ * MUF of the n_hops-hop mode of a link through a tilted ionosphere: prhf_gradient_muf_f64 with S(f) = skip_km of
+ * prhf_gradient_hop_skip_f64 on prhf_field_build_f64's field at f (+inf at status -1).  All arguments before n_hops,
+ * the statuses -1, 0, 1, 2, the bisection m = lo + 0.5 * (hi - lo), n_bisect (1 .. 64) and the trip that does not move
+ * are that call's.
+ *   out is (n_links, 3 + 6 + 15 * n_hops): muf_hz, f_above_hz, status, then the row prhf_gradient_hop_skip_f64 gives on
+ * prhf_field_build_f64's field at muf_hz, bit for bit (NaN throughout for status -1 and 2; f_above_hz is NaN for status
+ * 1).  Scratch is 48 * n0 * n1 bytes per link, as in prhf_gradient_muf_f64: PRHF_ENOMEM when it cannot be allocated.
+ * With n_hops = 1 the call finds what prhf_gradient_muf_f64 finds.  PRHF_EINVAL for a null context (before anything
+ * else), n_hops outside 1 .. 16 and whatever prhf_gradient_muf_f64 refuses; PRHF_ENEGDEN likewise.  Synchronous.
+ */
+int prhf_gradient_hop_muf_f64(prhf_ctx* ctx, int32_t geometry, const double* den, const double* bmag, const double* bpsi,
+                              int64_t n0, int64_t n1, const double* axis0, const double* axis1, int32_t mode,
+                              int32_t edge_order, const double* link_x0_km, const double* link_z0_km,
+                              const double* link_target_km, int64_t n_links, double f_lo_hz, double f_hi_hz, int32_t n_bisect,
+                              const double* scan_elevation_deg, int64_t n_scan, double earth_radius_km, double s_max_km,
+                              double rtol, double atol, double max_step_km, double z_ground_km, double top, double left,
+                              double right, int32_t renormalize_every, double fill_n, double fill_grad, double fill_mup,
+                              double elev_tol_deg, int32_t max_iter, int32_t n_hops, double* out, uint32_t flags);
+
+/* prhf_gradient_skip_counters with a fifth word, for the context's last skip or MUF call of the gradient tracers,
+ * one-hop or multi-hop: counters[0 .. 3] as there - prhf_gradient_skip_counters reports the multi-hop calls too, a ray
+ * being a chain and a ray slot one lane-trip whatever the hops -, [4] hop rays: the hops of the refine lanes' chains
+ * that landed, n_hops each (a chain that does not land ends its group's search; it counts under [1] alone); 0 after a
+ * one-hop call.  Per slot a lane traced [4] / [2] hops.  No device call. */
+int prhf_gradient_hop_skip_counters(prhf_ctx* ctx, uint64_t* counters);
 
 /* Diagnostics of option "pair_plan", summed over every launch since the context was made: counters[0] reflecting pairs
  * whose sum ran from a plan made by one thread, [1] pairs of the same slices that computed their plan themselves (no

@@ -17,7 +17,9 @@ from .gradient import (STATUS_NAMES, RefractiveField, build_mup_function,       
                        home_hops_spherical_gradient, home_rays_cartesian_gradient,
                        home_rays_spherical_gradient, muf_cartesian_gradient, muf_spherical_gradient,
                        refractive_field, refractive_field_device, skip_distance_cartesian_gradient,
-                       skip_distance_spherical_gradient,
+                       skip_distance_spherical_gradient, muf_hops_cartesian_gradient,
+                       muf_hops_spherical_gradient, skip_distance_hops_cartesian_gradient,
+                       skip_distance_hops_spherical_gradient,
                        trace_fan_cartesian_gradient, trace_fan_spherical_gradient,
                        trace_hop_fan_cartesian_gradient, trace_hop_fan_spherical_gradient,
                        trace_hops_cartesian_gradient, trace_hops_spherical_gradient,
@@ -37,5 +39,7 @@ __all__ = ["logger", "__version__", "STATUS_NAMES", "RefractiveField", "build_mu
            "refractive_field_device", "skip_distance_cartesian_gradient", "skip_distance_spherical_gradient",
            "muf_cartesian_gradient", "muf_spherical_gradient", "trace_hops_cartesian_gradient",
            "trace_hops_spherical_gradient", "trace_hop_fan_cartesian_gradient", "trace_hop_fan_spherical_gradient",
-           "home_hops_cartesian_gradient", "home_hops_spherical_gradient", "residual_VH_many", "brute_force_fit_many",
+           "home_hops_cartesian_gradient", "home_hops_spherical_gradient",
+           "skip_distance_hops_cartesian_gradient", "skip_distance_hops_spherical_gradient",
+           "muf_hops_cartesian_gradient", "muf_hops_spherical_gradient", "residual_VH_many", "brute_force_fit_many",
            "minimize_parameters_many"]

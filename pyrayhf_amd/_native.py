@@ -150,7 +150,19 @@ _PROTOTYPES = {
                               [ctypes.c_int64, ctypes.c_double, ctypes.c_double, ctypes.c_int32, ctypes.c_void_p,
                                ctypes.c_int64] + [ctypes.c_double] * 9 + [ctypes.c_int32] + [ctypes.c_double] * 4 +
                               [ctypes.c_int32, ctypes.c_void_p, ctypes.c_uint32]),
+    "prhf_gradient_hop_skip_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64,
+                                                  ctypes.c_int64, ctypes.c_int64] + [ctypes.c_void_p] * 5 +
+                                   [ctypes.c_int64] + [ctypes.c_void_p, ctypes.c_int64] + [ctypes.c_double] * 9 +
+                                   [ctypes.c_int32] + [ctypes.c_double] * 4 +
+                                   [ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_uint32]),
+    "prhf_gradient_hop_muf_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32] + [ctypes.c_void_p] * 3 +
+                                  [ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
+                                   ctypes.c_int32] + [ctypes.c_void_p] * 3 +
+                                  [ctypes.c_int64, ctypes.c_double, ctypes.c_double, ctypes.c_int32, ctypes.c_void_p,
+                                   ctypes.c_int64] + [ctypes.c_double] * 9 + [ctypes.c_int32] + [ctypes.c_double] * 4 +
+                                  [ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_uint32]),
     "prhf_gradient_skip_counters": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
+    "prhf_gradient_hop_skip_counters": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
     "prhf_pair_plan_counters": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
     "prhf_panel_counters": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
     "prhf_occupancy": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
@@ -472,6 +484,33 @@ class Context:
                                                float(f_hi), int(n_bisect), scan_elev, n_scan, float(earth_radius),
                                                *(float(v) for v in controls[:8]), int(controls[8]),
                                                *(float(v) for v in fills), float(elev_tol), int(max_iter), out, flags)
+
+    def gradient_hop_skip(self, geometry, records, n_fields, n0, n1, axis0, axis1, group_field, group_x0, group_z0, n_groups,
+                          scan_elev, n_scan, earth_radius, controls, fills, elev_tol, max_iter, n_hops, out, flags):
+        """gradient_skip on the landing of hop ``n_hops`` - 1; ``out``: (n_groups, 6 + 15 n_hops) doubles."""
+        return self._lib.prhf_gradient_hop_skip_f64(self._h, int(geometry), records, n_fields, n0, n1, axis0, axis1,
+                                                    group_field, group_x0, group_z0, n_groups, scan_elev, n_scan,
+                                                    float(earth_radius), *(float(v) for v in controls[:8]),
+                                                    int(controls[8]), *(float(v) for v in fills), float(elev_tol),
+                                                    int(max_iter), int(n_hops), out, flags)
+
+    def gradient_hop_muf(self, geometry, den, bmag, bpsi, n0, n1, axis0, axis1, mode, edge_order, link_x0, link_z0,
+                         link_target, n_links, f_lo, f_hi, n_bisect, scan_elev, n_scan, earth_radius, controls, fills,
+                         elev_tol, max_iter, n_hops, out, flags):
+        """gradient_muf of the ``n_hops``-hop mode; ``out``: (n_links, 3 + 6 + 15 n_hops) doubles."""
+        return self._lib.prhf_gradient_hop_muf_f64(self._h, int(geometry), den, bmag, bpsi, n0, n1, axis0, axis1, int(mode),
+                                                   int(edge_order), link_x0, link_z0, link_target, n_links, float(f_lo),
+                                                   float(f_hi), int(n_bisect), scan_elev, n_scan, float(earth_radius),
+                                                   *(float(v) for v in controls[:8]), int(controls[8]),
+                                                   *(float(v) for v in fills), float(elev_tol), int(max_iter),
+                                                   int(n_hops), out, flags)
+
+    def gradient_hop_skip_counters(self):
+        """``gradient_skip_counters`` and, fifth, the hop rays of the refine lanes' chains that landed (0 after a
+        one-hop call), of the last skip or MUF call of the gradient tracers."""
+        buf = (ctypes.c_uint64 * 5)()
+        raise_for(self._lib.prhf_gradient_hop_skip_counters(self._h, buf))
+        return tuple(int(v) for v in buf)
 
     def gradient_skip_counters(self):
         """(groups refined, rays traced by the refine lanes, ray slots, refine wavefronts) of the last gradient_skip or

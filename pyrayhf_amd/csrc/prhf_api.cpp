@@ -169,7 +169,7 @@ struct prhf_ctx {
     bool status_pending = false;
     uint64_t grad_home_counters[PRHF_GRAD_HOME_COUNTERS] = {};   // of the last prhf_gradient_home_f64 (prhf_gradient_home_counters)
     DevBuf fields;    // prhf_gradient_muf_f64: mu, mu' and the records of every link's field (48 bytes per node and link)
-    uint64_t grad_skip_counters[PRHF_GRAD_SKIP_COUNTERS] = {};   // of the last prhf_gradient_skip_f64 / prhf_gradient_muf_f64
+    uint64_t grad_skip_counters[PRHF_GRAD_SKIP_COUNTERS + 1] = {};   // of the last skip / MUF call of the gradient tracers, one-hop or chain; [4]: hop rays
 };
 
 namespace {
@@ -2444,6 +2444,7 @@ int grad_skip_finish(prhf_ctx* c, const unsigned* queue) {
     const int rc = prhf_sync(c);
     c->grad_skip_counters[0] = w[4];
     for (int k = 1; k < PRHF_GRAD_SKIP_COUNTERS; ++k) c->grad_skip_counters[k] = w[k];
+    c->grad_skip_counters[PRHF_GRAD_SKIP_COUNTERS] = w[5];
     return rc;
 }
 }  // namespace
@@ -2506,14 +2507,16 @@ int prhf_field_build_f64(prhf_ctx* c, const double* den, const double* bmag, con
     return PRHF_OK;
 }
 
-int prhf_gradient_skip_f64(prhf_ctx* c, int32_t geometry, const double* records, int64_t n_fields, int64_t n0, int64_t n1,
-                           const double* axis0, const double* axis1, const int64_t* group_field, const double* group_x0_km,
-                           const double* group_z0_km, int64_t n_groups, const double* scan_elevation_deg, int64_t n_scan,
-                           double earth_radius_km, double s_max_km, double rtol, double atol, double max_step_km,
-                           double z_ground_km, double top, double left, double right, int32_t renormalize_every,
-                           double fill_n, double fill_grad, double fill_mup, double elev_tol_deg, int32_t max_iter,
-                           double* out, uint32_t flags) {
-    if (!c) return fail(PRHF_EINVAL, "null context");
+namespace {
+// Both skip calls.  n_hops 0: prhf_gradient_skip_f64 (rows of 18); else prhf_gradient_hop_skip_f64 (6 + 15 n_hops).
+int grad_skip_run(prhf_ctx* c, int32_t n_hops, int32_t geometry, const double* records, int64_t n_fields, int64_t n0, int64_t n1,
+                  const double* axis0, const double* axis1, const int64_t* group_field, const double* group_x0_km,
+                  const double* group_z0_km, int64_t n_groups, const double* scan_elevation_deg, int64_t n_scan,
+                  double earth_radius_km, double s_max_km, double rtol, double atol, double max_step_km,
+                  double z_ground_km, double top, double left, double right, int32_t renormalize_every,
+                  double fill_n, double fill_grad, double fill_mup, double elev_tol_deg, int32_t max_iter,
+                  double* out, uint32_t flags) {
+    const int row_width = n_hops ? PRHF_GRAD_HOP_SKIP_OUTPUTS(n_hops) : PRHF_GRAD_SKIP_OUTPUTS;
     if (!records || !group_field || !group_x0_km || !group_z0_km || !scan_elevation_deg || !out)
         return fail(PRHF_EINVAL, "null array pointer");
     int rc = grad_search_check(geometry, earth_radius_km, s_max_km, rtol, atol, max_step_km, renormalize_every, n_scan,
@@ -2535,7 +2538,7 @@ int prhf_gradient_skip_f64(prhf_ctx* c, int32_t geometry, const double* records,
     }
     for (uint64_t& w : c->grad_skip_counters) w = 0;
     ENTER_DEVICE(c->device);
-    const size_t G = (size_t)n_groups, E = (size_t)n_scan, out_elems = G * PRHF_GRAD_SKIP_OUTPUTS;
+    const size_t G = (size_t)n_groups, E = (size_t)n_scan, out_elems = G * (size_t)row_width;
     rc = ensure(c, c->arena, ((size_t)(n0 + n1) + (dev ? 0 : 3 * G + E + out_elems)) * 8);
     if (rc != PRHF_OK) return rc;
     double* p = static_cast<double*>(c->arena.p);
@@ -2546,6 +2549,7 @@ int prhf_gradient_skip_f64(prhf_ctx* c, int32_t geometry, const double* records,
     grad_search_args(c, h.g, geometry, records, n_fields, n0, n1, p, earth_radius_km, s_max_km, rtol, atol, max_step_km,
                      z_ground_km, top, left, right, renormalize_every, fill_n, fill_grad, fill_mup);
     h.n_groups = n_groups; h.n_scan = (int)n_scan; h.elev_tol = elev_tol_deg; h.max_iter = max_iter;
+    h.row_width = row_width; h.g.n_hops = n_hops ? n_hops : 1; h.g.hop_z0 = z_ground_km;
     if (dev) {
         h.group_field = reinterpret_cast<const long long*>(group_field); h.group_x0 = group_x0_km; h.group_z0 = group_z0_km;
         h.scan_elev = scan_elevation_deg; h.out = out;
@@ -2572,22 +2576,53 @@ int prhf_gradient_skip_f64(prhf_ctx* c, int32_t geometry, const double* records,
         h.scan_d = reinterpret_cast<double*>(q + queue_bytes + work_bytes);
     }
     HIP_TRY(hipEventRecord(c->begin_ev(), c->stream));
-    HIP_TRY(prhf::launch_grad_skip(h, c->stream));
+    HIP_TRY(prhf::launch_grad_skip(h, n_hops != 0, c->stream));
     HIP_TRY(hipEventRecord(c->pending_end_ev(), c->stream));
     c->mark_timed();
     c->status_pending = true;
     if (!dev) HIP_TRY(hipMemcpyAsync(out, h.out, out_elems * 8, hipMemcpyDeviceToHost, c->stream));
     return grad_skip_finish(c, h.queue);
 }
+}  // namespace
 
-int prhf_gradient_muf_f64(prhf_ctx* c, int32_t geometry, const double* den, const double* bmag, const double* bpsi, int64_t n0,
-                          int64_t n1, const double* axis0, const double* axis1, int32_t mode, int32_t edge_order,
-                          const double* link_x0_km, const double* link_z0_km, const double* link_target_km, int64_t n_links,
-                          double f_lo_hz, double f_hi_hz, int32_t n_bisect, const double* scan_elevation_deg, int64_t n_scan,
-                          double earth_radius_km, double s_max_km, double rtol, double atol, double max_step_km,
-                          double z_ground_km, double top, double left, double right, int32_t renormalize_every, double fill_n,
-                          double fill_grad, double fill_mup, double elev_tol_deg, int32_t max_iter, double* out, uint32_t flags) {
+int prhf_gradient_skip_f64(prhf_ctx* c, int32_t geometry, const double* records, int64_t n_fields, int64_t n0, int64_t n1,
+                           const double* axis0, const double* axis1, const int64_t* group_field, const double* group_x0_km,
+                           const double* group_z0_km, int64_t n_groups, const double* scan_elevation_deg, int64_t n_scan,
+                           double earth_radius_km, double s_max_km, double rtol, double atol, double max_step_km,
+                           double z_ground_km, double top, double left, double right, int32_t renormalize_every,
+                           double fill_n, double fill_grad, double fill_mup, double elev_tol_deg, int32_t max_iter,
+                           double* out, uint32_t flags) {
     if (!c) return fail(PRHF_EINVAL, "null context");
+    return grad_skip_run(c, 0, geometry, records, n_fields, n0, n1, axis0, axis1, group_field, group_x0_km, group_z0_km, n_groups,
+                         scan_elevation_deg, n_scan, earth_radius_km, s_max_km, rtol, atol, max_step_km, z_ground_km, top, left,
+                         right, renormalize_every, fill_n, fill_grad, fill_mup, elev_tol_deg, max_iter, out, flags);
+}
+
+int prhf_gradient_hop_skip_f64(prhf_ctx* c, int32_t geometry, const double* records, int64_t n_fields, int64_t n0, int64_t n1,
+                               const double* axis0, const double* axis1, const int64_t* group_field,
+                               const double* group_x0_km, const double* group_z0_km, int64_t n_groups,
+                               const double* scan_elevation_deg, int64_t n_scan, double earth_radius_km, double s_max_km,
+                               double rtol, double atol, double max_step_km, double z_ground_km, double top, double left,
+                               double right, int32_t renormalize_every, double fill_n, double fill_grad, double fill_mup,
+                               double elev_tol_deg, int32_t max_iter, int32_t n_hops, double* out, uint32_t flags) {
+    if (!c) return fail(PRHF_EINVAL, "null context");
+    if (n_hops < 1 || n_hops > PRHF_GRAD_MAX_HOPS) return fail(PRHF_EINVAL, "n_hops is 1 .. 16");
+    return grad_skip_run(c, n_hops, geometry, records, n_fields, n0, n1, axis0, axis1, group_field, group_x0_km, group_z0_km, n_groups,
+                         scan_elevation_deg, n_scan, earth_radius_km, s_max_km, rtol, atol, max_step_km, z_ground_km, top, left,
+                         right, renormalize_every, fill_n, fill_grad, fill_mup, elev_tol_deg, max_iter, out, flags);
+}
+
+namespace {
+// Both MUF calls.  n_hops 0: prhf_gradient_muf_f64 (rows of 21); else prhf_gradient_hop_muf_f64 (3 + 6 + 15 n_hops).
+
+int grad_muf_run(prhf_ctx* c, int32_t n_hops, int32_t geometry, const double* den, const double* bmag, const double* bpsi, int64_t n0,
+                 int64_t n1, const double* axis0, const double* axis1, int32_t mode, int32_t edge_order,
+                 const double* link_x0_km, const double* link_z0_km, const double* link_target_km, int64_t n_links,
+                 double f_lo_hz, double f_hi_hz, int32_t n_bisect, const double* scan_elevation_deg, int64_t n_scan,
+                 double earth_radius_km, double s_max_km, double rtol, double atol, double max_step_km,
+                 double z_ground_km, double top, double left, double right, int32_t renormalize_every, double fill_n,
+                 double fill_grad, double fill_mup, double elev_tol_deg, int32_t max_iter, double* out, uint32_t flags) {
+    const int row_width = n_hops ? PRHF_GRAD_HOP_SKIP_OUTPUTS(n_hops) : PRHF_GRAD_SKIP_OUTPUTS;
     if (!den || !bmag || !bpsi || !link_x0_km || !link_z0_km || !link_target_km || !scan_elevation_deg || !out)
         return fail(PRHF_EINVAL, "null array pointer");
     int rc = grad_search_check(geometry, earth_radius_km, s_max_km, rtol, atol, max_step_km, renormalize_every, n_scan,
@@ -2614,7 +2649,7 @@ int prhf_gradient_muf_f64(prhf_ctx* c, int32_t geometry, const double* den, cons
     }
     for (uint64_t& w : c->grad_skip_counters) w = 0;
     ENTER_DEVICE(c->device);
-    const size_t out_elems = L * PRHF_GRAD_MUF_OUTPUTS;
+    const size_t out_elems = L * (size_t)(3 + row_width);
     rc = ensure(c, c->arena, ((size_t)(n0 + n1) + (dev ? 0 : 3 * plane + 3 * L + E + out_elems)) * 8);
     if (rc != PRHF_OK) return rc;
     // one field per link: mu, mu' and the records, 48 bytes per node
@@ -2632,6 +2667,7 @@ int prhf_gradient_muf_f64(prhf_ctx* c, int32_t geometry, const double* den, cons
     grad_search_args(c, h.g, geometry, rec, n_links, n0, n1, p, earth_radius_km, s_max_km, rtol, atol, max_step_km,
                      z_ground_km, top, left, right, renormalize_every, fill_n, fill_grad, fill_mup);
     h.n_groups = n_links; h.n_scan = (int)n_scan; h.elev_tol = elev_tol_deg; h.max_iter = max_iter;
+    h.row_width = row_width; h.g.n_hops = n_hops ? n_hops : 1; h.g.hop_z0 = z_ground_km;
     m.n_links = n_links; m.f_lo = f_lo_hz; m.f_hi = f_hi_hz; m.n_bisect = n_bisect;
     double* d_result = out;
     if (dev) {
@@ -2654,7 +2690,7 @@ int prhf_gradient_muf_f64(prhf_ctx* c, int32_t geometry, const double* den, cons
         // the counters, the work list, the scan's ground ranges; per link its frequency, field index, bracket, the skip
         // row of the trip, the head of the row at the bracket's lower end and the "is searching" word
         const size_t queue_bytes = 128, work_bytes = L * 8, scan_bytes = L * E * 8;
-        const size_t link_doubles = L * (1 + 1 + 4 + (PRHF_GRAD_SKIP_OUTPUTS - PRHF_GRAD_OUTPUTS) + PRHF_GRAD_SKIP_OUTPUTS);
+        const size_t link_doubles = L * (1 + 1 + 4 + (PRHF_GRAD_SKIP_OUTPUTS - PRHF_GRAD_OUTPUTS) + (size_t)row_width);
         rc = ensure(c, c->partial, queue_bytes + work_bytes + scan_bytes + link_doubles * 8 + L * 4);
         if (rc != PRHF_OK) return rc;
         char* q = static_cast<char*>(c->partial.p);
@@ -2666,7 +2702,7 @@ int prhf_gradient_muf_f64(prhf_ctx* c, int32_t geometry, const double* den, cons
         m.group_field = reinterpret_cast<long long*>(r); r += L;
         m.state = r; r += 4 * L;
         m.best = r; r += L * (PRHF_GRAD_SKIP_OUTPUTS - PRHF_GRAD_OUTPUTS);
-        h.out = r; r += L * PRHF_GRAD_SKIP_OUTPUTS;
+        h.out = r; r += L * (size_t)row_width;
         m.active = reinterpret_cast<int*>(r);
     }
     h.group_field = m.group_field; h.active = m.active;
@@ -2676,17 +2712,54 @@ int prhf_gradient_muf_f64(prhf_ctx* c, int32_t geometry, const double* den, cons
     m.p.mu = m.b.mu; m.p.mup = m.b.mup; m.p.a0 = p; m.p.a1 = p + n0; m.p.rec = rec; m.p.n_fields = n_links;
     m.p.n0 = (int)n0; m.p.n1 = (int)n1; m.p.uniform0 = u0; m.p.uniform1 = u1; m.p.edge_order = edge_order;
     HIP_TRY(hipEventRecord(c->begin_ev(), c->stream));
-    HIP_TRY(prhf::launch_grad_muf(m, c->stream));
+    HIP_TRY(prhf::launch_grad_muf(m, n_hops != 0, c->stream));
     HIP_TRY(hipEventRecord(c->pending_end_ev(), c->stream));
     c->mark_timed();
     c->status_pending = true;
     if (!dev) HIP_TRY(hipMemcpyAsync(out, d_result, out_elems * 8, hipMemcpyDeviceToHost, c->stream));
     return grad_skip_finish(c, h.queue);
 }
+}  // namespace
+
+int prhf_gradient_muf_f64(prhf_ctx* c, int32_t geometry, const double* den, const double* bmag, const double* bpsi, int64_t n0,
+                          int64_t n1, const double* axis0, const double* axis1, int32_t mode, int32_t edge_order,
+                          const double* link_x0_km, const double* link_z0_km, const double* link_target_km, int64_t n_links,
+                          double f_lo_hz, double f_hi_hz, int32_t n_bisect, const double* scan_elevation_deg, int64_t n_scan,
+                          double earth_radius_km, double s_max_km, double rtol, double atol, double max_step_km,
+                          double z_ground_km, double top, double left, double right, int32_t renormalize_every, double fill_n,
+                          double fill_grad, double fill_mup, double elev_tol_deg, int32_t max_iter, double* out, uint32_t flags) {
+    if (!c) return fail(PRHF_EINVAL, "null context");
+    return grad_muf_run(c, 0, geometry, den, bmag, bpsi, n0, n1, axis0, axis1, mode, edge_order, link_x0_km, link_z0_km, link_target_km,
+                        n_links, f_lo_hz, f_hi_hz, n_bisect, scan_elevation_deg, n_scan, earth_radius_km, s_max_km, rtol, atol,
+                        max_step_km, z_ground_km, top, left, right, renormalize_every, fill_n, fill_grad, fill_mup, elev_tol_deg,
+                        max_iter, out, flags);
+}
+
+int prhf_gradient_hop_muf_f64(prhf_ctx* c, int32_t geometry, const double* den, const double* bmag, const double* bpsi,
+                              int64_t n0, int64_t n1, const double* axis0, const double* axis1, int32_t mode,
+                              int32_t edge_order, const double* link_x0_km, const double* link_z0_km,
+                              const double* link_target_km, int64_t n_links, double f_lo_hz, double f_hi_hz, int32_t n_bisect,
+                              const double* scan_elevation_deg, int64_t n_scan, double earth_radius_km, double s_max_km,
+                              double rtol, double atol, double max_step_km, double z_ground_km, double top, double left,
+                              double right, int32_t renormalize_every, double fill_n, double fill_grad, double fill_mup,
+                              double elev_tol_deg, int32_t max_iter, int32_t n_hops, double* out, uint32_t flags) {
+    if (!c) return fail(PRHF_EINVAL, "null context");
+    if (n_hops < 1 || n_hops > PRHF_GRAD_MAX_HOPS) return fail(PRHF_EINVAL, "n_hops is 1 .. 16");
+    return grad_muf_run(c, n_hops, geometry, den, bmag, bpsi, n0, n1, axis0, axis1, mode, edge_order, link_x0_km, link_z0_km, link_target_km,
+                        n_links, f_lo_hz, f_hi_hz, n_bisect, scan_elevation_deg, n_scan, earth_radius_km, s_max_km, rtol, atol,
+                        max_step_km, z_ground_km, top, left, right, renormalize_every, fill_n, fill_grad, fill_mup, elev_tol_deg,
+                        max_iter, out, flags);
+}
 
 int prhf_gradient_skip_counters(prhf_ctx* c, uint64_t* counters) {
     if (!c || !counters) return fail(PRHF_EINVAL, "null pointer");
     for (int k = 0; k < PRHF_GRAD_SKIP_COUNTERS; ++k) counters[k] = c->grad_skip_counters[k];
+    return PRHF_OK;
+}
+
+int prhf_gradient_hop_skip_counters(prhf_ctx* c, uint64_t* counters) {
+    if (!c || !counters) return fail(PRHF_EINVAL, "null pointer");
+    for (int k = 0; k <= PRHF_GRAD_SKIP_COUNTERS; ++k) counters[k] = c->grad_skip_counters[k];
     return PRHF_OK;
 }
 

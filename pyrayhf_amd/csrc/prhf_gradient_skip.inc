@@ -1,10 +1,11 @@
 // prhf_gradient_skip.inc - for the gradient ray tracers of both geometries: the fields of many frequencies built on the
 // device from one 2-D ionosphere, the skip distance of a transmitter (field, x0, z0), and the MUF of a link through that
 // ionosphere - the frequency at which the skip distance reaches the link's target.  Included by prhf_kernels.hip behind
-// prhf_gradient_homing.inc, inside namespace prhf.  Every ray here is grad_ray<GEO, FULL> of prhf_gradient.inc: FULL =
-// false (the range-only ray) for the scan and the refinement, FULL = true for the result rows, so that a ray of a given
-// field, launch point, elevation and controls has the bits prhf_trace_gradient_f64 / prhf_trace_gradient_spherical_f64
-// give it.  The reference has none of the three; DESIGN.md section 4.11 defines them: the rule is section 4.10's.
+// prhf_gradient_homing.inc and prhf_gradient_hops.inc, inside namespace prhf.  Every ray here is grad_ray<GEO, FULL> of
+// prhf_gradient.inc: FULL = false (the range-only ray) for the scan and the refinement, FULL = true for the result rows,
+// so that a ray of a given field, launch point, elevation and controls has the bits prhf_trace_gradient_f64 /
+// prhf_trace_gradient_spherical_f64 give it.  The reference has none of the three; DESIGN.md section 4.11 defines them:
+// the rule is section 4.10's.
 //
 // Fields (launch_field_bmax, launch_field_build): per node and frequency f_N = sqrt(Ne) c_p, X = (f_N f_N) / (f f),
 // Y = (g_p B) / f, each operation rounded once, then index_faithful<mode> - or index_unmagnetised when that frequency's
@@ -36,12 +37,20 @@
 // enqueued on one stream; the host waits once.
 // queue[]: 0 the work list's length (zeroed by every scan launch), 1 rays traced by the refine lanes, 2 ray slots (64
 // per trip of a refine wavefront's loop), 3 refine wavefronts with work, 4 groups refined: lane utilisation = [1] / [2].
+//
+// Multi-hop (DESIGN.md section 4.13, prhf_gradient_hop_skip_f64 / prhf_gradient_hop_muf_f64): the same rule with D(e)
+// the landing x of hop g.n_hops - 1 of the chain launched at e - grad_hops<GEO, false> of prhf_gradient_hops.inc, NaN
+// unless every hop lands - and a row of 6 + PRHF_GRAD_HOP_OUTPUTS g.n_hops doubles: the head, then grad_hops<GEO, true>
+// at the row's elevation.  The scan, refine and result kernels are instantiated on a compile-time CHAIN flag: false is
+// the one-hop call as it was (the direct grad_ray, rows of 18), true the chain; the entry point chooses.  The node and
+// the MUF kernels take the row's stride from h.row_width.  A ray slot is still one lane-trip, whatever the hops;
+// queue[5] counts the hops of the refine lanes' chains that landed (n_hops each; a chain that does not land ends its
+// group's search and is counted under [1] alone).
 
 namespace {
 
 constexpr int kGradSkipOutputs = PRHF_GRAD_SKIP_OUTPUTS;
 constexpr int kGradSkipHead = PRHF_GRAD_SKIP_OUTPUTS - PRHF_GRAD_OUTPUTS;   // skip_km .. n_evals
-constexpr int kGradMufOutputs = PRHF_GRAD_MUF_OUTPUTS;
 
 // ---- fields -----------------------------------------------------------------------------------------------------------
 // words[0] = nanmax|B| as a bit pattern (it orders like the double for non-negative values), words[1] != 0 when any B is
@@ -92,7 +101,15 @@ __global__ __launch_bounds__(256) void field_build_kernel(const FieldBuildArgs a
 }
 
 // ---- skip distance ----------------------------------------------------------------------------------------------------
-template <int GEO>
+// D(e): the range-only ray, or the range-only chain of a.n_hops hops
+template <int GEO, bool CHAIN>
+__device__ __forceinline__ double grad_skip_range(const GradTraceArgs& a, const double* axes, long long field, double elev_deg,
+                                                  double x0_km, double z0_km) {
+    if (CHAIN) return grad_hops<GEO, false>(a, axes, axes + a.n0, 0, field, elev_deg, x0_km, z0_km, nullptr);
+    return grad_ray<GEO, false>(a, axes, axes + a.n0, 0, field, elev_deg, x0_km, z0_km, nullptr);
+}
+
+template <int GEO, bool CHAIN>
 __global__ __launch_bounds__(PRHF_GRAD_TRACE_THREADS) void grad_skip_scan_kernel(const GradSkipArgs h) {
     extern __shared__ __attribute__((aligned(16))) double grad_axes[];
     if (blockIdx.x == 0 && threadIdx.x == 0) h.queue[0] = 0u;      // (the work list's length: read two kernels on)
@@ -107,8 +124,7 @@ __global__ __launch_bounds__(PRHF_GRAD_TRACE_THREADS) void grad_skip_scan_kernel
     if (f < 0 || f >= h.g.n_fields)       // (device-resident group_field: not checked by the host) no ray, a NaN row
         post_status(h.g.status, (unsigned)PRHF_STATUS_BADFIELD);
     else
-        d = grad_ray<GEO, false>(h.g, grad_axes, grad_axes + h.g.n0, 0, f, h.scan_elev[i], h.group_x0[grp], h.group_z0[grp],
-                                 nullptr);
+        d = grad_skip_range<GEO, CHAIN>(h.g, grad_axes, f, h.scan_elev[i], h.group_x0[grp], h.group_z0[grp]);
     h.scan_d[grp * h.n_scan + i] = d;
 }
 
@@ -117,7 +133,7 @@ __global__ __launch_bounds__(64) void grad_skip_node_kernel(const GradSkipArgs h
     const long long g = blockIdx.x;
     if (h.active && h.active[g] == 0) return;
     const double* d = h.scan_d + g * h.n_scan;
-    double* row = h.out + g * kGradSkipOutputs;
+    double* row = h.out + g * h.row_width;
     const double inf = __builtin_inf();
     double d_min = inf;
     int i_min = -1;
@@ -134,7 +150,11 @@ __global__ __launch_bounds__(64) void grad_skip_node_kernel(const GradSkipArgs h
         }
     }
     if (i_min < 0) {                                                // no ray of the scan lands
-        if (lane < kGradSkipOutputs) row[lane] = (lane == 2 || lane == 3) ? -1.0 : (lane == 5) ? 0.0 : qnan();
+        // (behind the head: NaN for the one-hop call, the chain call's hop rows unused as grad_hops writes them)
+        const bool hop_rows = h.row_width != kGradSkipOutputs;
+        for (int k = lane; k < h.row_width; k += 64)
+            row[k] = (k == 2 || k == 3) ? -1.0 : (k == 5) ? 0.0
+                     : (hop_rows && k >= kGradSkipHead) ? grad_hop_unused((k - kGradSkipHead) % PRHF_GRAD_HOP_OUTPUTS) : qnan();
         return;
     }
     const bool edge = i_min == 0 || i_min == h.n_scan - 1 || !finite64(d[max(i_min - 1, 0)]) ||
@@ -153,7 +173,7 @@ __global__ __launch_bounds__(64) void grad_skip_node_kernel(const GradSkipArgs h
     }
 }
 
-template <int GEO>
+template <int GEO, bool CHAIN>
 __global__ __launch_bounds__(PRHF_GRAD_TRACE_THREADS) void grad_skip_refine_kernel(const GradSkipArgs h) {
 #pragma clang fp contract(off)
     extern __shared__ __attribute__((aligned(16))) double grad_axes[];
@@ -176,7 +196,7 @@ __global__ __launch_bounds__(PRHF_GRAD_TRACE_THREADS) void grad_skip_refine_kern
         d_b = h.scan_d[g * h.n_scan + i];
     }
     bool busy = mine;
-    unsigned rays = 0, trips = 0;
+    unsigned rays = 0, trips = 0, landed = 0;
     // golden-section search on (a, b, c): D_b is the least ground range seen; at most max_iter rays, one per trip
     for (int trip = 0; trip <= h.max_iter && __ballot(busy) != 0; ++trip) {
         ++trips;
@@ -190,9 +210,10 @@ __global__ __launch_bounds__(PRHF_GRAD_TRACE_THREADS) void grad_skip_refine_kern
             } else if (n_evals >= h.max_iter) {
                 status = 3; busy = false;
             } else {
-                const double dx = grad_ray<GEO, false>(h.g, grad_axes, grad_axes + h.g.n0, 0, f, x, x0, z0, nullptr);
+                const double dx = grad_skip_range<GEO, CHAIN>(h.g, grad_axes, f, x, x0, z0);
                 ++n_evals;
                 ++rays;
+                if (CHAIN && finite64(dx)) ++landed;
                 if (!finite64(dx)) {
                     status = 2; busy = false;                       // the ray does not land inside the bracket
                 } else if (dx < d_b) {
@@ -206,7 +227,7 @@ __global__ __launch_bounds__(PRHF_GRAD_TRACE_THREADS) void grad_skip_refine_kern
         }
     }
     if (mine) {
-        double* row = h.out + g * kGradSkipOutputs;
+        double* row = h.out + g * h.row_width;
         row[0] = d_b;
         row[1] = e_b;
         row[2] = (double)status;
@@ -214,6 +235,7 @@ __global__ __launch_bounds__(PRHF_GRAD_TRACE_THREADS) void grad_skip_refine_kern
         row[4] = e_c - e_a;
         row[5] = (double)n_evals;
         if (rays) atomicAdd(h.queue + 1, rays);
+        if (CHAIN && landed) atomicAdd(h.queue + 5, landed * (unsigned)h.g.n_hops);
     }
     if (lane == 0) {
         atomicAdd(h.queue + 2, 64u * trips);
@@ -222,17 +244,21 @@ __global__ __launch_bounds__(PRHF_GRAD_TRACE_THREADS) void grad_skip_refine_kern
     }
 }
 
-template <int GEO>
+template <int GEO, bool CHAIN>
 __global__ __launch_bounds__(PRHF_GRAD_TRACE_THREADS) void grad_skip_result_kernel(const GradSkipArgs h) {
     extern __shared__ __attribute__((aligned(16))) double grad_axes[];
     grad_home_stage_axes(h.g, grad_axes);
     const long long g = (long long)blockIdx.x * 64 + threadIdx.x;
     if (g >= h.n_groups) return;
     if (h.active && h.active[g] == 0) return;
-    double* row = h.out + g * kGradSkipOutputs;
+    double* row = h.out + g * h.row_width;
     if (row[2] == -1.0) return;                                     // no ray of the scan lands (or a bad field): NaN row
-    (void)grad_ray<GEO, true>(h.g, grad_axes, grad_axes + h.g.n0, 0, h.group_field[g], row[1], h.group_x0[g], h.group_z0[g],
-                              row + kGradSkipHead);
+    if (CHAIN)
+        (void)grad_hops<GEO, true>(h.g, grad_axes, grad_axes + h.g.n0, 0, h.group_field[g], row[1], h.group_x0[g],
+                                   h.group_z0[g], row + kGradSkipHead);
+    else
+        (void)grad_ray<GEO, true>(h.g, grad_axes, grad_axes + h.g.n0, 0, h.group_field[g], row[1], h.group_x0[g],
+                                  h.group_z0[g], row + kGradSkipHead);
 }
 
 // ---- MUF: one thread per link -----------------------------------------------------------------------------------------
@@ -258,7 +284,7 @@ __global__ __launch_bounds__(64) void grad_muf_set_kernel(const GradMufArgs m, i
         on = (st == 0.0 || st == 1.0) ? 1 : 0;
         if (on) {
             f = m.state[4 * l];
-            for (int k = 0; k < kGradSkipHead; ++k) m.k.out[l * kGradSkipOutputs + k] = m.best[l * kGradSkipHead + k];
+            for (int k = 0; k < kGradSkipHead; ++k) m.k.out[l * m.k.row_width + k] = m.best[l * kGradSkipHead + k];
         }
     }
     m.group_freq[l] = f;
@@ -268,15 +294,15 @@ __global__ __launch_bounds__(64) void grad_muf_set_kernel(const GradMufArgs m, i
 __global__ __launch_bounds__(64) void grad_muf_decide_kernel(const GradMufArgs m, int phase) {
     const long long l = (long long)blockIdx.x * 64 + threadIdx.x;
     if (l >= m.n_links) return;
-    const double* cur = m.k.out + l * kGradSkipOutputs;
+    const double* cur = m.k.out + l * m.k.row_width;
     double* s = m.state + 4 * l;
     if (phase == 3) {
-        double* row = m.out + l * kGradMufOutputs;
+        double* row = m.out + l * (3 + m.k.row_width);
         const bool none = s[2] == -1.0 || s[2] == 2.0;
         row[0] = none ? qnan() : s[0];
         row[1] = none ? qnan() : s[1];
         row[2] = s[2];
-        for (int k = 0; k < kGradSkipOutputs; ++k) row[3 + k] = none ? qnan() : cur[k];
+        for (int k = 0; k < m.k.row_width; ++k) row[3 + k] = none ? qnan() : cur[k];
         return;
     }
     if (m.active[l] == 0) return;
@@ -299,7 +325,16 @@ __global__ __launch_bounds__(64) void grad_muf_decide_kernel(const GradMufArgs m
         for (int k = 0; k < kGradSkipHead; ++k) best[k] = cur[k];
 }
 
-hipError_t grad_skip_enqueue(const GradSkipArgs& h, bool search, bool result, hipStream_t stream) {
+// One launch of kernel<GEO, CHAIN> for the call's geometry and kind
+#define PRHF_GRAD_SKIP_LAUNCH(kernel, grid)                                                                        \
+    do {                                                                                                           \
+        if (sph && chain) hipLaunchKernelGGL((kernel<PRHF_GEO_SPHERICAL, true>), grid, threads, lds, stream, h);   \
+        else if (sph) hipLaunchKernelGGL((kernel<PRHF_GEO_SPHERICAL, false>), grid, threads, lds, stream, h);      \
+        else if (chain) hipLaunchKernelGGL((kernel<PRHF_GEO_CARTESIAN, true>), grid, threads, lds, stream, h);     \
+        else hipLaunchKernelGGL((kernel<PRHF_GEO_CARTESIAN, false>), grid, threads, lds, stream, h);               \
+    } while (0)
+
+hipError_t grad_skip_enqueue(const GradSkipArgs& h, bool chain, bool search, bool result, hipStream_t stream) {
     const long long per_group = (h.n_scan + 63) / 64;
     const size_t lds = field_axes_lds_bytes(h.g.n0, h.g.n1);
     const dim3 threads(PRHF_GRAD_TRACE_THREADS), scan_grid((unsigned)(h.n_groups * per_group)),
@@ -307,23 +342,25 @@ hipError_t grad_skip_enqueue(const GradSkipArgs& h, bool search, bool result, hi
     const bool sph = h.g.geometry == PRHF_GEO_SPHERICAL;
     hipError_t e;
     if (search) {
-        if (sph) hipLaunchKernelGGL(grad_skip_scan_kernel<PRHF_GEO_SPHERICAL>, scan_grid, threads, lds, stream, h);
-        else hipLaunchKernelGGL(grad_skip_scan_kernel<PRHF_GEO_CARTESIAN>, scan_grid, threads, lds, stream, h);
+        PRHF_GRAD_SKIP_LAUNCH(grad_skip_scan_kernel, scan_grid);
         e = hipGetLastError();
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(grad_skip_node_kernel, dim3((unsigned)h.n_groups), dim3(64), 0, stream, h);
         e = hipGetLastError();
         if (e != hipSuccess) return e;
-        if (sph) hipLaunchKernelGGL(grad_skip_refine_kernel<PRHF_GEO_SPHERICAL>, row_grid, threads, lds, stream, h);
-        else hipLaunchKernelGGL(grad_skip_refine_kernel<PRHF_GEO_CARTESIAN>, row_grid, threads, lds, stream, h);
+        PRHF_GRAD_SKIP_LAUNCH(grad_skip_refine_kernel, row_grid);
         e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
-    if (result) {
-        if (sph) hipLaunchKernelGGL(grad_skip_result_kernel<PRHF_GEO_SPHERICAL>, row_grid, threads, lds, stream, h);
-        else hipLaunchKernelGGL(grad_skip_result_kernel<PRHF_GEO_CARTESIAN>, row_grid, threads, lds, stream, h);
-    }
+    if (result) PRHF_GRAD_SKIP_LAUNCH(grad_skip_result_kernel, row_grid);
     return hipGetLastError();
+}
+#undef PRHF_GRAD_SKIP_LAUNCH
+
+// (a chain call: 1 .. PRHF_GRAD_MAX_HOPS hops and the row that holds them; the one-hop call: rows of 18)
+bool grad_skip_rows_fit(const GradSkipArgs& h, bool chain) {
+    if (!chain) return h.row_width == kGradSkipOutputs;
+    return h.g.n_hops >= 1 && h.g.n_hops <= PRHF_GRAD_MAX_HOPS && h.row_width == kGradSkipHead + PRHF_GRAD_HOP_OUTPUTS * h.g.n_hops;
 }
 
 bool grad_skip_fits(const GradSkipArgs& h) {
@@ -349,17 +386,17 @@ hipError_t launch_field_build(const FieldBuildArgs& a, hipStream_t stream) {
     return hipGetLastError();
 }
 
-hipError_t launch_grad_skip(const GradSkipArgs& h, hipStream_t stream) {
+hipError_t launch_grad_skip(const GradSkipArgs& h, bool chain, hipStream_t stream) {
     if (h.n_groups <= 0) return hipSuccess;
-    if (!grad_skip_fits(h)) return hipErrorInvalidValue;
+    if (!grad_skip_fits(h) || !grad_skip_rows_fit(h, chain)) return hipErrorInvalidValue;
     const hipError_t e = hipMemsetAsync(h.queue, 0, PRHF_GRAD_SKIP_QUEUE_WORDS * sizeof(unsigned), stream);
     if (e != hipSuccess) return e;
-    return grad_skip_enqueue(h, true, true, stream);
+    return grad_skip_enqueue(h, chain, true, true, stream);
 }
 
-hipError_t launch_grad_muf(const GradMufArgs& m, hipStream_t stream) {
+hipError_t launch_grad_muf(const GradMufArgs& m, bool chain, hipStream_t stream) {
     if (m.n_links <= 0) return hipSuccess;
-    if (!grad_skip_fits(m.k)) return hipErrorInvalidValue;
+    if (!grad_skip_fits(m.k) || !grad_skip_rows_fit(m.k, chain)) return hipErrorInvalidValue;
     hipError_t e = hipMemsetAsync(m.k.queue, 0, PRHF_GRAD_SKIP_QUEUE_WORDS * sizeof(unsigned), stream);
     if (e != hipSuccess) return e;
     e = launch_field_bmax(m.b.bmag, m.b.plane, const_cast<unsigned long long*>(m.b.bmax), stream);
@@ -375,7 +412,7 @@ hipError_t launch_grad_muf(const GradMufArgs& m, hipStream_t stream) {
         if (e != hipSuccess) return e;
         e = launch_field_pack(m.p, stream);
         if (e != hipSuccess) return e;
-        e = grad_skip_enqueue(m.k, phase != 3, phase == 3, stream);
+        e = grad_skip_enqueue(m.k, chain, phase != 3, phase == 3, stream);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(grad_muf_decide_kernel, links, dim3(64), 0, stream, m, phase);
         e = hipGetLastError();

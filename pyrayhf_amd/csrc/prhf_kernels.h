@@ -505,7 +505,9 @@ hipError_t launch_field_build(const FieldBuildArgs& a, hipStream_t stream);
 #define PRHF_GRAD_SKIP_OUTPUTS (6 + PRHF_GRAD_OUTPUTS)       // skip_km, elevation_deg, status, scan_index, bracket_deg, n_evals, then the tracer's twelve
 #define PRHF_GRAD_MUF_OUTPUTS (3 + PRHF_GRAD_SKIP_OUTPUTS)   // muf_hz, f_above_hz, status, then the skip row at muf_hz
 #define PRHF_GRAD_SKIP_COUNTERS 4                            // groups refined, rays refined, ray slots of the refine waves, refine waves
-#define PRHF_GRAD_SKIP_QUEUE_WORDS 8                         // [0] the work list's length, [1..3] counters 1..3, [4] counter 0
+#define PRHF_GRAD_SKIP_QUEUE_WORDS 8                         // [0] the work list's length, [1..3] counters 1..3, [4] counter 0, [5] hop rays
+// Multi-hop rows: the six head values, then the g.n_hops hop rows of launch_grad_hop_trace
+#define PRHF_GRAD_HOP_SKIP_OUTPUTS(n_hops) (6 + PRHF_GRAD_HOP_OUTPUTS * (n_hops))
 struct GradSkipArgs {
     GradTraceArgs g;             // records, axes, controls, fills, geometry, status; the per-ray arrays and the paths are null
     const long long* group_field;   // (n_groups) field, launch point of each group
@@ -520,12 +522,16 @@ struct GradSkipArgs {
     double* scan_d;              // (n_groups, n_scan) scratch: ground range of every scan ray
     int* work;                   // (n_groups, 2) scratch: (group, scan node) of the groups to refine; 8-byte aligned
     unsigned* queue;             // PRHF_GRAD_SKIP_QUEUE_WORDS words of scratch, zero when the call's first kernel starts
-    double* out;                 // (n_groups, PRHF_GRAD_SKIP_OUTPUTS)
+    // the doubles of a row of `out`: PRHF_GRAD_SKIP_OUTPUTS for the one-hop call (g.n_hops is not read);
+    // PRHF_GRAD_HOP_SKIP_OUTPUTS(g.n_hops) for the chain call, where D(e) is the landing x of hop g.n_hops - 1
+    int row_width;
+    double* out;                 // (n_groups, row_width)
 };
-hipError_t launch_grad_skip(const GradSkipArgs& h, hipStream_t stream);   // scan, node, refinement, result rays: four kernels
+// scan, node, refinement, result rays: four kernels.  chain: the multi-hop instantiations (rows of row_width doubles)
+hipError_t launch_grad_skip(const GradSkipArgs& h, bool chain, hipStream_t stream);
 struct GradMufArgs {
     GradSkipArgs k;              // a link is a group: k.n_groups == n_links, k.group_field == group_field, k.active == active,
-                                 // k.g.rec == p.rec, k.out (n_links, PRHF_GRAD_SKIP_OUTPUTS) scratch: the skip rows of the trip
+                                 // k.g.rec == p.rec, k.out (n_links, k.row_width) scratch: the skip rows of the trip
     FieldBuildArgs b;            // b.freq == group_freq, b.active == active, b.n_freq == n_links
     FieldPackArgs p;             // p.mu == b.mu, p.mup == b.mup, p.n_fields == n_links
     const double* link_target;   // (n_links) target ground_range_km
@@ -537,10 +543,10 @@ struct GradMufArgs {
     int* active;                 // (n_links) scratch
     double* state;               // (n_links, 4) scratch: lo, hi, status, 0
     double* best;                // (n_links, 6) scratch: the head of the skip row at lo
-    double* out;                 // (n_links, PRHF_GRAD_MUF_OUTPUTS)
+    double* out;                 // (n_links, 3 + k.row_width)
 };
 // Bmax, then (2 + n_bisect) x (set, build, pack, scan, node, refine, decide), then set, build, pack, result, decide
-hipError_t launch_grad_muf(const GradMufArgs& m, hipStream_t stream);
+hipError_t launch_grad_muf(const GradMufArgs& m, bool chain, hipStream_t stream);
 
 // residual / cost may be null
 hipError_t launch_residual(const double* vh_model, const double* vh_obs, long long n_prof, int n_freq,

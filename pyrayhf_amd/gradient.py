@@ -38,7 +38,9 @@ __all__ = ["build_refractive_index_interpolator_cartesian", "build_refractive_in
            "home_rays_spherical_gradient", "refractive_field_device", "skip_distance_cartesian_gradient",
            "skip_distance_spherical_gradient", "muf_cartesian_gradient", "muf_spherical_gradient", "STATUS_NAMES",
            "trace_hops_cartesian_gradient", "trace_hops_spherical_gradient", "trace_hop_fan_cartesian_gradient",
-           "trace_hop_fan_spherical_gradient", "home_hops_cartesian_gradient", "home_hops_spherical_gradient"]
+           "trace_hop_fan_spherical_gradient", "home_hops_cartesian_gradient", "home_hops_spherical_gradient",
+           "skip_distance_hops_cartesian_gradient", "skip_distance_hops_spherical_gradient",
+           "muf_hops_cartesian_gradient", "muf_hops_spherical_gradient"]
 
 STATUS_NAMES = ("ground", "domain", "length", "failure")          # reference library.py:1391-1398
 _KEYS = ("group_path_km", "group_delay_sec", "x_midpoint", "z_midpoint", "ground_range_km", "x_apex_km", "z_apex_km",
@@ -859,15 +861,35 @@ def _search_controls(scan_elevation_deg, elev_tol_deg, max_iter, controls):
     return scan, elev_tol_deg, max_iter, ctl
 
 
-def _skip_rows(out, lead):
-    """The dict of the skip calls from rows of 18 (include/prhf.h), reshaped to ``lead``."""
-    out = out.reshape(lead + (18,))
+def _skip_head(out):
+    """The six rule keys from rows ``(..., >= 6)`` (include/prhf.h)."""
     res = {"skip_km": out[..., 0].copy(), "elevation_deg": out[..., 1].copy()}
-    status = np.where(np.isfinite(out[..., 2]), out[..., 2], -1.0).astype(np.int64)
-    res["status"] = status
+    res["status"] = np.where(np.isfinite(out[..., 2]), out[..., 2], -1.0).astype(np.int64)
     res["scan_index"] = np.where(np.isfinite(out[..., 3]), out[..., 3], -1.0).astype(np.int64)
     res["bracket_deg"] = out[..., 4].copy()
     res["n_evals"] = np.where(np.isfinite(out[..., 5]), out[..., 5], 0.0).astype(np.int64)
+    return res
+
+
+_HOP_UNUSED_ROW = np.array([np.nan] * 10 + [-1.0, 0.0, 0.0, 0.0, 0.0])
+
+
+def _hop_skip_rows(out, lead, n_hops):
+    """The dict of the multi-hop skip calls from rows of ``6 + 15 n_hops``, reshaped to ``lead``: the rule keys, then
+    ``_hop_dict``'s.  A row that a MUF call left NaN throughout (no frequency found) reads as unused hops."""
+    out = out.reshape(lead + (6 + 15 * n_hops,))
+    res = _skip_head(out)
+    rows = out[..., 6:].reshape(lead + (n_hops, 15)).copy()
+    rows[~np.isfinite(out[..., 2])] = _HOP_UNUSED_ROW
+    res.update(_hop_dict(rows, "ray_status"))
+    return res
+
+
+def _skip_rows(out, lead):
+    """The dict of the skip calls from rows of 18 (include/prhf.h), reshaped to ``lead``."""
+    out = out.reshape(lead + (18,))
+    res = _skip_head(out)
+    status = res["status"]
     none = status < 0
     for i, k in enumerate(_KEYS):
         v = out[..., 6 + i]
@@ -881,9 +903,13 @@ def _skip_rows(out, lead):
     return res
 
 
-def _skip(field, geometry, name, x0_km, z0_km, controls, scan_elevation_deg, elev_tol_deg, max_iter, earth_radius):
-    """Both skip calls: the groups are (field, transmitter) in C order."""
+def _skip(field, geometry, name, x0_km, z0_km, controls, scan_elevation_deg, elev_tol_deg, max_iter, earth_radius,
+          n_hops=None):
+    """Both skip calls: the groups are (field, transmitter) in C order.  ``n_hops``: the skip distance of the landing of
+    hop ``n_hops - 1`` (``prhf_gradient_hop_skip_f64``), whose rows hold every hop."""
     _need_geometry(field, geometry, name)
+    if n_hops is not None:
+        n_hops = _check_hops(n_hops)
     scan, elev_tol_deg, max_iter, ctl = _search_controls(scan_elevation_deg, elev_tol_deg, max_iter, controls)
     x0 = np.atleast_1d(np.asarray(x0_km, dtype=np.float64))
     z0 = np.atleast_1d(np.asarray(z0_km, dtype=np.float64))
@@ -897,15 +923,18 @@ def _skip(field, geometry, name, x0_km, z0_km, controls, scan_elevation_deg, ele
     group_f = np.ascontiguousarray(np.repeat(np.arange(n_fields, dtype=np.int64), n_tx))
     group_x = np.ascontiguousarray(np.tile(x0, n_fields))
     group_z = np.ascontiguousarray(np.tile(z0, n_fields))
-    out = np.empty((group_f.size, 18), dtype=np.float64)
+    out = np.empty((group_f.size, 18 if n_hops is None else 6 + 15 * n_hops), dtype=np.float64)
     rec = field.records()
     ctx = field._ctx()
-    _native.raise_for(ctx.gradient_skip(0 if earth_radius is None else 1, rec.data_ptr(), n_fields, field.axis0.size,
-                                        field.axis1.size, field.axis0.ctypes.data, field.axis1.ctypes.data,
-                                        group_f.ctypes.data, group_x.ctypes.data, group_z.ctypes.data, group_f.size,
-                                        scan.ctypes.data, scan.size, 0.0 if earth_radius is None else earth_radius, ctl,
-                                        field.fills, elev_tol_deg, max_iter, out.ctypes.data, 0))
-    return _skip_rows(out, (n_fields, n_tx))
+    head = (0 if earth_radius is None else 1, rec.data_ptr(), n_fields, field.axis0.size, field.axis1.size,
+            field.axis0.ctypes.data, field.axis1.ctypes.data, group_f.ctypes.data, group_x.ctypes.data, group_z.ctypes.data,
+            group_f.size, scan.ctypes.data, scan.size, 0.0 if earth_radius is None else earth_radius, ctl, field.fills,
+            elev_tol_deg, max_iter)
+    if n_hops is None:
+        _native.raise_for(ctx.gradient_skip(*head, out.ctypes.data, 0))
+        return _skip_rows(out, (n_fields, n_tx))
+    _native.raise_for(ctx.gradient_hop_skip(*head, n_hops, out.ctypes.data, 0))
+    return _hop_skip_rows(out, (n_fields, n_tx), n_hops)
 
 
 def skip_distance_cartesian_gradient(field, x0_km=0.0, z0_km=0.0, s_max_km=5000.0, *, scan_elevation_deg=None,
@@ -965,7 +994,9 @@ _MUF_SCRATCH_BYTES = 1 << 30      # the MUF calls cut their links into slabs who
 
 
 def _muf(geometry, target_x_km, x0_km, z0_km, Ne, Babs, bpsi, z_grid, x_grid, mode, f_lo_hz, f_hi_hz, n_bisect, controls,
-         scan_elevation_deg, elev_tol_deg, max_iter, R_E, edge_order, fills, device, slab_links):
+         scan_elevation_deg, elev_tol_deg, max_iter, R_E, edge_order, fills, device, slab_links, n_hops=None):
+    if n_hops is not None:
+        n_hops = _check_hops(n_hops)
     Ne, Babs, bpsi, axis0, axis1, R_E = _ionosphere(Ne, Babs, bpsi, z_grid, x_grid, mode, geometry, R_E, edge_order)
     scan, elev_tol_deg, max_iter, ctl = _search_controls(scan_elevation_deg, elev_tol_deg, max_iter, controls)
     n_bisect, f_lo_hz, f_hi_hz = int(n_bisect), float(f_lo_hz), float(f_hi_hz)
@@ -983,20 +1014,23 @@ def _muf(geometry, target_x_km, x0_km, z0_km, Ne, Babs, bpsi, z_grid, x_grid, mo
     slab_links = int(slab_links)
     if slab_links < 1:
         raise ValueError("a slab holds at least one link")
-    out = np.empty((t.size, 21), dtype=np.float64)
+    out = np.empty((t.size, 21 if n_hops is None else 9 + 15 * n_hops), dtype=np.float64)
     ctx = _native.host_context(device)
     for lo in range(0, t.size, slab_links):
         n = min(slab_links, t.size - lo)
         # (contiguous 1-D arrays: a slice's address is its first element's)
-        _native.raise_for(ctx.gradient_muf(0 if geometry == "cartesian" else 1, Ne.ctypes.data, Babs.ctypes.data,
-                                           bpsi.ctypes.data, axis0.size, axis1.size, axis0.ctypes.data, axis1.ctypes.data,
-                                           _MODE_CODE[mode], edge_order, x0[lo:].ctypes.data, z0[lo:].ctypes.data,
-                                           t[lo:].ctypes.data, n, f_lo_hz, f_hi_hz, n_bisect, scan.ctypes.data, scan.size,
-                                           0.0 if R_E is None else R_E, ctl, fills, elev_tol_deg, max_iter,
-                                           out[lo:].ctypes.data, 0))
+        head = (0 if geometry == "cartesian" else 1, Ne.ctypes.data, Babs.ctypes.data, bpsi.ctypes.data, axis0.size,
+                axis1.size, axis0.ctypes.data, axis1.ctypes.data, _MODE_CODE[mode], edge_order, x0[lo:].ctypes.data,
+                z0[lo:].ctypes.data, t[lo:].ctypes.data, n, f_lo_hz, f_hi_hz, n_bisect, scan.ctypes.data, scan.size,
+                0.0 if R_E is None else R_E, ctl, fills, elev_tol_deg, max_iter)
+        if n_hops is None:
+            _native.raise_for(ctx.gradient_muf(*head, out[lo:].ctypes.data, 0))
+        else:
+            _native.raise_for(ctx.gradient_hop_muf(*head, n_hops, out[lo:].ctypes.data, 0))
     res = {"muf_hz": out[:, 0].reshape(shape).copy(), "f_above_hz": out[:, 1].reshape(shape).copy(),
            "status": out[:, 2].astype(np.int64).reshape(shape)}
-    for k, v in _skip_rows(np.ascontiguousarray(out[:, 3:]), shape).items():
+    row = np.ascontiguousarray(out[:, 3:])
+    for k, v in (_skip_rows(row, shape) if n_hops is None else _hop_skip_rows(row, shape, n_hops)).items():
         res["skip_status" if k == "status" else k] = v
     return res
 
@@ -1043,6 +1077,76 @@ def muf_spherical_gradient(target_x_km, Ne, Babs, bpsi, z_grid, x_grid, mode, f_
                 _controls(s_max_km, rtol, atol, max_step_km, z_ground_km, r_max_km, phi_min, phi_max, renormalize_every),
                 scan_elevation_deg, elev_tol_deg, max_iter, R_E, edge_order,
                 (float(fill_value_n), float(fill_value_grad), float(fill_value_mup)), device, _slab_links)
+
+
+def skip_distance_hops_cartesian_gradient(field, n_hops, x0_km=0.0, z0_km=0.0, s_max_km=5000.0, *, scan_elevation_deg=None,
+                                          elev_tol_deg=1e-3, max_iter=64, rtol=1e-7, atol=1e-9, max_step_km=None,
+                                          z_ground_km=0.0, z_min_km=-1.0, z_max_km=1000.0, x_min_km=-1e6, x_max_km=1e6,
+                                          renormalize_every=50):
+    """Skip distance of the ``n_hops``-hop mode (2F, 3F ..) through a tilted ionosphere: where that mode starts to be
+    heard.  ``skip_distance_cartesian_gradient`` with the landing coordinate of a ray replaced by
+    ``total_ground_range_km`` of ``trace_hops_cartesian_gradient``'s chain - NaN unless all ``n_hops`` (1 .. 16) hops
+    land - in one call (``prhf_gradient_hop_skip_f64``); scan, the first index of the minimum,
+    refinement, statuses and keyword arguments are that call's.  D(e) of a chain jumps between layers and is not
+    unimodal: what is found is the minimum next to the first scan node that attains the least landing coordinate.
+
+    Returns a dict of ``(F, T)`` arrays ``skip_km``, ``elevation_deg``, ``status``, ``scan_index``, ``bracket_deg``,
+    ``n_evals`` (chains, not hops), ``n_landed`` and the three totals, and with shape ``(F, T, H)`` the per-hop keys of
+    ``trace_hops_cartesian_gradient`` for the chain at ``elevation_deg``, bit for bit what that call returns there (the
+    tracer's own ``status`` is ``ray_status`` here); ``skip_km`` has the bits of ``total_ground_range_km``.  ``status``
+    -1: no chain of the scan lands - NaN, the hops unused (``ray_status`` -1, the counts 0)."""
+    return _skip(field, "cartesian", "skip_distance_hops_cartesian_gradient", x0_km, z0_km,
+                 _controls(s_max_km, rtol, atol, max_step_km, z_ground_km, z_max_km, x_min_km, x_max_km, renormalize_every),
+                 scan_elevation_deg, elev_tol_deg, max_iter, None, n_hops=n_hops)
+
+
+def skip_distance_hops_spherical_gradient(field, n_hops, x0_km=0.0, z0_km=0.0, s_max_km=6000.0, *, R_E=None,
+                                          scan_elevation_deg=None, elev_tol_deg=1e-3, max_iter=64, z_ground_km=0.0,
+                                          r_max_km=None, phi_min=-np.pi, phi_max=np.pi, rtol=1e-7, atol=1e-9,
+                                          max_step_km=2.0, renormalize_every=50):
+    """The same over a spherical Earth: ``skip_distance_spherical_gradient``'s arguments,
+    ``trace_hops_spherical_gradient``'s chains."""
+    _need_geometry(field, "spherical", "skip_distance_hops_spherical_gradient")
+    R_E, r_max_km = _spherical_defaults(R_E, field.R_E, r_max_km)
+    return _skip(field, "spherical", "skip_distance_hops_spherical_gradient", x0_km, z0_km,
+                 _controls(s_max_km, rtol, atol, max_step_km, z_ground_km, r_max_km, phi_min, phi_max, renormalize_every),
+                 scan_elevation_deg, elev_tol_deg, max_iter, R_E, n_hops=n_hops)
+
+
+def muf_hops_cartesian_gradient(target_x_km, n_hops, Ne, Babs, bpsi, z_grid, x_grid, mode, f_lo_hz, f_hi_hz, x0_km=0.0,
+                                z0_km=0.0, s_max_km=5000.0, *, n_bisect=40, scan_elevation_deg=None, elev_tol_deg=1e-3,
+                                max_iter=64, edge_order=2, fill_value_n=np.nan, fill_value_grad=0.0, fill_value_mup=np.nan,
+                                rtol=1e-7, atol=1e-9, max_step_km=None, z_ground_km=0.0, z_min_km=-1.0, z_max_km=1000.0,
+                                x_min_km=-1e6, x_max_km=1e6, renormalize_every=50, device=None, _slab_links=None):
+    """MUF of the ``n_hops``-hop mode of links through a tilted ionosphere - the 2F or 3F MUF of a link that no one-hop
+    ray reaches, which ``muf_cartesian_gradient`` can only answer with status 2: that call with S(f) the ``skip_km`` of
+    ``skip_distance_hops_cartesian_gradient`` on ``refractive_field_device``'s field at f (``prhf_gradient_hop_muf_f64``,
+    DESIGN.md section 4.13).  Arguments, statuses, the bisection and the slabs under 1 GiB are ``muf_cartesian_gradient``'s.
+
+    Returns a dict of arrays of the links' broadcast shape: ``muf_hz``, ``f_above_hz``, ``status`` and the keys of
+    ``skip_distance_hops_cartesian_gradient`` for the field at ``muf_hz`` (per-hop keys with a trailing hop axis), bit
+    for bit what that call returns on ``refractive_field_device([muf_hz], ...)`` (its ``status`` is ``skip_status``
+    here)."""
+    return _muf("cartesian", target_x_km, x0_km, z0_km, Ne, Babs, bpsi, z_grid, x_grid, mode, f_lo_hz, f_hi_hz, n_bisect,
+                _controls(s_max_km, rtol, atol, max_step_km, z_ground_km, z_max_km, x_min_km, x_max_km, renormalize_every),
+                scan_elevation_deg, elev_tol_deg, max_iter, None, edge_order,
+                (float(fill_value_n), float(fill_value_grad), float(fill_value_mup)), device, _slab_links, n_hops=n_hops)
+
+
+def muf_hops_spherical_gradient(target_x_km, n_hops, Ne, Babs, bpsi, z_grid, x_grid, mode, f_lo_hz, f_hi_hz, x0_km=0.0,
+                                z0_km=0.0, s_max_km=6000.0, *, R_E=None, n_bisect=40, scan_elevation_deg=None,
+                                elev_tol_deg=1e-3, max_iter=64, edge_order=2, fill_value_n=np.nan, fill_value_grad=0.0,
+                                fill_value_mup=np.nan, z_ground_km=0.0, r_max_km=None, phi_min=-np.pi, phi_max=np.pi,
+                                rtol=1e-7, atol=1e-9, max_step_km=2.0, renormalize_every=50, device=None, _slab_links=None):
+    """The same over a spherical Earth of radius ``R_E`` (default ``constants()[2]``): ``muf_spherical_gradient``'s
+    arguments, ``skip_distance_hops_spherical_gradient``'s S(f)."""
+    R_E = float(constants()[2] if R_E is None else R_E)
+    if r_max_km is None:
+        r_max_km = R_E + 1200.0                                             # :2226-2227
+    return _muf("spherical", target_x_km, x0_km, z0_km, Ne, Babs, bpsi, z_grid, x_grid, mode, f_lo_hz, f_hi_hz, n_bisect,
+                _controls(s_max_km, rtol, atol, max_step_km, z_ground_km, r_max_km, phi_min, phi_max, renormalize_every),
+                scan_elevation_deg, elev_tol_deg, max_iter, R_E, edge_order,
+                (float(fill_value_n), float(fill_value_grad), float(fill_value_mup)), device, _slab_links, n_hops=n_hops)
 
 
 def trace_ray_spherical_gradient(n_and_grad_rphi, mup_func, x0_km, z0_km, elevation_deg, s_max_km=6000.0, *, R_E=None,

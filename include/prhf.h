@@ -141,16 +141,21 @@ int prhf_ctx_set_math(prhf_ctx* ctx, int level);
  *                        segment too close to X + Y = 1 keeps the sum of before; "strided_top" = 0 switches both off)
  *   "panel_lower"        0: the segments below the top three are summed as "strided_lower" says, the launch of before this
  *                        option bit for bit (1: where "strided_lower" applies, the region below the top three segments is
- *                        cut at every multiple of 128 points and at every segment's first point; a piece of more than 8
- *                        points is summed from eight nodes at real-valued indices - Gauss-Legendre abscissae, weights
- *                        that make the rule exact for the discrete sum of polynomials of degree 7 - within 1e-12 of
- *                        the full sum; a pair with such a piece too close to X + Y = 1 keeps the sum of before)
- *   "panel_nodes"        8: every piece of the panel sum takes eight lanes, the launch of before this option bit for bit
- *                        (4: a piece of at most four points, or one whose segment's continuation reaches X + Y = 1 at
- *                        least 16 piece lengths from its centre, takes four lanes - its own points, or the four nodes of
- *                        the Gauss rule of the counting measure on its points, exact for the same polynomials; every
- *                        other piece takes eight lanes as before.  The same pairs take the rule and the same pairs fall
- *                        back; values stay within 1e-12.  Values between 4 and 8 count as 8)
+ *                        cut at every segment's first point, and a segment's run of n points into ceil(n / 128) pieces
+ *                        of equal length; a piece is summed from nodes at real-valued indices ("panel_nodes") with
+ *                        weights that make the rule exact for the discrete sum of polynomials of degree 7 - within 1e-12
+ *                        of the full sum; a pair with a piece of more than 8 points too close to X + Y = 1 keeps the sum
+ *                        of before)
+ *   "panel_nodes"        8: every piece of the panel sum takes eight lanes - its own points up to eight, else eight
+ *                        Gauss-Legendre nodes.  Since the region is cut at segments' first points alone, and a segment's
+ *                        run into ceil(n / 128) equal pieces, this setting no longer gives the bits of the launch before
+ *                        the option existed
+ *                        (4: a piece takes four lanes - its own points up to four, else the four nodes of the Gauss rule
+ *                        of the counting measure on its points, exact for the same polynomials; the pieces of a run
+ *                        whose segment's continuation reaches X + Y = 1 within 16 piece lengths of it are halved until
+ *                        it does not, or until they hold at most four points.  Both settings use the same cuts and the
+ *                        same guard: the same pairs take the rule and the same pairs fall back; with 4 values stay
+ *                        within 1e-12 of "panel_lower" = 0.  Values between 4 and 8 count as 8)
  *   "strided_grade"      0: the strided stretch of each of the top three segments takes every eighth point throughout, the
  *                        launch of before this option bit for bit (1: the stretch is cut into zones by the distance to
  *                        the index where the segment's continuation reaches X + Y = 1 - every 32nd point at least 1024

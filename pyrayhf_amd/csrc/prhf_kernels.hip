@@ -163,11 +163,11 @@ __device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirs
 constexpr int kStridedLowerBit = 1 << 30;
 // ... and bit 29: where they do, the panel sum comes first (SegDev::panel_lower)
 constexpr int kPanelLowerBit = 1 << 29;
-// ... and bit 28: pieces far from X + Y = 1 are summed from four nodes on four lanes (SegDev::panel_nodes == 4)
+// ... and bit 28: every entry of the panel sum takes four nodes on four lanes (SegDev::panel_nodes == 4)
 constexpr int kPanelNodes4Bit = 1 << 28;
 // ... and bit 27: a strided stretch of the top three segments is cut into zones of stride 32, 16 and 8 (SegDev::strided_grade)
 constexpr int kStridedGradeBit = 1 << 27;
-// a piece takes four nodes where X + Y = 1 lies at least kPanelFar n + 2 indices from its centre
+// a part of a panel piece takes four nodes where X + Y = 1 lies at least kPanelFar n + 2 indices from its centre
 constexpr int kPanelFar = 16;
 // what the main loop reports about the panel sum in the bits above kPanelStateShift of LeanResult::first (a grid point's
 // index stays below 2^27): 1 the pair's lower segments took it, 2 the pair was eligible and kept the sum of before
@@ -1667,22 +1667,23 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
         auto x_of = [&](int j) { return index_of((double)j * rkj); };
         // The panel sum (option panel_lower): the region [S_P, E_P), multiples of PRHF_PANEL_BLOCK, from the
         // lowest segment that holds PRHF_PANEL_MIN_SEGMENT points up to where the top three segments' own loops begin, is
-        // cut at every multiple of the block and at every segment's first point.  A piece [p, p + n) lies in one segment,
-        // where the summand is an analytic function of the real-valued index x: m(x) = 1 + c0 - e(x), w = c1 e(x),
-        // e(x) = (1 - m_i + c0) exp(-10 (x - i) / (N - 1)) from the table entry i next to x.  Eight lanes sum a piece: its
-        // own points if it holds at most eight, else the Gauss-Legendre abscissae of order 8 over [p, p + n - 1] with the
-        // weights of kPanelPairs, which make the rule the discrete sum of every polynomial of degree 7.  The nodes go
-        // through the indexed step like any point.  One lane per piece makes the list, 63 pieces at a time: the first
-        // n_blk pieces begin at a multiple of the block and end at the next one or at the next segment's first point, the
-        // others begin at a segment's first point inside the region - found like the top segments' by the closed form and
-        // four table entries around it, with a grid point's segment the indexed step's own (int)(m kj) - and end at the
-        // next segment's (the next lane's) or at the next multiple.  Guard, per piece of more than eight points: the
-        // index where the segment's continuation reaches X + Y = 1 lies at least max(32, 4 n) from the piece's centre,
-        // and 1 - X - Y >= 1e-6 at both levels of the segment; one piece that fails, or one guess that does not bracket,
-        // leaves the whole pair to the sums below.  With option panel_nodes = 4 a piece far from that index, or of at most
-        // four points, takes four lanes instead - its own points, or the four nodes of the Gauss rule of the counting
-        // measure on its n points (kPanel4Pairs), exact for the same polynomials - sixteen pieces per wave-iteration; the
-        // guard and with it the pairs that fall back stay the same.  Everything here is a function of the pair alone.
+        // cut at every segment's first point and nowhere else: a run [p, p + n) is the part of one segment inside the
+        // region.  A run is cut into k = ceil(n / PRHF_PANEL_BLOCK) base pieces of L = ceil(n / k) points, the last one
+        // shorter.  Inside one segment the summand is an analytic function of the real-valued index x: m(x) = 1 + c0 -
+        // e(x), w = c1 e(x), e(x) = (1 - m_i + c0) exp(-10 (x - i) / (N - 1)) from the table entry i next to x.  Four lanes
+        // sum an entry (option panel_nodes = 4, the default): its own points if it holds at most four, else the four nodes
+        // of the Gauss rule of the counting measure on its points (kPanel4Pairs), which is the discrete sum of every
+        // polynomial of degree 7 - sixteen entries per wave-iteration.  An entry is a base piece, or one of the 2^s balanced
+        // parts of a base piece whose run comes too near to the index where the segment's continuation reaches X + Y = 1
+        // (the level s below).  The nodes go through the indexed step like any point.  One lane per run makes the list,
+        // 63 runs at a time: a run begins at its segment's first point - found like the top segments' by the closed form
+        // and four table entries around it, with a grid point's segment the indexed step's own (int)(m kj) - and ends at
+        // the next segment's (the next lane's).  Guard, per base piece of more than eight points: the index where the
+        // segment's continuation reaches X + Y = 1 lies at least max(32, 4 n) from the piece's centre, and 1 - X - Y >=
+        // 1e-6 at both levels of the segment; one piece that fails, or one guess that does not bracket, leaves the whole
+        // pair to the sums below.  With option panel_nodes = 8 a base piece is an entry of eight lanes - its own points up
+        // to eight, else the eight Gauss-Legendre nodes of kPanelPairs - on the same cuts and the same guard, so the same
+        // pairs fall back.  Everything here is a function of the pair alone.
         if (lower && panel_req && end < 65536) {
             bool panel_ok = false;
             int S_P = 0;
@@ -1724,30 +1725,34 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
                 __builtin_memcpy(&gs, &vs, sizeof gs);
                 __builtin_memcpy(&ge, &ve, sizeof ge);
                 const int j_s = uniform((int)(gs.x * kj)), j_e = uniform((int)(ge.x * kj));
-                const int n_blk = (E_P - S_P) >> kLogB, total = n_blk + (j_e - j_s);
+                typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
                 const double s10 = uniform(-10.0 / n1);
                 const double r2 = 1.4142135623730951;
                 bool fail = false;
+                // (the loop function is at the end of its scalar registers: the segment of the list's first run and the
+                //  runs left are all the loop carries)
+                int j_0 = j_s, left = j_e - j_s + 1;
 #pragma unroll 1
-                for (int s0 = 0; s0 < total && !fail; s0 += 63) {
-                    // lane l: piece s0 + l (lane 63 only finds the first point that ends lane 62's piece)
-                    const int s = s0 + lane;
-                    const bool live = s < total, is_blk = s < n_blk;
-                    const int bs = S_P + (min(s, n_blk - 1) << kLogB);
-                    typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-                    const u32x2 vb = __builtin_amdgcn_raw_buffer_load_b64(rsrc, (unsigned)bs * (unsigned)sizeof(double2), 0, 0);
-                    double mb;
-                    __builtin_memcpy(&mb, &vb, sizeof mb);
-                    const int j_a = (int)(mb * kj);
-                    const int jq = is_blk ? j_a + 1 : (live ? j_s + 1 + (s - n_blk) : j_s + 1);
+                while (left > 0) {
+                    // lane l: the run in segment j_0 + l, from the segment's first point (the region's for the lowest
+                    // run) to the next lane's (lane 63 only finds the first point that ends lane 62's run)
+                    const bool live = lane < left;
+                    const int j_g = live ? j_0 + lane : j_0;
                     bool ok;
-                    const int fq = first_point(jq, ok);
-                    const int F = live ? fq : (1 << 20);
-                    const int F_next = __shfl_down(F, 1);
-                    const int p = is_blk ? bs : F;
-                    const int e = is_blk ? min(bs + B, F) : min(F_next, (F & ~(B - 1)) + B);
-                    int n = live && lane < 63 && (is_blk || (F & (B - 1)) != 0) ? max(e - p, 0) : 0;
-                    const int j_g = is_blk ? j_a : jq;
+                    const int fq = first_point(j_g, ok);
+                    const int p = live ? max(fq, S_P) : E_P;
+                    const int p_next = __shfl_down(p, 1);
+                    const int n = live && lane < 63 ? max(min(p_next, E_P) - p, 0) : 0;
+                    // k base pieces of L = ceil(n / k) points, the last one shorter (the quotient from the single-
+                    // precision reciprocal, set right by two products: n < 2^16, k <= 2^9)
+                    const int k = (n + B - 1) >> kLogB;
+                    int L = n;
+                    if (__any(k > 1)) {
+                        int q = (int)((float)n * __builtin_amdgcn_rcpf((float)max(k, 1)));
+                        q += q * k < n ? 1 : 0;
+                        q -= (q - 1) * k >= n ? 1 : 0;
+                        L = k > 1 ? q : n;
+                    }
                     // guard, from the segment's node: 1 - X - Y = gap - sl m on its continuation (strided_run)
                     const unsigned nd = __umul24((unsigned)j_g, (unsigned)sizeof(Node));
                     const double o = nodes_v.f64(nd + 8), den = nodes_v.f64(nd + 16), sden = nodes_v.f64(nd + 24),
@@ -1756,66 +1761,111 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
                     const double gap = 1.0 - cX * (den + sden * o) - r2 * (cYs * (bf + sb * o));
                     const double m_hi = (double)(j_g + 1) * rkj;
                     const double g_lo = gap - sl * ((double)j_g * rkj), g_hi = gap - sl * m_hi;
-                    const bool big = n > 8;
-                    bool clear = g_lo >= 1e-6 && g_hi >= 1e-6;
+                    const bool big = n > 8;                // (a run of several pieces has pieces of more than 64 points)
+                    const bool levels = g_lo >= 1e-6 && g_hi >= 1e-6;
+                    bool clear = levels;
                     // (nearly always the continuation reaches X + Y = 1 far above the segment: the index grows by at least
                     //  (N - 1) / (10 a_j+1) per unit of m up there, so g_hi / sl of m is more than 4 B + 2 indices - no
                     //  logarithm, no division)
                     const bool far = sl > 0.0 && (n1 * 0.1) * g_hi >= (double)(4 * B + 2) * (sl * ((1.0 - m_hi) + c0));
-                    if (__any(big && clear && !far)) {
-                        if (__builtin_fabs(sl) > 1e-300) {
-                            const double i_sing = index_of(gap / sl);
-                            const double c = (double)p + 0.5 * (double)(n - 1);
-                            clear = clear && __builtin_fabs(i_sing - c) >= fmax(32.0, 4.0 * (double)n);
+                    const int k_chk = big && clear && !far && __builtin_fabs(sl) > 1e-300 ? k : 0;
+                    if (__any(k_chk > 0)) {
+                        const double i_sing = index_of(gap / sl);
+                        for (int i = 0; __ballot(i < k_chk) != 0ull; ++i) {
+                            const int n_i = min(L, n - i * L);
+                            const double c = (double)(p + i * L) + 0.5 * (double)(n_i - 1);
+                            if (i < k_chk && n_i > 8)
+                                clear = clear && __builtin_fabs(i_sing - c) >= fmax(32.0, 4.0 * (double)n_i);
                         }
                     }
-                    fail = __ballot((live && !ok) || (big && !clear)) != 0ull;
-                    if (fail) break;
-                    unsigned word = n > 0 ? (unsigned)p | ((unsigned)n << 16) : 0u;
-                    // the list the evaluation reads: n4 four-lane pieces from lane 0 up, n8 eight-lane pieces from lane
-                    // flip down (option panel_nodes = 8: every piece takes eight lanes, the list is the lanes' own)
-                    int n4 = 0, n8 = min(63, total - s0);
-                    unsigned flip = 0u;
+                    // Parts (option panel_nodes = 4): every base piece of the run is halved lvl times, lvl the least
+                    // number at which the run's longest part - n_s = ceil(L / 2^lvl) points - holds at most four points or
+                    // has X + Y = 1 on the segment's continuation at least kPanelFar n_s + 2 indices from its centre,
+                    // taken where the run comes nearest to it: the last part's where sl >= 0, the first part's where
+                    // sl < 0.  The stretch has 1 - m_i + c0 = (1 + c0) exp(-10 i / (N - 1)), so 1 - m_sing + c0 is set
+                    // against that at the index so far from the centre; multiplied by sl both sides read the same (no
+                    // logarithm, no division; the two spare indices cover the single-precision exponential).  Nearly
+                    // every run passes at lvl = 0: one trip.
+                    int lvl = 0;
                     if (nodes4_req) {
-                        // Four lanes: a piece of at most four points (its own), or one whose segment's continuation
-                        // reaches X + Y = 1 at least kPanelFar n + 2 indices from its centre - above it where sl > 0,
-                        // below it where sl < 0.  The stretch has 1 - m_i + c0 = (1 + c0) exp(-10 i / (N - 1)), so
-                        // 1 - m_sing + c0 is set against that at the index so far from the centre; multiplied by sl
-                        // both sides read the same (no logarithm, no division; the two spare indices cover the
-                        // single-precision exponential).  Everything else takes eight lanes as before.
-                        const double kk = (double)(kPanelFar * n + 2);
-                        const double i_far = ((double)p + 0.5 * (double)(n - 1)) + (sl < 0.0 ? -kk : kk);
-                        const double e_far = (double)__builtin_amdgcn_exp2f((float)(i_far * (s10 * 1.4426950408889634)));
-                        const bool c4 = n > 0 && (n <= 4 || (g_lo >= 1e-6 && g_hi >= 1e-6 &&
-                                                            (1.0 + c0) * sl - gap <= sl * ((1.0 + c0) * e_far)));
-                        const unsigned long long b4 = __ballot(c4), b8 = __ballot(n > 0 && !c4);
-                        const int r4 = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(b4 >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b4, 0u));
-                        const int r8 = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(b8 >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b8, 0u));
-                        n4 = __builtin_popcountll(b4);
-                        n8 = __builtin_popcountll(b8);
-                        // (a permutation of the 64 lanes: the lanes without a piece fill the middle with their zeros)
-                        const int dest = c4 ? r4 : (n > 0 ? 63 - r8 : n4 + (lane - r4 - r8));
-                        word = (unsigned)__builtin_amdgcn_ds_permute(dest << 2, (int)word);
-                        flip = 63u;
+                        bool open = n > 0;
+                        for (int t = 0;; ++t) {
+                            if (open) {
+                                const int n_s = (L + (1 << t) - 1) >> t;
+                                const double kk = (double)(kPanelFar * n_s + 2);
+                                const double i_far = sl < 0.0 ? ((double)p + 0.5 * (double)((L >> t) - 1)) - kk
+                                                              : ((double)(p + n - 1) - 0.5 * (double)(n_s - 1)) + kk;
+                                const double e_far = (double)__builtin_amdgcn_exp2f((float)(i_far * (s10 * 1.4426950408889634)));
+                                lvl = t;
+                                open = !(n_s <= 4 || (levels && (1.0 + c0) * sl - gap <= sl * ((1.0 + c0) * e_far)));
+                            }
+                            if (__ballot(open) == 0ull) break;
+                        }
                     }
-                    // (one copy of the evaluation loop for both classes: lanes per piece and table by scalar selects)
+                    const int cnt = n > 0 ? k << lvl : 0;      // the run's entries
+                    fail = __ballot((live && !ok) || (big && !clear) || cnt > 128) != 0ull;
+                    if (fail) break;
+                    // The list the evaluation reads: entry e in lane e & 63 of lst_a (e < 64) or lst_b, up to 128 entries
+                    // of as many consecutive runs as fit.  Nearly always every run is its own single entry and the list
+                    // is the lanes' own words; else (a scalar branch) an entry finds its run by bisection in the running
+                    // sum of the counts and cuts its part from the run's p, n, L and lvl.
+                    unsigned lst_a = n > 0 ? (unsigned)p | ((unsigned)n << 16) : 0u, lst_b = 0u;
+                    int total = min(63, left), n_take = total;
+                    if (__ballot(cnt != (live && lane < 63 ? 1 : 0)) != 0ull) {
+                        int incl = cnt;
+                        incl += __builtin_amdgcn_update_dpp(0, incl, 0x111, 0xf, 0xf, false);    // row_shr:1
+                        incl += __builtin_amdgcn_update_dpp(0, incl, 0x112, 0xf, 0xf, false);    // row_shr:2
+                        incl += __builtin_amdgcn_update_dpp(0, incl, 0x114, 0xf, 0xf, false);    // row_shr:4
+                        incl += __builtin_amdgcn_update_dpp(0, incl, 0x118, 0xf, 0xf, false);    // row_shr:8
+                        incl += __builtin_amdgcn_update_dpp(0, incl, 0x142, 0xa, 0xf, false);    // row_bcast:15 into rows 1 and 3
+                        incl += __builtin_amdgcn_update_dpp(0, incl, 0x143, 0xc, 0xf, false);    // row_bcast:31 into rows 2 and 3
+                        // (lane 0 is a live run of at most 128 entries: n_take >= 1)
+                        n_take = __builtin_popcountll(__ballot(live && lane < 63 && incl <= 128));
+                        total = __builtin_amdgcn_readlane(incl, n_take - 1);
+                        const unsigned pk = lst_a;
+                        const unsigned aux = (unsigned)(incl - cnt) | ((unsigned)L << 8) | ((unsigned)lvl << 16);
 #pragma unroll 1
-                    for (int cls = nodes4_req ? 0 : 1; cls < 2; ++cls) {
-                    const int sh = cls == 0 ? 2 : 3, cnt = cls == 0 ? n4 : n8;
-                    const unsigned fl = cls == 0 ? 0u : flip;
-                    const char* tab = reinterpret_cast<const char*>(cls == 0 ? kPanel4Pairs : kPanelPairs);
-                    // (the class' own words, zeros elsewhere: the last wave-iteration may reach past them)
-                    const unsigned lst = ((unsigned)lane ^ fl) < (unsigned)cnt ? word : 0u;
+                        for (int half = 0; half < (total > 64 ? 2 : 1); ++half) {
+                            const int e = 64 * half + lane;
+                            int at = 0;                    // the lanes whose running sum is at most e: the entry's run
+#pragma unroll
+                            for (int step = 32; step > 0; step >>= 1)
+                                at += __builtin_amdgcn_ds_bpermute((at + step - 1) << 2, incl) <= e ? step : 0;
+                            const unsigned rp = (unsigned)__builtin_amdgcn_ds_bpermute(at << 2, (int)pk);
+                            const unsigned ra = (unsigned)__builtin_amdgcn_ds_bpermute(at << 2, (int)aux);
+                            const int r_n = (int)(rp >> 16), r_L = (int)((ra >> 8) & 255u), r_s = (int)(ra >> 16);
+                            const int q = e - (int)(ra & 255u);
+                            const int i = q >> r_s, t = q & ((1 << r_s) - 1);
+                            const int n_b = max(min(r_L, r_n - i * r_L), 0);
+                            const int a = (t * n_b) >> r_s, b = ((t + 1) * n_b) >> r_s;
+                            const unsigned w = e < total ? ((rp & 0xffffu) + (unsigned)(i * r_L + a)) | ((unsigned)(b - a) << 16) : 0u;
+                            if (half == 0) lst_a = w; else lst_b = w;
+                        }
+                    }
+                    j_0 += n_take;
+                    left -= n_take;
+                    // (lanes per entry and the table by scalar selects: one copy of the evaluation loop for both settings;
+                    //  taken from the option's bit here, so that they do not wait in registers while the list is made)
+                    int four = nodes4_req ? 1 : 0;
+                    asm volatile("" : "+s"(four));
+                    const int sh = four ? 2 : 3;
+                    const char* tab = reinterpret_cast<const char*>(four ? kPanel4Pairs : kPanelPairs);
                     const unsigned lk16 = (unsigned)(lane & ((1 << sh) - 1)) << 4;
-                    int src = (int)((((unsigned)lane >> sh) ^ fl) << 2);
-                    const int step = fl != 0u ? -(256 >> sh) : 256 >> sh;
+                    const int src0 = (lane >> sh) << 2;
+                    int src = src0;
 #pragma unroll 1
-                    for (int k0 = 0; k0 < cnt; k0 += 64 >> sh) {
-                        // sixteen pieces of four lanes, or eight pieces of eight lanes
-                        const unsigned w = (unsigned)__builtin_amdgcn_ds_bpermute(src, (int)lst);
-                        src += step;
+                    for (int k0 = 0; k0 < total; k0 += 64 >> sh) {
+                        // sixteen entries of four lanes, or eight entries of eight lanes; the second half of a long list
+                        // behind a scalar branch
+                        if (k0 == 64) {
+                            lst_a = lst_b;
+                            src = src0;
+                            asm volatile("" : "+v"(lst_a), "+v"(src));
+                        }
+                        const unsigned w = (unsigned)__builtin_amdgcn_ds_bpermute(src, (int)lst_a);
+                        src += 256 >> sh;
                         const int pp = (int)(w & 0xffffu);
-                        // the node's offset from the piece's first point, its weight
+                        // the node's offset from the entry's first point, its weight
                         const double2 ow = *reinterpret_cast<const double2*>(tab + (((w >> 16) << (sh + 4)) | lk16));
                         const double xk = (double)pp + ow.x;
                         const double xr = __builtin_rint(xk);
@@ -1829,7 +1879,6 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
                         gm.x = (1.0 + c0) - ek;
                         gm.y = ow.y * (sc1 * ek);
                         accm = lean_step<MODE, false, POLY, HINT, G>(gm, span, a0v, kj, cX, hcY2, accm, wc, viol, nodes_v, cur);
-                    }
                     }
                 }
                 panel_ok = !fail;
@@ -1911,6 +1960,9 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
                 run_indexed(pass == 0 ? S_R : j_whole); // one by one up to S_R, then the strided table's entries
             }
             tab_off = 0;
+            // (a pair whose region the panel sum has taken has no boundary pass: none of its set-up either)
+            const int n_items = n_R < 0 ? 0 : 32 * n_R + rest;
+            if (n_items > 0) {
             // coefficients of the points b-3+p around a boundary with a - b = 16 and 24, and of the two ends of R
             // (a-3 .. a+3 around S_R, then b-3 .. b+7 around E_R - 8): per lane, once per pair
             const int p = lane & 31;
@@ -1927,7 +1979,6 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
             const double c16 = around(p, 19), c24 = around(p, 27);
             const double c_ends = p < 3 ? -mag(3 - p) : (p == 3 ? -3.5 : (p < 7 ? mag(p - 3) : (p < 18 ? around(p - 7, 64) : 0.0)));
             const double c0 = 1.0 / 22025.465794806718;
-            const int n_items = n_R < 0 ? 0 : 32 * n_R + rest;
             for (int t0 = 0; t0 < n_items; t0 += 64) {
                 const int grp = (t0 >> 5) + (lane >> 5);
                 int idx = S_R;
@@ -1949,6 +2000,7 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
                 __builtin_memcpy(&gm, &vm, sizeof gm);
                 gm.y = coef * (sc1 * ((1.0 - gm.x) + c0));
                 accm = lean_step<MODE, false, POLY, HINT, G>(gm, span, a0v, kj, cX, hcY2, accm, wc, viol, nodes_v, cur);
+            }
             }
             first = E_R;
             g0 = grid_at(first);

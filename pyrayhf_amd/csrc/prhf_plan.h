@@ -85,14 +85,16 @@ struct Knobs {
                                        // and one pass over the segment boundaries (0: the launch of strided_top alone,
                                        // bit for bit; strided_top = 0 switches both off)
     double panel_lower = 1;            // ... and where strided_lower applies, the region below the top three segments is cut
-                                       // into pieces of at most PRHF_PANEL_BLOCK points inside one segment, each summed from
-                                       // eight nodes at real-valued indices (a pair with a piece too close to
-                                       // X + Y = 1 keeps strided_lower's sum; 0: the launch of before, bit for bit)
-    double panel_nodes = 4;            // ... and a piece whose segment's continuation reaches X + Y = 1 at least 16 piece
-                                       // lengths from its centre, or that holds at most four points, is summed from the four
-                                       // nodes of the Gauss rule of the counting measure on four lanes, sixteen pieces per
-                                       // wave-iteration (8, or anything but 4: eight lanes for every piece,
-                                       // the launch of before, bit for bit)
+                                       // at every segment's first point, a segment's run into pieces of at most
+                                       // PRHF_PANEL_BLOCK points, each summed from nodes at real-valued indices (DESIGN.md 4.1;
+                                       // a pair with a piece too close to X + Y = 1 keeps strided_lower's sum; 0: the launch
+                                       // of before, bit for bit)
+    double panel_nodes = 4;            // ... every piece from the four nodes of the Gauss rule of the counting measure on four
+                                       // lanes, sixteen per wave-iteration; the pieces of a run whose segment's continuation
+                                       // reaches X + Y = 1 within 16 piece lengths are halved until it does not, or until
+                                       // they hold at most four points (8, or anything but 4: no halving,
+                                       // eight Gauss-Legendre nodes on eight lanes for every piece - the same cuts and the
+                                       // same guard, not the bits of the launch before the cuts changed)
     double strided_grade = 1;          // ... and the strided stretch of each of the top three segments is cut into zones:
                                        // every 32nd point at least 1024 indices below the index where the segment's
                                        // continuation reaches X + Y = 1 and where 1 - X - Y >= 1.6e-4, every 16th at

@@ -232,6 +232,57 @@ int prhf_vfo_worklist_f64(prhf_ctx* ctx,
                           double* vh_out, uint32_t flags);
 
 /*
+ * The derivative of prhf_vfo_batch_f64's virtual heights with respect to the density column: the dense Jacobian
+ * jac_out[p, f, k] = d vh[p, f] / d den[p, k], or its product with an upstream gradient,
+ * grad_den_out[p, k] = sum_f grad_vh[p, f] * d vh[p, f] / d den[p, k]  (what reverse-mode differentiation of a loss
+ * needs; H^T of data assimilation).  The function differentiated is the reference's discrete sum exactly
+ * (library.py:324-438, :259-293): vh = min(alt) + sum_i mu'(z_i) dz_i on the stretched grid z_i = alt_0 + m_i (h - alt_0)
+ * below the reflection height h, np.interp's crossing of the running maximum of X (O mode) or X + Y (X mode) minus
+ * 1e-6 km - the grid moves with h, and h with the two levels of its bracket.  Analytic (forward-mode dual numbers
+ * through the group index), not finite differences.
+ *
+ * Arguments as prhf_vfo_batch_f64.  vh_out (n_prof, n_freq) may be NULL; when given it is written by the operator's own
+ * launch and equals prhf_vfo_batch_f64's output bit for bit.  jac_out is (n_prof, n_freq, n_alt), grad_vh (n_prof, n_freq),
+ * grad_den_out (n_prof, n_alt), all row-major.  Flags: PRHF_FLAG_DEVICE_PTRS, PRHF_FLAG_ASYNC (device pointers only),
+ * PRHF_FLAG_GRID_STABLE (accepted; these kernels keep no table of the grid), PRHF_FLAG_SHARED_FIELD.
+ *
+ * Conventions:
+ *   - a pair that has no virtual height (vh NaN: the frequency is not reflected) has a row of zeros; grad_vh is not
+ *     read at such a pair, so a NaN there does no harm;
+ *   - levels at and above the density peak (k >= argmax den) get 0;
+ *   - a one-level bottomside (the peak at level 1) whose frequency escapes also has a row of zeros: the value np.interp's
+ *     one-node rule gives such a pair in the reference, mu'(level 0) * 1e-6, is not differentiated;
+ *   - grid points whose term the reference's sum skips (NaN, library.py:288) are constants;
+ *   - the unmagnetised branch (library.py:201-207, decided per profile as in prhf_vfo_batch_f64) is differentiated as
+ *     mu' = (1 - X)^(-1/2);
+ *   - the operator has kinks - a grid point exactly on a level, a tie in the density's argmax or in the running maximum,
+ *     a running maximum of exactly 1 at a level; there the result is one of the one-sided derivatives, which one is
+ *     unspecified.
+ * The arithmetic is the same in every math tier (IEEE divide and square root).  Results are reproducible bit for bit:
+ * they do not depend on scheduling, on the other profiles of the launch, or on repetition; no atomics are used.
+ * Limits: the levels below the highest density peak of the launch, plus the per-wave accumulator rows, must fit in LDS:
+ * about 1200 levels up to the peak (n_alt itself may be larger: a pre-pass then finds the peak, one synchronisation).
+ * A taller bottomside is refused with PRHF_EINVAL ("... stages at most N levels ...").  Mixed work lists are not
+ * supported.  Data errors (negative density, peak at level 0) are those of prhf_vfo_batch_f64.
+ */
+int prhf_vfo_jacobian_f64(prhf_ctx* ctx,
+                          const double* freq_mhz, int64_t n_freq,
+                          const double* den, const double* bmag, const double* bpsi,
+                          const double* alt,
+                          int64_t n_prof, int64_t n_alt,
+                          int64_t prof_stride_elems, int64_t alt_stride_elems,
+                          const double* multiplier, int32_t n_points, int32_t mode,
+                          double* vh_out, double* jac_out, uint32_t flags);
+int prhf_vfo_vjp_f64(prhf_ctx* ctx,
+                     const double* freq_mhz, int64_t n_freq,
+                     const double* den, const double* bmag, const double* bpsi,
+                     const double* alt,
+                     int64_t n_prof, int64_t n_alt,
+                     int64_t prof_stride_elems, int64_t alt_stride_elems,
+                     const double* multiplier, int32_t n_points, int32_t mode,
+                     const double* grad_vh, double* vh_out, double* grad_den_out, uint32_t flags);
+
+/*
  * Appleton-Hartree phase index mu and group index mu' on flat arrays of n elements.
  * Replaces: find_mu_mup (reference library.py:161-256); psi_deg in degrees.  As in the reference,
  * the isotropic formulas are used when max|Y| over the whole array is below 1e-12 (:201-207).

@@ -48,6 +48,14 @@ _PROTOTYPES = {
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
         ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
         ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_uint32]),
+    "prhf_vfo_jacobian_f64": (ctypes.c_int, [
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
+        ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32]),
+    "prhf_vfo_vjp_f64": (ctypes.c_int, [
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
+        ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32]),
     "prhf_vfo_worklist_f64": (ctypes.c_int, [
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
         ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
@@ -298,6 +306,18 @@ class Context:
         """All array arguments are raw addresses (ints)."""
         return self._lib.prhf_vfo_batch_f64(self._h, freq, n_freq, den, bmag, bpsi, alt, n_prof, n_alt,
                                             prof_stride, alt_stride, mult, n_points, mode, out, flags)
+
+    def vfo_jacobian(self, freq, n_freq, den, bmag, bpsi, alt, n_prof, n_alt, prof_stride, alt_stride,
+                     mult, n_points, mode, vh_out, jac_out, flags):
+        """d vh / d den, dense; ``vh_out`` may be None.  All array arguments are raw addresses (ints)."""
+        return self._lib.prhf_vfo_jacobian_f64(self._h, freq, n_freq, den, bmag, bpsi, alt, n_prof, n_alt,
+                                               prof_stride, alt_stride, mult, n_points, mode, vh_out, jac_out, flags)
+
+    def vfo_vjp(self, freq, n_freq, den, bmag, bpsi, alt, n_prof, n_alt, prof_stride, alt_stride,
+                mult, n_points, mode, grad_vh, vh_out, grad_den_out, flags):
+        """sum_f grad_vh * d vh / d den; ``vh_out`` may be None."""
+        return self._lib.prhf_vfo_vjp_f64(self._h, freq, n_freq, den, bmag, bpsi, alt, n_prof, n_alt, prof_stride,
+                                          alt_stride, mult, n_points, mode, grad_vh, vh_out, grad_den_out, flags)
 
     def vfo_worklist(self, freq, n_freq, den, bmag, bpsi, alt, n_prof, n_alt, prof_stride, alt_stride,
                      mult, mult_len, segments, out, flags):

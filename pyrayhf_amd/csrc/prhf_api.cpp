@@ -139,6 +139,7 @@ struct prhf_ctx {
     DevBuf leftover_tall_x; // ... of the X-mode short-grid launch
     DevBuf order;           // short-grid launch: its blocks by cost class (short_order_kernel)
     DevBuf tall;         // profiles of more than kMaxAlt levels: one slab of staged levels per resident workgroup
+    DevBuf vjp;          // prhf_vfo_jacobian_f64 / prhf_vfo_vjp_f64 on host buffers: their inputs and result
     const double* pairs_src = nullptr;   // PRHF_FLAG_GRID_STABLE: multiplier array the table was built from
     int64_t pairs_len = 0;
     prhf::StridedPieces pairs_pieces = {};   // ... and the strided table's pieces that were built behind it
@@ -1041,6 +1042,7 @@ int prhf_ctx_destroy(prhf_ctx* c) {
     if (c->leftover_tall_x.p) (void)hipFree(c->leftover_tall_x.p);
     if (c->order.p) (void)hipFree(c->order.p);
     if (c->tall.p) (void)hipFree(c->tall.p);
+    if (c->vjp.p) (void)hipFree(c->vjp.p);
     if (c->fields.p) (void)hipFree(c->fields.p);
     for (int g = 0; g < c->n_host_grids; ++g) {
         if (c->host_grid[g].mult.p) (void)hipFree(c->host_grid[g].mult.p);
@@ -1140,6 +1142,137 @@ int prhf_vfo_worklist_f64(prhf_ctx* ctx, const double* freq_mhz, int64_t n_freq,
                           int32_t n_segs, double* vh_out, uint32_t flags) {
     return run(ctx, freq_mhz, n_freq, den, bmag, bpsi, alt, n_prof, n_alt, prof_stride_elems, alt_stride_elems,
                multiplier, multiplier_len, segs, n_segs, vh_out, flags);
+}
+
+namespace {
+
+// prhf_vfo_jacobian_f64 / prhf_vfo_vjp_f64: check, find the levels to stage, plan (plan_vjp, prhf_plan.h), stage host
+// buffers, launch.  vh_out comes from the operator's own launch on the same arguments.
+int vjp_run(prhf_ctx* c, const double* freq, int64_t n_freq, const double* den, const double* bmag, const double* bpsi,
+            const double* alt, int64_t n_prof, int64_t n_alt, int64_t prof_stride, int64_t alt_stride, const double* mult,
+            int32_t n_points, int32_t mode, const double* grad_vh, double* vh_out, double* out, bool jacobian, uint32_t flags) {
+    if (!c) return fail(PRHF_EINVAL, "null context");
+    if (!freq || !den || !bmag || !bpsi || !alt || !mult || !out || (!jacobian && !grad_vh))
+        return fail(PRHF_EINVAL, "null array pointer");
+    if (n_freq < 1 || n_prof < 0 || n_alt < 1 || n_points < 1) return fail(PRHF_EINVAL, "bad shape");
+    if (n_alt > kMaxAltTall) return fail(PRHF_EINVAL, "n_alt %lld exceeds the limit of %lld levels", (long long)n_alt, kMaxAltTall);
+    if (n_freq > (1 << 20)) return fail(PRHF_EINVAL, "n_freq too large");
+    if (prof_stride < n_alt || (alt_stride != 0 && alt_stride < n_alt)) return fail(PRHF_EINVAL, "row stride shorter than a row");
+    if (mode != PRHF_MODE_O && mode != PRHF_MODE_X) return fail(PRHF_EINVAL, "mode must be 'O' or 'X'");
+    if (flags & ~(PRHF_FLAG_DEVICE_PTRS | PRHF_FLAG_ASYNC | PRHF_FLAG_GRID_STABLE | PRHF_FLAG_SHARED_FIELD))
+        return fail(PRHF_EINVAL, "unknown flag bits");
+    const bool dev = (flags & PRHF_FLAG_DEVICE_PTRS) != 0, shared_field = (flags & PRHF_FLAG_SHARED_FIELD) != 0;
+    if ((flags & PRHF_FLAG_ASYNC) && !dev) return fail(PRHF_EINVAL, "PRHF_FLAG_ASYNC needs device pointers");
+    if (!dev)
+        for (int64_t i = 1; i < n_points; ++i)
+            if (mult[i] < mult[i - 1])
+                return fail(PRHF_EINVAL, "multiplier[%lld] decreases: the stretched grid must be non-decreasing", (long long)i);
+    ENTER_DEVICE(c->device);
+    // Levels to stage: the whole column where LDS holds it; else up to the highest density peak of the launch
+    // (np.argmax's rule, the first NaN ranking highest: a host scan, or the peak pre-pass and one synchronisation)
+    VjpPlan pl;
+    char why[256];
+    long long levels = n_alt;
+    if (plan_vjp(n_prof, n_freq, levels, jacobian, pl, why, sizeof why) != PRHF_OK && n_prof > 0) {
+        long long max_peak = 0;
+        if (dev) {
+            HIP_TRY(hipMemsetAsync(c->d_status + kWordPeak, 0, sizeof(unsigned), c->stream));
+            HIP_TRY(prhf::launch_peak_levels(den, n_prof, n_alt, prof_stride, c->d_status + kWordPeak, c->stream));
+            unsigned peak = 0;
+            HIP_TRY(hipMemcpyAsync(&peak, c->d_status + kWordPeak, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            max_peak = peak;
+        } else {
+            for (int64_t p = 0; p < n_prof; ++p) {
+                const double* d = den + (size_t)p * prof_stride;
+                double bv = -HUGE_VAL;
+                long long bi = 0;
+                for (int64_t i = 0; i < n_alt; ++i) {
+                    const double key = (d[i] != d[i]) ? HUGE_VAL : d[i];
+                    if (key > bv) { bv = key; bi = i; }
+                }
+                max_peak = std::max(max_peak, bi);
+            }
+        }
+        levels = max_peak + 1;
+        if (plan_vjp(n_prof, n_freq, levels, jacobian, pl, why, sizeof why) != PRHF_OK) return fail(PRHF_EINVAL, "%s", why);
+    }
+    int rc;
+    if (vh_out) {
+        rc = prhf_vfo_batch_f64(c, freq, n_freq, den, bmag, bpsi, alt, n_prof, n_alt, prof_stride, alt_stride, mult, n_points,
+                                mode, vh_out, flags);
+        if (rc != PRHF_OK) return rc;
+    }
+    const size_t out_elems = jacobian ? (size_t)n_prof * (size_t)n_freq * (size_t)n_alt : (size_t)n_prof * (size_t)n_alt;
+    if (n_prof == 0) return PRHF_OK;
+    prhf::VjpArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.n_prof = n_prof; a.n_freq = n_freq; a.n_alt = n_alt; a.lds_levels = levels; a.n_points = n_points;
+    a.mode = mode == PRHF_MODE_O ? PRHF_KMODE_O : PRHF_KMODE_X;
+    a.waves = pl.waves;
+    a.status = c->h_status_dev;
+    if (dev) {
+        a.freq = freq; a.den = den; a.bmag = bmag; a.bpsi = bpsi; a.alt = alt; a.mult = mult; a.grad_vh = grad_vh; a.out = out;
+        a.prof_stride = prof_stride;
+        a.field_stride = shared_field ? 0 : prof_stride;
+        a.alt_stride = alt_stride;
+    } else {
+        const size_t field_rows = shared_field ? 1 : (size_t)n_prof, alt_rows = alt_stride ? (size_t)n_prof : 1;
+        const size_t pf = jacobian ? 0 : (size_t)n_prof * (size_t)n_freq;
+        const size_t in_elems = (size_t)n_freq + (size_t)n_points + ((size_t)n_prof + 2 * field_rows + alt_rows) * (size_t)n_alt + pf;
+        if ((rc = ensure(c, c->vjp, (in_elems + out_elems) * 8)) != PRHF_OK) return rc;
+        double* d_freq = static_cast<double*>(c->vjp.p);
+        double* d_mult = d_freq + n_freq;
+        double* d_den = d_mult + n_points;
+        double* d_bmag = d_den + (size_t)n_prof * n_alt;
+        double* d_bpsi = d_bmag + field_rows * n_alt;
+        double* d_alt = d_bpsi + field_rows * n_alt;
+        double* d_g = d_alt + alt_rows * n_alt;
+        double* d_out = d_g + pf;
+        const size_t row_bytes = (size_t)n_alt * 8;
+        auto up_rows = [&](double* dst, const double* src, size_t rows, int64_t stride) {
+            return hipMemcpy2DAsync(dst, row_bytes, src, (size_t)(rows > 1 ? stride : n_alt) * 8, row_bytes, rows,
+                                    hipMemcpyHostToDevice, c->stream);
+        };
+        HIP_TRY(hipMemcpyAsync(d_freq, freq, (size_t)n_freq * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_mult, mult, (size_t)n_points * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(up_rows(d_den, den, (size_t)n_prof, prof_stride));
+        HIP_TRY(up_rows(d_bmag, bmag, field_rows, prof_stride));
+        HIP_TRY(up_rows(d_bpsi, bpsi, field_rows, prof_stride));
+        HIP_TRY(up_rows(d_alt, alt, alt_rows, alt_stride));
+        if (pf) HIP_TRY(hipMemcpyAsync(d_g, grad_vh, pf * 8, hipMemcpyHostToDevice, c->stream));
+        a.freq = d_freq; a.den = d_den; a.bmag = d_bmag; a.bpsi = d_bpsi; a.alt = d_alt; a.mult = d_mult; a.grad_vh = d_g;
+        a.out = d_out;
+        a.prof_stride = n_alt;
+        a.field_stride = shared_field ? 0 : n_alt;
+        a.alt_stride = alt_stride ? n_alt : 0;
+    }
+    HIP_TRY(hipEventRecord(c->begin_ev(), c->stream));
+    HIP_TRY(prhf::launch_vfo_vjp(a, jacobian, pl.lds_bytes, c->stream));
+    HIP_TRY(hipEventRecord(c->pending_end_ev(), c->stream));
+    c->mark_timed();
+    c->status_pending = true;
+    if (!dev) HIP_TRY(hipMemcpyAsync(out, a.out, out_elems * 8, hipMemcpyDeviceToHost, c->stream));
+    if (flags & PRHF_FLAG_ASYNC) return PRHF_OK;
+    return prhf_sync(c);
+}
+
+}  // namespace
+
+int prhf_vfo_jacobian_f64(prhf_ctx* ctx, const double* freq_mhz, int64_t n_freq, const double* den, const double* bmag,
+                          const double* bpsi, const double* alt, int64_t n_prof, int64_t n_alt, int64_t prof_stride_elems,
+                          int64_t alt_stride_elems, const double* multiplier, int32_t n_points, int32_t mode, double* vh_out,
+                          double* jac_out, uint32_t flags) {
+    return vjp_run(ctx, freq_mhz, n_freq, den, bmag, bpsi, alt, n_prof, n_alt, prof_stride_elems, alt_stride_elems, multiplier,
+                   n_points, mode, nullptr, vh_out, jac_out, true, flags);
+}
+
+int prhf_vfo_vjp_f64(prhf_ctx* ctx, const double* freq_mhz, int64_t n_freq, const double* den, const double* bmag,
+                     const double* bpsi, const double* alt, int64_t n_prof, int64_t n_alt, int64_t prof_stride_elems,
+                     int64_t alt_stride_elems, const double* multiplier, int32_t n_points, int32_t mode, const double* grad_vh,
+                     double* vh_out, double* grad_den_out, uint32_t flags) {
+    return vjp_run(ctx, freq_mhz, n_freq, den, bmag, bpsi, alt, n_prof, n_alt, prof_stride_elems, alt_stride_elems, multiplier,
+                   n_points, mode, grad_vh, vh_out, grad_den_out, false, flags);
 }
 
 int prhf_vfo_residual_f64(prhf_ctx* ctx, const double* freq_mhz, int64_t n_freq, const double* den,

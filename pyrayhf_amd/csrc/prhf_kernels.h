@@ -281,6 +281,32 @@ struct RegridArgs {
     int n_points, mode;
 };
 hipError_t launch_regrid(const RegridArgs& a, size_t lds_bytes, hipStream_t stream);
+// Derivative of the operator with respect to the density column (prhf_vjp.inc): Jacobian rows or the vector-Jacobian
+// product, one workgroup of PRHF_VJP_THREADS per profile; all pointers are device memory.
+#define PRHF_VJP_THREADS 256
+struct VjpArgs {
+    const double* freq;       // MHz, (n_freq)
+    const double* den;
+    const double* bmag;
+    const double* bpsi;
+    const double* alt;
+    const double* mult;       // the stretched grid, (n_points)
+    const double* grad_vh;    // VJP: upstream gradient (n_prof, n_freq); not read where a pair has no value
+    double* out;              // Jacobian: (n_prof, n_freq, n_alt); VJP: (n_prof, n_alt)
+    unsigned* status;
+    long long n_prof, n_freq, n_alt;
+    long long prof_stride, field_stride, alt_stride;
+    long long lds_levels;     // levels the staged arrays hold (> every bottomside of the launch)
+    int n_points, mode;       // PRHF_KMODE_*
+    int waves;                // waves of the workgroup that take frequencies (each owns rows in LDS): 1, 2 or 4
+};
+// LDS of one workgroup: the operator's staged profile (without its candidate list), then per frequency-taking wave
+// one row of lds_levels doubles (Jacobian) or two (VJP: the current row and the wave's accumulated product)
+inline size_t vjp_lds_bytes(long long levels, int waves, bool jacobian) {
+    return (size_t)(levels + 1) * PRHF_NODE_BYTES + (size_t)levels * 16 + PRHF_HINT_BUCKETS * 2 + PRHF_RED_DOUBLES * 8 +
+           (size_t)waves * (jacobian ? 1 : 2) * (size_t)levels * 8;
+}
+hipError_t launch_vfo_vjp(const VjpArgs& a, bool jacobian, size_t lds_bytes, hipStream_t stream);
 // Stratified Snell's-law tracer (library.py:1096-1268), one wavefront per ray; device pointers.
 #define PRHF_SNELL_OUTPUTS 8   // path km, delay s, x_mid, z_mid, ground range, x_turn, z_turn, n_path
 struct SnellArgs {

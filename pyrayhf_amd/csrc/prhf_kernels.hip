@@ -3559,6 +3559,7 @@ hipError_t launch_vfo_shortx(const KArgs& a, long long grid_blocks, size_t lds_b
 #include "prhf_gradient_homing.inc"
 #include "prhf_gradient_hops.inc"
 #include "prhf_gradient_skip.inc"
+#include "prhf_vjp.inc"
 
 // Resident workgroups per CU the runtime predicts for the fused kernel (diagnostics).
 hipError_t query_occupancy(int tier, size_t lds_bytes, int* blocks_per_cu) {

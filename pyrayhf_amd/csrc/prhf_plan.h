@@ -605,6 +605,44 @@ inline int plan_launch(const LaunchShape& sh, const prhf_segment* segs, int32_t 
     return PRHF_OK;
 }
 
+// The launch of the Jacobian / VJP kernels (prhf_vjp.inc): one workgroup per profile, the staged bottomside plus one
+// (Jacobian) or two (VJP) rows of lds_levels doubles per wave that takes frequencies.  Four such waves where LDS holds
+// their rows, else two, else one - and never more than there are frequencies; a bottomside that leaves no room for one
+// wave's rows is refused (staging it in global memory, as vfo_tall_kernel does, is not implemented for the derivative).
+// The bits of a VJP depend on the number of waves (the order its frequencies are added in): it changes only where
+// the rows stop fitting, from vjp_max_levels(.., 4) levels on.
+struct VjpPlan {
+    long long blocks;
+    int threads, waves;
+    size_t lds_bytes;
+};
+inline long long vjp_max_levels(bool jacobian, int waves) {
+    long long L = 1;
+    while (prhf::vjp_lds_bytes(L + 1, waves, jacobian) <= kLdsFull) ++L;
+    return L;
+}
+inline int plan_vjp(long long n_prof, long long n_freq, long long lds_levels, bool jacobian, VjpPlan& pl, char* why,
+                    size_t why_len) {
+    std::memset(&pl, 0, sizeof pl);
+    if (n_prof < 0 || n_freq < 1 || lds_levels < 1) {
+        std::snprintf(why, why_len, "bad shape");
+        return PRHF_EINVAL;
+    }
+    int waves = PRHF_VJP_THREADS / 64;
+    while (waves > 1 && (waves / 2 >= n_freq || prhf::vjp_lds_bytes(lds_levels, waves, jacobian) > kLdsFull)) waves /= 2;
+    if (prhf::vjp_lds_bytes(lds_levels, waves, jacobian) > kLdsFull) {
+        std::snprintf(why, why_len, "the %s stages at most %lld levels up to the density peak in LDS; this launch needs %lld "
+                      "(tall bottomsides are not supported by the derivative kernels)", jacobian ? "Jacobian" : "VJP",
+                      vjp_max_levels(jacobian, 1), lds_levels);
+        return PRHF_EINVAL;
+    }
+    pl.blocks = n_prof;
+    pl.threads = PRHF_VJP_THREADS;
+    pl.waves = waves;
+    pl.lds_bytes = prhf::vjp_lds_bytes(lds_levels, waves, jacobian);
+    return PRHF_OK;
+}
+
 }  // namespace
 
 #endif  // PRHF_PLAN_H

@@ -10,6 +10,9 @@ error behaviour of ``PyRayHF.library.vertical_forward_operator`` (reference
 * inputs may be ``torch`` tensors resident on the GPU (zero-copy, result is a tensor);
 * ``vertical_forward_operator_mixed`` evaluates slices with different mode / n_points
   in one launch (BASELINE config 5).
+* ``vertical_jacobian`` / ``vertical_vjp`` give the operator's analytic derivative with respect
+  to the density column (dense rows, or the product with an upstream gradient in one launch);
+  ``pyrayhf_amd.autograd`` wraps the operator for ``torch.autograd``.
 
 The tiny host-side helpers of the path (constants, unit conversions, the stretched unit
 grid) are provided under the reference's names so that callers can switch imports.
@@ -26,7 +29,7 @@ from . import _native, logger
 __all__ = [
     "constants", "den2freq", "freq2den", "find_X", "find_Y", "smooth_nonuniform_grid",
     "vertical_to_magnetic_angle", "find_mu_mup", "vertical_forward_operator",
-    "vertical_forward_operator_mixed", "last_kernel_ms", "MATH_FAITHFUL", "MATH_FAST", "MATH_AUTO",
+    "vertical_forward_operator_mixed", "vertical_jacobian", "vertical_vjp", "last_kernel_ms", "MATH_FAITHFUL", "MATH_FAST", "MATH_AUTO",
 ]
 
 MATH_FAITHFUL = _native.MATH_FAITHFUL   # reference operation order, IEEE divide / sqrt
@@ -465,6 +468,155 @@ def vertical_forward_operator(freq, den, bmag, bpsi, alt, mode='O', n_points=200
     if any(_is_torch(x) and x.is_cuda for x in (den, bmag, bpsi)):
         return _torch_operator(freq, den, bmag, bpsi, alt, code, n_points, math, sync, out)
     return _np_operator(freq, den, bmag, bpsi, alt, code, n_points, device, math, devices)
+
+
+# ----------------------------------------------------------------------------------------
+# the operator's derivative with respect to the density column
+# ----------------------------------------------------------------------------------------
+def _np_batch(freq, den, bmag, bpsi, alt):
+    """Host inputs of a derivative call: (f, d2, b2, p2, a, single, shared, alt_stride), validated like the operator's."""
+    f = np.ascontiguousarray(np.atleast_1d(np.asarray(freq)), dtype=np.float64)
+    if f.ndim != 1:
+        raise ValueError("freq must be a scalar or 1-D")
+    d, b, p, a = _as_rows("den", den), _as_rows("bmag", bmag), _as_rows("bpsi", bpsi), _as_rows("alt", alt)
+    single = d.ndim == 1
+    shared = d.ndim == 2 and b.ndim == 1 and p.ndim == 1 and b.shape == p.shape == d.shape[1:]
+    d2 = d.reshape(1, -1) if single else d
+    b2, p2 = (b, p) if shared else (b.reshape(1, -1) if b.ndim == 1 else b, p.reshape(1, -1) if p.ndim == 1 else p)
+    if not shared and not (d2.shape == b2.shape == p2.shape):
+        raise ValueError("den, bmag and bpsi must have the same shape")
+    n_prof, n_alt = d2.shape
+    if a.shape[-1] != n_alt or (a.ndim == 2 and a.shape[0] != n_prof):
+        raise ValueError("alt must have one value per density level")
+    return f, d2, b2, p2, a, single, shared, (n_alt if a.ndim == 2 else 0)
+
+
+def _torch_batch(freq, den, bmag, bpsi, alt):
+    """The same for GPU-resident torch inputs (used in place; host arrays among them are copied to den's device)."""
+    import torch
+
+    dev = den.device
+    if dev.type != "cuda":
+        raise ValueError("torch inputs must live on the GPU; pass NumPy arrays for host data")
+
+    def prep(x, name):
+        if not _is_torch(x):
+            x = torch.as_tensor(np.asarray(x, dtype=np.float64), device=dev)
+        if x.device != dev:
+            raise ValueError(f"{name} is on {x.device}, expected {dev}")
+        return x.detach().to(torch.float64).contiguous()
+
+    f = prep(freq, "freq").reshape(-1)
+    d, b, p, a = (prep(x, n) for x, n in ((den, "den"), (bmag, "bmag"), (bpsi, "bpsi"), (alt, "alt")))
+    single = d.dim() == 1
+    shared = d.dim() == 2 and b.dim() == 1 and p.dim() == 1 and b.shape == p.shape == d.shape[1:]
+    d2 = d.reshape(1, -1) if single else d
+    b2, p2 = (b, p) if shared else tuple(x.reshape(1, -1) if x.dim() == 1 else x for x in (b, p))
+    if d2.dim() != 2 or (not shared and not (d2.shape == b2.shape == p2.shape)):
+        raise ValueError("den, bmag and bpsi must have the same 1-D or 2-D shape")
+    n_prof, n_alt = d2.shape
+    if a.shape[-1] != n_alt or (a.dim() == 2 and a.shape[0] != n_prof):
+        raise ValueError("alt must have one value per density level")
+    return f, d2, b2, p2, a, single, shared, (n_alt if a.dim() == 2 else 0)
+
+
+def vertical_jacobian(freq, den, bmag, bpsi, alt, mode='O', n_points=200, *, device=None, sync=True):
+    """``(vh, J)``: the virtual heights of ``vertical_forward_operator`` and their derivative with respect to the density
+    column, ``J[..., f, k] = d vh[..., f] / d den[..., k]`` [km m^3] - ``(F, N_alt)`` for one profile, ``(P, F, N_alt)``
+    for a batch.  Analytic: the derivative of the reference's discrete sum itself (stretched grid, ``np.interp``
+    bracket of the reflection height and all), computed by HIP kernels; not finite differences.
+
+    Inputs as ``vertical_forward_operator``: NumPy arrays (``device`` picks the GPU), or GPU-resident torch tensors,
+    which are used in place on torch's current stream and give tensors (``sync=False``: do not wait).  ``vh`` is the
+    operator's own output, bit for bit.
+
+    Conventions: a pair without a virtual height (``vh`` NaN) has a row of zeros; levels at and above the density peak
+    get 0; grid points the reference's sum skips (NaN terms) count as constants; an unmagnetised profile is
+    differentiated as ``mu' = (1 - X)^(-1/2)``; at a kink of the operator (a grid point exactly on a level, a tie in the
+    density's argmax or in the running maximum, a running maximum of exactly 1) the result is one of the one-sided
+    derivatives.  The arithmetic does not depend on the ``math`` tier.  ``ValueError`` when the levels below the highest
+    density peak do not fit the GPU's local memory next to the accumulator rows (about 1200 levels).
+    """
+    code = _mode_code(mode)
+    mult_np = _multiplier(n_points)
+    if any(_is_torch(x) and x.is_cuda for x in (den, bmag, bpsi)):
+        import torch
+        f, d2, b2, p2, a, single, shared, alt_stride = _torch_batch(freq, den, bmag, bpsi, alt)
+        dev = d2.device
+        n_prof, n_alt = d2.shape
+        mult, grid_flag = _device_grid((int(n_points),), dev)
+        vh = torch.empty((n_prof, f.numel()), dtype=torch.float64, device=dev)
+        jac = torch.empty((n_prof, f.numel(), n_alt), dtype=torch.float64, device=dev)
+        ctx = _native.context(dev.index if dev.index is not None else torch.cuda.current_device())
+        ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+        ctx.set_math(MATH_AUTO)
+        rc = ctx.vfo_jacobian(f.data_ptr(), f.numel(), d2.data_ptr(), b2.data_ptr(), p2.data_ptr(), a.data_ptr(), n_prof, n_alt,
+                              n_alt, alt_stride, mult.data_ptr(), int(n_points), code, vh.data_ptr(), jac.data_ptr(),
+                              _native.FLAG_DEVICE_PTRS | _native.FLAG_ASYNC | grid_flag |
+                              (_native.FLAG_SHARED_FIELD if shared else 0))
+        _native.raise_for(rc)
+        if sync:
+            _native.raise_for(ctx.sync())
+        return (vh[0], jac[0]) if single else (vh, jac)
+    f, d2, b2, p2, a, single, shared, alt_stride = _np_batch(freq, den, bmag, bpsi, alt)
+    n_prof, n_alt = d2.shape
+    vh = np.empty((n_prof, f.size), dtype=np.float64)
+    jac = np.empty((n_prof, f.size, n_alt), dtype=np.float64)
+    ctx = _native.host_context(device)
+    ctx.set_math(MATH_AUTO)
+    rc = ctx.vfo_jacobian(f.ctypes.data, f.size, d2.ctypes.data, b2.ctypes.data, p2.ctypes.data, a.ctypes.data, n_prof, n_alt,
+                          n_alt, alt_stride, mult_np.ctypes.data, int(n_points), code, vh.ctypes.data, jac.ctypes.data,
+                          (_native.FLAG_SHARED_FIELD if shared else 0) | _grid_flag(mult_np, n_points))
+    _native.raise_for(rc)
+    return (vh[0], jac[0]) if single else (vh, jac)
+
+
+def vertical_vjp(freq, den, bmag, bpsi, alt, grad_vh, mode='O', n_points=200, *, device=None, sync=True):
+    """``grad_den[..., k] = sum_f grad_vh[..., f] * d vh[..., f] / d den[..., k]``: the vector-Jacobian product of
+    ``vertical_forward_operator`` with an upstream gradient ``grad_vh`` (``(F,)`` or ``(P, F)``), in one launch and
+    without forming the Jacobian - the backward pass of ``pyrayhf_amd.autograd.differentiable_forward_operator``.
+
+    Inputs and conventions as ``vertical_jacobian``; ``grad_vh`` is not read where a pair has no virtual height, so a
+    NaN there does no harm.  Returns ``(N_alt,)`` or ``(P, N_alt)``, a tensor for GPU-resident torch inputs.  The result
+    is reproducible bit for bit (no atomics; a profile's row does not depend on the rest of the batch).
+    """
+    code = _mode_code(mode)
+    mult_np = _multiplier(n_points)
+    if any(_is_torch(x) and x.is_cuda for x in (den, bmag, bpsi)):
+        import torch
+        f, d2, b2, p2, a, single, shared, alt_stride = _torch_batch(freq, den, bmag, bpsi, alt)
+        dev = d2.device
+        n_prof, n_alt = d2.shape
+        g = grad_vh if _is_torch(grad_vh) else torch.as_tensor(np.asarray(grad_vh, dtype=np.float64), device=dev)
+        if g.device != dev:
+            raise ValueError(f"grad_vh is on {g.device}, expected {dev}")
+        g = g.detach().to(torch.float64).contiguous()
+        if tuple(g.shape) != ((f.numel(),) if single else (n_prof, f.numel())):
+            raise ValueError("grad_vh must have the shape of the operator's output")
+        mult, grid_flag = _device_grid((int(n_points),), dev)
+        out = torch.empty((n_prof, n_alt), dtype=torch.float64, device=dev)
+        ctx = _native.context(dev.index if dev.index is not None else torch.cuda.current_device())
+        ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+        rc = ctx.vfo_vjp(f.data_ptr(), f.numel(), d2.data_ptr(), b2.data_ptr(), p2.data_ptr(), a.data_ptr(), n_prof, n_alt,
+                         n_alt, alt_stride, mult.data_ptr(), int(n_points), code, g.data_ptr(), None, out.data_ptr(),
+                         _native.FLAG_DEVICE_PTRS | _native.FLAG_ASYNC | grid_flag |
+                         (_native.FLAG_SHARED_FIELD if shared else 0))
+        _native.raise_for(rc)
+        if sync:
+            _native.raise_for(ctx.sync())
+        return out[0] if single else out
+    f, d2, b2, p2, a, single, shared, alt_stride = _np_batch(freq, den, bmag, bpsi, alt)
+    n_prof, n_alt = d2.shape
+    g = np.ascontiguousarray(np.asarray(grad_vh), dtype=np.float64)
+    if g.shape != ((f.size,) if single else (n_prof, f.size)):
+        raise ValueError("grad_vh must have the shape of the operator's output")
+    out = np.empty((n_prof, n_alt), dtype=np.float64)
+    ctx = _native.host_context(device)
+    rc = ctx.vfo_vjp(f.ctypes.data, f.size, d2.ctypes.data, b2.ctypes.data, p2.ctypes.data, a.ctypes.data, n_prof, n_alt,
+                     n_alt, alt_stride, mult_np.ctypes.data, int(n_points), code, g.ctypes.data, None, out.ctypes.data,
+                     (_native.FLAG_SHARED_FIELD if shared else 0) | _grid_flag(mult_np, n_points))
+    _native.raise_for(rc)
+    return out[0] if single else out
 
 
 def vertical_forward_operator_mixed(freq, den, bmag, bpsi, alt, segments, *, device=None, math=None, sync=True):

@@ -42,7 +42,7 @@ extern "C" {
                               *    prhf_trace_gradient_hops_f64, prhf_gradient_hop_home_f64, and
                               *    prhf_residual_many_f64, prhf_vfo_residual_many_f64, and
                               *    prhf_gradient_hop_skip_f64, prhf_gradient_hop_muf_f64,
-                              *    prhf_gradient_hop_skip_counters) */
+                              *    prhf_gradient_hop_skip_counters, and prhf_panel_upper_counters) */
 
 /* return codes */
 #define PRHF_OK        0
@@ -156,6 +156,15 @@ int prhf_ctx_set_math(prhf_ctx* ctx, int level);
  *                        it does not, or until they hold at most four points.  Both settings use the same cuts and the
  *                        same guard: the same pairs take the rule and the same pairs fall back; with 4 values stay
  *                        within 1e-12 of "panel_lower" = 0.  Values between 4 and 8 count as 8)
+ *   "panel_upper"        0: the region of the panel sum ends below the third segment from the top, the launch of before
+ *                        this option bit for bit (1: where "panel_lower" applies, under either setting of "panel_nodes",
+ *                        the region ends at the top segment's first point, rounded down to a multiple of 64 from four
+ *                        points above it: the two segments below the top one are runs of the panel sum like any other,
+ *                        and only the top segment keeps its strided sum.  A pair does so if the runs whose extent
+ *                        changes - from the third segment below the top one upwards - pass the tests every run passes,
+ *                        which is settled from the pair alone before any of them is summed; a pair where one fails
+ *                        keeps the lower region and the strided sums of those two segments, it does not fall back as a
+ *                        whole on their account.  Values stay within 1e-12 of the full sum)
  *   "strided_grade"      0: the strided stretch of each of the top three segments takes every eighth point throughout, the
  *                        launch of before this option bit for bit (1: the stretch is cut into zones by the distance to
  *                        the index where the segment's continuation reaches X + Y = 1 - every 32nd point at least 1024
@@ -893,6 +902,14 @@ int prhf_pair_plan_counters(prhf_ctx* ctx, uint64_t* counters);
  * (a piece too close to X + Y = 1, a region of fewer than 256 points, a guess that did not bracket).  Waits for the
  * context's stream. */
 int prhf_panel_counters(prhf_ctx* ctx, uint64_t* counters);
+
+/* Diagnostics of option "panel_upper", summed over every launch since the context was made: of the pairs that
+ * prhf_panel_counters counts under [0], counters[0] those whose panel region reached the top segment's first point, [1]
+ * those that kept the lower region and the strided sums of the two segments below the top one.  Both stay 0 with the
+ * option off.  (prhf_panel_counters itself counts with the option what it counts without it, except for a pair whose run
+ * next below those segments fails the tests when it ends at the lower region's end and passes when it reaches its
+ * segment's end: such a pair takes the panel sum with the option and falls back without.)  Waits for the context's stream. */
+int prhf_panel_upper_counters(prhf_ctx* ctx, uint64_t* counters);
 
 /* Diagnostics: workgroups of the fused kernel the runtime expects to keep resident per CU for
  * profiles of n_alt levels (LDS-limited) in arithmetic tier `math`. */

@@ -173,6 +173,7 @@ _PROTOTYPES = {
     "prhf_gradient_hop_skip_counters": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
     "prhf_pair_plan_counters": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
     "prhf_panel_counters": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
+    "prhf_panel_upper_counters": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
     "prhf_occupancy": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
                                       ctypes.POINTER(ctypes.c_int32)]),
     "prhf_sync": (ctypes.c_int, [ctypes.c_void_p]),
@@ -551,6 +552,13 @@ class Context:
         context was made (option ``panel_lower``, include/prhf.h)."""
         buf = (ctypes.c_uint64 * 2)()
         raise_for(self._lib.prhf_panel_counters(self._h, buf))
+        return tuple(int(v) for v in buf)
+
+    def panel_upper_counters(self):
+        """(pairs whose panel region reached the top segment, pairs that kept the lower region only) since this
+        context was made (option ``panel_upper``, include/prhf.h)."""
+        buf = (ctypes.c_uint64 * 2)()
+        raise_for(self._lib.prhf_panel_upper_counters(self._h, buf))
         return tuple(int(v) for v in buf)
 
     def occupancy(self, n_alt, math):

@@ -166,7 +166,7 @@ struct prhf_ctx {
     double* h_pack_dev = nullptr;   // half, mapped into the device (h_pack_dev), takes a small result straight from the kernel
     unsigned long long* d_words = nullptr;   // 2 words: nanmax|Y| bits, any-not-NaN
     unsigned long long* h_words = nullptr;   // pinned
-    unsigned long long* d_plan_counters = nullptr;   // 4 words, since the context was made (prhf_pair_plan_counters, prhf_panel_counters)
+    unsigned long long* d_plan_counters = nullptr;   // 6 words, since the context was made (prhf_pair_plan_counters, prhf_panel_counters, prhf_panel_upper_counters)
     bool status_pending = false;
     uint64_t grad_home_counters[PRHF_GRAD_HOME_COUNTERS] = {};   // of the last prhf_gradient_home_f64 (prhf_gradient_home_counters)
     DevBuf fields;    // prhf_gradient_muf_f64: mu, mu' and the records of every link's field (48 bytes per node and link)
@@ -1002,8 +1002,8 @@ int prhf_ctx_create(int device, prhf_ctx** out) {
         (e = hipMalloc(reinterpret_cast<void**>(&c->d_words), 2 * sizeof(unsigned long long))) != hipSuccess ||
         (e = hipHostMalloc(reinterpret_cast<void**>(&c->h_words), 2 * sizeof(unsigned long long),
                            hipHostMallocDefault)) != hipSuccess ||
-        (e = hipMalloc(reinterpret_cast<void**>(&c->d_plan_counters), 4 * sizeof(unsigned long long))) != hipSuccess ||
-        (e = hipMemset(c->d_plan_counters, 0, 4 * sizeof(unsigned long long))) != hipSuccess ||
+        (e = hipMalloc(reinterpret_cast<void**>(&c->d_plan_counters), 6 * sizeof(unsigned long long))) != hipSuccess ||
+        (e = hipMemset(c->d_plan_counters, 0, 6 * sizeof(unsigned long long))) != hipSuccess ||
         (e = prhf::configure_kernels(staged_lds_bytes(kMaxAlt))) != hipSuccess) {
         prhf_ctx_destroy(c);
         return fail(PRHF_EHIP, "context setup failed: %s", hipGetErrorString(e));
@@ -2914,6 +2914,19 @@ int prhf_panel_counters(prhf_ctx* c, uint64_t* counters) {
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipMemcpy(w, c->d_plan_counters + 2, sizeof w, hipMemcpyDeviceToHost));
     counters[0] = w[0];
+    counters[1] = w[1];
+    return PRHF_OK;
+}
+
+int prhf_panel_upper_counters(prhf_ctx* c, uint64_t* counters) {
+    if (!c || !counters) return fail(PRHF_EINVAL, "null pointer");
+    DeviceScope device_scope_(c->device);
+    unsigned long long w[2] = {0, 0};
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpy(w, c->d_plan_counters + 4, sizeof w, hipMemcpyDeviceToHost));
+    // (the device counts the pairs that took the panel sum with the option on - each of them reports one or the other - and
+    //  among them those that kept the lower region)
+    counters[0] = w[0] - w[1];
     counters[1] = w[1];
     return PRHF_OK;
 }

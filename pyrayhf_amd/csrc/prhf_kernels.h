@@ -99,6 +99,9 @@ struct SegDev {
     // drains quickly: profiles [tail_prof, P) of the slice use tail_bpp blocks each (tail_prof = P: none).
     long long tail_prof;
     int tail_bpp;
+    int panel_upper;                 // with panel_lower (below): the panel sum's region reaches up to the top segment's first
+                                     // point where the two segments below it pass the runs' tests (option panel_upper; it sits
+                                     // here, in what was padding: the kernels' argument layout is the one of before)
     // Faithful tier only: where 1 - X exceeds this at all 64 points of a wave-iteration the reduced
     // algebra is used instead of the reference's operation order (+inf: never).
     double well_conditioned;
@@ -159,7 +162,9 @@ struct KArgs {
     long long lds_levels;
     // The planning pass (SegDev::pair_plan): [0] pairs that ran from a plan, [1] eligible pairs that planned themselves,
     // added to once per workgroup and block; plan_cap > 0 caps the records per workgroup (tests).  [2] pairs whose lower
-    // segments took the panel sum, [3] eligible pairs that fell back (SegDev::panel_lower), added to once per wave and block
+    // segments took the panel sum, [3] eligible pairs that fell back (SegDev::panel_lower), [4] the pairs of [2] in
+    // slices with SegDev::panel_upper, [5] those of them whose panel region stayed the lower one, added to once per wave and
+    // block ([5]: once per such pair, they are few; the others' region reached the top segment)
     unsigned long long* plan_counters;
     int plan_cap;
     SegDev seg[PRHF_MAX_SEGMENTS];

@@ -167,10 +167,13 @@ constexpr int kPanelLowerBit = 1 << 29;
 constexpr int kPanelNodes4Bit = 1 << 28;
 // ... and bit 27: a strided stretch of the top three segments is cut into zones of stride 32, 16 and 8 (SegDev::strided_grade)
 constexpr int kStridedGradeBit = 1 << 27;
+// ... and bit 31: the panel sum's region may reach up to the top segment's first point (SegDev::panel_upper)
+constexpr int kPanelUpperBit = (int)(1u << 31);
 // a part of a panel piece takes four nodes where X + Y = 1 lies at least kPanelFar n + 2 indices from its centre
 constexpr int kPanelFar = 16;
 // what the main loop reports about the panel sum in the bits above kPanelStateShift of LeanResult::first (a grid point's
-// index stays below 2^27): 1 the pair's lower segments took it, 2 the pair was eligible and kept the sum of before
+// index stays below 2^27): 1 the pair's lower segments took it, 2 the pair was eligible and kept the sum of before; with
+// option panel_upper 3 and 4 in the place of 1: the region reached the top segment, the region stayed the lower one
 constexpr int kPanelStateShift = 28;
 #define PRHF_PANEL_NODES_DECL [[maybe_unused]] static __device__ const double kPanelNodes[8]   // (the table's own abscissae: the pairs below hold them as offsets)
 #define PRHF_PANEL_PAIRS_DECL static __device__ __attribute__((aligned(16))) const double kPanelPairs[(PRHF_PANEL_N_MAX + 1) * 16]
@@ -1221,7 +1224,8 @@ struct LeanResult {
 // TOP: with the top-segment phase (long grids on a uniform altitude grid); the short-grid callers use the
 // variant without it, which needs 24 fewer vector registers around the call.
 // GRADE: with the zones of the strided sum (option strided_grade); without, the function is the one of before.
-template <int MODE, bool CHECK, int POLY, bool HINT, bool TOP, bool G, bool GRADE>
+// UPPER: the panel sum's region may reach the top segment (option panel_upper); without, the function is the one of before.
+template <int MODE, bool CHECK, int POLY, bool HINT, bool TOP, bool G, bool GRADE, bool UPPER>
 __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type nodes_arg, unsigned hint_lds,
                                                      const double2* __restrict__ pairs, int first, int end,
                                                      int last_special, double span, double a0, double kj,
@@ -1492,8 +1496,12 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
     const bool panel_req = (sp_off & kPanelLowerBit) != 0;
     const bool nodes4_req = (sp_off & kPanelNodes4Bit) != 0;
     constexpr bool grade_req = GRADE;                  // (lean_loop picks the instance by the option's bit)
-    sp_off &= ~(kStridedLowerBit | kPanelLowerBit | kPanelNodes4Bit | kStridedGradeBit);
-    int panel_state = 0;                               // (waits in a vector register, where the result travels anyway)
+    static_assert(!UPPER || (STRIDED && !HINT), "only an instance with the panel block has the upper region");
+    sp_off &= ~(kStridedLowerBit | kPanelLowerBit | kPanelNodes4Bit | kStridedGradeBit | kPanelUpperBit);
+    // (waits in a vector register, where the result travels anyway; until the panel block is through, three bits above
+    //  the state's three carry the flags of option panel_upper there too - the function has no scalar register to spare)
+    constexpr int kUpperKept = 16, kUpperRegion = 8;
+    int panel_state = 0;
     asm volatile("" : "+v"(panel_state));
     if (STRIDED && sp_off > 0 && n_seg > 0 && first == 0 && last_special >= 0 && end >= PRHF_TOP3_MIN_POINTS) {
         const u32x4 vh = __builtin_amdgcn_raw_buffer_load_b128(rsrc, 0, sp_off * (int)sizeof(double2), 0);
@@ -1716,11 +1724,27 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
             const int lo_min = uniform(first_point(j_min, ok_min));
             S_P = (lo_min + B - 1) & ~(B - 1);
             auto region_end = [&]() { return ((seg_lo[2] + 4) & ~63) & ~(B - 1); };
+            // Option panel_upper (UPPER): the region may end at the top segment's first point, E_up, instead - the two
+            // segments below the top one, j_top - 2 and j_top - 1, become runs like any other, and so do the top segment's
+            // first points where E_up lies above them.  It does if the runs whose extent is the upper region's - from run
+            // j_top - 3, which no longer ends at today's end, upwards - pass the tests every run passes; else the region
+            // keeps today's end and the two segments their strided sums, and the pair does not fall back on their
+            // account.  Below today's end both regions have the same runs, so the lists are made for the upper region until
+            // the first list whose lanes hold every run that is left: there those runs' tests are known before any of
+            // them is summed, and where one fails the list is made again for the lower region.  (A list with more runs
+            // left than it has lanes ends in front of run j_top - 3 and ignores what the lanes behind its end found.)
+            // A function of the pair alone, like the rest.
+            auto upper_end = [&]() { return (seg_lo[0] + 4) & ~63; };
             if (__ballot(!ok_min) == 0ull && j_min < seg_j[2] && region_end() - S_P >= 256) {
-                const int E_P = region_end();
+                // (the region's end, from the flag: nothing more for the loop to carry)
+                auto upper_now = [&]() {
+                    asm volatile("" : "+v"(panel_state));
+                    return (uniform(panel_state) & kUpperRegion) != 0;
+                };
+                const int E_lo = region_end();
                 // the segments of the region's first and last point
                 const u32x4 vs = __builtin_amdgcn_raw_buffer_load_b128(rsrc, 0, S_P * (int)sizeof(double2), 0);
-                const u32x4 ve = __builtin_amdgcn_raw_buffer_load_b128(rsrc, 0, (E_P - 1) * (int)sizeof(double2), 0);
+                const u32x4 ve = __builtin_amdgcn_raw_buffer_load_b128(rsrc, 0, (E_lo - 1) * (int)sizeof(double2), 0);
                 double2 gs, ge;
                 __builtin_memcpy(&gs, &vs, sizeof gs);
                 __builtin_memcpy(&ge, &ve, sizeof ge);
@@ -1732,15 +1756,41 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
                 // (the loop function is at the end of its scalar registers: the segment of the list's first run and the
                 //  runs left are all the loop carries)
                 int j_0 = j_s, left = j_e - j_s + 1;
+                // (the lower region's last segment waits in a vector register)
+                // (... and so do the region's two ends, which only the lanes' arithmetic reads)
+                int j_e_lo = j_e, e_v = E_lo, s_v = S_P;
+                if constexpr (UPPER) {
+                    asm volatile("" : "+v"(j_e_lo), "+v"(s_v));
+                    const u32x4 vu = __builtin_amdgcn_raw_buffer_load_b128(rsrc, 0, (upper_end() - 1) * (int)sizeof(double2), 0);
+                    double2 gu;
+                    __builtin_memcpy(&gu, &vu, sizeof gu);
+                    // (the region's last point lies in the segment below the top one, or is one of the top one's first)
+                    const int up = uniform((int)(gu.x * kj)) - (seg_j[0] - 1);
+                    if (up == 0 || up == 1) {
+                        panel_state = 2 | kUpperRegion;
+                        left = seg_j[0] + up - j_s;
+                        e_v = upper_end();
+                    } else {
+                        // (the segment below the top one lies wholly above E_up, or the table is not monotone there)
+                        panel_state = 2 | kUpperKept;
+                    }
+                    asm volatile("" : "+v"(e_v));
+                }
 #pragma unroll 1
                 while (left > 0) {
+                    int E_P = E_lo, S_L = S_P;                 // (UPPER: both in vector registers)
+                    if constexpr (UPPER) {
+                        asm volatile("" : "+v"(j_e_lo), "+v"(e_v), "+v"(s_v));
+                        E_P = e_v;
+                        S_L = s_v;
+                    }
                     // lane l: the run in segment j_0 + l, from the segment's first point (the region's for the lowest
                     // run) to the next lane's (lane 63 only finds the first point that ends lane 62's run)
                     const bool live = lane < left;
                     const int j_g = live ? j_0 + lane : j_0;
                     bool ok;
                     const int fq = first_point(j_g, ok);
-                    const int p = live ? max(fq, S_P) : E_P;
+                    const int p = live ? max(fq, S_L) : E_P;
                     const int p_next = __shfl_down(p, 1);
                     const int n = live && lane < 63 ? max(min(p_next, E_P) - p, 0) : 0;
                     // k base pieces of L = ceil(n / k) points, the last one shorter (the quotient from the single-
@@ -1803,14 +1853,40 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
                         }
                     }
                     const int cnt = n > 0 ? k << lvl : 0;      // the run's entries
-                    fail = __ballot((live && !ok) || (big && !clear) || cnt > 128) != 0ull;
-                    if (fail) break;
+                    // (what a lane found waits in a vector register for the rare list with a run that fails)
+                    if constexpr (UPPER) {
+                        // (what a lane found waits in a vector register for the rare list with a run that fails)
+                        int bad_v = (live && !ok) || (big && !clear) || cnt > 128 ? 1 : 0;
+                        fail = __ballot(bad_v != 0) != 0ull;
+                        if (fail) {
+                            // (a run below j_top - 3 is the same run in both regions: the pair falls back.  The runs from
+                            //  j_top - 3 up have the upper region's extent: where one of them fails and every run left has
+                            //  its lane, before any of them is summed, the list is made again for the lower region; in a
+                            //  list with more runs left they lie behind the list's end and are judged later)
+                            asm volatile("" : "+v"(bad_v));
+                            if (!upper_now() || __ballot(bad_v != 0 && j_g < seg_j[0] - 3) != 0ull) break;
+                            fail = false;
+                            if (left <= 63) {
+                                panel_state = 2 | kUpperKept;
+                                e_v = region_end();
+                                left = uniform(j_e_lo) - j_0 + 1;
+                                continue;
+                            }
+                        }
+                    } else {
+                        fail = __ballot((live && !ok) || (big && !clear) || cnt > 128) != 0ull;
+                        if (fail) break;
+                    }
                     // The list the evaluation reads: entry e in lane e & 63 of lst_a (e < 64) or lst_b, up to 128 entries
                     // of as many consecutive runs as fit.  Nearly always every run is its own single entry and the list
                     // is the lanes' own words; else (a scalar branch) an entry finds its run by bisection in the running
                     // sum of the counts and cuts its part from the run's p, n, L and lvl.
-                    unsigned lst_a = n > 0 ? (unsigned)p | ((unsigned)n << 16) : 0u, lst_b = 0u;
                     int total = min(63, left), n_take = total;
+                    if constexpr (UPPER) {
+                        // (the list ends in front of run j_top - 3, see above; the lanes behind its end are idle)
+                        if (left > 63 && upper_now()) total = n_take = min(total, seg_j[0] - 3 - j_0);
+                    }
+                    unsigned lst_a = n > 0 && (!UPPER || lane < total) ? (unsigned)p | ((unsigned)n << 16) : 0u, lst_b = 0u;
                     if (__ballot(cnt != (live && lane < 63 ? 1 : 0)) != 0ull) {
                         int incl = cnt;
                         incl += __builtin_amdgcn_update_dpp(0, incl, 0x111, 0xf, 0xf, false);    // row_shr:1
@@ -1820,7 +1896,7 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
                         incl += __builtin_amdgcn_update_dpp(0, incl, 0x142, 0xa, 0xf, false);    // row_bcast:15 into rows 1 and 3
                         incl += __builtin_amdgcn_update_dpp(0, incl, 0x143, 0xc, 0xf, false);    // row_bcast:31 into rows 2 and 3
                         // (lane 0 is a live run of at most 128 entries: n_take >= 1)
-                        n_take = __builtin_popcountll(__ballot(live && lane < 63 && incl <= 128));
+                        n_take = __builtin_popcountll(__ballot((UPPER ? lane < total : live && lane < 63) && incl <= 128));
                         total = __builtin_amdgcn_readlane(incl, n_take - 1);
                         const unsigned pk = lst_a;
                         const unsigned aux = (unsigned)(incl - cnt) | ((unsigned)L << 8) | ((unsigned)lvl << 16);
@@ -1882,12 +1958,22 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
                     }
                 }
                 panel_ok = !fail;
+                if constexpr (UPPER) S_P = uniform(s_v);    // (back from its vector register)
                 if (!panel_ok) accm = 0.0;                 // (nothing else has been summed yet: first == 0)
                 g0 = grid_at(first);                       // (loaded again: four vector registers fewer across this block)
             }
             // (the loop function is at the end of its scalar registers: the region travels on in the lower block's own
             //  variables, n_R < 0 says that the panel sum has taken it)
-            if (panel_ok) {
+            if constexpr (UPPER) {
+                const int flags = uniform(panel_state);
+                panel_state = !panel_ok ? 2 : ((flags & kUpperRegion) != 0 ? 3 : 4);
+                asm volatile("" : "+v"(panel_state));
+                if (panel_ok) {
+                    S_R = S_P;
+                    E_R = (flags & kUpperRegion) != 0 ? upper_end() : region_end();
+                    n_R = -1;
+                }
+            } else if (panel_ok) {
                 panel_state = 1;
                 asm volatile("" : "+v"(panel_state));
                 S_R = S_P;
@@ -2008,8 +2094,10 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
     }
     if (TOP) {
         // (one copy of the two loops: the run's bounds are picked with scalar selects, not by unrolling)
+        // (a pair whose panel sum reached the top segment has that segment left, option panel_upper)
+        const int sidx_0 = UPPER && uniform(panel_state) == 3 ? 0 : n_seg - 1;
 #pragma unroll 1
-        for (int sidx = n_seg - 1; sidx >= 0 && !(CHECK && viol); --sidx) {
+        for (int sidx = sidx_0; sidx >= 0 && !(CHECK && viol); --sidx) {
             // (the runs' bounds from the segments' first points, as the search set them - a whole pair begins at grid point
             //  0: six scalar registers fewer across the blocks above)
             const int lo_b = sidx == 0 ? seg_lo[0] : (sidx == 1 ? seg_lo[1] : seg_lo[2]);
@@ -2063,13 +2151,32 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
     return r;
 }
 
+template <int MODE, bool CHECK, int POLY, bool HINT, bool TOP, bool G, bool GRADE, bool UPPER>
+__device__ __attribute__((noinline)) LeanResult lean_loop_region(typename NodeArg<G>::type nodes_arg, unsigned hint_lds,
+                                                                 const double2* __restrict__ pairs, int first, int end,
+                                                                 int last_special, double span, double a0, double kj,
+                                                                 double cX, double cY2, double well_conditioned, int sp_off) {
+    return lean_loop_body<MODE, CHECK, POLY, HINT, TOP, G, GRADE, UPPER>(nodes_arg, hint_lds, pairs, first, end, last_special,
+                                                                          span, a0, kj, cX, cY2, well_conditioned, sp_off);
+}
+// (the option panel_upper picks one of two instances in the same way, one tail call further on and only where the loop
+//  function has the panel block: a dispatcher with more than two targets loses its tail calls and takes a stack frame)
 template <int MODE, bool CHECK, int POLY, bool HINT, bool TOP, bool G, bool GRADE>
 __device__ __attribute__((noinline)) LeanResult lean_loop_instance(typename NodeArg<G>::type nodes_arg, unsigned hint_lds,
                                                                    const double2* __restrict__ pairs, int first, int end,
                                                                    int last_special, double span, double a0, double kj,
                                                                    double cX, double cY2, double well_conditioned, int sp_off) {
-    return lean_loop_body<MODE, CHECK, POLY, HINT, TOP, G, GRADE>(nodes_arg, hint_lds, pairs, first, end, last_special, span,
-                                                                   a0, kj, cX, cY2, well_conditioned, sp_off);
+    if constexpr (TOP && MODE == PRHF_KMODE_X && !CHECK && !G && !HINT) {
+        if ((uniform(sp_off) & kPanelUpperBit) != 0)
+            return lean_loop_region<MODE, CHECK, POLY, HINT, TOP, G, GRADE, true>(nodes_arg, hint_lds, pairs, first, end,
+                                                                                  last_special, span, a0, kj, cX, cY2,
+                                                                                  well_conditioned, sp_off);
+        return lean_loop_region<MODE, CHECK, POLY, HINT, TOP, G, GRADE, false>(nodes_arg, hint_lds, pairs, first, end, last_special,
+                                                                               span, a0, kj, cX, cY2, well_conditioned, sp_off);
+    } else {
+        return lean_loop_body<MODE, CHECK, POLY, HINT, TOP, G, GRADE, false>(nodes_arg, hint_lds, pairs, first, end, last_special,
+                                                                             span, a0, kj, cX, cY2, well_conditioned, sp_off);
+    }
 }
 // (the option strided_grade picks one of two instances of the loop function here, by one scalar branch and a tail call:
 //  a launch without it runs the instruction stream of before in a function of its own, and the kernel keeps its single
@@ -2680,10 +2787,12 @@ __device__ __forceinline__ void run_items(const KArgs& a, const SegDev& sg, cons
     const double2* pairs = (a.pairs && sg.lean) ? reinterpret_cast<const double2*>(a.pairs) + sg.mult_off : nullptr;
     // the strided table's piece of this slice's grid, in entries from `pairs`; 0: none
     // (bit 30: the segments below the top three take the strided sum too - an offset stays below 2^27 entries)
+    // (bit 31 is one of them: whoever uses the offset masks the bits off first, lean_loop_body)
     const int sp_off = (pairs && sg.sp_off > 0)
                            ? uniform((int)(sg.sp_off - sg.mult_off) | (sg.strided_lower ? kStridedLowerBit : 0) |
                                      (sg.strided_lower && sg.panel_lower ? kPanelLowerBit : 0) |
                                      (sg.strided_lower && sg.panel_lower && sg.panel_nodes == 4 ? kPanelNodes4Bit : 0) |
+                                     (!G && sg.strided_lower && sg.panel_lower && sg.panel_upper ? kPanelUpperBit : 0) |
                                      (sg.strided_grade ? kStridedGradeBit : 0)) : 0;
     const long long pair_base = prof_local * F;
     const int first_item = block_in_prof * W, round_items = blocks_per_prof * W;
@@ -2757,7 +2866,11 @@ __device__ __forceinline__ void run_items(const KArgs& a, const SegDev& sg, cons
             }
         }
         if constexpr (MODE == PRHF_KMODE_X && TIER == 1 && !G) {
-            panel_cnt += panel == 1 ? 1 : (panel == 2 ? 0x10000 : 0);
+            panel_cnt += panel == 2 ? 0x10000 : (panel != 0 ? 1 : 0);
+            // (option panel_upper: with it a pair that took the panel sum reports 3, its region reached the top segment, or 4,
+            //  it kept the lower one.  The few of the second kind are counted one by one, and all of them once per wave below:
+            //  no third count waits in a register across the items, of which the kernel has none to spare)
+            if (panel == 4 && lane == 0 && a.plan_counters) atomicAdd(&a.plan_counters[5], 1ull);
         }
         if (lane == 0) {
             if (local) {
@@ -2775,6 +2888,7 @@ __device__ __forceinline__ void run_items(const KArgs& a, const SegDev& sg, cons
         if (lane == 0 && a.plan_counters) {
             if (panel_cnt & 0xffff) atomicAdd(&a.plan_counters[2], (unsigned long long)(panel_cnt & 0xffff));
             if (panel_cnt >> 16) atomicAdd(&a.plan_counters[3], (unsigned long long)(panel_cnt >> 16));
+            if (sg.panel_upper && (panel_cnt & 0xffff)) atomicAdd(&a.plan_counters[4], (unsigned long long)(panel_cnt & 0xffff));
         }
     }
     if (local) {

@@ -95,6 +95,11 @@ struct Knobs {
                                        // they hold at most four points (8, or anything but 4: no halving,
                                        // eight Gauss-Legendre nodes on eight lanes for every piece - the same cuts and the
                                        // same guard, not the bits of the launch before the cuts changed)
+    double panel_upper = 1;            // ... and the region of the panel sum ends at the top segment's first point, not at the
+                                       // third segment's from the top, in every pair whose runs from the third segment below
+                                       // the top one upwards pass the tests of the panel sum's runs; the other pairs keep the lower region and
+                                       // the strided sums of those two segments (0: the launch of before, bit
+                                       // for bit)
     double strided_grade = 1;          // ... and the strided stretch of each of the top three segments is cut into zones:
                                        // every 32nd point at least 1024 indices below the index where the segment's
                                        // continuation reaches X + Y = 1 and where 1 - X - Y >= 1.6e-4, every 16th at
@@ -143,6 +148,7 @@ const KnobName kKnobNames[] = {
     {"strided_lower", &Knobs::strided_lower, 0, 1},
     {"panel_lower", &Knobs::panel_lower, 0, 1},
     {"panel_nodes", &Knobs::panel_nodes, 4, 8},
+    {"panel_upper", &Knobs::panel_upper, 0, 1},
     {"strided_grade", &Knobs::strided_grade, 0, 1},
     {"pair_plan", &Knobs::pair_plan, 0, 1},
     {"pair_plan_cap", &Knobs::pair_plan_cap, 0, 1024},
@@ -581,6 +587,7 @@ inline int plan_launch(const LaunchShape& sh, const prhf_segment* segs, int32_t 
             s.strided_lower = kn.strided_lower != 0;
             s.panel_lower = s.strided_lower && kn.panel_lower != 0;
             s.panel_nodes = s.panel_lower && kn.panel_nodes == 4 ? 4 : 8;
+            s.panel_upper = s.panel_lower && kn.panel_upper != 0;
             s.strided_grade = kn.strided_grade != 0;
             s.pair_plan = slice_plans_pairs(s, tall, n_freq, lds_levels, kn) ? 1 : 0;
             pl.any_plan = pl.any_plan || s.pair_plan != 0;

@@ -1925,36 +1925,73 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
                     int four = nodes4_req ? 1 : 0;
                     asm volatile("" : "+s"(four));
                     const int sh = four ? 2 : 3;
-                    const char* tab = reinterpret_cast<const char*>(four ? kPanel4Pairs : kPanelPairs);
+                    // (the table's address through a register the compiler cannot see through: a load it knows to be from
+                    //  constant data crosses the fence below and is moved down to its first use, a trip later - out of flight)
+                    unsigned long long tab_bits = reinterpret_cast<unsigned long long>(four ? kPanel4Pairs : kPanelPairs);
+                    asm volatile("" : "+s"(tab_bits));
+                    typedef double f64x2 __attribute__((ext_vector_type(2)));
+                    typedef const char __attribute__((address_space(1)))* TablePtr;
+                    const TablePtr tab = (TablePtr)tab_bits;
                     const unsigned lk16 = (unsigned)(lane & ((1 << sh) - 1)) << 4;
                     const int src0 = (lane >> sh) << 2;
-                    int src = src0;
-#pragma unroll 1
-                    for (int k0 = 0; k0 < total; k0 += 64 >> sh) {
-                        // sixteen entries of four lanes, or eight entries of eight lanes; the second half of a long list
-                        // behind a scalar branch
-                        if (k0 == 64) {
+                    const int step = 64 >> sh;             // sixteen entries of four lanes, or eight entries of eight lanes
+                    // The evaluation runs one entry ahead of itself: `fetch` takes an entry's list word, its
+                    // table row (offset, weight) and m at the grid point next to the node - three look-ups, each waiting
+                    // for the one before - and is issued for the next entry before `eval`, the arithmetic of the entry
+                    // whose m has arrived, as it always was: m travels under the evaluation before its own (the list word
+                    // and the table row are waited for inside `fetch`; asking for them earlier still was measured and
+                    // bought too little, profiles/ab_panel_pipeline.txt).  The fence in front of `eval` keeps the
+                    // compiler from moving a look-up down to where its value is used.  The last
+                    // entry is evaluated behind the loop's exit, with nothing fetched beside it, so no look-up goes past
+                    // the list's end.  Two trips per loop trip, so that the two sets of registers swap roles.
+                    struct Located { double d, wt; u32x2 vm; };
+                    auto fetch = [&](int k, Located& e) {
+                        // the second half of a long list behind a scalar branch: from entry 64 on the words come from lst_b
+                        if (k == 64) {
                             lst_a = lst_b;
-                            src = src0;
-                            asm volatile("" : "+v"(lst_a), "+v"(src));
+                            asm volatile("" : "+v"(lst_a));
                         }
-                        const unsigned w = (unsigned)__builtin_amdgcn_ds_bpermute(src, (int)lst_a);
-                        src += 256 >> sh;
+                        const unsigned w = (unsigned)__builtin_amdgcn_ds_bpermute(src0 + ((k & 63) << 2), (int)lst_a);
                         const int pp = (int)(w & 0xffffu);
                         // the node's offset from the entry's first point, its weight
-                        const double2 ow = *reinterpret_cast<const double2*>(tab + (((w >> 16) << (sh + 4)) | lk16));
+                        const f64x2 ow = *(const f64x2 __attribute__((address_space(1)))*)(tab + (((w >> 16) << (sh + 4)) | lk16));
                         const double xk = (double)pp + ow.x;
                         const double xr = __builtin_rint(xk);
-                        const u32x2 vm = __builtin_amdgcn_raw_buffer_load_b64(rsrc, (unsigned)(int)xr * (unsigned)sizeof(double2), 0, 0);
+                        e.vm = __builtin_amdgcn_raw_buffer_load_b64(rsrc, (unsigned)(int)xr * (unsigned)sizeof(double2), 0, 0);
+                        e.d = xk - xr;
+                        e.wt = ow.y;
+                    };
+                    auto eval = [&](const Located& e) {
+                        asm volatile("" ::: "memory");
                         double m0;
-                        __builtin_memcpy(&m0, &vm, sizeof m0);
-                        const double t = (xk - xr) * s10;             // |t| <= 5 / (N - 1): five terms of the exponential
+                        __builtin_memcpy(&m0, &e.vm, sizeof m0);
+                        const double t = e.d * s10;                   // |t| <= 5 / (N - 1): five terms of the exponential
                         const double ex = 1.0 + t * (1.0 + t * (0.5 + t * (1.0 / 6.0 + t * (1.0 / 24.0))));
                         const double ek = ((1.0 - m0) + c0) * ex;
                         double2 gm;
                         gm.x = (1.0 + c0) - ek;
-                        gm.y = ow.y * (sc1 * ek);
+                        gm.y = e.wt * (sc1 * ek);
                         accm = lean_step<MODE, false, POLY, HINT, G>(gm, span, a0v, kj, cX, hcY2, accm, wc, viol, nodes_v, cur);
+                    };
+                    if (total > 0) {
+                        Located ea, eb;
+                        fetch(0, ea);
+#pragma unroll 1
+                        for (int k0 = step;; k0 += step) {             // k0: the entry to fetch
+                            if (k0 >= total) {
+                                eval(ea);
+                                break;
+                            }
+                            fetch(k0, eb);
+                            eval(ea);
+                            k0 += step;
+                            if (k0 >= total) {
+                                eval(eb);
+                                break;
+                            }
+                            fetch(k0, ea);
+                            eval(eb);
+                        }
                     }
                 }
                 panel_ok = !fail;

@@ -42,7 +42,8 @@ extern "C" {
                               *    prhf_trace_gradient_hops_f64, prhf_gradient_hop_home_f64, and
                               *    prhf_residual_many_f64, prhf_vfo_residual_many_f64, and
                               *    prhf_gradient_hop_skip_f64, prhf_gradient_hop_muf_f64,
-                              *    prhf_gradient_hop_skip_counters, and prhf_panel_upper_counters) */
+                              *    prhf_gradient_hop_skip_counters, and prhf_panel_upper_counters,
+                              *    and prhf_stream_launches) */
 
 /* return codes */
 #define PRHF_OK        0
@@ -180,6 +181,15 @@ int prhf_ctx_set_math(prhf_ctx* ctx, int level);
  *                        closed-form guess of a segment's first point does not bracket it, still computes its own.  The
  *                        integers are the same either way: no value depends on this option)
  *   "pair_plan_cap"      > 0: a workgroup keeps at most this many plans (0: as many as fit; tests)
+ *   "stream_blocks"      0: every persistent launch is the general kernel's, the launch of before this option instruction
+ *                        for instruction (1: a persistent launch of ONE X-mode fast-tier slice of whole pairs whose
+ *                        workgroups settle reflection heights per thread - at most 512 frequencies, a uniform altitude
+ *                        grid still decided per profile - and whose staged profile fits half of a CU's LDS runs as one
+ *                        16-wave workgroup per CU with two staged profiles: one wave stages the next profile while the
+ *                        others sum the current one, and no barrier separates two profiles.  2: also when the launch has
+ *                        fewer blocks than the device keeps resident; tests.  No value depends on this option.  A wave
+ *                        that waits seconds for a slot of its own workgroup gives the launch up: PRHF_EHIP)
+ *   "stream_grid"        > 0: the streaming form launches at most this many workgroups (0: one per CU; tests, A/B runs)
  *   "short_compact", "short_prio", "short_order", "short_lanes"
  *                        geometry of the short-grid kernels: four 4-wave workgroups per CU (1), wave priorities by age (1),
  *                        blocks in descending cost order (1), lanes per pair in the O kernel (8; 16: four pairs per work
@@ -910,6 +920,10 @@ int prhf_panel_counters(prhf_ctx* ctx, uint64_t* counters);
  * next below those segments fails the tests when it ends at the lower region's end and passes when it reaches its
  * segment's end: such a pair takes the panel sum with the option and falls back without.)  Waits for the context's stream. */
 int prhf_panel_upper_counters(prhf_ctx* ctx, uint64_t* counters);
+
+/* Diagnostics of option "stream_blocks": *count = the operator launches of this context that took the streaming form
+ * since the context was made (a launch that keeps the general kernel does not count).  Host-side; does not synchronize. */
+int prhf_stream_launches(prhf_ctx* ctx, uint64_t* count);
 
 /* Diagnostics: workgroups of the fused kernel the runtime expects to keep resident per CU for
  * profiles of n_alt levels (LDS-limited) in arithmetic tier `math`. */

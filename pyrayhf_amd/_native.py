@@ -174,6 +174,7 @@ _PROTOTYPES = {
     "prhf_pair_plan_counters": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
     "prhf_panel_counters": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
     "prhf_panel_upper_counters": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
+    "prhf_stream_launches": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
     "prhf_occupancy": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
                                       ctypes.POINTER(ctypes.c_int32)]),
     "prhf_sync": (ctypes.c_int, [ctypes.c_void_p]),
@@ -560,6 +561,13 @@ class Context:
         buf = (ctypes.c_uint64 * 2)()
         raise_for(self._lib.prhf_panel_upper_counters(self._h, buf))
         return tuple(int(v) for v in buf)
+
+    def stream_launches(self):
+        """Operator launches of this context that took the streaming form of the persistent launch (option
+        ``stream_blocks``, include/prhf.h) since it was made."""
+        n = ctypes.c_uint64(0)
+        raise_for(self._lib.prhf_stream_launches(self._h, ctypes.byref(n)))
+        return int(n.value)
 
     def occupancy(self, n_alt, math):
         n = ctypes.c_int32(0)

@@ -166,6 +166,7 @@ struct prhf_ctx {
     double* h_pack_dev = nullptr;   // half, mapped into the device (h_pack_dev), takes a small result straight from the kernel
     unsigned long long* d_words = nullptr;   // 2 words: nanmax|Y| bits, any-not-NaN
     unsigned long long* h_words = nullptr;   // pinned
+    uint64_t stream_launches = 0;   // operator launches that took the streaming form since the context was made (prhf_stream_launches)
     unsigned long long* d_plan_counters = nullptr;   // 6 words, since the context was made (prhf_pair_plan_counters, prhf_panel_counters, prhf_panel_upper_counters)
     bool status_pending = false;
     uint64_t grad_home_counters[PRHF_GRAD_HOME_COUNTERS] = {};   // of the last prhf_gradient_home_f64 (prhf_gradient_home_counters)
@@ -207,6 +208,14 @@ struct Residual {
     size_t cost_elems(int64_t n_prof) const { return (size_t)n_prof * (size_t)(n_iono && !ionogram_of_row ? n_iono : 1); }
 };
 
+// The most dynamic LDS of a streaming workgroup (two slots; plan_launch admits what fits kLdsFull).  A -DPRHF_TRACE build
+// keeps a kilobyte of marks in static LDS on top of the slots' headers: the launches it is made for leave that room.
+#ifdef PRHF_TRACE
+constexpr size_t kStreamLdsMax = kLdsFull - 2048;
+#else
+constexpr size_t kStreamLdsMax = kLdsFull;
+#endif
+
 int status_to_code(unsigned bits) {
     if (bits & PRHF_STATUS_PEAK0)
         return fail(PRHF_EPEAK0, "density peak at index 0: no bottomside levels below the peak");
@@ -217,6 +226,9 @@ int status_to_code(unsigned bits) {
     if (bits & PRHF_STATUS_BADINDEX) return fail(PRHF_EINVAL, "profile_index outside [0, n_prof)");
     if (bits & PRHF_STATUS_BADFIELD) return fail(PRHF_EINVAL, "field index outside [0, n_fields)");
     if (bits & PRHF_STATUS_PATHLEN) return fail(PRHF_EINVAL, "a ray has more path nodes than path_stride");
+    if (bits & PRHF_STATUS_STALL)
+        return fail(PRHF_EHIP, "streaming launch gave up: a wave waited seconds for a slot of its own workgroup (the outputs of "
+                    "this call are incomplete; option stream_blocks = 0 takes the general kernel)");
     return PRHF_OK;
 }
 
@@ -582,7 +594,13 @@ int zero_control_words(prhf_ctx* c, const LaunchPlan& pl) {
 
 int launch_general(prhf_ctx* c, const LaunchPlan& pl, prhf::KArgs& a) {
     if (pl.queue) a.queue = c->d_status + kWordGeneral;
-    if (pl.tall) HIP_TRY(prhf::launch_vfo_tall(a, pl.grid, c->stream));
+    if (pl.stream) {
+        a.n_blocks = pl.stream_blocks;         // (the form's own tail: LaunchPlan::stream_tail_bpp)
+        a.seg[0].tail_bpp = pl.stream_tail_bpp;
+        a.seg[0].tail_prof = pl.stream_tail_prof;
+        HIP_TRY(prhf::launch_vfo_stream(a, pl.stream_grid, c->stream));
+        ++c->stream_launches;
+    } else if (pl.tall) HIP_TRY(prhf::launch_vfo_tall(a, pl.grid, c->stream));
     else HIP_TRY(prhf::launch_vfo(a, pl.grid, pl.launch_tier, pl.lds_bytes, c->stream));
     return PRHF_OK;
 }
@@ -832,7 +850,8 @@ int run(prhf_ctx* c, const double* freq, int64_t n_freq, const double* den, cons
 #ifdef PRHF_TRACE
     // diagnostics build (tools/wave_trace.py): per-wave wall-clock stamps of this launch, dumped to $PRHF_TRACE_FILE
     static DevBuf trace_buf;
-    const size_t trace_words = (size_t)pl.blocks * kWavesPerBlock * 6;   // start, end, staged, and three staging marks
+    // start, end, staged, four staging marks, workgroup (the streaming form: PRHF_STREAM_THREADS / 64 waves per block)
+    const size_t trace_words = (size_t)pl.blocks * (pl.stream ? PRHF_STREAM_THREADS / 64 : kWavesPerBlock) * 8;
     if (std::getenv("PRHF_TRACE_FILE") && pl.blocks > 0) {
         if ((rc = ensure(c, trace_buf, trace_words * 8)) != PRHF_OK) return rc;
         HIP_TRY(hipMemsetAsync(trace_buf.p, 0, trace_words * 8, c->stream));
@@ -1004,7 +1023,7 @@ int prhf_ctx_create(int device, prhf_ctx** out) {
                            hipHostMallocDefault)) != hipSuccess ||
         (e = hipMalloc(reinterpret_cast<void**>(&c->d_plan_counters), 6 * sizeof(unsigned long long))) != hipSuccess ||
         (e = hipMemset(c->d_plan_counters, 0, 6 * sizeof(unsigned long long))) != hipSuccess ||
-        (e = prhf::configure_kernels(staged_lds_bytes(kMaxAlt))) != hipSuccess) {
+        (e = prhf::configure_kernels(staged_lds_bytes(kMaxAlt), kStreamLdsMax)) != hipSuccess) {
         prhf_ctx_destroy(c);
         return fail(PRHF_EHIP, "context setup failed: %s", hipGetErrorString(e));
     }
@@ -2928,6 +2947,12 @@ int prhf_panel_upper_counters(prhf_ctx* c, uint64_t* counters) {
     //  among them those that kept the lower region)
     counters[0] = w[0] - w[1];
     counters[1] = w[1];
+    return PRHF_OK;
+}
+
+int prhf_stream_launches(prhf_ctx* c, uint64_t* count) {
+    if (!c || !count) return fail(PRHF_EINVAL, "null pointer");
+    *count = c->stream_launches;
     return PRHF_OK;
 }
 

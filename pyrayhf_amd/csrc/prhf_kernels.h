@@ -17,6 +17,7 @@
 #define PRHF_STATUS_WORDS 8         // one word of host-visible memory per status bit (post_status)
 #define PRHF_STATUS_NANINPUT 0x10   // NaN in a profile's altitude column, or in |B| / psi below its peak
 #define PRHF_STATUS_BADGROUP 0x8    // a ray's ray_group outside [0, n_groups) (grouped tracer launch)
+#define PRHF_STATUS_STALL 0x80      // streaming launch: a wave waited for a slot of its workgroup beyond the bound and gave up
 
 #ifndef PRHF_BLOCK_THREADS
 #define PRHF_BLOCK_THREADS 512      // 8 wavefronts share one staged profile
@@ -27,6 +28,7 @@
 #ifndef PRHF_SHORT_WAVES_PER_SIMD
 #define PRHF_SHORT_WAVES_PER_SIMD 4 // ... and the occupancy their register budget is set for
 #endif
+#define PRHF_STREAM_THREADS 1024    // the streaming form of the persistent launch: sixteen waves share two staged profiles
 #define PRHF_HINT_BUCKETS 1024      // uint16 segment hints, 2 KiB of LDS (non-uniform altitude grids)
 #define PRHF_MAX_CAND 1024          // uint16 list of the frequencies that may reflect, 2 KiB of LDS
 #define PRHF_MAX_SEGMENTS 8
@@ -172,7 +174,7 @@ struct KArgs {
 
 // n_alt + 1 nodes (the last one may be the +inf sentinel), f_N^2 and g_p*B per level,
 // segment hints, candidate frequencies, block-reduction scratch
-inline size_t lds_bytes_for(long long n_alt) {
+inline __host__ __device__ size_t lds_bytes_for(long long n_alt) {
     return (size_t)(n_alt + 1) * PRHF_NODE_BYTES + (size_t)n_alt * 16 + PRHF_HINT_BUCKETS * 2 + PRHF_MAX_CAND * 2 +
            PRHF_RED_DOUBLES * 8;
 }
@@ -211,7 +213,7 @@ inline int short_queue_entries(long long n_alt, long long n_freq, size_t budget,
     return (int)(q > PRHF_SHORT_MAX_QUEUE ? PRHF_SHORT_MAX_QUEUE : q);
 }
 
-hipError_t configure_kernels(size_t max_lds_bytes);
+hipError_t configure_kernels(size_t max_lds_bytes, size_t max_stream_lds_bytes);
 hipError_t query_occupancy(int tier, size_t lds_bytes, int* blocks_per_cu);
 // pairs[2 i], pairs[2 i + 1] = mult[i], mult[i + 1] - mult[i]; `pairs` holds n + PRHF_PAIR_PAD entries
 hipError_t launch_grid_pairs(const double* mult, long long n, double* pairs, hipStream_t stream);
@@ -238,6 +240,9 @@ hipError_t launch_freq_table(const double* freq_mhz, long long n_freq, double* t
 // a.n_blocks blocks of work; with a.queue set the grid is `grid_blocks` persistent workgroups that pull
 // block indices from the queue, else grid_blocks must equal a.n_blocks
 hipError_t launch_vfo(const KArgs& a, long long grid_blocks, int tier, size_t lds_bytes, hipStream_t stream);
+// the streaming form (vfo_stream_kernel): grid_blocks workgroups of PRHF_STREAM_THREADS, each with two slots of
+// lds_bytes_for(a.lds_levels) bytes; a.queue set; one X-mode fast-tier slice of whole pairs (LaunchPlan::stream)
+hipError_t launch_vfo_stream(const KArgs& a, long long grid_blocks, hipStream_t stream);
 // profiles of more than 1400 levels: a.tall holds grid_blocks slabs of a.tall_stride >= tall_slab_bytes(n_alt) bytes
 hipError_t launch_vfo_tall(const KArgs& a, long long grid_blocks, hipStream_t stream);
 // *max_peak (one device word, zeroed by the caller) = the highest density-peak index - np.argmax, the first NaN

@@ -477,10 +477,11 @@ constexpr int kHintBuckets = PRHF_HINT_BUCKETS;
 constexpr int kNanRow = 0x100;
 static_assert(kNanRow >= (1 << PRHF_STATUS_WORDS), "kNanRow must not be a status bit");
 
-// -DPRHF_TRACE builds: wall-clock marks of the staging phases of the current block (thread 0 writes them)
+// -DPRHF_TRACE builds: wall-clock marks of the staging phases of the current block (thread 0 writes them; a wave that
+// stages alone - the team forms below - keeps eight words of its own behind the first eight)
 #ifdef PRHF_TRACE
 __device__ __forceinline__ unsigned long long* trace_marks() {
-    __shared__ unsigned long long marks[4];
+    __shared__ unsigned long long marks[8 + 8 * 16];
     return marks;
 }
 #define PRHF_MARK(i) do { if (threadIdx.x == 0) trace_marks()[i] = wall_clock64(); } while (0)
@@ -488,8 +489,39 @@ __device__ __forceinline__ unsigned long long* trace_marks() {
 #define PRHF_MARK(i) do { } while (0)
 #endif
 
-// Stage one profile into LDS.  Every thread of the block calls this.
-template <int TIER, int THREADS>
+// The staging functions (stage_profile, list_candidates, plan_pairs) run on a TEAM of threads: the whole workgroup of
+// THREADS threads (TEAM == THREADS, the default: thread index, __syncthreads) or one wave of it that stages alone beside
+// the others (TEAM == 64: lane index; a barrier becomes a wave-local wait for the wave's own LDS operations, which
+// the LDS carries out in the order they were issued; the rounds of THREADS become loops over rounds of 64).  THREADS
+// keeps fixing what the rest of the workgroup relies on: where the kept scalars lie in `red` and how the items of a
+// profile are numbered.  Every arithmetic statement is the same in both forms, so a value does not depend on the form.
+template <int TEAM, int THREADS>
+__device__ __forceinline__ int team_tid() {
+    static_assert(TEAM == THREADS || TEAM == 64, "a team is the workgroup or one wave");
+    return TEAM == THREADS ? (int)threadIdx.x : (int)(threadIdx.x & 63);
+}
+template <int TEAM, int THREADS>
+__device__ __forceinline__ void team_sync() {
+    if constexpr (TEAM == THREADS) {
+        __syncthreads();
+    } else {
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+template <int TEAM, int THREADS>
+__device__ __forceinline__ void team_mark(int i) {
+#ifdef PRHF_TRACE
+    if constexpr (TEAM == THREADS) {
+        if (threadIdx.x == 0) trace_marks()[i] = wall_clock64();
+    } else {
+        if ((threadIdx.x & 63) == 0) trace_marks()[8 + 8 * (threadIdx.x >> 6) + i] = wall_clock64();
+    }
+#endif
+}
+
+// Stage one profile into LDS.  Every thread of the team calls this.
+template <int TIER, int THREADS, int TEAM = THREADS>
 __device__ __forceinline__ BlockInfo stage_profile(const double* __restrict__ den,
                                                    const double* __restrict__ bmag,
                                                    const double* __restrict__ bpsi,
@@ -499,9 +531,10 @@ __device__ __forceinline__ BlockInfo stage_profile(const double* __restrict__ de
                                                    unsigned short* hint, double* red, int capacity,
                                                    bool bottomside_alt = false) {
 #pragma clang fp contract(off)
-    constexpr int W = THREADS / 64;
-    static_assert(10 * W + 3 <= PRHF_RED_DOUBLES, "reduction scratch too small");
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    constexpr int W = TEAM / 64;
+    constexpr int KW = 10 * (THREADS / 64);            // the kept scalars (kept_scalars<THREADS>)
+    static_assert(10 * W <= KW && KW + 3 <= PRHF_RED_DOUBLES, "reduction scratch too small");
+    const int tid = team_tid<TEAM, THREADS>(), lane = tid & 63, wave = tid >> 6;
     // red rows of W doubles: 0 peak value, 1 peak index, 2 alt min, 3 freq min,
     //                        4 |B| max, 5 negative density, 6 max angle step, 7 non-uniform grid,
     //                        8 f_N^2 max below the peak, 9 NaN in the density or altitude column
@@ -518,7 +551,7 @@ __device__ __forceinline__ BlockInfo stage_profile(const double* __restrict__ de
     // bottomside_alt (the standalone regrid, which never reads np.min(alt)): only a NaN altitude BELOW the peak counts,
     // and phase 2 finds it - the reference's regrid reads nothing at or above the peak but the density (:371-375).
     int nan_in = 0;
-    for (int i = tid; i < n_alt; i += THREADS) {
+    for (int i = tid; i < n_alt; i += TEAM) {
         const double v = den[i], al = alt[i];
         const double key = (v != v) ? __builtin_inf() : v;
         if (key > bv) { bv = key; bi = i; }
@@ -526,7 +559,7 @@ __device__ __forceinline__ BlockInfo stage_profile(const double* __restrict__ de
         nan_in |= (al != al && !bottomside_alt) ? 1 : 0;
     }
     double fm = __builtin_inf();
-    for (int i = tid; i < n_freq; i += THREADS) fm = fmin(fm, fabs(freq[i]));
+    for (int i = tid; i < n_freq; i += TEAM) fm = fmin(fm, fabs(freq[i]));
     {
         // first occurrence of the maximum: a symmetric choice between the two halves, then lane ^ 16 ... ^ 1
         double v0, v1;
@@ -554,7 +587,7 @@ __device__ __forceinline__ BlockInfo stage_profile(const double* __restrict__ de
         red[3 * W + wave] = fm;
         red[9 * W + wave] = (double)nan_in;
     }
-    __syncthreads();
+    team_sync<TEAM, THREADS>();
     bv = red[0];
     bi = (int)red[W];
     amin = red[2 * W];
@@ -569,11 +602,11 @@ __device__ __forceinline__ BlockInfo stage_profile(const double* __restrict__ de
         fm = fmin(fm, red[3 * W + w]);
         nan_in |= (int)red[9 * W + w];
     }
-    PRHF_MARK(0);
+    team_mark<TEAM, THREADS>(0);
     BlockInfo info;
     info.K = uniform((bi == 0x7fffffff) ? 0 : bi);      // library.py:371-375: levels [0, argmax)
     // every thread holds the same reduced value and writes it: a wave reads back what it wrote itself
-    red[10 * W + kKeepAltMin] = amin;
+    red[KW + kKeepAltMin] = amin;
     fm = uniform(fm);
     info.bad = 0;
     info.unmag = 0;
@@ -604,7 +637,7 @@ __device__ __forceinline__ BlockInfo stage_profile(const double* __restrict__ de
     const double step0 = (K > 1) ? alt[1] - alt[0] : 1.0;
     double bmax = 0.0, pmax = 0.0;
     int neg = 0, ragged = 0, trig = 0, cubic = 0, quadratic = 0, steep = 0;
-    for (int k = tid; k <= K; k += THREADS) {
+    for (int k = tid; k <= K; k += TEAM) {
         Node nd;
         if (k == K) {                              // sentinel: no abscissa is >= +inf
             nd.alt = __builtin_inf();
@@ -702,7 +735,7 @@ __device__ __forceinline__ BlockInfo stage_profile(const double* __restrict__ de
         red[7 * W + wave] = (double)ragged;
         red[8 * W + wave] = pmax;
     }
-    __syncthreads();
+    team_sync<TEAM, THREADS>();
     pmax = red[8 * W];
     bmax = red[4 * W];
     neg = (int)red[5 * W];
@@ -721,8 +754,8 @@ __device__ __forceinline__ BlockInfo stage_profile(const double* __restrict__ de
         ragged |= (int)red[7 * W + w];
     }
     bmax = uniform(bmax);
-    red[10 * W + kKeepPf2Max] = pmax;
-    red[10 * W + kKeepGbMax] = kGyro * bmax;
+    red[KW + kKeepPf2Max] = pmax;
+    red[KW + kKeepGbMax] = kGyro * bmax;
     neg = uniform(neg);
     trig = uniform(trig);
     ragged = uniform(ragged);
@@ -745,7 +778,7 @@ __device__ __forceinline__ BlockInfo stage_profile(const double* __restrict__ de
         // Rotation form for EVERY segment of this profile: 2 cos^2(psi_j + r x) = 1 + cos(2 psi_j) cos(theta) -
         // sin(2 psi_j) sin(theta), theta = 2 r x: u0 = cos 2psi_j, u1 = 2 r [rad/km], u2 = sin 2psi_j (lean_step<POLY 4>).
         // u3 stays / becomes NaN: the generic loop (tails, fallbacks) keeps taking sin() of the interpolated angle.
-        for (int k = tid; k < K; k += THREADS) {
+        for (int k = tid; k < K; k += TEAM) {
             double sp, cp;
             prhf_cr::sincos_table(nodes[k].psi * kDegToRad, &sp, &cp);
             nodes[k].u0 = (cp - sp) * (cp + sp);
@@ -753,7 +786,7 @@ __device__ __forceinline__ BlockInfo stage_profile(const double* __restrict__ de
             nodes[k].u2 = 2.0 * (sp * cp);
             nodes[k].u3 = qnan();
         }
-        __syncthreads();
+        team_sync<TEAM, THREADS>();
     }
     // ---- phase 3: segment lookup: closed form when uniform, else a hint table --------------
     const double a0 = uniform(nodes[0].alt);
@@ -765,7 +798,7 @@ __device__ __forceinline__ BlockInfo stage_profile(const double* __restrict__ de
     if (!info.uniform) {
         // hint[b] = last level with alt <= a0 + b*w
         const double w = span / (double)kHintBuckets;
-        for (int b = tid; b < kHintBuckets; b += THREADS) {
+        for (int b = tid; b < kHintBuckets; b += TEAM) {
             const double t = a0 + (double)b * w;
             int lo = 0, hi = K - 1;               // invariant: alt[lo] <= t (alt[0] = a0 <= t)
             while (lo < hi) {
@@ -774,7 +807,7 @@ __device__ __forceinline__ BlockInfo stage_profile(const double* __restrict__ de
             }
             hint[b] = (unsigned short)lo;
         }
-        __syncthreads();
+        team_sync<TEAM, THREADS>();
     }
     return info;
 }
@@ -2409,17 +2442,28 @@ __device__ __forceinline__ void prefix_max_in_place(double* v, int K, double* re
 // reflection_height, the same IEEE operations on the same values - instead of each WAVE settling one pair later
 // on: ~2 vector instructions per pair instead of ~80, which is a sixth of a pair's cost on a 200-point grid.
 // heights[i] belongs to cand[i]; every listed frequency reflects.
-template <int THREADS>
+template <int THREADS, int TEAM = THREADS>
 __device__ __forceinline__ int list_candidates(const KArgs& a, const SegDev& sg, const double* keep,
                                                long long pair_base, unsigned short* cand, int* cand_count,
                                                const Node* nodes, const double* pf2, const double* gb, int K,
                                                double* heights) {
-    constexpr int W = THREADS / 64;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    constexpr int W = TEAM / 64;
+    const int tid = team_tid<TEAM, THREADS>(), lane = tid & 63, wave = tid >> 6;
     const int F = (int)a.n_freq;
+    // One wave alone takes the frequencies in rounds of 64.  X mode keeps its heights where f_N^2 lived, and a later
+    // round's scan still reads that: every lane holds its heights (one per round, THREADS / 64 rounds at most: heights
+    // are settled only for n_freq <= THREADS) until the last scan is done.
+    constexpr bool kDefer = TEAM != THREADS;
+    constexpr int kRounds = kDefer ? THREADS / TEAM : 1;
+    [[maybe_unused]] double h_kept[kRounds];
+    [[maybe_unused]] int pos_kept[kRounds];
+    if constexpr (kDefer) {
+#pragma unroll
+        for (int r = 0; r < kRounds; ++r) { h_kept[r] = 0.0; pos_kept[r] = -1; }
+    }
     const double pmax = keep[kKeepPf2Max], gmax = keep[kKeepGbMax];
     int total = 0;
-    for (int base = 0; base < F; base += THREADS) {
+    for (int base = 0; base < F; base += TEAM) {
         const int f = base + tid;
         bool may = false;
         double h = 0.0;
@@ -2537,7 +2581,7 @@ __device__ __forceinline__ int list_candidates(const KArgs& a, const SegDev& sg,
         }
         const unsigned long long mask = __ballot(may);
         if (lane == 0) cand_count[wave] = __popcll(mask);
-        __syncthreads();
+        team_sync<TEAM, THREADS>();
         int at = total, chunk = 0;
 #pragma unroll
         for (int w = 0; w < W; ++w) {
@@ -2550,10 +2594,25 @@ __device__ __forceinline__ int list_candidates(const KArgs& a, const SegDev& sg,
         if (may) {
             const int pos = at + __popcll(mask & ((1ull << lane) - 1ull));
             cand[pos] = (unsigned short)f;
-            if (heights) heights[pos] = h;
+            if constexpr (!kDefer) {
+                if (heights) heights[pos] = h;
+            } else {
+                const int round = base / TEAM;             // (wave-uniform)
+#pragma unroll
+                for (int r = 0; r < kRounds; ++r)
+                    if (r == round) { h_kept[r] = h; pos_kept[r] = pos; }
+            }
         }
-        __syncthreads();
+        team_sync<TEAM, THREADS>();
         total += chunk;
+    }
+    if constexpr (kDefer) {
+        if (heights) {
+#pragma unroll
+            for (int r = 0; r < kRounds; ++r)
+                if (pos_kept[r] >= 0) heights[pos_kept[r]] = h_kept[r];
+        }
+        team_sync<TEAM, THREADS>();
     }
     return uniform(total);
 }
@@ -2672,6 +2731,10 @@ __device__ __forceinline__ unsigned plan_slot(const PlanRoom& r, int i) {
 // each - written to `rec` (six words).  Returns false where the guess does not bracket (another grid, a range's
 // edge): that pair's wave runs its own search.  `h` is the settled reflection height (span > 0 and kj inside the node
 // table: checked by the caller, as integrate_chunk does).
+// (FORM: one copy of the function for the workgroup-wide pass of the general kernels, another for the lone stager of the
+//  streaming form - the backend fits a shared function's registers to all of its callers, and the general kernels keep
+//  the code they had)
+template <int FORM>
 __device__ __attribute__((noinline)) bool plan_pair(const Node* nodes, int K, const double2* __restrict__ pairs, int n_points,
                                                     double span, double kj, double cX, double cY2, bool grade,
                                                     unsigned* rec) {
@@ -2739,11 +2802,11 @@ __device__ __attribute__((noinline)) bool plan_pair(const Node* nodes, int K, co
 // sum requires - X mode, fast tier, whole pairs of PRHF_TOP3_MIN_POINTS .. 65535 points on the reference's stretch
 // (header word 0) - with heights settled per thread and a uniform altitude grid.  Counts, once per workgroup, the
 // main-loop pairs that got a plan and those that will plan themselves (no room, guess not bracketing).
-template <int TIER, int THREADS, bool G>
+template <int TIER, int THREADS, bool G, int TEAM = THREADS>
 __device__ __forceinline__ PlanRoom plan_pairs(const KArgs& a, const SegDev& sg, const Node* nodes, double* pf2, double* gb,
                                                unsigned short* hint, const unsigned short* cand, const BlockInfo& info,
                                                int block_in_prof, int blocks_per_prof, unsigned* plan_cnt) {
-    constexpr int W = THREADS / 64;
+    constexpr int W = THREADS / 64;            // (the numbering of the items: the workgroup's, whatever the team)
     PlanRoom room;
     room.base0 = room.base1 = room.base2 = 0u;
     room.cap0 = room.cap01 = room.total = 0;
@@ -2768,7 +2831,7 @@ __device__ __forceinline__ PlanRoom plan_pairs(const KArgs& a, const SegDev& sg,
     if (a.plan_cap > 0) room.total = min(room.total, a.plan_cap);
     const int first_item = block_in_prof * W, round_items = blocks_per_prof * W;
     int n_planned = 0, n_self = 0;
-    for (int u = threadIdx.x;; u += THREADS) {
+    for (int u = team_tid<TEAM, THREADS>();; u += TEAM) {
         const int t = (u / W) * round_items + first_item + (u % W);
         if (t >= info.n_cand) break;
         const double span = info.heights[t] - info.a0;
@@ -2782,7 +2845,7 @@ __device__ __forceinline__ PlanRoom plan_pairs(const KArgs& a, const SegDev& sg,
                                                             : reinterpret_cast<unsigned*>(pf2 + used) + kWords * (u - room.cap01));
             if (main_loop) {
                 const double* row = a.ftab + 8 * (long long)cand[t];
-                done = plan_pair(nodes, info.K, pairs, sg.n_points, span, kj, row[2], row[3], sg.strided_grade != 0, rec);
+                done = plan_pair<TEAM == THREADS ? 0 : 1>(nodes, info.K, pairs, sg.n_points, span, kj, row[2], row[3], sg.strided_grade != 0, rec);
             }
             if (!done) rec[3] = 0u;
         }
@@ -2792,8 +2855,8 @@ __device__ __forceinline__ PlanRoom plan_pairs(const KArgs& a, const SegDev& sg,
     }
     if (n_planned) atomicAdd(&plan_cnt[0], (unsigned)n_planned);
     if (n_self) atomicAdd(&plan_cnt[1], (unsigned)n_self);
-    __syncthreads();
-    if (threadIdx.x == 0 && a.plan_counters) {
+    team_sync<TEAM, THREADS>();
+    if (team_tid<TEAM, THREADS>() == 0 && a.plan_counters) {
         if (plan_cnt[0]) atomicAdd(&a.plan_counters[0], (unsigned long long)plan_cnt[0]);
         if (plan_cnt[1]) atomicAdd(&a.plan_counters[1], (unsigned long long)plan_cnt[1]);
     }
@@ -2984,6 +3047,7 @@ __device__ __forceinline__ unsigned long long run_block(const KArgs& a, const Se
     // (every thread of the workgroup takes the same branches up to here: the pass has a barrier of its own)
     const PlanRoom room = plan_pairs<TIER, THREADS, G>(a, sg, nodes, pf2, gb, hint, cand, info, block_in_prof, blocks_per_prof,
                                                        plan_cnt);
+    PRHF_MARK(3);
     if (sg.mode == PRHF_KMODE_O)
         run_items<PRHF_KMODE_O, TIER, THREADS, G>(a, sg, nodes, pf2, gb, hint, cand, info, prof_local, block_in_prof,
                                                blocks_per_prof, item_next, red, room);
@@ -3097,13 +3161,15 @@ __device__ __forceinline__ void vfo_kernel_body(const KArgs& a) {
         (void)t_staged;
 #ifdef PRHF_TRACE
         if (a.trace && (threadIdx.x & 63) == 0) {
-            unsigned long long* t = a.trace + (bid * (THREADS / 64) + (threadIdx.x >> 6)) * 6;
+            unsigned long long* t = a.trace + (bid * (THREADS / 64) + (threadIdx.x >> 6)) * 8;
             t[0] = t_start;
-            t[1] = wall_clock64();
-            t[2] = t_staged;
+            t[1] = wall_clock64();             // (this wave's arrival at the end-of-block barrier)
+            t[2] = t_staged;                   // candidate list made
             t[3] = trace_marks()[0];           // argmax known; [4] nodes staged; [5] running maximum done
             t[4] = trace_marks()[1];
             t[5] = trace_marks()[2];
+            t[6] = trace_marks()[3];           // pairs planned
+            t[7] = blockIdx.x;                 // the workgroup: its blocks in order of start give the queue's turnaround
         }
 #endif
         if (a.queue == nullptr) break;
@@ -3124,6 +3190,237 @@ __global__ __launch_bounds__(THREADS, PRHF_MIN_WAVES_PER_SIMD) void vfo_kernel(c
 template <int THREADS>
 __global__ __launch_bounds__(THREADS, PRHF_MIN_WAVES_PER_SIMD) void vfo_tall_kernel(const KArgs a) {
     vfo_kernel_body<2, THREADS, true>(a);
+}
+
+// ---- The streaming form of the persistent launch (option stream_blocks) ---------------------------------
+// One workgroup of sixteen waves per CU and two slots of LDS, each what lds_bytes_for describes.  The waves sum the
+// pairs of the profile in one slot while ONE wave - the last to leave the other slot - stages the next profile there,
+// alone: no wave waits at a barrier for the slowest one, none stands by while a profile is staged.  No __syncthreads
+// behind the start-up.  The hand-offs are inside one workgroup (LDS words, workgroup-scope release / acquire), so
+// nothing depends on which workgroups are resident.
+struct SlotHeader {
+    int state;                 // the generation that is ready (a wave's n-th visit of the slot needs state >= n);
+                               // kSlotFinished: the queue has no block for that visit, the launch is over
+    int item_next;             // run_items' counter
+    int left;                  // waves that have left the current generation: the sixteenth stages the next one
+    unsigned plan_cnt[2];      // plan_pairs' counts
+    int cand_count[2];         // list_candidates' count (one wave)
+    // published by the stager, read by every wave behind its acquire
+    BlockInfo info;
+    PlanRoom room;
+    long long prof_local, bid;
+    int block_in_prof, bpp, prio;
+};
+constexpr int kSlotFinished = 0x7fffffff;
+constexpr int kSlotAbort = -1;
+// A wave polls for a slot at most this long (100 MHz wall clock: four seconds - a block takes milliseconds).  Then it
+// gives the launch up: PRHF_STATUS_STALL, an error return of the call.
+constexpr unsigned long long kStallTicks = 400000000ull;
+
+struct SlotArrays {
+    Node* nodes;
+    double* pf2;
+    double* gb;
+    unsigned short* hint;
+    unsigned short* cand;
+    double* red;
+};
+__device__ __forceinline__ SlotArrays slot_arrays(unsigned char* smem, int slot, int levels) {
+    unsigned char* base = smem + (size_t)slot * lds_bytes_for(levels);
+    SlotArrays s;
+    s.nodes = reinterpret_cast<Node*>(base);
+    s.pf2 = reinterpret_cast<double*>(base + (size_t)(levels + 1) * sizeof(Node));
+    s.gb = s.pf2 + levels;
+    s.hint = reinterpret_cast<unsigned short*>(s.pf2 + 2 * (size_t)levels);
+    s.cand = s.hint + kHintBuckets;
+    s.red = reinterpret_cast<double*>(s.cand + PRHF_MAX_CAND);
+    return s;
+}
+
+// Wait until generation `gen` of the slot is ready (returns it), the launch is over (kSlotFinished) or given up
+// (kSlotAbort).  One lane polls, relaxed; one acquire behind the poll.  Wave-uniform.
+__device__ __forceinline__ int slot_wait(SlotHeader* h, int gen, int* abort_word, unsigned* status) {
+    const int lane = threadIdx.x & 63;
+    const unsigned long long t0 = wall_clock64();
+    for (;;) {
+        int st = 0, ab = 0;
+        if (lane == 0) {
+            st = __hip_atomic_load(&h->state, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            ab = __hip_atomic_load(abort_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+        st = uniform(st);
+        ab = uniform(ab);
+        if (ab) return kSlotAbort;
+        if (st >= gen) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+            return st;
+        }
+        if (wall_clock64() - t0 > kStallTicks) {
+            if (lane == 0) {
+                __hip_atomic_store(abort_word, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                post_status(status, PRHF_STATUS_STALL);
+            }
+            return kSlotAbort;
+        }
+        __builtin_amdgcn_s_sleep(8);
+    }
+}
+
+// One wave stages the block of `ticket` into the slot, alone, and publishes it as generation `gen` - or, past the
+// last block, publishes the end of the launch.  What run_block does in front of run_items, in the team forms of the
+// three staging functions; the item numbering and the place of the kept scalars are the general kernel's (LAYOUT).
+template <int LAYOUT>
+__device__ __forceinline__ void stage_slot(const KArgs& a, const SegDev& sg, SlotHeader* h, const SlotArrays& s, long long ticket,
+                                           int gen, long long resident) {
+    const int lane = threadIdx.x & 63;
+    if (ticket >= a.n_blocks) {
+        if (lane == 0) __hip_atomic_store(&h->state, kSlotFinished, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+        return;
+    }
+    team_mark<64, LAYOUT>(4);
+    // The stager runs above every sum of the CU (which run at 2 at the most): its phases are latency chains of few
+    // instructions, and the waves that poll for this slot wait for them (short_prio's phase rule; measured: -2 %)
+    __builtin_amdgcn_s_setprio(3);
+    long long lb = ticket - sg.block_begin;
+    const long long head_blocks = sg.tail_prof * sg.blocks_per_prof;
+    int bpp = sg.blocks_per_prof;
+    long long prof0 = 0;
+    if (lb >= head_blocks) {                   // the slice's tail: more, shorter blocks per profile
+        lb -= head_blocks;
+        bpp = sg.tail_bpp;
+        prof0 = sg.tail_prof;
+    }
+    const long long prof_local = prof0 + lb / bpp;
+    const int block_in_prof = (int)(lb % bpp);
+    // (vfo_kernel's rule: the blocks of the last three resident rounds rank below everything pulled before them)
+    const long long left = a.n_blocks - ticket;
+    const int prio = left > 3 * resident ? 3 : (left > 2 * resident ? 2 : (left > resident ? 1 : 0));
+    if (lane == 0) {
+        h->item_next = 0;
+        h->plan_cnt[0] = h->plan_cnt[1] = 0u;
+    }
+    const long long p = sg.prof_begin + prof_local;
+    BlockInfo info = stage_profile<1, LAYOUT, 64>(
+        a.den + p * a.prof_stride, a.bmag + p * a.field_stride, a.bpsi + p * a.field_stride,
+        a.alt + p * a.alt_stride, a.freq, (int)a.n_freq, (int)a.n_alt, s.nodes, s.pf2, s.gb, s.hint, s.red, (int)a.lds_levels);
+    team_mark<64, LAYOUT>(1);
+    if (info.nan_b && !info.bad) info.bad = kNanRow;       // (X mode: see stage_profile)
+    info.n_cand = -1;
+    info.heights = nullptr;
+    if (a.ftab && !a.no_candidates && sg.chunks == 1 && a.n_freq <= PRHF_MAX_CAND && !info.bad && info.K > 1) {
+        double* heights = (a.n_freq <= a.lds_levels && a.n_freq <= LAYOUT && sg.thread_scan) ? s.pf2 : nullptr;
+        info.n_cand = list_candidates<LAYOUT, 64>(a, sg, kept_scalars<LAYOUT>(s.red), prof_local * a.n_freq, s.cand,
+                                                  h->cand_count, s.nodes, s.pf2, s.gb, info.K, heights);
+        info.heights = heights;
+    }
+    team_mark<64, LAYOUT>(2);
+    if (lane == 0 && block_in_prof == 0 && info.bad) post_status(a.status, (unsigned)info.bad);
+    const PlanRoom room = plan_pairs<1, LAYOUT, false, 64>(a, sg, s.nodes, s.pf2, s.gb, s.hint, s.cand, info, block_in_prof, bpp,
+                                                           h->plan_cnt);
+    if (lane == 0) {
+        h->info = info;
+        h->room = room;
+        h->prof_local = prof_local;
+        h->bid = ticket;
+        h->block_in_prof = block_in_prof;
+        h->bpp = bpp;
+        h->prio = prio;
+        __hip_atomic_store(&h->state, gen, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+    team_mark<64, LAYOUT>(3);
+#ifdef PRHF_TRACE
+    if (a.trace && lane == 0) {
+        unsigned long long* t = a.trace + (ticket * (blockDim.x / 64) + (threadIdx.x >> 6)) * 8;
+        const unsigned long long* m = trace_marks() + 8 + 8 * (threadIdx.x >> 6);
+        t[3] = m[0]; t[4] = m[1]; t[5] = m[2]; t[6] = m[3]; t[7] = m[4];
+    }
+#endif
+}
+
+template <int THREADS>
+__global__ __launch_bounds__(THREADS, PRHF_MIN_WAVES_PER_SIMD) void vfo_stream_kernel(const KArgs a) {
+    constexpr int LAYOUT = PRHF_BLOCK_THREADS, W = THREADS / 64;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    __shared__ SlotHeader hdr[2];
+    __shared__ int abort_word;
+    const int lane = threadIdx.x & 63, wave = uniform((int)(threadIdx.x >> 6));
+    const int levels = (int)a.lds_levels;
+    const SegDev& sg = a.seg[0];
+    const long long resident = 2 * (long long)gridDim.x;       // block slots of the launch: the rounds of the priority rule
+    if (threadIdx.x < 2) {
+        hdr[threadIdx.x].state = 0;
+        hdr[threadIdx.x].left = 0;
+    }
+    if (threadIdx.x == 0) abort_word = 0;
+    __syncthreads();                           // the only one: from here on the waves meet at the slots' words
+    // waves 0 and 1 stage the first two blocks (tickets blockIdx.x and gridDim.x + blockIdx.x: the first resident round
+    // in index order, as the general kernel's); the queue hands out the tickets behind them
+    if (wave < 2) stage_slot<LAYOUT>(a, sg, &hdr[wave], slot_arrays(smem, wave, levels), (long long)blockIdx.x + wave * (long long)gridDim.x,
+                                     1, resident);
+    for (int visit = 0;; ++visit) {
+        const int slot = visit & 1, gen = (visit >> 1) + 1;
+        SlotHeader* h = &hdr[slot];
+#ifdef PRHF_TRACE
+        const unsigned long long t_arrive = wall_clock64();
+#endif
+        const int st = slot_wait(h, gen, &abort_word, a.status);
+        if (st == kSlotFinished || st == kSlotAbort) break;    // every wave leaves through this one uniform test
+#ifdef PRHF_TRACE
+        const unsigned long long t_ready = wall_clock64();
+#endif
+        const SlotArrays s = slot_arrays(smem, slot, levels);
+        BlockInfo info;
+        info.K = uniform(h->info.K);
+        info.bad = uniform(h->info.bad);
+        info.unmag = uniform(h->info.unmag);
+        info.uniform = uniform(h->info.uniform);
+        info.poly_angle = uniform(h->info.poly_angle);
+        info.n_cand = uniform(h->info.n_cand);
+        info.nan_b = uniform(h->info.nan_b);
+        info.nan_p = uniform(h->info.nan_p);
+        info.heights = uniform(h->info.heights != nullptr ? 1 : 0) ? s.pf2 : nullptr;      // (X mode: where f_N^2 lived)
+        info.a0 = uniform(h->info.a0);
+        info.inv_w = uniform(h->info.inv_w);
+        info.inv_step = uniform(h->info.inv_step);
+        PlanRoom room;
+        room.base0 = (unsigned)uniform((int)h->room.base0);
+        room.base1 = (unsigned)uniform((int)h->room.base1);
+        room.base2 = (unsigned)uniform((int)h->room.base2);
+        room.cap0 = uniform(h->room.cap0);
+        room.cap01 = uniform(h->room.cap01);
+        room.total = uniform(h->room.total);
+        const int block_in_prof = uniform(h->block_in_prof), bpp = uniform(h->bpp), prio = uniform(h->prio);
+        const long long prof_local = ((long long)uniform((int)(h->prof_local >> 32)) << 32) |
+                                     (unsigned)uniform((int)(h->prof_local & 0xffffffffLL));
+        // (the sums leave the highest priority to the stagers: the blocks of the third round from the end rank with the
+        //  ones before them, the last two rounds below, as in the general kernel)
+        if (prio >= 2) __builtin_amdgcn_s_setprio(2);
+        else if (prio == 1) __builtin_amdgcn_s_setprio(1);
+        else __builtin_amdgcn_s_setprio(0);
+        run_items<PRHF_KMODE_X, 1, LAYOUT, false>(a, sg, s.nodes, s.pf2, s.gb, s.hint, s.cand, info, prof_local, block_in_prof, bpp,
+                                                  &h->item_next, s.red, room);
+#ifdef PRHF_TRACE
+        if (a.trace && lane == 0) {
+            const long long bid = h->bid;
+            unsigned long long* t = a.trace + (bid * W + wave) * 8;
+            t[0] = t_arrive;
+            t[1] = wall_clock64();
+            t[2] = t_ready;
+        }
+#endif
+        // leave: this wave's reads of the slot are done (release); the sixteenth to leave sees every wave's (acquire)
+        int n_left = 0;
+        if (lane == 0) n_left = __hip_atomic_fetch_add(&h->left, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (uniform(n_left) == W - 1) {
+            long long ticket = 0;
+            if (lane == 0) {
+                h->left = 0;
+                ticket = resident + (long long)atomicAdd(a.queue, 1u);
+            }
+            ticket = (long long)(unsigned)uniform((int)ticket);        // (blocks < 2^31)
+            stage_slot<LAYOUT>(a, sg, h, s, ticket, gen + 1, resident);
+        }
+    }
 }
 
 // Pair table of the fast tier's main loop: (m_i, m_i+1 - m_i) side by side, one 16-byte load per
@@ -3712,6 +4009,16 @@ hipError_t launch_vfo_shortx(const KArgs& a, long long grid_blocks, size_t lds_b
 #include "prhf_gradient_skip.inc"
 #include "prhf_vjp.inc"
 
+// The streaming form: `grid_blocks` workgroups of PRHF_STREAM_THREADS with two slots of lds_bytes_for(a.lds_levels) each;
+// a.queue set, one slice, X mode, fast tier (plan_launch decides)
+hipError_t launch_vfo_stream(const KArgs& a, long long grid_blocks, hipStream_t stream) {
+    if (grid_blocks <= 0 || a.n_blocks <= 0) return hipSuccess;
+    if (!a.queue || a.n_segs != 1 || a.block_list || a.seg[0].slots != 0 || a.seg[0].chunks != 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((vfo_stream_kernel<PRHF_STREAM_THREADS>), dim3((unsigned)grid_blocks), dim3(PRHF_STREAM_THREADS),
+                       2 * lds_bytes_for(a.lds_levels), stream, a);
+    return hipGetLastError();
+}
+
 // Resident workgroups per CU the runtime predicts for the fused kernel (diagnostics).
 hipError_t query_occupancy(int tier, size_t lds_bytes, int* blocks_per_cu) {
     constexpr int THREADS = PRHF_BLOCK_THREADS;
@@ -3722,7 +4029,13 @@ hipError_t query_occupancy(int tier, size_t lds_bytes, int* blocks_per_cu) {
     return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, vfo_kernel<2, THREADS>, THREADS, lds_bytes);
 }
 
-hipError_t configure_kernels(size_t max_lds_bytes) {
+hipError_t configure_kernels(size_t max_lds_bytes, size_t max_stream_lds_bytes) {
+    {
+        // (the streaming form's one workgroup per CU holds two slots: up to all of a CU's LDS but its static words)
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&vfo_stream_kernel<PRHF_STREAM_THREADS>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)max_stream_lds_bytes);
+        if (e != hipSuccess) return e;
+    }
     constexpr int THREADS = PRHF_BLOCK_THREADS;
     const void* kernels[] = {reinterpret_cast<const void*>(&vfo_kernel<0, THREADS>),
                              reinterpret_cast<const void*>(&vfo_kernel<1, THREADS>),

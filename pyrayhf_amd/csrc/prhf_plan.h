@@ -112,6 +112,14 @@ struct Knobs {
                                        // pair's wave (0: the launch of before, bit for bit; values never
                                        // depend on it)
     double pair_plan_cap = 0;          // > 0: a workgroup keeps at most this many plans, the other pairs plan themselves (tests)
+    double stream_blocks = 1;          // a persistent launch of one X-mode fast-tier slice whose workgroups settle reflection
+                                       // heights per thread (what slice_plans_pairs asks of the shape) and whose staged
+                                       // profile fits half of a CU's LDS takes the streaming form: one 16-wave workgroup
+                                       // per CU with two slots, the next profile staged by one wave beside the sums of the
+                                       // current one, no barrier per profile (vfo_stream_kernel).  0: the
+                                       // launch of before, instruction for instruction; 2: also a launch of fewer blocks
+                                       // than resident slots (tests).  Values never depend on it
+    double stream_grid = 0;            // > 0: the streaming form launches at most this many workgroups (tests, A/B runs)
 };
 struct KnobName {
     const char* name;
@@ -152,6 +160,8 @@ const KnobName kKnobNames[] = {
     {"strided_grade", &Knobs::strided_grade, 0, 1},
     {"pair_plan", &Knobs::pair_plan, 0, 1},
     {"pair_plan_cap", &Knobs::pair_plan_cap, 0, 1024},
+    {"stream_blocks", &Knobs::stream_blocks, 0, 2},
+    {"stream_grid", &Knobs::stream_grid, 0, 65536},
 };
 constexpr int kWavesPerBlock = PRHF_BLOCK_THREADS / 64;
 
@@ -390,6 +400,12 @@ struct LaunchPlan {
     bool short_order;         // ... by short_order_kernel, which sorts the short-grid O launch's blocks by cost as well
     bool zero_queues;         // without that table: the queue words are zeroed by a memset
     bool forked;              // short-grid launches on the second stream, beside the general launch
+    bool stream;              // the general launch takes the streaming form (vfo_stream_kernel; option stream_blocks):
+    long long stream_grid;    // ... this many workgroups of PRHF_STREAM_THREADS, which pull their blocks from kWordGeneral,
+    size_t stream_lds_bytes;  // ... with two slots of lds_bytes each,
+    long long stream_blocks;  // ... over this many blocks: the slice's, with its tail cut into
+    int stream_tail_bpp;      // ... this many blocks per profile (seg[0].tail_bpp and `blocks` stay the general kernel's)
+    long long stream_tail_prof;
     prhf::StridedPieces pieces;
     prhf::SegDev seg[PRHF_MAX_SEGMENTS];
     ShortKind o, x;
@@ -591,6 +607,43 @@ inline int plan_launch(const LaunchShape& sh, const prhf_segment* segs, int32_t 
             s.strided_grade = kn.strided_grade != 0;
             s.pair_plan = slice_plans_pairs(s, tall, n_freq, lds_levels, kn) ? 1 : 0;
             pl.any_plan = pl.any_plan || s.pair_plan != 0;
+        }
+    }
+    // The streaming form (option stream_blocks): the launch is one slice, alone on the device - no
+    // short-grid launch beside it - and persistent today (option 2: or would be with more blocks); the slice is what
+    // slice_plans_pairs asks for, whatever option pair_plan says (without plans every pair plans itself, as in the
+    // general kernel); two slots fit one workgroup's LDS.  One workgroup per CU; a launch of few blocks, fewer.
+    pl.stream = false;
+    pl.stream_grid = 0;
+    pl.stream_lds_bytes = 0;
+    pl.stream_blocks = 0;
+    pl.stream_tail_bpp = 0;
+    pl.stream_tail_prof = 0;
+    if (kn.stream_blocks != 0 && kPersistent && !tall && pl.n_segs == 1 && pl.o.n_segs == 0 && pl.x.n_segs == 0 && pl.blocks > 0 &&
+        (pl.queue || kn.stream_blocks == 2) && 2 * pl.lds_bytes <= kLdsFull) {
+        Knobs with_plans = kn;
+        with_plans.pair_plan = 1;
+        if (slice_plans_pairs(pl.seg[0], tall, n_freq, lds_levels, with_plans)) {
+            pl.stream = true;
+            pl.queue = true;                   // (the queue word is zeroed and handed to the kernel)
+            // The tail (plan_slice): a block of this form is summed by sixteen waves, not eight, and staged by ONE wave,
+            // which takes three times as long as eight do.  Pieces of the general kernel's duration are half as many per
+            // profile: with tail_bpp = 4 as it stands the CU's one stager was what the last round waited for (+3 %
+            // against the general kernel), with 2 the form gains (profiles/ab_stream_blocks.txt).
+            const prhf::SegDev& s = pl.seg[0];
+            const long long P = s.prof_end - s.prof_begin;
+            pl.stream_blocks = pl.blocks;
+            pl.stream_tail_bpp = s.tail_bpp;
+            pl.stream_tail_prof = s.tail_prof;
+            if (s.tail_prof < P && s.tail_bpp > s.blocks_per_prof) {
+                const int bpp = std::max(s.blocks_per_prof, s.tail_bpp / (PRHF_STREAM_THREADS / PRHF_BLOCK_THREADS));
+                pl.stream_blocks -= (P - s.tail_prof) * (s.tail_bpp - bpp);
+                pl.stream_tail_bpp = bpp;
+                if (bpp == s.blocks_per_prof) pl.stream_tail_prof = P;
+            }
+            pl.stream_lds_bytes = 2 * pl.lds_bytes;
+            pl.stream_grid = std::min<long long>(sh.cu_count, (pl.stream_blocks + 1) / 2);
+            if (kn.stream_grid > 0) pl.stream_grid = std::min(pl.stream_grid, (long long)kn.stream_grid);
         }
     }
     // per-frequency scalars: long launches read them from a table instead of dividing once per pair (a short

@@ -11,7 +11,7 @@ alt, den, bmag, bpsi = synth.chapman_profiles(10000, 20260003)
 t = [torch.as_tensor(x, device=dev) for x in (synth.sounder_frequencies(3), den, bmag, bpsi, alt)]
 for _ in range(2):
     library.vertical_forward_operator(*t, "O", 200)
-w = np.fromfile(path, dtype=np.uint64).reshape(-1, 8, 6).astype(np.float64) / 100.0  # us: start, end, staged
+w = np.fromfile(path, dtype=np.uint64).reshape(-1, 8, 8).astype(np.float64) / 100.0  # us: start, end, staged
 t0 = w[:, :, 0].min()
 start, end, staged = w[:, :, 0] - t0, w[:, :, 1] - t0, w[:, :, 2] - t0
 life = end.max(axis=1) - start.min(axis=1)

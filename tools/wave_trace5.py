@@ -14,7 +14,7 @@ alt, den, bmag, bpsi = synth.chapman_profiles(50000, 20260005, rows=rows)
 t = [torch.as_tensor(x, device=dev) for x in (synth.sounder_frequencies(5), den, bmag, bpsi, alt)]
 for _ in range(2):
     library.vertical_forward_operator_mixed(*t, local)
-w = np.fromfile(path, dtype=np.uint64).reshape(-1, 8, 6).astype(np.float64) / 100.0
+w = np.fromfile(path, dtype=np.uint64).reshape(-1, 8, 8).astype(np.float64) / 100.0
 w = w[w[:, :, 1].max(axis=1) > 0]
 t0 = w[:, :, 0].min()
 start, end = w[:, :, 0] - t0, w[:, :, 1] - t0
@@ -32,7 +32,7 @@ print("resident workgroups per 1/40 of the launch:", [round(x) for x in res])
 waves = [(np.minimum(end, b) - np.maximum(start, a)).clip(0).sum() / (b - a) for a, b in zip(edges[:-1], edges[1:])]
 print("busy waves per 1/40 of the launch:", [round(x) for x in waves])
 order = np.argsort(-life)[:12]
-keep = np.flatnonzero(np.fromfile(path, dtype=np.uint64).reshape(-1, 8, 6)[:, :, 1].max(axis=1) > 0)
+keep = np.flatnonzero(np.fromfile(path, dtype=np.uint64).reshape(-1, 8, 8)[:, :, 1].max(axis=1) > 0)
 print("longest blocks (block index, start us, life us):", [(int(keep[i]), round(float(wg_start[i])), round(float(life[i]))) for i in order])
 by_bid = {int(keep[i]): (round(float(wg_start[i])), round(float(life[i]))) for i in range(len(keep))}
 print("blocks 0..1200 every 24th (index: start us, life us):", {b: by_bid.get(b) for b in range(0, 1200, 24)})

@@ -302,6 +302,42 @@ int prhf_vfo_vjp_f64(prhf_ctx* ctx,
                      const double* grad_vh, double* vh_out, double* grad_den_out, uint32_t flags);
 
 /*
+ * The Jacobian-vector product of the same derivative - the tangent-linear operator, H dx of data assimilation, what
+ * forward-mode differentiation needs:  dvh_out[p, f, t] = sum_k (d vh[p, f] / d den[p, k]) * tangents[p, t, k]  for n_tan
+ * directions per profile, without forming the Jacobian: what is written is n_prof * n_freq * n_tan doubles.  The matrix
+ * is exactly the one prhf_vfo_jacobian_f64 returns, with its conventions; the product is formed per grid point (the
+ * node's total dX along the tangent - interpolated tangent plus the node's motion with the reflection height - before
+ * it meets d mu'/dX), so it agrees with jac_out times the tangent to rounding, not bit for bit.
+ *
+ * Arguments as prhf_vfo_vjp_f64, with: tangents, n_tan rows of n_alt doubles per profile; tan_prof_stride_elems, the
+ * distance between two profiles' sets in doubles (>= n_tan * n_alt), or 0 for ONE set (n_tan, n_alt) applied to every
+ * profile; vh_out (n_prof, n_freq), may be NULL - when given it is written by the operator's own launch and equals
+ * prhf_vfo_batch_f64's output bit for bit; dvh_out (n_prof, n_freq, n_tan), row-major.  Flags as for the VJP.
+ * n_tan == 0 is PRHF_OK and writes nothing to dvh_out (vh_out, when given, is still written).
+ *
+ * Conventions, beyond those of the Jacobian:
+ *   - a pair that has no virtual height has dvh = 0 for every tangent, as its Jacobian row is zero: the adjoint identity
+ *     sum_f g_f dvh_f = sum_k (J^T g)_k t_k holds exactly there;
+ *   - tangent entries at levels k >= argmax den are not read, so a NaN there does no harm;
+ *   - at a kink of the operator the result is one of the one-sided derivatives, the one the Jacobian gives.
+ * The bits of dvh_out[p, f, t] depend on profile p, the frequency, n_points, mode and tangent t only: not on n_tan, on the
+ * other tangents, profiles or frequencies of the call, or on repetition.  No atomics.
+ * Tangents go through the kernel eight at a time - one launch per eight, the rest in a last one - while the bottomside
+ * and eight tangent columns fit in LDS (908 levels up to the highest density peak of the call), four, two or one at a
+ * time above that.  Limit: 1332 levels up to the peak (n_alt itself may be larger: the peak pre-pass, one
+ * synchronisation); a taller bottomside is refused with PRHF_EINVAL ("the JVP stages at most 1332 levels ...").
+ */
+int prhf_vfo_jvp_f64(prhf_ctx* ctx,
+                     const double* freq_mhz, int64_t n_freq,
+                     const double* den, const double* bmag, const double* bpsi,
+                     const double* alt,
+                     int64_t n_prof, int64_t n_alt,
+                     int64_t prof_stride_elems, int64_t alt_stride_elems,
+                     const double* multiplier, int32_t n_points, int32_t mode,
+                     const double* tangents, int64_t n_tan, int64_t tan_prof_stride_elems,
+                     double* vh_out, double* dvh_out, uint32_t flags);
+
+/*
  * Appleton-Hartree phase index mu and group index mu' on flat arrays of n elements.
  * Replaces: find_mu_mup (reference library.py:161-256); psi_deg in degrees.  As in the reference,
  * the isotropic formulas are used when max|Y| over the whole array is below 1e-12 (:201-207).

@@ -56,6 +56,11 @@ _PROTOTYPES = {
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
         ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
         ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32]),
+    "prhf_vfo_jvp_f64": (ctypes.c_int, [
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
+        ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_uint32]),
     "prhf_vfo_worklist_f64": (ctypes.c_int, [
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
         ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
@@ -320,6 +325,13 @@ class Context:
         """sum_f grad_vh * d vh / d den; ``vh_out`` may be None."""
         return self._lib.prhf_vfo_vjp_f64(self._h, freq, n_freq, den, bmag, bpsi, alt, n_prof, n_alt, prof_stride,
                                           alt_stride, mult, n_points, mode, grad_vh, vh_out, grad_den_out, flags)
+
+    def vfo_jvp(self, freq, n_freq, den, bmag, bpsi, alt, n_prof, n_alt, prof_stride, alt_stride,
+                mult, n_points, mode, tangents, n_tan, tan_prof_stride, vh_out, dvh_out, flags):
+        """sum_k d vh / d den_k * tangent_k for ``n_tan`` tangents; ``vh_out`` may be None."""
+        return self._lib.prhf_vfo_jvp_f64(self._h, freq, n_freq, den, bmag, bpsi, alt, n_prof, n_alt, prof_stride,
+                                          alt_stride, mult, n_points, mode, tangents, n_tan, tan_prof_stride, vh_out,
+                                          dvh_out, flags)
 
     def vfo_worklist(self, freq, n_freq, den, bmag, bpsi, alt, n_prof, n_alt, prof_stride, alt_stride,
                      mult, mult_len, segments, out, flags):

@@ -1165,14 +1165,12 @@ int prhf_vfo_worklist_f64(prhf_ctx* ctx, const double* freq_mhz, int64_t n_freq,
 
 namespace {
 
-// prhf_vfo_jacobian_f64 / prhf_vfo_vjp_f64: check, find the levels to stage, plan (plan_vjp, prhf_plan.h), stage host
-// buffers, launch.  vh_out comes from the operator's own launch on the same arguments.
-int vjp_run(prhf_ctx* c, const double* freq, int64_t n_freq, const double* den, const double* bmag, const double* bpsi,
-            const double* alt, int64_t n_prof, int64_t n_alt, int64_t prof_stride, int64_t alt_stride, const double* mult,
-            int32_t n_points, int32_t mode, const double* grad_vh, double* vh_out, double* out, bool jacobian, uint32_t flags) {
+// What the derivative entry points (Jacobian, VJP, JVP) check alike; others_given: the arrays of their own are there
+int derivative_check(prhf_ctx* c, const double* freq, int64_t n_freq, const double* den, const double* bmag, const double* bpsi,
+                     const double* alt, int64_t n_prof, int64_t n_alt, int64_t prof_stride, int64_t alt_stride, const double* mult,
+                     int32_t n_points, int32_t mode, bool others_given, uint32_t flags) {
     if (!c) return fail(PRHF_EINVAL, "null context");
-    if (!freq || !den || !bmag || !bpsi || !alt || !mult || !out || (!jacobian && !grad_vh))
-        return fail(PRHF_EINVAL, "null array pointer");
+    if (!freq || !den || !bmag || !bpsi || !alt || !mult || !others_given) return fail(PRHF_EINVAL, "null array pointer");
     if (n_freq < 1 || n_prof < 0 || n_alt < 1 || n_points < 1) return fail(PRHF_EINVAL, "bad shape");
     if (n_alt > kMaxAltTall) return fail(PRHF_EINVAL, "n_alt %lld exceeds the limit of %lld levels", (long long)n_alt, kMaxAltTall);
     if (n_freq > (1 << 20)) return fail(PRHF_EINVAL, "n_freq too large");
@@ -1180,12 +1178,51 @@ int vjp_run(prhf_ctx* c, const double* freq, int64_t n_freq, const double* den, 
     if (mode != PRHF_MODE_O && mode != PRHF_MODE_X) return fail(PRHF_EINVAL, "mode must be 'O' or 'X'");
     if (flags & ~(PRHF_FLAG_DEVICE_PTRS | PRHF_FLAG_ASYNC | PRHF_FLAG_GRID_STABLE | PRHF_FLAG_SHARED_FIELD))
         return fail(PRHF_EINVAL, "unknown flag bits");
-    const bool dev = (flags & PRHF_FLAG_DEVICE_PTRS) != 0, shared_field = (flags & PRHF_FLAG_SHARED_FIELD) != 0;
+    const bool dev = (flags & PRHF_FLAG_DEVICE_PTRS) != 0;
     if ((flags & PRHF_FLAG_ASYNC) && !dev) return fail(PRHF_EINVAL, "PRHF_FLAG_ASYNC needs device pointers");
     if (!dev)
         for (int64_t i = 1; i < n_points; ++i)
             if (mult[i] < mult[i - 1])
                 return fail(PRHF_EINVAL, "multiplier[%lld] decreases: the stretched grid must be non-decreasing", (long long)i);
+    return PRHF_OK;
+}
+
+// The highest density peak of the launch (np.argmax's rule, the first NaN ranking highest): a host scan, or the peak
+// pre-pass and one synchronisation.  The caller has entered the device.
+int highest_peak(prhf_ctx* c, const double* den, int64_t n_prof, int64_t n_alt, int64_t prof_stride, bool dev, long long* out) {
+    long long max_peak = 0;
+    if (dev) {
+        HIP_TRY(hipMemsetAsync(c->d_status + kWordPeak, 0, sizeof(unsigned), c->stream));
+        HIP_TRY(prhf::launch_peak_levels(den, n_prof, n_alt, prof_stride, c->d_status + kWordPeak, c->stream));
+        unsigned peak = 0;
+        HIP_TRY(hipMemcpyAsync(&peak, c->d_status + kWordPeak, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        max_peak = peak;
+    } else {
+        for (int64_t p = 0; p < n_prof; ++p) {
+            const double* d = den + (size_t)p * prof_stride;
+            double bv = -HUGE_VAL;
+            long long bi = 0;
+            for (int64_t i = 0; i < n_alt; ++i) {
+                const double key = (d[i] != d[i]) ? HUGE_VAL : d[i];
+                if (key > bv) { bv = key; bi = i; }
+            }
+            max_peak = std::max(max_peak, bi);
+        }
+    }
+    *out = max_peak;
+    return PRHF_OK;
+}
+
+// prhf_vfo_jacobian_f64 / prhf_vfo_vjp_f64: check, find the levels to stage, plan (plan_vjp, prhf_plan.h), stage host
+// buffers, launch.  vh_out comes from the operator's own launch on the same arguments.
+int vjp_run(prhf_ctx* c, const double* freq, int64_t n_freq, const double* den, const double* bmag, const double* bpsi,
+            const double* alt, int64_t n_prof, int64_t n_alt, int64_t prof_stride, int64_t alt_stride, const double* mult,
+            int32_t n_points, int32_t mode, const double* grad_vh, double* vh_out, double* out, bool jacobian, uint32_t flags) {
+    int rc = derivative_check(c, freq, n_freq, den, bmag, bpsi, alt, n_prof, n_alt, prof_stride, alt_stride, mult, n_points, mode,
+                              out && (jacobian || grad_vh), flags);
+    if (rc != PRHF_OK) return rc;
+    const bool dev = (flags & PRHF_FLAG_DEVICE_PTRS) != 0, shared_field = (flags & PRHF_FLAG_SHARED_FIELD) != 0;
     ENTER_DEVICE(c->device);
     // Levels to stage: the whole column where LDS holds it; else up to the highest density peak of the launch
     // (np.argmax's rule, the first NaN ranking highest: a host scan, or the peak pre-pass and one synchronisation)
@@ -1194,29 +1231,10 @@ int vjp_run(prhf_ctx* c, const double* freq, int64_t n_freq, const double* den, 
     long long levels = n_alt;
     if (plan_vjp(n_prof, n_freq, levels, jacobian, pl, why, sizeof why) != PRHF_OK && n_prof > 0) {
         long long max_peak = 0;
-        if (dev) {
-            HIP_TRY(hipMemsetAsync(c->d_status + kWordPeak, 0, sizeof(unsigned), c->stream));
-            HIP_TRY(prhf::launch_peak_levels(den, n_prof, n_alt, prof_stride, c->d_status + kWordPeak, c->stream));
-            unsigned peak = 0;
-            HIP_TRY(hipMemcpyAsync(&peak, c->d_status + kWordPeak, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            max_peak = peak;
-        } else {
-            for (int64_t p = 0; p < n_prof; ++p) {
-                const double* d = den + (size_t)p * prof_stride;
-                double bv = -HUGE_VAL;
-                long long bi = 0;
-                for (int64_t i = 0; i < n_alt; ++i) {
-                    const double key = (d[i] != d[i]) ? HUGE_VAL : d[i];
-                    if (key > bv) { bv = key; bi = i; }
-                }
-                max_peak = std::max(max_peak, bi);
-            }
-        }
+        if ((rc = highest_peak(c, den, n_prof, n_alt, prof_stride, dev, &max_peak)) != PRHF_OK) return rc;
         levels = max_peak + 1;
         if (plan_vjp(n_prof, n_freq, levels, jacobian, pl, why, sizeof why) != PRHF_OK) return fail(PRHF_EINVAL, "%s", why);
     }
-    int rc;
     if (vh_out) {
         rc = prhf_vfo_batch_f64(c, freq, n_freq, den, bmag, bpsi, alt, n_prof, n_alt, prof_stride, alt_stride, mult, n_points,
                                 mode, vh_out, flags);
@@ -1292,6 +1310,110 @@ int prhf_vfo_vjp_f64(prhf_ctx* ctx, const double* freq_mhz, int64_t n_freq, cons
                      double* vh_out, double* grad_den_out, uint32_t flags) {
     return vjp_run(ctx, freq_mhz, n_freq, den, bmag, bpsi, alt, n_prof, n_alt, prof_stride_elems, alt_stride_elems, multiplier,
                    n_points, mode, grad_vh, vh_out, grad_den_out, false, flags);
+}
+
+namespace {
+
+// prhf_vfo_jvp_f64: check, find the levels to stage, plan (plan_jvp, prhf_plan.h), stage host buffers, then one launch
+// per chunk of tangents.  vh_out comes from the operator's own launch on the same arguments.
+int jvp_run(prhf_ctx* c, const double* freq, int64_t n_freq, const double* den, const double* bmag, const double* bpsi,
+            const double* alt, int64_t n_prof, int64_t n_alt, int64_t prof_stride, int64_t alt_stride, const double* mult,
+            int32_t n_points, int32_t mode, const double* tangents, int64_t n_tan, int64_t tan_stride, double* vh_out,
+            double* out, uint32_t flags) {
+    int rc = derivative_check(c, freq, n_freq, den, bmag, bpsi, alt, n_prof, n_alt, prof_stride, alt_stride, mult, n_points, mode,
+                              n_tan <= 0 || (tangents && out), flags);
+    if (rc != PRHF_OK) return rc;
+    if (n_tan < 0 || n_tan > (1 << 20)) return fail(PRHF_EINVAL, "bad number of tangents");
+    if (tan_stride != 0 && tan_stride < n_tan * n_alt) return fail(PRHF_EINVAL, "tangent stride shorter than a profile's tangents");
+    const bool dev = (flags & PRHF_FLAG_DEVICE_PTRS) != 0, shared_field = (flags & PRHF_FLAG_SHARED_FIELD) != 0;
+    ENTER_DEVICE(c->device);
+    // Levels to stage: as vjp_run
+    JvpPlan pl;
+    char why[256];
+    long long levels = n_alt;
+    if (n_tan > 0 && n_prof > 0 && plan_jvp(n_prof, n_freq, levels, n_tan, pl, why, sizeof why) != PRHF_OK) {
+        long long max_peak = 0;
+        if ((rc = highest_peak(c, den, n_prof, n_alt, prof_stride, dev, &max_peak)) != PRHF_OK) return rc;
+        levels = max_peak + 1;
+        if (plan_jvp(n_prof, n_freq, levels, n_tan, pl, why, sizeof why) != PRHF_OK) return fail(PRHF_EINVAL, "%s", why);
+    }
+    if (vh_out) {
+        rc = prhf_vfo_batch_f64(c, freq, n_freq, den, bmag, bpsi, alt, n_prof, n_alt, prof_stride, alt_stride, mult, n_points,
+                                mode, vh_out, flags);
+        if (rc != PRHF_OK) return rc;
+    }
+    if (n_prof == 0 || n_tan == 0) return PRHF_OK;
+    const size_t out_elems = (size_t)n_prof * (size_t)n_freq * (size_t)n_tan;
+    prhf::JvpArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.n_prof = n_prof; a.n_freq = n_freq; a.n_alt = n_alt; a.lds_levels = levels; a.n_points = n_points;
+    a.mode = mode == PRHF_MODE_O ? PRHF_KMODE_O : PRHF_KMODE_X;
+    a.out_stride = n_tan;
+    a.status = c->h_status_dev;
+    if (dev) {
+        a.freq = freq; a.den = den; a.bmag = bmag; a.bpsi = bpsi; a.alt = alt; a.mult = mult; a.tan = tangents; a.out = out;
+        a.prof_stride = prof_stride;
+        a.field_stride = shared_field ? 0 : prof_stride;
+        a.alt_stride = alt_stride;
+        a.tan_prof_stride = tan_stride;
+    } else {
+        const size_t field_rows = shared_field ? 1 : (size_t)n_prof, alt_rows = alt_stride ? (size_t)n_prof : 1;
+        const size_t tan_sets = tan_stride ? (size_t)n_prof : 1, set_elems = (size_t)n_tan * (size_t)n_alt;
+        const size_t in_elems = (size_t)n_freq + (size_t)n_points + ((size_t)n_prof + 2 * field_rows + alt_rows) * (size_t)n_alt +
+                                tan_sets * set_elems;
+        if ((rc = ensure(c, c->vjp, (in_elems + out_elems) * 8)) != PRHF_OK) return rc;
+        double* d_freq = static_cast<double*>(c->vjp.p);
+        double* d_mult = d_freq + n_freq;
+        double* d_den = d_mult + n_points;
+        double* d_bmag = d_den + (size_t)n_prof * n_alt;
+        double* d_bpsi = d_bmag + field_rows * n_alt;
+        double* d_alt = d_bpsi + field_rows * n_alt;
+        double* d_tan = d_alt + alt_rows * n_alt;
+        double* d_out = d_tan + tan_sets * set_elems;
+        auto up_rows = [&](double* dst, const double* src, size_t row_elems, size_t rows, int64_t stride) {
+            return hipMemcpy2DAsync(dst, row_elems * 8, src, (rows > 1 ? (size_t)stride : row_elems) * 8, row_elems * 8, rows,
+                                    hipMemcpyHostToDevice, c->stream);
+        };
+        HIP_TRY(hipMemcpyAsync(d_freq, freq, (size_t)n_freq * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_mult, mult, (size_t)n_points * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(up_rows(d_den, den, (size_t)n_alt, (size_t)n_prof, prof_stride));
+        HIP_TRY(up_rows(d_bmag, bmag, (size_t)n_alt, field_rows, prof_stride));
+        HIP_TRY(up_rows(d_bpsi, bpsi, (size_t)n_alt, field_rows, prof_stride));
+        HIP_TRY(up_rows(d_alt, alt, (size_t)n_alt, alt_rows, alt_stride));
+        HIP_TRY(up_rows(d_tan, tangents, set_elems, tan_sets, tan_stride));
+        a.freq = d_freq; a.den = d_den; a.bmag = d_bmag; a.bpsi = d_bpsi; a.alt = d_alt; a.mult = d_mult; a.tan = d_tan;
+        a.out = d_out;
+        a.prof_stride = n_alt;
+        a.field_stride = shared_field ? 0 : n_alt;
+        a.alt_stride = alt_stride ? n_alt : 0;
+        a.tan_prof_stride = tan_stride ? (long long)set_elems : 0;
+    }
+    double* const d_out = a.out;
+    const double* const d_tan = a.tan;
+    HIP_TRY(hipEventRecord(c->begin_ev(), c->stream));
+    for (long long i = 0; i < pl.n_chunks; ++i) {
+        const JvpChunk ch = jvp_chunk(pl, n_tan, i);
+        a.tan = d_tan + (size_t)ch.first * (size_t)n_alt;
+        a.out = d_out + ch.first;
+        a.n_tan = ch.count;
+        HIP_TRY(prhf::launch_vfo_jvp(a, ch.nt, pl.threads, ch.lds_bytes, c->stream));
+    }
+    HIP_TRY(hipEventRecord(c->pending_end_ev(), c->stream));
+    c->mark_timed();
+    c->status_pending = true;
+    if (!dev) HIP_TRY(hipMemcpyAsync(out, d_out, out_elems * 8, hipMemcpyDeviceToHost, c->stream));
+    if (flags & PRHF_FLAG_ASYNC) return PRHF_OK;
+    return prhf_sync(c);
+}
+
+}  // namespace
+
+int prhf_vfo_jvp_f64(prhf_ctx* ctx, const double* freq_mhz, int64_t n_freq, const double* den, const double* bmag,
+                     const double* bpsi, const double* alt, int64_t n_prof, int64_t n_alt, int64_t prof_stride_elems,
+                     int64_t alt_stride_elems, const double* multiplier, int32_t n_points, int32_t mode, const double* tangents,
+                     int64_t n_tan, int64_t tan_prof_stride_elems, double* vh_out, double* dvh_out, uint32_t flags) {
+    return jvp_run(ctx, freq_mhz, n_freq, den, bmag, bpsi, alt, n_prof, n_alt, prof_stride_elems, alt_stride_elems, multiplier,
+                   n_points, mode, tangents, n_tan, tan_prof_stride_elems, vh_out, dvh_out, flags);
 }
 
 int prhf_vfo_residual_f64(prhf_ctx* ctx, const double* freq_mhz, int64_t n_freq, const double* den,

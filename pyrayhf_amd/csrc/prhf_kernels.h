@@ -317,6 +317,36 @@ inline size_t vjp_lds_bytes(long long levels, int waves, bool jacobian) {
            (size_t)waves * (jacobian ? 1 : 2) * (size_t)levels * 8;
 }
 hipError_t launch_vfo_vjp(const VjpArgs& a, bool jacobian, size_t lds_bytes, hipStream_t stream);
+// Jacobian-vector product of the operator (prhf_jvp.inc): dvh[p, f, t] = sum_k J[p, f, k] tan[p, t, k] for up to
+// PRHF_JVP_MAX_NT tangents per launch, one workgroup of PRHF_VJP_THREADS or PRHF_JVP_THREADS_WIDE per profile; all pointers
+// are device memory.
+#define PRHF_JVP_MAX_NT 8
+#define PRHF_JVP_THREADS_WIDE 512
+struct JvpArgs {
+    const double* freq;       // MHz, (n_freq)
+    const double* den;
+    const double* bmag;
+    const double* bpsi;
+    const double* alt;
+    const double* mult;       // the stretched grid, (n_points)
+    const double* tan;        // the launch's first tangent: rows of n_alt doubles, tan_prof_stride between profiles (0: shared)
+    double* out;              // the launch's first column of dvh (n_prof, n_freq, out_stride)
+    unsigned* status;
+    long long n_prof, n_freq, n_alt;
+    long long prof_stride, field_stride, alt_stride, tan_prof_stride;
+    long long out_stride;     // tangents of the whole call: doubles between two frequencies in dvh
+    long long lds_levels;     // levels the staged arrays hold (> every bottomside of the launch)
+    int n_points, mode;       // PRHF_KMODE_*
+    int n_tan;                // tangents of this launch, 1 ... NT of the instantiation that runs
+};
+// LDS of one workgroup: the operator's staged profile (without its candidate list), then nt tangent columns of
+// lds_levels doubles.  No per-wave rows: every wave takes frequencies whatever the bottomside's height.
+inline size_t jvp_lds_bytes(long long levels, int nt) {
+    return (size_t)(levels + 1) * PRHF_NODE_BYTES + (size_t)levels * 16 + PRHF_HINT_BUCKETS * 2 + PRHF_RED_DOUBLES * 8 +
+           (size_t)nt * (size_t)levels * 8;
+}
+// nt: accumulators per lane of the instantiation, 1, 2, 4 or 8 (>= a.n_tan); threads: PRHF_VJP_THREADS or PRHF_JVP_THREADS_WIDE
+hipError_t launch_vfo_jvp(const JvpArgs& a, int nt, int threads, size_t lds_bytes, hipStream_t stream);
 // Stratified Snell's-law tracer (library.py:1096-1268), one wavefront per ray; device pointers.
 #define PRHF_SNELL_OUTPUTS 8   // path km, delay s, x_mid, z_mid, ground range, x_turn, z_turn, n_path
 struct SnellArgs {

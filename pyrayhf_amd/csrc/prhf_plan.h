@@ -703,6 +703,67 @@ inline int plan_vjp(long long n_prof, long long n_freq, long long lds_levels, bo
     return PRHF_OK;
 }
 
+// The launches of the JVP kernel (prhf_jvp.inc): one workgroup per profile, the staged bottomside plus the tangent
+// columns of one chunk.  Nothing in LDS is per wave, so every wave takes frequencies at every height (`waves`: those that
+// get one), and a workgroup may as well have eight of them where there are frequencies for more than four: the LDS of a
+// tall bottomside admits one or two workgroups per CU, and 512 threads then put twice the waves on its SIMDs
+// (PRHF_JVP_WIDE = 0 builds keep 256, to measure against).  A result's bits do not depend on the workgroup's size.  The T tangents of a call go in chunks of `chunk` - 8 where LDS holds eight columns
+// beside the bottomside (up to jvp_max_levels(8) = 908 levels), else 4, 2 or 1 - one launch per chunk, the last one with
+// what remains, on the smallest instantiation that holds it (jvp_chunk).  A result's bits do not depend on the chunking.
+// Limit: jvp_max_levels(1) = 1332 levels up to the highest density peak; beyond it the call is refused.
+#ifndef PRHF_JVP_WIDE
+#define PRHF_JVP_WIDE 1
+#endif
+struct JvpPlan {
+    long long blocks;
+    int threads, waves;
+    int chunk;                // tangents of a full launch (= its instantiation's NT)
+    long long n_chunks;       // launches
+    long long lds_levels;
+};
+inline long long jvp_max_levels(int nt) {
+    long long L = 1;
+    while (prhf::jvp_lds_bytes(L + 1, nt) <= kLdsFull) ++L;
+    return L;
+}
+inline int plan_jvp(long long n_prof, long long n_freq, long long lds_levels, long long n_tan, JvpPlan& pl, char* why,
+                    size_t why_len) {
+    std::memset(&pl, 0, sizeof pl);
+    if (n_prof < 0 || n_freq < 1 || lds_levels < 1 || n_tan < 0) {
+        std::snprintf(why, why_len, "bad shape");
+        return PRHF_EINVAL;
+    }
+    int chunk = PRHF_JVP_MAX_NT;
+    while (chunk > 1 && (chunk / 2 >= n_tan || prhf::jvp_lds_bytes(lds_levels, chunk) > kLdsFull)) chunk /= 2;
+    if (prhf::jvp_lds_bytes(lds_levels, chunk) > kLdsFull) {
+        std::snprintf(why, why_len, "the JVP stages at most %lld levels up to the density peak in LDS; this launch needs %lld "
+                      "(tall bottomsides are not supported by the derivative kernels)", jvp_max_levels(1), lds_levels);
+        return PRHF_EINVAL;
+    }
+    pl.blocks = n_prof;
+    pl.threads = (PRHF_JVP_WIDE && n_freq > PRHF_VJP_THREADS / 64) ? PRHF_JVP_THREADS_WIDE : PRHF_VJP_THREADS;
+    pl.waves = (int)std::min<long long>(pl.threads / 64, n_freq);
+    pl.chunk = chunk;
+    pl.n_chunks = (n_tan + chunk - 1) / chunk;
+    pl.lds_levels = lds_levels;
+    return PRHF_OK;
+}
+// Launch i of the plan: its first tangent, how many it takes, the instantiation (1, 2, 4, 8 >= count) and its LDS
+struct JvpChunk {
+    long long first;
+    int count, nt;
+    size_t lds_bytes;
+};
+inline JvpChunk jvp_chunk(const JvpPlan& pl, long long n_tan, long long i) {
+    JvpChunk ch;
+    ch.first = i * pl.chunk;
+    ch.count = (int)std::min<long long>(pl.chunk, n_tan - ch.first);
+    ch.nt = 1;
+    while (ch.nt < ch.count) ch.nt *= 2;
+    ch.lds_bytes = prhf::jvp_lds_bytes(pl.lds_levels, ch.nt);
+    return ch;
+}
+
 }  // namespace
 
 #endif  // PRHF_PLAN_H

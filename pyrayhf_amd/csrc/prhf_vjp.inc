@@ -156,6 +156,73 @@ __device__ __forceinline__ bool vjp_bracket(const Node* __restrict__ nodes, cons
     return true;
 }
 
+// One grid point of a reflecting pair, shared by the Jacobian, VJP and JVP kernels: point i of the stretched grid below
+// H = h - alt_0, its segment, and mu' with its two tangents there.
+//   GX    D_i (dmu'/dX)_i cX, 0 where the reference's sum skips the term
+//   term  mu'_i D_i, the point's share of the virtual height
+//   sh    its share of S_H
+//   msd   m_i sden_i: dX of the node per unit of dH;  tt: the interpolation weight of level s + 1
+struct VjpPoint {
+    double GX, term, sh, msd, tt;
+    int s;
+    bool active;
+};
+template <int MODE>
+__device__ __forceinline__ VjpPoint vjp_point(const double* __restrict__ mult, int n, int i, double H, double a0, double cX,
+                                              double cY, const Node* nodes, const unsigned short* hint,
+                                              const BlockInfo& info, int K) {
+#pragma clang fp contract(off)
+    const bool active = i < n;
+    const double m = active ? mult[i] : 0.0;
+    const bool last = i + 1 >= n;
+    const double m1 = last ? m : mult[i + 1];
+    const double z = m * H + a0;                               // :413
+    const double dist = !active ? 0.0 : (last ? kBackoff : (m1 * H + a0) - z);   // :415-416
+    const double wgt = m1 - m;
+    int s = guess_segment(hint, info, z);                      // np.interp's segment, at most K - 2
+    if (s > K - 2) s = K > 1 ? K - 2 : 0;
+    while (s > 0 && z < nodes[s].alt) --s;
+    while (s + 2 < K && z >= nodes[s + 1].alt) ++s;
+    const Node nd = nodes[s];
+    double dz = z > a0 ? z - nd.alt : 0.0;
+    const bool inside = dz > 0.0 && K > 1;
+    if (!inside) dz = 0.0;
+    const double seg_len = nodes[s + 1].alt - nd.alt;          // (level K is the +inf sentinel)
+    const double sden = inside ? nd.sden : 0.0, sb = inside ? nd.sb : 0.0, sp = inside ? nd.spsi : 0.0;
+    const double tt = inside ? dz / seg_len : 0.0;
+    const double den = sden * dz + nd.den;
+    const Dual X = Dual{cX * den, 1.0, 0.0};
+    Dual mup;
+    bool ok;
+    if (info.unmag) {
+        const Dual am = 1.0 - X;                               // :201-207 as mu' = (1 - X)^-1/2
+        mup = dual(1.0) / dual_sqrt(am);
+        ok = am.v > 0.0;
+    } else {
+        const double Y = cY * (sb * dz + nd.b);
+        const double psi = (sp * dz + nd.psi) * kDegToRad;
+        double sn, cs;
+        sincos(psi, &sn, &cs);
+        const double s2p = 2.0 * (sn * cs) * (sp * kDegToRad);
+        const Dual Y2 = Dual{Y * Y, 0.0, 2.0 * Y * (cY * sb)};
+        const Dual S2 = Dual{sn * sn, 0.0, s2p};
+        const Dual C2 = Dual{cs * cs, 0.0, -s2p};
+        mup = group_index_dual<MODE>(X, Y2, S2, C2, &ok);
+    }
+    const double inf = __builtin_inf();
+    ok = ok && active && __builtin_fabs(mup.v) < inf && __builtin_fabs(mup.a) < inf && __builtin_fabs(mup.b) < inf;
+    // (a NaN term is skipped by the reference's nansum, :288: a constant)
+    VjpPoint pt;
+    pt.GX = ok ? dist * mup.a * cX : 0.0;
+    pt.term = ok ? mup.v * dist : 0.0;
+    pt.sh = (ok ? mup.v * wgt : 0.0) + (ok ? dist * m * mup.b : 0.0);
+    pt.msd = m * sden;
+    pt.tt = tt;
+    pt.s = s;
+    pt.active = active;
+    return pt;
+}
+
 // Dynamic LDS: the staged profile of the operator's kernels (nodes, f_N^2, g_p |B|), the hint table, the reduction
 // scratch, then `rows` rows of lds_levels doubles for each of the `waves` waves that take frequencies
 // (vjp_lds_bytes, prhf_kernels.h).  JAC: one row per wave - the Jacobian row of the wave's current frequency, written
@@ -215,52 +282,14 @@ __device__ __forceinline__ void vjp_body(const VjpArgs& a) {
                 }
                 const double H = br.h - a0;
                 for (int base = 0; base < n; base += 64) {
-                    const int i = base + lane;
-                    const bool active = i < n;
-                    const double m = active ? a.mult[i] : 0.0;
-                    const bool last = i + 1 >= n;
-                    const double m1 = last ? m : a.mult[i + 1];
-                    const double z = m * H + a0;                               // :413
-                    const double dist = !active ? 0.0 : (last ? kBackoff : (m1 * H + a0) - z);   // :415-416
-                    const double wgt = m1 - m;
-                    int s = guess_segment(hint, info, z);                      // np.interp's segment, at most K - 2
-                    if (s > K - 2) s = K > 1 ? K - 2 : 0;
-                    while (s > 0 && z < nodes[s].alt) --s;
-                    while (s + 2 < K && z >= nodes[s + 1].alt) ++s;
-                    const Node nd = nodes[s];
-                    double dz = z > a0 ? z - nd.alt : 0.0;
-                    const bool inside = dz > 0.0 && K > 1;
-                    if (!inside) dz = 0.0;
-                    const double seg_len = nodes[s + 1].alt - nd.alt;          // (level K is the +inf sentinel)
-                    const double sden = inside ? nd.sden : 0.0, sb = inside ? nd.sb : 0.0, sp = inside ? nd.spsi : 0.0;
-                    const double tt = inside ? dz / seg_len : 0.0;
-                    const double den = sden * dz + nd.den;
-                    const Dual X = Dual{cX * den, 1.0, 0.0};
-                    Dual mup;
-                    bool ok;
-                    if (info.unmag) {
-                        const Dual am = 1.0 - X;                               // :201-207 as mu' = (1 - X)^-1/2
-                        mup = dual(1.0) / dual_sqrt(am);
-                        ok = am.v > 0.0;
-                    } else {
-                        const double Y = cY * (sb * dz + nd.b);
-                        const double psi = (sp * dz + nd.psi) * kDegToRad;
-                        double sn, cs;
-                        sincos(psi, &sn, &cs);
-                        const double s2p = 2.0 * (sn * cs) * (sp * kDegToRad);
-                        const Dual Y2 = Dual{Y * Y, 0.0, 2.0 * Y * (cY * sb)};
-                        const Dual S2 = Dual{sn * sn, 0.0, s2p};
-                        const Dual C2 = Dual{cs * cs, 0.0, -s2p};
-                        mup = group_index_dual<MODE>(X, Y2, S2, C2, &ok);
-                    }
-                    const double inf = __builtin_inf();
-                    ok = ok && active && __builtin_fabs(mup.v) < inf && __builtin_fabs(mup.a) < inf && __builtin_fabs(mup.b) < inf;
-                    // (a NaN term is skipped by the reference's nansum, :288: a constant)
-                    const double GX = ok ? dist * mup.a * cX : 0.0;
-                    total += ok ? mup.v * dist : 0.0;
-                    SH += (ok ? mup.v * wgt : 0.0) + (ok ? dist * m * mup.b : 0.0);
+                    const VjpPoint pt = vjp_point<MODE>(a.mult, n, base + lane, H, a0, cX, cY, nodes, hint, info, K);
+                    const bool active = pt.active;
+                    const int s = pt.s;
+                    const double GX = pt.GX, tt = pt.tt;
+                    total += pt.term;
+                    SH += pt.sh;
                     // total dX of this node per unit of den at its two levels: weight + the node's own motion with h
-                    const double msd = m * sden;
+                    const double msd = pt.msd;
                     double c_lo = 1.0 - tt, c_hi = tt;
                     if (s == jm) c_lo += msd * HA;
                     if (s + 1 == jm) c_hi += msd * HA;

@@ -23,7 +23,7 @@ from . import _native
 from .library import _mode_code, _multiplier, _as_rows, _is_torch, _device_grid, _grid_flag, MATH_AUTO
 
 __all__ = ["residual_VH_batch", "brute_force_fit", "peak_density_from_trace", "brute_grid", "minimize_parameters",
-           "resolve_method", "BoundedPair", "pyiri_edp_builder", "model_VH", "residual_VH", "residual_VH_many",
+           "resolve_method", "BoundedPair", "pyiri_edp_builder", "model_VH", "trace_sensitivity", "residual_VH", "residual_VH_many",
            "brute_force_fit_many", "minimize_parameters_many"]
 
 
@@ -60,6 +60,57 @@ def model_VH(F2, F1, E, f_in, alt, b_mag, b_psi, mode='O', n_points=200, bottom_
     build = pyiri_edp_builder if edp_builder is None else edp_builder
     edp = np.asarray(build(F2, F1, E, alt, bottom_type), dtype=np.float64).ravel()
     return vertical_forward_operator(f_in, edp, b_mag, b_psi, alt, mode, n_points, device=device, math=math), edp
+
+
+_LAYER_KEYS = {'NmF2': 'Nm', 'hmF2': 'hm', 'B_bot': 'B_bot', 'B0': 'B0', 'B1': 'B1'}
+
+
+def trace_sensitivity(F2, F1, E, f_in, alt, b_mag, b_psi, names=('NmF2', 'hmF2', 'B_bot'), mode='O', n_points=200,
+                      bottom_type='B_bot', *, edp_builder=None, rel_step=1e-6, device=None):
+    """``(vh, S, edp)``: ``model_VH``'s trace and profile, and the sensitivity of the trace to the F2 layer parameters
+    ``names``, ``S[f, i] = d vh_f / d param_i`` [km per unit of the parameter], by the chain rule through the density
+    column: ``S = J D`` with ``D[:, i] = d edp / d param_i`` and J the operator's analytic Jacobian
+    (``library.vertical_jacobian``), applied without being formed - all columns of D go through ONE
+    ``library.vertical_jvp`` call.
+
+    D is a central difference of the profile builder, a smooth function of the parameters, at ``value * (1 +- rel_step)``:
+    ``2 len(names)`` host calls; the layer dictionaries are copied for each, not mutated.  The operator itself is NOT
+    differenced.
+
+    What this derivative is: the slope of the trace between the operator's kinks and jumps, at fixed discrete structure
+    - the density peak stays at its level, every grid point in its segment, the reflection height in its bracket.  The
+    operator as a function of the parameters is only piecewise smooth: the bottomside ends at the level below the density
+    peak, so the trace near foF2 jumps whenever hmF2 crosses half a level (see the docstring of
+    ``test_minimize_parameters_other_lmfit_methods``), and the moving grid crosses a level at almost every step of a
+    finite difference of the operator - such differences do not converge to S, nor to anything else.  Rows of
+    frequencies that are not reflected (``vh`` NaN) are zero.  Not used by ``minimize_parameters``.
+    """
+    from copy import deepcopy
+
+    from . import library
+    build = pyiri_edp_builder if edp_builder is None else edp_builder
+    names = tuple(names)
+    for name in names:
+        if name not in _LAYER_KEYS or _LAYER_KEYS[name] not in F2:
+            raise ValueError(f"unknown or absent layer parameter {name!r}")
+    if not rel_step > 0.0:
+        raise ValueError("rel_step must be positive")
+
+    def profile(name=None, value=None):
+        f2, f1, e = deepcopy(F2), deepcopy(F1), deepcopy(E)
+        if name is not None:
+            f2[_LAYER_KEYS[name]] = np.full_like(np.asarray(F2[_LAYER_KEYS[name]], dtype=np.float64), value)
+        return np.asarray(build(f2, f1, e, alt, bottom_type), dtype=np.float64).ravel()
+    edp = profile()
+    tangents = np.empty((len(names), edp.size))
+    for i, name in enumerate(names):
+        value = float(np.asarray(F2[_LAYER_KEYS[name]]).ravel()[0])
+        if value == 0.0:
+            raise ValueError(f"{name} is 0: a relative step cannot move it")
+        hi, lo = value * (1.0 + rel_step), value * (1.0 - rel_step)
+        tangents[i] = (profile(name, hi) - profile(name, lo)) / (hi - lo)
+    vh, S = library.vertical_jvp(np.atleast_1d(f_in), edp, b_mag, b_psi, alt, tangents, mode, n_points, device=device)
+    return vh, S, edp
 
 
 def residual_VH(params, F2_init, F1_init, E_init, f_in, vh_obs, alt, b_mag, b_psi, mode='O', n_points=200,

@@ -11,8 +11,9 @@ error behaviour of ``PyRayHF.library.vertical_forward_operator`` (reference
 * ``vertical_forward_operator_mixed`` evaluates slices with different mode / n_points
   in one launch (BASELINE config 5).
 * ``vertical_jacobian`` / ``vertical_vjp`` give the operator's analytic derivative with respect
-  to the density column (dense rows, or the product with an upstream gradient in one launch);
-  ``pyrayhf_amd.autograd`` wraps the operator for ``torch.autograd``.
+  to the density column (dense rows, or the product with an upstream gradient in one launch),
+  ``vertical_jvp`` its product with perturbations of the column (the tangent-linear operator);
+  ``pyrayhf_amd.autograd`` wraps the operator for ``torch.autograd``, reverse and forward mode.
 
 The tiny host-side helpers of the path (constants, unit conversions, the stretched unit
 grid) are provided under the reference's names so that callers can switch imports.
@@ -29,7 +30,7 @@ from . import _native, logger
 __all__ = [
     "constants", "den2freq", "freq2den", "find_X", "find_Y", "smooth_nonuniform_grid",
     "vertical_to_magnetic_angle", "find_mu_mup", "vertical_forward_operator",
-    "vertical_forward_operator_mixed", "vertical_jacobian", "vertical_vjp", "last_kernel_ms", "MATH_FAITHFUL", "MATH_FAST", "MATH_AUTO",
+    "vertical_forward_operator_mixed", "vertical_jacobian", "vertical_vjp", "vertical_jvp", "last_kernel_ms", "MATH_FAITHFUL", "MATH_FAST", "MATH_AUTO",
 ]
 
 MATH_FAITHFUL = _native.MATH_FAITHFUL   # reference operation order, IEEE divide / sqrt
@@ -617,6 +618,85 @@ def vertical_vjp(freq, den, bmag, bpsi, alt, grad_vh, mode='O', n_points=200, *,
                      (_native.FLAG_SHARED_FIELD if shared else 0) | _grid_flag(mult_np, n_points))
     _native.raise_for(rc)
     return out[0] if single else out
+
+
+def _tangent_layout(shape, den_shape, shared):
+    """``(T, per_profile_sets, squeeze)`` of a tangent array of ``shape`` for a density of ``den_shape``."""
+    shape, den_shape = tuple(shape), tuple(den_shape)
+    n_alt = den_shape[-1]
+    if shared:
+        if shape == (n_alt,):
+            return 1, False, True
+        if len(shape) == 2 and shape[1] == n_alt:
+            return shape[0], False, False
+        raise ValueError("shared tangents must have shape (N_alt,) or (T, N_alt)")
+    if shape == den_shape:
+        return 1, True, True
+    if len(shape) == len(den_shape) + 1 and shape[:-2] == den_shape[:-1] and shape[-1] == n_alt:
+        return shape[-2], True, False
+    raise ValueError("tangents must have den's shape, or den.shape[:-1] + (T, N_alt)")
+
+
+def vertical_jvp(freq, den, bmag, bpsi, alt, tangents, mode='O', n_points=200, *, shared=False, device=None, sync=True):
+    """``(vh, dvh)``: the virtual heights of ``vertical_forward_operator`` and their directional derivatives along
+    perturbations of the density column, ``dvh[..., f, t] = sum_k d vh[..., f] / d den[..., k] * tangents[..., t, k]`` -
+    the Jacobian-vector product (the tangent-linear operator) in one call, without forming the Jacobian of
+    ``vertical_jacobian``; the forward-mode pass of ``pyrayhf_amd.autograd.differentiable_forward_operator``.
+
+    ``tangents`` has ``den``'s shape - one direction per profile, ``dvh`` then has ``vh``'s shape - or
+    ``den.shape[:-1] + (T, N_alt)`` for T directions per profile, ``dvh`` then is ``(..., F, T)``.  With
+    ``shared=True`` it is ``(T, N_alt)`` or ``(N_alt,)`` and applies to every profile.  T may be 0 (an empty ``dvh``).
+
+    Inputs and conventions as ``vertical_jacobian``; ``vh`` is the operator's own output, bit for bit.  A pair without a
+    virtual height has ``dvh = 0`` along every tangent; tangent entries at and above the density peak are not read, so
+    a NaN there does no harm.  ``dvh[..., f, t]`` is reproducible bit for bit and depends on its profile, frequency and
+    tangent only - not on T, the other tangents or the rest of the batch.  ``ValueError`` on a shape mismatch, and when
+    the levels below the highest density peak do not fit the GPU's local memory next to one tangent column (more than
+    1332 levels); up to 908 levels the tangents go through the kernel eight at a time, fewer at a time above that.
+    """
+    code = _mode_code(mode)
+    mult_np = _multiplier(n_points)
+    if any(_is_torch(x) and x.is_cuda for x in (den, bmag, bpsi)):
+        import torch
+        f, d2, b2, p2, a, single, shared_field, alt_stride = _torch_batch(freq, den, bmag, bpsi, alt)
+        dev = d2.device
+        n_prof, n_alt = d2.shape
+        t = tangents if _is_torch(tangents) else torch.as_tensor(np.asarray(tangents, dtype=np.float64), device=dev)
+        if t.device != dev:
+            raise ValueError(f"tangents is on {t.device}, expected {dev}")
+        t = t.detach().to(torch.float64).contiguous()
+        n_tan, per_profile, squeeze = _tangent_layout(t.shape, (n_alt,) if single else (n_prof, n_alt), shared)
+        mult, grid_flag = _device_grid((int(n_points),), dev)
+        vh = torch.empty((n_prof, f.numel()), dtype=torch.float64, device=dev)
+        dvh = torch.empty((n_prof, f.numel(), n_tan), dtype=torch.float64, device=dev)
+        ctx = _native.context(dev.index if dev.index is not None else torch.cuda.current_device())
+        ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+        ctx.set_math(MATH_AUTO)
+        rc = ctx.vfo_jvp(f.data_ptr(), f.numel(), d2.data_ptr(), b2.data_ptr(), p2.data_ptr(), a.data_ptr(), n_prof, n_alt,
+                         n_alt, alt_stride, mult.data_ptr(), int(n_points), code, t.data_ptr() if n_tan else None, n_tan,
+                         n_tan * n_alt if per_profile else 0, vh.data_ptr(), dvh.data_ptr() if n_tan else None,
+                         _native.FLAG_DEVICE_PTRS | _native.FLAG_ASYNC | grid_flag |
+                         (_native.FLAG_SHARED_FIELD if shared_field else 0))
+        _native.raise_for(rc)
+        if sync:
+            _native.raise_for(ctx.sync())
+    else:
+        f, d2, b2, p2, a, single, shared_field, alt_stride = _np_batch(freq, den, bmag, bpsi, alt)
+        n_prof, n_alt = d2.shape
+        t = np.ascontiguousarray(np.asarray(tangents), dtype=np.float64)
+        n_tan, per_profile, squeeze = _tangent_layout(t.shape, (n_alt,) if single else (n_prof, n_alt), shared)
+        vh = np.empty((n_prof, f.size), dtype=np.float64)
+        dvh = np.empty((n_prof, f.size, n_tan), dtype=np.float64)
+        ctx = _native.host_context(device)
+        ctx.set_math(MATH_AUTO)
+        rc = ctx.vfo_jvp(f.ctypes.data, f.size, d2.ctypes.data, b2.ctypes.data, p2.ctypes.data, a.ctypes.data, n_prof, n_alt,
+                         n_alt, alt_stride, mult_np.ctypes.data, int(n_points), code, t.ctypes.data if n_tan else None, n_tan,
+                         n_tan * n_alt if per_profile else 0, vh.ctypes.data, dvh.ctypes.data if n_tan else None,
+                         (_native.FLAG_SHARED_FIELD if shared_field else 0) | _grid_flag(mult_np, n_points))
+        _native.raise_for(rc)
+    if squeeze:
+        dvh = dvh[:, :, 0]
+    return (vh[0], dvh[0]) if single else (vh, dvh)
 
 
 def vertical_forward_operator_mixed(freq, den, bmag, bpsi, alt, segments, *, device=None, math=None, sync=True):

@@ -43,7 +43,7 @@ extern "C" {
                               *    prhf_residual_many_f64, prhf_vfo_residual_many_f64, and
                               *    prhf_gradient_hop_skip_f64, prhf_gradient_hop_muf_f64,
                               *    prhf_gradient_hop_skip_counters, and prhf_panel_upper_counters,
-                              *    and prhf_stream_launches) */
+                              *    and prhf_stream_launches, and prhf_panel_plan_counters) */
 
 /* return codes */
 #define PRHF_OK        0
@@ -956,6 +956,13 @@ int prhf_panel_counters(prhf_ctx* ctx, uint64_t* counters);
  * next below those segments fails the tests when it ends at the lower region's end and passes when it reaches its
  * segment's end: such a pair takes the panel sum with the option and falls back without.)  Waits for the context's stream. */
 int prhf_panel_upper_counters(prhf_ctx* ctx, uint64_t* counters);
+
+/* Diagnostics of the panel region's set-up, summed over every launch since the context was made: counters[0] the pairs
+ * among those of prhf_pair_plan_counters' first word whose plan carries the panel sum's region - its first point, the
+ * segments of its ends, whether it reaches the top segment - so that their waves read it instead of computing it.
+ * Stays 0 with option "pair_plan", "panel_lower" or "panel_upper" off, and wherever no pair is planned.  Waits for the
+ * context's stream. */
+int prhf_panel_plan_counters(prhf_ctx* ctx, uint64_t* counters);
 
 /* Diagnostics of option "stream_blocks": *count = the operator launches of this context that took the streaming form
  * since the context was made (a launch that keeps the general kernel does not count).  Host-side; does not synchronize. */

@@ -179,6 +179,7 @@ _PROTOTYPES = {
     "prhf_pair_plan_counters": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
     "prhf_panel_counters": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
     "prhf_panel_upper_counters": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
+    "prhf_panel_plan_counters": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
     "prhf_stream_launches": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
     "prhf_occupancy": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
                                       ctypes.POINTER(ctypes.c_int32)]),
@@ -572,6 +573,13 @@ class Context:
         context was made (option ``panel_upper``, include/prhf.h)."""
         buf = (ctypes.c_uint64 * 2)()
         raise_for(self._lib.prhf_panel_upper_counters(self._h, buf))
+        return tuple(int(v) for v in buf)
+
+    def panel_plan_counters(self):
+        """(pairs whose plan carried the panel sum's region, so that their waves read it instead of computing it,)
+        since this context was made (include/prhf.h)."""
+        buf = (ctypes.c_uint64 * 1)()
+        raise_for(self._lib.prhf_panel_plan_counters(self._h, buf))
         return tuple(int(v) for v in buf)
 
     def stream_launches(self):

@@ -166,7 +166,8 @@ struct KArgs {
     // added to once per workgroup and block; plan_cap > 0 caps the records per workgroup (tests).  [2] pairs whose lower
     // segments took the panel sum, [3] eligible pairs that fell back (SegDev::panel_lower), [4] the pairs of [2] in
     // slices with SegDev::panel_upper, [5] those of them whose panel region stayed the lower one, added to once per wave and
-    // block ([5]: once per such pair, they are few; the others' region reached the top segment)
+    // block ([5]: once per such pair, they are few; the others' region reached the top segment), [6] the pairs of [0] whose
+    // plan carries the panel region's set-up (the record's second form), added to with [0]
     unsigned long long* plan_counters;
     int plan_cap;
     SegDev seg[PRHF_MAX_SEGMENTS];

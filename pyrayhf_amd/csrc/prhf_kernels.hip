@@ -1203,6 +1203,58 @@ __device__ __forceinline__ StridedZones strided_zones(int lo_s, int q_s, int beg
 // segments (10 bits each, in segment order from bit 0 of the fifth word).
 constexpr int kPlanBytes = 24;
 constexpr unsigned kPlanValid = 1u << 30;
+// The record's second form (bit 31 of the fourth word; DESIGN.md 4.1, "the panel region from the plan"): a pair whose
+// panel block will pass its entry test never reads the zones of segments j_top - 1 and j_top - 2 unless its panel sum
+// falls back or keeps the lower region, so their fields hold the region's set-up instead - S_P / 64 (ten bits) and
+// `up` (two bits: 0, 1, or 2 for anything else) in the fourth word beside the two flags, j_s and j_e (16 bits each) in
+// the sixth.  The top segment's fields stay where they are.  The form bit is the entry test: j_min and ok_min have no
+// reader behind it.
+constexpr unsigned kPlanPanel = 1u << 31;
+// The record's address as it waits in lean_loop_body's vector register: records lie at multiples of eight, and bit 0
+// says that the record has the second form, so that nobody reads the fourth word again to learn it.  Every reader goes
+// through these two.
+__device__ __forceinline__ unsigned plan_waiting(unsigned lds, bool panel) { return lds | (panel ? 1u : 0u); }
+__device__ __forceinline__ unsigned plan_addr(unsigned waiting) { return waiting & ~1u; }
+__device__ __forceinline__ bool plan_is_panel(unsigned waiting) { return (waiting & 1u) != 0u; }
+// The constants of a block (plan_pairs), two doubles in LDS of the kernel's own (the general kernels: one pair; the
+// streaming form: one per slot, in its header): what the panel region's set-up takes from the launch alone, N and c1 -
+// [0] -1 / (1 - q^M), [1] -10 / (N - 1) - computed once per block.  A record of the second form carries their address / 8
+// in bits 12 .. 26 of its fourth word, so the pair's wave finds [1] without a new argument and without a division.
+constexpr int kPlanBlockShift = 12;
+constexpr unsigned kPlanBlockMask = 0x7fffu;        // (LDS has 160 KiB: an address / 8 has 15 bits)
+// The panel region's set-up (lean_loop_body's panel block), spelled once for the pair's wave and for the planner's
+// thread, so that both come to the same integers by construction.  (Contraction is set here and not by the caller: the
+// wave had 1 - q^8 under its own setting before these were functions, and keeps that rounding.)
+// -1 / (1 - q^M), q = 1 - c1: a constant of the launch
+__device__ __forceinline__ double panel_launch_term(double sc1) {
+#pragma clang fp contract(fast)
+    double qm = 1.0 - sc1;
+    for (int s = 1; s < PRHF_PANEL_MIN_SEGMENT; s *= 2) qm = qm * qm;
+    return -1.0 / (1.0 - qm);
+}
+// the lowest segment that holds PRHF_PANEL_MIN_SEGMENT points
+__device__ __forceinline__ int panel_j_min(double kj, double term) {
+#pragma clang fp contract(fast)
+    const double c0 = 1.0 / 22025.465794806718;
+    return (int)fmin(fmax(__builtin_ceil(__builtin_fma(kj, 1.0 + c0, term)), 0.0), 1e6);
+}
+// the first grid point of segment j; ok: the four entries around the guess bracket it (m_at(i): the table's m_i)
+template <class MAt>
+__device__ __forceinline__ int panel_first_point(int j, double rkj, double kj, double n1, int i_last, bool& ok, MAt m_at) {
+#pragma clang fp contract(fast)
+    const int guess = stretch_guess((double)j * rkj, n1);
+    const int base = min(max(guess, 0) + 3, i_last) - 3;
+    bool hit[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) hit[q] = (int)(m_at(base + q) * kj) >= j;
+    ok = j <= 0 || (guess == base && !hit[0] && hit[3]);
+    return j <= 0 ? 0 : base + (hit[1] ? 1 : (hit[2] ? 2 : 3));
+}
+// the region's two possible ends, from the first points of segments j_top - 2 and j_top
+__device__ __forceinline__ int panel_region_end(int lo2) { return ((lo2 + 4) & ~63) & ~(PRHF_PANEL_BLOCK - 1); }
+__device__ __forceinline__ int panel_upper_end(int lo0) { return (lo0 + 4) & ~63; }
+// a grid point's segment, as the indexed step finds it
+__device__ __forceinline__ int panel_level(double m, double kj) { return (int)(m * kj); }
 
 template <bool G>
 __device__ __forceinline__ TopSegment top_segment(const NodeSpace<G>& nodes_v, int j, double span, double cY) {
@@ -1332,7 +1384,19 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
     //  in a vector register, like a0 and the node table's, and strided_run reads its two words when its turn comes)
     typedef __attribute__((address_space(3))) const unsigned* LdsU32;
     unsigned plan_lds = 0u, plan_v = 0u;
-    if constexpr (PLANNABLE) {
+    // (UPPER: a record of the second form, kPlanPanel, says so in bit 0 of the waiting address - records lie at multiples
+    //  of eight - so that nobody reads the fourth word again to learn the form)
+    bool plan_panel = false;
+    if constexpr (PLANNABLE && UPPER) {
+        plan_lds = (unsigned)uniform((int)hint_lds);
+        if (plan_lds != 0u) {
+            const unsigned pw3 = (unsigned)uniform((int)((LdsU32)(uintptr_t)plan_lds)[3]);
+            if ((pw3 & kPlanValid) == 0u) plan_lds = 0u;
+            else plan_panel = (pw3 & kPlanPanel) != 0u;
+        }
+        plan_v = plan_waiting(plan_lds, plan_panel);
+        asm volatile("" : "+v"(plan_v));
+    } else if constexpr (PLANNABLE) {
         plan_lds = (unsigned)uniform((int)hint_lds);
         if (plan_lds != 0u && ((unsigned)uniform((int)((LdsU32)(uintptr_t)plan_lds)[3]) & kPlanValid) == 0u) plan_lds = 0u;
         plan_v = plan_lds;
@@ -1537,13 +1601,35 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
     int panel_state = 0;
     asm volatile("" : "+v"(panel_state));
     if (STRIDED && sp_off > 0 && n_seg > 0 && first == 0 && last_special >= 0 && end >= PRHF_TOP3_MIN_POINTS) {
-        const u32x4 vh = __builtin_amdgcn_raw_buffer_load_b128(rsrc, 0, sp_off * (int)sizeof(double2), 0);
-        double2 gh;
-        __builtin_memcpy(&gh, &vh, sizeof gh);
-        const int hw = uniform((int)vh.x);
-        strided_on = (hw & 1) == 0;
-        lower_on = lower_req && hw == 0;
-        sc1 = uniform(gh.y);
+        if constexpr (UPPER) {
+            // (a record of the second form exists only where the planner read the header word 0: such a pair asks for c1
+            //  alone and waits for nothing here - c1 stays in the vector registers it arrives in, only vector arithmetic
+            //  reads it; the header word beside it would arrive in registers that are free again at once, and the next
+            //  instruction to write one of them would wait for the load)
+            if (plan_panel) {
+                typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+                const u32x2 vc = __builtin_amdgcn_raw_buffer_load_b64(rsrc, 0, sp_off * (int)sizeof(double2) + 8, 0);
+                __builtin_memcpy(&sc1, &vc, sizeof sc1);
+                strided_on = true;
+                lower_on = lower_req;
+            } else {
+                const u32x4 vh = __builtin_amdgcn_raw_buffer_load_b128(rsrc, 0, sp_off * (int)sizeof(double2), 0);
+                double2 gh;
+                __builtin_memcpy(&gh, &vh, sizeof gh);
+                const int hw = uniform((int)vh.x);
+                strided_on = (hw & 1) == 0;
+                lower_on = lower_req && hw == 0;
+                sc1 = gh.y;
+            }
+        } else {
+            const u32x4 vh = __builtin_amdgcn_raw_buffer_load_b128(rsrc, 0, sp_off * (int)sizeof(double2), 0);
+            double2 gh;
+            __builtin_memcpy(&gh, &vh, sizeof gh);
+            const int hw = uniform((int)vh.x);
+            strided_on = (hw & 1) == 0;
+            lower_on = lower_req && hw == 0;
+            sc1 = uniform(gh.y);
+        }
     }
     // The strided sum of a top segment ("every eighth point"): inside one segment the summand
     // g(i) = mu'(m_i) w(m_i) is an analytic function of the index - linear interpolants, exponential stretch - so
@@ -1568,9 +1654,15 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
     auto strided_run = [&](int lo_s, int q_s, int begin_s, int sidx) {
         int a_s, e_s, z2_s, z1_s;
         const unsigned plan_s = PLANNABLE ? (unsigned)uniform((int)plan_v) : 0u;
-        if (PLANNABLE && plan_s != 0u) {
+        // (a record of the second form, kPlanPanel, has the top segment's zones only: the rare pair that comes here for one
+        //  of the two segments below it - its panel sum fell back or kept the lower region - computes them itself)
+        bool from_plan = PLANNABLE && plan_s != 0u;
+        if constexpr (UPPER && PLANNABLE) {
+            if (sidx != 0 && plan_is_panel(plan_s)) from_plan = false;
+        }
+        if (from_plan) {
             // (a_s / 64, e_s / 64: ten bits each, in segment order from bit 0 of the third word)
-            const LdsU32 rec = (LdsU32)(uintptr_t)plan_s;
+            const LdsU32 rec = (LdsU32)(uintptr_t)(UPPER ? plan_addr(plan_s) : plan_s);
             const unsigned pw2 = (unsigned)uniform((int)rec[2]), pw3 = (unsigned)uniform((int)rec[3]);
             const unsigned pa = sidx == 0 ? pw2 : (sidx == 1 ? pw2 >> 20 : pw3 >> 10);
             const unsigned pe = sidx == 0 ? pw2 >> 10 : (sidx == 1 ? pw3 : pw3 >> 20);
@@ -1734,29 +1826,42 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
             asm volatile("" : "+v"(panel_state));
             // segment j holds at least M points where ln(a_j / (a_j - 1 / kj)) >= 10 M / (N - 1), a_j = 1 - j / kj + c0:
             // j >= kj (1 + c0) - 1 / (1 - q^M), q = exp(-10 / (N - 1)) = 1 - c1
-            double qm = 1.0 - sc1;
-            for (int s = 1; s < PRHF_PANEL_MIN_SEGMENT; s *= 2) qm = qm * qm;
-            const int j_min = uniform((int)fmin(fmax(__builtin_ceil(__builtin_fma(kj, 1.0 + c0, -1.0 / (1.0 - qm))), 0.0), 1e6));
             // the first grid point of segment j (per lane); ok: the four entries around the guess bracket it
             auto first_point = [&](int j, bool& ok) {
-                const int guess = stretch_guess((double)j * rkj, n1);
-                const int base = min(max(guess, 0) + 3, i_last_s) - 3;
-                typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-                bool hit[4];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rsrc, (unsigned)(base + q) * (unsigned)sizeof(double2), 0, 0);
+                return panel_first_point(j, rkj, kj, n1, i_last_s, ok, [&](int i) {
+                    typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+                    const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rsrc, (unsigned)i * (unsigned)sizeof(double2), 0, 0);
                     double mq;
                     __builtin_memcpy(&mq, &v, sizeof mq);
-                    hit[q] = (int)(mq * kj) >= j;
-                }
-                ok = j <= 0 || (guess == base && !hit[0] && hit[3]);
-                return j <= 0 ? 0 : base + (hit[1] ? 1 : (hit[2] ? 2 : 3));
+                    return mq;
+                });
             };
-            bool ok_min;
-            const int lo_min = uniform(first_point(j_min, ok_min));
-            S_P = (lo_min + B - 1) & ~(B - 1);
-            auto region_end = [&]() { return ((seg_lo[2] + 4) & ~63) & ~(B - 1); };
+            auto region_end = [&]() { return panel_region_end(seg_lo[2]); };
+            // The region's set-up: from the pair's plan where its record has the second form (kPlanPanel: the planner's
+            // thread passed the entry test below with the same functions on the same inputs), else here, wave-uniformly -
+            // a pair without a plan, and every pair of the non-UPPER instance, whose records all have the first form.
+            constexpr bool REC = UPPER && PLANNABLE;
+            // (both of the record's words are asked for at once: one wait)
+            unsigned pw3 = 0u, pw5 = 0u;
+            if constexpr (REC) {
+                const unsigned plan_s = (unsigned)uniform((int)plan_v);
+                if (plan_is_panel(plan_s)) {
+                    const LdsU32 rec = (LdsU32)(uintptr_t)plan_addr(plan_s);
+                    const unsigned w3 = rec[3], w5 = rec[5];
+                    pw3 = (unsigned)uniform((int)w3);
+                    pw5 = (unsigned)uniform((int)w5);
+                }
+            }
+            const bool from_rec = REC && pw3 != 0u;
+            int j_min = 0;
+            bool ok_min = true;
+            if (from_rec) {
+                S_P = (int)(pw3 & 1023u) << 6;
+            } else {
+                j_min = uniform(panel_j_min(kj, panel_launch_term(sc1)));
+                const int lo_min = uniform(first_point(j_min, ok_min));
+                S_P = (lo_min + B - 1) & ~(B - 1);
+            }
             // Option panel_upper (UPPER): the region may end at the top segment's first point, E_up, instead - the two
             // segments below the top one, j_top - 2 and j_top - 1, become runs like any other, and so do the top segment's
             // first points where E_up lies above them.  It does if the runs whose extent is the upper region's - from run
@@ -1767,8 +1872,8 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
             // them is summed, and where one fails the list is made again for the lower region.  (A list with more runs
             // left than it has lanes ends in front of run j_top - 3 and ignores what the lanes behind its end found.)
             // A function of the pair alone, like the rest.
-            auto upper_end = [&]() { return (seg_lo[0] + 4) & ~63; };
-            if (__ballot(!ok_min) == 0ull && j_min < seg_j[2] && region_end() - S_P >= 256) {
+            auto upper_end = [&]() { return panel_upper_end(seg_lo[0]); };
+            if (from_rec || (__ballot(!ok_min) == 0ull && j_min < seg_j[2] && region_end() - S_P >= 256)) {
                 // (the region's end, from the flag: nothing more for the loop to carry)
                 auto upper_now = [&]() {
                     asm volatile("" : "+v"(panel_state));
@@ -1776,14 +1881,24 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
                 };
                 const int E_lo = region_end();
                 // the segments of the region's first and last point
-                const u32x4 vs = __builtin_amdgcn_raw_buffer_load_b128(rsrc, 0, S_P * (int)sizeof(double2), 0);
-                const u32x4 ve = __builtin_amdgcn_raw_buffer_load_b128(rsrc, 0, (E_lo - 1) * (int)sizeof(double2), 0);
-                double2 gs, ge;
-                __builtin_memcpy(&gs, &vs, sizeof gs);
-                __builtin_memcpy(&ge, &ve, sizeof ge);
-                const int j_s = uniform((int)(gs.x * kj)), j_e = uniform((int)(ge.x * kj));
+                int j_s, j_e;
+                if (from_rec) {
+                    j_s = (int)(pw5 & 0xffffu);
+                    j_e = (int)(pw5 >> 16);
+                } else {
+                    const u32x4 vs = __builtin_amdgcn_raw_buffer_load_b128(rsrc, 0, S_P * (int)sizeof(double2), 0);
+                    const u32x4 ve = __builtin_amdgcn_raw_buffer_load_b128(rsrc, 0, (E_lo - 1) * (int)sizeof(double2), 0);
+                    double2 gs, ge;
+                    __builtin_memcpy(&gs, &vs, sizeof gs);
+                    __builtin_memcpy(&ge, &ve, sizeof ge);
+                    j_s = uniform(panel_level(gs.x, kj));
+                    j_e = uniform(panel_level(ge.x, kj));
+                }
                 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-                const double s10 = uniform(-10.0 / n1);
+                // (a constant of the launch: the planner's, where the record says that the planner was here)
+                typedef __attribute__((address_space(3))) const double* LdsF64;
+                const double s10 = from_rec ? uniform(((LdsF64)(uintptr_t)(((pw3 >> kPlanBlockShift) & kPlanBlockMask) << 3))[1])
+                                            : uniform(-10.0 / n1);
                 const double r2 = 1.4142135623730951;
                 bool fail = false;
                 // (the loop function is at the end of its scalar registers: the segment of the list's first run and the
@@ -1794,11 +1909,16 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
                 int j_e_lo = j_e, e_v = E_lo, s_v = S_P;
                 if constexpr (UPPER) {
                     asm volatile("" : "+v"(j_e_lo), "+v"(s_v));
-                    const u32x4 vu = __builtin_amdgcn_raw_buffer_load_b128(rsrc, 0, (upper_end() - 1) * (int)sizeof(double2), 0);
-                    double2 gu;
-                    __builtin_memcpy(&gu, &vu, sizeof gu);
-                    // (the region's last point lies in the segment below the top one, or is one of the top one's first)
-                    const int up = uniform((int)(gu.x * kj)) - (seg_j[0] - 1);
+                    int up;
+                    if (from_rec) {
+                        up = (int)((pw3 >> 10) & 3u);
+                    } else {
+                        const u32x4 vu = __builtin_amdgcn_raw_buffer_load_b128(rsrc, 0, (upper_end() - 1) * (int)sizeof(double2), 0);
+                        double2 gu;
+                        __builtin_memcpy(&gu, &vu, sizeof gu);
+                        // (the region's last point lies in the segment below the top one, or is one of the top one's first)
+                        up = uniform(panel_level(gu.x, kj)) - (seg_j[0] - 1);
+                    }
                     if (up == 0 || up == 1) {
                         panel_state = 2 | kUpperRegion;
                         left = seg_j[0] + up - j_s;
@@ -2728,20 +2848,22 @@ __device__ __forceinline__ unsigned plan_slot(const PlanRoom& r, int i) {
 
 // The plan of one pair by one thread: the integers lean_loop_body would compute wave-uniformly - first points of the
 // top three segments by the closed form of the stretch and its four-entry bracket check, then the strided stretch of
-// each - written to `rec` (six words).  Returns false where the guess does not bracket (another grid, a range's
-// edge): that pair's wave runs its own search.  `h` is the settled reflection height (span > 0 and kj inside the node
-// table: checked by the caller, as integrate_chunk does).
+// each - written to `rec` (six words).  Returns 0 where the guess does not bracket (another grid, a range's edge):
+// that pair's wave runs its own search; 1 for a record of the first form, 2 for one of the second (kPlanPanel).  The
+// caller has checked span > 0 and kj inside the node table, as integrate_chunk does.  `panel`: the slice's pairs may
+// take the second form - the caller's gates: options strided_lower, panel_lower and panel_upper, the strided table's
+// header word 0, fewer than 65536 points - and its value is the LDS address of the block's two constants; 0: none.
 // (FORM: one copy of the function for the workgroup-wide pass of the general kernels, another for the lone stager of the
 //  streaming form - the backend fits a shared function's registers to all of its callers, and the general kernels keep
 //  the code they had)
 template <int FORM>
-__device__ __attribute__((noinline)) bool plan_pair(const Node* nodes, int K, const double2* __restrict__ pairs, int n_points,
-                                                    double span, double kj, double cX, double cY2, bool grade,
-                                                    unsigned* rec) {
+__device__ __attribute__((noinline)) int plan_pair(const Node* nodes, int K, const double2* __restrict__ pairs, int n_points,
+                                                   double span, double kj, double cX, double cY2, bool grade,
+                                                   unsigned panel, unsigned* rec) {
     const int i_last = n_points - 1;
     const double n1 = (double)i_last;
     const int j_top = (int)(pairs[i_last].x * kj);
-    if (j_top < 0 || j_top > K - 1) return false;
+    if (j_top < 0 || j_top > K - 1) return 0;
     int search_hi = i_last + 1, run_end = i_last & ~63;
     // one segment: 0 the guess does not bracket, 1 a loop of its own from *lo, 2 too short for one (nor are those below)
     auto find = [&](int j, int* lo_out) {
@@ -2761,15 +2883,15 @@ __device__ __attribute__((noinline)) bool plan_pair(const Node* nodes, int K, co
     };
     int lo0 = 0, lo1 = 0, lo2 = 0, n_seg = 0;
     const int f0 = find(j_top, &lo0);
-    if (f0 == 0) return false;
+    if (f0 == 0) return 0;
     if (f0 == 1) {
         n_seg = 1;
         const int f1 = find(j_top - 1, &lo1);
-        if (f1 == 0) return false;
+        if (f1 == 0) return 0;
         if (f1 == 1) {
             n_seg = 2;
             const int f2 = find(j_top - 2, &lo2);
-            if (f2 == 0) return false;
+            if (f2 == 0) return 0;
             if (f2 == 1) n_seg = 3;
         }
     }
@@ -2784,6 +2906,33 @@ __device__ __attribute__((noinline)) bool plan_pair(const Node* nodes, int K, co
         return ((unsigned long long)zz << 32) | ((unsigned)(sp.a_s >> 6) | ((unsigned)(sp.e_s >> 6) << 10));
     };
     const unsigned long long s0 = n_seg > 0 ? span_of(j_top, lo0, i_last - 1) : 0ull;
+    // The second form (kPlanPanel): the slice has the panel sum with the upper region (`panel`, the caller's gates)
+    // and the pair all three segments, so its wave will come to the panel block's entry test.  Where that test passes - the wave's own functions, on the wave's own inputs - the record carries the
+    // region's set-up, and the zones of the two segments below the top one, which such a pair hardly ever reads, are not
+    // computed.
+    if (panel != 0u && n_seg == 3) {
+        const double rkj = 1.0 / kj;
+        typedef __attribute__((address_space(3))) const double* LdsF64;
+        const int j_min = panel_j_min(kj, ((LdsF64)(uintptr_t)panel)[0]);
+        bool ok_min;
+        const int lo_min = panel_first_point(j_min, rkj, kj, n1, i_last, ok_min, [&](int i) { return pairs[i].x; });
+        const int S_P = (lo_min + PRHF_PANEL_BLOCK - 1) & ~(PRHF_PANEL_BLOCK - 1);
+        const int E_lo = panel_region_end(lo2);
+        if (ok_min && j_min < j_top - 2 && E_lo - S_P >= 256) {
+            const int j_s = panel_level(pairs[S_P].x, kj), j_e = panel_level(pairs[E_lo - 1].x, kj);
+            const int up = panel_level(pairs[panel_upper_end(lo0) - 1].x, kj) - (j_top - 1);
+            if (j_s >= 0 && j_s < 65536 && j_e >= 0 && j_e < 65536) {
+                rec[0] = (unsigned)lo0 | ((unsigned)lo1 << 16);
+                rec[1] = (unsigned)lo2 | ((unsigned)j_top << 16);
+                rec[2] = (unsigned)s0 | (3u << 30);
+                rec[3] = (unsigned)(S_P >> 6) | ((up == 0 || up == 1 ? (unsigned)up : 2u) << 10) |
+                         ((panel >> 3) << kPlanBlockShift) | kPlanValid | kPlanPanel;
+                rec[4] = (unsigned)(s0 >> 32);
+                rec[5] = (unsigned)j_s | ((unsigned)j_e << 16);
+                return 2;
+            }
+        }
+    }
     const unsigned long long s1 = n_seg > 1 ? span_of(j_top - 1, lo1, lo0 - 1) : 0ull;
     const unsigned long long s2 = n_seg > 2 ? span_of(j_top - 2, lo2, lo1 - 1) : 0ull;
     const unsigned ae0 = (unsigned)s0, ae1 = (unsigned)s1, ae2 = (unsigned)s2;
@@ -2794,7 +2943,7 @@ __device__ __attribute__((noinline)) bool plan_pair(const Node* nodes, int K, co
     rec[3] = (ae1 >> 10) | (ae2 << 10) | kPlanValid;
     rec[4] = zz0 | ((zz1 & 1023u) << 20);
     rec[5] = (zz1 >> 10) | (zz2 << 10);
-    return true;
+    return 1;
 }
 
 // The planning pass: after the candidate list, before the items.  Thread i plans the i-th item this
@@ -2805,7 +2954,8 @@ __device__ __attribute__((noinline)) bool plan_pair(const Node* nodes, int K, co
 template <int TIER, int THREADS, bool G, int TEAM = THREADS>
 __device__ __forceinline__ PlanRoom plan_pairs(const KArgs& a, const SegDev& sg, const Node* nodes, double* pf2, double* gb,
                                                unsigned short* hint, const unsigned short* cand, const BlockInfo& info,
-                                               int block_in_prof, int blocks_per_prof, unsigned* plan_cnt) {
+                                               int block_in_prof, int blocks_per_prof, unsigned* plan_cnt,
+                                               double* plan_consts) {
     constexpr int W = THREADS / 64;            // (the numbering of the items: the workgroup's, whatever the team)
     PlanRoom room;
     room.base0 = room.base1 = room.base2 = 0u;
@@ -2830,14 +2980,27 @@ __device__ __forceinline__ PlanRoom plan_pairs(const KArgs& a, const SegDev& sg,
     room.total = room.cap01 + max(levels - used, 0) * 8 / kPlanBytes;
     if (a.plan_cap > 0) room.total = min(room.total, a.plan_cap);
     const int first_item = block_in_prof * W, round_items = blocks_per_prof * W;
-    int n_planned = 0, n_self = 0;
+    // (what the panel region's set-up takes from the launch alone, N and c1 from the strided table's header: once per
+    //  block, by one thread, for the planner's threads and for the waves; !panel: this slice's pairs have no upper
+    //  region, and every record keeps the first form)
+    const bool panel = sg.strided_lower && sg.panel_lower && sg.panel_upper;
+    if (panel) {
+        if (team_tid<TEAM, THREADS>() == 0) {
+            const double term = panel_launch_term(pairs[sg.sp_off - sg.mult_off].y);
+            const double s10 = -10.0 / (double)(sg.n_points - 1);
+            plan_consts[0] = term;
+            plan_consts[1] = s10;
+        }
+        team_sync<TEAM, THREADS>();
+    }
+    int n_planned = 0, n_self = 0, n_panel = 0;
     for (int u = team_tid<TEAM, THREADS>();; u += TEAM) {
         const int t = (u / W) * round_items + first_item + (u % W);
         if (t >= info.n_cand) break;
         const double span = info.heights[t] - info.a0;
         const double kj = span * info.inv_step;
         const bool main_loop = span > 0.0 && kj <= (double)(info.K - 1);       // (integrate_chunk's own test)
-        bool done = false;
+        int done = 0;
         if (u < room.total) {
             constexpr int kWords = kPlanBytes / 4;
             unsigned* rec = u < room.cap0 ? reinterpret_cast<unsigned*>(gb) + kWords * u
@@ -2845,20 +3008,24 @@ __device__ __forceinline__ PlanRoom plan_pairs(const KArgs& a, const SegDev& sg,
                                                             : reinterpret_cast<unsigned*>(pf2 + used) + kWords * (u - room.cap01));
             if (main_loop) {
                 const double* row = a.ftab + 8 * (long long)cand[t];
-                done = plan_pair<TEAM == THREADS ? 0 : 1>(nodes, info.K, pairs, sg.n_points, span, kj, row[2], row[3], sg.strided_grade != 0, rec);
+                done = plan_pair<TEAM == THREADS ? 0 : 1>(nodes, info.K, pairs, sg.n_points, span, kj, row[2], row[3], sg.strided_grade != 0,
+                                                          panel ? (unsigned)(uintptr_t)(LdsDouble)plan_consts : 0u, rec);
             }
             if (!done) rec[3] = 0u;
         }
         if (main_loop) {
             if (done) ++n_planned; else ++n_self;
+            if (done == 2) ++n_panel;
         }
     }
     if (n_planned) atomicAdd(&plan_cnt[0], (unsigned)n_planned);
     if (n_self) atomicAdd(&plan_cnt[1], (unsigned)n_self);
+    if (n_panel) atomicAdd(&plan_cnt[2], (unsigned)n_panel);
     team_sync<TEAM, THREADS>();
     if (team_tid<TEAM, THREADS>() == 0 && a.plan_counters) {
         if (plan_cnt[0]) atomicAdd(&a.plan_counters[0], (unsigned long long)plan_cnt[0]);
         if (plan_cnt[1]) atomicAdd(&a.plan_counters[1], (unsigned long long)plan_cnt[1]);
+        if (plan_cnt[2]) atomicAdd(&a.plan_counters[6], (unsigned long long)plan_cnt[2]);
     }
     room.base0 = (unsigned)uniform((int)room.base0);
     room.base1 = (unsigned)uniform((int)room.base1);
@@ -3011,7 +3178,7 @@ template <int TIER, int THREADS, bool G>
 __device__ __forceinline__ unsigned long long run_block(const KArgs& a, const SegDev& sg, Node* nodes, double* pf2, double* gb,
                                           unsigned short* hint, unsigned short* cand, int* cand_count, double* red,
                                           long long prof_local, int block_in_prof, int blocks_per_prof,
-                                          int* item_next, unsigned* plan_cnt) {
+                                          int* item_next, unsigned* plan_cnt, double* plan_consts) {
     const long long p = sg.prof_begin + prof_local;
     BlockInfo info = stage_profile<TIER, THREADS>(
         a.den + p * a.prof_stride, a.bmag + p * a.field_stride, a.bpsi + p * a.field_stride,
@@ -3046,7 +3213,7 @@ __device__ __forceinline__ unsigned long long run_block(const KArgs& a, const Se
     }
     // (every thread of the workgroup takes the same branches up to here: the pass has a barrier of its own)
     const PlanRoom room = plan_pairs<TIER, THREADS, G>(a, sg, nodes, pf2, gb, hint, cand, info, block_in_prof, blocks_per_prof,
-                                                       plan_cnt);
+                                                       plan_cnt, plan_consts);
     PRHF_MARK(3);
     if (sg.mode == PRHF_KMODE_O)
         run_items<PRHF_KMODE_O, TIER, THREADS, G>(a, sg, nodes, pf2, gb, hint, cand, info, prof_local, block_in_prof,
@@ -3096,7 +3263,8 @@ __device__ __forceinline__ void vfo_kernel_body(const KArgs& a) {
     __shared__ long long next_bid;
     __shared__ int item_next;
     __shared__ int cand_count[PRHF_BLOCK_THREADS / 64 + 1];
-    __shared__ unsigned plan_cnt[2];           // pairs of this block that got a plan / that plan themselves (plan_pairs)
+    __shared__ unsigned plan_cnt[3];           // pairs of this block that got a plan / that plan themselves / whose plan has the second form (plan_pairs)
+    __shared__ double plan_consts[2];          // ... and the block's constants
     // Follow-up of a short-grid launch: the blocks to evaluate are listed (block_list[1 .. block_list[0]])
     const unsigned* list = a.block_list;
     const long long n_blocks = list ? (long long)list[0] : a.n_blocks;
@@ -3109,7 +3277,7 @@ __device__ __forceinline__ void vfo_kernel_body(const KArgs& a) {
     for (;;) {
         if (threadIdx.x == 0) {                // ordered before their first use by the barriers of stage_profile
             item_next = 0;
-            plan_cnt[0] = plan_cnt[1] = 0u;
+            plan_cnt[0] = plan_cnt[1] = plan_cnt[2] = 0u;
         }
 #ifdef PRHF_TRACE
         const unsigned long long t_start = wall_clock64();
@@ -3155,9 +3323,9 @@ __device__ __forceinline__ void vfo_kernel_body(const KArgs& a) {
 
         const unsigned long long t_staged = (TIER_SEL == 0 || (TIER_SEL == 2 && sg.tier == 0))
             ? run_block<0, THREADS, TALL>(a, sg, nodes, pf2, gb, hint, cand, cand_count, red, prof_local, block_in_prof, bpp,
-                                    &item_next, plan_cnt)
+                                    &item_next, plan_cnt, plan_consts)
             : run_block<1, THREADS, TALL>(a, sg, nodes, pf2, gb, hint, cand, cand_count, red, prof_local, block_in_prof, bpp,
-                                    &item_next, plan_cnt);
+                                    &item_next, plan_cnt, plan_consts);
         (void)t_staged;
 #ifdef PRHF_TRACE
         if (a.trace && (threadIdx.x & 63) == 0) {
@@ -3203,8 +3371,9 @@ struct SlotHeader {
                                // kSlotFinished: the queue has no block for that visit, the launch is over
     int item_next;             // run_items' counter
     int left;                  // waves that have left the current generation: the sixteenth stages the next one
-    unsigned plan_cnt[2];      // plan_pairs' counts
+    unsigned plan_cnt[3];      // plan_pairs' counts
     int cand_count[2];         // list_candidates' count (one wave)
+    double plan_consts[2];     // plan_pairs' constants of the block
     // published by the stager, read by every wave behind its acquire
     BlockInfo info;
     PlanRoom room;
@@ -3297,7 +3466,7 @@ __device__ __forceinline__ void stage_slot(const KArgs& a, const SegDev& sg, Slo
     const int prio = left > 3 * resident ? 3 : (left > 2 * resident ? 2 : (left > resident ? 1 : 0));
     if (lane == 0) {
         h->item_next = 0;
-        h->plan_cnt[0] = h->plan_cnt[1] = 0u;
+        h->plan_cnt[0] = h->plan_cnt[1] = h->plan_cnt[2] = 0u;
     }
     const long long p = sg.prof_begin + prof_local;
     BlockInfo info = stage_profile<1, LAYOUT, 64>(
@@ -3316,7 +3485,7 @@ __device__ __forceinline__ void stage_slot(const KArgs& a, const SegDev& sg, Slo
     team_mark<64, LAYOUT>(2);
     if (lane == 0 && block_in_prof == 0 && info.bad) post_status(a.status, (unsigned)info.bad);
     const PlanRoom room = plan_pairs<1, LAYOUT, false, 64>(a, sg, s.nodes, s.pf2, s.gb, s.hint, s.cand, info, block_in_prof, bpp,
-                                                           h->plan_cnt);
+                                                           h->plan_cnt, h->plan_consts);
     if (lane == 0) {
         h->info = info;
         h->room = room;

@@ -43,7 +43,8 @@ extern "C" {
                               *    prhf_residual_many_f64, prhf_vfo_residual_many_f64, and
                               *    prhf_gradient_hop_skip_f64, prhf_gradient_hop_muf_f64,
                               *    prhf_gradient_hop_skip_counters, and prhf_panel_upper_counters,
-                              *    and prhf_stream_launches, and prhf_panel_plan_counters) */
+                              *    and prhf_stream_launches, and prhf_panel_plan_counters, and
+                              *    prhf_panel_quick_counters) */
 
 /* return codes */
 #define PRHF_OK        0
@@ -165,7 +166,16 @@ int prhf_ctx_set_math(prhf_ctx* ctx, int level);
  *                        changes - from the third segment below the top one upwards - pass the tests every run passes,
  *                        which is settled from the pair alone before any of them is summed; a pair where one fails
  *                        keeps the lower region and the strided sums of those two segments, it does not fall back as a
- *                        whole on their account.  Values stay within 1e-12 of the full sum)
+ *                        whole on their account.  Values stay within 1e-12 of the full sum.  A grid whose piece of the
+ *                        strided table lies 2^26 entries - 1 GiB of pair table - or more behind the grid itself keeps
+ *                        the lower region as with 0: the main loop reads option "panel_quick" in that bit of the offset)
+ *   "panel_quick"        0: every list of the panel sum's runs puts every run to the exact tests (1: where "panel_upper"
+ *                        applies, a list - up to 63 runs of a pair's region - whose every run passes a bound from
+ *                        1 - X - Y at the two levels of its segment skips them: both levels at 1e-3 or more, and the
+ *                        index where the segment's continuation reaches X + Y = 1 at least 16 L + 10 indices beyond the
+ *                        run, L the points of the run's pieces.  The bound implies what the exact tests would find, so
+ *                        values, fall-backs and every other counter are the same under both settings;
+ *                        prhf_panel_quick_counters counts the lists of both kinds)
  *   "strided_grade"      0: the strided stretch of each of the top three segments takes every eighth point throughout, the
  *                        launch of before this option bit for bit (1: the stretch is cut into zones by the distance to
  *                        the index where the segment's continuation reaches X + Y = 1 - every 32nd point at least 1024
@@ -963,6 +973,15 @@ int prhf_panel_upper_counters(prhf_ctx* ctx, uint64_t* counters);
  * Stays 0 with option "pair_plan", "panel_lower" or "panel_upper" off, and wherever no pair is planned.  Waits for the
  * context's stream. */
 int prhf_panel_plan_counters(prhf_ctx* ctx, uint64_t* counters);
+
+/* Diagnostics of option "panel_quick", summed over every launch since the context was made: the list passes of the panel
+ * sum - one pass lists up to 63 runs of a pair's region, a pair makes two or three - in slices with option "panel_upper":
+ * counters[0] the passes whose runs all passed the quick bound and skipped the runs' exact tests, [1] the passes that
+ * took the exact tests.  [0] stays 0 with the option off; both stay 0 with option "panel_upper", "panel_lower" or
+ * "strided_lower" off and wherever no pair comes to the panel sum.  (A pair with more than 63 passes of one kind counts
+ * 63 of them; a grid of fewer than 65536 points on a profile that fits the kernel's staged arrays does not come
+ * near.)  Waits for the context's stream. */
+int prhf_panel_quick_counters(prhf_ctx* ctx, uint64_t* counters);
 
 /* Diagnostics of option "stream_blocks": *count = the operator launches of this context that took the streaming form
  * since the context was made (a launch that keeps the general kernel does not count).  Host-side; does not synchronize. */

@@ -180,6 +180,7 @@ _PROTOTYPES = {
     "prhf_panel_counters": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
     "prhf_panel_upper_counters": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
     "prhf_panel_plan_counters": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
+    "prhf_panel_quick_counters": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
     "prhf_stream_launches": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
     "prhf_occupancy": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
                                       ctypes.POINTER(ctypes.c_int32)]),
@@ -580,6 +581,13 @@ class Context:
         since this context was made (include/prhf.h)."""
         buf = (ctypes.c_uint64 * 1)()
         raise_for(self._lib.prhf_panel_plan_counters(self._h, buf))
+        return tuple(int(v) for v in buf)
+
+    def panel_quick_counters(self):
+        """(list passes of the panel sum whose runs all passed the quick bound and skipped the exact tests, list passes
+        that took the exact tests) since this context was made (option ``panel_quick``, include/prhf.h)."""
+        buf = (ctypes.c_uint64 * 2)()
+        raise_for(self._lib.prhf_panel_quick_counters(self._h, buf))
         return tuple(int(v) for v in buf)
 
     def stream_launches(self):

@@ -167,7 +167,7 @@ struct prhf_ctx {
     unsigned long long* d_words = nullptr;   // 2 words: nanmax|Y| bits, any-not-NaN
     unsigned long long* h_words = nullptr;   // pinned
     uint64_t stream_launches = 0;   // operator launches that took the streaming form since the context was made (prhf_stream_launches)
-    unsigned long long* d_plan_counters = nullptr;   // 7 words, since the context was made (prhf_pair_plan_counters, prhf_panel_counters, prhf_panel_upper_counters, prhf_panel_plan_counters)
+    unsigned long long* d_plan_counters = nullptr;   // prhf::kPlanCounterWords words, since the context was made (prhf_pair_plan_counters, prhf_panel_counters, prhf_panel_upper_counters, prhf_panel_plan_counters, prhf_panel_quick_counters)
     bool status_pending = false;
     uint64_t grad_home_counters[PRHF_GRAD_HOME_COUNTERS] = {};   // of the last prhf_gradient_home_f64 (prhf_gradient_home_counters)
     DevBuf fields;    // prhf_gradient_muf_f64: mu, mu' and the records of every link's field (48 bytes per node and link)
@@ -1021,8 +1021,8 @@ int prhf_ctx_create(int device, prhf_ctx** out) {
         (e = hipMalloc(reinterpret_cast<void**>(&c->d_words), 2 * sizeof(unsigned long long))) != hipSuccess ||
         (e = hipHostMalloc(reinterpret_cast<void**>(&c->h_words), 2 * sizeof(unsigned long long),
                            hipHostMallocDefault)) != hipSuccess ||
-        (e = hipMalloc(reinterpret_cast<void**>(&c->d_plan_counters), 7 * sizeof(unsigned long long))) != hipSuccess ||
-        (e = hipMemset(c->d_plan_counters, 0, 7 * sizeof(unsigned long long))) != hipSuccess ||
+        (e = hipMalloc(reinterpret_cast<void**>(&c->d_plan_counters), prhf::kPlanCounterWords * sizeof(unsigned long long))) != hipSuccess ||
+        (e = hipMemset(c->d_plan_counters, 0, prhf::kPlanCounterWords * sizeof(unsigned long long))) != hipSuccess ||
         (e = prhf::configure_kernels(staged_lds_bytes(kMaxAlt), kStreamLdsMax)) != hipSuccess) {
         prhf_ctx_destroy(c);
         return fail(PRHF_EHIP, "context setup failed: %s", hipGetErrorString(e));
@@ -3079,6 +3079,21 @@ int prhf_panel_plan_counters(prhf_ctx* c, uint64_t* counters) {
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipMemcpy(w, c->d_plan_counters + 6, sizeof w, hipMemcpyDeviceToHost));
     counters[0] = w[0];
+    return PRHF_OK;
+}
+
+int prhf_panel_quick_counters(prhf_ctx* c, uint64_t* counters) {
+    if (!c || !counters) return fail(PRHF_EINVAL, "null pointer");
+    DeviceScope device_scope_(c->device);
+    unsigned long long w[prhf::kQuickSlots * prhf::kQuickSlotWords];
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpy(w, c->d_plan_counters + prhf::kQuickSlotBase, sizeof w, hipMemcpyDeviceToHost));
+    // (the waves add into one of kQuickSlots slots each: run_items)
+    counters[0] = counters[1] = 0;
+    for (int s = 0; s < prhf::kQuickSlots; ++s) {
+        counters[0] += w[s * prhf::kQuickSlotWords];
+        counters[1] += w[s * prhf::kQuickSlotWords + 1];
+    }
     return PRHF_OK;
 }
 

@@ -103,7 +103,9 @@ struct SegDev {
     int tail_bpp;
     int panel_upper;                 // with panel_lower (below): the panel sum's region reaches up to the top segment's first
                                      // point where the two segments below it pass the runs' tests (option panel_upper; it sits
-                                     // here, in what was padding: the kernels' argument layout is the one of before)
+                                     // here, in what was padding: the kernels' argument layout is the one of before).
+                                     // Bit 1, set beside bit 0 only: a list of the panel sum whose runs all pass the quick
+                                     // bound skips the runs' exact tests (option panel_quick)
     // Faithful tier only: where 1 - X exceeds this at all 64 points of a wave-iteration the reduced
     // algebra is used instead of the reference's operation order (+inf: never).
     double well_conditioned;
@@ -126,6 +128,12 @@ struct SegDev {
                                      // list is made (on by default; PRHF_THREAD_SCAN_MIN turns it off for A/B runs.
                                      // O mode always does, by binary search)
 };
+
+// KArgs::plan_counters: seven words and one of padding, then kQuickSlots slots of kQuickSlotWords words (a cache line)
+// whose first two words count the list passes of the panel sum that took the quick path and the exact tests; the
+// host adds the slots up (prhf_panel_quick_counters)
+constexpr int kQuickSlots = 64, kQuickSlotWords = 8, kQuickSlotBase = 8;
+constexpr int kPlanCounterWords = kQuickSlotBase + kQuickSlots * kQuickSlotWords;
 
 struct KArgs {
     const double* freq;
@@ -167,7 +175,9 @@ struct KArgs {
     // segments took the panel sum, [3] eligible pairs that fell back (SegDev::panel_lower), [4] the pairs of [2] in
     // slices with SegDev::panel_upper, [5] those of them whose panel region stayed the lower one, added to once per wave and
     // block ([5]: once per such pair, they are few; the others' region reached the top segment), [6] the pairs of [0] whose
-    // plan carries the panel region's set-up (the record's second form), added to with [0]
+    // plan carries the panel region's set-up (the record's second form), added to with [0]; from kQuickSlotBase the slots
+    // of the panel sum's list passes in slices with SegDev::panel_upper - quick path (option panel_quick), exact tests -
+    // added to with [2]
     unsigned long long* plan_counters;
     int plan_cap;
     SegDev seg[PRHF_MAX_SEGMENTS];

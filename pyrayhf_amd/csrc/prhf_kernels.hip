@@ -169,12 +169,22 @@ constexpr int kPanelNodes4Bit = 1 << 28;
 constexpr int kStridedGradeBit = 1 << 27;
 // ... and bit 31: the panel sum's region may reach up to the top segment's first point (SegDev::panel_upper)
 constexpr int kPanelUpperBit = (int)(1u << 31);
+// ... and, beside bit 31 only, bit 26: a list of the panel sum whose runs all pass the quick bound skips the runs' exact
+// tests (option panel_quick, the second bit of SegDev::panel_upper; launch_plan keeps panel_upper to slices whose offset
+// stays below 2^26 entries, so the bit is never a bit of an offset where it is set; run_items sets it only for a profile
+// on a uniform altitude grid, whose whole pairs go to the instance that bit 31 selects, and that instance alone reads
+// and clears it - nobody else touches bit 26)
+constexpr int kPanelQuickBit = 1 << 26;
 // a part of a panel piece takes four nodes where X + Y = 1 lies at least kPanelFar n + 2 indices from its centre
 constexpr int kPanelFar = 16;
 // what the main loop reports about the panel sum in the bits above kPanelStateShift of LeanResult::first (a grid point's
 // index stays below 2^27): 1 the pair's lower segments took it, 2 the pair was eligible and kept the sum of before; with
 // option panel_upper 3 and 4 in the place of 1: the region reached the top segment, the region stayed the lower one
 constexpr int kPanelStateShift = 28;
+// ... and, where that is not 0 (the grid has fewer than 65536 points then), from bit kPanelQuickShift twice six bits: the
+// pair's list passes that took the quick path and those that took the exact tests (option panel_quick; 0 from an
+// instance without it)
+constexpr int kPanelQuickShift = 16;
 #define PRHF_PANEL_NODES_DECL [[maybe_unused]] static __device__ const double kPanelNodes[8]   // (the table's own abscissae: the pairs below hold them as offsets)
 #define PRHF_PANEL_PAIRS_DECL static __device__ __attribute__((aligned(16))) const double kPanelPairs[(PRHF_PANEL_N_MAX + 1) * 16]
 #include "prhf_panel_table.inc"
@@ -1255,6 +1265,26 @@ __device__ __forceinline__ int panel_region_end(int lo2) { return ((lo2 + 4) & ~
 __device__ __forceinline__ int panel_upper_end(int lo0) { return (lo0 + 4) & ~63; }
 // a grid point's segment, as the indexed step finds it
 __device__ __forceinline__ int panel_level(double m, double kj) { return (int)(m * kj); }
+// The quick bound of one run of the panel sum's lists (option panel_quick; DESIGN.md 4.1, "the lists' quick bound"): true
+// only where the exact tests of the panel block are sure to find both levels of the segment at 1e-6 or more, every base
+// piece clear of X + Y = 1 and the run's level 0, so that a list whose runs all pass skips those tests.  g_j and g_n are
+// 1 - X - Y at the two levels of the run's segment j, [m_lo, m_hi] = [j / kj, (j + 1) / kj] the segment, L the points of
+// the run's base pieces.  1 - X - Y = g_j - sl (m - m_lo) on the segment's continuation, sl = (g_j - g_n) kj, and the
+// index of the stretch grows by at least (N - 1) / (10 (1 - m + c0)) per unit of m: where sl >= 0, X + Y = 1 lies at
+// least D indices behind the segment's end, where sl < 0 at least D in front of its first point, D = 16 L + 10 - the
+// kPanelFar L + 2 that level 0 asks of a part's centre, and eight more for the single-precision exponential and
+// logarithm of the exact tests and the rounding of sl, which is a difference here and a sum of slopes there.  Base
+// pieces of at most four points need the levels alone.  (A NaN fails every comparison: no quick pass.)
+__device__ __forceinline__ bool panel_run_quick(double g_j, double g_n, double kj, double m_lo, double m_hi, double n1, int L) {
+#pragma clang fp contract(fast)
+    const double c0 = 1.0 / 22025.465794806718;
+    const double sl = (g_j - g_n) * kj;
+    const double D = L <= 4 ? 0.0 : (double)(kPanelFar * L + 10);
+    const bool up = sl >= 0.0;
+    const double lhs = (n1 * 0.1) * (up ? g_n : g_j);
+    const double rhs = up ? D * (sl * ((1.0 - m_hi) + c0)) : D * (g_j - sl * ((1.0 - m_lo) + c0));
+    return g_j >= 1e-3 && g_n >= 1e-3 && lhs >= rhs;
+}
 
 template <bool G>
 __device__ __forceinline__ TopSegment top_segment(const NodeSpace<G>& nodes_v, int j, double span, double cY) {
@@ -1598,7 +1628,14 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
     // (waits in a vector register, where the result travels anyway; until the panel block is through, three bits above
     //  the state's three carry the flags of option panel_upper there too - the function has no scalar register to spare)
     constexpr int kUpperKept = 16, kUpperRegion = 8;
+    // (UPPER: the option panel_quick waits there as well, in bit 5, and the pair's list passes are counted above it - those
+    //  that took the quick path from bit 8, those that took the exact tests from bit 20, twelve bits each)
+    constexpr int kQuickOn = 32, kQuickPass = 1 << 8, kExactPass = 1 << 20;
     int panel_state = 0;
+    if constexpr (UPPER) {
+        panel_state = (sp_off & kPanelQuickBit) != 0 ? kQuickOn : 0;
+        sp_off &= ~kPanelQuickBit;
+    }
     asm volatile("" : "+v"(panel_state));
     if (STRIDED && sp_off > 0 && n_seg > 0 && first == 0 && last_special >= 0 && end >= PRHF_TOP3_MIN_POINTS) {
         if constexpr (UPPER) {
@@ -1822,7 +1859,8 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
             int S_P = 0;
             constexpr int B = PRHF_PANEL_BLOCK, kLogB = B == 128 ? 7 : 6;
             const double c0 = 1.0 / 22025.465794806718;
-            panel_state = 2;
+            if constexpr (UPPER) panel_state = (panel_state & kQuickOn) | 2;
+            else panel_state = 2;
             asm volatile("" : "+v"(panel_state));
             // segment j holds at least M points where ln(a_j / (a_j - 1 / kj)) >= 10 M / (N - 1), a_j = 1 - j / kj + c0:
             // j >= kj (1 + c0) - 1 / (1 - q^M), q = exp(-10 / (N - 1)) = 1 - c1
@@ -1920,12 +1958,12 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
                         up = uniform(panel_level(gu.x, kj)) - (seg_j[0] - 1);
                     }
                     if (up == 0 || up == 1) {
-                        panel_state = 2 | kUpperRegion;
+                        panel_state |= kUpperRegion;
                         left = seg_j[0] + up - j_s;
                         e_v = upper_end();
                     } else {
                         // (the segment below the top one lies wholly above E_up, or the table is not monotone there)
-                        panel_state = 2 | kUpperKept;
+                        panel_state |= kUpperKept;
                     }
                     asm volatile("" : "+v"(e_v));
                 }
@@ -1956,6 +1994,40 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
                         q -= (q - 1) * k >= n ? 1 : 0;
                         L = k > 1 ? q : n;
                     }
+                    // The quick bound (UPPER, option panel_quick): 1 - X - Y at the two levels of every run's segment, from
+                    // the level's own density and field - the lane's and the next lane's; the lane behind the last run
+                    // reads the level that ends it - settles nearly every list (panel_run_quick): where every live run
+                    // has its first point bracketed, at most 128 base pieces and passes the bound, the exact tests below
+                    // would find nothing bad, every run at level 0 and so k entries per run, and are not made.  One run
+                    // that does not pass leaves the whole list to them.
+                    bool quick = false;
+                    if constexpr (UPPER) {
+                        asm volatile("" : "+v"(panel_state));
+                        if ((uniform(panel_state) & kQuickOn) != 0) {
+                            // (that level is at most j_top + 1 <= K: kj <= K - 1 gives j_top <= K - 1, and the staged
+                            //  table ends in a sentinel node K of zeros - g = 1 there, a level the run passes only if the
+                            //  exact tests, which see no slope in segment K - 1, pass on the lower level alone)
+                            const unsigned nq = __umul24((unsigned)(j_0 + min(lane, left)), (unsigned)sizeof(Node));
+                            const double g_j = 1.0 - cX * nodes_v.f64(nq + 16) - r2 * (cYs * nodes_v.f64(nq + 32));
+                            const double g_n = __shfl_down(g_j, 1);
+                            const bool pass = !live || (ok && k <= 128 &&
+                                                        (n == 0 || panel_run_quick(g_j, g_n, kj, (double)j_g * rkj,
+                                                                                   (double)(j_g + 1) * rkj, n1, L)));
+                            quick = __ballot(!pass) == 0ull;
+                        }
+                    }
+                    int lvl = 0, cnt = 0;                      // the run's level and entries
+                    // (a jump and not a branch around the tests: the instance without the option keeps the text it had)
+                    if constexpr (UPPER) {
+                        if (quick) {
+                            cnt = n > 0 ? k : 0;
+                            fail = false;
+                            panel_state += kQuickPass;
+                            goto listed;
+                        }
+                        panel_state += kExactPass;
+                    }
+                    {
                     // guard, from the segment's node: 1 - X - Y = gap - sl m on its continuation (strided_run)
                     const unsigned nd = __umul24((unsigned)j_g, (unsigned)sizeof(Node));
                     const double o = nodes_v.f64(nd + 8), den = nodes_v.f64(nd + 16), sden = nodes_v.f64(nd + 24),
@@ -1989,7 +2061,6 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
                     // against that at the index so far from the centre; multiplied by sl both sides read the same (no
                     // logarithm, no division; the two spare indices cover the single-precision exponential).  Nearly
                     // every run passes at lvl = 0: one trip.
-                    int lvl = 0;
                     if (nodes4_req) {
                         bool open = n > 0;
                         for (int t = 0;; ++t) {
@@ -2005,8 +2076,7 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
                             if (__ballot(open) == 0ull) break;
                         }
                     }
-                    const int cnt = n > 0 ? k << lvl : 0;      // the run's entries
-                    // (what a lane found waits in a vector register for the rare list with a run that fails)
+                    cnt = n > 0 ? k << lvl : 0;
                     if constexpr (UPPER) {
                         // (what a lane found waits in a vector register for the rare list with a run that fails)
                         int bad_v = (live && !ok) || (big && !clear) || cnt > 128 ? 1 : 0;
@@ -2020,7 +2090,7 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
                             if (!upper_now() || __ballot(bad_v != 0 && j_g < seg_j[0] - 3) != 0ull) break;
                             fail = false;
                             if (left <= 63) {
-                                panel_state = 2 | kUpperKept;
+                                panel_state = (panel_state & ~kUpperRegion) | kUpperKept;
                                 e_v = region_end();
                                 left = uniform(j_e_lo) - j_0 + 1;
                                 continue;
@@ -2030,6 +2100,8 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
                         fail = __ballot((live && !ok) || (big && !clear) || cnt > 128) != 0ull;
                         if (fail) break;
                     }
+                    }
+                listed: __attribute__((unused));
                     // The list the evaluation reads: entry e in lane e & 63 of lst_a (e < 64) or lst_b, up to 128 entries
                     // of as many consecutive runs as fit.  Nearly always every run is its own single entry and the list
                     // is the lanes' own words; else (a scalar branch) an entry finds its run by bisection in the running
@@ -2156,7 +2228,8 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
             //  variables, n_R < 0 says that the panel sum has taken it)
             if constexpr (UPPER) {
                 const int flags = uniform(panel_state);
-                panel_state = !panel_ok ? 2 : ((flags & kUpperRegion) != 0 ? 3 : 4);
+                // (the counts of the list passes stay where they are)
+                panel_state = (flags & ~(kQuickPass - 1)) | (!panel_ok ? 2 : ((flags & kUpperRegion) != 0 ? 3 : 4));
                 asm volatile("" : "+v"(panel_state));
                 if (panel_ok) {
                     S_R = S_P;
@@ -2285,7 +2358,7 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
     if (TOP) {
         // (one copy of the two loops: the run's bounds are picked with scalar selects, not by unrolling)
         // (a pair whose panel sum reached the top segment has that segment left, option panel_upper)
-        const int sidx_0 = UPPER && uniform(panel_state) == 3 ? 0 : n_seg - 1;
+        const int sidx_0 = UPPER && (uniform(panel_state) & 7) == 3 ? 0 : n_seg - 1;
 #pragma unroll 1
         for (int sidx = sidx_0; sidx >= 0 && !(CHECK && viol); --sidx) {
             // (the runs' bounds from the segments' first points, as the search set them - a whole pair begins at grid point
@@ -2337,7 +2410,16 @@ __device__ __forceinline__ LeanResult lean_loop_body(typename NodeArg<G>::type n
     }
     LeanResult r;
     r.acc = accm * span;                               // :415: dh = (m_i+1 - m_i) * span
-    r.first = first | (panel_state << kPanelStateShift);
+    if constexpr (UPPER) {
+        // (a pair that came to the panel block has fewer than 65536 points: the counts of its list passes, at most 63 of
+        //  either kind, travel in the twelve bits above the sixteen of `first`; integrate_chunk takes them apart)
+        const unsigned ps = (unsigned)uniform(panel_state);
+        const unsigned n_quick = min((ps >> 8) & 0xfffu, 63u), n_exact = min(ps >> 20, 63u);
+        r.first = first | (int)((ps & 7u) << kPanelStateShift) | (int)(n_quick << kPanelQuickShift) |
+                  (int)(n_exact << (kPanelQuickShift + 6));
+    } else {
+        r.first = first | (panel_state << kPanelStateShift);
+    }
     return r;
 }
 
@@ -2471,6 +2553,14 @@ __device__ __forceinline__ double integrate_chunk(const Node* __restrict__ nodes
                 first = uniform(r.first) & ((1 << kPanelStateShift) - 1);
             }
             panel_state = uniform(r.first) >> kPanelStateShift;
+            if constexpr (MODE == PRHF_KMODE_X && TIER == 1 && !G) {
+                // (the counts of the pair's list passes ride above the sixteen bits of `first`, kPanelQuickShift: to the
+                //  caller above the state's four bits)
+                if (panel_state != 0) {
+                    panel_state |= ((uniform(r.first) >> kPanelQuickShift) & 0xfff) << 4;
+                    first &= 0xffff;
+                }
+            }
         }
     }
     // Generic loop over [first, i1).  Its wave-iterations are aligned to the END of the range - a short first
@@ -3054,12 +3144,17 @@ __device__ __forceinline__ void run_items(const KArgs& a, const SegDev& sg, cons
     const double2* pairs = (a.pairs && sg.lean) ? reinterpret_cast<const double2*>(a.pairs) + sg.mult_off : nullptr;
     // the strided table's piece of this slice's grid, in entries from `pairs`; 0: none
     // (bit 30: the segments below the top three take the strided sum too - an offset stays below 2^27 entries)
-    // (bit 31 is one of them: whoever uses the offset masks the bits off first, lean_loop_body)
+    // (bit 31 is one of them: whoever uses the offset masks the bits off first, lean_loop_body; bit 26 beside bit 31 is
+    //  another - launch_plan sets SegDev::panel_upper only where the offset stays below 2^26)
     const int sp_off = (pairs && sg.sp_off > 0)
                            ? uniform((int)(sg.sp_off - sg.mult_off) | (sg.strided_lower ? kStridedLowerBit : 0) |
                                      (sg.strided_lower && sg.panel_lower ? kPanelLowerBit : 0) |
                                      (sg.strided_lower && sg.panel_lower && sg.panel_nodes == 4 ? kPanelNodes4Bit : 0) |
                                      (!G && sg.strided_lower && sg.panel_lower && sg.panel_upper ? kPanelUpperBit : 0) |
+                                     // (... and never for a profile on the hint table, whose instances of the loop
+                                     //  function do not know the bit: left on, it is 2^26 entries of offset to them)
+                                     (!G && info.uniform && sg.strided_lower && sg.panel_lower && (sg.panel_upper & 2)
+                                          ? kPanelQuickBit : 0) |
                                      (sg.strided_grade ? kStridedGradeBit : 0)) : 0;
     const long long pair_base = prof_local * F;
     const int first_item = block_in_prof * W, round_items = blocks_per_prof * W;
@@ -3082,8 +3177,27 @@ __device__ __forceinline__ void run_items(const KArgs& a, const SegDev& sg, cons
     double* part = red + 10 * W + 8;                   // (behind the kept scalars; rows 0 .. 9 may still be read by a
     if (local && lane == 0) part[wave] = 0.0;          //  wave that left stage_profile early)
     int pulled = 0;                                    // how many items this workgroup had pulled before the current one
-    int panel_cnt = 0;                                 // pairs of this wave whose lower segments took the panel sum (low half:
-                                                       // a wave pulls far fewer than 65536 items of a block) / fell back (high)
+    // Four counts of this wave in one register, eight bits each: pairs whose lower segments took the panel sum (from bit 0)
+    // and eligible pairs that fell back (bit 8), list passes of the panel sum that took the quick path (bit 16) and that
+    // took the exact tests (bit 24).  An item adds at most 1, 1, 63 and 63; the counts go to the launch's counters where
+    // one of them has reached 128, and behind the last item.
+    unsigned panel_cnt = 0u;
+    auto flush_panel_cnt = [&]() {
+        if (lane == 0 && a.plan_counters) {
+            const unsigned took = panel_cnt & 0xffu, fell = (panel_cnt >> 8) & 0xffu;
+            const unsigned n_quick = (panel_cnt >> 16) & 0xffu, n_exact = panel_cnt >> 24;
+            if (took) atomicAdd(&a.plan_counters[2], (unsigned long long)took);
+            if (fell) atomicAdd(&a.plan_counters[3], (unsigned long long)fell);
+            if (sg.panel_upper && took) atomicAdd(&a.plan_counters[4], (unsigned long long)took);
+            // (the list passes into one of kQuickSlots pairs of words, a cache line each, by workgroup - a scalar address:
+            //  two more adds to one address from every wave and block cost the headline launch 0.66 ms, the waves wait
+            //  for them at their next load, where the three adds above cost what they did)
+            unsigned long long* slot = a.plan_counters + kQuickSlotBase + (blockIdx.x & (kQuickSlots - 1)) * kQuickSlotWords;
+            if (n_quick) atomicAdd(slot, (unsigned long long)n_quick);
+            if (n_exact) atomicAdd(slot + 1, (unsigned long long)n_exact);
+        }
+        panel_cnt = 0u;
+    };
     auto next_item = [&]() {
         const int u = uniform(atomicAdd(item_next, 1)) >> 6;
         pulled = u;
@@ -3133,11 +3247,15 @@ __device__ __forceinline__ void run_items(const KArgs& a, const SegDev& sg, cons
             }
         }
         if constexpr (MODE == PRHF_KMODE_X && TIER == 1 && !G) {
-            panel_cnt += panel == 2 ? 0x10000 : (panel != 0 ? 1 : 0);
+            // (the state in the low four bits, above it the pair's list passes: six bits quick, six bits exact)
+            const int state = panel & 15;
+            panel_cnt += (state == 2 ? 0x100u : (state != 0 ? 1u : 0u)) | (((unsigned)panel >> 4) & 63u) << 16 |
+                         (((unsigned)panel >> 10) & 63u) << 24;
+            if ((panel_cnt & 0x80808080u) != 0u) flush_panel_cnt();
             // (option panel_upper: with it a pair that took the panel sum reports 3, its region reached the top segment, or 4,
             //  it kept the lower one.  The few of the second kind are counted one by one, and all of them once per wave below:
             //  no third count waits in a register across the items, of which the kernel has none to spare)
-            if (panel == 4 && lane == 0 && a.plan_counters) atomicAdd(&a.plan_counters[5], 1ull);
+            if (state == 4 && lane == 0 && a.plan_counters) atomicAdd(&a.plan_counters[5], 1ull);
         }
         if (lane == 0) {
             if (local) {
@@ -3152,11 +3270,7 @@ __device__ __forceinline__ void run_items(const KArgs& a, const SegDev& sg, cons
         }
     }
     if constexpr (MODE == PRHF_KMODE_X && TIER == 1 && !G) {
-        if (lane == 0 && a.plan_counters) {
-            if (panel_cnt & 0xffff) atomicAdd(&a.plan_counters[2], (unsigned long long)(panel_cnt & 0xffff));
-            if (panel_cnt >> 16) atomicAdd(&a.plan_counters[3], (unsigned long long)(panel_cnt >> 16));
-            if (sg.panel_upper && (panel_cnt & 0xffff)) atomicAdd(&a.plan_counters[4], (unsigned long long)(panel_cnt & 0xffff));
-        }
+        if (panel_cnt != 0u) flush_panel_cnt();
     }
     if (local) {
         __syncthreads();

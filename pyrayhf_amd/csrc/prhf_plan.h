@@ -100,6 +100,11 @@ struct Knobs {
                                        // the top one upwards pass the tests of the panel sum's runs; the other pairs keep the lower region and
                                        // the strided sums of those two segments (0: the launch of before, bit
                                        // for bit)
+    double panel_quick = 1;            // ... and a list of the panel sum's runs whose every run passes a bound from 1 - X - Y at
+                                       // its segment's two levels - X + Y = 1 at least 16 L + 10 indices beyond the run,
+                                       // both levels at 1e-3 or more - skips the runs' exact tests, which would find
+                                       // nothing (0: the exact tests for every list; values never depend
+                                       // on it)
     double strided_grade = 1;          // ... and the strided stretch of each of the top three segments is cut into zones:
                                        // every 32nd point at least 1024 indices below the index where the segment's
                                        // continuation reaches X + Y = 1 and where 1 - X - Y >= 1.6e-4, every 16th at
@@ -157,6 +162,7 @@ const KnobName kKnobNames[] = {
     {"panel_lower", &Knobs::panel_lower, 0, 1},
     {"panel_nodes", &Knobs::panel_nodes, 4, 8},
     {"panel_upper", &Knobs::panel_upper, 0, 1},
+    {"panel_quick", &Knobs::panel_quick, 0, 1},
     {"strided_grade", &Knobs::strided_grade, 0, 1},
     {"pair_plan", &Knobs::pair_plan, 0, 1},
     {"pair_plan_cap", &Knobs::pair_plan_cap, 0, 1024},
@@ -603,7 +609,10 @@ inline int plan_launch(const LaunchShape& sh, const prhf_segment* segs, int32_t 
             s.strided_lower = kn.strided_lower != 0;
             s.panel_lower = s.strided_lower && kn.panel_lower != 0;
             s.panel_nodes = s.panel_lower && kn.panel_nodes == 4 ? 4 : 8;
-            s.panel_upper = s.panel_lower && kn.panel_upper != 0;
+            // (bit 1: option panel_quick.  The main loop's instance for panel_upper reads that option in bit 26 of the
+            //  piece's offset from the slice's grid: a piece 2^26 entries - 1 GiB - or more away keeps the lower region)
+            s.panel_upper = s.panel_lower && kn.panel_upper != 0 && s.sp_off - s.mult_off < (1LL << 26)
+                                ? 1 | (kn.panel_quick != 0 ? 2 : 0) : 0;
             s.strided_grade = kn.strided_grade != 0;
             s.pair_plan = slice_plans_pairs(s, tall, n_freq, lds_levels, kn) ? 1 : 0;
             pl.any_plan = pl.any_plan || s.pair_plan != 0;

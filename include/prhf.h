@@ -276,19 +276,24 @@ int prhf_vfo_worklist_f64(prhf_ctx* ctx,
  * PRHF_FLAG_GRID_STABLE (accepted; these kernels keep no table of the grid), PRHF_FLAG_SHARED_FIELD.
  *
  * Conventions:
- *   - a pair that has no virtual height (vh NaN: the frequency is not reflected) has a row of zeros; grad_vh is not
- *     read at such a pair, so a NaN there does no harm;
- *   - levels at and above the density peak (k >= argmax den) get 0;
+ *   - a pair that has no virtual height (vh NaN: the frequency is not reflected - or a NaN altitude, a NaN |B| below the
+ *     peak in X mode, every term skipped) has a row of zeros; grad_vh is not read at such a pair, so a NaN there does no
+ *     harm;
+ *   - levels at and above the density peak (k >= argmax den, the first NaN density ranking highest) get 0;
  *   - a one-level bottomside (the peak at level 1) whose frequency escapes also has a row of zeros: the value np.interp's
  *     one-node rule gives such a pair in the reference, mu'(level 0) * 1e-6, is not differentiated;
- *   - grid points whose term the reference's sum skips (NaN, library.py:288) are constants;
+ *   - grid points whose term the reference's sum skips (NaN, library.py:288: a NaN |B| or psi next to the point,
+ *     mu^2 < 0, mu > 1 - library.py:233, :238) are constants;
  *   - the unmagnetised branch (library.py:201-207, decided per profile as in prhf_vfo_batch_f64) is differentiated as
  *     mu' = (1 - X)^(-1/2);
  *   - the operator has kinks - a grid point exactly on a level, a tie in the density's argmax or in the running maximum,
  *     a running maximum of exactly 1 at a level; there the result is one of the one-sided derivatives, which one is
  *     unspecified.
  * The arithmetic is the same in every math tier (IEEE divide and square root).  Results are reproducible bit for bit:
- * they do not depend on scheduling, on the other profiles of the launch, or on repetition; no atomics are used.
+ * they do not depend on scheduling, on the other profiles of the launch, or on repetition; no atomics are used.  (One
+ * exception: the VJP adds its frequencies on four waves up to 908 staged levels, on two or one above, and the levels
+ * staged are those of the launch's highest peak - above 908 a profile's grad_den_out row depends on the launch in the
+ * rounding of that sum.  Jacobian rows do not.)
  * Limits: the levels below the highest density peak of the launch, plus the per-wave accumulator rows, must fit in LDS:
  * about 1200 levels up to the peak (n_alt itself may be larger: a pre-pass then finds the peak, one synchronisation).
  * A taller bottomside is refused with PRHF_EINVAL ("... stages at most N levels ...").  Mixed work lists are not

@@ -53,7 +53,7 @@ __device__ __forceinline__ void wave_lds_order() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// mu' below the reflection height from X, Y^2, sin^2 psi, cos^2 psi; *ok: D > 0 and mu^2 > 0 (library.py:233)
+// mu' below the reflection height from X, Y^2, sin^2 psi, cos^2 psi; *ok: D > 0 and 0 < mu^2 <= 1 (library.py:233, :238)
 template <int MODE>
 __device__ __forceinline__ Dual group_index_dual(Dual X, Dual Y2, Dual S2, Dual C2, bool* ok) {
 #pragma clang fp contract(off)
@@ -73,7 +73,9 @@ __device__ __forceinline__ Dual group_index_dual(Dual X, Dual Y2, Dual S2, Dual 
     const Dual Nw = N * w;
     const Dual q = 1.0 - Nw * Nw;                              // 1 - mu^2
     const Dual U = Sp1 * q + (D - X);
-    *ok = D.v > 0.0 && N.v * D.v > 0.0;
+    // (mu^2 = N / D; with D, N > 0 it exceeds 1 exactly where a < 0: X > 1 on a grid collapsed onto level 0 below the
+    //  gyrofrequency - the reference makes such a term NaN, library.py:238)
+    *ok = D.v > 0.0 && N.v * D.v > 0.0 && a.v >= 0.0;
     return w * U;
 }
 

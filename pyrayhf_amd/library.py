@@ -531,8 +531,10 @@ def vertical_jacobian(freq, den, bmag, bpsi, alt, mode='O', n_points=200, *, dev
     which are used in place on torch's current stream and give tensors (``sync=False``: do not wait).  ``vh`` is the
     operator's own output, bit for bit.
 
-    Conventions: a pair without a virtual height (``vh`` NaN) has a row of zeros; levels at and above the density peak
-    get 0; grid points the reference's sum skips (NaN terms) count as constants; an unmagnetised profile is
+    Conventions: a pair without a virtual height (``vh`` NaN, whatever made it so: no reflection, a NaN altitude, a NaN
+    ``|B|`` below the peak in X mode, every term skipped) has a row of zeros; levels at and above the density peak - the
+    first NaN density counts as the peak - get 0; grid points the reference's sum skips (NaN terms: a NaN ``|B|`` or
+    ``bpsi`` next to the point, mu^2 < 0, mu > 1) count as constants; an unmagnetised profile (``nanmax|Y| < 1e-12``) is
     differentiated as ``mu' = (1 - X)^(-1/2)``; at a kink of the operator (a grid point exactly on a level, a tie in the
     density's argmax or in the running maximum, a running maximum of exactly 1) the result is one of the one-sided
     derivatives.  The arithmetic does not depend on the ``math`` tier.  ``ValueError`` when the levels below the highest
@@ -579,7 +581,10 @@ def vertical_vjp(freq, den, bmag, bpsi, alt, grad_vh, mode='O', n_points=200, *,
 
     Inputs and conventions as ``vertical_jacobian``; ``grad_vh`` is not read where a pair has no virtual height, so a
     NaN there does no harm.  Returns ``(N_alt,)`` or ``(P, N_alt)``, a tensor for GPU-resident torch inputs.  The result
-    is reproducible bit for bit (no atomics; a profile's row does not depend on the rest of the batch).
+    is reproducible bit for bit (no atomics).  A profile's row does not depend on the rest of the batch as long as the
+    batch stages at most 908 levels; above that the frequencies are added by two waves or one instead of four, in another
+    order, and the levels staged are those up to the batch's highest peak - the row then moves within the rounding of a
+    sum of F terms.  Jacobian rows and JVP columns do not depend on it at any height.
     """
     code = _mode_code(mode)
     mult_np = _multiplier(n_points)

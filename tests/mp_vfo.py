@@ -40,6 +40,18 @@ def _consts():
     return mpf(float(PLASMA_CONST)), mpf(float(GYRO_CONST)), mpf(float(BACKOFF))
 
 
+def unmagnetised(freq_mhz, den, bmag):
+    """The isotropic decision of library.py:201 for one call: nanmax|Y| < 1e-12, a NaN |B| not counting (all NaN: False).
+    |Y| is largest at the call's lowest frequency and, between levels, no larger than at a level."""
+    K = int(np.argmax(np.asarray(den, dtype=np.float64)))
+    b = np.abs(np.asarray(bmag, dtype=np.float64)[:K])
+    b = b[~np.isnan(b)]
+    if b.size == 0:
+        return False
+    f = float(np.min(np.abs(np.atleast_1d(np.asarray(freq_mhz, dtype=np.float64))))) * 1e6
+    return bool(float(GYRO_CONST) * float(b.max()) / f < UNMAG_TOL)
+
+
 def _interp(z, xp, fp):
     """np.interp for one abscissa: left / right clamps, x == xp[j] returns fp[j], bracket xp[j] <= z < xp[j+1]."""
     n = len(xp)
@@ -102,7 +114,8 @@ def _mup(X, Y, psi_deg, mode, unmag):
     dD_dY = -YT * s + sign * dbeta_dY
     dmu_dY = (X * Xm1 * dD_dY) / (2 * mu * D ** 2)
     dmu_dX = (1 / (2 * mu * D)) * (2 * X - 1 + X * Xm1 / D * dD_dX)
-    return mu - (2 * X * dmu_dX + Y * dmu_dY)
+    mup = mu - (2 * X * dmu_dX + Y * dmu_dY)
+    return None if mpmath.isnan(mup) else mup              # a NaN |B| or psi: the term is skipped by nansum (:288)
 
 
 class Pair:
@@ -125,7 +138,7 @@ class Pair:
         self.mode = mode
         if unmag is None:
             # :201 - nanmax|Y| over the call's array; callers with several frequencies pass the call-wide answer
-            unmag = float(GYRO_CONST) * float(np.max(np.abs(np.asarray(bmag)[:K]))) / (float(freq_mhz) * 1e6) < UNMAG_TOL
+            unmag = unmagnetised(freq_mhz, den, bmag)
         self.unmag = bool(unmag)
 
     # -- reflection ----------------------------------------------------------------------
@@ -141,6 +154,8 @@ class Pair:
         """(reflects, j, jm, r_j, r_j1): np.interp's bracket of 1.0 in the running maximum, and the level jm <= j where
         that running maximum was attained first.  j = -1: left clamp; j = K - 1: the last level is hit exactly."""
         c = self._cond(self.den if den is None else den)
+        if any(mpmath.isnan(v) for v in c):            # np.maximum.accumulate carries a NaN to the last level: no reflection
+            return False, None, None, None, None
         run, arg, best, bi = [], [], None, -1
         for k, v in enumerate(c):
             if best is None or v > best:
@@ -157,6 +172,8 @@ class Pair:
         return True, j, arg[j], run[j], run[j + 1]
 
     def height(self, den=None):
+        if mpmath.isnan(self.alt_min):                 # min(alt) is added to every sum (:292): no pair has a value
+            return None
         ok, j, _, rj, rj1 = self.bracket(den)
         if not ok:
             return None

@@ -4,12 +4,11 @@ such error of the float64 NumPy restatement (tests/vfo_jacobian_numpy.py) - the 
 last bits, not another algorithm.  Every row of the fixture is checked.  The measured errors go to
 profiles/jacobian_parity.md."""
 
-import os
-
 import numpy as np
 import pytest
 
-from conftest import REPO, load_golden, same_bits
+from conftest import load_golden, same_bits
+from parity_report import put_section
 from pyrayhf_amd import library
 
 pytestmark = pytest.mark.gpu
@@ -57,11 +56,7 @@ def test_every_row_within_four_times_the_float64_restatement(g26, computed):
                 failures.append((name, i, err))
     lines += ["", f"Worst: O {worst['O']:.3e} ({worst['O'] / e_ref['O']:.2f} x e_ref), "
               f"X {worst['X']:.3e} ({worst['X'] / e_ref['X']:.2f} x e_ref)."]
-    try:
-        with open(os.path.join(REPO, "profiles", "jacobian_parity.md"), "w") as fh:
-            fh.write("\n".join(lines) + "\n")
-    except OSError:                                    # (a read-only checkout: the printed figures remain)
-        pass
+    put_section(lines, first=True)                     # (the other files' sections of the report stay)
     assert not failures, failures
 
 

@@ -7,12 +7,11 @@ density peak (the only ones J is non-zero at); the restatement's own J @ t stays
 Nothing is compared with finite differences of the operator (they do not converge).  The measured ratios
 are appended to profiles/jacobian_parity.md."""
 
-import os
-
 import numpy as np
 import pytest
 
-from conftest import REPO, load_golden, same_bits
+from conftest import load_golden, same_bits
+from parity_report import put_section
 from pyrayhf_amd import library, synth
 
 pytestmark = pytest.mark.gpu
@@ -53,18 +52,9 @@ def computed(g26):
 
 
 def _append_table(lines):
-    """Put the section under HEADING at the end of profiles/jacobian_parity.md; what is there stays (an earlier copy of
-    this section is replaced)."""
-    path = os.path.join(REPO, "profiles", "jacobian_parity.md")
-    try:
-        text = open(path).read() if os.path.exists(path) else ""
-        if HEADING in text:
-            text = text[:text.index(HEADING)]
-        text = text.rstrip("\n") + "\n\n" if text.strip() else ""
-        with open(path, "w") as fh:
-            fh.write(text + "\n".join(lines) + "\n")
-    except OSError:                                    # (a read-only checkout: the printed figures remain)
-        pass
+    """Put the section under HEADING into profiles/jacobian_parity.md; the other sections stay (an earlier copy of this
+    one is replaced)."""
+    put_section(lines)
 
 
 def test_every_jacobian_column_within_the_jacobian_kernels_bound(g26, computed):

@@ -18,6 +18,15 @@ UNMAG_TOL = 1e-12
 DEG = 0.017453292519943295
 
 
+def unmagnetised(freq_mhz, bottom_bmag):
+    """nanmax|Y| < 1e-12 over the call (library.py:201): a NaN |B| does not count; all NaN: magnetised."""
+    b = np.abs(np.asarray(bottom_bmag, dtype=np.float64))
+    b = b[~np.isnan(b)]
+    if b.size == 0:
+        return False
+    return bool(GYRO_CONST * b.max() / (np.min(np.abs(np.atleast_1d(freq_mhz))) * 1e6) < UNMAG_TOL)
+
+
 class Dual:
     """value + two tangents, elementwise on arrays."""
 
@@ -90,12 +99,15 @@ def group_index_dual(X, Y2, S2, C2, mode):
     q = 1.0 - Nw * Nw
     U = Sp1 * q + (D - X)
     mup = w * U
-    ok = (D.v > 0.0) & (N.v * D.v > 0.0)
+    # (mu^2 = N / D > 1 exactly where X > 1 - a grid collapsed onto a level above the cutoff, below the gyrofrequency:
+    #  library.py:238 makes the term NaN)
+    ok = (D.v > 0.0) & (N.v * D.v > 0.0) & (a.v >= 0.0)
     return mup, ok
 
 
 def jacobian_row(freq_mhz, den, bmag, bpsi, alt, mode, mult, unmag=None):
-    """(vh, row (n_alt,)): the analytic derivative of the discrete sum for one pair.  Zeros for a pair without a value."""
+    """(vh, row (n_alt,)): the analytic derivative of the discrete sum for one pair.  A pair without a value - whatever
+    made vh NaN, min(alt) included - has a row of (finite) zeros."""
     den, bmag, bpsi, alt = (np.asarray(x, dtype=np.float64) for x in (den, bmag, bpsi, alt))
     m = np.asarray(mult, dtype=np.float64)
     n_alt, n = den.size, m.size
@@ -109,7 +121,7 @@ def jacobian_row(freq_mhz, den, bmag, bpsi, alt, mode, mult, unmag=None):
     cX = (PLASMA_CONST * PLASMA_CONST) / f2
     cY = GYRO_CONST / f
     if unmag is None:
-        unmag = GYRO_CONST * np.max(np.abs(b)) / f < UNMAG_TOL
+        unmag = unmagnetised(freq_mhz, b)
     with np.errstate(all="ignore"):
         fn = np.sqrt(d) * PLASMA_CONST
         c = (fn * fn) / f2
@@ -177,16 +189,18 @@ def jacobian_row(freq_mhz, den, bmag, bpsi, alt, mode, mult, unmag=None):
         if K > 1:
             dX[idx, s + 1] += tt
         dX += np.outer(m * sden, Hk)
+        vh = total + np.min(alt)
+        if not np.isfinite(vh):                                         # (a NaN altitude)
+            return np.nan, row
         row[:K] = (GX[:, None] * dX).sum(axis=0) + SH * Hk
-    return total + np.min(alt), row
+    return vh, row
 
 
 def jacobian(freq_mhz, den, bmag, bpsi, alt, mode, mult):
     """(vh (F,), J (F, n_alt)) for one profile; the isotropic branch is decided for the call, as the reference does."""
     freq = np.atleast_1d(np.asarray(freq_mhz, dtype=np.float64))
     K = int(np.argmax(den))
-    bmax = np.max(np.abs(np.asarray(bmag)[:K])) if K else 0.0
-    unmag = GYRO_CONST * bmax / (np.min(np.abs(freq)) * 1e6) < UNMAG_TOL
+    unmag = unmagnetised(freq, np.asarray(bmag)[:K]) if K else True
     vh = np.empty(freq.size)
     J = np.zeros((freq.size, np.asarray(den).size))
     for i, fm in enumerate(freq):

@@ -952,6 +952,12 @@ int prhf_gradient_hop_muf_f64(prhf_ctx* ctx, int32_t geometry, const double* den
  * one-hop call.  Per slot a lane traced [4] / [2] hops.  No device call. */
 int prhf_gradient_hop_skip_counters(prhf_ctx* ctx, uint64_t* counters);
 
+/* The five diagnostics below (prhf_pair_plan_counters, prhf_panel_counters, prhf_panel_upper_counters,
+ * prhf_panel_plan_counters, prhf_panel_quick_counters) read words that the operator's kernels add to once per workgroup,
+ * when the workgroup leaves the kernel: a launch's counts are complete once the launch has finished - each of the five
+ * waits for the context's stream, so what it returns is - and a launch in flight has added only the workgroups that
+ * have left.  A call that returns a data error (a status of the profiles) has counted its other profiles all the same. */
+
 /* Diagnostics of option "pair_plan", summed over every launch since the context was made: counters[0] reflecting pairs
  * whose sum ran from a plan made by one thread, [1] pairs of the same slices that computed their plan themselves (no
  * room for the plan, or a guess that did not bracket).  Pairs of slices that are not eligible count in neither.

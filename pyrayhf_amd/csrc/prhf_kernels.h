@@ -170,14 +170,14 @@ struct KArgs {
     // Levels the staged arrays (nodes, f_N^2, g_p |B|) have room for: n_alt, or - a column of more than 1400 levels
     // whose bottomsides all fit LDS (launch_peak_levels) - the highest peak index of the launch + 1
     long long lds_levels;
-    // The planning pass (SegDev::pair_plan): [0] pairs that ran from a plan, [1] eligible pairs that planned themselves,
-    // added to once per workgroup and block; plan_cap > 0 caps the records per workgroup (tests).  [2] pairs whose lower
-    // segments took the panel sum, [3] eligible pairs that fell back (SegDev::panel_lower), [4] the pairs of [2] in
-    // slices with SegDev::panel_upper, [5] those of them whose panel region stayed the lower one, added to once per wave and
-    // block ([5]: once per such pair, they are few; the others' region reached the top segment), [6] the pairs of [0] whose
-    // plan carries the panel region's set-up (the record's second form), added to with [0]; from kQuickSlotBase the slots
-    // of the panel sum's list passes in slices with SegDev::panel_upper - quick path (option panel_quick), exact tests -
-    // added to with [2]
+    // The planning pass (SegDev::pair_plan): [0] pairs that ran from a plan, [1] eligible pairs that planned themselves;
+    // plan_cap > 0 caps the records per workgroup (tests).  [2] pairs whose lower segments took the panel sum, [3] eligible
+    // pairs that fell back (SegDev::panel_lower), [4] the pairs of [2] in slices with SegDev::panel_upper, [5] those of
+    // them whose panel region stayed the lower one (the others' region reached the top segment), [6] the pairs of [0] whose
+    // plan carries the panel region's set-up (the record's second form); from kQuickSlotBase the slots of the panel sum's
+    // list passes in slices with SegDev::panel_upper - quick path (option panel_quick), exact tests.  A workgroup counts
+    // in its LDS (WgCounts in prhf_kernels.hip) and adds its words here once, when it leaves the kernel: the words are
+    // complete when the launch has finished.  Null: nothing is added
     unsigned long long* plan_counters;
     int plan_cap;
     SegDev seg[PRHF_MAX_SEGMENTS];

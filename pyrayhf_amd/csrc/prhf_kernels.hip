@@ -3036,15 +3036,48 @@ __device__ __attribute__((noinline)) int plan_pair(const Node* nodes, int K, con
     return 1;
 }
 
+// What a workgroup counts for KArgs::plan_counters, in LDS for the workgroup's life: zeroed once in front
+// of its first block, added to by plan_pairs and run_items, added to the launch's words once when the workgroup leaves
+// (flush_counts).  The words sit behind run_items' item counter, which both functions' callers already hand down: an
+// LDS add at a constant offset, no register, nothing on vmcnt.
+// No count is lost: a word grows by at most 2^20 frequencies x 63 list passes < 2^26 per block, a workgroup runs at
+// most the launch's 2^31 blocks, so a 64-bit word stays below 2^57 whatever the ABI admits; the launch's words are
+// 64-bit as before.
+struct WgCounts {
+    int item_next;                             // run_items' counter, zeroed per block
+    int pad;
+    // [0] pairs that ran from a plan, [1] that planned themselves, [2] whose lower segments took the panel sum, [3] that
+    // fell back, [4] those of [2] under panel_upper, [5] those of them that kept the lower region, [6] those of [0] whose
+    // plan has the second form (KArgs::plan_counters' words [0..6]); [7], [8] list passes on the quick path and on the
+    // exact tests (the workgroup's quick slot)
+    unsigned long long n[9];
+};
+constexpr int kWgCountWords = 9;
+
+__device__ __forceinline__ void zero_counts(WgCounts* c, int tid) {
+    if (tid < kWgCountWords) c->n[tid] = 0ull;
+}
+
+// Thread `tid` < kWgCountWords of a workgroup that is leaving the kernel adds one word of its counts (the streaming
+// form: of both slots' counts) to the launch's.  Behind a barrier that every wave of the workgroup has passed.
+__device__ __forceinline__ void flush_counts(const KArgs& a, const WgCounts* c0, const WgCounts* c1, int tid) {
+    if (tid >= kWgCountWords || !a.plan_counters) return;
+    const unsigned long long v = c0->n[tid] + (c1 ? c1->n[tid] : 0ull);
+    if (v == 0ull) return;
+    unsigned long long* dst = tid < 7 ? a.plan_counters + tid
+                                      : a.plan_counters + kQuickSlotBase + (blockIdx.x & (kQuickSlots - 1)) * kQuickSlotWords + (tid - 7);
+    atomicAdd(dst, v);
+}
+
 // The planning pass: after the candidate list, before the items.  Thread i plans the i-th item this
 // workgroup will pull (a profile cut into several workgroups: each plans its own share).  Eligible: what the strided
 // sum requires - X mode, fast tier, whole pairs of PRHF_TOP3_MIN_POINTS .. 65535 points on the reference's stretch
-// (header word 0) - with heights settled per thread and a uniform altitude grid.  Counts, once per workgroup, the
-// main-loop pairs that got a plan and those that will plan themselves (no room, guess not bracketing).
+// (header word 0) - with heights settled per thread and a uniform altitude grid.  Counts the main-loop pairs that got
+// a plan and those that will plan themselves (no room, guess not bracketing) into the workgroup's words (WgCounts::n).
 template <int TIER, int THREADS, bool G, int TEAM = THREADS>
 __device__ __forceinline__ PlanRoom plan_pairs(const KArgs& a, const SegDev& sg, const Node* nodes, double* pf2, double* gb,
                                                unsigned short* hint, const unsigned short* cand, const BlockInfo& info,
-                                               int block_in_prof, int blocks_per_prof, unsigned* plan_cnt,
+                                               int block_in_prof, int blocks_per_prof, unsigned long long* plan_cnt,
                                                double* plan_consts) {
     constexpr int W = THREADS / 64;            // (the numbering of the items: the workgroup's, whatever the team)
     PlanRoom room;
@@ -3108,15 +3141,10 @@ __device__ __forceinline__ PlanRoom plan_pairs(const KArgs& a, const SegDev& sg,
             if (done == 2) ++n_panel;
         }
     }
-    if (n_planned) atomicAdd(&plan_cnt[0], (unsigned)n_planned);
-    if (n_self) atomicAdd(&plan_cnt[1], (unsigned)n_self);
-    if (n_panel) atomicAdd(&plan_cnt[2], (unsigned)n_panel);
+    if (n_planned) atomicAdd(&plan_cnt[0], (unsigned long long)n_planned);
+    if (n_self) atomicAdd(&plan_cnt[1], (unsigned long long)n_self);
+    if (n_panel) atomicAdd(&plan_cnt[6], (unsigned long long)n_panel);
     team_sync<TEAM, THREADS>();
-    if (team_tid<TEAM, THREADS>() == 0 && a.plan_counters) {
-        if (plan_cnt[0]) atomicAdd(&a.plan_counters[0], (unsigned long long)plan_cnt[0]);
-        if (plan_cnt[1]) atomicAdd(&a.plan_counters[1], (unsigned long long)plan_cnt[1]);
-        if (plan_cnt[2]) atomicAdd(&a.plan_counters[6], (unsigned long long)plan_cnt[2]);
-    }
     room.base0 = (unsigned)uniform((int)room.base0);
     room.base1 = (unsigned)uniform((int)room.base1);
     room.base2 = (unsigned)uniform((int)room.base2);
@@ -3179,22 +3207,22 @@ __device__ __forceinline__ void run_items(const KArgs& a, const SegDev& sg, cons
     int pulled = 0;                                    // how many items this workgroup had pulled before the current one
     // Four counts of this wave in one register, eight bits each: pairs whose lower segments took the panel sum (from bit 0)
     // and eligible pairs that fell back (bit 8), list passes of the panel sum that took the quick path (bit 16) and that
-    // took the exact tests (bit 24).  An item adds at most 1, 1, 63 and 63; the counts go to the launch's counters where
-    // one of them has reached 128, and behind the last item.
+    // took the exact tests (bit 24).  An item adds at most 1, 1, 63 and 63; the counts go to the workgroup's words in LDS
+    // (WgCounts, behind the item counter) where one of them has reached 128, and behind the last item.  Nothing here
+    // goes to global memory: adds from every wave and block to a few addresses of the launch cost it 0.66 ms for two
+    // of them, the waves wait for them at their next load (profiles/ab_panel_quick.txt 6); the workgroup adds its
+    // words to the launch's once, when it leaves (flush_counts).
+    unsigned long long* wg_cnt = reinterpret_cast<WgCounts*>(item_next)->n;     // (only where this function counts: see WgCounts)
     unsigned panel_cnt = 0u;
     auto flush_panel_cnt = [&]() {
-        if (lane == 0 && a.plan_counters) {
+        if (lane == 0) {
             const unsigned took = panel_cnt & 0xffu, fell = (panel_cnt >> 8) & 0xffu;
             const unsigned n_quick = (panel_cnt >> 16) & 0xffu, n_exact = panel_cnt >> 24;
-            if (took) atomicAdd(&a.plan_counters[2], (unsigned long long)took);
-            if (fell) atomicAdd(&a.plan_counters[3], (unsigned long long)fell);
-            if (sg.panel_upper && took) atomicAdd(&a.plan_counters[4], (unsigned long long)took);
-            // (the list passes into one of kQuickSlots pairs of words, a cache line each, by workgroup - a scalar address:
-            //  two more adds to one address from every wave and block cost the headline launch 0.66 ms, the waves wait
-            //  for them at their next load, where the three adds above cost what they did)
-            unsigned long long* slot = a.plan_counters + kQuickSlotBase + (blockIdx.x & (kQuickSlots - 1)) * kQuickSlotWords;
-            if (n_quick) atomicAdd(slot, (unsigned long long)n_quick);
-            if (n_exact) atomicAdd(slot + 1, (unsigned long long)n_exact);
+            if (took) atomicAdd(&wg_cnt[2], (unsigned long long)took);
+            if (fell) atomicAdd(&wg_cnt[3], (unsigned long long)fell);
+            if (sg.panel_upper && took) atomicAdd(&wg_cnt[4], (unsigned long long)took);
+            if (n_quick) atomicAdd(&wg_cnt[7], (unsigned long long)n_quick);
+            if (n_exact) atomicAdd(&wg_cnt[8], (unsigned long long)n_exact);
         }
         panel_cnt = 0u;
     };
@@ -3255,7 +3283,7 @@ __device__ __forceinline__ void run_items(const KArgs& a, const SegDev& sg, cons
             // (option panel_upper: with it a pair that took the panel sum reports 3, its region reached the top segment, or 4,
             //  it kept the lower one.  The few of the second kind are counted one by one, and all of them once per wave below:
             //  no third count waits in a register across the items, of which the kernel has none to spare)
-            if (state == 4 && lane == 0 && a.plan_counters) atomicAdd(&a.plan_counters[5], 1ull);
+            if (state == 4 && lane == 0) atomicAdd(&wg_cnt[5], 1ull);
         }
         if (lane == 0) {
             if (local) {
@@ -3292,7 +3320,7 @@ template <int TIER, int THREADS, bool G>
 __device__ __forceinline__ unsigned long long run_block(const KArgs& a, const SegDev& sg, Node* nodes, double* pf2, double* gb,
                                           unsigned short* hint, unsigned short* cand, int* cand_count, double* red,
                                           long long prof_local, int block_in_prof, int blocks_per_prof,
-                                          int* item_next, unsigned* plan_cnt, double* plan_consts) {
+                                          int* item_next, unsigned long long* plan_cnt, double* plan_consts) {
     const long long p = sg.prof_begin + prof_local;
     BlockInfo info = stage_profile<TIER, THREADS>(
         a.den + p * a.prof_stride, a.bmag + p * a.field_stride, a.bpsi + p * a.field_stride,
@@ -3375,9 +3403,14 @@ __device__ __forceinline__ void vfo_kernel_body(const KArgs& a) {
     // workgroup slots empty: measured with tools/wave_trace.py.)  Every wave leaves the loop through
     // the same uniform test, so the grid always drains.
     __shared__ long long next_bid;
-    __shared__ int item_next;
+    // run_items' item counter - and behind it, in the kernels that count (only the fast tier on staged arrays in LDS
+    // does: plan_pairs, run_items), what this workgroup counts for the launch's counters
+    constexpr bool kCounts = TIER_SEL != 0 && !TALL;
+    __shared__ WgCounts counts;
+    __shared__ int item_alone;
+    int* const item_next = kCounts ? &counts.item_next : &item_alone;
+    unsigned long long* const plan_cnt = kCounts ? counts.n : nullptr;
     __shared__ int cand_count[PRHF_BLOCK_THREADS / 64 + 1];
-    __shared__ unsigned plan_cnt[3];           // pairs of this block that got a plan / that plan themselves / whose plan has the second form (plan_pairs)
     __shared__ double plan_consts[2];          // ... and the block's constants
     // Follow-up of a short-grid launch: the blocks to evaluate are listed (block_list[1 .. block_list[0]])
     const unsigned* list = a.block_list;
@@ -3386,13 +3419,11 @@ __device__ __forceinline__ void vfo_kernel_body(const KArgs& a) {
     //  zero for the next call's short_order_kernel)
     if (a.zero_after && blockIdx.x == 0 && threadIdx.x < PRHF_ORDER_CLASSES) a.zero_after[threadIdx.x] = 0u;
     long long ticket = blockIdx.x;
-    if (ticket >= n_blocks) return;
+    if (ticket >= n_blocks) return;            // (the whole workgroup, which has counted nothing)
     long long bid = list ? (long long)list[1 + ticket] : ticket;
+    if (kCounts) zero_counts(&counts, threadIdx.x);    // (ordered like the item counter below)
     for (;;) {
-        if (threadIdx.x == 0) {                // ordered before their first use by the barriers of stage_profile
-            item_next = 0;
-            plan_cnt[0] = plan_cnt[1] = plan_cnt[2] = 0u;
-        }
+        if (threadIdx.x == 0) *item_next = 0;              // ordered before its first use by the barriers of stage_profile
 #ifdef PRHF_TRACE
         const unsigned long long t_start = wall_clock64();
 #endif
@@ -3437,9 +3468,9 @@ __device__ __forceinline__ void vfo_kernel_body(const KArgs& a) {
 
         const unsigned long long t_staged = (TIER_SEL == 0 || (TIER_SEL == 2 && sg.tier == 0))
             ? run_block<0, THREADS, TALL>(a, sg, nodes, pf2, gb, hint, cand, cand_count, red, prof_local, block_in_prof, bpp,
-                                    &item_next, plan_cnt, plan_consts)
+                                    item_next, plan_cnt, plan_consts)
             : run_block<1, THREADS, TALL>(a, sg, nodes, pf2, gb, hint, cand, cand_count, red, prof_local, block_in_prof, bpp,
-                                    &item_next, plan_cnt, plan_consts);
+                                    item_next, plan_cnt, plan_consts);
         (void)t_staged;
 #ifdef PRHF_TRACE
         if (a.trace && (threadIdx.x & 63) == 0) {
@@ -3462,6 +3493,11 @@ __device__ __forceinline__ void vfo_kernel_body(const KArgs& a) {
         if (ticket >= n_blocks) break;
         bid = list ? (long long)list[1 + ticket] : ticket;
     }
+    // every path out of the loop comes here, the whole workgroup by the same one: its counts go to the launch's
+    if (kCounts) {
+        __syncthreads();
+        flush_counts(a, &counts, nullptr, threadIdx.x);
+    }
 }
 
 template <int TIER_SEL, int THREADS>
@@ -3478,14 +3514,14 @@ __global__ __launch_bounds__(THREADS, PRHF_MIN_WAVES_PER_SIMD) void vfo_tall_ker
 // One workgroup of sixteen waves per CU and two slots of LDS, each what lds_bytes_for describes.  The waves sum the
 // pairs of the profile in one slot while ONE wave - the last to leave the other slot - stages the next profile there,
 // alone: no wave waits at a barrier for the slowest one, none stands by while a profile is staged.  No __syncthreads
-// behind the start-up.  The hand-offs are inside one workgroup (LDS words, workgroup-scope release / acquire), so
-// nothing depends on which workgroups are resident.
+// between the start-up and the exit (where the workgroup's counts are flushed).  The hand-offs are inside one
+// workgroup (LDS words, workgroup-scope release / acquire), so nothing depends on which workgroups are resident.
 struct SlotHeader {
+    WgCounts cnt;              // run_items' counter, and what the waves and the stagers count in this slot: both
+                               // slots' words go to the launch's when the workgroup leaves
     int state;                 // the generation that is ready (a wave's n-th visit of the slot needs state >= n);
                                // kSlotFinished: the queue has no block for that visit, the launch is over
-    int item_next;             // run_items' counter
     int left;                  // waves that have left the current generation: the sixteenth stages the next one
-    unsigned plan_cnt[3];      // plan_pairs' counts
     int cand_count[2];         // list_candidates' count (one wave)
     double plan_consts[2];     // plan_pairs' constants of the block
     // published by the stager, read by every wave behind its acquire
@@ -3578,10 +3614,7 @@ __device__ __forceinline__ void stage_slot(const KArgs& a, const SegDev& sg, Slo
     // (vfo_kernel's rule: the blocks of the last three resident rounds rank below everything pulled before them)
     const long long left = a.n_blocks - ticket;
     const int prio = left > 3 * resident ? 3 : (left > 2 * resident ? 2 : (left > resident ? 1 : 0));
-    if (lane == 0) {
-        h->item_next = 0;
-        h->plan_cnt[0] = h->plan_cnt[1] = h->plan_cnt[2] = 0u;
-    }
+    if (lane == 0) h->cnt.item_next = 0;
     const long long p = sg.prof_begin + prof_local;
     BlockInfo info = stage_profile<1, LAYOUT, 64>(
         a.den + p * a.prof_stride, a.bmag + p * a.field_stride, a.bpsi + p * a.field_stride,
@@ -3599,7 +3632,7 @@ __device__ __forceinline__ void stage_slot(const KArgs& a, const SegDev& sg, Slo
     team_mark<64, LAYOUT>(2);
     if (lane == 0 && block_in_prof == 0 && info.bad) post_status(a.status, (unsigned)info.bad);
     const PlanRoom room = plan_pairs<1, LAYOUT, false, 64>(a, sg, s.nodes, s.pf2, s.gb, s.hint, s.cand, info, block_in_prof, bpp,
-                                                           h->plan_cnt, h->plan_consts);
+                                                           h->cnt.n, h->plan_consts);
     if (lane == 0) {
         h->info = info;
         h->room = room;
@@ -3634,8 +3667,10 @@ __global__ __launch_bounds__(THREADS, PRHF_MIN_WAVES_PER_SIMD) void vfo_stream_k
         hdr[threadIdx.x].state = 0;
         hdr[threadIdx.x].left = 0;
     }
+    zero_counts(&hdr[0].cnt, threadIdx.x);
+    zero_counts(&hdr[1].cnt, threadIdx.x);
     if (threadIdx.x == 0) abort_word = 0;
-    __syncthreads();                           // the only one: from here on the waves meet at the slots' words
+    __syncthreads();                           // the only one in front of the exit: from here on the waves meet at the slots' words
     // waves 0 and 1 stage the first two blocks (tickets blockIdx.x and gridDim.x + blockIdx.x: the first resident round
     // in index order, as the general kernel's); the queue hands out the tickets behind them
     if (wave < 2) stage_slot<LAYOUT>(a, sg, &hdr[wave], slot_arrays(smem, wave, levels), (long long)blockIdx.x + wave * (long long)gridDim.x,
@@ -3681,7 +3716,7 @@ __global__ __launch_bounds__(THREADS, PRHF_MIN_WAVES_PER_SIMD) void vfo_stream_k
         else if (prio == 1) __builtin_amdgcn_s_setprio(1);
         else __builtin_amdgcn_s_setprio(0);
         run_items<PRHF_KMODE_X, 1, LAYOUT, false>(a, sg, s.nodes, s.pf2, s.gb, s.hint, s.cand, info, prof_local, block_in_prof, bpp,
-                                                  &h->item_next, s.red, room);
+                                                  &h->cnt.item_next, s.red, room);
 #ifdef PRHF_TRACE
         if (a.trace && lane == 0) {
             const long long bid = h->bid;
@@ -3704,6 +3739,10 @@ __global__ __launch_bounds__(THREADS, PRHF_MIN_WAVES_PER_SIMD) void vfo_stream_k
             stage_slot<LAYOUT>(a, sg, h, s, ticket, gen + 1, resident);
         }
     }
+    // Every wave comes here, a stager behind its staging, on every path (kSlotAbort included): behind this barrier no
+    // wave counts any more, and nine threads add the two slots' words to the launch's
+    __syncthreads();
+    flush_counts(a, &hdr[0].cnt, &hdr[1].cnt, threadIdx.x);
 }
 
 // Pair table of the fast tier's main loop: (m_i, m_i+1 - m_i) side by side, one 16-byte load per

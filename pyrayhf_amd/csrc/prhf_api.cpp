@@ -20,6 +20,7 @@
 
 #include "prhf.h"
 #include "prhf_kernels.h"
+#include "prhf_arena.h"       // Carver: a scratch buffer's layout stated once, for its size and its pointers
 #include "prhf_plan.h"        // Knobs, plan_launch, StatusWord: the launch planning, HIP-free
 
 namespace {
@@ -1163,26 +1164,131 @@ int prhf_vfo_worklist_f64(prhf_ctx* ctx, const double* freq_mhz, int64_t n_freq,
                multiplier, multiplier_len, segs, n_segs, vh_out, flags);
 }
 
+}  // extern "C"
+// The entry points below have C linkage from their declarations in prhf.h (the templates among the shared steps need
+// C++ linkage).  A new entry point defined below must be declared there first: without the declaration it is exported
+// under a mangled name, which pyrayhf_amd/_native.py reports when it loads the library.
+
 namespace {
 
-// What the derivative entry points (Jacobian, VJP, JVP) check alike; others_given: the arrays of their own are there
-int derivative_check(prhf_ctx* c, const double* freq, int64_t n_freq, const double* den, const double* bmag, const double* bpsi,
-                     const double* alt, int64_t n_prof, int64_t n_alt, int64_t prof_stride, int64_t alt_stride, const double* mult,
-                     int32_t n_points, int32_t mode, bool others_given, uint32_t flags) {
+// ---- The steps the tracer and derivative entry points are assembled from: checks, carve, stage, tail ----
+
+#define PRHF_TRY(expr)                     \
+    do {                                   \
+        const int rc_ = (expr);            \
+        if (rc_ != PRHF_OK) return rc_;    \
+    } while (0)
+
+hipError_t upload(prhf_ctx* c, void* dst, const void* src, size_t bytes) {
+    return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream);
+}
+hipError_t download(prhf_ctx* c, void* dst, const void* src, size_t bytes) {
+    return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream);
+}
+// rows of row_elems doubles, `stride` elements apart at the source (a single row: as it stands), packed at dst
+hipError_t upload_rows(prhf_ctx* c, double* dst, const double* src, size_t row_elems, size_t rows, int64_t stride) {
+    return hipMemcpy2DAsync(dst, row_elems * 8, src, (rows > 1 ? (size_t)stride : row_elems) * 8, row_elems * 8, rows,
+                            hipMemcpyHostToDevice, c->stream);
+}
+
+// A Carver (prhf_arena.h) that also stages: put() takes the room of a host array and, on the pass over the buffer,
+// enqueues its upload.  A null array takes its room and gives a null pointer.
+class Stager : public Carver {
+  public:
+    // pack: host memory that mirrors the buffer - put() copies there instead, for the caller to send in one piece
+    Stager(prhf_ctx* c, void* base, void* pack = nullptr) : Carver(base), c_(c), pack_(static_cast<char*>(pack)) {}
+    template <class T>
+    T* put(const void* src, size_t count) {
+        const size_t at = used();
+        T* d = take<T>(count);
+        if (!src) return nullptr;
+        if (d && pack_) std::memcpy(pack_ + at, src, count * sizeof(T));
+        else if (d && err_ == hipSuccess) err_ = upload(c_, d, src, count * sizeof(T));
+        return d;
+    }
+    hipError_t error() const { return err_; }
+
+  private:
+    prhf_ctx* c_;
+    char* pack_;
+    hipError_t err_ = hipSuccess;
+};
+
+// A buffer of the context laid out by `layout`, a function of a Stager: the pass over a null base gives the bytes the
+// buffer must hold, the pass over the buffer gives the pointers and sends the uploads.  No size is written down beside
+// its carving.
+template <class Layout>
+int carve(prhf_ctx* c, DevBuf& b, Layout layout) {
+    Stager sizing(c, nullptr);
+    layout(sizing);
+    PRHF_TRY(ensure(c, b, sizing.used()));
+    Stager k(c, b.p);
+    layout(k);
+    HIP_TRY(k.error());
+    return PRHF_OK;
+}
+
+// The tail of a launch: the two timing events around `launch` (one launch or a body of several, the first error
+// returned), the ring slot published and - posts_status - the status words read at the next prhf_sync.
+template <class Launch>
+int timed_launch(prhf_ctx* c, bool posts_status, Launch launch) {
+    HIP_TRY(hipEventRecord(c->begin_ev(), c->stream));
+    HIP_TRY(launch());
+    HIP_TRY(hipEventRecord(c->pending_end_ev(), c->stream));
+    c->mark_timed();
+    if (posts_status) c->status_pending = true;
+    return PRHF_OK;
+}
+
+// Host-side range check of an index array
+int check_index(const char* name, const int64_t* idx, int64_t n, const char* limit_name, int64_t limit) {
+    for (int64_t i = 0; i < n; ++i)
+        if (idx[i] < 0 || idx[i] >= limit)
+            return fail(PRHF_EINVAL, "%s[%lld] outside [0, %s)", name, (long long)i, limit_name);
+    return PRHF_OK;
+}
+
+// A host scan grid: strictly increasing (a NaN fails the test); lone_finite: a grid of one elevation holds a finite one
+int check_scan_grid(const double* scan_elevation_deg, int64_t n_scan, bool lone_finite) {
+    for (int64_t i = 0; i + 1 < n_scan; ++i)
+        if (!(scan_elevation_deg[i + 1] > scan_elevation_deg[i]))
+            return fail(PRHF_EINVAL, "scan_elevation_deg must be strictly increasing");
+    if (lone_finite && n_scan == 1 && !std::isfinite(scan_elevation_deg[0]))
+        return fail(PRHF_EINVAL, "scan_elevation_deg must be finite");
+    return PRHF_OK;
+}
+
+// What the operator and its derivatives (Jacobian, VJP, JVP) are called on
+struct OperatorInputs {
+    const double* freq;
+    int64_t n_freq;
+    const double *den, *bmag, *bpsi, *alt;
+    int64_t n_prof, n_alt, prof_stride, alt_stride;
+    const double* mult;
+    int32_t n_points, mode;
+    uint32_t flags;
+    bool dev() const { return (flags & PRHF_FLAG_DEVICE_PTRS) != 0; }
+    bool shared_field() const { return (flags & PRHF_FLAG_SHARED_FIELD) != 0; }
+};
+
+// What the derivative entry points check alike; others_given: the arrays of their own are there
+int derivative_check(prhf_ctx* c, const OperatorInputs& in, bool others_given) {
     if (!c) return fail(PRHF_EINVAL, "null context");
-    if (!freq || !den || !bmag || !bpsi || !alt || !mult || !others_given) return fail(PRHF_EINVAL, "null array pointer");
-    if (n_freq < 1 || n_prof < 0 || n_alt < 1 || n_points < 1) return fail(PRHF_EINVAL, "bad shape");
-    if (n_alt > kMaxAltTall) return fail(PRHF_EINVAL, "n_alt %lld exceeds the limit of %lld levels", (long long)n_alt, kMaxAltTall);
-    if (n_freq > (1 << 20)) return fail(PRHF_EINVAL, "n_freq too large");
-    if (prof_stride < n_alt || (alt_stride != 0 && alt_stride < n_alt)) return fail(PRHF_EINVAL, "row stride shorter than a row");
-    if (mode != PRHF_MODE_O && mode != PRHF_MODE_X) return fail(PRHF_EINVAL, "mode must be 'O' or 'X'");
-    if (flags & ~(PRHF_FLAG_DEVICE_PTRS | PRHF_FLAG_ASYNC | PRHF_FLAG_GRID_STABLE | PRHF_FLAG_SHARED_FIELD))
+    if (!in.freq || !in.den || !in.bmag || !in.bpsi || !in.alt || !in.mult || !others_given)
+        return fail(PRHF_EINVAL, "null array pointer");
+    if (in.n_freq < 1 || in.n_prof < 0 || in.n_alt < 1 || in.n_points < 1) return fail(PRHF_EINVAL, "bad shape");
+    if (in.n_alt > kMaxAltTall)
+        return fail(PRHF_EINVAL, "n_alt %lld exceeds the limit of %lld levels", (long long)in.n_alt, kMaxAltTall);
+    if (in.n_freq > (1 << 20)) return fail(PRHF_EINVAL, "n_freq too large");
+    if (in.prof_stride < in.n_alt || (in.alt_stride != 0 && in.alt_stride < in.n_alt))
+        return fail(PRHF_EINVAL, "row stride shorter than a row");
+    if (in.mode != PRHF_MODE_O && in.mode != PRHF_MODE_X) return fail(PRHF_EINVAL, "mode must be 'O' or 'X'");
+    if (in.flags & ~(PRHF_FLAG_DEVICE_PTRS | PRHF_FLAG_ASYNC | PRHF_FLAG_GRID_STABLE | PRHF_FLAG_SHARED_FIELD))
         return fail(PRHF_EINVAL, "unknown flag bits");
-    const bool dev = (flags & PRHF_FLAG_DEVICE_PTRS) != 0;
-    if ((flags & PRHF_FLAG_ASYNC) && !dev) return fail(PRHF_EINVAL, "PRHF_FLAG_ASYNC needs device pointers");
-    if (!dev)
-        for (int64_t i = 1; i < n_points; ++i)
-            if (mult[i] < mult[i - 1])
+    if ((in.flags & PRHF_FLAG_ASYNC) && !in.dev()) return fail(PRHF_EINVAL, "PRHF_FLAG_ASYNC needs device pointers");
+    if (!in.dev())
+        for (int64_t i = 1; i < in.n_points; ++i)
+            if (in.mult[i] < in.mult[i - 1])
                 return fail(PRHF_EINVAL, "multiplier[%lld] decreases: the stretched grid must be non-decreasing", (long long)i);
     return PRHF_OK;
 }
@@ -1214,83 +1320,133 @@ int highest_peak(prhf_ctx* c, const double* den, int64_t n_prof, int64_t n_alt, 
     return PRHF_OK;
 }
 
-// prhf_vfo_jacobian_f64 / prhf_vfo_vjp_f64: check, find the levels to stage, plan (plan_vjp, prhf_plan.h), stage host
-// buffers, launch.  vh_out comes from the operator's own launch on the same arguments.
-int vjp_run(prhf_ctx* c, const double* freq, int64_t n_freq, const double* den, const double* bmag, const double* bpsi,
-            const double* alt, int64_t n_prof, int64_t n_alt, int64_t prof_stride, int64_t alt_stride, const double* mult,
-            int32_t n_points, int32_t mode, const double* grad_vh, double* vh_out, double* out, bool jacobian, uint32_t flags) {
-    int rc = derivative_check(c, freq, n_freq, den, bmag, bpsi, alt, n_prof, n_alt, prof_stride, alt_stride, mult, n_points, mode,
-                              out && (jacobian || grad_vh), flags);
-    if (rc != PRHF_OK) return rc;
-    const bool dev = (flags & PRHF_FLAG_DEVICE_PTRS) != 0, shared_field = (flags & PRHF_FLAG_SHARED_FIELD) != 0;
-    ENTER_DEVICE(c->device);
-    // Levels to stage: the whole column where LDS holds it; else up to the highest density peak of the launch
-    // (np.argmax's rule, the first NaN ranking highest: a host scan, or the peak pre-pass and one synchronisation)
-    VjpPlan pl;
+// Levels to stage: the whole column where `plan` (plan_vjp or plan_jvp of prhf_plan.h on this call's shape) takes it;
+// else up to the highest density peak of the launch; refused there too: the planner's text.
+template <class Planner>
+int levels_to_stage(prhf_ctx* c, const OperatorInputs& in, Planner plan, long long* levels) {
     char why[256];
-    long long levels = n_alt;
-    if (plan_vjp(n_prof, n_freq, levels, jacobian, pl, why, sizeof why) != PRHF_OK && n_prof > 0) {
-        long long max_peak = 0;
-        if ((rc = highest_peak(c, den, n_prof, n_alt, prof_stride, dev, &max_peak)) != PRHF_OK) return rc;
-        levels = max_peak + 1;
-        if (plan_vjp(n_prof, n_freq, levels, jacobian, pl, why, sizeof why) != PRHF_OK) return fail(PRHF_EINVAL, "%s", why);
-    }
-    if (vh_out) {
-        rc = prhf_vfo_batch_f64(c, freq, n_freq, den, bmag, bpsi, alt, n_prof, n_alt, prof_stride, alt_stride, mult, n_points,
-                                mode, vh_out, flags);
-        if (rc != PRHF_OK) return rc;
-    }
-    const size_t out_elems = jacobian ? (size_t)n_prof * (size_t)n_freq * (size_t)n_alt : (size_t)n_prof * (size_t)n_alt;
-    if (n_prof == 0) return PRHF_OK;
-    prhf::VjpArgs a;
+    *levels = in.n_alt;
+    if (plan(*levels, why, sizeof why) == PRHF_OK) return PRHF_OK;
+    long long max_peak = 0;
+    PRHF_TRY(highest_peak(c, in.den, in.n_prof, in.n_alt, in.prof_stride, in.dev(), &max_peak));
+    *levels = max_peak + 1;
+    if (plan(*levels, why, sizeof why) != PRHF_OK) return fail(PRHF_EINVAL, "%s", why);
+    return PRHF_OK;
+}
+
+// vh_out of a derivative call: the operator's own launch on the same arguments
+int operator_launch(prhf_ctx* c, const OperatorInputs& in, double* vh_out) {
+    return prhf_vfo_batch_f64(c, in.freq, in.n_freq, in.den, in.bmag, in.bpsi, in.alt, in.n_prof, in.n_alt, in.prof_stride,
+                              in.alt_stride, in.mult, in.n_points, in.mode, vh_out, in.flags);
+}
+
+// The fields VjpArgs and JvpArgs share.  Host buffers: the six inputs go to the head of c->vjp, packed, and `rest`
+// carves what the caller keeps behind them (its own input, the result).
+template <class Args, class Rest>
+int stage_derivative(prhf_ctx* c, const OperatorInputs& in, long long levels, Args& a, Rest rest) {
     std::memset(&a, 0, sizeof a);
-    a.n_prof = n_prof; a.n_freq = n_freq; a.n_alt = n_alt; a.lds_levels = levels; a.n_points = n_points;
-    a.mode = mode == PRHF_MODE_O ? PRHF_KMODE_O : PRHF_KMODE_X;
-    a.waves = pl.waves;
+    a.n_prof = in.n_prof; a.n_freq = in.n_freq; a.n_alt = in.n_alt; a.lds_levels = levels; a.n_points = in.n_points;
+    a.mode = in.mode == PRHF_MODE_O ? PRHF_KMODE_O : PRHF_KMODE_X;
     a.status = c->h_status_dev;
-    if (dev) {
-        a.freq = freq; a.den = den; a.bmag = bmag; a.bpsi = bpsi; a.alt = alt; a.mult = mult; a.grad_vh = grad_vh; a.out = out;
-        a.prof_stride = prof_stride;
-        a.field_stride = shared_field ? 0 : prof_stride;
-        a.alt_stride = alt_stride;
-    } else {
-        const size_t field_rows = shared_field ? 1 : (size_t)n_prof, alt_rows = alt_stride ? (size_t)n_prof : 1;
-        const size_t pf = jacobian ? 0 : (size_t)n_prof * (size_t)n_freq;
-        const size_t in_elems = (size_t)n_freq + (size_t)n_points + ((size_t)n_prof + 2 * field_rows + alt_rows) * (size_t)n_alt + pf;
-        if ((rc = ensure(c, c->vjp, (in_elems + out_elems) * 8)) != PRHF_OK) return rc;
-        double* d_freq = static_cast<double*>(c->vjp.p);
-        double* d_mult = d_freq + n_freq;
-        double* d_den = d_mult + n_points;
-        double* d_bmag = d_den + (size_t)n_prof * n_alt;
-        double* d_bpsi = d_bmag + field_rows * n_alt;
-        double* d_alt = d_bpsi + field_rows * n_alt;
-        double* d_g = d_alt + alt_rows * n_alt;
-        double* d_out = d_g + pf;
-        const size_t row_bytes = (size_t)n_alt * 8;
-        auto up_rows = [&](double* dst, const double* src, size_t rows, int64_t stride) {
-            return hipMemcpy2DAsync(dst, row_bytes, src, (size_t)(rows > 1 ? stride : n_alt) * 8, row_bytes, rows,
-                                    hipMemcpyHostToDevice, c->stream);
-        };
-        HIP_TRY(hipMemcpyAsync(d_freq, freq, (size_t)n_freq * 8, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(d_mult, mult, (size_t)n_points * 8, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(up_rows(d_den, den, (size_t)n_prof, prof_stride));
-        HIP_TRY(up_rows(d_bmag, bmag, field_rows, prof_stride));
-        HIP_TRY(up_rows(d_bpsi, bpsi, field_rows, prof_stride));
-        HIP_TRY(up_rows(d_alt, alt, alt_rows, alt_stride));
-        if (pf) HIP_TRY(hipMemcpyAsync(d_g, grad_vh, pf * 8, hipMemcpyHostToDevice, c->stream));
-        a.freq = d_freq; a.den = d_den; a.bmag = d_bmag; a.bpsi = d_bpsi; a.alt = d_alt; a.mult = d_mult; a.grad_vh = d_g;
-        a.out = d_out;
-        a.prof_stride = n_alt;
-        a.field_stride = shared_field ? 0 : n_alt;
-        a.alt_stride = alt_stride ? n_alt : 0;
+    if (in.dev()) {
+        a.freq = in.freq; a.den = in.den; a.bmag = in.bmag; a.bpsi = in.bpsi; a.alt = in.alt; a.mult = in.mult;
+        a.prof_stride = in.prof_stride;
+        a.field_stride = in.shared_field() ? 0 : in.prof_stride;
+        a.alt_stride = in.alt_stride;
+        return PRHF_OK;
     }
-    HIP_TRY(hipEventRecord(c->begin_ev(), c->stream));
-    HIP_TRY(prhf::launch_vfo_vjp(a, jacobian, pl.lds_bytes, c->stream));
-    HIP_TRY(hipEventRecord(c->pending_end_ev(), c->stream));
-    c->mark_timed();
-    c->status_pending = true;
-    if (!dev) HIP_TRY(hipMemcpyAsync(out, a.out, out_elems * 8, hipMemcpyDeviceToHost, c->stream));
-    if (flags & PRHF_FLAG_ASYNC) return PRHF_OK;
+    const size_t P = (size_t)in.n_prof, A = (size_t)in.n_alt;
+    const size_t field_rows = in.shared_field() ? 1 : P, alt_rows = in.alt_stride ? P : 1;
+    double *d_den = nullptr, *d_bmag = nullptr, *d_bpsi = nullptr, *d_alt = nullptr;
+    PRHF_TRY(carve(c, c->vjp, [&](Stager& k) {
+        a.freq = k.put<double>(in.freq, (size_t)in.n_freq);
+        a.mult = k.put<double>(in.mult, (size_t)in.n_points);
+        a.den = d_den = k.take<double>(P * A);
+        a.bmag = d_bmag = k.take<double>(field_rows * A);
+        a.bpsi = d_bpsi = k.take<double>(field_rows * A);
+        a.alt = d_alt = k.take<double>(alt_rows * A);
+        rest(k);
+    }));
+    HIP_TRY(upload_rows(c, d_den, in.den, A, P, in.prof_stride));
+    HIP_TRY(upload_rows(c, d_bmag, in.bmag, A, field_rows, in.prof_stride));
+    HIP_TRY(upload_rows(c, d_bpsi, in.bpsi, A, field_rows, in.prof_stride));
+    HIP_TRY(upload_rows(c, d_alt, in.alt, A, alt_rows, in.alt_stride));
+    a.prof_stride = in.n_alt;
+    a.field_stride = in.shared_field() ? 0 : in.n_alt;
+    a.alt_stride = in.alt_stride ? in.n_alt : 0;
+    return PRHF_OK;
+}
+
+// prhf_vfo_jacobian_f64 / prhf_vfo_vjp_f64: check, find the levels to stage, plan (plan_vjp, prhf_plan.h), stage host
+// buffers, launch.
+int vjp_run(prhf_ctx* c, const OperatorInputs& in, const double* grad_vh, double* vh_out, double* out, bool jacobian) {
+    PRHF_TRY(derivative_check(c, in, out && (jacobian || grad_vh)));
+    ENTER_DEVICE(c->device);
+    VjpPlan pl;
+    long long levels = in.n_alt;
+    auto plan = [&](long long lv, char* why, size_t n) { return plan_vjp(in.n_prof, in.n_freq, lv, jacobian, pl, why, n); };
+    if (in.n_prof > 0) PRHF_TRY(levels_to_stage(c, in, plan, &levels));
+    if (vh_out) PRHF_TRY(operator_launch(c, in, vh_out));
+    if (in.n_prof == 0) return PRHF_OK;
+    const size_t P = (size_t)in.n_prof, F = (size_t)in.n_freq, A = (size_t)in.n_alt;
+    const size_t out_elems = jacobian ? P * F * A : P * A, pf = jacobian ? 0 : P * F;
+    prhf::VjpArgs a;
+    double* d_g = nullptr;
+    double* d_out = out;
+    PRHF_TRY(stage_derivative(c, in, levels, a, [&](Stager& k) {
+        d_g = k.take<double>(pf);
+        d_out = k.take<double>(out_elems);
+    }));
+    if (!in.dev() && pf) HIP_TRY(upload(c, d_g, grad_vh, pf * 8));
+    a.grad_vh = in.dev() ? grad_vh : d_g;
+    a.out = d_out;
+    a.waves = pl.waves;
+    PRHF_TRY(timed_launch(c, true, [&] { return prhf::launch_vfo_vjp(a, jacobian, pl.lds_bytes, c->stream); }));
+    if (!in.dev()) HIP_TRY(download(c, out, d_out, out_elems * 8));
+    if (in.flags & PRHF_FLAG_ASYNC) return PRHF_OK;
+    return prhf_sync(c);
+}
+
+// prhf_vfo_jvp_f64: as vjp_run with plan_jvp, then one launch per chunk of tangents
+int jvp_run(prhf_ctx* c, const OperatorInputs& in, const double* tangents, int64_t n_tan, int64_t tan_stride, double* vh_out,
+            double* out) {
+    PRHF_TRY(derivative_check(c, in, n_tan <= 0 || (tangents && out)));
+    if (n_tan < 0 || n_tan > (1 << 20)) return fail(PRHF_EINVAL, "bad number of tangents");
+    if (tan_stride != 0 && tan_stride < n_tan * in.n_alt)
+        return fail(PRHF_EINVAL, "tangent stride shorter than a profile's tangents");
+    ENTER_DEVICE(c->device);
+    JvpPlan pl;
+    long long levels = in.n_alt;
+    auto plan = [&](long long lv, char* why, size_t n) { return plan_jvp(in.n_prof, in.n_freq, lv, n_tan, pl, why, n); };
+    if (n_tan > 0 && in.n_prof > 0) PRHF_TRY(levels_to_stage(c, in, plan, &levels));
+    if (vh_out) PRHF_TRY(operator_launch(c, in, vh_out));
+    if (in.n_prof == 0 || n_tan == 0) return PRHF_OK;
+    const size_t out_elems = (size_t)in.n_prof * (size_t)in.n_freq * (size_t)n_tan;
+    const size_t tan_sets = tan_stride ? (size_t)in.n_prof : 1, set_elems = (size_t)n_tan * (size_t)in.n_alt;
+    prhf::JvpArgs a;
+    double* d_tan = nullptr;
+    double* d_out = out;
+    PRHF_TRY(stage_derivative(c, in, levels, a, [&](Stager& k) {
+        d_tan = k.take<double>(tan_sets * set_elems);
+        d_out = k.take<double>(out_elems);
+    }));
+    if (!in.dev()) HIP_TRY(upload_rows(c, d_tan, tangents, set_elems, tan_sets, tan_stride));
+    const double* const tan0 = in.dev() ? tangents : d_tan;
+    a.tan_prof_stride = in.dev() ? tan_stride : (tan_stride ? (long long)set_elems : 0);
+    a.out_stride = n_tan;
+    PRHF_TRY(timed_launch(c, true, [&] {
+        for (long long i = 0; i < pl.n_chunks; ++i) {
+            const JvpChunk ch = jvp_chunk(pl, n_tan, i);
+            a.tan = tan0 + (size_t)ch.first * (size_t)in.n_alt;
+            a.out = d_out + ch.first;
+            a.n_tan = ch.count;
+            const hipError_t e = prhf::launch_vfo_jvp(a, ch.nt, pl.threads, ch.lds_bytes, c->stream);
+            if (e != hipSuccess) return e;
+        }
+        return hipSuccess;
+    }));
+    if (!in.dev()) HIP_TRY(download(c, out, d_out, out_elems * 8));
+    if (in.flags & PRHF_FLAG_ASYNC) return PRHF_OK;
     return prhf_sync(c);
 }
 
@@ -1300,120 +1456,27 @@ int prhf_vfo_jacobian_f64(prhf_ctx* ctx, const double* freq_mhz, int64_t n_freq,
                           const double* bpsi, const double* alt, int64_t n_prof, int64_t n_alt, int64_t prof_stride_elems,
                           int64_t alt_stride_elems, const double* multiplier, int32_t n_points, int32_t mode, double* vh_out,
                           double* jac_out, uint32_t flags) {
-    return vjp_run(ctx, freq_mhz, n_freq, den, bmag, bpsi, alt, n_prof, n_alt, prof_stride_elems, alt_stride_elems, multiplier,
-                   n_points, mode, nullptr, vh_out, jac_out, true, flags);
+    const OperatorInputs in{freq_mhz, n_freq, den, bmag, bpsi, alt, n_prof, n_alt, prof_stride_elems, alt_stride_elems,
+                            multiplier, n_points, mode, flags};
+    return vjp_run(ctx, in, nullptr, vh_out, jac_out, true);
 }
 
 int prhf_vfo_vjp_f64(prhf_ctx* ctx, const double* freq_mhz, int64_t n_freq, const double* den, const double* bmag,
                      const double* bpsi, const double* alt, int64_t n_prof, int64_t n_alt, int64_t prof_stride_elems,
                      int64_t alt_stride_elems, const double* multiplier, int32_t n_points, int32_t mode, const double* grad_vh,
                      double* vh_out, double* grad_den_out, uint32_t flags) {
-    return vjp_run(ctx, freq_mhz, n_freq, den, bmag, bpsi, alt, n_prof, n_alt, prof_stride_elems, alt_stride_elems, multiplier,
-                   n_points, mode, grad_vh, vh_out, grad_den_out, false, flags);
+    const OperatorInputs in{freq_mhz, n_freq, den, bmag, bpsi, alt, n_prof, n_alt, prof_stride_elems, alt_stride_elems,
+                            multiplier, n_points, mode, flags};
+    return vjp_run(ctx, in, grad_vh, vh_out, grad_den_out, false);
 }
-
-namespace {
-
-// prhf_vfo_jvp_f64: check, find the levels to stage, plan (plan_jvp, prhf_plan.h), stage host buffers, then one launch
-// per chunk of tangents.  vh_out comes from the operator's own launch on the same arguments.
-int jvp_run(prhf_ctx* c, const double* freq, int64_t n_freq, const double* den, const double* bmag, const double* bpsi,
-            const double* alt, int64_t n_prof, int64_t n_alt, int64_t prof_stride, int64_t alt_stride, const double* mult,
-            int32_t n_points, int32_t mode, const double* tangents, int64_t n_tan, int64_t tan_stride, double* vh_out,
-            double* out, uint32_t flags) {
-    int rc = derivative_check(c, freq, n_freq, den, bmag, bpsi, alt, n_prof, n_alt, prof_stride, alt_stride, mult, n_points, mode,
-                              n_tan <= 0 || (tangents && out), flags);
-    if (rc != PRHF_OK) return rc;
-    if (n_tan < 0 || n_tan > (1 << 20)) return fail(PRHF_EINVAL, "bad number of tangents");
-    if (tan_stride != 0 && tan_stride < n_tan * n_alt) return fail(PRHF_EINVAL, "tangent stride shorter than a profile's tangents");
-    const bool dev = (flags & PRHF_FLAG_DEVICE_PTRS) != 0, shared_field = (flags & PRHF_FLAG_SHARED_FIELD) != 0;
-    ENTER_DEVICE(c->device);
-    // Levels to stage: as vjp_run
-    JvpPlan pl;
-    char why[256];
-    long long levels = n_alt;
-    if (n_tan > 0 && n_prof > 0 && plan_jvp(n_prof, n_freq, levels, n_tan, pl, why, sizeof why) != PRHF_OK) {
-        long long max_peak = 0;
-        if ((rc = highest_peak(c, den, n_prof, n_alt, prof_stride, dev, &max_peak)) != PRHF_OK) return rc;
-        levels = max_peak + 1;
-        if (plan_jvp(n_prof, n_freq, levels, n_tan, pl, why, sizeof why) != PRHF_OK) return fail(PRHF_EINVAL, "%s", why);
-    }
-    if (vh_out) {
-        rc = prhf_vfo_batch_f64(c, freq, n_freq, den, bmag, bpsi, alt, n_prof, n_alt, prof_stride, alt_stride, mult, n_points,
-                                mode, vh_out, flags);
-        if (rc != PRHF_OK) return rc;
-    }
-    if (n_prof == 0 || n_tan == 0) return PRHF_OK;
-    const size_t out_elems = (size_t)n_prof * (size_t)n_freq * (size_t)n_tan;
-    prhf::JvpArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.n_prof = n_prof; a.n_freq = n_freq; a.n_alt = n_alt; a.lds_levels = levels; a.n_points = n_points;
-    a.mode = mode == PRHF_MODE_O ? PRHF_KMODE_O : PRHF_KMODE_X;
-    a.out_stride = n_tan;
-    a.status = c->h_status_dev;
-    if (dev) {
-        a.freq = freq; a.den = den; a.bmag = bmag; a.bpsi = bpsi; a.alt = alt; a.mult = mult; a.tan = tangents; a.out = out;
-        a.prof_stride = prof_stride;
-        a.field_stride = shared_field ? 0 : prof_stride;
-        a.alt_stride = alt_stride;
-        a.tan_prof_stride = tan_stride;
-    } else {
-        const size_t field_rows = shared_field ? 1 : (size_t)n_prof, alt_rows = alt_stride ? (size_t)n_prof : 1;
-        const size_t tan_sets = tan_stride ? (size_t)n_prof : 1, set_elems = (size_t)n_tan * (size_t)n_alt;
-        const size_t in_elems = (size_t)n_freq + (size_t)n_points + ((size_t)n_prof + 2 * field_rows + alt_rows) * (size_t)n_alt +
-                                tan_sets * set_elems;
-        if ((rc = ensure(c, c->vjp, (in_elems + out_elems) * 8)) != PRHF_OK) return rc;
-        double* d_freq = static_cast<double*>(c->vjp.p);
-        double* d_mult = d_freq + n_freq;
-        double* d_den = d_mult + n_points;
-        double* d_bmag = d_den + (size_t)n_prof * n_alt;
-        double* d_bpsi = d_bmag + field_rows * n_alt;
-        double* d_alt = d_bpsi + field_rows * n_alt;
-        double* d_tan = d_alt + alt_rows * n_alt;
-        double* d_out = d_tan + tan_sets * set_elems;
-        auto up_rows = [&](double* dst, const double* src, size_t row_elems, size_t rows, int64_t stride) {
-            return hipMemcpy2DAsync(dst, row_elems * 8, src, (rows > 1 ? (size_t)stride : row_elems) * 8, row_elems * 8, rows,
-                                    hipMemcpyHostToDevice, c->stream);
-        };
-        HIP_TRY(hipMemcpyAsync(d_freq, freq, (size_t)n_freq * 8, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(d_mult, mult, (size_t)n_points * 8, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(up_rows(d_den, den, (size_t)n_alt, (size_t)n_prof, prof_stride));
-        HIP_TRY(up_rows(d_bmag, bmag, (size_t)n_alt, field_rows, prof_stride));
-        HIP_TRY(up_rows(d_bpsi, bpsi, (size_t)n_alt, field_rows, prof_stride));
-        HIP_TRY(up_rows(d_alt, alt, (size_t)n_alt, alt_rows, alt_stride));
-        HIP_TRY(up_rows(d_tan, tangents, set_elems, tan_sets, tan_stride));
-        a.freq = d_freq; a.den = d_den; a.bmag = d_bmag; a.bpsi = d_bpsi; a.alt = d_alt; a.mult = d_mult; a.tan = d_tan;
-        a.out = d_out;
-        a.prof_stride = n_alt;
-        a.field_stride = shared_field ? 0 : n_alt;
-        a.alt_stride = alt_stride ? n_alt : 0;
-        a.tan_prof_stride = tan_stride ? (long long)set_elems : 0;
-    }
-    double* const d_out = a.out;
-    const double* const d_tan = a.tan;
-    HIP_TRY(hipEventRecord(c->begin_ev(), c->stream));
-    for (long long i = 0; i < pl.n_chunks; ++i) {
-        const JvpChunk ch = jvp_chunk(pl, n_tan, i);
-        a.tan = d_tan + (size_t)ch.first * (size_t)n_alt;
-        a.out = d_out + ch.first;
-        a.n_tan = ch.count;
-        HIP_TRY(prhf::launch_vfo_jvp(a, ch.nt, pl.threads, ch.lds_bytes, c->stream));
-    }
-    HIP_TRY(hipEventRecord(c->pending_end_ev(), c->stream));
-    c->mark_timed();
-    c->status_pending = true;
-    if (!dev) HIP_TRY(hipMemcpyAsync(out, d_out, out_elems * 8, hipMemcpyDeviceToHost, c->stream));
-    if (flags & PRHF_FLAG_ASYNC) return PRHF_OK;
-    return prhf_sync(c);
-}
-
-}  // namespace
 
 int prhf_vfo_jvp_f64(prhf_ctx* ctx, const double* freq_mhz, int64_t n_freq, const double* den, const double* bmag,
                      const double* bpsi, const double* alt, int64_t n_prof, int64_t n_alt, int64_t prof_stride_elems,
                      int64_t alt_stride_elems, const double* multiplier, int32_t n_points, int32_t mode, const double* tangents,
                      int64_t n_tan, int64_t tan_prof_stride_elems, double* vh_out, double* dvh_out, uint32_t flags) {
-    return jvp_run(ctx, freq_mhz, n_freq, den, bmag, bpsi, alt, n_prof, n_alt, prof_stride_elems, alt_stride_elems, multiplier,
-                   n_points, mode, tangents, n_tan, tan_prof_stride_elems, vh_out, dvh_out, flags);
+    const OperatorInputs in{freq_mhz, n_freq, den, bmag, bpsi, alt, n_prof, n_alt, prof_stride_elems, alt_stride_elems,
+                            multiplier, n_points, mode, flags};
+    return jvp_run(ctx, in, tangents, n_tan, tan_prof_stride_elems, vh_out, dvh_out);
 }
 
 int prhf_vfo_residual_f64(prhf_ctx* ctx, const double* freq_mhz, int64_t n_freq, const double* den,
@@ -1713,31 +1776,125 @@ int prhf_residual_many_f64(prhf_ctx* c, const double* vh_model, int64_t n_rows, 
 }
 
 namespace {
+// ---- The Snell family: prhf_snell_cartesian_f64 .. prhf_snell_muf_f64 ----
+
 struct SnellGeometry {
     int geometry;
     double earth_radius_km, dz_target_km, apex_boost;
     int max_substeps;
 };
+int check_snell_geometry(int32_t geometry) {
+    if (geometry != 0 && geometry != 1) return fail(PRHF_EINVAL, "geometry is 0 (flat Earth) or 1 (spherical Earth)");
+    return PRHF_OK;
+}
+// The four spherical controls, checked where the geometry reads them; a flat Earth takes its defaults
+int snell_controls(int32_t geometry, double earth_radius_km, double dz_target_km, double apex_boost, int32_t max_substeps,
+                   SnellGeometry* geo) {
+    *geo = SnellGeometry{0, 6371.0, 1.0, 200.0, 400};
+    if (geometry == 0) return PRHF_OK;
+    if (!(earth_radius_km > 0.0) || !(earth_radius_km < 1e300) || !(dz_target_km > 0.0) || !(apex_boost >= 0.0) || max_substeps < 1)
+        return fail(PRHF_EINVAL, "bad spherical tracer controls");
+    *geo = SnellGeometry{1, earth_radius_km, dz_target_km, apex_boost, max_substeps};
+    return PRHF_OK;
+}
+
+// The profile columns a Snell call is made on, and the path arrays a tracer call may ask for
+struct SnellColumns {
+    const double *den, *bmag, *bpsi, *alt;
+    int64_t n_prof, n_alt, alt_stride;
+    int32_t mode;
+};
+struct SnellPaths {
+    double *x, *z;
+    int64_t stride;
+};
+
+// What the three drivers put into SnellArgs alike: the columns' shape, mode, geometry, status words
+void snell_args(prhf_ctx* c, prhf::SnellArgs& a, const SnellGeometry& geo, int64_t n_rays, const SnellColumns& p) {
+    a.n_rays = n_rays; a.n_prof = p.n_prof; a.n_alt = p.n_alt; a.prof_stride = p.n_alt; a.alt_stride = p.alt_stride;
+    a.mode = p.mode == PRHF_MODE_O ? PRHF_KMODE_O : PRHF_KMODE_X;
+    a.geometry = geo.geometry;
+    a.earth_radius_km = geo.earth_radius_km;
+    a.dz_target_km = geo.dz_target_km;
+    a.apex_boost = geo.apex_boost;
+    a.max_substeps = geo.max_substeps;
+    a.status = c->h_status_dev;
+    a.resident_cus = c->cu_count;
+}
+
+// The level tables of a grouped launch, c->levels.  Per group and level: mu' (8 B), the compacted entry (32 B), its grid
+// level (4 B); per group: four scalars.
+struct LevelTables {
+    double *levels, *entries;
+    int *info, *kidx;
+};
+LevelTables carve_level_tables(Carver& k, int64_t n_groups, int64_t n_alt) {
+    const size_t cells = (size_t)n_groups * (size_t)(n_alt + 1);
+    LevelTables t;
+    t.levels = k.take<double>((cells + 1) & ~(size_t)1);          // (the entries behind them are read 16 bytes at a time)
+    t.entries = k.take<double>(4 * cells);
+    t.info = k.take<int>(4 * (size_t)n_groups);
+    t.kidx = k.take<int>(cells);
+    return t;
+}
+// limits: what the message names as counted in 32 bits ("groups", or "groups / rays" where the launch has rays of its
+// own: n_rays, else 0); verb: what to do in batches
+int check_level_tables(int64_t n_groups, int64_t n_alt, int64_t n_rays, const char* limits, const char* verb) {
+    Carver sizing(nullptr);
+    carve_level_tables(sizing, n_groups, n_alt);
+    if (sizing.used() > ((size_t)64 << 30) || n_groups > 0x7fffffffLL || n_rays > 0x7fffffffLL)
+        return fail(PRHF_EINVAL, "level tables of %lld groups exceed 64 GiB (or 2^31 - 1 %s): %s in batches",
+                    (long long)n_groups, limits, verb);
+    return PRHF_OK;
+}
+int level_tables(prhf_ctx* c, prhf::SnellArgs& a, int64_t n_groups, int64_t n_alt) {
+    return carve(c, c->levels, [&](Stager& k) {
+        const LevelTables t = carve_level_tables(k, n_groups, n_alt);
+        a.levels = t.levels; a.group_entries = t.entries; a.group_info = t.info; a.group_kidx = t.kidx;
+    });
+}
+
+// The per-profile scalars at the head of c->partial (the operator's chunk scratch is free here), 128-byte rounded
+void carve_prof_info(Carver& k, prhf::SnellArgs& a, int64_t n_prof) {
+    a.prof_info = k.take<double>(4 * (size_t)n_prof);
+    k.align(128);
+}
+// The per-profile table of a launch with n_keys (profile, frequency) keys: option "snell_table", at most 1 GiB
+int profile_table(prhf_ctx* c, prhf::SnellArgs& a, int64_t n_keys, int64_t n_prof, int64_t n_alt) {
+    const size_t prof_elems = (size_t)n_prof * (size_t)n_alt;
+    a.ptab = nullptr;
+    if (c->knobs.snell_table > 0 && (double)n_keys >= c->knobs.snell_table * (double)n_prof && prof_elems * 32 <= ((size_t)1 << 30)) {
+        PRHF_TRY(ensure(c, c->ptab, prof_elems * 32));
+        a.ptab = static_cast<double*>(c->ptab.p);
+    }
+    return PRHF_OK;
+}
+
+// The four columns of a host-buffer call at the head of the arena: den, bmag, bpsi (n_prof, n_alt) and alt
+void put_columns(Stager& k, prhf::SnellArgs& a, const SnellColumns& p) {
+    const size_t prof_elems = (size_t)p.n_prof * (size_t)p.n_alt;
+    a.den = k.put<double>(p.den, prof_elems);
+    a.bmag = k.put<double>(p.bmag, prof_elems);
+    a.bpsi = k.put<double>(p.bpsi, prof_elems);
+    a.alt = k.put<double>(p.alt, p.alt_stride ? prof_elems : (size_t)p.n_alt);
+}
+
 // Grouped launch: freq_hz / profile_index describe n_groups (profile, frequency) groups and ray_group[r] names the
 // group of ray r; ungrouped: ray_group == nullptr, n_groups == 0 and freq_hz / profile_index are per ray.
-int snell_run(prhf_ctx* c, const SnellGeometry& geo, const double* freq_hz, const double* elevation_deg,
-              const int64_t* profile_index, int64_t n_rays, const double* den, const double* bmag,
-              const double* bpsi, const double* alt, int64_t n_prof, int64_t n_alt, int64_t alt_stride_elems,
-              int32_t mode, double* out, double* path_x, double* path_z, int64_t path_stride, uint32_t flags,
+int snell_run(prhf_ctx* c, const SnellGeometry& geo, const SnellColumns& p, const double* freq_hz, const double* elevation_deg,
+              const int64_t* profile_index, int64_t n_rays, double* out, const SnellPaths& paths, uint32_t flags,
               const int64_t* ray_group = nullptr, int64_t n_groups = 0) {
+    const double *den = p.den, *bmag = p.bmag, *bpsi = p.bpsi, *alt = p.alt;
+    const int64_t n_prof = p.n_prof, n_alt = p.n_alt, alt_stride_elems = p.alt_stride, path_stride = paths.stride;
+    const int32_t mode = p.mode;
+    double *const path_x = paths.x, *const path_z = paths.z;
     if (!c) return fail(PRHF_EINVAL, "null context");
     if (!freq_hz || !elevation_deg || !den || !bmag || !bpsi || !alt || !out)
         return fail(PRHF_EINVAL, "null array pointer");
     const bool grouped = ray_group != nullptr;
     if (grouped && n_groups < 1) return fail(PRHF_EINVAL, "a grouped launch needs at least one group");
     const int64_t n_keys = grouped ? n_groups : n_rays;          // entries of freq_hz / profile_index
-    // per group and level: mu' (8 B), the compacted entry (32 B), its grid level (4 B); per group: four scalars
-    const size_t level_cells = grouped ? (size_t)n_groups * (size_t)(n_alt + 1) : 0;
-    const size_t mup_cells = (level_cells + 1) & ~(size_t)1;      // (the entries behind them are read 16 bytes at a time)
-    const size_t level_bytes = mup_cells * 8 + level_cells * 36 + (grouped ? (size_t)n_groups * 16 : 0);
-    if (level_bytes > ((size_t)64 << 30) || n_groups > 0x7fffffffLL || (grouped && n_rays > 0x7fffffffLL))
-        return fail(PRHF_EINVAL, "level tables of %lld groups exceed 64 GiB (or 2^31 - 1 groups / rays): trace in batches",
-                    (long long)n_groups);
+    if (grouped) PRHF_TRY(check_level_tables(n_groups, n_alt, n_rays, "groups / rays", "trace"));
     if (n_rays < 0 || n_prof < 1 || n_alt < 2 || n_alt > 3000) return fail(PRHF_EINVAL, "bad shape");
     if (grouped && n_prof > 0x7fffffffLL) return fail(PRHF_EINVAL, "a grouped launch takes at most 2^31 - 1 profiles");
     if ((path_x == nullptr) != (path_z == nullptr)) return fail(PRHF_EINVAL, "path_x and path_z go together");
@@ -1748,154 +1905,93 @@ int snell_run(prhf_ctx* c, const SnellGeometry& geo, const double* freq_hz, cons
     if (flags & ~PRHF_FLAG_DEVICE_PTRS) return fail(PRHF_EINVAL, "unknown flag bits");
     if (n_rays == 0) return PRHF_OK;
     const bool dev = (flags & PRHF_FLAG_DEVICE_PTRS) != 0;
-    if (!dev && profile_index)
-        for (int64_t r = 0; r < n_keys; ++r)
-            if (profile_index[r] < 0 || profile_index[r] >= n_prof)
-                return fail(PRHF_EINVAL, "profile_index[%lld] outside [0, n_prof)", (long long)r);
-    if (!dev && grouped)
-        for (int64_t r = 0; r < n_rays; ++r)
-            if (ray_group[r] < 0 || ray_group[r] >= n_groups)
-                return fail(PRHF_EINVAL, "ray_group[%lld] outside [0, n_groups)", (long long)r);
+    if (!dev && profile_index) PRHF_TRY(check_index("profile_index", profile_index, n_keys, "n_prof", n_prof));
+    if (!dev && grouped) PRHF_TRY(check_index("ray_group", ray_group, n_rays, "n_groups", n_groups));
     ENTER_DEVICE(c->device);
     prhf::SnellArgs a;
     std::memset(&a, 0, sizeof a);
-    a.n_rays = n_rays; a.n_alt = n_alt; a.prof_stride = n_alt; a.alt_stride = alt_stride_elems;
+    snell_args(c, a, geo, n_rays, p);
     a.path_stride = path_x ? path_stride : 0;
-    a.mode = mode == PRHF_MODE_O ? PRHF_KMODE_O : PRHF_KMODE_X;
-    a.geometry = geo.geometry;
     a.reduced = (c->math == PRHF_MATH_FAITHFUL) ? 0 : 1;        // (grouped launches read faithful level tables either way)
-    a.earth_radius_km = geo.earth_radius_km;
-    a.dz_target_km = geo.dz_target_km;
-    a.apex_boost = geo.apex_boost;
-    a.max_substeps = geo.max_substeps;
-    a.status = c->h_status_dev;
-    const size_t prof_elems = (size_t)n_prof * (size_t)n_alt;
-    const size_t alt_elems = alt_stride_elems ? prof_elems : (size_t)n_alt;
-    const size_t path_elems = path_x ? (size_t)n_rays * (size_t)path_stride : 0;
-    const double* d_keyf = nullptr;
-    const long long* d_keyp = nullptr;
-    const long long* d_group = nullptr;
+    const size_t R = (size_t)n_rays, path_elems = path_x ? R * (size_t)path_stride : 0;
+    const double* d_keyf = freq_hz;
+    const long long* d_keyp = reinterpret_cast<const long long*>(profile_index);
+    const long long* d_group = reinterpret_cast<const long long*>(ray_group);
     bool small_out = false;                    // a small host-buffer call: the kernel writes its results into pinned host memory
     if (dev) {
         a.den = den; a.bmag = bmag; a.bpsi = bpsi; a.alt = alt; a.elev_deg = elevation_deg;
-        d_keyf = freq_hz;
-        d_keyp = reinterpret_cast<const long long*>(profile_index);
-        d_group = reinterpret_cast<const long long*>(ray_group);
         a.out = out; a.path_x = path_x; a.path_z = path_z;
     } else {
-        const size_t elems = 3 * prof_elems + alt_elems + 2 * (size_t)n_keys + 2 * (size_t)n_rays +
-                             PRHF_SNELL_OUTPUTS * (size_t)n_rays + 2 * path_elems;
-        int rc = ensure(c, c->arena, elems * 8);
-        if (rc != PRHF_OK) return rc;
-        double* p = static_cast<double*>(c->arena.p);
-        double* d_den = p; p += prof_elems;
-        double* d_bmag = p; p += prof_elems;
-        double* d_bpsi = p; p += prof_elems;
-        double* d_alt = p; p += alt_elems;
-        double* d_f = p; p += n_keys;
-        long long* d_i = reinterpret_cast<long long*>(p); p += n_keys;
-        double* d_e = p; p += n_rays;
-        long long* d_g = reinterpret_cast<long long*>(p); p += n_rays;
-        double* d_out = p; p += PRHF_SNELL_OUTPUTS * (size_t)n_rays;
-        double* d_px = path_x ? p : nullptr; p += path_elems;
-        double* d_pz = path_x ? p : nullptr;
+        auto inputs = [&](Stager& k) {
+            put_columns(k, a, p);
+            d_keyf = k.put<double>(freq_hz, (size_t)n_keys);
+            d_keyp = k.put<long long>(profile_index, (size_t)n_keys);
+            a.elev_deg = k.put<double>(elevation_deg, R);
+            d_group = k.put<long long>(ray_group, R);
+        };
+        auto outputs = [&](Stager& k) {
+            a.out = k.take<double>(PRHF_SNELL_OUTPUTS * R);
+            a.path_x = k.take<double>(path_elems);
+            a.path_z = k.take<double>(path_elems);
+        };
+        Stager sizing(c, nullptr);
+        inputs(sizing);
+        const size_t in_bytes = sizing.used();
+        outputs(sizing);
+        PRHF_TRY(ensure(c, c->arena, sizing.used()));
         // A small call (the reference's own: ONE ray, its path arrays back): six to eight uploads from pageable memory
         // and three copies back cost several times the kernels.  As in run(): the inputs are packed in the arena's own
         // order and sent in one piece - or, on a large-BAR device with the arena idle, written straight into it by the
         // CPU - and the kernel writes the results into pinned host memory that the device sees (the upper half of the
         // pack buffer).
-        double* base = static_cast<double*>(c->arena.p);
-        const size_t in_elems = (size_t)(d_out - base);
-        const size_t out_elems = PRHF_SNELL_OUTPUTS * (size_t)n_rays + 2 * path_elems;
-        small_out = c->h_pack && in_elems * 8 <= kPackBytes / 2 && out_elems * 8 <= kPackBytes / 4;
-        if (small_out) {
-            const bool direct = c->large_bar && c->knobs.direct_upload != 0 && in_elems * 8 <= kDirectBytes &&
-                                hipStreamQuery(c->stream) == hipSuccess &&
-                                (!c->timed || hipEventQuery(c->end_ev()) == hipSuccess);
-            (void)hipGetLastError();               // (hipErrorNotReady from the two queries is not an error)
-            double* h = direct ? base : c->h_pack;
-            std::memcpy(h + (d_den - base), den, prof_elems * 8);
-            std::memcpy(h + (d_bmag - base), bmag, prof_elems * 8);
-            std::memcpy(h + (d_bpsi - base), bpsi, prof_elems * 8);
-            std::memcpy(h + (d_alt - base), alt, alt_elems * 8);
-            std::memcpy(h + (d_f - base), freq_hz, (size_t)n_keys * 8);
-            std::memcpy(h + (d_e - base), elevation_deg, (size_t)n_rays * 8);
-            if (profile_index) std::memcpy(h + (reinterpret_cast<double*>(d_i) - base), profile_index, (size_t)n_keys * 8);
-            if (grouped) std::memcpy(h + (reinterpret_cast<double*>(d_g) - base), ray_group, (size_t)n_rays * 8);
-            if (direct) _mm_sfence();
-            else HIP_TRY(hipMemcpyAsync(base, h, in_elems * 8, hipMemcpyHostToDevice, c->stream));
-        } else {
-            HIP_TRY(hipMemcpyAsync(d_den, den, prof_elems * 8, hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(hipMemcpyAsync(d_bmag, bmag, prof_elems * 8, hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(hipMemcpyAsync(d_bpsi, bpsi, prof_elems * 8, hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(hipMemcpyAsync(d_alt, alt, alt_elems * 8, hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(hipMemcpyAsync(d_f, freq_hz, (size_t)n_keys * 8, hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(hipMemcpyAsync(d_e, elevation_deg, (size_t)n_rays * 8, hipMemcpyHostToDevice, c->stream));
-            if (profile_index)
-                HIP_TRY(hipMemcpyAsync(d_i, profile_index, (size_t)n_keys * 8, hipMemcpyHostToDevice, c->stream));
-            if (grouped)
-                HIP_TRY(hipMemcpyAsync(d_g, ray_group, (size_t)n_rays * 8, hipMemcpyHostToDevice, c->stream));
-        }
-        a.den = d_den; a.bmag = d_bmag; a.bpsi = d_bpsi; a.alt = d_alt; a.elev_deg = d_e;
-        d_keyf = d_f;
-        d_keyp = profile_index ? d_i : nullptr;
-        d_group = grouped ? d_g : nullptr;
-        a.out = d_out; a.path_x = d_px; a.path_z = d_pz;
+        const size_t out_elems = PRHF_SNELL_OUTPUTS * R + 2 * path_elems;
+        small_out = c->h_pack && in_bytes <= kPackBytes / 2 && out_elems * 8 <= kPackBytes / 4;
+        const bool direct = small_out && c->large_bar && c->knobs.direct_upload != 0 && in_bytes <= kDirectBytes &&
+                            hipStreamQuery(c->stream) == hipSuccess && (!c->timed || hipEventQuery(c->end_ev()) == hipSuccess);
+        if (small_out) (void)hipGetLastError();        // (hipErrorNotReady from the two queries is not an error)
+        void* const pack = !small_out ? nullptr : direct ? c->arena.p : c->h_pack;
+        Stager k(c, c->arena.p, pack);
+        inputs(k);
+        HIP_TRY(k.error());
+        if (direct) _mm_sfence();
+        else if (small_out) HIP_TRY(upload(c, c->arena.p, pack, in_bytes));
+        outputs(k);
         if (small_out) {
             a.out = c->h_pack_dev + kPackBytes / 16;               // doubles: byte offset kPackBytes / 2
-            a.path_x = path_x ? a.out + PRHF_SNELL_OUTPUTS * (size_t)n_rays : nullptr;
-            a.path_z = path_x ? a.path_x + path_elems : nullptr;
+            a.path_x = a.out + PRHF_SNELL_OUTPUTS * R;
+            a.path_z = a.path_x + path_elems;
         }
+        if (!path_x) a.path_x = a.path_z = nullptr;
     }
     if (grouped) {
         a.ray_group = d_group; a.group_freq = d_keyf; a.group_prof = d_keyp; a.n_groups = n_groups;
-        int rc3 = ensure(c, c->levels, level_bytes);
-        if (rc3 != PRHF_OK) return rc3;
-        a.levels = static_cast<double*>(c->levels.p);
-        a.group_entries = a.levels + mup_cells;
-        a.group_info = reinterpret_cast<int*>(a.group_entries + 4 * level_cells);
-        a.group_kidx = a.group_info + 4 * (size_t)n_groups;
+        PRHF_TRY(level_tables(c, a, n_groups, n_alt));
     } else {
         a.freq_hz = d_keyf; a.prof_idx = d_keyp;
-        // per-ray launch: persistent wavefronts drawing rays from a queue
-        a.ray_queue = nullptr;                                     // (set below: behind the per-profile scalars)
     }
-    a.resident_cus = c->cu_count;
-    {
-        // per-profile scalars (the operator's chunk scratch is free here); behind them the per-ray launch's queue counters
-        const size_t info_bytes = (((size_t)n_prof * 32 + 127) / 128) * 128;
-        int rc2 = ensure(c, c->partial, info_bytes + prhf::snell_queue_bytes());
-        if (rc2 != PRHF_OK) return rc2;
-        a.prof_info = static_cast<double*>(c->partial.p);
-        a.n_prof = n_prof;
-        if (!grouped) a.ray_queue = reinterpret_cast<unsigned*>(static_cast<char*>(c->partial.p) + info_bytes);
-    }
-    a.ptab = nullptr;
-    if (c->knobs.snell_table > 0 && (double)n_keys >= c->knobs.snell_table * (double)n_prof && prof_elems * 32 <= ((size_t)1 << 30)) {
-        int rc4 = ensure(c, c->ptab, prof_elems * 32);
-        if (rc4 != PRHF_OK) return rc4;
-        a.ptab = static_cast<double*>(c->ptab.p);
-    }
-    HIP_TRY(hipEventRecord(c->begin_ev(), c->stream));
-    HIP_TRY(prhf::launch_snell(a, c->stream));
-    HIP_TRY(hipEventRecord(c->pending_end_ev(), c->stream));
-    c->mark_timed();
-    c->status_pending = true;
+    // per-profile scalars; behind them the queue counters of the per-ray launch (persistent wavefronts drawing rays from a queue)
+    PRHF_TRY(carve(c, c->partial, [&](Stager& k) {
+        carve_prof_info(k, a, n_prof);
+        unsigned* queue = k.take<unsigned>(prhf::snell_queue_bytes() / sizeof(unsigned));
+        a.ray_queue = grouped ? nullptr : queue;
+    }));
+    PRHF_TRY(profile_table(c, a, n_keys, n_prof, n_alt));
+    PRHF_TRY(timed_launch(c, true, [&] { return prhf::launch_snell(a, c->stream); }));
     if (small_out) {                                               // (written by the kernel itself into pinned memory)
         const int rc = prhf_sync(c);
         const double* h_out = c->h_pack + kPackBytes / 16;
-        std::memcpy(out, h_out, PRHF_SNELL_OUTPUTS * (size_t)n_rays * 8);
+        std::memcpy(out, h_out, PRHF_SNELL_OUTPUTS * R * 8);
         if (path_x) {
-            std::memcpy(path_x, h_out + PRHF_SNELL_OUTPUTS * (size_t)n_rays, path_elems * 8);
-            std::memcpy(path_z, h_out + PRHF_SNELL_OUTPUTS * (size_t)n_rays + path_elems, path_elems * 8);
+            std::memcpy(path_x, h_out + PRHF_SNELL_OUTPUTS * R, path_elems * 8);
+            std::memcpy(path_z, h_out + PRHF_SNELL_OUTPUTS * R + path_elems, path_elems * 8);
         }
         return rc;
     }
     if (!dev) {
-        HIP_TRY(hipMemcpyAsync(out, a.out, PRHF_SNELL_OUTPUTS * (size_t)n_rays * 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(download(c, out, a.out, PRHF_SNELL_OUTPUTS * R * 8));
         if (path_x) {
-            HIP_TRY(hipMemcpyAsync(path_x, a.path_x, path_elems * 8, hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipMemcpyAsync(path_z, a.path_z, path_elems * 8, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(download(c, path_x, a.path_x, path_elems * 8));
+            HIP_TRY(download(c, path_z, a.path_z, path_elems * 8));
         }
     }
     return prhf_sync(c);
@@ -1907,9 +2003,10 @@ int prhf_snell_cartesian_f64(prhf_ctx* c, const double* freq_hz, const double* e
                              const double* bpsi, const double* alt, int64_t n_prof, int64_t n_alt,
                              int64_t alt_stride_elems, int32_t mode, double* out, double* path_x, double* path_z,
                              int64_t path_stride, uint32_t flags) {
-    const SnellGeometry geo{0, 6371.0, 1.0, 200.0, 400};
-    return snell_run(c, geo, freq_hz, elevation_deg, profile_index, n_rays, den, bmag, bpsi, alt, n_prof, n_alt,
-                     alt_stride_elems, mode, out, path_x, path_z, path_stride, flags);
+    SnellGeometry geo;
+    PRHF_TRY(snell_controls(0, 0.0, 0.0, 0.0, 0, &geo));
+    return snell_run(c, geo, SnellColumns{den, bmag, bpsi, alt, n_prof, n_alt, alt_stride_elems, mode}, freq_hz, elevation_deg,
+                     profile_index, n_rays, out, SnellPaths{path_x, path_z, path_stride}, flags);
 }
 
 int prhf_snell_spherical_f64(prhf_ctx* c, const double* freq_hz, const double* elevation_deg,
@@ -1918,11 +2015,10 @@ int prhf_snell_spherical_f64(prhf_ctx* c, const double* freq_hz, const double* e
                              int64_t alt_stride_elems, int32_t mode, double earth_radius_km, double dz_target_km,
                              double apex_boost, int32_t max_substeps, double* out, double* path_x, double* path_z,
                              int64_t path_stride, uint32_t flags) {
-    if (!(earth_radius_km > 0.0) || !(earth_radius_km < 1e300) || !(dz_target_km > 0.0) || !(apex_boost >= 0.0) || max_substeps < 1)
-        return fail(PRHF_EINVAL, "bad spherical tracer controls");
-    const SnellGeometry geo{1, earth_radius_km, dz_target_km, apex_boost, max_substeps};
-    return snell_run(c, geo, freq_hz, elevation_deg, profile_index, n_rays, den, bmag, bpsi, alt, n_prof, n_alt,
-                     alt_stride_elems, mode, out, path_x, path_z, path_stride, flags);
+    SnellGeometry geo;
+    PRHF_TRY(snell_controls(1, earth_radius_km, dz_target_km, apex_boost, max_substeps, &geo));
+    return snell_run(c, geo, SnellColumns{den, bmag, bpsi, alt, n_prof, n_alt, alt_stride_elems, mode}, freq_hz, elevation_deg,
+                     profile_index, n_rays, out, SnellPaths{path_x, path_z, path_stride}, flags);
 }
 
 int prhf_snell_fan_f64(prhf_ctx* c, int32_t geometry, const double* group_freq_hz, const int64_t* group_profile_index,
@@ -1931,15 +2027,13 @@ int prhf_snell_fan_f64(prhf_ctx* c, int32_t geometry, const double* group_freq_h
                        int64_t n_alt, int64_t alt_stride_elems, int32_t mode, double earth_radius_km,
                        double dz_target_km, double apex_boost, int32_t max_substeps, double* out, double* path_x,
                        double* path_z, int64_t path_stride, uint32_t flags) {
-    if (geometry != 0 && geometry != 1) return fail(PRHF_EINVAL, "geometry is 0 (flat Earth) or 1 (spherical Earth)");
+    PRHF_TRY(check_snell_geometry(geometry));
     if (!ray_group) return fail(PRHF_EINVAL, "null array pointer");
-    if (geometry == 1 && (!(earth_radius_km > 0.0) || !(earth_radius_km < 1e300) || !(dz_target_km > 0.0) || !(apex_boost >= 0.0) ||
-                          max_substeps < 1))
-        return fail(PRHF_EINVAL, "bad spherical tracer controls");
-    const SnellGeometry geo = geometry == 0 ? SnellGeometry{0, 6371.0, 1.0, 200.0, 400}
-                                            : SnellGeometry{1, earth_radius_km, dz_target_km, apex_boost, max_substeps};
-    return snell_run(c, geo, group_freq_hz, elevation_deg, group_profile_index, n_rays, den, bmag, bpsi, alt, n_prof, n_alt,
-                     alt_stride_elems, mode, out, path_x, path_z, path_stride, flags, ray_group, n_groups);
+    SnellGeometry geo;
+    PRHF_TRY(snell_controls(geometry, earth_radius_km, dz_target_km, apex_boost, max_substeps, &geo));
+    return snell_run(c, geo, SnellColumns{den, bmag, bpsi, alt, n_prof, n_alt, alt_stride_elems, mode}, group_freq_hz,
+                     elevation_deg, group_profile_index, n_rays, out, SnellPaths{path_x, path_z, path_stride}, flags, ray_group,
+                     n_groups);
 }
 
 int prhf_snell_home_f64(prhf_ctx* c, int32_t geometry, const double* group_freq_hz, const int64_t* group_profile_index,
@@ -1953,23 +2047,16 @@ int prhf_snell_home_f64(prhf_ctx* c, int32_t geometry, const double* group_freq_
     if (!group_freq_hz || !link_group || !link_range_km || !scan_elevation_deg || !den || !bmag || !bpsi || !alt || !out ||
         !n_brackets)
         return fail(PRHF_EINVAL, "null array pointer");
-    if (geometry != 0 && geometry != 1) return fail(PRHF_EINVAL, "geometry is 0 (flat Earth) or 1 (spherical Earth)");
-    if (geometry == 1 && (!(earth_radius_km > 0.0) || !(earth_radius_km < 1e300) || !(dz_target_km > 0.0) || !(apex_boost >= 0.0) ||
-                          max_substeps < 1))
-        return fail(PRHF_EINVAL, "bad spherical tracer controls");
+    SnellGeometry geo;
+    PRHF_TRY(check_snell_geometry(geometry));
+    PRHF_TRY(snell_controls(geometry, earth_radius_km, dz_target_km, apex_boost, max_substeps, &geo));
     if (n_scan < 2) return fail(PRHF_EINVAL, "the scan grid needs at least 2 elevations");
     if (max_iter < 1 || max_iter > 128) return fail(PRHF_EINVAL, "max_iter is 1 .. 128");
     if (max_roots < 1 || max_roots > 64) return fail(PRHF_EINVAL, "max_roots is 1 .. 64");
     if (!(range_tol_km >= 0.0) || !std::isfinite(range_tol_km))
         return fail(PRHF_EINVAL, "range_tol_km must be finite and not negative");
     if (n_groups < 1) return fail(PRHF_EINVAL, "homing needs at least one group");
-    // per group and level: mu' (8 B), the compacted entry (32 B), its grid level (4 B); per group: four scalars (snell_run)
-    const size_t level_cells = (size_t)n_groups * (size_t)(n_alt + 1);
-    const size_t mup_cells = (level_cells + 1) & ~(size_t)1;
-    const size_t level_bytes = mup_cells * 8 + level_cells * 36 + (size_t)n_groups * 16;
-    if (level_bytes > ((size_t)64 << 30) || n_groups > 0x7fffffffLL)
-        return fail(PRHF_EINVAL, "level tables of %lld groups exceed 64 GiB (or 2^31 - 1 groups): home in batches",
-                    (long long)n_groups);
+    PRHF_TRY(check_level_tables(n_groups, n_alt, 0, "groups", "home"));
     if (n_links < 0 || n_prof < 1 || n_prof > 0x7fffffffLL || n_alt < 2 || n_alt > 3000) return fail(PRHF_EINVAL, "bad shape");
     if (n_groups * n_scan > 0x7fffffffLL || n_links * (int64_t)max_roots > 0x7fffffffLL)
         return fail(PRHF_EINVAL, "more than 2^31 - 1 scan rays or result rows: home in batches");
@@ -1978,35 +2065,21 @@ int prhf_snell_home_f64(prhf_ctx* c, int32_t geometry, const double* group_freq_
     if (flags & ~PRHF_FLAG_DEVICE_PTRS) return fail(PRHF_EINVAL, "unknown flag bits");
     const bool dev = (flags & PRHF_FLAG_DEVICE_PTRS) != 0;
     if (!dev) {
-        for (int64_t i = 0; i + 1 < n_scan; ++i)
-            if (!(scan_elevation_deg[i + 1] > scan_elevation_deg[i]))
-                return fail(PRHF_EINVAL, "scan_elevation_deg must be strictly increasing");
-        if (group_profile_index)
-            for (int64_t g = 0; g < n_groups; ++g)
-                if (group_profile_index[g] < 0 || group_profile_index[g] >= n_prof)
-                    return fail(PRHF_EINVAL, "profile_index[%lld] outside [0, n_prof)", (long long)g);
-        for (int64_t l = 0; l < n_links; ++l)
-            if (link_group[l] < 0 || link_group[l] >= n_groups)
-                return fail(PRHF_EINVAL, "link_group[%lld] outside [0, n_groups)", (long long)l);
+        PRHF_TRY(check_scan_grid(scan_elevation_deg, n_scan, false));
+        if (group_profile_index) PRHF_TRY(check_index("profile_index", group_profile_index, n_groups, "n_prof", n_prof));
+        PRHF_TRY(check_index("link_group", link_group, n_links, "n_groups", n_groups));
     }
     if (n_links == 0) return PRHF_OK;
     ENTER_DEVICE(c->device);
+    const SnellColumns p{den, bmag, bpsi, alt, n_prof, n_alt, alt_stride_elems, mode};
     prhf::HomeArgs h;
     std::memset(&h, 0, sizeof h);
     prhf::SnellArgs& a = h.s;
-    a.n_rays = 1; a.n_alt = n_alt; a.prof_stride = n_alt; a.alt_stride = alt_stride_elems;
-    a.mode = mode == PRHF_MODE_O ? PRHF_KMODE_O : PRHF_KMODE_X;
-    a.geometry = geometry;
-    a.earth_radius_km = geometry == 0 ? 6371.0 : earth_radius_km;
-    a.dz_target_km = geometry == 0 ? 1.0 : dz_target_km;
-    a.apex_boost = geometry == 0 ? 200.0 : apex_boost;
-    a.max_substeps = geometry == 0 ? 400 : max_substeps;
-    a.status = c->h_status_dev;
-    a.n_groups = n_groups; a.n_prof = n_prof; a.resident_cus = c->cu_count;
+    snell_args(c, a, geo, 1, p);
+    a.n_groups = n_groups;
     h.n_links = n_links; h.n_scan = (int)n_scan; h.range_tol = range_tol_km; h.max_iter = max_iter; h.max_roots = max_roots;
-    const size_t prof_elems = (size_t)n_prof * (size_t)n_alt;
-    const size_t alt_elems = alt_stride_elems ? prof_elems : (size_t)n_alt;
-    const size_t out_elems = (size_t)n_links * (size_t)max_roots * PRHF_HOME_OUTPUTS;
+    const size_t G = (size_t)n_groups, L = (size_t)n_links, E = (size_t)n_scan;
+    const size_t out_elems = L * (size_t)max_roots * PRHF_HOME_OUTPUTS;
     if (dev) {
         a.den = den; a.bmag = bmag; a.bpsi = bpsi; a.alt = alt;
         a.group_freq = group_freq_hz;
@@ -2015,72 +2088,31 @@ int prhf_snell_home_f64(prhf_ctx* c, int32_t geometry, const double* group_freq_
         h.link_range = link_range_km; h.scan_elev = scan_elevation_deg;
         h.out = out; h.n_brackets = reinterpret_cast<long long*>(n_brackets);
     } else {
-        const size_t elems = 3 * prof_elems + alt_elems + 2 * (size_t)n_groups + 3 * (size_t)n_links + (size_t)n_scan + out_elems;
-        int rc = ensure(c, c->arena, elems * 8);
-        if (rc != PRHF_OK) return rc;
-        double* p = static_cast<double*>(c->arena.p);
-        double* d_den = p; p += prof_elems;
-        double* d_bmag = p; p += prof_elems;
-        double* d_bpsi = p; p += prof_elems;
-        double* d_alt = p; p += alt_elems;
-        double* d_f = p; p += n_groups;
-        long long* d_i = reinterpret_cast<long long*>(p); p += n_groups;
-        long long* d_lg = reinterpret_cast<long long*>(p); p += n_links;
-        double* d_lr = p; p += n_links;
-        double* d_e = p; p += n_scan;
-        long long* d_nb = reinterpret_cast<long long*>(p); p += n_links;
-        double* d_out = p;
-        HIP_TRY(hipMemcpyAsync(d_den, den, prof_elems * 8, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(d_bmag, bmag, prof_elems * 8, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(d_bpsi, bpsi, prof_elems * 8, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(d_alt, alt, alt_elems * 8, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(d_f, group_freq_hz, (size_t)n_groups * 8, hipMemcpyHostToDevice, c->stream));
-        if (group_profile_index)
-            HIP_TRY(hipMemcpyAsync(d_i, group_profile_index, (size_t)n_groups * 8, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(d_lg, link_group, (size_t)n_links * 8, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(d_lr, link_range_km, (size_t)n_links * 8, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(d_e, scan_elevation_deg, (size_t)n_scan * 8, hipMemcpyHostToDevice, c->stream));
-        a.den = d_den; a.bmag = d_bmag; a.bpsi = d_bpsi; a.alt = d_alt;
-        a.group_freq = d_f; a.group_prof = group_profile_index ? d_i : nullptr;
-        h.link_group = d_lg; h.link_range = d_lr; h.scan_elev = d_e;
-        h.out = d_out; h.n_brackets = d_nb;
+        PRHF_TRY(carve(c, c->arena, [&](Stager& k) {
+            put_columns(k, a, p);
+            a.group_freq = k.put<double>(group_freq_hz, G);
+            a.group_prof = k.put<long long>(group_profile_index, G);
+            h.link_group = k.put<long long>(link_group, L);
+            h.link_range = k.put<double>(link_range_km, L);
+            h.scan_elev = k.put<double>(scan_elevation_deg, E);
+            h.n_brackets = k.take<long long>(L);
+            h.out = k.take<double>(out_elems);
+        }));
     }
-    {
-        int rc = ensure(c, c->levels, level_bytes);
-        if (rc != PRHF_OK) return rc;
-        a.levels = static_cast<double*>(c->levels.p);
-        a.group_entries = a.levels + mup_cells;
-        a.group_info = reinterpret_cast<int*>(a.group_entries + 4 * level_cells);
-        a.group_kidx = a.group_info + 4 * (size_t)n_groups;
-    }
-    {
-        // per-profile scalars; behind them the refine launch's counters, the work list and the scan's ground ranges
-        const size_t info_bytes = (((size_t)n_prof * 32 + 127) / 128) * 128;
-        const size_t queue_bytes = ((prhf::home_queue_bytes() + 127) / 128) * 128;
-        const size_t work_bytes = (size_t)n_links * (size_t)max_roots * 16;
-        const size_t scan_bytes = (size_t)n_groups * (size_t)n_scan * 8;
-        int rc = ensure(c, c->partial, info_bytes + queue_bytes + work_bytes + scan_bytes);
-        if (rc != PRHF_OK) return rc;
-        char* q = static_cast<char*>(c->partial.p);
-        a.prof_info = reinterpret_cast<double*>(q);
-        h.queue = reinterpret_cast<unsigned*>(q + info_bytes);
-        h.work = reinterpret_cast<int*>(q + info_bytes + queue_bytes);
-        h.scan_d = reinterpret_cast<double*>(q + info_bytes + queue_bytes + work_bytes);
-    }
-    a.ptab = nullptr;
-    if (c->knobs.snell_table > 0 && (double)n_groups >= c->knobs.snell_table * (double)n_prof && prof_elems * 32 <= ((size_t)1 << 30)) {
-        int rc = ensure(c, c->ptab, prof_elems * 32);
-        if (rc != PRHF_OK) return rc;
-        a.ptab = static_cast<double*>(c->ptab.p);
-    }
-    HIP_TRY(hipEventRecord(c->begin_ev(), c->stream));
-    HIP_TRY(prhf::launch_snell_home(h, c->stream));
-    HIP_TRY(hipEventRecord(c->pending_end_ev(), c->stream));
-    c->mark_timed();
-    c->status_pending = true;
+    PRHF_TRY(level_tables(c, a, n_groups, n_alt));
+    // per-profile scalars; behind them the refine launch's counters, the work list and the scan's ground ranges
+    PRHF_TRY(carve(c, c->partial, [&](Stager& k) {
+        carve_prof_info(k, a, n_prof);
+        h.queue = k.take<unsigned>(prhf::home_queue_bytes() / sizeof(unsigned));
+        k.align(128);
+        h.work = k.take<int>(L * (size_t)max_roots * 4);
+        h.scan_d = k.take<double>(G * E);
+    }));
+    PRHF_TRY(profile_table(c, a, n_groups, n_prof, n_alt));
+    PRHF_TRY(timed_launch(c, true, [&] { return prhf::launch_snell_home(h, c->stream); }));
     if (!dev) {
-        HIP_TRY(hipMemcpyAsync(out, h.out, out_elems * 8, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipMemcpyAsync(n_brackets, h.n_brackets, (size_t)n_links * 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(download(c, out, h.out, out_elems * 8));
+        HIP_TRY(download(c, n_brackets, h.n_brackets, L * 8));
     }
     return prhf_sync(c);
 }
@@ -2089,50 +2121,47 @@ namespace {
 // prhf_snell_skip_f64 (link_range_km null: group_freq_hz and group_profile_index describe n_groups groups) and
 // prhf_snell_muf_f64 (a link is a group: group_profile_index is the links' profile index, n_groups their number, and the
 // group frequencies are the device's own).
-int skip_run(prhf_ctx* c, int32_t geometry, const double* group_freq_hz, const int64_t* group_profile_index, int64_t n_groups,
-             const double* link_range_km, double f_lo_hz, double f_hi_hz, int32_t n_bisect, const double* scan_elevation_deg,
-             int64_t n_scan, const double* den, const double* bmag, const double* bpsi, const double* alt, int64_t n_prof,
-             int64_t n_alt, int64_t alt_stride_elems, int32_t mode, double earth_radius_km, double dz_target_km,
-             double apex_boost, int32_t max_substeps, double elev_tol_deg, int32_t max_iter, double* out, uint32_t flags) {
+struct SkipControls {
+    int32_t geometry;
+    double earth_radius_km, dz_target_km, apex_boost;
+    int32_t max_substeps;
+    double elev_tol_deg;
+    int32_t max_iter;
+    double f_lo_hz, f_hi_hz;     // MUF only
+    int32_t n_bisect;
+};
+int skip_run(prhf_ctx* c, const SkipControls& s, const SnellColumns& p, const double* group_freq_hz,
+             const int64_t* group_profile_index, int64_t n_groups, const double* link_range_km, const double* scan_elevation_deg,
+             int64_t n_scan, double* out, uint32_t flags) {
+    const double *den = p.den, *bmag = p.bmag, *bpsi = p.bpsi, *alt = p.alt;
+    const int64_t n_prof = p.n_prof, n_alt = p.n_alt, alt_stride_elems = p.alt_stride;
+    const int32_t mode = p.mode;
     const bool muf = link_range_km != nullptr;
     if (!c) return fail(PRHF_EINVAL, "null context");
     if ((!muf && !group_freq_hz) || !scan_elevation_deg || !den || !bmag || !bpsi || !alt || !out)
         return fail(PRHF_EINVAL, "null array pointer");
-    if (geometry != 0 && geometry != 1) return fail(PRHF_EINVAL, "geometry is 0 (flat Earth) or 1 (spherical Earth)");
-    if (geometry == 1 && (!(earth_radius_km > 0.0) || !(earth_radius_km < 1e300) || !(dz_target_km > 0.0) || !(apex_boost >= 0.0) ||
-                          max_substeps < 1))
-        return fail(PRHF_EINVAL, "bad spherical tracer controls");
+    SnellGeometry geo;
+    PRHF_TRY(check_snell_geometry(s.geometry));
+    PRHF_TRY(snell_controls(s.geometry, s.earth_radius_km, s.dz_target_km, s.apex_boost, s.max_substeps, &geo));
     if (n_scan < 1) return fail(PRHF_EINVAL, "the scan grid needs at least 1 elevation");
-    if (max_iter < 1 || max_iter > 128) return fail(PRHF_EINVAL, "max_iter is 1 .. 128");
-    if (!(elev_tol_deg >= 0.0) || !std::isfinite(elev_tol_deg))
+    if (s.max_iter < 1 || s.max_iter > 128) return fail(PRHF_EINVAL, "max_iter is 1 .. 128");
+    if (!(s.elev_tol_deg >= 0.0) || !std::isfinite(s.elev_tol_deg))
         return fail(PRHF_EINVAL, "elev_tol_deg must be finite and not negative");
     if (muf) {
-        if (n_bisect < 1 || n_bisect > 64) return fail(PRHF_EINVAL, "n_bisect is 1 .. 64");
-        if (!(f_lo_hz > 0.0) || !(f_hi_hz > f_lo_hz) || !std::isfinite(f_hi_hz))
+        if (s.n_bisect < 1 || s.n_bisect > 64) return fail(PRHF_EINVAL, "n_bisect is 1 .. 64");
+        if (!(s.f_lo_hz > 0.0) || !(s.f_hi_hz > s.f_lo_hz) || !std::isfinite(s.f_hi_hz))
             return fail(PRHF_EINVAL, "the frequency bracket needs 0 < f_lo_hz < f_hi_hz, both finite");
     }
     if (n_groups < 0 || n_prof < 1 || n_prof > 0x7fffffffLL || n_alt < 2 || n_alt > 3000) return fail(PRHF_EINVAL, "bad shape");
-    // per group and level: mu' (8 B), the compacted entry (32 B), its grid level (4 B); per group: four scalars (snell_run)
-    const size_t level_cells = (size_t)n_groups * (size_t)(n_alt + 1);
-    const size_t mup_cells = (level_cells + 1) & ~(size_t)1;
-    const size_t level_bytes = mup_cells * 8 + level_cells * 36 + (size_t)n_groups * 16;
-    if (level_bytes > ((size_t)64 << 30) || n_groups > 0x7fffffffLL)
-        return fail(PRHF_EINVAL, "level tables of %lld groups exceed 64 GiB (or 2^31 - 1 groups): search in batches",
-                    (long long)n_groups);
+    PRHF_TRY(check_level_tables(n_groups, n_alt, 0, "groups", "search"));
     if (n_groups * n_scan > 0x7fffffffLL) return fail(PRHF_EINVAL, "more than 2^31 - 1 scan rays: search in batches");
     if (mode != PRHF_MODE_O && mode != PRHF_MODE_X) return fail(PRHF_EINVAL, "Mode must be O or X");
     if (alt_stride_elems != 0 && alt_stride_elems != n_alt) return fail(PRHF_EINVAL, "alt stride is 0 or n_alt");
     if (flags & ~PRHF_FLAG_DEVICE_PTRS) return fail(PRHF_EINVAL, "unknown flag bits");
     const bool dev = (flags & PRHF_FLAG_DEVICE_PTRS) != 0;
     if (!dev) {
-        for (int64_t i = 0; i + 1 < n_scan; ++i)
-            if (!(scan_elevation_deg[i + 1] > scan_elevation_deg[i]))
-                return fail(PRHF_EINVAL, "scan_elevation_deg must be strictly increasing");
-        if (n_scan == 1 && !std::isfinite(scan_elevation_deg[0])) return fail(PRHF_EINVAL, "scan_elevation_deg must be finite");
-        if (group_profile_index)
-            for (int64_t g = 0; g < n_groups; ++g)
-                if (group_profile_index[g] < 0 || group_profile_index[g] >= n_prof)
-                    return fail(PRHF_EINVAL, "profile_index[%lld] outside [0, n_prof)", (long long)g);
+        PRHF_TRY(check_scan_grid(scan_elevation_deg, n_scan, true));
+        if (group_profile_index) PRHF_TRY(check_index("profile_index", group_profile_index, n_groups, "n_prof", n_prof));
     }
     if (n_groups == 0) return PRHF_OK;
     ENTER_DEVICE(c->device);
@@ -2140,21 +2169,12 @@ int skip_run(prhf_ctx* c, int32_t geometry, const double* group_freq_hz, const i
     std::memset(&m, 0, sizeof m);
     prhf::SkipArgs& h = m.k;
     prhf::SnellArgs& a = h.s;
-    a.n_rays = 1; a.n_alt = n_alt; a.prof_stride = n_alt; a.alt_stride = alt_stride_elems;
-    a.mode = mode == PRHF_MODE_O ? PRHF_KMODE_O : PRHF_KMODE_X;
-    a.geometry = geometry;
-    a.earth_radius_km = geometry == 0 ? 6371.0 : earth_radius_km;
-    a.dz_target_km = geometry == 0 ? 1.0 : dz_target_km;
-    a.apex_boost = geometry == 0 ? 200.0 : apex_boost;
-    a.max_substeps = geometry == 0 ? 400 : max_substeps;
-    a.status = c->h_status_dev;
-    a.n_groups = n_groups; a.n_prof = n_prof; a.resident_cus = c->cu_count;
-    h.n_scan = (int)n_scan; h.elev_tol = elev_tol_deg; h.max_iter = max_iter;
-    m.n_links = n_groups; m.f_lo = f_lo_hz; m.f_hi = f_hi_hz; m.n_bisect = n_bisect;
-    const size_t prof_elems = (size_t)n_prof * (size_t)n_alt;
-    const size_t alt_elems = alt_stride_elems ? prof_elems : (size_t)n_alt;
-    const size_t width = muf ? PRHF_MUF_OUTPUTS : PRHF_SKIP_OUTPUTS;
-    const size_t out_elems = (size_t)n_groups * width;
+    snell_args(c, a, geo, 1, p);
+    a.n_groups = n_groups;
+    h.n_scan = (int)n_scan; h.elev_tol = s.elev_tol_deg; h.max_iter = s.max_iter;
+    m.n_links = n_groups; m.f_lo = s.f_lo_hz; m.f_hi = s.f_hi_hz; m.n_bisect = s.n_bisect;
+    const size_t G = (size_t)n_groups, E = (size_t)n_scan;
+    const size_t out_elems = G * (muf ? PRHF_MUF_OUTPUTS : PRHF_SKIP_OUTPUTS);
     double* d_result = out;
     if (dev) {
         a.den = den; a.bmag = bmag; a.bpsi = bpsi; a.alt = alt;
@@ -2162,79 +2182,37 @@ int skip_run(prhf_ctx* c, int32_t geometry, const double* group_freq_hz, const i
         a.group_prof = reinterpret_cast<const long long*>(group_profile_index);
         m.link_range = link_range_km; h.scan_elev = scan_elevation_deg;
     } else {
-        const size_t elems = 3 * prof_elems + alt_elems + 3 * (size_t)n_groups + (size_t)n_scan + out_elems;
-        int rc = ensure(c, c->arena, elems * 8);
-        if (rc != PRHF_OK) return rc;
-        double* p = static_cast<double*>(c->arena.p);
-        double* d_den = p; p += prof_elems;
-        double* d_bmag = p; p += prof_elems;
-        double* d_bpsi = p; p += prof_elems;
-        double* d_alt = p; p += alt_elems;
-        double* d_f = p; p += n_groups;
-        long long* d_i = reinterpret_cast<long long*>(p); p += n_groups;
-        double* d_lr = p; p += n_groups;
-        double* d_e = p; p += n_scan;
-        d_result = p;
-        HIP_TRY(hipMemcpyAsync(d_den, den, prof_elems * 8, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(d_bmag, bmag, prof_elems * 8, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(d_bpsi, bpsi, prof_elems * 8, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(d_alt, alt, alt_elems * 8, hipMemcpyHostToDevice, c->stream));
-        if (!muf) HIP_TRY(hipMemcpyAsync(d_f, group_freq_hz, (size_t)n_groups * 8, hipMemcpyHostToDevice, c->stream));
-        if (group_profile_index)
-            HIP_TRY(hipMemcpyAsync(d_i, group_profile_index, (size_t)n_groups * 8, hipMemcpyHostToDevice, c->stream));
-        if (muf) HIP_TRY(hipMemcpyAsync(d_lr, link_range_km, (size_t)n_groups * 8, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(d_e, scan_elevation_deg, (size_t)n_scan * 8, hipMemcpyHostToDevice, c->stream));
-        a.den = d_den; a.bmag = d_bmag; a.bpsi = d_bpsi; a.alt = d_alt;
-        a.group_freq = d_f; a.group_prof = group_profile_index ? d_i : nullptr;
-        m.link_range = d_lr; h.scan_elev = d_e;
+        PRHF_TRY(carve(c, c->arena, [&](Stager& k) {
+            put_columns(k, a, p);
+            a.group_freq = k.put<double>(group_freq_hz, G);              // (null for the MUF: the device's own, below)
+            a.group_prof = k.put<long long>(group_profile_index, G);
+            m.link_range = k.put<double>(link_range_km, G);
+            h.scan_elev = k.put<double>(scan_elevation_deg, E);
+            d_result = k.take<double>(out_elems);
+        }));
     }
-    {
-        int rc = ensure(c, c->levels, level_bytes);
-        if (rc != PRHF_OK) return rc;
-        a.levels = static_cast<double*>(c->levels.p);
-        a.group_entries = a.levels + mup_cells;
-        a.group_info = reinterpret_cast<int*>(a.group_entries + 4 * level_cells);
-        a.group_kidx = a.group_info + 4 * (size_t)n_groups;
-    }
-    {
-        // per-profile scalars; behind them the scan's ground ranges and - MUF - the links' frequencies, brackets, skip rows
-        // of the trip and of the bracket's lower end, and "still searching" words
-        const size_t info_bytes = (((size_t)n_prof * 32 + 127) / 128) * 128;
-        const size_t scan_bytes = (size_t)n_groups * (size_t)n_scan * 8;
-        const size_t link_doubles = muf ? (size_t)n_groups * (1 + 4 + 2 * PRHF_SKIP_OUTPUTS) : 0;
-        const size_t flag_bytes = muf ? (size_t)n_groups * 4 : 0;
-        int rc = ensure(c, c->partial, info_bytes + scan_bytes + link_doubles * 8 + flag_bytes);
-        if (rc != PRHF_OK) return rc;
-        char* q = static_cast<char*>(c->partial.p);
-        a.prof_info = reinterpret_cast<double*>(q);
-        h.scan_d = reinterpret_cast<double*>(q + info_bytes);
-        if (muf) {
-            double* p = h.scan_d + (size_t)n_groups * (size_t)n_scan;
-            m.group_freq = p; p += n_groups;
-            m.state = p; p += 4 * (size_t)n_groups;
-            m.best = p; p += (size_t)n_groups * PRHF_SKIP_OUTPUTS;
-            h.out = p; p += (size_t)n_groups * PRHF_SKIP_OUTPUTS;
-            m.active = reinterpret_cast<int*>(p);
-            a.group_freq = m.group_freq;
-            h.active = m.active;
-            m.out = d_result;
-        } else {
-            h.out = d_result;
-        }
-    }
-    a.ptab = nullptr;
-    if (c->knobs.snell_table > 0 && (double)n_groups >= c->knobs.snell_table * (double)n_prof && prof_elems * 32 <= ((size_t)1 << 30)) {
-        int rc = ensure(c, c->ptab, prof_elems * 32);
-        if (rc != PRHF_OK) return rc;
-        a.ptab = static_cast<double*>(c->ptab.p);
-    }
-    HIP_TRY(hipEventRecord(c->begin_ev(), c->stream));
-    if (muf) HIP_TRY(prhf::launch_snell_muf(m, c->stream));
-    else HIP_TRY(prhf::launch_snell_skip(h, c->stream));
-    HIP_TRY(hipEventRecord(c->pending_end_ev(), c->stream));
-    c->mark_timed();
-    c->status_pending = true;
-    if (!dev) HIP_TRY(hipMemcpyAsync(out, d_result, out_elems * 8, hipMemcpyDeviceToHost, c->stream));
+    PRHF_TRY(level_tables(c, a, n_groups, n_alt));
+    // per-profile scalars; behind them the scan's ground ranges and - MUF - the links' frequencies, brackets, skip rows
+    // of the trip and of the bracket's lower end, and "still searching" words
+    PRHF_TRY(carve(c, c->partial, [&](Stager& k) {
+        carve_prof_info(k, a, n_prof);
+        h.scan_d = k.take<double>(G * E);
+        h.out = d_result;
+        if (!muf) return;
+        m.group_freq = k.take<double>(G);
+        m.state = k.take<double>(4 * G);
+        m.best = k.take<double>(G * PRHF_SKIP_OUTPUTS);
+        h.out = k.take<double>(G * PRHF_SKIP_OUTPUTS);
+        m.active = k.take<int>(G);
+        a.group_freq = m.group_freq;
+        h.active = m.active;
+        m.out = d_result;
+    }));
+    PRHF_TRY(profile_table(c, a, n_groups, n_prof, n_alt));
+    PRHF_TRY(timed_launch(c, true, [&] {
+        return muf ? prhf::launch_snell_muf(m, c->stream) : prhf::launch_snell_skip(h, c->stream);
+    }));
+    if (!dev) HIP_TRY(download(c, out, d_result, out_elems * 8));
     return prhf_sync(c);
 }
 }  // namespace
@@ -2246,9 +2224,9 @@ int prhf_snell_skip_f64(prhf_ctx* c, int32_t geometry, const double* group_freq_
                         double apex_boost, int32_t max_substeps, double elev_tol_deg, int32_t max_iter, double* out,
                         uint32_t flags) {
     if (c && n_groups < 1) return fail(PRHF_EINVAL, "the search needs at least one group");
-    return skip_run(c, geometry, group_freq_hz, group_profile_index, n_groups, nullptr, 0.0, 0.0, 0, scan_elevation_deg, n_scan,
-                    den, bmag, bpsi, alt, n_prof, n_alt, alt_stride_elems, mode, earth_radius_km, dz_target_km, apex_boost,
-                    max_substeps, elev_tol_deg, max_iter, out, flags);
+    const SkipControls s{geometry, earth_radius_km, dz_target_km, apex_boost, max_substeps, elev_tol_deg, max_iter, 0.0, 0.0, 0};
+    return skip_run(c, s, SnellColumns{den, bmag, bpsi, alt, n_prof, n_alt, alt_stride_elems, mode}, group_freq_hz,
+                    group_profile_index, n_groups, nullptr, scan_elevation_deg, n_scan, out, flags);
 }
 
 int prhf_snell_muf_f64(prhf_ctx* c, int32_t geometry, const int64_t* link_profile_index, const double* link_range_km,
@@ -2259,9 +2237,10 @@ int prhf_snell_muf_f64(prhf_ctx* c, int32_t geometry, const int64_t* link_profil
                        double* out, uint32_t flags) {
     if (c && !link_range_km) return fail(PRHF_EINVAL, "null array pointer");
     if (c && n_links < 1) return fail(PRHF_EINVAL, "the search needs at least one link");
-    return skip_run(c, geometry, nullptr, link_profile_index, n_links, link_range_km, f_lo_hz, f_hi_hz, n_bisect,
-                    scan_elevation_deg, n_scan, den, bmag, bpsi, alt, n_prof, n_alt, alt_stride_elems, mode, earth_radius_km,
-                    dz_target_km, apex_boost, max_substeps, elev_tol_deg, max_iter, out, flags);
+    const SkipControls s{geometry, earth_radius_km, dz_target_km, apex_boost, max_substeps, elev_tol_deg, max_iter, f_lo_hz, f_hi_hz,
+                         n_bisect};
+    return skip_run(c, s, SnellColumns{den, bmag, bpsi, alt, n_prof, n_alt, alt_stride_elems, mode}, nullptr, link_profile_index,
+                    n_links, link_range_km, scan_elevation_deg, n_scan, out, flags);
 }
 
 namespace {
@@ -2378,82 +2357,127 @@ int prhf_field_sample_f64(prhf_ctx* c, const double* records, int64_t n_fields, 
 }
 
 namespace {
-// Both gradient tracers.  Spherical (geometry PRHF_GEO_SPHERICAL): the axes are r and phi, z_ground_km .. x_max_km carry
-// R_E + z_ground_km, r_max_km, phi_min, phi_max and the paths are t, r, phi, v_r, v_phi.  n_hops > 0: the multi-hop call
-// (prhf_trace_gradient_hops_f64) - out is (n_rays, n_hops, 15), the paths hold n_rays n_hops rows and hop_z0_km is
-// z_ground_km as the caller gave it.
-int grad_trace_run(prhf_ctx* c, int n_hops, double hop_z0_km, int geometry, double earth_radius_km, const double* records, int64_t n_fields, int64_t nz,
-                   int64_t nx, const double* z_axis, const double* x_axis, const double* x0_km, const double* z0_km,
-                   const double* elevation_deg, const int64_t* ray_field, int64_t n_rays, double s_max_km, double rtol,
-                   double atol, double max_step_km, double z_ground_km, double z_max_km, double x_min_km, double x_max_km,
-                   int32_t renormalize_every, double fill_n, double fill_grad, double fill_mup, double* out, double* path_t,
-                   double* path_x, double* path_z, double* path_vx, double* path_vz, int64_t path_stride, uint32_t flags) {
-    if (!c) return fail(PRHF_EINVAL, "null context");
-    if (!records || !x0_km || !z0_km || !elevation_deg || !out) return fail(PRHF_EINVAL, "null array pointer");
-    if (n_rays < 0) return fail(PRHF_EINVAL, "bad shape");
+// ---- The gradient family: prhf_trace_gradient_f64 .. prhf_gradient_hop_muf_f64, and prhf_field_build_f64 ----
+
+// The field grid of a call: records (n_fields, n0, n1, 4) on the device, the axes in host memory
+struct FieldGrid {
+    const double* records;
+    int64_t n_fields, n0, n1;
+    const double *axis0, *axis1;
+};
+// The tracer's controls as the exported calls take them (z_ground_km above the ground in both geometries; top, left,
+// right: z_max_km, x_min_km, x_max_km, or r_max_km, phi_min, phi_max)
+struct GradControls {
+    int32_t geometry;
+    double earth_radius_km, s_max_km, rtol, atol, max_step_km, z_ground_km, top, left, right;
+    int32_t renormalize_every;
+    double fill_n, fill_grad, fill_mup;
+    bool spherical() const { return geometry == PRHF_GEO_SPHERICAL; }
+};
+
+// The checks of the tracer's controls, in three parts: prhf_trace_gradient*_f64 make other checks between them
+int check_grad_geometry(const GradControls& t) {
+    if (t.geometry != PRHF_GEO_CARTESIAN && t.geometry != PRHF_GEO_SPHERICAL)
+        return fail(PRHF_EINVAL, "geometry is 0 (Cartesian) or 1 (spherical)");
+    if (t.spherical() && (!(t.earth_radius_km > 0) || !std::isfinite(t.earth_radius_km)))
+        return fail(PRHF_EINVAL, "earth_radius_km must be positive and finite");
+    return PRHF_OK;
+}
+int check_grad_flags(uint32_t flags) {
     if (flags & ~PRHF_FLAG_DEVICE_PTRS) return fail(PRHF_EINVAL, "unknown flag bits");
-    const int n_paths = (path_t != nullptr) + (path_x != nullptr) + (path_z != nullptr) + (path_vx != nullptr) + (path_vz != nullptr);
+    return PRHF_OK;
+}
+int check_grad_steps(const GradControls& t) {
+    if (!(t.s_max_km > 0) || !std::isfinite(t.s_max_km)) return fail(PRHF_EINVAL, "s_max_km must be positive and finite");
+    if (!(t.max_step_km > 0)) return fail(PRHF_EINVAL, "`max_step` must be positive.");
+    if (!(t.rtol >= 0) || !(t.atol >= 0)) return fail(PRHF_EINVAL, "`atol` must be positive.");
+    if (t.renormalize_every < 0) return fail(PRHF_EINVAL, "renormalize_every must not be negative");
+    return PRHF_OK;
+}
+int check_grad_controls(const GradControls& t, uint32_t flags) {
+    PRHF_TRY(check_grad_geometry(t));
+    PRHF_TRY(check_grad_flags(flags));
+    return check_grad_steps(t);
+}
+// ... and of a skip or MUF search on top of them
+int check_grad_search(int64_t n_scan, double elev_tol_deg, int32_t max_iter) {
+    if (n_scan < 1 || n_scan > 0x7fffffffLL) return fail(PRHF_EINVAL, "the scan grid needs at least 1 elevation");
+    if (max_iter < 1 || max_iter > 128) return fail(PRHF_EINVAL, "max_iter is 1 .. 128");
+    if (!(elev_tol_deg >= 0.0) || !std::isfinite(elev_tol_deg))
+        return fail(PRHF_EINVAL, "elev_tol_deg must be finite and not negative");
+    return PRHF_OK;
+}
+
+// Both axes of a field (host memory in every flag combination) at the head of the arena
+template <class Args>
+void put_axes(Stager& k, Args& a, const double* axis0, const double* axis1, int64_t n0, int64_t n1) {
+    a.a0 = k.put<double>(axis0, (size_t)n0);
+    a.a1 = k.put<double>(axis1, (size_t)n1);
+}
+
+// The tracer's arguments from the call's grid and controls; the axes, n_hops, hop_z0 and the per-ray arrays are the caller's
+void grad_trace_args(prhf_ctx* c, prhf::GradTraceArgs& a, const FieldGrid& f, const GradControls& t) {
+    a.rec = f.records; a.n0 = (int)f.n0; a.n1 = (int)f.n1; a.n_fields = f.n_fields;
+    a.s_max = t.s_max_km;
+    a.rtol = t.rtol < 100 * 2.220446049250313e-16 ? 100 * 2.220446049250313e-16 : t.rtol;     // (solve_ivp raises a too small rtol so)
+    a.atol = t.atol; a.max_step = t.max_step_km;
+    // (the reference's spherical tracer binds R_E + z_ground_km to the ground event before it subtracts, :2240)
+    a.z_ground = t.spherical() ? t.earth_radius_km + t.z_ground_km : t.z_ground_km;
+    a.z_max = t.top; a.x_min = t.left; a.x_max = t.right; a.renormalize_every = t.renormalize_every;
+    a.fill_n = t.fill_n; a.fill_grad = t.fill_grad; a.fill_mup = t.fill_mup; a.status = c->h_status_dev;
+    a.geometry = t.geometry; a.earth_radius = t.spherical() ? t.earth_radius_km : 0.0;
+}
+
+// Both gradient tracers.  Spherical: the axes are r and phi, top .. right carry r_max_km, phi_min, phi_max and the paths
+// are t, r, phi, v_r, v_phi.  n_hops > 0: the multi-hop call (prhf_trace_gradient_hops_f64) - out is (n_rays, n_hops, 15)
+// and the paths hold n_rays n_hops rows.
+int grad_trace_run(prhf_ctx* c, int n_hops, const GradControls& t, const FieldGrid& f, const double* x0_km, const double* z0_km,
+                   const double* elevation_deg, const int64_t* ray_field, int64_t n_rays, double* out, double* const paths[5],
+                   int64_t path_stride, uint32_t flags) {
+    if (!c) return fail(PRHF_EINVAL, "null context");
+    if (!f.records || !x0_km || !z0_km || !elevation_deg || !out) return fail(PRHF_EINVAL, "null array pointer");
+    if (n_rays < 0) return fail(PRHF_EINVAL, "bad shape");
+    PRHF_TRY(check_grad_flags(flags));
+    int n_paths = 0;
+    for (int k = 0; k < 5; ++k) n_paths += paths[k] != nullptr;
     if (n_paths != 0 && n_paths != 5) return fail(PRHF_EINVAL, "the five path arrays go together");
     if (n_paths && path_stride < 1) return fail(PRHF_EINVAL, "path_stride must hold at least the launch point");
-    if (!(s_max_km > 0) || !std::isfinite(s_max_km)) return fail(PRHF_EINVAL, "s_max_km must be positive and finite");
-    if (!(max_step_km > 0)) return fail(PRHF_EINVAL, "`max_step` must be positive.");
-    if (!(rtol >= 0) || !(atol >= 0)) return fail(PRHF_EINVAL, "`atol` must be positive.");
-    if (renormalize_every < 0) return fail(PRHF_EINVAL, "renormalize_every must not be negative");
+    PRHF_TRY(check_grad_steps(t));
     int u0 = 0, u1 = 0;
-    int rc = check_field_shape(z_axis, x_axis, n_fields, nz, nx, 2, &u0, &u1);
-    if (rc != PRHF_OK) return rc;
+    PRHF_TRY(check_field_shape(f.axis0, f.axis1, f.n_fields, f.n0, f.n1, 2, &u0, &u1));
     const bool dev = (flags & PRHF_FLAG_DEVICE_PTRS) != 0;
-    if (!dev && ray_field)
-        for (int64_t r = 0; r < n_rays; ++r)
-            if (ray_field[r] < 0 || ray_field[r] >= n_fields)
-                return fail(PRHF_EINVAL, "ray_field[%lld] outside [0, n_fields)", (long long)r);
+    if (!dev && ray_field) PRHF_TRY(check_index("ray_field", ray_field, n_rays, "n_fields", f.n_fields));
     if (n_rays == 0) return PRHF_OK;
     ENTER_DEVICE(c->device);
     const size_t R = (size_t)n_rays, path_elems = n_paths ? R * (size_t)(n_hops ? n_hops : 1) * (size_t)path_stride : 0;
     const size_t out_elems = R * (n_hops ? (size_t)n_hops * PRHF_GRAD_HOP_OUTPUTS : (size_t)PRHF_GRAD_OUTPUTS);
-    rc = ensure(c, c->arena, ((size_t)(nz + nx) + (dev ? 0 : 4 * R + out_elems + 5 * path_elems)) * 8);
-    if (rc != PRHF_OK) return rc;
-    double* p = static_cast<double*>(c->arena.p);
     prhf::GradTraceArgs a;
     std::memset(&a, 0, sizeof a);
-    HIP_TRY(hipMemcpyAsync(p, z_axis, (size_t)nz * 8, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(p + nz, x_axis, (size_t)nx * 8, hipMemcpyHostToDevice, c->stream));
-    a.rec = records; a.a0 = p; a.a1 = p + nz; a.n0 = (int)nz; a.n1 = (int)nx; a.n_fields = n_fields; a.n_rays = n_rays;
-    a.path_stride = n_paths ? path_stride : 0;
-    a.s_max = s_max_km;
-    a.rtol = rtol < 100 * 2.220446049250313e-16 ? 100 * 2.220446049250313e-16 : rtol;     // (solve_ivp raises a too small rtol so)
-    a.atol = atol; a.max_step = max_step_km; a.z_ground = z_ground_km; a.z_max = z_max_km;
-    a.x_min = x_min_km; a.x_max = x_max_km; a.renormalize_every = renormalize_every;
-    a.fill_n = fill_n; a.fill_grad = fill_grad; a.fill_mup = fill_mup; a.status = c->h_status_dev;
-    a.geometry = geometry; a.earth_radius = earth_radius_km; a.n_hops = n_hops; a.hop_z0 = hop_z0_km;
-    double* host_paths[5] = {path_t, path_x, path_z, path_vx, path_vz};
-    double* d_paths[5] = {path_t, path_x, path_z, path_vx, path_vz};
-    if (dev) {
-        a.x0 = x0_km; a.z0 = z0_km; a.elev = elevation_deg; a.ray_field = reinterpret_cast<const long long*>(ray_field);
-        a.out = out;
-    } else {
-        double* q = p + nz + nx;
-        HIP_TRY(hipMemcpyAsync(q, x0_km, R * 8, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(q + R, z0_km, R * 8, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(q + 2 * R, elevation_deg, R * 8, hipMemcpyHostToDevice, c->stream));
-        if (ray_field) HIP_TRY(hipMemcpyAsync(q + 3 * R, ray_field, R * 8, hipMemcpyHostToDevice, c->stream));
-        a.x0 = q; a.z0 = q + R; a.elev = q + 2 * R;
-        a.ray_field = ray_field ? reinterpret_cast<const long long*>(q + 3 * R) : nullptr;
-        a.out = q + 4 * R;
-        for (int k = 0; k < 5; ++k) d_paths[k] = n_paths ? a.out + out_elems + k * path_elems : nullptr;
-    }
+    grad_trace_args(c, a, f, t);
+    a.n_rays = n_rays; a.path_stride = n_paths ? path_stride : 0;
+    a.n_hops = n_hops; a.hop_z0 = n_hops ? t.z_ground_km : 0.0;
+    a.x0 = x0_km; a.z0 = z0_km; a.elev = elevation_deg; a.ray_field = reinterpret_cast<const long long*>(ray_field);
+    a.out = out;
+    double* d_paths[5] = {paths[0], paths[1], paths[2], paths[3], paths[4]};
+    PRHF_TRY(carve(c, c->arena, [&](Stager& k) {
+        put_axes(k, a, f.axis0, f.axis1, f.n0, f.n1);
+        if (dev) return;
+        a.x0 = k.put<double>(x0_km, R);
+        a.z0 = k.put<double>(z0_km, R);
+        a.elev = k.put<double>(elevation_deg, R);
+        a.ray_field = k.put<long long>(ray_field, R);
+        a.out = k.take<double>(out_elems);
+        for (int i = 0; i < 5; ++i) d_paths[i] = n_paths ? k.take<double>(path_elems) : nullptr;
+    }));
     // nodes a ray does not reach stay NaN (all bits set)
-    for (int k = 0; k < 5 && n_paths; ++k) HIP_TRY(hipMemsetAsync(d_paths[k], 0xff, path_elems * 8, c->stream));
+    for (int i = 0; i < 5 && n_paths; ++i) HIP_TRY(hipMemsetAsync(d_paths[i], 0xff, path_elems * 8, c->stream));
     a.path_t = d_paths[0]; a.path_x = d_paths[1]; a.path_z = d_paths[2]; a.path_vx = d_paths[3]; a.path_vz = d_paths[4];
-    HIP_TRY(hipEventRecord(c->begin_ev(), c->stream));
-    HIP_TRY(n_hops ? prhf::launch_grad_hop_trace(a, c->stream) : prhf::launch_grad_trace(a, c->stream));
-    HIP_TRY(hipEventRecord(c->pending_end_ev(), c->stream));
-    c->mark_timed();
-    c->status_pending = true;
+    PRHF_TRY(timed_launch(c, true, [&] {
+        return n_hops ? prhf::launch_grad_hop_trace(a, c->stream) : prhf::launch_grad_trace(a, c->stream);
+    }));
     if (!dev) {
-        HIP_TRY(hipMemcpyAsync(out, a.out, out_elems * 8, hipMemcpyDeviceToHost, c->stream));
-        for (int k = 0; k < 5 && n_paths; ++k)
-            HIP_TRY(hipMemcpyAsync(host_paths[k], d_paths[k], path_elems * 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(download(c, out, a.out, out_elems * 8));
+        for (int i = 0; i < 5 && n_paths; ++i) HIP_TRY(download(c, paths[i], d_paths[i], path_elems * 8));
     }
     return prhf_sync(c);
 }
@@ -2466,10 +2490,11 @@ int prhf_trace_gradient_f64(prhf_ctx* c, const double* records, int64_t n_fields
                             double x_min_km, double x_max_km, int32_t renormalize_every, double fill_n, double fill_grad,
                             double fill_mup, double* out, double* path_t, double* path_x, double* path_z, double* path_vx,
                             double* path_vz, int64_t path_stride, uint32_t flags) {
-    return grad_trace_run(c, 0, 0.0, PRHF_GEO_CARTESIAN, 0.0, records, n_fields, nz, nx, z_axis, x_axis, x0_km, z0_km, elevation_deg,
-                          ray_field, n_rays, s_max_km, rtol, atol, max_step_km, z_ground_km, z_max_km, x_min_km, x_max_km,
-                          renormalize_every, fill_n, fill_grad, fill_mup, out, path_t, path_x, path_z, path_vx, path_vz,
-                          path_stride, flags);
+    const GradControls t{PRHF_GEO_CARTESIAN, 0.0, s_max_km, rtol, atol, max_step_km, z_ground_km, z_max_km, x_min_km, x_max_km,
+                         renormalize_every, fill_n, fill_grad, fill_mup};
+    const FieldGrid f{records, n_fields, nz, nx, z_axis, x_axis};
+    double* const paths[5] = {path_t, path_x, path_z, path_vx, path_vz};
+    return grad_trace_run(c, 0, t, f, x0_km, z0_km, elevation_deg, ray_field, n_rays, out, paths, path_stride, flags);
 }
 
 int prhf_trace_gradient_spherical_f64(prhf_ctx* c, const double* records, int64_t n_fields, int64_t nr, int64_t nphi,
@@ -2481,13 +2506,12 @@ int prhf_trace_gradient_spherical_f64(prhf_ctx* c, const double* records, int64_
                                       double fill_mup, double* out, double* path_t, double* path_r, double* path_phi,
                                       double* path_v_r, double* path_v_phi, int64_t path_stride, uint32_t flags) {
     if (!c) return fail(PRHF_EINVAL, "null context");
-    if (!(earth_radius_km > 0) || !std::isfinite(earth_radius_km))
-        return fail(PRHF_EINVAL, "earth_radius_km must be positive and finite");
-    // (the reference binds R_E + z_ground_km to the ground event before it subtracts, :2240)
-    return grad_trace_run(c, 0, 0.0, PRHF_GEO_SPHERICAL, earth_radius_km, records, n_fields, nr, nphi, r_axis, phi_axis, x0_km, z0_km,
-                          elevation_deg, ray_field, n_rays, s_max_km, rtol, atol, max_step_km, earth_radius_km + z_ground_km,
-                          r_max_km, phi_min, phi_max, renormalize_every, fill_n, fill_grad, fill_mup, out, path_t, path_r,
-                          path_phi, path_v_r, path_v_phi, path_stride, flags);
+    const GradControls t{PRHF_GEO_SPHERICAL, earth_radius_km, s_max_km, rtol, atol, max_step_km, z_ground_km, r_max_km, phi_min,
+                         phi_max, renormalize_every, fill_n, fill_grad, fill_mup};
+    PRHF_TRY(check_grad_geometry(t));
+    const FieldGrid f{records, n_fields, nr, nphi, r_axis, phi_axis};
+    double* const paths[5] = {path_t, path_r, path_phi, path_v_r, path_v_phi};
+    return grad_trace_run(c, 0, t, f, x0_km, z0_km, elevation_deg, ray_field, n_rays, out, paths, path_stride, flags);
 }
 
 int prhf_trace_gradient_hops_f64(prhf_ctx* c, int32_t geometry, const double* records, int64_t n_fields, int64_t n0,
@@ -2500,42 +2524,41 @@ int prhf_trace_gradient_hops_f64(prhf_ctx* c, int32_t geometry, const double* re
                                  int64_t path_stride, uint32_t flags) {
     if (!c) return fail(PRHF_EINVAL, "null context");
     if (n_hops < 1 || n_hops > PRHF_GRAD_MAX_HOPS) return fail(PRHF_EINVAL, "n_hops is 1 .. 16");
-    if (geometry != PRHF_GEO_CARTESIAN && geometry != PRHF_GEO_SPHERICAL)
-        return fail(PRHF_EINVAL, "geometry is 0 (Cartesian) or 1 (spherical)");
-    const bool sph = geometry == PRHF_GEO_SPHERICAL;
-    if (sph && (!(earth_radius_km > 0) || !std::isfinite(earth_radius_km)))
-        return fail(PRHF_EINVAL, "earth_radius_km must be positive and finite");
+    const GradControls t{geometry, earth_radius_km, s_max_km, rtol, atol, max_step_km, z_ground_km, top, left, right,
+                         renormalize_every, fill_n, fill_grad, fill_mup};
+    PRHF_TRY(check_grad_geometry(t));
     if (n_rays > 0x7fffffffLL / PRHF_GRAD_MAX_HOPS) return fail(PRHF_EINVAL, "more than 2^27 - 1 rays: trace in batches");
-    // (the spherical tracer binds R_E + z_ground_km to the ground event, prhf_trace_gradient_spherical_f64)
-    return grad_trace_run(c, n_hops, z_ground_km, geometry, sph ? earth_radius_km : 0.0, records, n_fields, n0, n1, axis0, axis1,
-                          x0_km, z0_km, elevation_deg, ray_field, n_rays, s_max_km, rtol, atol, max_step_km,
-                          sph ? earth_radius_km + z_ground_km : z_ground_km, top, left, right, renormalize_every, fill_n,
-                          fill_grad, fill_mup, out, path_t, path_a, path_b, path_va, path_vb, path_stride, flags);
+    const FieldGrid f{records, n_fields, n0, n1, axis0, axis1};
+    double* const paths[5] = {path_t, path_a, path_b, path_va, path_vb};
+    return grad_trace_run(c, n_hops, t, f, x0_km, z0_km, elevation_deg, ray_field, n_rays, out, paths, path_stride, flags);
 }
 
 namespace {
+// The groups of a homing or skip call: the field and the launch point of each
+struct GradGroups {
+    const int64_t* field;
+    const double *x0_km, *z0_km;
+    int64_t n;
+};
+// ... behind the axes in the arena, for GradHomeArgs and GradSkipArgs alike
+template <class Args>
+void put_groups(Stager& k, Args& h, const GradGroups& g) {
+    h.group_field = k.put<long long>(g.field, (size_t)g.n);
+    h.group_x0 = k.put<double>(g.x0_km, (size_t)g.n);
+    h.group_z0 = k.put<double>(g.z0_km, (size_t)g.n);
+}
+
 // Both homing calls.  n_hops 0: prhf_gradient_home_f64 (rows of 15); else prhf_gradient_hop_home_f64.
-int grad_home_run(prhf_ctx* c, int32_t n_hops, int32_t geometry, const double* records, int64_t n_fields, int64_t n0, int64_t n1,
-                  const double* axis0, const double* axis1, const int64_t* group_field, const double* group_x0_km,
-                  const double* group_z0_km, int64_t n_groups, const int64_t* link_group,
-                  const double* link_target_km, int64_t n_links, const double* scan_elevation_deg, int64_t n_scan,
-                  double earth_radius_km, double s_max_km, double rtol, double atol, double max_step_km,
-                  double z_ground_km, double top, double left, double right, int32_t renormalize_every,
-                  double fill_n, double fill_grad, double fill_mup, double range_tol_km, int32_t max_iter,
-                  int32_t max_roots, double* out, int64_t* n_brackets, uint32_t flags) {
+int grad_home_run(prhf_ctx* c, int32_t n_hops, const GradControls& t, const FieldGrid& f, const GradGroups& g,
+                  const int64_t* link_group, const double* link_target_km, int64_t n_links, const double* scan_elevation_deg,
+                  int64_t n_scan, double range_tol_km, int32_t max_iter, int32_t max_roots, double* out, int64_t* n_brackets,
+                  uint32_t flags) {
     const int row_width = n_hops ? 3 + PRHF_GRAD_HOP_OUTPUTS * n_hops : PRHF_GRAD_HOME_OUTPUTS;
-    if (!records || !group_field || !group_x0_km || !group_z0_km || !link_group || !link_target_km || !scan_elevation_deg ||
-        !out || !n_brackets)
+    const int64_t n_groups = g.n;
+    if (!f.records || !g.field || !g.x0_km || !g.z0_km || !link_group || !link_target_km || !scan_elevation_deg || !out ||
+        !n_brackets)
         return fail(PRHF_EINVAL, "null array pointer");
-    if (geometry != PRHF_GEO_CARTESIAN && geometry != PRHF_GEO_SPHERICAL)
-        return fail(PRHF_EINVAL, "geometry is 0 (Cartesian) or 1 (spherical)");
-    if (geometry == PRHF_GEO_SPHERICAL && (!(earth_radius_km > 0) || !std::isfinite(earth_radius_km)))
-        return fail(PRHF_EINVAL, "earth_radius_km must be positive and finite");
-    if (flags & ~PRHF_FLAG_DEVICE_PTRS) return fail(PRHF_EINVAL, "unknown flag bits");
-    if (!(s_max_km > 0) || !std::isfinite(s_max_km)) return fail(PRHF_EINVAL, "s_max_km must be positive and finite");
-    if (!(max_step_km > 0)) return fail(PRHF_EINVAL, "`max_step` must be positive.");
-    if (!(rtol >= 0) || !(atol >= 0)) return fail(PRHF_EINVAL, "`atol` must be positive.");
-    if (renormalize_every < 0) return fail(PRHF_EINVAL, "renormalize_every must not be negative");
+    PRHF_TRY(check_grad_controls(t, flags));
     if (n_scan < 2) return fail(PRHF_EINVAL, "the scan grid needs at least 2 elevations");
     if (max_iter < 1 || max_iter > 128) return fail(PRHF_EINVAL, "max_iter is 1 .. 128");
     if (max_roots < 1 || max_roots > 64) return fail(PRHF_EINVAL, "max_roots is 1 .. 64");
@@ -2546,88 +2569,50 @@ int grad_home_run(prhf_ctx* c, int32_t n_hops, int32_t geometry, const double* r
     if (n_scan > 0x7fffffffLL || n_groups * ((n_scan + 63) / 64) > 0x7fffffffLL || n_links * (int64_t)max_roots > 0x7fffffffLL)
         return fail(PRHF_EINVAL, "more than 2^31 - 1 scan rays or result rows: home in batches");
     int u0 = 0, u1 = 0;
-    int rc = check_field_shape(axis0, axis1, n_fields, n0, n1, 2, &u0, &u1);
-    if (rc != PRHF_OK) return rc;
+    PRHF_TRY(check_field_shape(f.axis0, f.axis1, f.n_fields, f.n0, f.n1, 2, &u0, &u1));
     const bool dev = (flags & PRHF_FLAG_DEVICE_PTRS) != 0;
     if (!dev) {
-        for (int64_t i = 0; i + 1 < n_scan; ++i)
-            if (!(scan_elevation_deg[i + 1] > scan_elevation_deg[i]))
-                return fail(PRHF_EINVAL, "scan_elevation_deg must be strictly increasing");
-        for (int64_t g = 0; g < n_groups; ++g)
-            if (group_field[g] < 0 || group_field[g] >= n_fields)
-                return fail(PRHF_EINVAL, "group_field[%lld] outside [0, n_fields)", (long long)g);
-        for (int64_t l = 0; l < n_links; ++l)
-            if (link_group[l] < 0 || link_group[l] >= n_groups)
-                return fail(PRHF_EINVAL, "link_group[%lld] outside [0, n_groups)", (long long)l);
+        PRHF_TRY(check_scan_grid(scan_elevation_deg, n_scan, false));
+        PRHF_TRY(check_index("group_field", g.field, n_groups, "n_fields", f.n_fields));
+        PRHF_TRY(check_index("link_group", link_group, n_links, "n_groups", n_groups));
     }
     for (uint64_t& w : c->grad_home_counters) w = 0;
     if (n_links == 0) return PRHF_OK;
     ENTER_DEVICE(c->device);
     const size_t G = (size_t)n_groups, L = (size_t)n_links, E = (size_t)n_scan;
     const size_t out_elems = L * (size_t)max_roots * (size_t)row_width;
-    rc = ensure(c, c->arena, ((size_t)(n0 + n1) + (dev ? 0 : 3 * G + 3 * L + E + out_elems)) * 8);
-    if (rc != PRHF_OK) return rc;
-    double* p = static_cast<double*>(c->arena.p);
     prhf::GradHomeArgs h;
     std::memset(&h, 0, sizeof h);
-    prhf::GradTraceArgs& a = h.g;
-    HIP_TRY(hipMemcpyAsync(p, axis0, (size_t)n0 * 8, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(p + n0, axis1, (size_t)n1 * 8, hipMemcpyHostToDevice, c->stream));
-    a.rec = records; a.a0 = p; a.a1 = p + n0; a.n0 = (int)n0; a.n1 = (int)n1; a.n_fields = n_fields;
-    a.s_max = s_max_km;
-    a.rtol = rtol < 100 * 2.220446049250313e-16 ? 100 * 2.220446049250313e-16 : rtol;     // (as the tracers: solve_ivp's floor)
-    a.atol = atol; a.max_step = max_step_km;
-    // (the spherical tracer binds R_E + z_ground_km to the ground event, prhf_trace_gradient_spherical_f64)
-    a.z_ground = geometry == PRHF_GEO_SPHERICAL ? earth_radius_km + z_ground_km : z_ground_km;
-    a.z_max = top; a.x_min = left; a.x_max = right; a.renormalize_every = renormalize_every;
-    a.fill_n = fill_n; a.fill_grad = fill_grad; a.fill_mup = fill_mup; a.status = c->h_status_dev;
-    a.geometry = geometry; a.earth_radius = geometry == PRHF_GEO_SPHERICAL ? earth_radius_km : 0.0;
+    grad_trace_args(c, h.g, f, t);
     h.n_groups = n_groups; h.n_links = n_links; h.n_scan = (int)n_scan; h.range_tol = range_tol_km; h.max_iter = max_iter;
-    h.max_roots = max_roots; h.row_width = row_width; a.n_hops = n_hops ? n_hops : 1; a.hop_z0 = z_ground_km;
-    if (dev) {
-        h.group_field = reinterpret_cast<const long long*>(group_field); h.group_x0 = group_x0_km; h.group_z0 = group_z0_km;
-        h.link_group = reinterpret_cast<const long long*>(link_group); h.link_target = link_target_km;
-        h.scan_elev = scan_elevation_deg; h.out = out; h.n_brackets = reinterpret_cast<long long*>(n_brackets);
-    } else {
-        double* q = p + n0 + n1;
-        long long* d_gf = reinterpret_cast<long long*>(q); q += G;
-        double* d_x0 = q; q += G;
-        double* d_z0 = q; q += G;
-        long long* d_lg = reinterpret_cast<long long*>(q); q += L;
-        double* d_lt = q; q += L;
-        long long* d_nb = reinterpret_cast<long long*>(q); q += L;
-        double* d_e = q; q += E;
-        HIP_TRY(hipMemcpyAsync(d_gf, group_field, G * 8, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(d_x0, group_x0_km, G * 8, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(d_z0, group_z0_km, G * 8, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(d_lg, link_group, L * 8, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(d_lt, link_target_km, L * 8, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(d_e, scan_elevation_deg, E * 8, hipMemcpyHostToDevice, c->stream));
-        h.group_field = d_gf; h.group_x0 = d_x0; h.group_z0 = d_z0; h.link_group = d_lg; h.link_target = d_lt;
-        h.scan_elev = d_e; h.n_brackets = d_nb; h.out = q;
-    }
-    {
-        // the counters, the work list and the scan's ground ranges
-        const size_t queue_bytes = 128, work_bytes = L * (size_t)max_roots * 16, scan_bytes = G * E * 8;
-        rc = ensure(c, c->partial, queue_bytes + work_bytes + scan_bytes);
-        if (rc != PRHF_OK) return rc;
-        char* q = static_cast<char*>(c->partial.p);
-        h.queue = reinterpret_cast<unsigned*>(q);
-        h.work = reinterpret_cast<int*>(q + queue_bytes);
-        h.scan_d = reinterpret_cast<double*>(q + queue_bytes + work_bytes);
-    }
-    HIP_TRY(hipEventRecord(c->begin_ev(), c->stream));
-    HIP_TRY(prhf::launch_grad_home(h, c->stream));
-    HIP_TRY(hipEventRecord(c->pending_end_ev(), c->stream));
-    c->mark_timed();
-    c->status_pending = true;
+    h.max_roots = max_roots; h.row_width = row_width; h.g.n_hops = n_hops ? n_hops : 1; h.g.hop_z0 = t.z_ground_km;
+    h.group_field = reinterpret_cast<const long long*>(g.field); h.group_x0 = g.x0_km; h.group_z0 = g.z0_km;
+    h.link_group = reinterpret_cast<const long long*>(link_group); h.link_target = link_target_km;
+    h.scan_elev = scan_elevation_deg; h.out = out; h.n_brackets = reinterpret_cast<long long*>(n_brackets);
+    PRHF_TRY(carve(c, c->arena, [&](Stager& k) {
+        put_axes(k, h.g, f.axis0, f.axis1, f.n0, f.n1);
+        if (dev) return;
+        put_groups(k, h, g);
+        h.link_group = k.put<long long>(link_group, L);
+        h.link_target = k.put<double>(link_target_km, L);
+        h.n_brackets = k.take<long long>(L);
+        h.scan_elev = k.put<double>(scan_elevation_deg, E);
+        h.out = k.take<double>(out_elems);
+    }));
+    // the counters, the work list and the scan's ground ranges
+    PRHF_TRY(carve(c, c->partial, [&](Stager& k) {
+        h.queue = k.take<unsigned>(128 / sizeof(unsigned));
+        h.work = k.take<int>(L * (size_t)max_roots * 4);
+        h.scan_d = k.take<double>(G * E);
+    }));
+    PRHF_TRY(timed_launch(c, true, [&] { return prhf::launch_grad_home(h, c->stream); }));
     unsigned counters[PRHF_GRAD_HOME_COUNTERS] = {};
-    HIP_TRY(hipMemcpyAsync(counters, h.queue, sizeof counters, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(download(c, counters, h.queue, sizeof counters));
     if (!dev) {
-        HIP_TRY(hipMemcpyAsync(out, h.out, out_elems * 8, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipMemcpyAsync(n_brackets, h.n_brackets, L * 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(download(c, out, h.out, out_elems * 8));
+        HIP_TRY(download(c, n_brackets, h.n_brackets, L * 8));
     }
-    rc = prhf_sync(c);
+    const int rc = prhf_sync(c);
     for (int k = 0; k < PRHF_GRAD_HOME_COUNTERS; ++k) c->grad_home_counters[k] = counters[k];
     return rc;
 }
@@ -2642,10 +2627,11 @@ int prhf_gradient_home_f64(prhf_ctx* c, int32_t geometry, const double* records,
                            double fill_n, double fill_grad, double fill_mup, double range_tol_km, int32_t max_iter,
                            int32_t max_roots, double* out, int64_t* n_brackets, uint32_t flags) {
     if (!c) return fail(PRHF_EINVAL, "null context");
-    return grad_home_run(c, 0, geometry, records, n_fields, n0, n1, axis0, axis1, group_field, group_x0_km, group_z0_km, n_groups,
-                         link_group, link_target_km, n_links, scan_elevation_deg, n_scan, earth_radius_km, s_max_km, rtol, atol,
-                         max_step_km, z_ground_km, top, left, right, renormalize_every, fill_n, fill_grad, fill_mup, range_tol_km,
-                         max_iter, max_roots, out, n_brackets, flags);
+    const GradControls t{geometry, earth_radius_km, s_max_km, rtol, atol, max_step_km, z_ground_km, top, left, right,
+                         renormalize_every, fill_n, fill_grad, fill_mup};
+    return grad_home_run(c, 0, t, FieldGrid{records, n_fields, n0, n1, axis0, axis1},
+                         GradGroups{group_field, group_x0_km, group_z0_km, n_groups}, link_group, link_target_km, n_links,
+                         scan_elevation_deg, n_scan, range_tol_km, max_iter, max_roots, out, n_brackets, flags);
 }
 
 int prhf_gradient_hop_home_f64(prhf_ctx* c, int32_t geometry, const double* records, int64_t n_fields, int64_t n0, int64_t n1,
@@ -2659,10 +2645,11 @@ int prhf_gradient_hop_home_f64(prhf_ctx* c, int32_t geometry, const double* reco
                                int64_t* n_brackets, uint32_t flags) {
     if (!c) return fail(PRHF_EINVAL, "null context");
     if (n_hops < 1 || n_hops > PRHF_GRAD_MAX_HOPS) return fail(PRHF_EINVAL, "n_hops is 1 .. 16");
-    return grad_home_run(c, n_hops, geometry, records, n_fields, n0, n1, axis0, axis1, group_field, group_x0_km, group_z0_km,
-                         n_groups, link_group, link_target_km, n_links, scan_elevation_deg, n_scan, earth_radius_km, s_max_km, rtol,
-                         atol, max_step_km, z_ground_km, top, left, right, renormalize_every, fill_n, fill_grad, fill_mup,
-                         range_tol_km, max_iter, max_roots, out, n_brackets, flags);
+    const GradControls t{geometry, earth_radius_km, s_max_km, rtol, atol, max_step_km, z_ground_km, top, left, right,
+                         renormalize_every, fill_n, fill_grad, fill_mup};
+    return grad_home_run(c, n_hops, t, FieldGrid{records, n_fields, n0, n1, axis0, axis1},
+                         GradGroups{group_field, group_x0_km, group_z0_km, n_groups}, link_group, link_target_km, n_links,
+                         scan_elevation_deg, n_scan, range_tol_km, max_iter, max_roots, out, n_brackets, flags);
 }
 
 int prhf_gradient_home_counters(prhf_ctx* c, uint64_t* counters) {
@@ -2672,54 +2659,27 @@ int prhf_gradient_home_counters(prhf_ctx* c, uint64_t* counters) {
 }
 
 namespace {
-// What prhf_gradient_skip_f64 and prhf_gradient_muf_f64 share: the checks of the tracer's controls and of the search's,
-// and the tracer's arguments (prhf_gradient_home_f64's rules).
-int grad_search_check(int32_t geometry, double earth_radius_km, double s_max_km, double rtol, double atol, double max_step_km,
-                      int32_t renormalize_every, int64_t n_scan, double elev_tol_deg, int32_t max_iter, uint32_t flags) {
-    if (geometry != PRHF_GEO_CARTESIAN && geometry != PRHF_GEO_SPHERICAL)
-        return fail(PRHF_EINVAL, "geometry is 0 (Cartesian) or 1 (spherical)");
-    if (geometry == PRHF_GEO_SPHERICAL && (!(earth_radius_km > 0) || !std::isfinite(earth_radius_km)))
-        return fail(PRHF_EINVAL, "earth_radius_km must be positive and finite");
-    if (flags & ~PRHF_FLAG_DEVICE_PTRS) return fail(PRHF_EINVAL, "unknown flag bits");
-    if (!(s_max_km > 0) || !std::isfinite(s_max_km)) return fail(PRHF_EINVAL, "s_max_km must be positive and finite");
-    if (!(max_step_km > 0)) return fail(PRHF_EINVAL, "`max_step` must be positive.");
-    if (!(rtol >= 0) || !(atol >= 0)) return fail(PRHF_EINVAL, "`atol` must be positive.");
-    if (renormalize_every < 0) return fail(PRHF_EINVAL, "renormalize_every must not be negative");
-    if (n_scan < 1 || n_scan > 0x7fffffffLL) return fail(PRHF_EINVAL, "the scan grid needs at least 1 elevation");
-    if (max_iter < 1 || max_iter > 128) return fail(PRHF_EINVAL, "max_iter is 1 .. 128");
-    if (!(elev_tol_deg >= 0.0) || !std::isfinite(elev_tol_deg))
-        return fail(PRHF_EINVAL, "elev_tol_deg must be finite and not negative");
-    return PRHF_OK;
-}
-int grad_scan_check(const double* scan_elevation_deg, int64_t n_scan) {
-    for (int64_t i = 0; i + 1 < n_scan; ++i)
-        if (!(scan_elevation_deg[i + 1] > scan_elevation_deg[i]))
-            return fail(PRHF_EINVAL, "scan_elevation_deg must be strictly increasing");
-    if (n_scan == 1 && !std::isfinite(scan_elevation_deg[0])) return fail(PRHF_EINVAL, "scan_elevation_deg must be finite");
-    return PRHF_OK;
-}
-void grad_search_args(prhf_ctx* c, prhf::GradTraceArgs& a, int32_t geometry, const double* records, int64_t n_fields, int64_t n0,
-                      int64_t n1, const double* d_axes, double earth_radius_km, double s_max_km, double rtol, double atol,
-                      double max_step_km, double z_ground_km, double top, double left, double right, int32_t renormalize_every,
-                      double fill_n, double fill_grad, double fill_mup) {
-    a.rec = records; a.a0 = d_axes; a.a1 = d_axes + n0; a.n0 = (int)n0; a.n1 = (int)n1; a.n_fields = n_fields;
-    a.s_max = s_max_km;
-    a.rtol = rtol < 100 * 2.220446049250313e-16 ? 100 * 2.220446049250313e-16 : rtol;     // (as the tracers: solve_ivp's floor)
-    a.atol = atol; a.max_step = max_step_km;
-    // (the spherical tracer binds R_E + z_ground_km to the ground event, prhf_trace_gradient_spherical_f64)
-    a.z_ground = geometry == PRHF_GEO_SPHERICAL ? earth_radius_km + z_ground_km : z_ground_km;
-    a.z_max = top; a.x_min = left; a.x_max = right; a.renormalize_every = renormalize_every;
-    a.fill_n = fill_n; a.fill_grad = fill_grad; a.fill_mup = fill_mup; a.status = c->h_status_dev;
-    a.geometry = geometry; a.earth_radius = geometry == PRHF_GEO_SPHERICAL ? earth_radius_km : 0.0;
-}
+// The end of a skip or MUF call of the gradient tracers: the counters come back with the results, one synchronisation
 int grad_skip_finish(prhf_ctx* c, const unsigned* queue) {
     unsigned w[PRHF_GRAD_SKIP_QUEUE_WORDS] = {};
-    HIP_TRY(hipMemcpyAsync(w, queue, sizeof w, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(download(c, w, queue, sizeof w));
     const int rc = prhf_sync(c);
     c->grad_skip_counters[0] = w[4];
     for (int k = 1; k < PRHF_GRAD_SKIP_COUNTERS; ++k) c->grad_skip_counters[k] = w[k];
     c->grad_skip_counters[PRHF_GRAD_SKIP_COUNTERS] = w[5];
     return rc;
+}
+// What the skip and MUF calls put into GradSkipArgs alike
+void grad_skip_args(prhf::GradSkipArgs& h, int64_t n_groups, int64_t n_scan, double elev_tol_deg, int32_t max_iter, int row_width,
+                    int32_t n_hops, const GradControls& t) {
+    h.n_groups = n_groups; h.n_scan = (int)n_scan; h.elev_tol = elev_tol_deg; h.max_iter = max_iter;
+    h.row_width = row_width; h.g.n_hops = n_hops ? n_hops : 1; h.g.hop_z0 = t.z_ground_km;
+}
+// ... and the head of their c->partial: the counters, the work list and the scan's ground ranges
+void carve_grad_skip_scratch(Carver& k, prhf::GradSkipArgs& h, size_t G, size_t E) {
+    h.queue = k.take<unsigned>(128 / sizeof(unsigned));
+    h.work = k.take<int>(2 * G);
+    h.scan_d = k.take<double>(G * E);
 }
 }  // namespace
 
@@ -2733,8 +2693,7 @@ int prhf_field_build_f64(prhf_ctx* c, const double* den, const double* bmag, con
     if (edge_order != 1 && edge_order != 2) return fail(PRHF_EINVAL, "edge_order is 1 or 2");
     if (flags & ~PRHF_FLAG_DEVICE_PTRS) return fail(PRHF_EINVAL, "unknown flag bits");
     int u0 = 0, u1 = 0;
-    int rc = check_field_shape(axis0, axis1, n_freq, n0, n1, edge_order + 1, &u0, &u1);
-    if (rc != PRHF_OK) return rc;
+    PRHF_TRY(check_field_shape(axis0, axis1, n_freq, n0, n1, edge_order + 1, &u0, &u1));
     const bool dev = (flags & PRHF_FLAG_DEVICE_PTRS) != 0;
     const size_t plane = (size_t)n0 * (size_t)n1, F = (size_t)n_freq, cells = F * plane;
     if (!dev)
@@ -2742,40 +2701,37 @@ int prhf_field_build_f64(prhf_ctx* c, const double* den, const double* bmag, con
             if (den[i] < 0) return fail(PRHF_ENEGDEN, "Density must be non-negative");
     ENTER_DEVICE(c->device);
     const bool own_mu = !dev || !mu_out;
-    rc = ensure(c, c->arena, ((size_t)(n0 + n1) + (dev ? 0 : 3 * plane + F) + (own_mu ? 2 * cells : 0)) * 8);
-    if (rc != PRHF_OK) return rc;
-    double* p = static_cast<double*>(c->arena.p);
-    HIP_TRY(hipMemcpyAsync(p, axis0, (size_t)n0 * 8, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(p + n0, axis1, (size_t)n1 * 8, hipMemcpyHostToDevice, c->stream));
     prhf::FieldBuildArgs b;
     std::memset(&b, 0, sizeof b);
     prhf::FieldPackArgs a;
     std::memset(&a, 0, sizeof a);
-    a.a0 = p; a.a1 = p + n0;
-    double* q = p + n0 + n1;
-    b.den = den; b.bmag = bmag; b.bpsi = bpsi; b.freq = freq_hz;
-    if (!dev) {
-        HIP_TRY(hipMemcpyAsync(q, den, plane * 8, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(q + plane, bmag, plane * 8, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(q + 2 * plane, bpsi, plane * 8, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(q + 3 * plane, freq_hz, F * 8, hipMemcpyHostToDevice, c->stream));
-        b.den = q; b.bmag = q + plane; b.bpsi = q + 2 * plane; b.freq = q + 3 * plane;
-        q += 3 * plane + F;
-    }
-    b.mu = own_mu ? q : mu_out; b.mup = own_mu ? q + cells : mup_out;
+    b.den = den; b.bmag = bmag; b.bpsi = bpsi; b.freq = freq_hz; b.mu = mu_out; b.mup = mup_out;
+    PRHF_TRY(carve(c, c->arena, [&](Stager& k) {
+        put_axes(k, a, axis0, axis1, n0, n1);
+        if (!dev) {
+            b.den = k.put<double>(den, plane);
+            b.bmag = k.put<double>(bmag, plane);
+            b.bpsi = k.put<double>(bpsi, plane);
+            b.freq = k.put<double>(freq_hz, F);
+        }
+        if (own_mu) {
+            b.mu = k.take<double>(cells);
+            b.mup = k.take<double>(cells);
+        }
+    }));
     b.bmax = c->d_words; b.n_freq = n_freq; b.plane = (long long)plane;
     b.mode = mode == PRHF_MODE_O ? PRHF_KMODE_O : PRHF_KMODE_X;
     a.mu = b.mu; a.mup = b.mup; a.rec = records; a.n_fields = n_freq; a.n0 = (int)n0; a.n1 = (int)n1;
     a.uniform0 = u0; a.uniform1 = u1; a.edge_order = edge_order;
-    HIP_TRY(hipEventRecord(c->begin_ev(), c->stream));
-    HIP_TRY(prhf::launch_field_bmax(b.bmag, b.plane, c->d_words, c->stream));
-    HIP_TRY(prhf::launch_field_build(b, c->stream));
-    HIP_TRY(prhf::launch_field_pack(a, c->stream));
-    HIP_TRY(hipEventRecord(c->pending_end_ev(), c->stream));
-    c->mark_timed();
+    PRHF_TRY(timed_launch(c, false, [&] {
+        hipError_t e = prhf::launch_field_bmax(b.bmag, b.plane, c->d_words, c->stream);
+        if (e == hipSuccess) e = prhf::launch_field_build(b, c->stream);
+        if (e == hipSuccess) e = prhf::launch_field_pack(a, c->stream);
+        return e;
+    }));
     if (!dev && mu_out) {
-        HIP_TRY(hipMemcpyAsync(mu_out, b.mu, cells * 8, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipMemcpyAsync(mup_out, b.mup, cells * 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(download(c, mu_out, b.mu, cells * 8));
+        HIP_TRY(download(c, mup_out, b.mup, cells * 8));
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
     return PRHF_OK;
@@ -2783,78 +2739,44 @@ int prhf_field_build_f64(prhf_ctx* c, const double* den, const double* bmag, con
 
 namespace {
 // Both skip calls.  n_hops 0: prhf_gradient_skip_f64 (rows of 18); else prhf_gradient_hop_skip_f64 (6 + 15 n_hops).
-int grad_skip_run(prhf_ctx* c, int32_t n_hops, int32_t geometry, const double* records, int64_t n_fields, int64_t n0, int64_t n1,
-                  const double* axis0, const double* axis1, const int64_t* group_field, const double* group_x0_km,
-                  const double* group_z0_km, int64_t n_groups, const double* scan_elevation_deg, int64_t n_scan,
-                  double earth_radius_km, double s_max_km, double rtol, double atol, double max_step_km,
-                  double z_ground_km, double top, double left, double right, int32_t renormalize_every,
-                  double fill_n, double fill_grad, double fill_mup, double elev_tol_deg, int32_t max_iter,
-                  double* out, uint32_t flags) {
+int grad_skip_run(prhf_ctx* c, int32_t n_hops, const GradControls& t, const FieldGrid& f, const GradGroups& g,
+                  const double* scan_elevation_deg, int64_t n_scan, double elev_tol_deg, int32_t max_iter, double* out,
+                  uint32_t flags) {
     const int row_width = n_hops ? PRHF_GRAD_HOP_SKIP_OUTPUTS(n_hops) : PRHF_GRAD_SKIP_OUTPUTS;
-    if (!records || !group_field || !group_x0_km || !group_z0_km || !scan_elevation_deg || !out)
+    const int64_t n_groups = g.n;
+    if (!f.records || !g.field || !g.x0_km || !g.z0_km || !scan_elevation_deg || !out)
         return fail(PRHF_EINVAL, "null array pointer");
-    int rc = grad_search_check(geometry, earth_radius_km, s_max_km, rtol, atol, max_step_km, renormalize_every, n_scan,
-                               elev_tol_deg, max_iter, flags);
-    if (rc != PRHF_OK) return rc;
+    PRHF_TRY(check_grad_controls(t, flags));
+    PRHF_TRY(check_grad_search(n_scan, elev_tol_deg, max_iter));
     if (n_groups < 1) return fail(PRHF_EINVAL, "the search needs at least one group");
     if (n_groups > 0x7fffffffLL || n_groups * ((n_scan + 63) / 64) > 0x7fffffffLL)
         return fail(PRHF_EINVAL, "more than 2^31 - 1 groups or scan wavefronts: search in batches");
     int u0 = 0, u1 = 0;
-    rc = check_field_shape(axis0, axis1, n_fields, n0, n1, 2, &u0, &u1);
-    if (rc != PRHF_OK) return rc;
+    PRHF_TRY(check_field_shape(f.axis0, f.axis1, f.n_fields, f.n0, f.n1, 2, &u0, &u1));
     const bool dev = (flags & PRHF_FLAG_DEVICE_PTRS) != 0;
     if (!dev) {
-        rc = grad_scan_check(scan_elevation_deg, n_scan);
-        if (rc != PRHF_OK) return rc;
-        for (int64_t g = 0; g < n_groups; ++g)
-            if (group_field[g] < 0 || group_field[g] >= n_fields)
-                return fail(PRHF_EINVAL, "group_field[%lld] outside [0, n_fields)", (long long)g);
+        PRHF_TRY(check_scan_grid(scan_elevation_deg, n_scan, true));
+        PRHF_TRY(check_index("group_field", g.field, n_groups, "n_fields", f.n_fields));
     }
     for (uint64_t& w : c->grad_skip_counters) w = 0;
     ENTER_DEVICE(c->device);
     const size_t G = (size_t)n_groups, E = (size_t)n_scan, out_elems = G * (size_t)row_width;
-    rc = ensure(c, c->arena, ((size_t)(n0 + n1) + (dev ? 0 : 3 * G + E + out_elems)) * 8);
-    if (rc != PRHF_OK) return rc;
-    double* p = static_cast<double*>(c->arena.p);
     prhf::GradSkipArgs h;
     std::memset(&h, 0, sizeof h);
-    HIP_TRY(hipMemcpyAsync(p, axis0, (size_t)n0 * 8, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(p + n0, axis1, (size_t)n1 * 8, hipMemcpyHostToDevice, c->stream));
-    grad_search_args(c, h.g, geometry, records, n_fields, n0, n1, p, earth_radius_km, s_max_km, rtol, atol, max_step_km,
-                     z_ground_km, top, left, right, renormalize_every, fill_n, fill_grad, fill_mup);
-    h.n_groups = n_groups; h.n_scan = (int)n_scan; h.elev_tol = elev_tol_deg; h.max_iter = max_iter;
-    h.row_width = row_width; h.g.n_hops = n_hops ? n_hops : 1; h.g.hop_z0 = z_ground_km;
-    if (dev) {
-        h.group_field = reinterpret_cast<const long long*>(group_field); h.group_x0 = group_x0_km; h.group_z0 = group_z0_km;
-        h.scan_elev = scan_elevation_deg; h.out = out;
-    } else {
-        double* q = p + n0 + n1;
-        long long* d_gf = reinterpret_cast<long long*>(q); q += G;
-        double* d_x0 = q; q += G;
-        double* d_z0 = q; q += G;
-        double* d_e = q; q += E;
-        HIP_TRY(hipMemcpyAsync(d_gf, group_field, G * 8, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(d_x0, group_x0_km, G * 8, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(d_z0, group_z0_km, G * 8, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(d_e, scan_elevation_deg, E * 8, hipMemcpyHostToDevice, c->stream));
-        h.group_field = d_gf; h.group_x0 = d_x0; h.group_z0 = d_z0; h.scan_elev = d_e; h.out = q;
-    }
-    {
-        // the counters, the work list and the scan's ground ranges
-        const size_t queue_bytes = 128, work_bytes = G * 8, scan_bytes = G * E * 8;
-        rc = ensure(c, c->partial, queue_bytes + work_bytes + scan_bytes);
-        if (rc != PRHF_OK) return rc;
-        char* q = static_cast<char*>(c->partial.p);
-        h.queue = reinterpret_cast<unsigned*>(q);
-        h.work = reinterpret_cast<int*>(q + queue_bytes);
-        h.scan_d = reinterpret_cast<double*>(q + queue_bytes + work_bytes);
-    }
-    HIP_TRY(hipEventRecord(c->begin_ev(), c->stream));
-    HIP_TRY(prhf::launch_grad_skip(h, n_hops != 0, c->stream));
-    HIP_TRY(hipEventRecord(c->pending_end_ev(), c->stream));
-    c->mark_timed();
-    c->status_pending = true;
-    if (!dev) HIP_TRY(hipMemcpyAsync(out, h.out, out_elems * 8, hipMemcpyDeviceToHost, c->stream));
+    grad_trace_args(c, h.g, f, t);
+    grad_skip_args(h, n_groups, n_scan, elev_tol_deg, max_iter, row_width, n_hops, t);
+    h.group_field = reinterpret_cast<const long long*>(g.field); h.group_x0 = g.x0_km; h.group_z0 = g.z0_km;
+    h.scan_elev = scan_elevation_deg; h.out = out;
+    PRHF_TRY(carve(c, c->arena, [&](Stager& k) {
+        put_axes(k, h.g, f.axis0, f.axis1, f.n0, f.n1);
+        if (dev) return;
+        put_groups(k, h, g);
+        h.scan_elev = k.put<double>(scan_elevation_deg, E);
+        h.out = k.take<double>(out_elems);
+    }));
+    PRHF_TRY(carve(c, c->partial, [&](Stager& k) { carve_grad_skip_scratch(k, h, G, E); }));
+    PRHF_TRY(timed_launch(c, true, [&] { return prhf::launch_grad_skip(h, n_hops != 0, c->stream); }));
+    if (!dev) HIP_TRY(download(c, out, h.out, out_elems * 8));
     return grad_skip_finish(c, h.queue);
 }
 }  // namespace
@@ -2867,9 +2789,11 @@ int prhf_gradient_skip_f64(prhf_ctx* c, int32_t geometry, const double* records,
                            double fill_n, double fill_grad, double fill_mup, double elev_tol_deg, int32_t max_iter,
                            double* out, uint32_t flags) {
     if (!c) return fail(PRHF_EINVAL, "null context");
-    return grad_skip_run(c, 0, geometry, records, n_fields, n0, n1, axis0, axis1, group_field, group_x0_km, group_z0_km, n_groups,
-                         scan_elevation_deg, n_scan, earth_radius_km, s_max_km, rtol, atol, max_step_km, z_ground_km, top, left,
-                         right, renormalize_every, fill_n, fill_grad, fill_mup, elev_tol_deg, max_iter, out, flags);
+    const GradControls t{geometry, earth_radius_km, s_max_km, rtol, atol, max_step_km, z_ground_km, top, left, right,
+                         renormalize_every, fill_n, fill_grad, fill_mup};
+    return grad_skip_run(c, 0, t, FieldGrid{records, n_fields, n0, n1, axis0, axis1},
+                         GradGroups{group_field, group_x0_km, group_z0_km, n_groups}, scan_elevation_deg, n_scan, elev_tol_deg,
+                         max_iter, out, flags);
 }
 
 int prhf_gradient_hop_skip_f64(prhf_ctx* c, int32_t geometry, const double* records, int64_t n_fields, int64_t n0, int64_t n1,
@@ -2881,116 +2805,103 @@ int prhf_gradient_hop_skip_f64(prhf_ctx* c, int32_t geometry, const double* reco
                                double elev_tol_deg, int32_t max_iter, int32_t n_hops, double* out, uint32_t flags) {
     if (!c) return fail(PRHF_EINVAL, "null context");
     if (n_hops < 1 || n_hops > PRHF_GRAD_MAX_HOPS) return fail(PRHF_EINVAL, "n_hops is 1 .. 16");
-    return grad_skip_run(c, n_hops, geometry, records, n_fields, n0, n1, axis0, axis1, group_field, group_x0_km, group_z0_km, n_groups,
-                         scan_elevation_deg, n_scan, earth_radius_km, s_max_km, rtol, atol, max_step_km, z_ground_km, top, left,
-                         right, renormalize_every, fill_n, fill_grad, fill_mup, elev_tol_deg, max_iter, out, flags);
+    const GradControls t{geometry, earth_radius_km, s_max_km, rtol, atol, max_step_km, z_ground_km, top, left, right,
+                         renormalize_every, fill_n, fill_grad, fill_mup};
+    return grad_skip_run(c, n_hops, t, FieldGrid{records, n_fields, n0, n1, axis0, axis1},
+                         GradGroups{group_field, group_x0_km, group_z0_km, n_groups}, scan_elevation_deg, n_scan, elev_tol_deg,
+                         max_iter, out, flags);
 }
 
 namespace {
+// The one ionosphere of a MUF call (prhf_field_build_f64's inputs) and its links
+struct MufIonosphere {
+    const double *den, *bmag, *bpsi;
+    int64_t n0, n1;
+    const double *axis0, *axis1;
+    int32_t mode, edge_order;
+};
+struct MufLinks {
+    const double *x0_km, *z0_km, *target_km;
+    int64_t n;
+    double f_lo_hz, f_hi_hz;
+    int32_t n_bisect;
+};
 // Both MUF calls.  n_hops 0: prhf_gradient_muf_f64 (rows of 21); else prhf_gradient_hop_muf_f64 (3 + 6 + 15 n_hops).
-
-int grad_muf_run(prhf_ctx* c, int32_t n_hops, int32_t geometry, const double* den, const double* bmag, const double* bpsi, int64_t n0,
-                 int64_t n1, const double* axis0, const double* axis1, int32_t mode, int32_t edge_order,
-                 const double* link_x0_km, const double* link_z0_km, const double* link_target_km, int64_t n_links,
-                 double f_lo_hz, double f_hi_hz, int32_t n_bisect, const double* scan_elevation_deg, int64_t n_scan,
-                 double earth_radius_km, double s_max_km, double rtol, double atol, double max_step_km,
-                 double z_ground_km, double top, double left, double right, int32_t renormalize_every, double fill_n,
-                 double fill_grad, double fill_mup, double elev_tol_deg, int32_t max_iter, double* out, uint32_t flags) {
+int grad_muf_run(prhf_ctx* c, int32_t n_hops, const GradControls& t, const MufIonosphere& io, const MufLinks& lk,
+                 const double* scan_elevation_deg, int64_t n_scan, double elev_tol_deg, int32_t max_iter, double* out,
+                 uint32_t flags) {
     const int row_width = n_hops ? PRHF_GRAD_HOP_SKIP_OUTPUTS(n_hops) : PRHF_GRAD_SKIP_OUTPUTS;
-    if (!den || !bmag || !bpsi || !link_x0_km || !link_z0_km || !link_target_km || !scan_elevation_deg || !out)
+    const int64_t n_links = lk.n, n0 = io.n0, n1 = io.n1;
+    if (!io.den || !io.bmag || !io.bpsi || !lk.x0_km || !lk.z0_km || !lk.target_km || !scan_elevation_deg || !out)
         return fail(PRHF_EINVAL, "null array pointer");
-    int rc = grad_search_check(geometry, earth_radius_km, s_max_km, rtol, atol, max_step_km, renormalize_every, n_scan,
-                               elev_tol_deg, max_iter, flags);
-    if (rc != PRHF_OK) return rc;
-    if (mode != PRHF_MODE_O && mode != PRHF_MODE_X) return fail(PRHF_EINVAL, "Mode must be O or X");
-    if (edge_order != 1 && edge_order != 2) return fail(PRHF_EINVAL, "edge_order is 1 or 2");
-    if (n_bisect < 1 || n_bisect > 64) return fail(PRHF_EINVAL, "n_bisect is 1 .. 64");
-    if (!(f_lo_hz > 0.0) || !(f_hi_hz > f_lo_hz) || !std::isfinite(f_hi_hz))
+    PRHF_TRY(check_grad_controls(t, flags));
+    PRHF_TRY(check_grad_search(n_scan, elev_tol_deg, max_iter));
+    if (io.mode != PRHF_MODE_O && io.mode != PRHF_MODE_X) return fail(PRHF_EINVAL, "Mode must be O or X");
+    if (io.edge_order != 1 && io.edge_order != 2) return fail(PRHF_EINVAL, "edge_order is 1 or 2");
+    if (lk.n_bisect < 1 || lk.n_bisect > 64) return fail(PRHF_EINVAL, "n_bisect is 1 .. 64");
+    if (!(lk.f_lo_hz > 0.0) || !(lk.f_hi_hz > lk.f_lo_hz) || !std::isfinite(lk.f_hi_hz))
         return fail(PRHF_EINVAL, "the frequency bracket needs 0 < f_lo_hz < f_hi_hz, both finite");
     if (n_links < 1) return fail(PRHF_EINVAL, "the search needs at least one link");
     if (n_links * ((n_scan + 63) / 64) > 0x7fffffffLL)
         return fail(PRHF_EINVAL, "more than 2^31 - 1 scan wavefronts: search in batches");
     int u0 = 0, u1 = 0;
-    rc = check_field_shape(axis0, axis1, n_links, n0, n1, edge_order + 1 > 2 ? edge_order + 1 : 2, &u0, &u1);
-    if (rc != PRHF_OK) return rc;
+    PRHF_TRY(check_field_shape(io.axis0, io.axis1, n_links, n0, n1, io.edge_order + 1 > 2 ? io.edge_order + 1 : 2, &u0, &u1));
     const bool dev = (flags & PRHF_FLAG_DEVICE_PTRS) != 0;
     const size_t plane = (size_t)n0 * (size_t)n1, L = (size_t)n_links, E = (size_t)n_scan;
     if (!dev) {
-        rc = grad_scan_check(scan_elevation_deg, n_scan);
-        if (rc != PRHF_OK) return rc;
+        PRHF_TRY(check_scan_grid(scan_elevation_deg, n_scan, true));
         for (size_t i = 0; i < plane; ++i)
-            if (den[i] < 0) return fail(PRHF_ENEGDEN, "Density must be non-negative");
+            if (io.den[i] < 0) return fail(PRHF_ENEGDEN, "Density must be non-negative");
     }
     for (uint64_t& w : c->grad_skip_counters) w = 0;
     ENTER_DEVICE(c->device);
     const size_t out_elems = L * (size_t)(3 + row_width);
-    rc = ensure(c, c->arena, ((size_t)(n0 + n1) + (dev ? 0 : 3 * plane + 3 * L + E + out_elems)) * 8);
-    if (rc != PRHF_OK) return rc;
-    // one field per link: mu, mu' and the records, 48 bytes per node
-    rc = ensure(c, c->fields, L * plane * 48);
-    if (rc != PRHF_OK) return rc;
-    double* p = static_cast<double*>(c->arena.p);
     prhf::GradMufArgs m;
     std::memset(&m, 0, sizeof m);
     prhf::GradSkipArgs& h = m.k;
-    HIP_TRY(hipMemcpyAsync(p, axis0, (size_t)n0 * 8, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(p + n0, axis1, (size_t)n1 * 8, hipMemcpyHostToDevice, c->stream));
-    double* fields = static_cast<double*>(c->fields.p);
-    m.b.mu = fields; m.b.mup = fields + L * plane;
-    double* rec = fields + 2 * L * plane;
-    grad_search_args(c, h.g, geometry, rec, n_links, n0, n1, p, earth_radius_km, s_max_km, rtol, atol, max_step_km,
-                     z_ground_km, top, left, right, renormalize_every, fill_n, fill_grad, fill_mup);
-    h.n_groups = n_links; h.n_scan = (int)n_scan; h.elev_tol = elev_tol_deg; h.max_iter = max_iter;
-    h.row_width = row_width; h.g.n_hops = n_hops ? n_hops : 1; h.g.hop_z0 = z_ground_km;
-    m.n_links = n_links; m.f_lo = f_lo_hz; m.f_hi = f_hi_hz; m.n_bisect = n_bisect;
-    double* d_result = out;
-    if (dev) {
-        m.b.den = den; m.b.bmag = bmag; m.b.bpsi = bpsi;
-        h.group_x0 = link_x0_km; h.group_z0 = link_z0_km; m.link_target = link_target_km; h.scan_elev = scan_elevation_deg;
-    } else {
-        double* q = p + n0 + n1;
-        const double* src[3] = {den, bmag, bpsi};
-        for (int k = 0; k < 3; ++k) HIP_TRY(hipMemcpyAsync(q + k * plane, src[k], plane * 8, hipMemcpyHostToDevice, c->stream));
-        m.b.den = q; m.b.bmag = q + plane; m.b.bpsi = q + 2 * plane;
-        q += 3 * plane;
-        HIP_TRY(hipMemcpyAsync(q, link_x0_km, L * 8, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(q + L, link_z0_km, L * 8, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(q + 2 * L, link_target_km, L * 8, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(q + 3 * L, scan_elevation_deg, E * 8, hipMemcpyHostToDevice, c->stream));
-        h.group_x0 = q; h.group_z0 = q + L; m.link_target = q + 2 * L; h.scan_elev = q + 3 * L;
-        d_result = q + 3 * L + E;
-    }
-    {
-        // the counters, the work list, the scan's ground ranges; per link its frequency, field index, bracket, the skip
-        // row of the trip, the head of the row at the bracket's lower end and the "is searching" word
-        const size_t queue_bytes = 128, work_bytes = L * 8, scan_bytes = L * E * 8;
-        const size_t link_doubles = L * (1 + 1 + 4 + (PRHF_GRAD_SKIP_OUTPUTS - PRHF_GRAD_OUTPUTS) + (size_t)row_width);
-        rc = ensure(c, c->partial, queue_bytes + work_bytes + scan_bytes + link_doubles * 8 + L * 4);
-        if (rc != PRHF_OK) return rc;
-        char* q = static_cast<char*>(c->partial.p);
-        h.queue = reinterpret_cast<unsigned*>(q);
-        h.work = reinterpret_cast<int*>(q + queue_bytes);
-        h.scan_d = reinterpret_cast<double*>(q + queue_bytes + work_bytes);
-        double* r = h.scan_d + L * E;
-        m.group_freq = r; r += L;
-        m.group_field = reinterpret_cast<long long*>(r); r += L;
-        m.state = r; r += 4 * L;
-        m.best = r; r += L * (PRHF_GRAD_SKIP_OUTPUTS - PRHF_GRAD_OUTPUTS);
-        h.out = r; r += L * (size_t)row_width;
-        m.active = reinterpret_cast<int*>(r);
-    }
+    // one field per link: mu, mu' and the records, 48 bytes per node (made room for before the first upload goes out)
+    double* rec = nullptr;
+    PRHF_TRY(carve(c, c->fields, [&](Stager& k) {
+        m.b.mu = k.take<double>(L * plane);
+        m.b.mup = k.take<double>(L * plane);
+        rec = k.take<double>(4 * L * plane);
+    }));
+    m.b.den = io.den; m.b.bmag = io.bmag; m.b.bpsi = io.bpsi;
+    h.group_x0 = lk.x0_km; h.group_z0 = lk.z0_km; m.link_target = lk.target_km; h.scan_elev = scan_elevation_deg; m.out = out;
+    PRHF_TRY(carve(c, c->arena, [&](Stager& k) {
+        put_axes(k, m.p, io.axis0, io.axis1, n0, n1);
+        if (dev) return;
+        m.b.den = k.put<double>(io.den, plane);
+        m.b.bmag = k.put<double>(io.bmag, plane);
+        m.b.bpsi = k.put<double>(io.bpsi, plane);
+        h.group_x0 = k.put<double>(lk.x0_km, L);
+        h.group_z0 = k.put<double>(lk.z0_km, L);
+        m.link_target = k.put<double>(lk.target_km, L);
+        h.scan_elev = k.put<double>(scan_elevation_deg, E);
+        m.out = k.take<double>(out_elems);
+    }));
+    grad_trace_args(c, h.g, FieldGrid{rec, n_links, n0, n1, io.axis0, io.axis1}, t);
+    h.g.a0 = m.p.a0; h.g.a1 = m.p.a1;
+    grad_skip_args(h, n_links, n_scan, elev_tol_deg, max_iter, row_width, n_hops, t);
+    m.n_links = n_links; m.f_lo = lk.f_lo_hz; m.f_hi = lk.f_hi_hz; m.n_bisect = lk.n_bisect;
+    // behind the skip call's scratch, per link: its frequency, field index, bracket, the head of the row at the bracket's
+    // lower end, the skip row of the trip and the "is searching" word
+    PRHF_TRY(carve(c, c->partial, [&](Stager& k) {
+        carve_grad_skip_scratch(k, h, L, E);
+        m.group_freq = k.take<double>(L);
+        m.group_field = k.take<long long>(L);
+        m.state = k.take<double>(4 * L);
+        m.best = k.take<double>(L * (PRHF_GRAD_SKIP_OUTPUTS - PRHF_GRAD_OUTPUTS));
+        h.out = k.take<double>(L * (size_t)row_width);
+        m.active = k.take<int>(L);
+    }));
     h.group_field = m.group_field; h.active = m.active;
-    m.out = d_result;
     m.b.freq = m.group_freq; m.b.active = m.active; m.b.bmax = c->d_words; m.b.n_freq = n_links; m.b.plane = (long long)plane;
-    m.b.mode = mode == PRHF_MODE_O ? PRHF_KMODE_O : PRHF_KMODE_X;
-    m.p.mu = m.b.mu; m.p.mup = m.b.mup; m.p.a0 = p; m.p.a1 = p + n0; m.p.rec = rec; m.p.n_fields = n_links;
-    m.p.n0 = (int)n0; m.p.n1 = (int)n1; m.p.uniform0 = u0; m.p.uniform1 = u1; m.p.edge_order = edge_order;
-    HIP_TRY(hipEventRecord(c->begin_ev(), c->stream));
-    HIP_TRY(prhf::launch_grad_muf(m, n_hops != 0, c->stream));
-    HIP_TRY(hipEventRecord(c->pending_end_ev(), c->stream));
-    c->mark_timed();
-    c->status_pending = true;
-    if (!dev) HIP_TRY(hipMemcpyAsync(out, d_result, out_elems * 8, hipMemcpyDeviceToHost, c->stream));
+    m.b.mode = io.mode == PRHF_MODE_O ? PRHF_KMODE_O : PRHF_KMODE_X;
+    m.p.mu = m.b.mu; m.p.mup = m.b.mup; m.p.rec = rec; m.p.n_fields = n_links;
+    m.p.n0 = (int)n0; m.p.n1 = (int)n1; m.p.uniform0 = u0; m.p.uniform1 = u1; m.p.edge_order = io.edge_order;
+    PRHF_TRY(timed_launch(c, true, [&] { return prhf::launch_grad_muf(m, n_hops != 0, c->stream); }));
+    if (!dev) HIP_TRY(download(c, out, m.out, out_elems * 8));
     return grad_skip_finish(c, h.queue);
 }
 }  // namespace
@@ -3003,10 +2914,11 @@ int prhf_gradient_muf_f64(prhf_ctx* c, int32_t geometry, const double* den, cons
                           double z_ground_km, double top, double left, double right, int32_t renormalize_every, double fill_n,
                           double fill_grad, double fill_mup, double elev_tol_deg, int32_t max_iter, double* out, uint32_t flags) {
     if (!c) return fail(PRHF_EINVAL, "null context");
-    return grad_muf_run(c, 0, geometry, den, bmag, bpsi, n0, n1, axis0, axis1, mode, edge_order, link_x0_km, link_z0_km, link_target_km,
-                        n_links, f_lo_hz, f_hi_hz, n_bisect, scan_elevation_deg, n_scan, earth_radius_km, s_max_km, rtol, atol,
-                        max_step_km, z_ground_km, top, left, right, renormalize_every, fill_n, fill_grad, fill_mup, elev_tol_deg,
-                        max_iter, out, flags);
+    const GradControls t{geometry, earth_radius_km, s_max_km, rtol, atol, max_step_km, z_ground_km, top, left, right,
+                         renormalize_every, fill_n, fill_grad, fill_mup};
+    return grad_muf_run(c, 0, t, MufIonosphere{den, bmag, bpsi, n0, n1, axis0, axis1, mode, edge_order},
+                        MufLinks{link_x0_km, link_z0_km, link_target_km, n_links, f_lo_hz, f_hi_hz, n_bisect}, scan_elevation_deg,
+                        n_scan, elev_tol_deg, max_iter, out, flags);
 }
 
 int prhf_gradient_hop_muf_f64(prhf_ctx* c, int32_t geometry, const double* den, const double* bmag, const double* bpsi,
@@ -3019,10 +2931,11 @@ int prhf_gradient_hop_muf_f64(prhf_ctx* c, int32_t geometry, const double* den, 
                               double elev_tol_deg, int32_t max_iter, int32_t n_hops, double* out, uint32_t flags) {
     if (!c) return fail(PRHF_EINVAL, "null context");
     if (n_hops < 1 || n_hops > PRHF_GRAD_MAX_HOPS) return fail(PRHF_EINVAL, "n_hops is 1 .. 16");
-    return grad_muf_run(c, n_hops, geometry, den, bmag, bpsi, n0, n1, axis0, axis1, mode, edge_order, link_x0_km, link_z0_km, link_target_km,
-                        n_links, f_lo_hz, f_hi_hz, n_bisect, scan_elevation_deg, n_scan, earth_radius_km, s_max_km, rtol, atol,
-                        max_step_km, z_ground_km, top, left, right, renormalize_every, fill_n, fill_grad, fill_mup, elev_tol_deg,
-                        max_iter, out, flags);
+    const GradControls t{geometry, earth_radius_km, s_max_km, rtol, atol, max_step_km, z_ground_km, top, left, right,
+                         renormalize_every, fill_n, fill_grad, fill_mup};
+    return grad_muf_run(c, n_hops, t, MufIonosphere{den, bmag, bpsi, n0, n1, axis0, axis1, mode, edge_order},
+                        MufLinks{link_x0_km, link_z0_km, link_target_km, n_links, f_lo_hz, f_hi_hz, n_bisect}, scan_elevation_deg,
+                        n_scan, elev_tol_deg, max_iter, out, flags);
 }
 
 int prhf_gradient_skip_counters(prhf_ctx* c, uint64_t* counters) {
@@ -3156,5 +3069,3 @@ int prhf_recent_kernel_ms(prhf_ctx* c, double* ms, int32_t capacity, int32_t* n_
     }
     return PRHF_OK;
 }
-
-}  // extern "C"

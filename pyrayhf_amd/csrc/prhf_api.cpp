@@ -21,6 +21,7 @@
 #include "prhf.h"
 #include "prhf_kernels.h"
 #include "prhf_arena.h"       // Carver: a scratch buffer's layout stated once, for its size and its pointers
+#include "prhf_layouts.h"     // ... the arena's blocks of the operator and the stage ops
 #include "prhf_plan.h"        // Knobs, plan_launch, StatusWord: the launch planning, HIP-free
 
 namespace {
@@ -195,6 +196,89 @@ int ensure(prhf_ctx* c, DevBuf& b, size_t bytes) {
     return PRHF_OK;
 }
 
+// ---- The steps every entry point is assembled from: checks, carve, stage, tail ----
+
+#define PRHF_TRY(expr)                     \
+    do {                                   \
+        const int rc_ = (expr);            \
+        if (rc_ != PRHF_OK) return rc_;    \
+    } while (0)
+
+hipError_t upload(prhf_ctx* c, void* dst, const void* src, size_t bytes) {
+    return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream);
+}
+hipError_t download(prhf_ctx* c, void* dst, const void* src, size_t bytes) {
+    return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream);
+}
+// rows of row_elems doubles, `stride` elements apart at the source (0: a single row, as it stands), packed at dst
+hipError_t upload_rows(prhf_ctx* c, double* dst, const double* src, size_t row_elems, size_t rows, int64_t stride) {
+    return hipMemcpy2DAsync(dst, row_elems * 8, src, (stride ? (size_t)stride : row_elems) * 8, row_elems * 8, rows,
+                            hipMemcpyHostToDevice, c->stream);
+}
+
+// A Carver (prhf_arena.h) that also stages: put() enqueues, on the pass over the buffer, the upload of a host array
+// into its room - room it takes itself, or room that a layout of prhf_layouts.h took (null on the sizing pass).  A
+// null array takes its room and gives a null pointer.
+class Stager : public Carver {
+  public:
+    // pack: host memory that mirrors the buffer - put() copies there instead, for the caller to send in one piece
+    Stager(prhf_ctx* c, void* base, void* pack = nullptr)
+        : Carver(base), c_(c), base_(static_cast<char*>(base)), pack_(static_cast<char*>(pack)) {}
+    template <class T>
+    T* put(const void* src, size_t count) {
+        T* d = take<T>(count);
+        if (!src) return nullptr;
+        put(d, src, count);
+        return d;
+    }
+    template <class T>
+    void put(T* d, const void* src, size_t count) {
+        if (!d || !src) return;
+        if (pack_) std::memcpy(mirror(d), src, count * sizeof(T));
+        else if (err_ == hipSuccess) err_ = upload(c_, d, src, count * sizeof(T));
+    }
+    // row-wise, for a strided source (upload_rows); no rows: nothing
+    void put_rows(double* d, const double* src, size_t row_elems, size_t rows, int64_t stride) {
+        if (!d || !rows) return;
+        if (pack_)
+            for (size_t r = 0; r < rows; ++r) std::memcpy(mirror(d + r * row_elems), src + r * (size_t)stride, row_elems * 8);
+        else if (err_ == hipSuccess) err_ = upload_rows(c_, d, src, row_elems, rows, stride);
+    }
+    hipError_t error() const { return err_; }
+
+  private:
+    char* mirror(const void* d) const { return pack_ + (static_cast<const char*>(d) - base_); }
+    prhf_ctx* c_;
+    char *base_, *pack_;
+    hipError_t err_ = hipSuccess;
+};
+
+// A buffer of the context laid out by `layout`, a function of a Stager: the pass over a null base gives the bytes the
+// buffer must hold, the pass over the buffer gives the pointers and sends the uploads.  No size is written down beside
+// its carving.
+template <class Layout>
+int carve(prhf_ctx* c, DevBuf& b, Layout layout) {
+    Stager sizing(c, nullptr);
+    layout(sizing);
+    PRHF_TRY(ensure(c, b, sizing.used()));
+    Stager k(c, b.p);
+    layout(k);
+    HIP_TRY(k.error());
+    return PRHF_OK;
+}
+
+// The tail of a launch: the two timing events around `launch` (one launch or a body of several, the first error
+// returned), the ring slot published and - posts_status - the status words read at the next prhf_sync.
+template <class Launch>
+int timed_launch(prhf_ctx* c, bool posts_status, Launch launch) {
+    HIP_TRY(hipEventRecord(c->begin_ev(), c->stream));
+    HIP_TRY(launch());
+    HIP_TRY(hipEventRecord(c->pending_end_ev(), c->stream));
+    c->mark_timed();
+    if (posts_status) c->status_pending = true;
+    return PRHF_OK;
+}
+
 // Optional second stage of a launch: residual rows against one observed trace (prhf_vfo_residual_f64), or - n_iono > 0 -
 // against the traces of many ionograms on the launch's frequency grid (prhf_vfo_residual_many_f64).
 struct Residual {
@@ -206,7 +290,9 @@ struct Residual {
     const int32_t* ionogram_of_row = nullptr;   // (n_prof), or null: shared candidates
     int64_t* best = nullptr;                    // (n_iono)
     double* best_cost = nullptr;                // (n_iono)
-    size_t cost_elems(int64_t n_prof) const { return (size_t)n_prof * (size_t)(n_iono && !ionogram_of_row ? n_iono : 1); }
+    size_t cost_elems(int64_t n_prof) const {
+        return n_iono ? many_cost_elems((size_t)n_prof, (size_t)n_iono, ionogram_of_row != nullptr) : (size_t)n_prof;
+    }
 };
 
 // The most dynamic LDS of a streaming workgroup (two slots; plan_launch admits what fits kLdsFull).  A -DPRHF_TRACE build
@@ -233,28 +319,56 @@ int status_to_code(unsigned bits) {
     return PRHF_OK;
 }
 
-// One operator call on its way through run(): the caller's arguments, and what one step leaves for the next
-struct Call {
-    prhf_ctx* c;
-    const double *freq, *den, *bmag, *bpsi, *alt, *mult;
-    int64_t n_freq, n_prof, n_alt, prof_stride, alt_stride, mult_len;
+// What the operator and its derivatives (Jacobian, VJP, JVP) are called on.  n_points, mode: of a call on the whole
+// batch (a work list names its own per slice)
+struct OperatorInputs {
+    const double* freq;
+    int64_t n_freq;
+    const double *den, *bmag, *bpsi, *alt;
+    int64_t n_prof, n_alt, prof_stride, alt_stride;
+    const double* mult;
+    int32_t n_points, mode;
+    uint32_t flags;
+    bool dev() const { return (flags & PRHF_FLAG_DEVICE_PTRS) != 0; }
+    bool shared_field() const { return (flags & PRHF_FLAG_SHARED_FIELD) != 0; }
+    OperatorShape shape(size_t mult_elems) const {       // of a host-buffer call's inputs in the arena (prhf_layouts.h)
+        const size_t P = (size_t)n_prof;
+        return {(size_t)n_freq, P, (size_t)n_alt, shared_field() ? 1 : P, alt_stride ? P : 1, mult_elems};
+    }
+};
+// ... and what an operator call does with them: its slices of the multiplier array, the result rows, the residual stage
+struct OperatorWork {
+    int64_t mult_len;
     const prhf_segment* segs;
     int32_t n_segs;
     double* out;
-    uint32_t flags;
     const Residual* post;
-    bool dev, shared_field;
+};
+// an input of a device-pointer call in a block's slot (prhf_layouts.h); the kernels read it only
+double* mut(const double* p) { return const_cast<double*>(p); }
+int kmode(int32_t mode) { return mode == PRHF_MODE_O ? PRHF_KMODE_O : PRHF_KMODE_X; }
+// The one slice of a call on the whole batch
+prhf_segment whole_batch(int64_t n_prof, int32_t mode, int32_t n_points) {
+    prhf_segment seg;
+    seg.prof_begin = 0;
+    seg.prof_end = n_prof;
+    seg.mode = mode;
+    seg.n_points = n_points;
+    seg.mult_offset = 0;
+    seg.out_offset = 0;
+    return seg;
+}
+
+// One operator call on its way through run(): the caller's arguments, and what one step leaves for the next
+struct Call : OperatorInputs, OperatorWork {
+    prhf_ctx* c;
     // stage_inputs:
     prhf_ctx::HostGrid* grid;   // host buffers with PRHF_FLAG_GRID_STABLE: the cached device copy of the grid
     double* d_out;              // host buffers: the result rows in the arena
     size_t in_elems, out_elems; // ... the doubles in front of them, and theirs
     bool out_direct;            // the kernels write the result into pinned host memory themselves
-    double* vh_dev;             // the modeled trace and the residual stage's other arrays on the device
-    const double* d_obs;
-    double *d_res, *d_cost;
-    const int32_t* d_ion;       // many ionograms: ionogram_of_row, best and best_cost on the device
-    int64_t* d_best;
-    double* d_best_cost;
+    double* vh_dev;             // the modeled trace on the device
+    ManyBlock stage;            // ... and the residual stage's arrays there (one trace: obs, residual, cost)
     // update_tables:
     unsigned* order_made;       // the short-grid O launch's blocks by cost (short_order_kernel), or null: index order
 };
@@ -266,67 +380,93 @@ prhf_ctx::HostGrid* find_host_grid(prhf_ctx* c, const double* mult, int64_t mult
     return nullptr;
 }
 
-int check_arguments(const Call& k) {
-    if (!k.c) return fail(PRHF_EINVAL, "null context");
-    if (!k.freq || !k.den || !k.bmag || !k.bpsi || !k.alt || !k.mult || !k.segs || (!k.out && !k.post))
+// The argument checks of the operator and its derivatives, in parts: an entry point calls them in its own order, which
+// is part of its contract (tests/test_gpu_operator_abi_rejections.py, tests/test_gpu_tracer_abi_rejections.py).
+// others_given: the arrays of the entry point's own are there
+int check_arrays(prhf_ctx* c, const OperatorInputs& in, bool others_given) {
+    if (!c) return fail(PRHF_EINVAL, "null context");
+    if (!in.freq || !in.den || !in.bmag || !in.bpsi || !in.alt || !in.mult || !others_given)
         return fail(PRHF_EINVAL, "null array pointer");
-    if (k.post && (!k.post->vh_obs || (!k.post->residual && !k.post->cost)))
-        return fail(PRHF_EINVAL, "null array pointer");
-    if (k.n_freq < 1 || k.n_prof < 0 || k.n_alt < 1) return fail(PRHF_EINVAL, "bad shape");
-    if (k.n_alt > kMaxAltTall) return fail(PRHF_EINVAL, "n_alt %lld exceeds the limit of %lld levels",
-                                           (long long)k.n_alt, kMaxAltTall);
-    if (k.n_freq > (1 << 20)) return fail(PRHF_EINVAL, "n_freq too large");
-    if (k.prof_stride < k.n_alt || (k.alt_stride != 0 && k.alt_stride < k.n_alt))
+    return PRHF_OK;
+}
+// whole_batch: n_points is the call's own
+int check_shape(const OperatorInputs& in, bool whole_batch) {
+    if (in.n_freq < 1 || in.n_prof < 0 || in.n_alt < 1 || (whole_batch && in.n_points < 1)) return fail(PRHF_EINVAL, "bad shape");
+    if (in.n_alt > kMaxAltTall)
+        return fail(PRHF_EINVAL, "n_alt %lld exceeds the limit of %lld levels", (long long)in.n_alt, kMaxAltTall);
+    if (in.n_freq > (1 << 20)) return fail(PRHF_EINVAL, "n_freq too large");
+    if (in.prof_stride < in.n_alt || (in.alt_stride != 0 && in.alt_stride < in.n_alt))
         return fail(PRHF_EINVAL, "row stride shorter than a row");
-    if (k.n_segs < 1 || k.n_segs > PRHF_MAX_SEGMENTS)
-        return fail(PRHF_EINVAL, "1..%d segments per launch", PRHF_MAX_SEGMENTS);
-    if (k.flags & ~(PRHF_FLAG_DEVICE_PTRS | PRHF_FLAG_ASYNC | PRHF_FLAG_GRID_STABLE | PRHF_FLAG_SHARED_FIELD))
+    return PRHF_OK;
+}
+int check_flags(const OperatorInputs& in) {
+    if (in.flags & ~(PRHF_FLAG_DEVICE_PTRS | PRHF_FLAG_ASYNC | PRHF_FLAG_GRID_STABLE | PRHF_FLAG_SHARED_FIELD))
         return fail(PRHF_EINVAL, "unknown flag bits");
-    if ((k.flags & PRHF_FLAG_ASYNC) && !k.dev) return fail(PRHF_EINVAL, "PRHF_FLAG_ASYNC needs device pointers");
-    // (A sounder frequency that is not a positive finite number gives a NaN column, host and device buffers alike:
-    //  freq_table_kernel / pair_freq.  The reference returns NaN for 0 and NaN, and something meaningless for f < 0.)
-    // The stretched grid must not decrease (smooth_nonuniform_grid never does): the top-segment search of the main
-    // loop relies on it.  Checked here for host buffers; device-resident grids are the caller's.
-    // (a stable host grid that is cached already was checked when it was uploaded)
-    const bool grid_known = !k.dev && (k.flags & PRHF_FLAG_GRID_STABLE) && find_host_grid(k.c, k.mult, k.mult_len);
-    if (!k.dev && !grid_known) {
-        const long long bad = first_decreasing_grid_entry(k.mult, k.mult_len, k.segs, k.n_segs);
-        if (bad >= 0) return fail(PRHF_EINVAL, "multiplier[%lld] decreases: the stretched grid must be non-decreasing", bad);
-    }
+    if ((in.flags & PRHF_FLAG_ASYNC) && !in.dev()) return fail(PRHF_EINVAL, "PRHF_FLAG_ASYNC needs device pointers");
+    return PRHF_OK;
+}
+// The stretched grid of a host-buffer call must not decrease (smooth_nonuniform_grid never does): the top-segment search
+// of the main loop relies on it.  Device-resident grids are the caller's.
+int check_grid(const double* mult, int64_t mult_len, const prhf_segment* segs, int32_t n_segs) {
+    const long long bad = first_decreasing_grid_entry(mult, mult_len, segs, n_segs);
+    if (bad >= 0) return fail(PRHF_EINVAL, "multiplier[%lld] decreases: the stretched grid must be non-decreasing", bad);
     return PRHF_OK;
 }
 
-// Profiles of more levels than LDS holds are staged in global memory and take the generic loop (vfo_tall_kernel):
-// no main loop, no candidate list, no short-grid kernels - the same values as any profile that leaves those paths.
-// Decided once the highest density peak of the launch is known: only the bottomside is staged, and a column of 2 500
-// levels at 0.25 km has its peak near level 900.  The peak index is np.argmax's, the first NaN ranking highest -
-// stage_profile's rule.  When every bottomside fits, the LDS kernels run with their staged arrays sized for that
-// peak (KArgs::lds_levels).
-int decide_tall(const Call& k, bool& tall, long long& lds_levels) {
-    prhf_ctx* c = k.c;
-    tall = k.n_alt > kMaxAlt;
-    lds_levels = k.n_alt;
-    if (!(tall && k.n_prof > 0 && c->knobs.trim_lds != 0)) return PRHF_OK;
+int check_arguments(const Call& k) {
+    PRHF_TRY(check_arrays(k.c, k, k.segs && (k.out || k.post)));
+    if (k.post && (!k.post->vh_obs || (!k.post->residual && !k.post->cost)))
+        return fail(PRHF_EINVAL, "null array pointer");
+    PRHF_TRY(check_shape(k, false));
+    if (k.n_segs < 1 || k.n_segs > PRHF_MAX_SEGMENTS)
+        return fail(PRHF_EINVAL, "1..%d segments per launch", PRHF_MAX_SEGMENTS);
+    PRHF_TRY(check_flags(k));
+    // (A sounder frequency that is not a positive finite number gives a NaN column, host and device buffers alike:
+    //  freq_table_kernel / pair_freq.  The reference returns NaN for 0 and NaN, and something meaningless for f < 0.)
+    // (a stable host grid that is cached already was checked when it was uploaded)
+    const bool grid_known = !k.dev() && (k.flags & PRHF_FLAG_GRID_STABLE) && find_host_grid(k.c, k.mult, k.mult_len);
+    if (!k.dev() && !grid_known) PRHF_TRY(check_grid(k.mult, k.mult_len, k.segs, k.n_segs));
+    return PRHF_OK;
+}
+
+// The highest density peak of the launch (np.argmax's rule, the first NaN ranking highest - stage_profile's): a host
+// scan, or the peak pre-pass and one synchronisation.  The caller has entered the device.
+int highest_peak(prhf_ctx* c, const double* den, int64_t n_prof, int64_t n_alt, int64_t prof_stride, bool dev, long long* out) {
     long long max_peak = 0;
-    if (k.dev) {
+    if (dev) {
         HIP_TRY(hipMemsetAsync(c->d_status + kWordPeak, 0, sizeof(unsigned), c->stream));
-        HIP_TRY(prhf::launch_peak_levels(k.den, k.n_prof, k.n_alt, k.prof_stride, c->d_status + kWordPeak, c->stream));
+        HIP_TRY(prhf::launch_peak_levels(den, n_prof, n_alt, prof_stride, c->d_status + kWordPeak, c->stream));
         unsigned peak = 0;
         HIP_TRY(hipMemcpyAsync(&peak, c->d_status + kWordPeak, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
         max_peak = peak;
     } else {
-        for (int64_t p = 0; p < k.n_prof; ++p) {
-            const double* d = k.den + (size_t)p * k.prof_stride;
+        for (int64_t p = 0; p < n_prof; ++p) {
+            const double* d = den + (size_t)p * prof_stride;
             double bv = -HUGE_VAL;
             long long bi = 0;
-            for (int64_t i = 0; i < k.n_alt; ++i) {
+            for (int64_t i = 0; i < n_alt; ++i) {
                 const double key = (d[i] != d[i]) ? HUGE_VAL : d[i];
                 if (key > bv) { bv = key; bi = i; }
             }
             max_peak = std::max(max_peak, bi);
         }
     }
+    *out = max_peak;
+    return PRHF_OK;
+}
+
+// Profiles of more levels than LDS holds are staged in global memory and take the generic loop (vfo_tall_kernel):
+// no main loop, no candidate list, no short-grid kernels - the same values as any profile that leaves those paths.
+// Decided once the highest density peak of the launch is known: only the bottomside is staged, and a column of 2 500
+// levels at 0.25 km has its peak near level 900 (highest_peak).  When every bottomside fits, the LDS kernels run with
+// their staged arrays sized for that peak (KArgs::lds_levels).
+int decide_tall(const Call& k, bool& tall, long long& lds_levels) {
+    tall = k.n_alt > kMaxAlt;
+    lds_levels = k.n_alt;
+    if (!(tall && k.n_prof > 0 && k.c->knobs.trim_lds != 0)) return PRHF_OK;
+    long long max_peak = 0;
+    PRHF_TRY(highest_peak(k.c, k.den, k.n_prof, k.n_alt, k.prof_stride, k.dev(), &max_peak));
     if (max_peak + 1 <= kMaxAlt) {
         tall = false;
         lds_levels = max_peak + 1;
@@ -347,21 +487,16 @@ int stage_inputs(Call& k, const LaunchPlan& pl, prhf::KArgs& a) {
     a.altmin = static_cast<double*>(c->altmin.p);
     a.status = c->h_status_dev;
 
-    const size_t row_bytes = (size_t)n_alt * 8;
     const size_t out_elems = k.out_elems = (size_t)pl.out_rows * (size_t)n_freq;
-    if (k.dev) {
+    ResidualBlock one = {};                    // host buffers: the residual stage's arrays behind the result rows
+    ManyBlock many = {};
+    if (k.dev()) {
         a.freq = k.freq; a.den = k.den; a.bmag = k.bmag; a.bpsi = k.bpsi; a.alt = k.alt; a.mult = k.mult;
         a.out = k.out;
         a.prof_stride = k.prof_stride;
-        a.field_stride = k.shared_field ? 0 : k.prof_stride;
+        a.field_stride = k.shared_field() ? 0 : k.prof_stride;
         a.alt_stride = k.alt_stride;
     } else {
-        const size_t n_alt_rows = k.alt_stride ? (size_t)n_prof : 1;
-        const size_t n_field_rows = k.shared_field ? 1 : (size_t)n_prof;
-        size_t post_elems = k.post ? (size_t)n_freq + out_elems + (size_t)n_prof : 0;
-        if (k.post && k.post->n_iono)      // observations, residual rows, costs, best and best_cost, ionogram_of_row (int32)
-            post_elems = (size_t)k.post->n_iono * ((size_t)n_freq + 2) + (k.post->residual ? out_elems : 0) +
-                         k.post->cost_elems(n_prof) + ((size_t)n_prof + 1) / 2;
         // a stable host grid lives in a device buffer of its own, uploaded on first sight
         if (k.flags & PRHF_FLAG_GRID_STABLE) {
             k.grid = find_host_grid(c, k.mult, mult_len);
@@ -376,19 +511,35 @@ int stage_inputs(Call& k, const LaunchPlan& pl, prhf::KArgs& a) {
                 ++c->n_host_grids;
             }
         }
-        const size_t mult_arena = k.grid ? 0 : (size_t)mult_len;
-        const size_t elems = (size_t)n_freq + ((size_t)n_prof + 2 * n_field_rows) * n_alt + n_alt_rows * n_alt +
-                             mult_arena + out_elems + post_elems;
-        if ((rc = ensure(c, c->arena, elems * 8)) != PRHF_OK) return rc;
-        double* base = static_cast<double*>(c->arena.p);
-        double* d_freq = base;
-        double* d_den = d_freq + n_freq;
-        double* d_bmag = d_den + (size_t)n_prof * n_alt;
-        double* d_bpsi = d_bmag + n_field_rows * n_alt;
-        double* d_alt = d_bpsi + n_field_rows * n_alt;
-        double* d_mult = d_alt + n_alt_rows * n_alt;
-        double* d_out = k.d_out = d_mult + mult_arena;
-        const size_t in_elems = k.in_elems = (size_t)(d_out - base);
+        // The arena: the inputs, packed (operator_block), the result rows, the residual stage's block
+        const OperatorShape shape = k.shape(k.grid ? 0 : (size_t)mult_len);
+        OperatorBlock b;
+        auto inputs = [&](Stager& st) {
+            b = operator_block(st, shape);
+            st.put(b.freq, k.freq, shape.n_freq);
+            st.put_rows(b.den, k.den, shape.n_alt, shape.n_prof, k.prof_stride);
+            if (n_prof > 0) st.put_rows(b.bmag, k.bmag, shape.n_alt, shape.field_rows, k.prof_stride);
+            if (n_prof > 0) st.put_rows(b.bpsi, k.bpsi, shape.n_alt, shape.field_rows, k.prof_stride);
+            if (k.alt_stride) st.put_rows(b.alt, k.alt, shape.n_alt, shape.n_prof, k.alt_stride);
+            else st.put(b.alt, k.alt, shape.n_alt);
+            if (!k.grid) st.put(b.mult, k.mult, shape.mult_len);
+            k.in_elems = st.used() / 8;
+        };
+        auto results = [&](Carver& st) {
+            k.d_out = st.take<double>(out_elems);
+            if (k.post && k.post->n_iono)
+                many = many_block(st, (size_t)k.post->n_iono, (size_t)n_freq, (size_t)n_prof, k.post->residual ? out_elems : 0,
+                                  k.post->ionogram_of_row != nullptr);
+            else if (k.post) one = residual_block(st, (size_t)n_freq, out_elems, (size_t)n_prof);
+        };
+        Stager sizing(c, nullptr);
+        inputs(sizing);
+        results(sizing);
+        PRHF_TRY(ensure(c, c->arena, sizing.used()));
+        double* const base = static_cast<double*>(c->arena.p);
+        const size_t in_elems = k.in_elems;
+        void* pack = nullptr;                  // the per-array route: a copy per array, rows as rows
+        bool direct = false;
         if (in_elems * 8 <= kPackBytes && c->h_pack) {
             // A small call (the reference's usual one: a single profile): six separate uploads from pageable
             // memory cost more than the kernel.  Pack the inputs in the arena's own order into a pinned
@@ -404,45 +555,20 @@ int stage_inputs(Call& k, const LaunchPlan& pl, prhf::KArgs& a) {
             // must be idle: host-buffer calls synchronise before they return, but an asynchronous device-pointer call -
             // or a launch on a stream the context borrowed before - may still be using it; then the staged copy, which is
             // ordered by the stream, is taken.
-            bool direct = c->large_bar && c->knobs.direct_upload != 0 && in_elems * 8 <= kDirectBytes &&
-                          hipStreamQuery(c->stream) == hipSuccess && (!c->timed || hipEventQuery(c->end_ev()) == hipSuccess);
+            direct = c->large_bar && c->knobs.direct_upload != 0 && in_elems * 8 <= kDirectBytes &&
+                     hipStreamQuery(c->stream) == hipSuccess && (!c->timed || hipEventQuery(c->end_ev()) == hipSuccess);
             (void)hipGetLastError();               // (hipErrorNotReady from the two queries is not an error)
-            double* h = direct ? base : c->h_pack;
-            std::memcpy(h + (d_freq - base), k.freq, (size_t)n_freq * 8);
-            for (int64_t p = 0; p < n_prof; ++p) {
-                std::memcpy(h + (d_den - base) + (size_t)p * n_alt, k.den + (size_t)p * k.prof_stride, row_bytes);
-                if (!k.shared_field || p == 0) {
-                    std::memcpy(h + (d_bmag - base) + (size_t)p * n_alt, k.bmag + (size_t)p * k.prof_stride, row_bytes);
-                    std::memcpy(h + (d_bpsi - base) + (size_t)p * n_alt, k.bpsi + (size_t)p * k.prof_stride, row_bytes);
-                }
-                if (k.alt_stride) std::memcpy(h + (d_alt - base) + (size_t)p * n_alt, k.alt + (size_t)p * k.alt_stride, row_bytes);
-            }
-            if (!k.alt_stride) std::memcpy(h + (d_alt - base), k.alt, row_bytes);
-            if (!k.grid) std::memcpy(h + (d_mult - base), k.mult, (size_t)mult_len * 8);
-            if (direct) _mm_sfence();
-            else HIP_TRY(hipMemcpyAsync(base, h, in_elems * 8, hipMemcpyHostToDevice, c->stream));
-        } else {
-            HIP_TRY(hipMemcpyAsync(d_freq, k.freq, (size_t)n_freq * 8, hipMemcpyHostToDevice, c->stream));
-            if (!k.grid) HIP_TRY(hipMemcpyAsync(d_mult, k.mult, (size_t)mult_len * 8, hipMemcpyHostToDevice, c->stream));
-            if (n_prof > 0) {
-                HIP_TRY(hipMemcpy2DAsync(d_den, row_bytes, k.den, (size_t)k.prof_stride * 8, row_bytes, (size_t)n_prof,
-                                         hipMemcpyHostToDevice, c->stream));
-                HIP_TRY(hipMemcpy2DAsync(d_bmag, row_bytes, k.bmag, (size_t)k.prof_stride * 8, row_bytes, n_field_rows,
-                                         hipMemcpyHostToDevice, c->stream));
-                HIP_TRY(hipMemcpy2DAsync(d_bpsi, row_bytes, k.bpsi, (size_t)k.prof_stride * 8, row_bytes, n_field_rows,
-                                         hipMemcpyHostToDevice, c->stream));
-            }
-            if (k.alt_stride) {
-                if (n_prof > 0)
-                    HIP_TRY(hipMemcpy2DAsync(d_alt, row_bytes, k.alt, (size_t)k.alt_stride * 8, row_bytes, (size_t)n_prof,
-                                             hipMemcpyHostToDevice, c->stream));
-            } else {
-                HIP_TRY(hipMemcpyAsync(d_alt, k.alt, row_bytes, hipMemcpyHostToDevice, c->stream));
-            }
+            pack = direct ? base : c->h_pack;
         }
-        a.freq = d_freq; a.den = d_den; a.bmag = d_bmag; a.bpsi = d_bpsi; a.alt = d_alt;
-        a.mult = k.grid ? static_cast<const double*>(k.grid->mult.p) : d_mult;
-        a.out = d_out;
+        Stager st(c, base, pack);
+        inputs(st);
+        HIP_TRY(st.error());
+        if (direct) _mm_sfence();
+        else if (pack) HIP_TRY(upload(c, base, pack, in_elems * 8));
+        results(st);
+        a.freq = b.freq; a.den = b.den; a.bmag = b.bmag; a.bpsi = b.bpsi; a.alt = b.alt;
+        a.mult = k.grid ? static_cast<const double*>(k.grid->mult.p) : b.mult;
+        double* const d_out = a.out = k.d_out;
         // rows that no segment covers must come back as NaN, not as whatever the arena held (all-ones bytes = NaN)
         long long covered = 0;
         for (int i = 0; i < k.n_segs; ++i) covered += k.segs[i].prof_end - k.segs[i].prof_begin;
@@ -458,47 +584,27 @@ int stage_inputs(Call& k, const LaunchPlan& pl, prhf::KArgs& a) {
         }
         if (covered < pl.out_rows && out_elems) HIP_TRY(hipMemsetAsync(d_out, 0xFF, out_elems * 8, c->stream));
         a.prof_stride = n_alt;
-        a.field_stride = k.shared_field ? 0 : n_alt;
+        a.field_stride = k.shared_field() ? 0 : n_alt;
         a.alt_stride = k.alt_stride ? n_alt : 0;
     }
 
     k.vh_dev = a.out;
-    if (k.dev && k.post && !k.out) {           // caller does not want the modeled trace: keep it in scratch
+    if (k.dev() && k.post && !k.out) {           // caller does not want the modeled trace: keep it in scratch
         if ((rc = ensure(c, c->arena, out_elems * 8)) != PRHF_OK) return rc;
         k.vh_dev = a.out = static_cast<double*>(c->arena.p);
     }
-    k.d_obs = k.post ? k.post->vh_obs : nullptr;
-    k.d_res = k.post ? k.post->residual : nullptr;
-    k.d_cost = k.post ? k.post->cost : nullptr;
-    k.d_ion = k.post ? k.post->ionogram_of_row : nullptr;
-    k.d_best = k.post ? k.post->best : nullptr;
-    k.d_best_cost = k.post ? k.post->best_cost : nullptr;
-    if (k.post && !k.dev && !k.post->n_iono) {
-        double* p0 = k.d_out + out_elems;
-        HIP_TRY(hipMemcpyAsync(p0, k.post->vh_obs, (size_t)n_freq * 8, hipMemcpyHostToDevice, c->stream));
-        k.d_obs = p0;
-        k.d_res = k.post->residual ? p0 + n_freq : nullptr;
-        k.d_cost = k.post->cost ? p0 + n_freq + out_elems : nullptr;
-    } else if (k.post && !k.dev) {
-        const Residual& r = *k.post;
-        const size_t obs_elems = (size_t)r.n_iono * (size_t)n_freq;
-        double* p0 = k.d_out + out_elems;
-        HIP_TRY(hipMemcpyAsync(p0, r.vh_obs, obs_elems * 8, hipMemcpyHostToDevice, c->stream));
-        k.d_obs = p0;
-        p0 += obs_elems;
-        k.d_res = r.residual ? p0 : nullptr;
-        if (r.residual) p0 += out_elems;
-        k.d_cost = p0;
-        p0 += r.cost_elems(n_prof);
-        k.d_best_cost = p0;
-        p0 += r.n_iono;
-        k.d_best = reinterpret_cast<int64_t*>(p0);
-        p0 += r.n_iono;
-        if (r.ionogram_of_row && n_prof > 0) {
-            HIP_TRY(hipMemcpyAsync(p0, r.ionogram_of_row, (size_t)n_prof * 4, hipMemcpyHostToDevice, c->stream));
-            k.d_ion = reinterpret_cast<const int32_t*>(p0);
-        }
-    }
+    // the residual stage's arrays: the caller's own on the device, else the arena's block behind the result rows
+    if (!k.post) return PRHF_OK;
+    const Residual& r = *k.post;
+    k.stage = {mut(r.vh_obs), r.residual, r.cost, r.best_cost, r.best, const_cast<int32_t*>(r.ionogram_of_row)};
+    if (k.dev()) return PRHF_OK;
+    const bool rows_named = r.n_iono && r.ionogram_of_row && n_prof > 0;
+    if (r.n_iono) k.stage = many;
+    else k.stage = {one.obs, one.residual, r.cost ? one.cost : nullptr, nullptr, nullptr, nullptr};
+    if (!r.residual) k.stage.residual = nullptr;
+    if (!rows_named) k.stage.ionogram_of_row = const_cast<int32_t*>(r.ionogram_of_row);
+    HIP_TRY(upload(c, k.stage.obs, r.vh_obs, (size_t)(r.n_iono ? r.n_iono : 1) * (size_t)n_freq * 8));
+    if (rows_named) HIP_TRY(upload(c, many.ionogram_of_row, r.ionogram_of_row, (size_t)n_prof * 4));
     return PRHF_OK;
 }
 
@@ -527,7 +633,7 @@ int update_tables(Call& k, const LaunchPlan& pl, prhf::KArgs& a) {
         }
         a.pairs = static_cast<const double*>(k.grid->pairs.p);
     } else {
-        const bool stable = k.dev && (k.flags & PRHF_FLAG_GRID_STABLE) != 0;
+        const bool stable = k.dev() && (k.flags & PRHF_FLAG_GRID_STABLE) != 0;
         if (!(stable && c->pairs.p && c->pairs_src == a.mult && c->pairs_len == k.mult_len && same_pieces(c->pairs_pieces))) {
             c->pairs_src = nullptr;
             if ((rc = build_pair_table(c, c->pairs, a.mult, k.mult_len, pl)) != PRHF_OK) return rc;
@@ -697,8 +803,8 @@ int launch_short_kind(prhf_ctx* c, const LaunchPlan& pl, const ShortKind& sk, co
 }
 
 // The many-ionogram residual stage on device arrays: masked residuals and costs, then every ionogram's winner
-int launch_many(prhf_ctx* c, const double* vh_model, int64_t n_rows, const double* vh_obs, int64_t n_iono, int64_t n_freq,
-                const int32_t* ionogram_of_row, double* residual, double* cost, int64_t* best, double* best_cost) {
+hipError_t launch_many(prhf_ctx* c, const double* vh_model, int64_t n_rows, const double* vh_obs, int64_t n_iono,
+                       int64_t n_freq, const int32_t* ionogram_of_row, double* residual, double* cost, int64_t* best, double* best_cost) {
     prhf::ResidualManyArgs m;
     m.vh_model = vh_model;
     m.vh_obs = vh_obs;
@@ -710,10 +816,10 @@ int launch_many(prhf_ctx* c, const double* vh_model, int64_t n_rows, const doubl
     m.items_per_wave = PRHF_MANY_ITEMS_PER_WAVE;
     m.residual = residual;
     m.cost = cost;
-    HIP_TRY(prhf::launch_residual_many(m, c->stream));
-    HIP_TRY(prhf::launch_residual_best(cost, ionogram_of_row, n_rows, (int)n_iono, reinterpret_cast<long long*>(best), best_cost,
-                                       c->stream));
-    return PRHF_OK;
+    const hipError_t e = prhf::launch_residual_many(m, c->stream);
+    if (e != hipSuccess) return e;
+    return prhf::launch_residual_best(cost, ionogram_of_row, n_rows, (int)n_iono, reinterpret_cast<long long*>(best), best_cost,
+                                      c->stream);
 }
 
 // What the two many-ionogram entries ask of their arguments, before any device is touched.  freq_mhz: the fused entry's
@@ -782,26 +888,26 @@ int download_and_sync(Call& k) {
     const size_t out_elems = k.out_elems;
     // small results come back through the pinned buffer too (its upper half; the inputs of a call this small
     // fit the lower one) and are handed over after the synchronisation below
-    const bool out_via_pack = !k.out_direct && !k.dev && k.out && out_elems && c->h_pack && out_elems * 8 <= kPackBytes / 4 &&
+    const bool out_via_pack = !k.out_direct && !k.dev() && k.out && out_elems && c->h_pack && out_elems * 8 <= kPackBytes / 4 &&
                               k.in_elems * 8 <= kPackBytes / 2;
     double* h_out = c->h_pack ? c->h_pack + kPackBytes / 16 : nullptr;       // doubles: byte offset kPackBytes / 2
     if (k.out_direct) {
         // (written by the kernel itself)
     } else if (out_via_pack)
         HIP_TRY(hipMemcpyAsync(h_out, k.d_out, out_elems * 8, hipMemcpyDeviceToHost, c->stream));
-    else if (!k.dev && out_elems && k.out)
+    else if (!k.dev() && out_elems && k.out)
         HIP_TRY(hipMemcpyAsync(k.out, k.d_out, out_elems * 8, hipMemcpyDeviceToHost, c->stream));
-    if (!k.dev && k.post) {
+    if (!k.dev() && k.post) {
         if (k.post->residual)
-            HIP_TRY(hipMemcpyAsync(k.post->residual, k.d_res, out_elems * 8, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipMemcpyAsync(k.post->residual, k.stage.residual, out_elems * 8, hipMemcpyDeviceToHost, c->stream));
         if (k.post->cost && !k.post->n_iono)
-            HIP_TRY(hipMemcpyAsync(k.post->cost, k.d_cost, (size_t)k.n_prof * 8, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipMemcpyAsync(k.post->cost, k.stage.cost, (size_t)k.n_prof * 8, hipMemcpyDeviceToHost, c->stream));
         if (k.post->n_iono) {
             if (k.post->cost_elems(k.n_prof))
-                HIP_TRY(hipMemcpyAsync(k.post->cost, k.d_cost, k.post->cost_elems(k.n_prof) * 8, hipMemcpyDeviceToHost,
+                HIP_TRY(hipMemcpyAsync(k.post->cost, k.stage.cost, k.post->cost_elems(k.n_prof) * 8, hipMemcpyDeviceToHost,
                                        c->stream));
-            HIP_TRY(hipMemcpyAsync(k.post->best, k.d_best, (size_t)k.post->n_iono * 8, hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipMemcpyAsync(k.post->best_cost, k.d_best_cost, (size_t)k.post->n_iono * 8, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipMemcpyAsync(k.post->best, k.stage.best, (size_t)k.post->n_iono * 8, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipMemcpyAsync(k.post->best_cost, k.stage.best_cost, (size_t)k.post->n_iono * 8, hipMemcpyDeviceToHost, c->stream));
         }
     }
     if (k.flags & PRHF_FLAG_ASYNC) return PRHF_OK;
@@ -812,12 +918,12 @@ int download_and_sync(Call& k) {
 
 // Every prhf_vfo_* call: check, decide where the profiles are staged, plan (plan_launch, prhf_plan.h), then carry the
 // plan out step by step.  The steps above enqueue on the context's stream in the order they are called here.
-int run(prhf_ctx* c, const double* freq, int64_t n_freq, const double* den, const double* bmag,
-        const double* bpsi, const double* alt, int64_t n_prof, int64_t n_alt, int64_t prof_stride,
-        int64_t alt_stride, const double* mult, int64_t mult_len, const prhf_segment* segs, int32_t n_segs,
-        double* out, uint32_t flags, const Residual* post = nullptr) {
-    Call k = {c, freq, den, bmag, bpsi, alt, mult, n_freq, n_prof, n_alt, prof_stride, alt_stride, mult_len, segs, n_segs,
-              out, flags, post, (flags & PRHF_FLAG_DEVICE_PTRS) != 0, (flags & PRHF_FLAG_SHARED_FIELD) != 0};
+int run(prhf_ctx* c, const OperatorInputs& in, const OperatorWork& w) {
+    Call k = {in, w, c};
+    const int64_t n_freq = in.n_freq, n_prof = in.n_prof, n_alt = in.n_alt, mult_len = w.mult_len;
+    const prhf_segment* const segs = w.segs;
+    const int32_t n_segs = w.n_segs;
+    const Residual* const post = w.post;
     int rc;
     if ((rc = check_arguments(k)) != PRHF_OK) return rc;
     ENTER_DEVICE(c->device);
@@ -845,7 +951,7 @@ int run(prhf_ctx* c, const double* freq, int64_t n_freq, const double* den, cons
 
     // (a synchronous host-buffer call may go untimed - option `timing`: nothing is left on the stream when it returns,
     //  so no later launch or stream switch needs its end event either)
-    const bool timed_launch = k.dev || c->knobs.timing != 0;
+    const bool timed_launch = k.dev() || c->knobs.timing != 0;
     if (timed_launch) HIP_TRY(hipEventRecord(c->begin_ev(), c->stream));
     if ((rc = update_tables(k, pl, a)) != PRHF_OK) return rc;
 #ifdef PRHF_TRACE
@@ -878,9 +984,8 @@ int run(prhf_ctx* c, const double* freq, int64_t n_freq, const double* den, cons
     }
 #endif
     if (post && post->n_iono) {
-        if ((rc = launch_many(c, k.vh_dev, n_prof, k.d_obs, post->n_iono, n_freq, k.d_ion, k.d_res, k.d_cost, k.d_best,
-                              k.d_best_cost)) != PRHF_OK) return rc;
-    } else if (post) HIP_TRY(prhf::launch_residual(k.vh_dev, k.d_obs, n_prof, (int)n_freq, k.d_res, k.d_cost, c->stream));
+        HIP_TRY(launch_many(c, k.vh_dev, n_prof, k.stage.obs, post->n_iono, n_freq, k.stage.ionogram_of_row, k.stage.residual, k.stage.cost, k.stage.best, k.stage.best_cost));
+    } else if (post) HIP_TRY(prhf::launch_residual(k.vh_dev, k.stage.obs, n_prof, (int)n_freq, k.stage.residual, k.stage.cost, c->stream));
     if (timed_launch) {
         HIP_TRY(hipEventRecord(c->pending_end_ev(), c->stream));
         c->mark_timed();
@@ -896,33 +1001,28 @@ int run(prhf_ctx* c, const double* freq, int64_t n_freq, const double* den, cons
 // staged rows as device-resident input), and slab k's result rows travel back (`down_stream`) while slab k + 1 runs.
 // A growing slab size keeps the first kernel's wait short and every later upload behind a kernel that is about as long.
 // Values do not depend on the cut: a launch's rows do not depend on their neighbours (tests/test_gpu_full_size.py).
-int run_host_slabs(prhf_ctx* c, const double* freq, int64_t n_freq, const double* den, const double* bmag,
-                   const double* bpsi, const double* alt, int64_t n_prof, int64_t n_alt, int64_t prof_stride,
-                   int64_t alt_stride, const double* mult, int32_t n_points, int32_t mode, double* out, uint32_t flags) {
-    const bool shared_field = (flags & PRHF_FLAG_SHARED_FIELD) != 0;
+int run_host_slabs(prhf_ctx* c, const OperatorInputs& in, double* out) {
+    const int64_t n_freq = in.n_freq, n_prof = in.n_prof, n_alt = in.n_alt, prof_stride = in.prof_stride, alt_stride = in.alt_stride;
+    const int32_t n_points = in.n_points;
+    const bool shared_field = in.shared_field();
     ENTER_DEVICE(c->device);
-    const size_t n_alt_rows = alt_stride ? (size_t)n_prof : 1, n_field_rows = shared_field ? 1 : (size_t)n_prof;
     const size_t row_bytes = (size_t)n_alt * 8;
-    const size_t elems = (size_t)n_freq + ((size_t)n_prof + 2 * n_field_rows + n_alt_rows) * (size_t)n_alt + (size_t)n_points +
-                         (size_t)n_prof * (size_t)n_freq;
     int rc;
-    if ((rc = ensure(c, c->arena, elems * 8)) != PRHF_OK) return rc;
-    double* d_freq = static_cast<double*>(c->arena.p);
-    double* d_den = d_freq + n_freq;
-    double* d_bmag = d_den + (size_t)n_prof * n_alt;
-    double* d_bpsi = d_bmag + n_field_rows * n_alt;
-    double* d_alt = d_bpsi + n_field_rows * n_alt;
-    double* d_mult = d_alt + n_alt_rows * n_alt;
-    double* d_out = d_mult + n_points;
+    OperatorBlock b;
+    double* d_out = nullptr;
+    PRHF_TRY(carve(c, c->arena, [&](Stager& k) {
+        b = operator_block(k, in.shape((size_t)n_points));
+        d_out = k.take<double>((size_t)n_prof * (size_t)n_freq);
+    }));
     // the arena may still be read by an earlier asynchronous launch of this context: the uploads wait for it
     HIP_TRY(hipEventRecord(c->slab_free, c->stream));
     HIP_TRY(hipStreamWaitEvent(c->up_stream, c->slab_free, 0));
-    HIP_TRY(hipMemcpyAsync(d_freq, freq, (size_t)n_freq * 8, hipMemcpyHostToDevice, c->up_stream));
-    HIP_TRY(hipMemcpyAsync(d_mult, mult, (size_t)n_points * 8, hipMemcpyHostToDevice, c->up_stream));
-    if (!alt_stride) HIP_TRY(hipMemcpyAsync(d_alt, alt, row_bytes, hipMemcpyHostToDevice, c->up_stream));
+    HIP_TRY(hipMemcpyAsync(b.freq, in.freq, (size_t)n_freq * 8, hipMemcpyHostToDevice, c->up_stream));
+    HIP_TRY(hipMemcpyAsync(b.mult, in.mult, (size_t)n_points * 8, hipMemcpyHostToDevice, c->up_stream));
+    if (!alt_stride) HIP_TRY(hipMemcpyAsync(b.alt, in.alt, row_bytes, hipMemcpyHostToDevice, c->up_stream));
     if (shared_field) {
-        HIP_TRY(hipMemcpyAsync(d_bmag, bmag, row_bytes, hipMemcpyHostToDevice, c->up_stream));
-        HIP_TRY(hipMemcpyAsync(d_bpsi, bpsi, row_bytes, hipMemcpyHostToDevice, c->up_stream));
+        HIP_TRY(hipMemcpyAsync(b.bmag, in.bmag, row_bytes, hipMemcpyHostToDevice, c->up_stream));
+        HIP_TRY(hipMemcpyAsync(b.bpsi, in.bpsi, row_bytes, hipMemcpyHostToDevice, c->up_stream));
     }
     const int n_slabs = 3;
     const int64_t cut[4] = {0, std::max<int64_t>(1, n_prof / 10), std::max<int64_t>(2, (n_prof * 4) / 10), n_prof};
@@ -935,24 +1035,20 @@ int run_host_slabs(prhf_ctx* c, const double* freq, int64_t n_freq, const double
             return hipMemcpy2DAsync(dst + (size_t)p0 * n_alt, row_bytes, src + (size_t)p0 * stride, (size_t)stride * 8, row_bytes,
                                     (size_t)rows, hipMemcpyHostToDevice, c->up_stream);
         };
-        HIP_TRY(up2d(d_den, den, prof_stride));
+        HIP_TRY(up2d(b.den, in.den, prof_stride));
         if (!shared_field) {
-            HIP_TRY(up2d(d_bmag, bmag, prof_stride));
-            HIP_TRY(up2d(d_bpsi, bpsi, prof_stride));
+            HIP_TRY(up2d(b.bmag, in.bmag, prof_stride));
+            HIP_TRY(up2d(b.bpsi, in.bpsi, prof_stride));
         }
-        if (alt_stride) HIP_TRY(up2d(d_alt, alt, alt_stride));
+        if (alt_stride) HIP_TRY(up2d(b.alt, in.alt, alt_stride));
         HIP_TRY(hipEventRecord(c->slab_up[k], c->up_stream));
         HIP_TRY(hipStreamWaitEvent(c->stream, c->slab_up[k], 0));
-        prhf_segment seg;
-        seg.prof_begin = 0;
-        seg.prof_end = rows;
-        seg.mode = mode;
-        seg.n_points = n_points;
-        seg.mult_offset = 0;
-        seg.out_offset = 0;
-        rc = run(c, d_freq, n_freq, d_den + (size_t)p0 * n_alt, shared_field ? d_bmag : d_bmag + (size_t)p0 * n_alt,
-                 shared_field ? d_bpsi : d_bpsi + (size_t)p0 * n_alt, alt_stride ? d_alt + (size_t)p0 * n_alt : d_alt, rows, n_alt,
-                 n_alt, alt_stride ? n_alt : 0, d_mult, n_points, &seg, 1, d_out + (size_t)p0 * n_freq, dev_flags);
+        const size_t at = (size_t)p0 * n_alt;
+        const prhf_segment seg = whole_batch(rows, in.mode, n_points);
+        const size_t field_at = shared_field ? 0 : at, alt_at = alt_stride ? at : 0;
+        const OperatorInputs slab = {b.freq, n_freq, b.den + at, b.bmag + field_at, b.bpsi + field_at, b.alt + alt_at, rows, n_alt, n_alt,
+                                     alt_stride ? n_alt : 0, b.mult, n_points, in.mode, dev_flags};
+        rc = run(c, slab, OperatorWork{n_points, &seg, 1, d_out + (size_t)p0 * n_freq, nullptr});
         if (rc != PRHF_OK) { first_error = rc; break; }
         HIP_TRY(hipEventRecord(c->slab_done[k], c->stream));
         // the rows of the slab before this one go home while this one runs (issued here, behind this slab's upload:
@@ -1131,28 +1227,20 @@ int prhf_vfo_batch_f64(prhf_ctx* ctx, const double* freq_mhz, int64_t n_freq, co
                        const double* bmag, const double* bpsi, const double* alt, int64_t n_prof, int64_t n_alt,
                        int64_t prof_stride_elems, int64_t alt_stride_elems, const double* multiplier,
                        int32_t n_points, int32_t mode, double* vh_out, uint32_t flags) {
-    prhf_segment seg;
-    seg.prof_begin = 0;
-    seg.prof_end = n_prof;
-    seg.mode = mode;
-    seg.n_points = n_points;
-    seg.mult_offset = 0;
-    seg.out_offset = 0;
+    const OperatorInputs in{freq_mhz, n_freq, den, bmag, bpsi, alt, n_prof, n_alt, prof_stride_elems, alt_stride_elems,
+                            multiplier, n_points, mode, flags};
+    const prhf_segment seg = whole_batch(n_prof, mode, n_points);
     // a large batch from host buffers: in slabs, transfers beside the kernels (run_host_slabs).  The checks of run()
-    // that concern the whole call are made by its first slab; shapes it would refuse are left to it here too.
-    if (ctx && !(flags & PRHF_FLAG_DEVICE_PTRS) && ctx->knobs.host_slabs >= 3 && freq_mhz && den && bmag && bpsi && alt &&
-        multiplier && vh_out && n_freq >= 1 && n_alt >= 1 && n_points >= 1 && n_prof >= 64 &&
-        prof_stride_elems >= n_alt && (alt_stride_elems == 0 || alt_stride_elems >= n_alt) &&
-        (mode == PRHF_MODE_O || mode == PRHF_MODE_X) && !(flags & ~(PRHF_FLAG_GRID_STABLE | PRHF_FLAG_SHARED_FIELD)) &&
-        (size_t)n_prof * (size_t)n_alt * 24 >= kSlabMinBytes && n_alt <= kMaxAltTall && n_freq <= (1 << 20)) {
-        for (int64_t i = 1; i < n_points; ++i)
-            if (multiplier[i] < multiplier[i - 1])
-                return fail(PRHF_EINVAL, "multiplier[%lld] decreases: the stretched grid must be non-decreasing", (long long)i);
-        return run_host_slabs(ctx, freq_mhz, n_freq, den, bmag, bpsi, alt, n_prof, n_alt, prof_stride_elems, alt_stride_elems,
-                              multiplier, n_points, mode, vh_out, flags);
+    // that concern the whole call are made by its first slab; a call that a check part refuses is left to run(), which
+    // refuses it in its own order.
+    const bool large_host = ctx && !in.dev() && ctx->knobs.host_slabs >= 3 && n_prof >= 64 &&
+                            (size_t)n_prof * (size_t)n_alt * 24 >= kSlabMinBytes;
+    if (large_host && check_arrays(ctx, in, vh_out != nullptr) == PRHF_OK && check_shape(in, true) == PRHF_OK &&
+        (mode == PRHF_MODE_O || mode == PRHF_MODE_X) && check_flags(in) == PRHF_OK) {
+        PRHF_TRY(check_grid(multiplier, n_points, &seg, 1));
+        return run_host_slabs(ctx, in, vh_out);
     }
-    return run(ctx, freq_mhz, n_freq, den, bmag, bpsi, alt, n_prof, n_alt, prof_stride_elems, alt_stride_elems,
-               multiplier, n_points, &seg, 1, vh_out, flags);
+    return run(ctx, in, OperatorWork{n_points, &seg, 1, vh_out, nullptr});
 }
 
 int prhf_vfo_worklist_f64(prhf_ctx* ctx, const double* freq_mhz, int64_t n_freq, const double* den,
@@ -1160,8 +1248,9 @@ int prhf_vfo_worklist_f64(prhf_ctx* ctx, const double* freq_mhz, int64_t n_freq,
                           int64_t n_alt, int64_t prof_stride_elems, int64_t alt_stride_elems,
                           const double* multiplier, int64_t multiplier_len, const prhf_segment* segs,
                           int32_t n_segs, double* vh_out, uint32_t flags) {
-    return run(ctx, freq_mhz, n_freq, den, bmag, bpsi, alt, n_prof, n_alt, prof_stride_elems, alt_stride_elems,
-               multiplier, multiplier_len, segs, n_segs, vh_out, flags);
+    const OperatorInputs in{freq_mhz, n_freq, den, bmag, bpsi, alt, n_prof, n_alt, prof_stride_elems, alt_stride_elems,
+                            multiplier, 0, 0, flags};
+    return run(ctx, in, OperatorWork{multiplier_len, segs, n_segs, vh_out, nullptr});
 }
 
 }  // extern "C"
@@ -1171,74 +1260,7 @@ int prhf_vfo_worklist_f64(prhf_ctx* ctx, const double* freq_mhz, int64_t n_freq,
 
 namespace {
 
-// ---- The steps the tracer and derivative entry points are assembled from: checks, carve, stage, tail ----
-
-#define PRHF_TRY(expr)                     \
-    do {                                   \
-        const int rc_ = (expr);            \
-        if (rc_ != PRHF_OK) return rc_;    \
-    } while (0)
-
-hipError_t upload(prhf_ctx* c, void* dst, const void* src, size_t bytes) {
-    return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream);
-}
-hipError_t download(prhf_ctx* c, void* dst, const void* src, size_t bytes) {
-    return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream);
-}
-// rows of row_elems doubles, `stride` elements apart at the source (a single row: as it stands), packed at dst
-hipError_t upload_rows(prhf_ctx* c, double* dst, const double* src, size_t row_elems, size_t rows, int64_t stride) {
-    return hipMemcpy2DAsync(dst, row_elems * 8, src, (rows > 1 ? (size_t)stride : row_elems) * 8, row_elems * 8, rows,
-                            hipMemcpyHostToDevice, c->stream);
-}
-
-// A Carver (prhf_arena.h) that also stages: put() takes the room of a host array and, on the pass over the buffer,
-// enqueues its upload.  A null array takes its room and gives a null pointer.
-class Stager : public Carver {
-  public:
-    // pack: host memory that mirrors the buffer - put() copies there instead, for the caller to send in one piece
-    Stager(prhf_ctx* c, void* base, void* pack = nullptr) : Carver(base), c_(c), pack_(static_cast<char*>(pack)) {}
-    template <class T>
-    T* put(const void* src, size_t count) {
-        const size_t at = used();
-        T* d = take<T>(count);
-        if (!src) return nullptr;
-        if (d && pack_) std::memcpy(pack_ + at, src, count * sizeof(T));
-        else if (d && err_ == hipSuccess) err_ = upload(c_, d, src, count * sizeof(T));
-        return d;
-    }
-    hipError_t error() const { return err_; }
-
-  private:
-    prhf_ctx* c_;
-    char* pack_;
-    hipError_t err_ = hipSuccess;
-};
-
-// A buffer of the context laid out by `layout`, a function of a Stager: the pass over a null base gives the bytes the
-// buffer must hold, the pass over the buffer gives the pointers and sends the uploads.  No size is written down beside
-// its carving.
-template <class Layout>
-int carve(prhf_ctx* c, DevBuf& b, Layout layout) {
-    Stager sizing(c, nullptr);
-    layout(sizing);
-    PRHF_TRY(ensure(c, b, sizing.used()));
-    Stager k(c, b.p);
-    layout(k);
-    HIP_TRY(k.error());
-    return PRHF_OK;
-}
-
-// The tail of a launch: the two timing events around `launch` (one launch or a body of several, the first error
-// returned), the ring slot published and - posts_status - the status words read at the next prhf_sync.
-template <class Launch>
-int timed_launch(prhf_ctx* c, bool posts_status, Launch launch) {
-    HIP_TRY(hipEventRecord(c->begin_ev(), c->stream));
-    HIP_TRY(launch());
-    HIP_TRY(hipEventRecord(c->pending_end_ev(), c->stream));
-    c->mark_timed();
-    if (posts_status) c->status_pending = true;
-    return PRHF_OK;
-}
+// ---- The tracer and derivative entry points ----
 
 // Host-side range check of an index array
 int check_index(const char* name, const int64_t* idx, int64_t n, const char* limit_name, int64_t limit) {
@@ -1258,66 +1280,14 @@ int check_scan_grid(const double* scan_elevation_deg, int64_t n_scan, bool lone_
     return PRHF_OK;
 }
 
-// What the operator and its derivatives (Jacobian, VJP, JVP) are called on
-struct OperatorInputs {
-    const double* freq;
-    int64_t n_freq;
-    const double *den, *bmag, *bpsi, *alt;
-    int64_t n_prof, n_alt, prof_stride, alt_stride;
-    const double* mult;
-    int32_t n_points, mode;
-    uint32_t flags;
-    bool dev() const { return (flags & PRHF_FLAG_DEVICE_PTRS) != 0; }
-    bool shared_field() const { return (flags & PRHF_FLAG_SHARED_FIELD) != 0; }
-};
-
 // What the derivative entry points check alike; others_given: the arrays of their own are there
 int derivative_check(prhf_ctx* c, const OperatorInputs& in, bool others_given) {
-    if (!c) return fail(PRHF_EINVAL, "null context");
-    if (!in.freq || !in.den || !in.bmag || !in.bpsi || !in.alt || !in.mult || !others_given)
-        return fail(PRHF_EINVAL, "null array pointer");
-    if (in.n_freq < 1 || in.n_prof < 0 || in.n_alt < 1 || in.n_points < 1) return fail(PRHF_EINVAL, "bad shape");
-    if (in.n_alt > kMaxAltTall)
-        return fail(PRHF_EINVAL, "n_alt %lld exceeds the limit of %lld levels", (long long)in.n_alt, kMaxAltTall);
-    if (in.n_freq > (1 << 20)) return fail(PRHF_EINVAL, "n_freq too large");
-    if (in.prof_stride < in.n_alt || (in.alt_stride != 0 && in.alt_stride < in.n_alt))
-        return fail(PRHF_EINVAL, "row stride shorter than a row");
+    PRHF_TRY(check_arrays(c, in, others_given));
+    PRHF_TRY(check_shape(in, true));
     if (in.mode != PRHF_MODE_O && in.mode != PRHF_MODE_X) return fail(PRHF_EINVAL, "mode must be 'O' or 'X'");
-    if (in.flags & ~(PRHF_FLAG_DEVICE_PTRS | PRHF_FLAG_ASYNC | PRHF_FLAG_GRID_STABLE | PRHF_FLAG_SHARED_FIELD))
-        return fail(PRHF_EINVAL, "unknown flag bits");
-    if ((in.flags & PRHF_FLAG_ASYNC) && !in.dev()) return fail(PRHF_EINVAL, "PRHF_FLAG_ASYNC needs device pointers");
-    if (!in.dev())
-        for (int64_t i = 1; i < in.n_points; ++i)
-            if (in.mult[i] < in.mult[i - 1])
-                return fail(PRHF_EINVAL, "multiplier[%lld] decreases: the stretched grid must be non-decreasing", (long long)i);
-    return PRHF_OK;
-}
-
-// The highest density peak of the launch (np.argmax's rule, the first NaN ranking highest): a host scan, or the peak
-// pre-pass and one synchronisation.  The caller has entered the device.
-int highest_peak(prhf_ctx* c, const double* den, int64_t n_prof, int64_t n_alt, int64_t prof_stride, bool dev, long long* out) {
-    long long max_peak = 0;
-    if (dev) {
-        HIP_TRY(hipMemsetAsync(c->d_status + kWordPeak, 0, sizeof(unsigned), c->stream));
-        HIP_TRY(prhf::launch_peak_levels(den, n_prof, n_alt, prof_stride, c->d_status + kWordPeak, c->stream));
-        unsigned peak = 0;
-        HIP_TRY(hipMemcpyAsync(&peak, c->d_status + kWordPeak, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        max_peak = peak;
-    } else {
-        for (int64_t p = 0; p < n_prof; ++p) {
-            const double* d = den + (size_t)p * prof_stride;
-            double bv = -HUGE_VAL;
-            long long bi = 0;
-            for (int64_t i = 0; i < n_alt; ++i) {
-                const double key = (d[i] != d[i]) ? HUGE_VAL : d[i];
-                if (key > bv) { bv = key; bi = i; }
-            }
-            max_peak = std::max(max_peak, bi);
-        }
-    }
-    *out = max_peak;
-    return PRHF_OK;
+    PRHF_TRY(check_flags(in));
+    const prhf_segment seg = whole_batch(in.n_prof, in.mode, in.n_points);
+    return in.dev() ? PRHF_OK : check_grid(in.mult, in.n_points, &seg, 1);
 }
 
 // Levels to stage: the whole column where `plan` (plan_vjp or plan_jvp of prhf_plan.h on this call's shape) takes it;
@@ -1355,22 +1325,18 @@ int stage_derivative(prhf_ctx* c, const OperatorInputs& in, long long levels, Ar
         a.alt_stride = in.alt_stride;
         return PRHF_OK;
     }
-    const size_t P = (size_t)in.n_prof, A = (size_t)in.n_alt;
-    const size_t field_rows = in.shared_field() ? 1 : P, alt_rows = in.alt_stride ? P : 1;
-    double *d_den = nullptr, *d_bmag = nullptr, *d_bpsi = nullptr, *d_alt = nullptr;
+    const OperatorShape s = in.shape((size_t)in.n_points);
     PRHF_TRY(carve(c, c->vjp, [&](Stager& k) {
-        a.freq = k.put<double>(in.freq, (size_t)in.n_freq);
-        a.mult = k.put<double>(in.mult, (size_t)in.n_points);
-        a.den = d_den = k.take<double>(P * A);
-        a.bmag = d_bmag = k.take<double>(field_rows * A);
-        a.bpsi = d_bpsi = k.take<double>(field_rows * A);
-        a.alt = d_alt = k.take<double>(alt_rows * A);
+        const OperatorBlock b = operator_block(k, s);
+        k.put(b.freq, in.freq, s.n_freq);
+        k.put_rows(b.den, in.den, s.n_alt, s.n_prof, in.prof_stride);
+        k.put_rows(b.bmag, in.bmag, s.n_alt, s.field_rows, in.prof_stride);
+        k.put_rows(b.bpsi, in.bpsi, s.n_alt, s.field_rows, in.prof_stride);
+        k.put_rows(b.alt, in.alt, s.n_alt, s.alt_rows, in.alt_stride);
+        k.put(b.mult, in.mult, s.mult_len);
+        a.freq = b.freq; a.den = b.den; a.bmag = b.bmag; a.bpsi = b.bpsi; a.alt = b.alt; a.mult = b.mult;
         rest(k);
     }));
-    HIP_TRY(upload_rows(c, d_den, in.den, A, P, in.prof_stride));
-    HIP_TRY(upload_rows(c, d_bmag, in.bmag, A, field_rows, in.prof_stride));
-    HIP_TRY(upload_rows(c, d_bpsi, in.bpsi, A, field_rows, in.prof_stride));
-    HIP_TRY(upload_rows(c, d_alt, in.alt, A, alt_rows, in.alt_stride));
     a.prof_stride = in.n_alt;
     a.field_stride = in.shared_field() ? 0 : in.n_alt;
     a.alt_stride = in.alt_stride ? in.n_alt : 0;
@@ -1484,16 +1450,11 @@ int prhf_vfo_residual_f64(prhf_ctx* ctx, const double* freq_mhz, int64_t n_freq,
                           int64_t n_alt, int64_t prof_stride_elems, int64_t alt_stride_elems,
                           const double* multiplier, int32_t n_points, int32_t mode, const double* vh_obs,
                           double* vh_out, double* residual_out, double* cost_out, uint32_t flags) {
-    prhf_segment seg;
-    seg.prof_begin = 0;
-    seg.prof_end = n_prof;
-    seg.mode = mode;
-    seg.n_points = n_points;
-    seg.mult_offset = 0;
-    seg.out_offset = 0;
+    const prhf_segment seg = whole_batch(n_prof, mode, n_points);
     Residual post{vh_obs, residual_out, cost_out};
-    return run(ctx, freq_mhz, n_freq, den, bmag, bpsi, alt, n_prof, n_alt, prof_stride_elems, alt_stride_elems,
-               multiplier, n_points, &seg, 1, vh_out, flags, &post);
+    const OperatorInputs in{freq_mhz, n_freq, den, bmag, bpsi, alt, n_prof, n_alt, prof_stride_elems, alt_stride_elems,
+                            multiplier, n_points, mode, flags};
+    return run(ctx, in, OperatorWork{n_points, &seg, 1, vh_out, &post});
 }
 
 int prhf_vfo_residual_many_f64(prhf_ctx* ctx, const double* freq_mhz, int64_t n_freq, const double* den,
@@ -1503,24 +1464,20 @@ int prhf_vfo_residual_many_f64(prhf_ctx* ctx, const double* freq_mhz, int64_t n_
                                int64_t n_iono, const int32_t* ionogram_of_row, double* vh_out, double* residual_out,
                                double* cost_out, int64_t* best_out, double* best_cost_out, uint32_t flags) {
     if (!freq_mhz) return fail(PRHF_EINVAL, "null array pointer");
-    int rc = check_many(freq_mhz, n_freq, n_prof, vh_obs, n_iono, ionogram_of_row, residual_out, cost_out, best_out,
-                        best_cost_out, flags);
-    if (rc != PRHF_OK) return rc;
-    prhf_segment seg;
-    seg.prof_begin = 0;
-    seg.prof_end = n_prof;
-    seg.mode = mode;
-    seg.n_points = n_points;
-    seg.mult_offset = 0;
-    seg.out_offset = 0;
+    PRHF_TRY(check_many(freq_mhz, n_freq, n_prof, vh_obs, n_iono, ionogram_of_row, residual_out, cost_out, best_out, best_cost_out,
+                        flags));
+    const prhf_segment seg = whole_batch(n_prof, mode, n_points);
     Residual post{vh_obs, residual_out, cost_out};
     post.n_iono = n_iono;
     post.ionogram_of_row = ionogram_of_row;
     post.best = best_out;
     post.best_cost = best_cost_out;
-    return run(ctx, freq_mhz, n_freq, den, bmag, bpsi, alt, n_prof, n_alt, prof_stride_elems, alt_stride_elems,
-               multiplier, n_points, &seg, 1, vh_out, flags, &post);
+    const OperatorInputs in{freq_mhz, n_freq, den, bmag, bpsi, alt, n_prof, n_alt, prof_stride_elems, alt_stride_elems,
+                            multiplier, n_points, mode, flags};
+    return run(ctx, in, OperatorWork{n_points, &seg, 1, vh_out, &post});
 }
+
+// ---- The un-fused stage ops: checks, carve (put the inputs, take the outputs), timed_launch, downloads, tail ----
 
 int prhf_mu_mup_f64(prhf_ctx* c, const double* X, const double* Y, const double* psi_deg, int64_t n,
                     int32_t mode, double* mu_out, double* mup_out, uint32_t flags) {
@@ -1532,27 +1489,18 @@ int prhf_mu_mup_f64(prhf_ctx* c, const double* X, const double* Y, const double*
     if (n == 0) return PRHF_OK;
     ENTER_DEVICE(c->device);
     const bool dev = (flags & PRHF_FLAG_DEVICE_PTRS) != 0;
-    const double *dX = X, *dY = Y, *dP = psi_deg;
-    double *dMu = mu_out, *dMup = mup_out;
-    const size_t bytes = (size_t)n * 8;
-    if (!dev) {
-        int rc = ensure(c, c->arena, 5 * bytes);
-        if (rc != PRHF_OK) return rc;
-        double* base = static_cast<double*>(c->arena.p);
-        HIP_TRY(hipMemcpyAsync(base, X, bytes, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(base + n, Y, bytes, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(base + 2 * n, psi_deg, bytes, hipMemcpyHostToDevice, c->stream));
-        dX = base; dY = base + n; dP = base + 2 * n; dMu = base + 3 * n; dMup = base + 4 * n;
-    }
-    HIP_TRY(hipEventRecord(c->begin_ev(), c->stream));
-    HIP_TRY(prhf::launch_mu_mup(dX, dY, dP, n, mode == PRHF_MODE_O ? PRHF_KMODE_O : PRHF_KMODE_X,
-                                c->math == PRHF_MATH_FAST ? 1 : 0, c->d_words, c->h_words, dMu, dMup, c->stream));
-    HIP_TRY(hipEventRecord(c->pending_end_ev(), c->stream));
-    c->mark_timed();
-    if (!dev) {
-        HIP_TRY(hipMemcpyAsync(mu_out, dMu, bytes, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipMemcpyAsync(mup_out, dMup, bytes, hipMemcpyDeviceToHost, c->stream));
-    }
+    const double* const src[3] = {X, Y, psi_deg};
+    double* const dst[2] = {mu_out, mup_out};
+    MuMupBlock b = {{mut(X), mut(Y), mut(psi_deg)}, {mu_out, mup_out}};
+    if (!dev) PRHF_TRY(carve(c, c->arena, [&](Stager& k) {
+        b = mu_mup_block(k, (size_t)n);
+        for (int i = 0; i < 3; ++i) k.put(b.in[i], src[i], (size_t)n);
+    }));
+    PRHF_TRY(timed_launch(c, false, [&] {
+        return prhf::launch_mu_mup(b.in[0], b.in[1], b.in[2], n, kmode(mode), c->math == PRHF_MATH_FAST ? 1 : 0, c->d_words,
+                                   c->h_words, b.out[0], b.out[1], c->stream);
+    }));
+    for (int i = 0; i < 2 && !dev; ++i) HIP_TRY(download(c, dst[i], b.out[i], (size_t)n * 8));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return PRHF_OK;
 }
@@ -1568,25 +1516,17 @@ int prhf_find_vh_f64(prhf_ctx* c, const double* X, const double* Y, const double
     if (n_rows == 0) return PRHF_OK;
     ENTER_DEVICE(c->device);
     const bool dev = (flags & PRHF_FLAG_DEVICE_PTRS) != 0;
-    const int64_t n = n_rows * n_cols;
-    const double *dX = X, *dY = Y, *dP = psi_deg, *dD = dh;
-    double* dV = vh_out;
-    if (!dev) {
-        int rc = ensure(c, c->arena, (size_t)(4 * n + n_rows) * 8);
-        if (rc != PRHF_OK) return rc;
-        double* base = static_cast<double*>(c->arena.p);
-        const double* src[4] = {X, Y, psi_deg, dh};
-        for (int k = 0; k < 4 && n > 0; ++k)
-            HIP_TRY(hipMemcpyAsync(base + k * n, src[k], (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
-        dX = base; dY = base + n; dP = base + 2 * n; dD = base + 3 * n; dV = base + 4 * n;
-    }
-    HIP_TRY(hipEventRecord(c->begin_ev(), c->stream));
-    HIP_TRY(prhf::launch_find_vh(dX, dY, dP, dD, n_rows, n_cols, alt_min,
-                                 mode == PRHF_MODE_O ? PRHF_KMODE_O : PRHF_KMODE_X,
-                                 c->math == PRHF_MATH_FAST ? 1 : 0, c->d_words, c->h_words, dV, c->stream));
-    HIP_TRY(hipEventRecord(c->pending_end_ev(), c->stream));
-    c->mark_timed();
-    if (!dev) HIP_TRY(hipMemcpyAsync(vh_out, dV, (size_t)n_rows * 8, hipMemcpyDeviceToHost, c->stream));
+    const double* const src[4] = {X, Y, psi_deg, dh};
+    FindVhBlock b = {{mut(X), mut(Y), mut(psi_deg), mut(dh)}, vh_out};
+    if (!dev) PRHF_TRY(carve(c, c->arena, [&](Stager& k) {
+        b = find_vh_block(k, (size_t)n_rows, (size_t)n_cols);
+        for (int i = 0; i < 4 && n_cols > 0; ++i) k.put(b.in[i], src[i], (size_t)(n_rows * n_cols));
+    }));
+    PRHF_TRY(timed_launch(c, false, [&] {
+        return prhf::launch_find_vh(b.in[0], b.in[1], b.in[2], b.in[3], n_rows, n_cols, alt_min, kmode(mode),
+                                    c->math == PRHF_MATH_FAST ? 1 : 0, c->d_words, c->h_words, b.vh, c->stream);
+    }));
+    if (!dev) HIP_TRY(download(c, vh_out, b.vh, (size_t)n_rows * 8));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return PRHF_OK;
 }
@@ -1607,77 +1547,39 @@ int prhf_regrid_f64(prhf_ctx* c, const double* freq_hz, int64_t n_freq, const do
     const bool dev = (flags & PRHF_FLAG_DEVICE_PTRS) != 0;
     const size_t fn = (size_t)n_freq * (size_t)n_points;
     // The reference regrids the levels below the density peak only (library.py:371-375).  A column of more levels than
-    // LDS holds stages just those: its peak - np.argmax, the first NaN ranking highest, the kernel's own rule - comes
-    // from a host scan or, for device memory, from launch_peak_levels (one synchronisation).  Shorter columns take
-    // neither.
+    // LDS holds stages just those, up to its peak (highest_peak: one synchronisation for device memory).  Shorter
+    // columns take neither.
     long long levels = n_alt;
     if (n_alt > kMaxAlt) {
         long long peak = 0;
-        if (dev) {
-            HIP_TRY(hipMemsetAsync(c->d_status + kWordPeak, 0, sizeof(unsigned), c->stream));
-            HIP_TRY(prhf::launch_peak_levels(den, 1, n_alt, n_alt, c->d_status + kWordPeak, c->stream));
-            unsigned p = 0;
-            HIP_TRY(hipMemcpyAsync(&p, c->d_status + kWordPeak, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            peak = p;
-        } else {
-            double bv = -HUGE_VAL;
-            for (int64_t i = 0; i < n_alt; ++i) {
-                const double key = (den[i] != den[i]) ? HUGE_VAL : den[i];
-                if (key > bv) { bv = key; peak = i; }
-            }
-        }
+        PRHF_TRY(highest_peak(c, den, 1, n_alt, n_alt, dev, &peak));
         if (peak + 1 > kMaxAlt)
             return fail(PRHF_EINVAL, "regrid stages at most %lld levels up to the density peak (the 1400-level "
                         "bottomside limit); this column's peak is at level %lld", kMaxAlt, peak);
         levels = peak + 1;
     }
+    const double* const col[4] = {den, bmag, bpsi, alt};
+    double* const host[7] = {out_freq, out_den, out_bmag, out_bpsi, out_dist, out_alt, out_crit};
+    RegridBlock b = {mut(freq_hz), {mut(den), mut(bmag), mut(bpsi), mut(alt)}, mut(multiplier),
+                     {out_freq, out_den, out_bmag, out_bpsi, out_dist, out_alt, out_crit}, reinterpret_cast<long long*>(out_ind)};
+    if (!dev) PRHF_TRY(carve(c, c->arena, [&](Stager& k) {
+        b = regrid_block(k, (size_t)n_freq, (size_t)n_alt, (size_t)n_points);
+        k.put(b.freq, freq_hz, (size_t)n_freq);
+        for (int i = 0; i < 4; ++i) k.put(b.col[i], col[i], (size_t)n_alt);
+        k.put(b.mult, multiplier, (size_t)n_points);
+    }));
     prhf::RegridArgs a;
     std::memset(&a, 0, sizeof a);
     a.n_freq = n_freq; a.n_alt = n_alt; a.lds_levels = levels; a.n_points = n_points;
-    a.mode = mode == PRHF_MODE_O ? PRHF_KMODE_O : PRHF_KMODE_X;
+    a.mode = kmode(mode);
     a.status = c->h_status_dev;
-    double* base = nullptr;
-    if (dev) {
-        a.freq_hz = freq_hz; a.den = den; a.bmag = bmag; a.bpsi = bpsi; a.alt = alt; a.mult = multiplier;
-        a.out_freq = out_freq; a.out_den = out_den; a.out_bmag = out_bmag; a.out_bpsi = out_bpsi;
-        a.out_dist = out_dist; a.out_alt = out_alt; a.out_crit = out_crit;
-        a.out_ind = reinterpret_cast<long long*>(out_ind);
-    } else {
-        const size_t in_elems = (size_t)n_freq + 4 * (size_t)n_alt + (size_t)n_points;
-        int rc = ensure(c, c->arena, (in_elems + 8 * fn) * 8);
-        if (rc != PRHF_OK) return rc;
-        base = static_cast<double*>(c->arena.p);
-        double* d_freq = base;
-        double* d_den = d_freq + n_freq;
-        double* d_bmag = d_den + n_alt;
-        double* d_bpsi = d_bmag + n_alt;
-        double* d_alt = d_bpsi + n_alt;
-        double* d_mult = d_alt + n_alt;
-        double* d_out = d_mult + n_points;
-        HIP_TRY(hipMemcpyAsync(d_freq, freq_hz, (size_t)n_freq * 8, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(d_den, den, (size_t)n_alt * 8, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(d_bmag, bmag, (size_t)n_alt * 8, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(d_bpsi, bpsi, (size_t)n_alt * 8, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(d_alt, alt, (size_t)n_alt * 8, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(d_mult, multiplier, (size_t)n_points * 8, hipMemcpyHostToDevice, c->stream));
-        a.freq_hz = d_freq; a.den = d_den; a.bmag = d_bmag; a.bpsi = d_bpsi; a.alt = d_alt; a.mult = d_mult;
-        a.out_freq = d_out; a.out_den = d_out + fn; a.out_bmag = d_out + 2 * fn; a.out_bpsi = d_out + 3 * fn;
-        a.out_dist = d_out + 4 * fn; a.out_alt = d_out + 5 * fn; a.out_crit = d_out + 6 * fn;
-        a.out_ind = reinterpret_cast<long long*>(d_out + 7 * fn);
-    }
-    HIP_TRY(hipEventRecord(c->begin_ev(), c->stream));
-    HIP_TRY(prhf::launch_regrid(a, staged_lds_bytes(levels), c->stream));
-    HIP_TRY(hipEventRecord(c->pending_end_ev(), c->stream));
-    c->mark_timed();
-    c->status_pending = true;
-    if (!dev) {
-        double* host[7] = {out_freq, out_den, out_bmag, out_bpsi, out_dist, out_alt, out_crit};
-        double* devp[7] = {a.out_freq, a.out_den, a.out_bmag, a.out_bpsi, a.out_dist, a.out_alt, a.out_crit};
-        for (int k = 0; k < 7; ++k)
-            HIP_TRY(hipMemcpyAsync(host[k], devp[k], fn * 8, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipMemcpyAsync(out_ind, a.out_ind, fn * 8, hipMemcpyDeviceToHost, c->stream));
-    }
+    a.freq_hz = b.freq; a.den = b.col[0]; a.bmag = b.col[1]; a.bpsi = b.col[2]; a.alt = b.col[3]; a.mult = b.mult;
+    a.out_freq = b.out[0]; a.out_den = b.out[1]; a.out_bmag = b.out[2]; a.out_bpsi = b.out[3];
+    a.out_dist = b.out[4]; a.out_alt = b.out[5]; a.out_crit = b.out[6];
+    a.out_ind = b.ind;
+    PRHF_TRY(timed_launch(c, true, [&] { return prhf::launch_regrid(a, staged_lds_bytes(levels), c->stream); }));
+    for (int i = 0; i < 7 && !dev; ++i) HIP_TRY(download(c, host[i], b.out[i], fn * 8));
+    if (!dev) HIP_TRY(download(c, out_ind, b.ind, fn * 8));
     return prhf_sync(c);
 }
 
@@ -1694,26 +1596,20 @@ int prhf_residual_f64(prhf_ctx* c, const double* vh_model, const double* vh_obs,
     if (n_prof == 0) return PRHF_OK;
     ENTER_DEVICE(c->device);
     const size_t pf = (size_t)n_prof * (size_t)n_freq;
-    const double *dM = vh_model, *dO = vh_obs;
-    double *dR = residual_out, *dC = cost_out;
-    if (!dev) {
-        int rc = ensure(c, c->arena, (2 * pf + (size_t)n_freq + (size_t)n_prof) * 8);
-        if (rc != PRHF_OK) return rc;
-        double* base = static_cast<double*>(c->arena.p);
-        HIP_TRY(hipMemcpyAsync(base, vh_model, pf * 8, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(base + pf, vh_obs, (size_t)n_freq * 8, hipMemcpyHostToDevice, c->stream));
-        dM = base; dO = base + pf;
-        dR = residual_out ? base + pf + n_freq : nullptr;
-        dC = cost_out ? base + 2 * pf + n_freq : nullptr;
-    }
-    HIP_TRY(hipEventRecord(c->begin_ev(), c->stream));
-    HIP_TRY(prhf::launch_residual(dM, dO, n_prof, (int)n_freq, dR, dC, c->stream));
-    HIP_TRY(hipEventRecord(c->pending_end_ev(), c->stream));
-    c->mark_timed();
-    if (!dev) {
-        if (residual_out) HIP_TRY(hipMemcpyAsync(residual_out, dR, pf * 8, hipMemcpyDeviceToHost, c->stream));
-        if (cost_out) HIP_TRY(hipMemcpyAsync(cost_out, dC, (size_t)n_prof * 8, hipMemcpyDeviceToHost, c->stream));
-    }
+    const double* model = vh_model;
+    ResidualBlock b = {mut(vh_obs), residual_out, cost_out};
+    if (!dev) PRHF_TRY(carve(c, c->arena, [&](Stager& k) {
+        model = k.put<double>(vh_model, pf);
+        b = residual_block(k, (size_t)n_freq, pf, (size_t)n_prof);
+        k.put(b.obs, vh_obs, (size_t)n_freq);
+        if (!residual_out) b.residual = nullptr;
+        if (!cost_out) b.cost = nullptr;
+    }));
+    PRHF_TRY(timed_launch(c, false, [&] {
+        return prhf::launch_residual(model, b.obs, n_prof, (int)n_freq, b.residual, b.cost, c->stream);
+    }));
+    if (!dev && residual_out) HIP_TRY(download(c, residual_out, b.residual, pf * 8));
+    if (!dev && cost_out) HIP_TRY(download(c, cost_out, b.cost, (size_t)n_prof * 8));
     if (flags & PRHF_FLAG_ASYNC) return PRHF_OK;
     HIP_TRY(hipStreamSynchronize(c->stream));
     return PRHF_OK;
@@ -1723,52 +1619,35 @@ int prhf_residual_many_f64(prhf_ctx* c, const double* vh_model, int64_t n_rows, 
                            int64_t n_freq, const int32_t* ionogram_of_row, double* residual_out, double* cost_out,
                            int64_t* best_out, double* best_cost_out, uint32_t flags) {
     if (!vh_model) return fail(PRHF_EINVAL, "null array pointer");
-    int rc = check_many(nullptr, n_freq, n_rows, vh_obs, n_iono, ionogram_of_row, residual_out, cost_out, best_out,
-                        best_cost_out, flags);
-    if (rc != PRHF_OK) return rc;
+    PRHF_TRY(check_many(nullptr, n_freq, n_rows, vh_obs, n_iono, ionogram_of_row, residual_out, cost_out, best_out, best_cost_out,
+                        flags));
     if (!c) return fail(PRHF_EINVAL, "null context");
     if (flags & ~(PRHF_FLAG_DEVICE_PTRS | PRHF_FLAG_ASYNC)) return fail(PRHF_EINVAL, "unknown flag bits");
     const bool dev = (flags & PRHF_FLAG_DEVICE_PTRS) != 0;
     if ((flags & PRHF_FLAG_ASYNC) && !dev) return fail(PRHF_EINVAL, "PRHF_FLAG_ASYNC needs device pointers");
     ENTER_DEVICE(c->device);
-    const size_t pf = (size_t)n_rows * (size_t)n_freq, obs_elems = (size_t)n_iono * (size_t)n_freq;
-    const size_t cost_elems = (size_t)n_rows * (size_t)(ionogram_of_row ? 1 : n_iono);
-    const double *dM = vh_model, *dO = vh_obs;
-    const int32_t* dI = ionogram_of_row;
-    double *dR = residual_out, *dC = cost_out, *dBC = best_cost_out;
-    int64_t* dB = best_out;
+    const size_t pf = (size_t)n_rows * (size_t)n_freq;
+    const size_t cost_elems = many_cost_elems((size_t)n_rows, (size_t)n_iono, ionogram_of_row != nullptr);
+    const double* model = vh_model;
+    ManyBlock b = {mut(vh_obs), residual_out, cost_out, best_cost_out, best_out, const_cast<int32_t*>(ionogram_of_row)};
+    if (!dev) PRHF_TRY(carve(c, c->arena, [&](Stager& k) {
+        double* const m = k.take<double>(pf);
+        if (pf) k.put(m, vh_model, pf);
+        model = m;
+        b = many_block(k, (size_t)n_iono, (size_t)n_freq, (size_t)n_rows, residual_out ? pf : 0, ionogram_of_row != nullptr);
+        k.put(b.obs, vh_obs, (size_t)n_iono * (size_t)n_freq);
+        if (ionogram_of_row && n_rows > 0) k.put(b.ionogram_of_row, ionogram_of_row, (size_t)n_rows);
+        else b.ionogram_of_row = const_cast<int32_t*>(ionogram_of_row);
+        if (!residual_out) b.residual = nullptr;
+    }));
+    PRHF_TRY(timed_launch(c, false, [&] {
+        return launch_many(c, model, n_rows, b.obs, n_iono, n_freq, b.ionogram_of_row, b.residual, b.cost, b.best, b.best_cost);
+    }));
     if (!dev) {
-        const size_t elems = pf + obs_elems + (residual_out ? pf : 0) + cost_elems + 2 * (size_t)n_iono + ((size_t)n_rows + 1) / 2;
-        if ((rc = ensure(c, c->arena, elems * 8)) != PRHF_OK) return rc;
-        double* p0 = static_cast<double*>(c->arena.p);
-        if (pf) HIP_TRY(hipMemcpyAsync(p0, vh_model, pf * 8, hipMemcpyHostToDevice, c->stream));
-        dM = p0;
-        p0 += pf;
-        HIP_TRY(hipMemcpyAsync(p0, vh_obs, obs_elems * 8, hipMemcpyHostToDevice, c->stream));
-        dO = p0;
-        p0 += obs_elems;
-        dR = residual_out ? p0 : nullptr;
-        if (residual_out) p0 += pf;
-        dC = p0;
-        p0 += cost_elems;
-        dBC = p0;
-        p0 += n_iono;
-        dB = reinterpret_cast<int64_t*>(p0);
-        p0 += n_iono;
-        if (ionogram_of_row && n_rows > 0) {
-            HIP_TRY(hipMemcpyAsync(p0, ionogram_of_row, (size_t)n_rows * 4, hipMemcpyHostToDevice, c->stream));
-            dI = reinterpret_cast<const int32_t*>(p0);
-        }
-    }
-    HIP_TRY(hipEventRecord(c->begin_ev(), c->stream));
-    if ((rc = launch_many(c, dM, n_rows, dO, n_iono, n_freq, dI, dR, dC, dB, dBC)) != PRHF_OK) return rc;
-    HIP_TRY(hipEventRecord(c->pending_end_ev(), c->stream));
-    c->mark_timed();
-    if (!dev) {
-        if (residual_out && pf) HIP_TRY(hipMemcpyAsync(residual_out, dR, pf * 8, hipMemcpyDeviceToHost, c->stream));
-        if (cost_elems) HIP_TRY(hipMemcpyAsync(cost_out, dC, cost_elems * 8, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipMemcpyAsync(best_out, dB, (size_t)n_iono * 8, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipMemcpyAsync(best_cost_out, dBC, (size_t)n_iono * 8, hipMemcpyDeviceToHost, c->stream));
+        if (residual_out && pf) HIP_TRY(download(c, residual_out, b.residual, pf * 8));
+        if (cost_elems) HIP_TRY(download(c, cost_out, b.cost, cost_elems * 8));
+        HIP_TRY(download(c, best_out, b.best, (size_t)n_iono * 8));
+        HIP_TRY(download(c, best_cost_out, b.best_cost, (size_t)n_iono * 8));
     }
     if (flags & PRHF_FLAG_ASYNC) return PRHF_OK;
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -2280,26 +2159,21 @@ int prhf_field_pack_f64(prhf_ctx* c, const double* mu, const double* mup, int64_
     ENTER_DEVICE(c->device);
     const bool dev = (flags & PRHF_FLAG_DEVICE_PTRS) != 0;
     const size_t cells = (size_t)n_fields * (size_t)n0 * (size_t)n1;
-    rc = ensure(c, c->arena, ((size_t)(n0 + n1) + (dev ? 0 : 2 * cells)) * 8);
-    if (rc != PRHF_OK) return rc;
-    double* p = static_cast<double*>(c->arena.p);
+    FieldPackBlock b;
+    PRHF_TRY(carve(c, c->arena, [&](Stager& k) {
+        b = field_pack_block(k, (size_t)n0, (size_t)n1, dev ? 0 : cells);
+        k.put(b.a0, axis0, (size_t)n0);
+        k.put(b.a1, axis1, (size_t)n1);
+        if (dev) return;
+        k.put(b.mu, mu, cells);
+        k.put(b.mup, mup, cells);
+    }));
     prhf::FieldPackArgs a;
     std::memset(&a, 0, sizeof a);
-    HIP_TRY(hipMemcpyAsync(p, axis0, (size_t)n0 * 8, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(p + n0, axis1, (size_t)n1 * 8, hipMemcpyHostToDevice, c->stream));
-    a.a0 = p; a.a1 = p + n0; a.mu = mu; a.mup = mup;
-    if (!dev) {
-        double* d_mu = p + n0 + n1;
-        HIP_TRY(hipMemcpyAsync(d_mu, mu, cells * 8, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(d_mu + cells, mup, cells * 8, hipMemcpyHostToDevice, c->stream));
-        a.mu = d_mu; a.mup = d_mu + cells;
-    }
+    a.a0 = b.a0; a.a1 = b.a1; a.mu = dev ? mu : b.mu; a.mup = dev ? mup : b.mup;
     a.rec = records; a.n_fields = n_fields; a.n0 = (int)n0; a.n1 = (int)n1; a.uniform0 = u0; a.uniform1 = u1;
     a.edge_order = edge_order;
-    HIP_TRY(hipEventRecord(c->begin_ev(), c->stream));
-    HIP_TRY(prhf::launch_field_pack(a, c->stream));
-    HIP_TRY(hipEventRecord(c->pending_end_ev(), c->stream));
-    c->mark_timed();
+    PRHF_TRY(timed_launch(c, false, [&] { return prhf::launch_field_pack(a, c->stream); }));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return PRHF_OK;
 }
@@ -2323,36 +2197,29 @@ int prhf_field_sample_f64(prhf_ctx* c, const double* records, int64_t n_fields, 
                 return fail(PRHF_EINVAL, "field_index[%lld] outside [0, n_fields)", (long long)i);
     if (n == 0) return PRHF_OK;
     ENTER_DEVICE(c->device);
-    double* outs[4] = {out_n, out_d1, out_d0, out_mup};
-    rc = ensure(c, c->arena, ((size_t)(n0 + n1) + (dev ? 0 : 7 * (size_t)n)) * 8);
-    if (rc != PRHF_OK) return rc;
-    double* p = static_cast<double*>(c->arena.p);
+    double* const outs[4] = {out_n, out_d1, out_d0, out_mup};
+    FieldSampleBlock b;
+    PRHF_TRY(carve(c, c->arena, [&](Stager& k) {
+        b = field_sample_block(k, (size_t)n0, (size_t)n1, dev ? 0 : (size_t)n);
+        k.put(b.a0, axis0, (size_t)n0);
+        k.put(b.a1, axis1, (size_t)n1);
+        if (dev) return;
+        k.put(b.p0, p0, (size_t)n);
+        k.put(b.p1, p1, (size_t)n);
+        k.put(b.field, field_index, (size_t)n);
+    }));
+    for (int i = 0; i < 4; ++i)
+        if (dev || !outs[i]) b.out[i] = outs[i];
     prhf::FieldSampleArgs a;
     std::memset(&a, 0, sizeof a);
-    HIP_TRY(hipMemcpyAsync(p, axis0, (size_t)n0 * 8, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(p + n0, axis1, (size_t)n1 * 8, hipMemcpyHostToDevice, c->stream));
-    a.rec = records; a.a0 = p; a.a1 = p + n0; a.n = n; a.n_fields = n_fields; a.n0 = (int)n0; a.n1 = (int)n1;
+    a.rec = records; a.a0 = b.a0; a.a1 = b.a1; a.n = n; a.n_fields = n_fields; a.n0 = (int)n0; a.n1 = (int)n1;
     a.fill_n = fill_n; a.fill_grad = fill_grad; a.fill_mup = fill_mup; a.status = c->h_status_dev;
-    double* d_out[4] = {out_n, out_d1, out_d0, out_mup};
-    if (dev) {
-        a.p0 = p0; a.p1 = p1; a.field = reinterpret_cast<const long long*>(field_index);
-    } else {
-        double* q = p + n0 + n1;
-        HIP_TRY(hipMemcpyAsync(q, p0, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(q + n, p1, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
-        if (field_index) HIP_TRY(hipMemcpyAsync(q + 2 * n, field_index, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
-        a.p0 = q; a.p1 = q + n; a.field = field_index ? reinterpret_cast<const long long*>(q + 2 * n) : nullptr;
-        for (int k = 0; k < 4; ++k) d_out[k] = outs[k] ? q + (3 + k) * n : nullptr;
-    }
-    a.out_n = d_out[0]; a.out_d1 = d_out[1]; a.out_d0 = d_out[2]; a.out_mup = d_out[3];
-    HIP_TRY(hipEventRecord(c->begin_ev(), c->stream));
-    HIP_TRY(prhf::launch_field_sample(a, c->stream));
-    HIP_TRY(hipEventRecord(c->pending_end_ev(), c->stream));
-    c->mark_timed();
-    c->status_pending = true;
-    if (!dev)
-        for (int k = 0; k < 4; ++k)
-            if (outs[k]) HIP_TRY(hipMemcpyAsync(outs[k], d_out[k], (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+    a.p0 = dev ? p0 : b.p0; a.p1 = dev ? p1 : b.p1;
+    a.field = dev || !field_index ? reinterpret_cast<const long long*>(field_index) : b.field;
+    a.out_n = b.out[0]; a.out_d1 = b.out[1]; a.out_d0 = b.out[2]; a.out_mup = b.out[3];
+    PRHF_TRY(timed_launch(c, true, [&] { return prhf::launch_field_sample(a, c->stream); }));
+    for (int i = 0; i < 4 && !dev; ++i)
+        if (outs[i]) HIP_TRY(download(c, outs[i], b.out[i], (size_t)n * 8));
     return prhf_sync(c);
 }
 
@@ -2950,57 +2817,36 @@ int prhf_gradient_hop_skip_counters(prhf_ctx* c, uint64_t* counters) {
     return PRHF_OK;
 }
 
-int prhf_pair_plan_counters(prhf_ctx* c, uint64_t* counters) {
-    if (!c || !counters) return fail(PRHF_EINVAL, "null pointer");
+namespace {
+// n_words of the launches' counters from first_word on (prhf::kPlanCounterWords, since the context was made), once the
+// stream has drained
+int read_plan_counters(prhf_ctx* c, int first_word, int n_words, uint64_t* dst) {
+    if (!c || !dst) return fail(PRHF_EINVAL, "null pointer");
     DeviceScope device_scope_(c->device);
-    unsigned long long w[2] = {0, 0};
     HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipMemcpy(w, c->d_plan_counters, sizeof w, hipMemcpyDeviceToHost));
-    counters[0] = w[0];
-    counters[1] = w[1];
+    HIP_TRY(hipMemcpy(dst, c->d_plan_counters + first_word, (size_t)n_words * sizeof *dst, hipMemcpyDeviceToHost));
     return PRHF_OK;
 }
+}  // namespace
 
-int prhf_panel_counters(prhf_ctx* c, uint64_t* counters) {
-    if (!c || !counters) return fail(PRHF_EINVAL, "null pointer");
-    DeviceScope device_scope_(c->device);
-    unsigned long long w[2] = {0, 0};
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipMemcpy(w, c->d_plan_counters + 2, sizeof w, hipMemcpyDeviceToHost));
-    counters[0] = w[0];
-    counters[1] = w[1];
-    return PRHF_OK;
-}
+int prhf_pair_plan_counters(prhf_ctx* c, uint64_t* counters) { return read_plan_counters(c, 0, 2, counters); }
+
+int prhf_panel_counters(prhf_ctx* c, uint64_t* counters) { return read_plan_counters(c, 2, 2, counters); }
 
 int prhf_panel_upper_counters(prhf_ctx* c, uint64_t* counters) {
-    if (!c || !counters) return fail(PRHF_EINVAL, "null pointer");
-    DeviceScope device_scope_(c->device);
-    unsigned long long w[2] = {0, 0};
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipMemcpy(w, c->d_plan_counters + 4, sizeof w, hipMemcpyDeviceToHost));
+    PRHF_TRY(read_plan_counters(c, 4, 2, counters));
     // (the device counts the pairs that took the panel sum with the option on - each of them reports one or the other - and
     //  among them those that kept the lower region)
-    counters[0] = w[0] - w[1];
-    counters[1] = w[1];
+    counters[0] -= counters[1];
     return PRHF_OK;
 }
 
-int prhf_panel_plan_counters(prhf_ctx* c, uint64_t* counters) {
-    if (!c || !counters) return fail(PRHF_EINVAL, "null pointer");
-    DeviceScope device_scope_(c->device);
-    unsigned long long w[1] = {0};
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipMemcpy(w, c->d_plan_counters + 6, sizeof w, hipMemcpyDeviceToHost));
-    counters[0] = w[0];
-    return PRHF_OK;
-}
+int prhf_panel_plan_counters(prhf_ctx* c, uint64_t* counters) { return read_plan_counters(c, 6, 1, counters); }
 
 int prhf_panel_quick_counters(prhf_ctx* c, uint64_t* counters) {
-    if (!c || !counters) return fail(PRHF_EINVAL, "null pointer");
-    DeviceScope device_scope_(c->device);
-    unsigned long long w[prhf::kQuickSlots * prhf::kQuickSlotWords];
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipMemcpy(w, c->d_plan_counters + prhf::kQuickSlotBase, sizeof w, hipMemcpyDeviceToHost));
+    if (!counters) return fail(PRHF_EINVAL, "null pointer");
+    uint64_t w[prhf::kQuickSlots * prhf::kQuickSlotWords];
+    PRHF_TRY(read_plan_counters(c, prhf::kQuickSlotBase, prhf::kQuickSlots * prhf::kQuickSlotWords, w));
     // (the waves add into one of kQuickSlots slots each: run_items)
     counters[0] = counters[1] = 0;
     for (int s = 0; s < prhf::kQuickSlots; ++s) {

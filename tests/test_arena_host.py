@@ -1,7 +1,10 @@
 """Host check of the scratch-buffer carver (pyrayhf_amd/csrc/prhf_arena.h), no GPU: tests/devtools/arena_host.cpp,
 a stand-alone program, built plain and under ASan + UBSan.  A buffer's layout is stated once and run twice - over a null
 base for its size, over the buffer for its pointers - so the program pins that the two passes agree and that the mixed
-layout of the gradient tracers' MUF scratch lands where the hand-written arithmetic before it put it."""
+layout of the gradient tracers' MUF scratch lands where the hand-written arithmetic before it put it.  It includes
+prhf_layouts.h, the arena's blocks of the operator, the residual stages and the stage ops as the library compiles them:
+for each, the size and every offset against the hand arithmetic they replaced, and a write to the block's last element
+inside a buffer of exactly used() bytes."""
 
 import os
 import shutil

@@ -44,7 +44,7 @@ extern "C" {
                               *    prhf_gradient_hop_skip_f64, prhf_gradient_hop_muf_f64,
                               *    prhf_gradient_hop_skip_counters, and prhf_panel_upper_counters,
                               *    and prhf_stream_launches, and prhf_panel_plan_counters, and
-                              *    prhf_panel_quick_counters) */
+                              *    prhf_panel_quick_counters, and prhf_vfo_lm_fit_f64, prhf_lm_fit_counters) */
 
 /* return codes */
 #define PRHF_OK        0
@@ -351,6 +351,86 @@ int prhf_vfo_jvp_f64(prhf_ctx* ctx,
                      const double* multiplier, int32_t n_points, int32_t mode,
                      const double* tangents, int64_t n_tan, int64_t tan_prof_stride_elems,
                      double* vh_out, double* dvh_out, uint32_t flags);
+
+/*
+ * Levenberg-Marquardt fits of n_iono ionograms on one common frequency grid, each in a small basis of log-density
+ * perturbations, in one call; the first consumer of the JVP inside the library:
+ *     den_i(c) = den0_i * exp(sum_t c_t * B_t),   t < n_tan,   1 <= n_tan <= PRHF_LM_MAX_TANGENTS
+ * so every trial column is positive where its background is, and d vh / d c_t is prhf_vfo_jvp_f64 along den_i * B_t.
+ * Per ionogram i the cost is  sum over K_i of (vh_obs - vh_model)^2 + sum_t prior_weight_t c_t^2,  K_i the frequencies
+ * where vh_obs[i] is finite, a modelled NaN filled as prhf_vfo_residual_many_f64 fills it (the mean of the finite
+ * |vh_model| over K_i, at least 100 km).  A pair without a virtual height has a zero JVP row: it counts in the cost and
+ * not in the step.
+ *
+ * The rule, per ionogram (pyrayhf_amd/csrc/prhf_lm_step.h holds it, operation by operation): evaluation k = 0 is made at
+ * c0 and accepted; a later one is accepted where its cost is strictly smaller (lambda / lambda_down), else rejected
+ * (lambda * lambda_up; lambda stays within [1e-12, 1e12]).  An accepted evaluation whose gain is at most ftol times the
+ * cost before ends with PRHF_LM_CONVERGED_F.  The step solves (A + lambda diag(max(A_tt, 1e-30))) delta = g by Cholesky,
+ * A = sum d d^T + diag(w), g = sum d r - w c of the accepted point; a pivot that is not positive raises lambda, at most 8
+ * times, then PRHF_LM_SINGULAR.  delta is scaled to max|delta_t| <= step_max; max|delta_t| <= xtol (max|c_t| + xtol)
+ * ends with PRHF_LM_CONVERGED_X.  An ionogram with a final status is frozen: it rides along in the later launches and
+ * nothing of its outputs changes.  PRHF_LM_RUNNING: max_iter evaluations were made.  PRHF_LM_NO_DATA: K_i is empty -
+ * c_out is c0, cost_out, den_out and vh_out are NaN.  PRHF_LM_NO_COST: the cost at c0 is not finite.
+ *
+ * Arguments: the operator's, with den0 in place of den - den0_stride_elems doubles between two ionograms' columns, 0
+ * for ONE background column; bmag and bpsi are one row each with PRHF_FLAG_SHARED_FIELD, else n_iono packed rows of n_alt
+ * doubles; alt_stride_elems as for the operator.  basis: n_tan rows of n_alt doubles, basis_prof_stride_elems between
+ * two ionograms' sets (>= n_tan * n_alt), 0 for ONE set.  vh_obs (n_iono, n_freq).  c0 (n_iono, n_tan) or NULL: zeros.
+ * prior_weight (n_tan), >= 0, or NULL: none.  options or NULL: the defaults of prhf_lm_options below.
+ * Outputs: c_out (n_iono, n_tan), cost_out, lambda_out (n_iono) doubles; status_out, n_eval_out, n_accept_out (n_iono)
+ * int32; den_out (n_iono, n_alt), the column at c_out; vh_out (n_iono, n_freq), the operator's trace of that column,
+ * bit for bit; cost_history_out (n_iono, max_iter) or NULL: the accepted cost after every evaluation (a frozen
+ * ionogram's entries repeat its last); state_out (n_iono, n_tan^2 + 2 n_tan) or NULL: A and g of the accepted point, A in
+ * full, and the last step that was computed (zeros where none was).
+ * Flags as for the JVP.  Host arrays are uploaded once and downloaded once.  With device pointers nothing visits the
+ * host, and a prior_weight on the device is not checked.
+ *
+ * Every evaluation is four launches on the context's stream - trial columns, operator, JVP, step - enqueued back to
+ * back: while the whole column fits the JVP's plan (n_alt <= 1332; above 908 levels the tangents go through in chunks of
+ * fewer than eight) the call synchronises once, at its end (never with PRHF_FLAG_ASYNC).  A taller column needs the peak
+ * pre-pass, whose answer can move with c: one synchronisation per evaluation.  prhf_lm_fit_counters reports what the last call did.
+ * Reproducible: every output row of ionogram i depends on that ionogram's inputs and the options only - not on the
+ * other ionograms, their number, or repetition; no atomics, every sum in a fixed order.  Data errors of den0 surface as
+ * in the operator.  PRHF_EINVAL before any device call: null context or array, n_tan outside [1, 8], a stride shorter
+ * than its row, max_iter < 1 or an option outside its range, a negative or NaN prior_weight in host memory.
+ * The cost is discontinuous where a grid frequency crosses a layer's critical frequency (E-layer cusp, foF2) between
+ * two trial columns: the rule then stalls at the jump - it rejects until lambda is large - and reports what it reached.
+ */
+#define PRHF_LM_RUNNING     0
+#define PRHF_LM_CONVERGED_F 1
+#define PRHF_LM_CONVERGED_X 2
+#define PRHF_LM_SINGULAR    3
+#define PRHF_LM_NO_DATA     4
+#define PRHF_LM_NO_COST     5
+#define PRHF_LM_MAX_TANGENTS 8
+typedef struct prhf_lm_options {
+    int32_t max_iter;      /* evaluations, 1 ... 1048576 (2^20); default 20 */
+    int32_t reserved;      /* 0 */
+    double lambda0;        /* > 0; 1e-3 */
+    double lambda_up;      /* > 1; 10 */
+    double lambda_down;    /* >= 1; 10 */
+    double step_max;       /* > 0: cap on max_t |delta_t|; 1.0 */
+    double ftol;           /* >= 0; 1e-10 */
+    double xtol;           /* >= 0; 1e-10 */
+} prhf_lm_options;
+int prhf_vfo_lm_fit_f64(prhf_ctx* ctx,
+                        const double* freq_mhz, int64_t n_freq,
+                        const double* den0, const double* bmag, const double* bpsi,
+                        const double* alt,
+                        int64_t n_iono, int64_t n_alt,
+                        int64_t den0_stride_elems, int64_t alt_stride_elems,
+                        const double* multiplier, int32_t n_points, int32_t mode,
+                        const double* basis, int64_t n_tan, int64_t basis_prof_stride_elems,
+                        const double* vh_obs, const double* c0, const double* prior_weight,
+                        const prhf_lm_options* options,
+                        double* c_out, double* cost_out, int32_t* status_out, int32_t* n_eval_out,
+                        int32_t* n_accept_out, double* lambda_out, double* den_out, double* vh_out,
+                        double* cost_history_out, double* state_out, uint32_t flags);
+/* counters[0 .. PRHF_LM_FIT_COUNTERS) of the last prhf_vfo_lm_fit_f64 on this context: evaluations enqueued, timed
+ * launches enqueued (see prhf_recent_kernel_ms: four per evaluation and the last column's), and the times the call made
+ * the host wait for the stream - synchronisations and buffers that had to grow. */
+#define PRHF_LM_FIT_COUNTERS 3
+int prhf_lm_fit_counters(prhf_ctx* ctx, uint64_t* counters);
 
 /*
  * Appleton-Hartree phase index mu and group index mu' on flat arrays of n elements.

@@ -27,7 +27,8 @@ from .gradient import (STATUS_NAMES, RefractiveField, build_mup_function,       
                        trace_rays_cartesian_gradient, trace_rays_spherical_gradient)
 from .tracers import (home_rays_cartesian_snells, home_rays_spherical_snells, muf_cartesian_snells,  # noqa: E402
                       muf_spherical_snells, skip_distance_cartesian_snells, skip_distance_spherical_snells)
-from .fitting import brute_force_fit_many, minimize_parameters_many, residual_VH_many               # noqa: E402
+from .fitting import (brute_force_fit_many, fit_profiles_lm, minimize_parameters_many,              # noqa: E402
+                      residual_VH_many)
 
 __all__ = ["logger", "__version__", "STATUS_NAMES", "RefractiveField", "build_mup_function",
            "build_refractive_index_interpolator_cartesian", "build_refractive_index_interpolator_spherical",
@@ -42,4 +43,4 @@ __all__ = ["logger", "__version__", "STATUS_NAMES", "RefractiveField", "build_mu
            "home_hops_cartesian_gradient", "home_hops_spherical_gradient",
            "skip_distance_hops_cartesian_gradient", "skip_distance_hops_spherical_gradient",
            "muf_hops_cartesian_gradient", "muf_hops_spherical_gradient", "residual_VH_many", "brute_force_fit_many",
-           "minimize_parameters_many"]
+           "minimize_parameters_many", "fit_profiles_lm"]

@@ -30,6 +30,19 @@ class Segment(ctypes.Structure):
                 ("mult_offset", ctypes.c_int64), ("out_offset", ctypes.c_int64)]
 
 
+class LmOptions(ctypes.Structure):
+    """``prhf_lm_options`` of include/prhf.h."""
+    _fields_ = [("max_iter", ctypes.c_int32), ("reserved", ctypes.c_int32), ("lambda0", ctypes.c_double),
+                ("lambda_up", ctypes.c_double), ("lambda_down", ctypes.c_double), ("step_max", ctypes.c_double),
+                ("ftol", ctypes.c_double), ("xtol", ctypes.c_double)]
+
+
+# statuses of prhf_vfo_lm_fit_f64 (PRHF_LM_* of include/prhf.h)
+LM_RUNNING, LM_CONVERGED_F, LM_CONVERGED_X, LM_SINGULAR, LM_NO_DATA, LM_NO_COST = range(6)
+LM_MAX_TANGENTS = 8
+LM_FIT_COUNTERS = 3
+
+
 class NativeLibraryError(RuntimeError):
     """libprhf.so is missing, stale, or the HIP runtime failed."""
 
@@ -61,6 +74,12 @@ _PROTOTYPES = {
         ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
         ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
         ctypes.c_uint32]),
+    "prhf_vfo_lm_fit_f64": (ctypes.c_int, [
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
+        ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_void_p] * 10 + [ctypes.c_uint32]),
+    "prhf_lm_fit_counters": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
     "prhf_vfo_worklist_f64": (ctypes.c_int, [
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
         ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
@@ -596,6 +615,24 @@ class Context:
         n = ctypes.c_uint64(0)
         raise_for(self._lib.prhf_stream_launches(self._h, ctypes.byref(n)))
         return int(n.value)
+
+    def vfo_lm_fit(self, freq, n_freq, den0, bmag, bpsi, alt, n_iono, n_alt, den0_stride, alt_stride, mult, n_points, mode,
+                   basis, n_tan, basis_stride, vh_obs, c0, prior_weight, options, c_out, cost_out, status_out, n_eval_out,
+                   n_accept_out, lambda_out, den_out, vh_out, history_out, state_out, flags):
+        """Levenberg-Marquardt fits of ``n_iono`` ionograms in a basis of ``n_tan`` log-density perturbations;
+        ``options`` an ``LmOptions`` or None, ``c0``, ``prior_weight``, ``history_out``, ``state_out`` may be None."""
+        return self._lib.prhf_vfo_lm_fit_f64(self._h, freq, n_freq, den0, bmag, bpsi, alt, n_iono, n_alt, den0_stride,
+                                             alt_stride, mult, n_points, mode, basis, n_tan, basis_stride, vh_obs, c0,
+                                             prior_weight, ctypes.addressof(options) if options is not None else None,
+                                             c_out, cost_out, status_out, n_eval_out, n_accept_out, lambda_out, den_out,
+                                             vh_out, history_out, state_out, flags)
+
+    def lm_fit_counters(self):
+        """(evaluations enqueued, timed launches enqueued, times the host waited for the stream) of this context's last
+        ``vfo_lm_fit`` (include/prhf.h)."""
+        buf = (ctypes.c_uint64 * LM_FIT_COUNTERS)()
+        raise_for(self._lib.prhf_lm_fit_counters(self._h, buf))
+        return tuple(int(v) for v in buf)
 
     def occupancy(self, n_alt, math):
         n = ctypes.c_int32(0)

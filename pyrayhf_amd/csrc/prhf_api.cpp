@@ -23,6 +23,7 @@
 #include "prhf_arena.h"       // Carver: a scratch buffer's layout stated once, for its size and its pointers
 #include "prhf_layouts.h"     // ... the arena's blocks of the operator and the stage ops
 #include "prhf_plan.h"        // Knobs, plan_launch, StatusWord: the launch planning, HIP-free
+#include "prhf_lm_step.h"     // the Levenberg-Marquardt rule's statuses and limits (prhf_vfo_lm_fit_f64)
 
 namespace {
 
@@ -174,6 +175,8 @@ struct prhf_ctx {
     uint64_t grad_home_counters[PRHF_GRAD_HOME_COUNTERS] = {};   // of the last prhf_gradient_home_f64 (prhf_gradient_home_counters)
     DevBuf fields;    // prhf_gradient_muf_f64: mu, mu' and the records of every link's field (48 bytes per node and link)
     uint64_t grad_skip_counters[PRHF_GRAD_SKIP_COUNTERS + 1] = {};   // of the last skip / MUF call of the gradient tracers, one-hop or chain; [4]: hop rays
+    uint64_t host_waits = 0;        // times the host waited for the stream: prhf_sync, the peak pre-pass, a buffer that grew (ensure)
+    uint64_t lm_counters[PRHF_LM_FIT_COUNTERS] = {};   // of the last prhf_vfo_lm_fit_f64 (prhf_lm_fit_counters)
 };
 
 namespace {
@@ -181,6 +184,7 @@ namespace {
 int ensure(prhf_ctx* c, DevBuf& b, size_t bytes) {
     if (bytes <= b.cap) return PRHF_OK;
     if (b.p) {
+        ++c->host_waits;
         HIP_TRY(hipStreamSynchronize(c->stream));
         HIP_TRY(hipFree(b.p));
         b.p = nullptr;
@@ -438,6 +442,7 @@ int highest_peak(prhf_ctx* c, const double* den, int64_t n_prof, int64_t n_alt, 
         HIP_TRY(prhf::launch_peak_levels(den, n_prof, n_alt, prof_stride, c->d_status + kWordPeak, c->stream));
         unsigned peak = 0;
         HIP_TRY(hipMemcpyAsync(&peak, c->d_status + kWordPeak, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+        ++c->host_waits;
         HIP_TRY(hipStreamSynchronize(c->stream));
         max_peak = peak;
     } else {
@@ -1443,6 +1448,192 @@ int prhf_vfo_jvp_f64(prhf_ctx* ctx, const double* freq_mhz, int64_t n_freq, cons
     const OperatorInputs in{freq_mhz, n_freq, den, bmag, bpsi, alt, n_prof, n_alt, prof_stride_elems, alt_stride_elems,
                             multiplier, n_points, mode, flags};
     return jvp_run(ctx, in, tangents, n_tan, tan_prof_stride_elems, vh_out, dvh_out);
+}
+
+namespace {
+
+static_assert(PRHF_LM_RUNNING == prhf_lm::kRunning && PRHF_LM_CONVERGED_F == prhf_lm::kConvergedF &&
+              PRHF_LM_CONVERGED_X == prhf_lm::kConvergedX && PRHF_LM_SINGULAR == prhf_lm::kSingular &&
+              PRHF_LM_NO_DATA == prhf_lm::kNoData && PRHF_LM_NO_COST == prhf_lm::kNoCost &&
+              PRHF_LM_MAX_TANGENTS == prhf_lm::kMaxT, "prhf.h and prhf_lm_step.h name the same statuses");
+
+// What prhf_vfo_lm_fit_f64 fits with and where its results go
+struct LmProblem {
+    const double* basis;
+    int64_t n_tan, basis_stride;
+    const double *vh_obs, *c0, *prior;
+    prhf_lm_options opt;
+    double *c, *cost;
+    int32_t *status, *n_eval, *n_accept;
+    double *lambda, *den, *vh, *history, *state;
+};
+
+int check_lm_options(const prhf_lm_options& o) {
+    if (o.max_iter < 1 || o.max_iter > (1 << 20))
+        return fail(PRHF_EINVAL, "max_iter %d outside [1, %d]", (int)o.max_iter, 1 << 20);
+    if (!(o.lambda0 > 0.0 && o.lambda0 < HUGE_VAL)) return fail(PRHF_EINVAL, "lambda0 must be positive and finite");
+    if (!(o.lambda_up > 1.0 && o.lambda_up < HUGE_VAL)) return fail(PRHF_EINVAL, "lambda_up must be greater than 1 and finite");
+    if (!(o.lambda_down >= 1.0 && o.lambda_down < HUGE_VAL)) return fail(PRHF_EINVAL, "lambda_down must be at least 1 and finite");
+    if (!(o.step_max > 0.0)) return fail(PRHF_EINVAL, "step_max must be positive");
+    if (!(o.ftol >= 0.0) || !(o.xtol >= 0.0)) return fail(PRHF_EINVAL, "ftol and xtol must not be negative");
+    return PRHF_OK;
+}
+
+// prhf_vfo_lm_fit_f64: check; carve the arena (host buffers: inputs and results too) and upload once; per evaluation
+// the trial columns, jvp_run on them - the operator's launch and the JVP's, asynchronous on device pointers - and the
+// step; the column at the result; download once; one synchronisation.  `in`: the operator's arguments with den0 as den
+// and den0's stride (0: one column) as prof_stride.
+int lm_run(prhf_ctx* c, const OperatorInputs& in, const LmProblem& q) {
+    if (!c) return fail(PRHF_EINVAL, "null context");
+    if (q.n_tan < 1 || q.n_tan > PRHF_LM_MAX_TANGENTS)
+        return fail(PRHF_EINVAL, "n_tan %lld outside [1, %d]: the basis goes through the JVP kernel in one pass", (long long)q.n_tan,
+                    PRHF_LM_MAX_TANGENTS);
+    const bool outputs = q.c && q.cost && q.status && q.n_eval && q.n_accept && q.lambda && q.den && q.vh;
+    PRHF_TRY(check_arrays(c, in, q.basis && q.vh_obs && outputs));
+    if (in.n_freq < 1 || in.n_prof < 0 || in.n_alt < 1 || in.n_points < 1) return fail(PRHF_EINVAL, "bad shape");
+    if (in.n_alt > kMaxAltTall)
+        return fail(PRHF_EINVAL, "n_alt %lld exceeds the limit of %lld levels", (long long)in.n_alt, kMaxAltTall);
+    if (in.n_freq > (1 << 20) || in.n_prof > 0x7fffffffLL) return fail(PRHF_EINVAL, "n_freq or n_iono too large");
+    if ((in.prof_stride != 0 && in.prof_stride < in.n_alt) || (in.alt_stride != 0 && in.alt_stride < in.n_alt) ||
+        (q.basis_stride != 0 && q.basis_stride < q.n_tan * in.n_alt))
+        return fail(PRHF_EINVAL, "row stride shorter than a row");
+    if (in.mode != PRHF_MODE_O && in.mode != PRHF_MODE_X) return fail(PRHF_EINVAL, "mode must be 'O' or 'X'");
+    PRHF_TRY(check_flags(in));
+    PRHF_TRY(check_lm_options(q.opt));
+    const bool dev = in.dev();
+    if (!dev) {
+        const prhf_segment seg = whole_batch(in.n_prof, in.mode, in.n_points);
+        PRHF_TRY(check_grid(in.mult, in.n_points, &seg, 1));
+        if (q.prior)
+            for (int64_t t = 0; t < q.n_tan; ++t)
+                if (!(q.prior[t] >= 0.0)) return fail(PRHF_EINVAL, "prior_weight[%lld] is negative or NaN", (long long)t);
+    }
+    std::fill(c->lm_counters, c->lm_counters + PRHF_LM_FIT_COUNTERS, 0);
+    if (in.n_prof == 0) return PRHF_OK;
+    ENTER_DEVICE(c->device);
+    const uint64_t waits0 = c->host_waits;
+    const unsigned long long timed0 = c->n_timed;
+
+    const size_t I = (size_t)in.n_prof, F = (size_t)in.n_freq, A = (size_t)in.n_alt, T = (size_t)q.n_tan, NA = T * (T + 1) / 2;
+    const size_t n_iter = (size_t)q.opt.max_iter, state_elems = T * T + 2 * T;
+    const size_t den0_rows = in.prof_stride ? I : 1, field_rows = in.shared_field() ? 1 : I, alt_rows = in.alt_stride ? I : 1;
+    const size_t basis_sets = q.basis_stride ? I : 1;
+    // the inputs and results on the device: the caller's own, or the arena's copies
+    OperatorInputs d = in;
+    LmProblem r = q;
+    double *den = nullptr, *tan = nullptr, *vh_eval = nullptr, *dvh = nullptr, *c_eval = nullptr, *nA = nullptr, *g = nullptr,
+           *delta = nullptr;
+    PRHF_TRY(carve(c, c->arena, [&](Stager& k) {
+        den = k.take<double>(I * A);
+        tan = k.take<double>(I * T * A);
+        vh_eval = k.take<double>(I * F);
+        dvh = k.take<double>(I * F * T);
+        c_eval = k.take<double>(I * T);
+        nA = k.take<double>(I * NA);
+        g = k.take<double>(I * T);
+        delta = k.take<double>(I * T);
+        if (dev) return;
+        double* p;
+        k.put(p = k.take<double>(F), in.freq, F); d.freq = p;
+        k.put_rows(p = k.take<double>(den0_rows * A), in.den, A, den0_rows, in.prof_stride); d.den = p;
+        k.put_rows(p = k.take<double>(field_rows * A), in.bmag, A, field_rows, (int64_t)A); d.bmag = p;
+        k.put_rows(p = k.take<double>(field_rows * A), in.bpsi, A, field_rows, (int64_t)A); d.bpsi = p;
+        k.put_rows(p = k.take<double>(alt_rows * A), in.alt, A, alt_rows, in.alt_stride); d.alt = p;
+        k.put(p = k.take<double>((size_t)in.n_points), in.mult, (size_t)in.n_points); d.mult = p;
+        k.put_rows(p = k.take<double>(basis_sets * T * A), q.basis, T * A, basis_sets, q.basis_stride); r.basis = p;
+        k.put(p = k.take<double>(I * F), q.vh_obs, I * F); r.vh_obs = p;
+        r.prior = k.put<double>(q.prior, q.prior ? T : 0);
+        r.c = k.take<double>(I * T);
+        r.cost = k.take<double>(I);
+        r.lambda = k.take<double>(I);
+        r.den = k.take<double>(I * A);
+        r.vh = k.take<double>(I * F);
+        r.history = k.take<double>(q.history ? I * n_iter : 0);
+        r.state = k.take<double>(q.state ? I * state_elems : 0);
+        r.status = k.take<int32_t>(I);
+        r.n_eval = k.take<int32_t>(I);
+        r.n_accept = k.take<int32_t>(I);
+    }));
+    if (!dev) {
+        if (!q.history) r.history = nullptr;
+        if (!q.state) r.state = nullptr;
+        d.prof_stride = in.prof_stride ? (int64_t)A : 0;
+        d.alt_stride = in.alt_stride ? (int64_t)A : 0;
+        r.basis_stride = q.basis_stride ? (int64_t)(T * A) : 0;
+    }
+    // the start: c0, or zeros (all-zero bytes)
+    if (q.c0) HIP_TRY(hipMemcpyAsync(c_eval, q.c0, I * T * 8, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
+    else HIP_TRY(hipMemsetAsync(c_eval, 0, I * T * 8, c->stream));
+    if (r.state) HIP_TRY(hipMemsetAsync(r.state, 0, I * state_elems * 8, c->stream));
+
+    // the operator and the JVP read the trial columns: packed rows of the arena, device pointers, nothing waits
+    OperatorInputs trial = d;
+    trial.den = den;
+    trial.prof_stride = (int64_t)A;
+    trial.flags = PRHF_FLAG_DEVICE_PTRS | PRHF_FLAG_ASYNC | (in.flags & PRHF_FLAG_SHARED_FIELD) |
+                  (dev ? (in.flags & PRHF_FLAG_GRID_STABLE) : 0u);
+    prhf::LmSynthArgs sy = {};
+    sy.den0 = d.den; sy.basis = r.basis; sy.c = c_eval; sy.status = nullptr; sy.den = den; sy.tan = tan;
+    sy.n_iono = in.n_prof; sy.n_alt = in.n_alt; sy.den0_stride = d.prof_stride; sy.basis_stride = r.basis_stride;
+    sy.n_tan = (int)T;
+    prhf::LmStepArgs st = {};
+    st.vh_obs = r.vh_obs; st.vh_eval = vh_eval; st.dvh = dvh; st.prior = r.prior;
+    st.c = r.c; st.c_eval = c_eval; st.A = nA; st.g = g; st.delta = delta; st.cost = r.cost; st.lambda = r.lambda;
+    st.status = r.status; st.n_eval = r.n_eval; st.n_accept = r.n_accept;
+    st.vh_fit = r.vh; st.history = r.history; st.state_out = r.state;
+    st.n_iono = in.n_prof; st.n_freq = (int)F; st.n_tan = (int)T; st.max_iter = q.opt.max_iter;
+    st.lambda0 = q.opt.lambda0; st.lambda_up = q.opt.lambda_up; st.lambda_down = q.opt.lambda_down;
+    st.step_max = q.opt.step_max; st.ftol = q.opt.ftol; st.xtol = q.opt.xtol;
+    for (int k = 0; k < q.opt.max_iter; ++k) {
+        sy.frozen = k > 0 ? r.status : nullptr;              // (a frozen ionogram's column and tangents stand from before)
+        PRHF_TRY(timed_launch(c, false, [&] { return prhf::launch_lm_synth(sy, c->stream); }));
+        PRHF_TRY(jvp_run(c, trial, tan, (int64_t)T, (int64_t)(T * A), vh_eval, dvh));
+        st.k = k;
+        PRHF_TRY(timed_launch(c, false, [&] { return prhf::launch_lm_step(st, c->stream); }));
+        ++c->lm_counters[0];
+    }
+    sy.c = r.c; sy.status = r.status; sy.frozen = nullptr; sy.den = r.den; sy.tan = nullptr;
+    PRHF_TRY(timed_launch(c, false, [&] { return prhf::launch_lm_synth(sy, c->stream); }));
+    if (!dev) {
+        HIP_TRY(download(c, q.c, r.c, I * T * 8));
+        HIP_TRY(download(c, q.cost, r.cost, I * 8));
+        HIP_TRY(download(c, q.lambda, r.lambda, I * 8));
+        HIP_TRY(download(c, q.den, r.den, I * A * 8));
+        HIP_TRY(download(c, q.vh, r.vh, I * F * 8));
+        if (q.history) HIP_TRY(download(c, q.history, r.history, I * n_iter * 8));
+        if (q.state) HIP_TRY(download(c, q.state, r.state, I * state_elems * 8));
+        HIP_TRY(download(c, q.status, r.status, I * 4));
+        HIP_TRY(download(c, q.n_eval, r.n_eval, I * 4));
+        HIP_TRY(download(c, q.n_accept, r.n_accept, I * 4));
+    }
+    const int rc = (in.flags & PRHF_FLAG_ASYNC) ? PRHF_OK : prhf_sync(c);
+    c->lm_counters[1] = c->n_timed - timed0;
+    c->lm_counters[2] = c->host_waits - waits0;
+    return rc;
+}
+
+}  // namespace
+
+int prhf_vfo_lm_fit_f64(prhf_ctx* ctx, const double* freq_mhz, int64_t n_freq, const double* den0, const double* bmag,
+                        const double* bpsi, const double* alt, int64_t n_iono, int64_t n_alt, int64_t den0_stride_elems,
+                        int64_t alt_stride_elems, const double* multiplier, int32_t n_points, int32_t mode, const double* basis,
+                        int64_t n_tan, int64_t basis_prof_stride_elems, const double* vh_obs, const double* c0,
+                        const double* prior_weight, const prhf_lm_options* options, double* c_out, double* cost_out,
+                        int32_t* status_out, int32_t* n_eval_out, int32_t* n_accept_out, double* lambda_out, double* den_out,
+                        double* vh_out, double* cost_history_out, double* state_out, uint32_t flags) {
+    const OperatorInputs in{freq_mhz, n_freq, den0, bmag, bpsi, alt, n_iono, n_alt, den0_stride_elems, alt_stride_elems,
+                            multiplier, n_points, mode, flags};
+    const prhf_lm_options defaults = {20, 0, 1e-3, 10.0, 10.0, 1.0, 1e-10, 1e-10};
+    const LmProblem q = {basis, n_tan, basis_prof_stride_elems, vh_obs, c0, prior_weight, options ? *options : defaults,
+                         c_out, cost_out, status_out, n_eval_out, n_accept_out, lambda_out, den_out, vh_out,
+                         cost_history_out, state_out};
+    return lm_run(ctx, in, q);
+}
+
+int prhf_lm_fit_counters(prhf_ctx* c, uint64_t* counters) {
+    if (!c || !counters) return fail(PRHF_EINVAL, "null pointer");
+    std::copy(c->lm_counters, c->lm_counters + PRHF_LM_FIT_COUNTERS, counters);
+    return PRHF_OK;
 }
 
 int prhf_vfo_residual_f64(prhf_ctx* ctx, const double* freq_mhz, int64_t n_freq, const double* den,
@@ -2875,6 +3066,7 @@ int prhf_occupancy(prhf_ctx* c, int64_t n_alt, int32_t math, int32_t* workgroups
 int prhf_sync(prhf_ctx* c) {
     if (!c) return fail(PRHF_EINVAL, "null context");
     ENTER_DEVICE(c->device);
+    ++c->host_waits;
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (c->status_pending) {
         c->status_pending = false;

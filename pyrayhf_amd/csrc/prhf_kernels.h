@@ -647,6 +647,37 @@ hipError_t launch_residual_many(const ResidualManyArgs& a, hipStream_t stream);
 hipError_t launch_residual_best(const double* cost, const int* ionogram_of_row, long long n_rows, int n_iono, long long* best,
                                 double* best_cost, hipStream_t stream);
 
+// Levenberg-Marquardt fits of many ionograms in a reduced basis (prhf_lm.inc); device pointers.
+struct LmSynthArgs {
+    const double* den0;      // background columns, den0_stride doubles apart (0: one column for every ionogram)
+    const double* basis;     // n_tan rows of n_alt, basis_stride doubles between ionograms (0: one set)
+    const double* c;         // (n_iono, n_tan) coefficients
+    const int* status;       // (n_iono) or null; given: an ionogram whose status is PRHF_LM_NO_DATA gets a NaN column
+    const int* frozen;       // (n_iono) statuses or null; given: an ionogram that is not PRHF_LM_RUNNING is left as it stands
+    double* den;             // (n_iono, n_alt): den0 exp(sum_t c_t B_t)
+    double* tan;             // (n_iono, n_tan, n_alt): den B_t, or null
+    long long n_iono, n_alt, den0_stride, basis_stride;
+    int n_tan;
+};
+hipError_t launch_lm_synth(const LmSynthArgs& a, hipStream_t stream);
+struct LmStepArgs {
+    const double* vh_obs;    // (n_iono, n_freq), NaN: no observation
+    const double* vh_eval;   // (n_iono, n_freq): the operator at c_eval
+    const double* dvh;       // (n_iono, n_freq, n_tan): its JVP along den B_t
+    const double* prior;     // (n_tan) or null
+    // one ionogram's state (prhf_lm_step.h); at k = 0 only c_eval is read (the start)
+    double *c, *c_eval, *A, *g, *delta, *cost, *lambda;    // (n_iono, n_tan) x 2, (n_iono, n_tan (n_tan + 1) / 2), (n_iono, n_tan) x 2, (n_iono) x 2
+    int *status, *n_eval, *n_accept;
+    double* vh_fit;          // (n_iono, n_freq): the trace of the accepted point
+    double* history;         // (n_iono, max_iter) accepted cost after every evaluation, or null
+    double* state_out;       // (n_iono, n_tan^2 + 2 n_tan): A in full, g, delta, of every ionogram still running, or null
+    long long n_iono;
+    int n_freq, n_tan, k;    // k: the evaluation, 0 ... max_iter - 1
+    int max_iter;
+    double lambda0, lambda_up, lambda_down, step_max, ftol, xtol;
+};
+hipError_t launch_lm_step(const LmStepArgs& a, hipStream_t stream);
+
 }  // namespace prhf
 
 #endif

@@ -27,6 +27,7 @@
 
 #include "prhf_crmath.h"
 #include "prhf_kernels.h"
+#include "prhf_lm_step.h"      // the Levenberg-Marquardt rule of prhf_lm.inc, HIP-free
 
 namespace prhf {
 
@@ -4331,6 +4332,7 @@ hipError_t launch_vfo_shortx(const KArgs& a, long long grid_blocks, size_t lds_b
 #include "prhf_gradient_skip.inc"
 #include "prhf_vjp.inc"
 #include "prhf_jvp.inc"
+#include "prhf_lm.inc"
 
 // The streaming form: `grid_blocks` workgroups of PRHF_STREAM_THREADS with two slots of lds_bytes_for(a.lds_levels) each;
 // a.queue set, one slice, X mode, fast tier (plan_launch decides)

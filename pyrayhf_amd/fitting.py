@@ -17,6 +17,8 @@ fixture; ``tests/test_gpu_fitting.py`` holds this module to those rows.
 
 from __future__ import annotations
 
+import collections
+
 import numpy as np
 
 from . import _native
@@ -24,7 +26,8 @@ from .library import _mode_code, _multiplier, _as_rows, _is_torch, _device_grid,
 
 __all__ = ["residual_VH_batch", "brute_force_fit", "peak_density_from_trace", "brute_grid", "minimize_parameters",
            "resolve_method", "BoundedPair", "pyiri_edp_builder", "model_VH", "trace_sensitivity", "residual_VH", "residual_VH_many",
-           "brute_force_fit_many", "minimize_parameters_many"]
+           "brute_force_fit_many", "minimize_parameters_many", "fit_profiles_lm", "LmFit", "LM_RUNNING", "LM_CONVERGED_F",
+           "LM_CONVERGED_X", "LM_SINGULAR", "LM_NO_DATA", "LM_NO_COST", "LM_STATUS_NAMES"]
 
 
 def pyiri_edp_builder(F2, F1, E, alt, bottom_type='B_bot'):
@@ -748,6 +751,157 @@ def brute_force_fit_many(freq, vh_obs, den_candidates, bmag, bpsi, alt, mode='O'
     return best, best_cost, vh_best, f
 
 
+# ----------------------------------------------------------------------------------------
+# Levenberg-Marquardt fits of many ionograms in a reduced basis, on the device
+# ----------------------------------------------------------------------------------------
+LM_RUNNING, LM_CONVERGED_F, LM_CONVERGED_X = _native.LM_RUNNING, _native.LM_CONVERGED_F, _native.LM_CONVERGED_X
+LM_SINGULAR, LM_NO_DATA, LM_NO_COST = _native.LM_SINGULAR, _native.LM_NO_DATA, _native.LM_NO_COST
+LM_STATUS_NAMES = {LM_RUNNING: "RUNNING", LM_CONVERGED_F: "CONVERGED_F", LM_CONVERGED_X: "CONVERGED_X",
+                   LM_SINGULAR: "SINGULAR", LM_NO_DATA: "NO_DATA", LM_NO_COST: "NO_COST"}
+
+LmFit = collections.namedtuple("LmFit", "c cost status n_eval n_accept lam den vh cost_history state")
+
+
+def _lm_shapes(den_shape, basis_shape, bmag_shape, bpsi_shape, alt_shape, obs_shape, c0_shape, prior):
+    """The shapes of a ``fit_profiles_lm`` call, checked: ``(I, N_alt, T, per-ionogram den0, per-ionogram basis, one field
+    row)``; ``prior`` is the host array of weights or None."""
+    n_iono, n_alt = int(obs_shape[0]), int(den_shape[-1])
+    if len(den_shape) not in (1, 2) or n_alt < 1 or (len(den_shape) == 2 and den_shape[0] != n_iono):
+        raise ValueError("den0 must be (N_alt,) or (I, N_alt), one row per ionogram of vh_obs")
+    if len(basis_shape) not in (2, 3) or basis_shape[-1] != n_alt or (len(basis_shape) == 3 and basis_shape[0] != n_iono):
+        raise ValueError("basis must be (T, N_alt) or (I, T, N_alt)")
+    n_tan = int(basis_shape[-2])
+    if not 1 <= n_tan <= _native.LM_MAX_TANGENTS:
+        raise ValueError(f"basis has {n_tan} rows: 1 to {_native.LM_MAX_TANGENTS} directions are fitted")
+    if tuple(bmag_shape) != tuple(bpsi_shape) or tuple(bmag_shape) not in ((n_alt,), (n_iono, n_alt)):
+        raise ValueError("bmag and bpsi must both be (N_alt,) or (I, N_alt)")
+    if tuple(alt_shape) != (n_alt,):
+        raise ValueError("alt must be 1-D with one value per density level")
+    if c0_shape is not None and tuple(c0_shape) not in ((n_tan,), (n_iono, n_tan)):
+        raise ValueError("c0 must be (T,) or (I, T)")
+    if prior is not None:
+        if prior.shape != (n_tan,):
+            raise ValueError("prior_weight must be (T,)")
+        if not np.all(prior >= 0.0):
+            raise ValueError("prior_weight must not be negative or NaN")
+    return n_iono, n_alt, n_tan, len(den_shape) == 2, len(basis_shape) == 3, len(bmag_shape) == 1
+
+
+def fit_profiles_lm(freq, vh_obs, den0, bmag, bpsi, alt, basis, mode='O', n_points=200, *, c0=None, prior_weight=None,
+                    max_iter=20, lambda0=1e-3, step_max=1.0, ftol=1e-10, xtol=1e-10, return_history=False,
+                    return_state=False, device=None):
+    """Fit MANY ionograms on one common frequency grid by Levenberg-Marquardt, each in a small basis of log-density
+    perturbations of a background column, in one call: ``den_i(c) = den0_i * exp(sum_t c_t * basis_t)``.  Every
+    evaluation - trial columns, operator, its JVP along ``den * basis_t``, the damped step with its accept / reject
+    decision - is enqueued on the GPU back to back; nothing visits the host in between.
+
+    ``freq`` (F,) the common grid [MHz] (sorted here, the columns of ``vh_obs`` with it); ``vh_obs`` (I, F) [km], NaN
+    where an ionogram has no echo.  ``den0`` (N_alt,) or (I, N_alt); ``basis`` (T, N_alt) shared or (I, T, N_alt),
+    1 <= T <= 8; ``bmag``, ``bpsi`` (N_alt,) or (I, N_alt); ``alt`` (N_alt,).  ``c0`` (T,) or (I, T): the start (zeros).
+    ``prior_weight`` (T,) >= 0 adds ``sum_t w_t c_t^2`` to the cost (the background term of an assimilation).
+    The cost is ``residual_VH_many``'s on the kept frequencies, plus the prior.  The rule - damping ``lambda0`` times or
+    over 10 per rejected or accepted evaluation, steps capped at ``step_max``, ``ftol`` on the relative gain of an
+    accepted evaluation, ``xtol`` on the step - is stated in include/prhf.h and ``pyrayhf_amd/csrc/prhf_lm_step.h``.
+
+    Returns ``LmFit(c (I, T), cost (I,), status (I,) int32, n_eval, n_accept (I,) int32, lam (I,), den (I, N_alt),
+    vh (I, F), cost_history, state)``: ``status`` is one of ``LM_RUNNING`` (``max_iter`` evaluations made),
+    ``LM_CONVERGED_F``, ``LM_CONVERGED_X``, ``LM_SINGULAR``, ``LM_NO_DATA`` (no finite observation: ``c`` is the start,
+    ``cost``, ``den`` and ``vh`` are NaN), ``LM_NO_COST`` (the cost at the start is not finite); ``vh`` is the operator's
+    trace of ``den`` on the ASCENDING grid, bit for bit; ``cost_history`` (I, max_iter) with ``return_history`` - the
+    accepted cost after every evaluation, never increasing - else None; ``state`` (I, T*T + 2*T) with ``return_state`` -
+    the normal matrix and the gradient of the accepted point, and the last step that was computed - else None.  An
+    ionogram's results do not depend on the others.
+    NumPy inputs, or a GPU-resident torch ``den0`` (results are tensors on its device), as ``residual_VH_many``.
+
+    A grid frequency next to a layer's critical frequency (E-layer cusp, foF2) makes the cost discontinuous in ``c``;
+    the fit then stalls at the jump.  Keep such frequencies out of ``vh_obs`` (NaN) where the background is that close.
+    """
+    code = _mode_code(mode)
+    if int(max_iter) < 1:
+        raise ValueError("max_iter must be at least 1")
+    on_gpu = _is_torch(den0) and den0.is_cuda
+    if _is_torch(vh_obs) and not on_gpu:
+        vh_obs = vh_obs.detach().cpu().numpy()
+    elif _is_torch(vh_obs) and vh_obs.device != den0.device:
+        vh_obs = vh_obs.to(den0.device)
+    f, obs, _ = _common_grid(freq, vh_obs)
+    prior = None if prior_weight is None else np.ascontiguousarray(
+        np.asarray(prior_weight.detach().cpu().numpy() if _is_torch(prior_weight) else prior_weight, dtype=np.float64))
+    opt = _native.LmOptions(int(max_iter), 0, float(lambda0), 10.0, 10.0, float(step_max), float(ftol), float(xtol))
+    if on_gpu:
+        return _torch_fit_lm(f, obs, den0, bmag, bpsi, alt, basis, code, n_points, c0, prior, opt, return_history,
+                             return_state)
+    d, B = _as_rows("den0", den0), np.ascontiguousarray(np.asarray(basis), dtype=np.float64)
+    b2, p2, a = _as_rows("bmag", bmag), _as_rows("bpsi", bpsi), _as_rows("alt", alt)
+    start = None if c0 is None else np.ascontiguousarray(np.asarray(c0), dtype=np.float64)
+    n_iono, n_alt, n_tan, own_den, own_basis, one_field = _lm_shapes(
+        d.shape, B.shape, b2.shape, p2.shape, a.shape, obs.shape, None if start is None else start.shape, prior)
+    if start is not None and start.ndim == 1:
+        start = np.ascontiguousarray(np.broadcast_to(start, (n_iono, n_tan)))
+    mult = _multiplier(n_points)
+    c = np.empty((n_iono, n_tan))
+    cost, lam = np.empty(n_iono), np.empty(n_iono)
+    status, n_eval, n_accept = (np.empty(n_iono, dtype=np.int32) for _ in range(3))
+    den, vh = np.empty((n_iono, n_alt)), np.empty((n_iono, f.size))
+    history = np.empty((n_iono, opt.max_iter)) if return_history else None
+    state = np.empty((n_iono, n_tan * n_tan + 2 * n_tan)) if return_state else None
+    ctx = _native.host_context(device)
+    ctx.set_math(MATH_AUTO)
+    _native.raise_for(ctx.vfo_lm_fit(
+        f.ctypes.data, f.size, d.ctypes.data, b2.ctypes.data, p2.ctypes.data, a.ctypes.data, n_iono, n_alt,
+        n_alt if own_den else 0, 0, mult.ctypes.data, int(n_points), code, B.ctypes.data, n_tan,
+        n_tan * n_alt if own_basis else 0, obs.ctypes.data, None if start is None else start.ctypes.data,
+        None if prior is None else prior.ctypes.data, opt, c.ctypes.data, cost.ctypes.data, status.ctypes.data,
+        n_eval.ctypes.data, n_accept.ctypes.data, lam.ctypes.data, den.ctypes.data, vh.ctypes.data,
+        history.ctypes.data if return_history else None, state.ctypes.data if return_state else None,
+        _native.FLAG_SHARED_FIELD if one_field else 0))
+    return LmFit(c, cost, status, n_eval, n_accept, lam, den, vh, history, state)
+
+
+def _torch_fit_lm(f, obs, den0, bmag, bpsi, alt, basis, code, n_points, c0, prior, opt, return_history, return_state):
+    import torch
+
+    dev = den0.device
+
+    def prep(x, name):
+        if not _is_torch(x):
+            x = torch.as_tensor(np.asarray(x, dtype=np.float64), device=dev)
+        if x.device != dev:
+            raise ValueError(f"{name} is on {x.device}, expected {dev}")
+        return x.detach().to(torch.float64).contiguous()
+
+    freq, obs = prep(f, "freq"), prep(obs, "vh_obs")
+    d, B, b2, p2, a = (prep(x, n) for x, n in ((den0, "den0"), (basis, "basis"), (bmag, "bmag"), (bpsi, "bpsi"), (alt, "alt")))
+    start = None if c0 is None else prep(c0, "c0")
+    n_iono, n_alt, n_tan, own_den, own_basis, one_field = _lm_shapes(
+        d.shape, B.shape, b2.shape, p2.shape, a.shape, obs.shape, None if start is None else start.shape, prior)
+    if start is not None and start.dim() == 1:
+        start = start.expand(n_iono, n_tan).contiguous()
+    w = None if prior is None else torch.as_tensor(prior, device=dev)
+    mult, grid_flag = _device_grid((int(n_points),), dev)
+    n_freq = freq.numel()
+
+    def new(*shape, dtype=torch.float64):
+        return torch.empty(shape, dtype=dtype, device=dev)
+
+    c, cost, lam, den, vh = new(n_iono, n_tan), new(n_iono), new(n_iono), new(n_iono, n_alt), new(n_iono, n_freq)
+    status, n_eval, n_accept = (new(n_iono, dtype=torch.int32) for _ in range(3))
+    history = new(n_iono, opt.max_iter) if return_history else None
+    state = new(n_iono, n_tan * n_tan + 2 * n_tan) if return_state else None
+    ctx = _native.context(dev.index if dev.index is not None else torch.cuda.current_device())
+    ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+    ctx.set_math(MATH_AUTO)
+    _native.raise_for(ctx.vfo_lm_fit(
+        freq.data_ptr(), n_freq, d.data_ptr(), b2.data_ptr(), p2.data_ptr(), a.data_ptr(), n_iono, n_alt,
+        n_alt if own_den else 0, 0, mult.data_ptr(), int(n_points), code, B.data_ptr(), n_tan,
+        n_tan * n_alt if own_basis else 0, obs.data_ptr(), None if start is None else start.data_ptr(),
+        None if w is None else w.data_ptr(), opt, c.data_ptr(), cost.data_ptr(), status.data_ptr(), n_eval.data_ptr(),
+        n_accept.data_ptr(), lam.data_ptr(), den.data_ptr(), vh.data_ptr(),
+        history.data_ptr() if return_history else None, state.data_ptr() if return_state else None,
+        _native.FLAG_DEVICE_PTRS | grid_flag | (_native.FLAG_SHARED_FIELD if one_field else 0)))
+    return LmFit(c, cost, status, n_eval, n_accept, lam, den, vh, history, state)
+
+
 def minimize_parameters_many(F2s, F1s, Es, freq, vh_obs, alt, b_mag, b_psi, percent_sigma=20., step=1., mode='O',
                              n_points=200, bottom_type='B_bot', *, edp_builder=None, method='brute', device=None,
                              math=None):
@@ -760,12 +914,14 @@ def minimize_parameters_many(F2s, F1s, Es, freq, vh_obs, alt, b_mag, b_psi, perc
     (``peak_density_from_trace``), candidates on ``brute_grid`` around its own initial values (so the groups are ragged),
     the first node of the smallest cost wins, and the result trace is evaluated at the grid frequencies as given
     (one batched operator call for all ionograms).  Returns a list of ``(vh_result, EDP_result, F2_fit)``.
-    Only the brute-force search is batched: for any other ``method`` call ``minimize_parameters`` per ionogram."""
+    Only the brute-force search is batched: for any other ``method`` call ``minimize_parameters`` per ionogram.
+    For a derivative-based batched fit of density columns in a reduced basis see ``fit_profiles_lm``."""
     from copy import deepcopy
 
     if resolve_method(method)[0] != 'brute':
         raise NotImplementedError(f"method={method!r}: minimize_parameters_many batches the brute-force search only; "
-                                  "call minimize_parameters per ionogram for the other methods")
+                                  "call minimize_parameters per ionogram for the other methods "
+                                  "(fit_profiles_lm is the derivative-based batched fit, in a reduced basis)")
     if bottom_type not in ('B_bot', 'B0_B1'):
         raise ValueError("bottom_type must be 'B_bot' or 'B0_B1'")
     n_iono = len(F2s)

@@ -376,7 +376,7 @@ int prhf_vfo_jvp_f64(prhf_ctx* ctx,
  * for ONE background column; bmag and bpsi are one row each with PRHF_FLAG_SHARED_FIELD, else n_iono packed rows of n_alt
  * doubles; alt_stride_elems as for the operator.  basis: n_tan rows of n_alt doubles, basis_prof_stride_elems between
  * two ionograms' sets (>= n_tan * n_alt), 0 for ONE set.  vh_obs (n_iono, n_freq).  c0 (n_iono, n_tan) or NULL: zeros.
- * prior_weight (n_tan), >= 0, or NULL: none.  options or NULL: the defaults of prhf_lm_options below.
+ * prior_weight (n_tan), finite, >= 0, or NULL: none.  options or NULL: the defaults of prhf_lm_options below.
  * Outputs: c_out (n_iono, n_tan), cost_out, lambda_out (n_iono) doubles; status_out, n_eval_out, n_accept_out (n_iono)
  * int32; den_out (n_iono, n_alt), the column at c_out; vh_out (n_iono, n_freq), the operator's trace of that column,
  * bit for bit; cost_history_out (n_iono, max_iter) or NULL: the accepted cost after every evaluation (a frozen
@@ -392,7 +392,7 @@ int prhf_vfo_jvp_f64(prhf_ctx* ctx,
  * Reproducible: every output row of ionogram i depends on that ionogram's inputs and the options only - not on the
  * other ionograms, their number, or repetition; no atomics, every sum in a fixed order.  Data errors of den0 surface as
  * in the operator.  PRHF_EINVAL before any device call: null context or array, n_tan outside [1, 8], a stride shorter
- * than its row, max_iter < 1 or an option outside its range, a negative or NaN prior_weight in host memory.
+ * than its row, max_iter < 1 or an option outside its range, a negative or non-finite prior_weight in host memory.
  * The cost is discontinuous where a grid frequency crosses a layer's critical frequency (E-layer cusp, foF2) between
  * two trial columns: the rule then stalls at the jump - it rejects until lambda is large - and reports what it reached.
  */

@@ -1506,7 +1506,8 @@ int lm_run(prhf_ctx* c, const OperatorInputs& in, const LmProblem& q) {
         PRHF_TRY(check_grid(in.mult, in.n_points, &seg, 1));
         if (q.prior)
             for (int64_t t = 0; t < q.n_tan; ++t)
-                if (!(q.prior[t] >= 0.0)) return fail(PRHF_EINVAL, "prior_weight[%lld] is negative or NaN", (long long)t);
+                if (!(q.prior[t] >= 0.0 && q.prior[t] < HUGE_VAL))
+                    return fail(PRHF_EINVAL, "prior_weight[%lld] is negative or not finite", (long long)t);
     }
     std::fill(c->lm_counters, c->lm_counters + PRHF_LM_FIT_COUNTERS, 0);
     if (in.n_prof == 0) return PRHF_OK;

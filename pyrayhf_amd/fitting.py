@@ -782,8 +782,8 @@ def _lm_shapes(den_shape, basis_shape, bmag_shape, bpsi_shape, alt_shape, obs_sh
     if prior is not None:
         if prior.shape != (n_tan,):
             raise ValueError("prior_weight must be (T,)")
-        if not np.all(prior >= 0.0):
-            raise ValueError("prior_weight must not be negative or NaN")
+        if not np.all((prior >= 0.0) & np.isfinite(prior)):
+            raise ValueError("prior_weight must be finite and not negative")
     return n_iono, n_alt, n_tan, len(den_shape) == 2, len(basis_shape) == 3, len(bmag_shape) == 1
 
 
@@ -798,7 +798,7 @@ def fit_profiles_lm(freq, vh_obs, den0, bmag, bpsi, alt, basis, mode='O', n_poin
     ``freq`` (F,) the common grid [MHz] (sorted here, the columns of ``vh_obs`` with it); ``vh_obs`` (I, F) [km], NaN
     where an ionogram has no echo.  ``den0`` (N_alt,) or (I, N_alt); ``basis`` (T, N_alt) shared or (I, T, N_alt),
     1 <= T <= 8; ``bmag``, ``bpsi`` (N_alt,) or (I, N_alt); ``alt`` (N_alt,).  ``c0`` (T,) or (I, T): the start (zeros).
-    ``prior_weight`` (T,) >= 0 adds ``sum_t w_t c_t^2`` to the cost (the background term of an assimilation).
+    ``prior_weight`` (T,) finite, >= 0 adds ``sum_t w_t c_t^2`` to the cost (the background term of an assimilation).
     The cost is ``residual_VH_many``'s on the kept frequencies, plus the prior.  The rule - damping ``lambda0`` times or
     over 10 per rejected or accepted evaluation, steps capped at ``step_max``, ``ftol`` on the relative gain of an
     accepted evaluation, ``xtol`` on the step - is stated in include/prhf.h and ``pyrayhf_amd/csrc/prhf_lm_step.h``.

@@ -1,5 +1,5 @@
 """The Levenberg-Marquardt rule of DESIGN.md section 4.16 in NumPy, driven by a callable: a helper of
-tests/test_lm_fit_host.py, tests/test_gpu_lm_fit.py and tools/bench_lm_fit.py, not a test.
+tests/test_lm_fit_host.py, tests/test_gpu_lm_fit.py, tests/test_gpu_lm_fit_edges.py and tools/bench_lm_fit.py, not a test.
 
 Every operation below is one float64 operation of pyrayhf_amd/csrc/prhf_lm_step.h, in the same order (no fused
 multiply-add; the sums over the frequencies in the wavefront's order: 64 lane sums over f = l, l + 64, ..., then the
@@ -174,3 +174,17 @@ def fit(evaluate, vh_obs, n_tan, c0=None, prior_weight=None, trace=None, **optio
             trace.append((c.copy(), c_eval.copy(), cost, lam, status))
     return dict(c=c, cost=cost, status=status, n_eval=n_eval, n_accept=n_accept, lam=lam, vh=vh_fit, history=history,
                 A=A, g=g, delta=delta)
+
+
+def capped_run(trace, step_max):
+    """The longest run of consecutive evaluations of a ``trace`` of ``fit`` whose step was scaled to ``step_max``: the
+    rule went on, and max |c_eval - c| equals ``step_max`` within an ulp of the largest number in the sum c + delta
+    (the step itself is not in the trace; c_eval = fl(c + delta) is within half an ulp of c_eval of the sum, and delta's
+    largest entry within an ulp of step_max)."""
+    best = run = 0
+    for c, c_eval, _, _, status in trace:
+        size = float(np.max(np.abs(c_eval - c)))
+        ulp = float(np.spacing(max(step_max, float(np.max(np.abs(c))), float(np.max(np.abs(c_eval))))))
+        run = run + 1 if (status == RUNNING and abs(size - step_max) <= ulp) else 0
+        best = max(best, run)
+    return best

@@ -17,59 +17,18 @@ import numpy as np
 import pytest
 
 import lm_rule
-from conftest import REPO, load_golden, same_bits
+from conftest import REPO, same_bits
+from lm_cases import CENTRES3, FIELDS, U, column, device_evaluate, fit_case, gauss_basis, oracle, well_posed
 from oracle import vfo_numpy as orc
 from parity_report import put_section
 from pyrayhf_amd import _native, fitting, library
 
 pytestmark = pytest.mark.gpu
 
-G26 = load_golden("g26_jacobian.npz")
-U = 2.0 ** -52
-CENTRES3 = (0.25, 0.575, 0.9)
 PARITY = os.path.join(REPO, "profiles", "lm_fit_parity.md")
 CONVERGED = (fitting.LM_CONVERGED_F, fitting.LM_CONVERGED_X)
 
-
-def column(name):
-    c = {k: G26[f"{name}_{k}"] for k in ("freq", "den", "bmag", "bpsi", "alt")}
-    c["mode"], c["n_points"] = str(G26[f"{name}_mode"]), int(G26[f"{name}_n_points"])
-    return c
-
-
-def gauss_basis(alt, den, centres, width=0.2):
-    k = int(np.argmax(den))
-    z = (alt - alt[0]) / (alt[k] - alt[0])
-    return np.exp(-0.5 * ((z[None, :] - np.asarray(centres, dtype=np.float64)[:, None]) / width) ** 2)
-
-
-def oracle(freq, den, col, mode=None, n_points=None):
-    den = np.atleast_2d(den)
-    rows = den.shape[0]
-    return orc.virtual_heights_batch(freq, den, np.broadcast_to(col["bmag"], (rows, col["bmag"].size)),
-                                     np.broadcast_to(col["bpsi"], (rows, col["bpsi"].size)), col["alt"],
-                                     mode or col["mode"], n_points or col["n_points"])
-
-
-def well_posed(name, lo, hi, seed):
-    col = column(name)
-    f = np.linspace(lo, hi, 10) * col["freq"].max()
-    B = gauss_basis(col["alt"], col["den"], CENTRES3)
-    c_true = np.random.default_rng(seed).uniform(-0.08, 0.08, 3)
-    vh_start = oracle(f, col["den"], col)[0]
-    obs = oracle(f, col["den"] * np.exp(c_true @ B), col)[0]
-    # the screen
-    assert np.isfinite(vh_start).all() and np.isfinite(obs).all(), name
-    assert np.max(np.abs(vh_start - obs)) <= 25.0, (name, float(np.max(np.abs(vh_start - obs))))
-    return dict(col, name=name, f=f, B=B, c_true=c_true, obs=obs)
-
-
 WELL = {"g": well_posed("g", 0.01, 0.6, 26), "h": well_posed("h", 0.37, 0.6, 27), "d": well_posed("d", 0.37, 0.6, 28)}
-
-
-def fit_case(w, **kw):
-    return fitting.fit_profiles_lm(w["f"], w["obs"][None, :], w["den"], w["bmag"], w["bpsi"], w["alt"], w["B"], w["mode"],
-                                   w["n_points"], **kw)
 
 
 # ---- 1. one step is the NumPy step ----
@@ -259,9 +218,6 @@ def batch():
     return args, fitting.fit_profiles_lm(**args, return_history=True, return_state=True)
 
 
-FIELDS = ("c", "cost", "status", "n_eval", "n_accept", "lam", "den", "vh", "state", "cost_history")
-
-
 def test_batch_rows_equal_the_ionogram_fitted_alone(batch):
     args, r = batch
     assert r.status[NO_DATA_AT] == fitting.LM_NO_DATA and np.isnan(r.cost[NO_DATA_AT])
@@ -330,16 +286,6 @@ def test_shared_arrays_equal_their_expansion():
 
 # ---- the state after many evaluations is the restated rule's, driven by the device's own vh and dvh ----
 
-def device_evaluate(w):
-    """evaluate(c) of tests/lm_rule.py with the device's own bits: the trial column is lm_synth_kernel's (a fit of one
-    evaluation from c returns it), its tangents are one product each, and the rows of ``library.vertical_jvp`` depend
-    on their own column and tangent only."""
-    def evaluate(c):
-        den = fit_case(w, c0=c, max_iter=1).den[0]
-        return library.vertical_jvp(w["f"], den, w["bmag"], w["bpsi"], w["alt"], den[None, :] * w["B"], w["mode"], w["n_points"])
-    return evaluate
-
-
 @pytest.mark.parametrize("prior", [None, (0.0, 40.0, 400.0)])
 @pytest.mark.parametrize("name", ["g", "h", "d"])
 def test_state_after_many_evaluations_is_the_restated_rules(name, prior):
@@ -393,7 +339,8 @@ def test_bad_arguments_are_einval_from_the_entry():
                      (dict(options=options(max_iter=0)), "max_iter"), (dict(options=options(lambda0=0.0)), "lambda0"),
                      (dict(options=options(lambda_up=1.0)), "lambda_up"), (dict(options=options(xtol=float("nan"))), "xtol"),
                      (dict(prior=np.array([0.0, -1.0, 0.0])), "prior_weight"),
-                     (dict(prior=np.array([0.0, float("nan"), 0.0])), "prior_weight"), (dict(mode=2), "mode"),
+                     (dict(prior=np.array([0.0, float("nan"), 0.0])), "prior_weight"),
+                     (dict(prior=np.array([0.0, float("inf"), 0.0])), "prior_weight"), (dict(mode=2), "mode"),
                      (dict(flags=_native.FLAG_ASYNC), "ASYNC"), (dict(flags=0x100), "flag")):
         assert call(**kw) == _native.EINVAL, kw
         assert text in _native.last_error(), (kw, _native.last_error())

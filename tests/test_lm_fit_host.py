@@ -82,6 +82,7 @@ def _inputs(n_iono=2, n_alt=12, n_freq=5, n_tan=3):
     (dict(c0=np.zeros(2)), "c0 must be"),
     (dict(max_iter=0), "max_iter"),
     (dict(mode="Z"), "mode must be"),
+    (dict(prior_weight=[1.0, float("inf"), 0.0]), "prior_weight must be finite"),
 ])
 def test_bad_arguments_raise_before_any_native_call(monkeypatch, change, match):
     def no_native_call(*args, **kwargs):
@@ -208,16 +209,10 @@ def host_program(tmp_path_factory):
     return exe
 
 
-@pytest.mark.parametrize("n_freq, n_tan, prior", [(10, 3, False), (70, 8, True), (130, 1, False), (65, 5, True)])
-def test_header_on_the_host_equals_the_restatement_bit_for_bit(tmp_path, host_program, n_freq, n_tan, prior):
-    exe = host_program
-    options = dict(lm_rule.DEFAULTS, max_iter=12)
-    rng = np.random.default_rng(n_freq)
-    cases = [_linear_case(100 + q, n_freq, n_tan, nan_obs=(q % 3) * min(3, n_freq // 4), nan_model=(q % 2) * 2) for q in range(4)]
-    cases.append((np.full(n_freq, np.nan),) + cases[0][1:])                       # NO_DATA
-    cases.append((cases[0][0], np.full(n_freq, np.nan), cases[0][2]))             # NO_COST
-    starts = [rng.uniform(-0.05, 0.05, n_tan) if q % 2 else np.zeros(n_tan) for q in range(len(cases))]
-    w = rng.uniform(0.0, 10.0, n_tan)
+def _header_against_the_restatement(exe, tmp_path, n_freq, n_tan, cases, starts, w, prior, options):
+    """Runs lm_step_host on ``cases`` (obs, vh0, D) from ``starts`` and asserts every line of its output - c, c_eval,
+    cost, lambda and the status after every evaluation, then the end's status, counts, A, g and delta - equal to
+    tests/lm_rule.py's on the same model, bit for bit.  Returns the restatement's ``(result, trace)`` per case."""
     head = [len(cases), n_tan, n_freq, options["max_iter"], options["lambda0"], options["lambda_up"], options["lambda_down"],
             options["step_max"], options["ftol"], options["xtol"], 1.0 if prior else 0.0]
     blob = [np.array(head, dtype=np.float64)]
@@ -230,7 +225,7 @@ def test_header_on_the_host_equals_the_restatement_bit_for_bit(tmp_path, host_pr
     assert "runtime error" not in run.stderr and "AddressSanitizer" not in run.stderr, run.stderr
     lines = run.stdout.splitlines()
     assert len(lines) == len(cases) * (options["max_iter"] + 1)
-    seen = set()
+    out = []
     for q, ((obs, vh0, D), c0) in enumerate(zip(cases, starts)):
         trace = []
         got = lm_rule.fit(_evaluate(vh0, D), obs, n_tan, c0=c0, prior_weight=w if prior else None, trace=trace, **options)
@@ -249,5 +244,79 @@ def test_header_on_the_host_equals_the_restatement_bit_for_bit(tmp_path, host_pr
         tail = [_word(x) for x in end[4:]]
         want = [_pattern(x) for x in got["A"].ravel()] + [_pattern(x) for x in got["g"]] + [_pattern(x) for x in got["delta"]]
         assert tail == want, q
-        seen.add(got["status"])
+        out.append((got, trace))
+    return out
+
+
+@pytest.mark.parametrize("n_freq, n_tan, prior", [(10, 3, False), (70, 8, True), (130, 1, False), (65, 5, True)])
+def test_header_on_the_host_equals_the_restatement_bit_for_bit(tmp_path, host_program, n_freq, n_tan, prior):
+    options = dict(lm_rule.DEFAULTS, max_iter=12)
+    rng = np.random.default_rng(n_freq)
+    cases = [_linear_case(100 + q, n_freq, n_tan, nan_obs=(q % 3) * min(3, n_freq // 4), nan_model=(q % 2) * 2) for q in range(4)]
+    cases.append((np.full(n_freq, np.nan),) + cases[0][1:])                       # NO_DATA
+    cases.append((cases[0][0], np.full(n_freq, np.nan), cases[0][2]))             # NO_COST
+    starts = [rng.uniform(-0.05, 0.05, n_tan) if q % 2 else np.zeros(n_tan) for q in range(len(cases))]
+    w = rng.uniform(0.0, 10.0, n_tan)
+    fits = _header_against_the_restatement(host_program, tmp_path, n_freq, n_tan, cases, starts, w, prior, options)
+    seen = {got["status"] for got, _ in fits}
     assert lm_rule.NO_DATA in seen and lm_rule.NO_COST in seen and seen & {lm_rule.CONVERGED_F, lm_rule.CONVERGED_X}
+
+
+# ---- the rule's rare ends: SINGULAR with its retries, both clamps of lambda, the step cap, the fill's floor ----
+
+RARE_F = 70
+
+
+@pytest.mark.parametrize("n_tan", [2, 5, 8])
+def test_header_on_the_host_equals_the_restatement_at_the_rare_ends(tmp_path_factory, host_program, n_tan):
+    """Four option sets on the linear model (F = 70, seed 1, noise 1e-3), each one run of the sanitized program and each
+    line of it the restatement's, bit for bit; what the rule must do there is asserted on the restatement's side.
+    1. D x 2^520 from c0 = 0: the rows and the cost are finite, D^T D overflows, the first column of the factor is
+       inf / inf: no pivot is positive at any lambda, eight retries, SINGULAR with lambda0 lambda_up^8 - 1e5 with the
+       defaults, the upper clamp 1e12 from lambda0 = 1e8.  The same run has NO_DATA, NO_COST, and heights of 50 - 80 km
+       with two modelled NaN, where the fill is its floor of 100 km and not the mean.
+    2. ftol = xtol = 0, lambda_up = 1e3, lambda_down = 1e6, 40 evaluations: accepted steps take lambda to the lower
+       clamp, then the cost stops falling at its rounding floor and the rejections take it to the upper one; nothing ends it.
+    3. step_max = 0.01: the first steps are scaled to the cap, and the fit still converges."""
+    obs, vh0, D = _linear_case(1, RARE_F, n_tan, noise=1e-3)
+    zeros, w = np.zeros(n_tan), np.zeros(n_tan)
+    huge = (obs, vh0, D * 2.0 ** 520)
+    with np.errstate(over="ignore", invalid="ignore"):
+        assert np.isfinite(huge[2]).all() and np.isinf(np.diag(huge[2].T @ huge[2])).all()
+    low_obs, low_vh0, low_D = _linear_case(2, RARE_F, n_tan, nan_model=2)
+    low = (low_obs - 200.0, low_vh0 - 200.0, low_D)
+    assert np.nanmax(low[1]) < 100.0 and np.isnan(low[1]).sum() == 2 and np.isfinite(low[0]).all()
+    seen = set()
+
+    def run(name, cases, **options):
+        options = dict(lm_rule.DEFAULTS, **options)
+        fits = _header_against_the_restatement(host_program, tmp_path_factory.mktemp(name), RARE_F, n_tan, cases,
+                                               [zeros] * len(cases), w, False, options)
+        seen.update(got["status"] for got, _ in fits)
+        return fits
+
+    # 1. SINGULAR
+    cases = [huge, (np.full(RARE_F, np.nan), vh0, D), (obs, np.full(RARE_F, np.nan), D), low, (obs, vh0, D)]
+    for lambda0, lam_end in ((lm_rule.DEFAULTS["lambda0"], 1e5), (1e8, 1e12)):
+        with np.errstate(over="ignore", invalid="ignore"):             # (the overflow is the case)
+            fits = run("singular", cases, max_iter=12, lambda0=lambda0)
+        got = fits[0][0]
+        assert (got["status"], got["n_eval"], got["n_accept"]) == (lm_rule.SINGULAR, 1, 1)
+        want = lambda0
+        for _ in range(lm_rule.RETRIES):
+            want = lm_rule.clamp(want * 10.0)
+        assert got["lam"] == want and abs(want - lam_end) <= 4 * np.spacing(lam_end)
+        assert np.array_equal(got["delta"], zeros) and np.isfinite(got["cost"]) and np.isinf(got["A"]).any()
+        assert [f[0]["status"] for f in fits[1:3]] == [lm_rule.NO_DATA, lm_rule.NO_COST]
+    # 2. the rounding floor
+    (got, trace), = run("floor", [(obs, vh0, D)], ftol=0.0, xtol=0.0, lambda_up=1e3, lambda_down=1e6, max_iter=40)
+    lams = {t[3] for t in trace}
+    assert lm_rule.LAMBDA_MIN in lams and lm_rule.LAMBDA_MAX in lams, sorted(lams)
+    assert got["status"] == lm_rule.RUNNING and got["n_eval"] == 40 and np.all(np.diff(got["history"]) <= 0.0)
+    # 3. the step cap
+    (got, trace), = run("cap", [(obs, vh0, D)], step_max=0.01)
+    assert lm_rule.capped_run(trace, 0.01) >= 3, [float(np.max(np.abs(t[1] - t[0]))) for t in trace]
+    assert got["status"] in (lm_rule.CONVERGED_F, lm_rule.CONVERGED_X) and got["n_eval"] <= lm_rule.DEFAULTS["max_iter"]
+    # 4. every end of the rule has been through the header
+    assert seen >= {lm_rule.RUNNING, lm_rule.SINGULAR, lm_rule.NO_DATA, lm_rule.NO_COST}
+    assert seen & {lm_rule.CONVERGED_F, lm_rule.CONVERGED_X}

@@ -29,6 +29,8 @@ Fixtures:
   G16 the reference's regrid_to_nonuniform_grid, find_mu_mup and find_vh on edge inputs: K == 1, reflection at
       level 0, f = 0 / NaN, X mode below f_H, plateau and E - F valley, ragged and tall columns, NaN above the peak,
       NaN padding; X, Y at and next to 1, Y = inf / NaN, isotropic arrays; find_vh rows that give NaN
+  G29 the spherical Snell tracer under twelve sets of its controls (R_E, dz_target_km, apex_boost, max_substeps) on the
+      columns of G8, and both Snell tracers on rays whose bracket lies at the edge of a chunk of 64 levels
   G12 (made with the ORACLE, not the reference: it needs a hook inside find_mu_mup) "rounding noise" of
       every O-mode fixture above: the response of the restated algorithm - bit-identical to the
       reference on G1-G11 - to -1/0/+1 ulp in the results of sin, cos, YT**4, YT**3
@@ -260,6 +262,7 @@ def main():
     except Exception as exc:                   # noqa: BLE001
         print("negative density ->", type(exc).__name__, exc)
     gen_snell(lib)
+    gen_snell_controls(lib)
     gen_config3(lib)
     gen_residual(lib)
     gen_rounding_noise(lib)
@@ -335,6 +338,156 @@ def gen_snell(lib):
         g9[f"{name}_offsets"] = np.array(offs)
         print("G9", name, "rays", len(rays), "traced", int(np.isfinite(np.array(scal)[:, 0]).sum()), flush=True)
     np.savez(os.path.join(OUT, "g9_snell_spherical.npz"), **g9)
+
+
+# G29's control sets: name -> the keyword arguments handed to trace_ray_spherical_snells (everything else at its default),
+# and the sub-step path of the kernels (prhf_snell.inc) each is there to hit
+SNELL_CONTROL_SETS = (
+    ("fine", dict(dz_target_km=0.25)),                                    # many intervals with 1 < N < cap
+    ("coarse", dict(dz_target_km=5.0, apex_boost=0.0)),                   # N == 1 everywhere
+    ("flat_count", dict(dz_target_km=0.05, apex_boost=0.0)),              # N >= 16 far from the apex
+    ("cap1", dict(max_substeps=1)),                                       # the clamp to 1
+    ("cap15", dict(max_substeps=15)),                                     # the clamp just below the shared-out count
+    ("cap16", dict(max_substeps=16)),                                     # ... at it
+    ("cap17", dict(max_substeps=17)),                                     # ... just above it
+    ("cap65", dict(max_substeps=65)),                                     # one more sub-step than lanes
+    ("beyond", dict(max_substeps=8193, apex_boost=2e4)),                  # the division path of substep_node
+    ("mars", dict(R_E=3389.5)),                                           # a radius other than Earth's
+    ("small", dict(R_E=600.0)),
+    ("mixed", dict(R_E=3389.5, dz_target_km=0.25, apex_boost=50.0, max_substeps=64)),   # no control at its default
+)
+SNELL_CONTROL_ORDER = ("R_E", "dz_target_km", "apex_boost", "max_substeps")
+SNELL_CONTROL_DEFAULTS = dict(R_E=6371.0, dz_target_km=1.0, apex_boost=200.0, max_substeps=400)
+SNELL_CONTROL_ELEVATIONS = (5.0, 45.0, 70.0, 89.9)
+
+
+def snell_edge_column(z0, n, repeat=False):
+    """G29 part B: the Gaussian layer of G8 cut at its peak, on n levels from z0 to 250 km (alt[31] = alt[30] with
+    `repeat`: the reference's `if dz <= 0: continue`)."""
+    alt = np.linspace(float(z0), 250.0, int(n))
+    if repeat:
+        alt[31] = alt[30]
+    return {"alt": alt, "den": 1e12 * np.exp(-(alt - 250) ** 2 / (2 * 60 ** 2)), "bmag": np.full_like(alt, 4e-5),
+            "bpsi": np.full_like(alt, 45.0)}
+
+
+def snell_bracket_sweep(prof, f_hz, mode, spherical, elevations):
+    """The bracket index of every elevation of a sweep, -1 where the ray does not turn: the first pair of valid levels
+    with crit[i] >= p >= crit[i + 1] (library.py:1085-1093 / :1598-1603) on the column with its ground level, from the
+    oracle's level indices.  Only used to pick elevations: what is stored comes from the reference's tracers."""
+    from oracle import snell_numpy as sn
+    alt, ne, babs, bpsi = sn.with_ground(prof["alt"], prof["den"], prof["bmag"], prof["bpsi"])
+    mu, _ = sn.level_indices(f_hz, ne, babs, bpsi, mode)
+    ok = np.isfinite(mu)
+    crit = mu[ok] * (6371.0 + alt[ok]) if spherical else mu[ok]
+    p = crit[0] * np.sin(np.radians(90.0 - elevations))
+    hit = (crit[None, :-1] >= p[:, None]) & (crit[None, 1:] <= p[:, None])
+    return np.where(hit.any(axis=1), hit.argmax(axis=1), -1)
+
+
+class _RayStore:
+    """Rays of G29 as G9 stores them: scalars per ray, the x path concatenated with offsets, and the apex node."""
+
+    def __init__(self):
+        self.cols = {k: [] for k in ("rays", "scalars", "n_path", "x_turn", "z_turn")}
+        self.xs, self.offs = [], [0]
+
+    def add(self, r, mode_i, f_hz, elev):
+        self.cols["rays"].append((mode_i, f_hz, elev))
+        self.cols["scalars"].append([r.get(k, np.nan) for k in ("group_path_km", "group_delay_sec", "x_midpoint",
+                                                                "z_midpoint", "ground_range_km")])
+        x = np.atleast_1d(np.asarray(r["x"], dtype=float))
+        z = np.atleast_1d(np.asarray(r["z"], dtype=float))
+        if x.size == 1 and np.isnan(x[0]):
+            x = z = np.empty(0)
+        self.cols["n_path"].append(x.size)
+        self.cols["x_turn"].append(x[x.size // 2] if x.size else np.nan)
+        self.cols["z_turn"].append(z[z.size // 2] if z.size else np.nan)
+        self.xs.append(x)
+        self.offs.append(self.offs[-1] + x.size)
+        return x.size
+
+    def into(self, g, prefix):
+        g[f"{prefix}_rays"] = np.array(self.cols["rays"], dtype=float)
+        g[f"{prefix}_scalars"] = np.array(self.cols["scalars"], dtype=float)
+        g[f"{prefix}_n_path"] = np.array(self.cols["n_path"], dtype=np.int64)
+        g[f"{prefix}_x_turn"] = np.array(self.cols["x_turn"], dtype=float)
+        g[f"{prefix}_z_turn"] = np.array(self.cols["z_turn"], dtype=float)
+        g[f"{prefix}_x"] = np.concatenate(self.xs)
+        g[f"{prefix}_offsets"] = np.array(self.offs, dtype=np.int64)
+
+
+def gen_snell_controls(lib):
+    """G29.  Part A (keys a_*): the spherical tracer (library.py:1460-1713) under the control sets of
+    SNELL_CONTROL_SETS on the gauss and day columns of G8 (referenced, not stored again): {O, X} x {5, 10, 12.5} MHz x
+    SNELL_CONTROL_ELEVATIONS and the 90-degree ray at 5 MHz O per column.  a_controls holds NaN where a control was
+    left at the reference's default.  a_substep_classes: per set the number of up-leg intervals with N == 1,
+    2 <= N < 16, N >= 16, N > 8192 and N == max_substeps sub-steps, counted by the oracle (bit for bit the reference on
+    these rays) - nothing here comes from a GPU.
+    Part B (keys b_*): rays whose bracket is the last interval of a 64-level chunk of the kernels, the one spanning two
+    chunks or the first of the next, on snell_edge_column(z0, n): 10 MHz, O and X, flat and spherical (defaults), the
+    first elevation of a 1 to 90 degree sweep in steps of 0.025 for every bracket index in {60..66} and {125..129}
+    the column has, its lowest and its last; and the n = 65 column with a repeated altitude at 20, 45 and 59 degrees."""
+    from oracle import snell_numpy as sn
+    g8 = dict(np.load(os.path.join(OUT, "g8_snell.npz")))
+    g = {"a_set_names": np.array([name for name, _ in SNELL_CONTROL_SETS]),
+         "a_control_order": np.array(SNELL_CONTROL_ORDER),
+         "a_controls": np.array([[kw.get(k, np.nan) for k in SNELL_CONTROL_ORDER] for _, kw in SNELL_CONTROL_SETS]),
+         "a_column_names": np.array(["gauss", "day"])}
+    store, sets, columns, classes = _RayStore(), [], [], []
+    for set_i, (set_name, kw) in enumerate(SNELL_CONTROL_SETS):
+        cap = kw.get("max_substeps", SNELL_CONTROL_DEFAULTS["max_substeps"])
+        counts, turned = [], 0
+        for col_i, name in enumerate(("gauss", "day")):
+            prof = [g8[f"{name}_{k}"] for k in ("alt", "den", "bmag", "bpsi")]
+            rays = [(mode_i, f_mhz * 1e6, elev) for mode_i in (0, 1) for f_mhz in (5.0, 10.0, 12.5)
+                    for elev in SNELL_CONTROL_ELEVATIONS] + [(0, 5e6, 90.0)]
+            for mode_i, f_hz, elev in rays:
+                r = lib.trace_ray_spherical_snells(f_hz, elev, *prof, "OX"[mode_i], **kw)
+                turned += store.add(r, mode_i, f_hz, elev) > 0
+                sets.append(set_i)
+                columns.append(col_i)
+                sn.trace_spherical(f_hz, elev, *prof, "OX"[mode_i], substep_counts=counts, **kw)
+        n = np.array(counts)
+        classes.append([(n == 1).sum(), ((n >= 2) & (n < 16)).sum(), (n >= 16).sum(), (n > 8192).sum(), (n == cap).sum()])
+        print("G29", set_name, "rays", len(rays) * 2, "turn", turned, "intervals N==1 / 2..15 / >=16 / >8192 / ==cap",
+              classes[-1], flush=True)
+    store.into(g, "a")
+    g["a_set"], g["a_column"] = np.array(sets, dtype=np.int64), np.array(columns, dtype=np.int64)
+    g["a_substep_classes"] = np.array(classes, dtype=np.int64)
+
+    # ---- part B ----
+    sweep = 1.0 + 0.025 * np.arange(3561)
+    col_table = [(z0, n, 0) for z0 in (0.0, 60.0) for n in (63, 64, 65, 66, 129, 130)] + [(0.0, 65, 1)]
+    g["b_columns"] = np.array(col_table, dtype=float)                    # z0, n, repeated altitude
+    store, geoms, cols, wanted = _RayStore(), [], [], []
+    for geometry in (0, 1):
+        tracer = lib.trace_ray_spherical_snells if geometry else lib.trace_ray_cartesian_snells
+        for col_i, (z0, n, repeat) in enumerate(col_table):
+            prof = snell_edge_column(z0, n, bool(repeat))
+            for mode_i, mode in enumerate("OX"):
+                if repeat:
+                    picks = [(-1, e) for e in (20.0, 45.0, 59.0)]
+                else:
+                    i0 = snell_bracket_sweep(prof, 10e6, mode, bool(geometry), sweep)
+                    has = sorted(set(i0[i0 >= 0].tolist()))
+                    want = sorted({has[0], has[-1]} | (set(range(60, 67)) | set(range(125, 130))) & set(has))
+                    picks = [(w, float(sweep[np.argmax(i0 == w)])) for w in want]
+                for w, elev in picks:
+                    r = tracer(10e6, elev, prof["alt"], prof["den"], prof["bmag"], prof["bpsi"], mode)
+                    n_path = store.add(r, mode_i, 10e6, elev)
+                    assert n_path > 0 and (w < 0 or 2 * w + 3 == n_path), (geometry, z0, n, mode, w, elev, n_path)
+                    geoms.append(geometry)
+                    cols.append(col_i)
+                    wanted.append((n_path - 3) // 2)
+                print("G29 edges", "spherical" if geometry else "flat", "z0", z0, "n", n, mode, "i0",
+                      [(n_p - 3) // 2 for n_p in store.cols["n_path"][-len(picks):]], flush=True)
+    store.into(g, "b")
+    g["b_geometry"], g["b_column"] = np.array(geoms, dtype=np.int64), np.array(cols, dtype=np.int64)
+    g["b_i0"] = np.array(wanted, dtype=np.int64)
+    path = os.path.join(OUT, "g29_snell_controls.npz")
+    np.savez(path, **g)
+    print("G29", os.path.getsize(path), "bytes", flush=True)
 
 
 def gen_config3(lib):
@@ -756,6 +909,6 @@ if __name__ == "__main__":
         ref = load_reference_library()
         for what in only:
             {"g8": gen_snell, "g10": gen_config3, "g11": gen_residual, "g12": gen_rounding_noise, "g13": gen_tall,
-             "g14": gen_config4, "g15": gen_config5, "g15r": add_rounding_noise_g15, "g16": gen_stage_edges}[what](ref)
+             "g14": gen_config4, "g15": gen_config5, "g15r": add_rounding_noise_g15, "g16": gen_stage_edges, "g29": gen_snell_controls}[what](ref)
     else:
         main()

@@ -109,10 +109,12 @@ def trace_cartesian(f0_hz, elevation_deg, alt_km, ne, babs, bpsi, mode):
 
 
 def trace_spherical(f0_hz, elevation_deg, alt_km, ne, babs, bpsi, mode="O", *, dz_target_km=1.0, apex_boost=200.0,
-                    max_substeps=400, R_E=None):
+                    max_substeps=400, R_E=None, substep_counts=None):
     """Spherical-Earth stratified Snell's law (Bouguer: mu r sin(theta) = const) with adaptive
     midpoint sub-steps towards the apex.  Reference library.py:1460-1713.  Returns the reference's dict
-    (a ray that never turns returns its seven-key NaN dict, library.py:1577-1583)."""
+    (a ray that never turns returns its seven-key NaN dict, library.py:1577-1583).  `substep_counts`: a list that
+    receives the number of sub-steps of every up-leg interval that has any (fixture G29 records which of the kernels'
+    sub-step paths its rays take); it changes no output."""
     if R_E is None:
         R_E = vfo.EARTH_RADIUS_KM
     alt, ne, babs, bpsi = with_ground(np.asarray(alt_km, float), np.asarray(ne, float), np.asarray(babs, float),
@@ -145,6 +147,8 @@ def trace_spherical(f0_hz, elevation_deg, alt_km, ne, babs, bpsi, mode="O", *, d
         n_sub = max(1, int(np.ceil(abs(dz) / dz_target_km)))
         gap = min(max(mu_a * r_up[k] - p, 1e-12), max(mu_b * r_up[k + 1] - p, 1e-12))
         n_sub = int(min(max_substeps, n_sub * (1.0 + apex_boost * (1.0 / gap))))
+        if substep_counts is not None:
+            substep_counts.append(n_sub)
         total = 0.0
         for j in range(n_sub):
             half = 0.5 * (j / n_sub + (j + 1) / n_sub)

@@ -87,6 +87,23 @@ __device__ __forceinline__ double lane_value(double v, int l) {
     return __hiloint2double(hi, lo);
 }
 
+// The spherical up-leg behind an interval without height.  The reference's loop leaves such an interval with
+// `if dz <= 0: continue` (:1641-1642) and so never reaches phi_up[k + 1] = phi_up[k] + dphi_sum (:1669): that node keeps
+// the 0 it was made with and the running angle starts again from there (a column with a repeated altitude; fixture
+// G29).  `incl`: the chunk's running sum of `du` with the carry in it; `restart`: this lane's interval is such a one
+// (its du is 0).  Every lane from the last such lane below it on gets the sum of what lies behind that lane alone.  One
+// ballot where there is none - every column but a degenerate one.  Every lane calls this.
+__device__ __forceinline__ double restart_behind_empty_intervals(double incl, double du, bool restart, int lane) {
+    unsigned long long m = __ballot(restart);
+    while (m) {
+        const int r = __ffsll((long long)m) - 1;
+        m &= m - 1;
+        const double behind = wave_inclusive_scan(lane > r ? du : 0.0, lane);
+        if (lane >= r) incl = behind;
+    }
+    return incl;
+}
+
 // np.interp(x, xp, fp) for one abscissa on a grid that may carry NaN ordinates (numpy arr_interp).
 __device__ __forceinline__ double interp_nan_aware(double x, int j, int n, double xj, double xj1, double fj,
                                                    double fj1) {
@@ -302,6 +319,7 @@ __device__ __forceinline__ void snell_ray_table(const SnellArgs& a, long long ra
         const double z0 = wave_shift_up_1(z1, z_carry), mu0 = wave_shift_up_1(mu1, mu_carry);
         const double mup0 = wave_shift_up_1(mup1, mup_carry);
         double du = 0.0;
+        bool empty = false;                                         // spherical: an interval with dz <= 0 (:1641)
         if (GEOM == 0 && s < n_up - 1) {
             const double dz = z1 - z0;
             double mm = 0.5 * (mu0 + mu1);
@@ -319,6 +337,7 @@ __device__ __forceinline__ void snell_ray_table(const SnellArgs& a, long long ra
             int N = 0;
             if (s < n_up - 1) {
                 dz = z1 - z0;
+                empty = dz <= 0.0;
                 if (dz > 0.0) {
                     const double gap_a = fmax(mu0 * (RE + z0) - p, 1e-12);
                     const double gap_b = fmax(mu1 * (RE + (z0 + dz)) - p, 1e-12);
@@ -357,7 +376,8 @@ __device__ __forceinline__ void snell_ray_table(const SnellArgs& a, long long ra
             }
             if (N > 0 && N < kShared) du = substeps(z0, dz, mu0, mu1, N, 0, 1);
         }
-        const double incl = wave_inclusive_scan(du, lane) + carry;
+        double incl = wave_inclusive_scan(du, lane) + carry;
+        if (GEOM == 1) incl = restart_behind_empty_intervals(incl, du, empty, lane);
         const double u_lo = wave_shift_up_1(incl, carry);           // the node below is the lane below's (lane 0: the carry)
         if (s < n_up - 1) {
             u_up[s + 1] = incl;
@@ -779,7 +799,8 @@ __device__ __forceinline__ void snell_ray(const SnellArgs& a, long long ray, dou
         } else {
             du = du_sphere(up, z0, dz, mu_a, mu_b, p);
         }
-        const double incl = wave_inclusive_scan(up ? du : 0.0, lane) + u_carry;
+        double incl = wave_inclusive_scan(up ? du : 0.0, lane) + u_carry;
+        if (GEOM == 1) incl = restart_behind_empty_intervals(incl, up ? du : 0.0, up && dz <= 0.0, lane);
         const double u_lo = wave_shift_up_1(incl, u_carry);          // the lane below's sum; lane 0: the carry
         if (up) {
             u_up[nv + lane] = incl;                                  // compacted level nv + lane, the interval's upper node
@@ -851,6 +872,7 @@ __device__ __forceinline__ void snell_ray(const SnellArgs& a, long long ray, dou
         if (GEOM == 0) du = du_flat(dz, lo_mu, mu_apex, p, true);
         else du = lane_value(du_sphere(lane == 0, lo_z, dz, lo_mu, mu_apex, p), 0);
         u_turn = u_l + du;
+        if (GEOM == 1 && dz <= 0.0) u_turn = 0.0;                   // (restart_behind_empty_intervals: the apex interval's turn)
         const double ds = seg_len_of(u_l, lo_z, u_turn, z_turn);
         const double tt = ((0.5 * (lo_mup + mup_apex)) / kLightKmS) * ds;
         if (lane == 0 && ds == ds) len_acc += ds;

@@ -199,6 +199,125 @@ def test_snell_spherical_tracer_g9():
                                                         "z_midpoint", "ground_range_km"}      # library.py:1577-1583
 
 
+def _oracle_against_g29(part, i, r):
+    """One oracle dict against row `i` of G29's part `part`, bit for bit: the scalars, the x path and the apex node, or
+    the NaN dict of a ray that does not turn"""
+    import snell_g29
+    g = snell_g29.fixture()
+    got = [r.get(k, np.nan) for k in snell_g29.SCALARS]
+    assert same_bits(got, g[f"{part}_scalars"][i]), (part, i, got, g[f"{part}_scalars"][i])
+    n = int(g[f"{part}_n_path"][i])
+    x = np.atleast_1d(np.asarray(r["x"], dtype=float))
+    if n == 0:
+        assert x.size == 1 and np.isnan(x[0]) and np.all(np.isnan(np.asarray(r["z"], dtype=float)))
+        assert all(np.isnan(v) for v in got)
+        assert np.isnan(g[f"{part}_x_turn"][i]) and np.isnan(g[f"{part}_z_turn"][i])
+        return 0
+    assert x.size == n and same_bits(x, snell_g29.x_path(part, i))
+    assert same_bits(x[n // 2], g[f"{part}_x_turn"][i]) and same_bits(r["z"][n // 2], g[f"{part}_z_turn"][i])
+    assert r["z"].size == n and r["z"][n // 2] == np.max(r["z"])
+    return 1
+
+
+def test_snell_spherical_controls_g29():
+    """oracle/snell_numpy.py trace_spherical under the twelve control sets of G29 part A against the reference's
+    trace_ray_spherical_snells run with the same keyword arguments: every stored value bit for bit, the NaN dicts of
+    the rays that do not turn included; the sub-step classes recounted through `substep_counts`, which changes no
+    output (the dicts with and without it are compared)."""
+    from oracle import snell_numpy as sn
+    import snell_g29
+    g = snell_g29.fixture()
+    names = snell_g29.set_names()
+    assert len(names) == 12 and g["a_rays"].shape == (600, 3)
+    for s in range(len(names)):
+        kw = snell_g29.controls(s)
+        counts = []
+        for i in np.nonzero(g["a_set"] == s)[0]:
+            mode_i, f_hz, elev = g["a_rays"][i]
+            prof = snell_g29.control_column(int(g["a_column"][i]))
+            r = sn.trace_spherical(f_hz, elev, *prof, "OX"[int(mode_i)], substep_counts=counts, **kw)
+            turned = _oracle_against_g29("a", i, r)
+            if names[s] in ("fine", "mixed") or not turned:
+                plain = sn.trace_spherical(f_hz, elev, *prof, "OX"[int(mode_i)], **kw)
+                assert set(plain) == set(r) and all(same_bits(plain[k], r[k]) for k in r)
+            if not turned:
+                assert set(r) == {"x", "z", "group_path_km", "group_delay_sec", "x_midpoint", "z_midpoint",
+                                  "ground_range_km"}                                     # library.py:1577-1583
+        n = np.array(counts)
+        cap = kw.get("max_substeps", 400)
+        assert np.array_equal(g["a_substep_classes"][s], [(n == 1).sum(), ((n >= 2) & (n < 16)).sum(), (n >= 16).sum(),
+                                                          (n > 8192).sum(), (n == cap).sum()]), names[s]
+
+
+def test_snell_chunk_edges_g29():
+    """Both oracle tracers against the reference's on G29 part B - rays whose bracket is the last interval of a chunk of
+    64 levels, the one across two chunks, the first of the next, a column's lowest and last, and a column with a repeated
+    altitude - bit for bit."""
+    from oracle import snell_numpy as sn
+    import snell_g29
+    g = snell_g29.fixture()
+    for i, (mode_i, f_hz, elev) in enumerate(g["b_rays"]):
+        fn = sn.trace_spherical if g["b_geometry"][i] else sn.trace_cartesian
+        assert _oracle_against_g29("b", i, fn(f_hz, elev, *snell_g29.edge_column(int(g["b_column"][i])), "OX"[int(mode_i)]))
+
+
+def test_g29_reaches_what_it_is_there_for():
+    """The conditions that keep G29 honest, on the fixture alone.  Part A: 50 rays per set of which at least 25 turn;
+    the sub-step classes each set is there to hit (prhf_snell.inc: N == 1, one lane below 16, the wavefront from 16 on,
+    the division beyond 8192).  `coarse` has one sub-step everywhere but in the ground interval inserted below the day
+    column - 80 km at dz_target_km = 5: 16 sub-steps, once per day-column ray that turns - and nothing in between.
+    Part B: every stored bracket index is (n_path - 3) / 2; every column of 64 levels or more has, in both geometries,
+    both modes and with and without the inserted ground level, each of the indices 61 ... 65 that it has at all
+    (its last interval is levels - 2, the ground level counted), and the columns of 129 and 130 levels have 125 and 126."""
+    import snell_g29
+    g = snell_g29.fixture()
+    names = snell_g29.set_names()
+    assert names == ["fine", "coarse", "flat_count", "cap1", "cap15", "cap16", "cap17", "cap65", "beyond", "mars", "small",
+                     "mixed"]
+    cls = {name: dict(zip(("one", "few", "shared", "beyond", "at_cap"), g["a_substep_classes"][s]))
+           for s, name in enumerate(names)}
+    for s, name in enumerate(names):
+        sel = g["a_set"] == s
+        assert sel.sum() == 50 and (g["a_n_path"][sel] > 0).sum() >= 25, name
+        assert np.array_equal(g["a_rays"][sel], g["a_rays"][g["a_set"] == 0])            # the same rays in every set
+    mixed = snell_g29.controls(names.index("mixed"))
+    assert len(mixed) == 4 and len(set(mixed.values())) == 4
+    assert all(mixed[k] != d for k, d in (("R_E", 6371.0), ("dz_target_km", 1.0), ("apex_boost", 200.0), ("max_substeps", 400)))
+    day_turning = int(((g["a_set"] == names.index("coarse")) & (g["a_column"] == 1) & (g["a_n_path"] > 0)).sum())
+    assert cls["coarse"]["few"] == 0 and cls["coarse"]["shared"] == day_turning and cls["coarse"]["at_cap"] == 0
+    assert cls["coarse"]["one"] > 1000
+    assert cls["fine"]["few"] >= 100
+    assert cls["flat_count"]["shared"] - cls["flat_count"]["at_cap"] >= 100                # N >= 16 below the cap of 400
+    assert cls["cap1"]["one"] == cls["cap1"]["at_cap"] > 0 and cls["cap1"]["few"] == cls["cap1"]["shared"] == 0
+    for name in ("cap15", "cap16", "cap17", "cap65"):
+        assert cls[name]["at_cap"] > 0, name
+    assert cls["cap15"]["shared"] == 0 and cls["cap16"]["shared"] == cls["cap16"]["at_cap"] > 0
+    assert cls["cap17"]["shared"] > cls["cap17"]["at_cap"]                                 # 16 itself occurs below the cap
+    assert cls["beyond"]["beyond"] >= 1
+    assert all(cls[name]["beyond"] == 0 for name in names if name != "beyond")
+
+    assert np.array_equal(g["b_i0"] * 2 + 3, g["b_n_path"])
+    assert np.all(g["b_rays"][:, 1] == 10e6)
+    for geometry in (0, 1):
+        for col_i, (z0, n, repeat) in enumerate(g["b_columns"]):
+            for mode_i in (0, 1):
+                sel = (g["b_geometry"] == geometry) & (g["b_column"] == col_i) & (g["b_rays"][:, 0] == mode_i)
+                have = set(g["b_i0"][sel].tolist())
+                if repeat:
+                    assert sorted(g["b_rays"][sel, 2]) == [20.0, 45.0, 59.0] and min(have) > 31   # the pair is below the apex
+                    continue
+                last = int(n) + int(z0 > 0) - 2
+                assert max(have) <= last
+                if n >= 64:
+                    assert {i for i in range(61, 66) if i <= last} <= have, (geometry, z0, n, mode_i, sorted(have))
+                    assert max(have) >= last - 1
+                if n >= 129:
+                    assert {125, 126} <= have
+    # the brackets around both chunk boundaries, taken over the columns: 62 | 63 | 64 and 126 | 127 | 128
+    for geometry in (0, 1):
+        assert {62, 63, 64, 126, 127, 128} <= set(g["b_i0"][g["b_geometry"] == geometry].tolist())
+
+
 def test_tall_and_nan_padded_profiles_g13():
     """Profiles of 3 096 / 2 600 levels and densities padded with NaN (np.argmax returns the first NaN,
     library.py:371), as the reference evaluates them."""
